@@ -10,6 +10,8 @@ At N = 1 the steps go through the library's scan pipeline (lrc_pipe_*: consecuti
 fills the wave slots the launch of step k leaves empty in its tail, the rows of step k are scattered by the leading
 workgroups of the launch of step k+2; same bytes as the two calls one after the other, checked in the run);
 --serial times the two calls on one stream instead (the round-3 step; what the rocprofv3 / PMC passes profile).
+--steps K: exactly K timed steps (one block; --min-seconds S repeats the block for S seconds and reports the median);
+ms_per_step = block time / K.  --dump-outputs DIR: what the last timed step computed, as .npy files (dump_outputs).
 Weak scaling: every rank scans its own 64 poses of a 64*N-pose trajectory over a replica of the scene.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the trace kernel against the roof that binds it -- vector-ALU issue
@@ -44,10 +46,9 @@ HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 # VALU instruction issues over 2 cycles on a SIMD-32).  One lane-operation = one lane of one VALU instruction.
 VALU_PEAK_GLANEOPS = 256 * 4 * 32 * 2.4          # = 78 643.2 G lane-op/s
 N_SIMDS, CLOCK_GHZ = 1024, 2.4
-MIN_TIMED_SECONDS = 3.0      # the timed block of --steps steps is repeated until this much wall time has passed (the driver's
-                             # GPU-busy sampler must be able to see the device busy: round 3's 0.25 s fell between its samples)
 SCENE = "synth_A6_office2"
 POSES_PER_GPU = 64
+DUMP_SAMPLE_ROWS = 1 << 20   # --dump-outputs: rows of the scene cloud written at most (a seeded sample beyond that)
 
 
 def bytes_per_ray(T, in_kernel_raygen=True):
@@ -210,6 +211,28 @@ def open3d_leg(mesh, sensor, poses, budget_s):
     }
 
 
+def dump_outputs(out_dir, rows, counts, sample=DUMP_SAMPLE_ROWS, seed=0):
+    """--dump-outputs: what the timed path handed its caller in its last step (the scene cloud's rows and the per-pose
+    counts), as .npy files of at most ~30 MB in all, so that two builds can be compared output for output:
+      counts.npy       (P,)    float64  kept rows per pose
+      row_index.npy    (M,)    float64  the rows of the cloud that follow: all of them, or M = DUMP_SAMPLE_ROWS drawn with
+                                        a fixed seed (sorted) when the cloud holds more
+      points.npy       (M, 3)  float32  x, y, z of those rows
+      sem.npy, ins.npy (M,)    float32  the semantic / instance label, unpacked from the row's fourth word (sem | ins << 16)"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    counts_h = counts.cpu().numpy()
+    k = int(counts_h.sum())
+    idx = np.arange(k) if k <= sample else np.sort(np.random.default_rng(seed).choice(k, sample, replace=False))
+    picked = rows[torch.from_numpy(idx).to(rows.device)].cpu().numpy()
+    label = np.ascontiguousarray(picked[:, 3]).view(np.uint32)
+    np.save(os.path.join(out_dir, "counts.npy"), counts_h.astype(np.float64))
+    np.save(os.path.join(out_dir, "row_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "points.npy"), np.ascontiguousarray(picked[:, :3]))
+    np.save(os.path.join(out_dir, "sem.npy"), (label & 0xFFFF).astype(np.float32))
+    np.save(os.path.join(out_dir, "ins.npy"), (label >> 16).astype(np.float32))
+
+
 def caller_path(scene, sensor, poses, dirs, mesh, reps=7):
     """What a HOST caller of the plugin surface gets on the same workload (never the bench `value`):
     caller_path_rays_per_s   RaycastEngineGPU.scan_frames = lrc_scan_poses_compact: poses + direction table in host
@@ -283,8 +306,12 @@ def main():
     ap.add_argument("--serial", action="store_true",
                     help="N = 1: time lrc_scan_poses_dev + lrc_compact_dev on one stream (the round-3 step) instead of the "
                          "scan pipeline; what the rocprofv3 --stats / PMC passes profile (one un-overlapped trace launch per step)")
-    ap.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS,
-                    help="repeat the timed block of --steps steps until this much wall time has passed")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the timed block of --steps steps until this much wall time has passed and report the "
+                         "median block (default 0: exactly one block, i.e. exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy "
+                         "(see dump_outputs); bench_outputs/ in the repository root is git-ignored for this")
     ap.add_argument("--dist-selftest", action="store_true",
                     help="run the N>1 code path (RCCL all-gather, double buffering) with world size 1 and check "
                          "the assembled cloud against the local one")
@@ -606,6 +633,7 @@ def main():
         if dist_path:
             dist_step(timed)
             return
+        timed = timed and len(k_events) < 256
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -629,6 +657,7 @@ def main():
 
     def serial_step(timed):
         """the step as two calls on one stream: trace launch (timed alone by HIP events) + compaction"""
+        timed = timed and len(k_events) < 256          # HIP events around the first few hundred trace launches are plenty
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -638,40 +667,17 @@ def main():
             k_events.append((e0, e1))
         ctx.compact_dev(P, N, io, stream)
 
-    serial_ms = None
-    if use_pipe:
-        # (1) the un-pipelined step on this box: gives the trace launch's own duration (HIP events on its stream; what the
-        # roofline is priced with and what rocprofv3 reports for `bench.py --serial`) and the figure the pipeline is held against
-        serial_rows, serial_counts = torch.empty_like(cloud), torch.zeros_like(counts)
-        io.out_xyzl, io.counts = serial_rows.data_ptr(), serial_counts.data_ptr()
-        for _ in range(5):
-            serial_step(False)
-        torch.cuda.synchronize()
-        sb = []
-        for _ in range(12):
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                serial_step(True)
-            torch.cuda.synchronize()
-            sb.append((time.perf_counter() - t0) / args.steps)
-        serial_ms = float(np.median(sb)) * 1e3
-
-    for _ in range(args.warmup):
-        step(False)
-    barrier()
-    # EXACTLY --steps steps form one timed block, bracketed by barrier + synchronize on both sides.  A block of the
-    # default 20 steps lasts ~7 ms, too short for a stable figure (clock ramp) and for the driver's GPU-busy sampler, so
-    # the block is repeated until --min-seconds have passed -- half of them before the host legs (CPU baseline, caller
-    # path), half after -- and the MEDIAN block is reported; value = rays of one block / its time.
-    blocks = []
-
-    def timed_blocks(seconds):
+    def timed_blocks(step_fn, sync):
+        """EXACTLY --steps steps of `step_fn` form one timed block, bracketed by `sync` (drain + synchronize) on both sides;
+        the block is repeated only while --min-seconds of wall time have not passed (default 0: one block).  Returns the
+        block times in seconds; the median block is reported."""
+        out = []
         t_begin = time.perf_counter()
         while True:
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                step(True)
-            barrier()
+                step_fn(True)
+            sync()
             dt = time.perf_counter() - t0
             if world > 1:
                 tmax = torch.tensor([dt, time.perf_counter() - t_begin], dtype=torch.float64, device=dev)
@@ -679,12 +685,34 @@ def main():
                 dt, total_elapsed = float(tmax[0].item()), float(tmax[1].item())       # every rank takes the same decision
             else:
                 total_elapsed = time.perf_counter() - t_begin
-            blocks.append(dt)
-            if total_elapsed >= seconds or len(blocks) >= 1 << 16:
-                break
+            out.append(dt)
+            if total_elapsed >= args.min_seconds or len(out) >= 1 << 16:
+                return out
 
+    serial_ms = None
+    if use_pipe:
+        # (1) the un-pipelined step on this box, timed exactly as the pipelined steps are below and right before them: gives
+        # the trace launch's own duration (HIP events on its stream; what the roofline is priced with and what rocprofv3
+        # reports for `bench.py --serial`) and the figure the pipeline is held against
+        serial_rows, serial_counts = torch.empty_like(cloud), torch.zeros_like(counts)
+        io.out_xyzl, io.counts = serial_rows.data_ptr(), serial_counts.data_ptr()
+        for _ in range(max(args.warmup, 5)):
+            serial_step(False)
+        torch.cuda.synchronize()
+        serial_ms = float(np.median(timed_blocks(serial_step, torch.cuda.synchronize))) / args.steps * 1e3
+
+    for _ in range(args.warmup):
+        step(False)
+    barrier()
+    # the timed steps, all of them before the host legs (CPU baseline, caller path) leave the GPU idle; value = rays of one
+    # block / its time
+    blocks = timed_blocks(step, barrier)
     host_legs = rank == 0 and world == 1 and not args.dist_selftest
-    timed_blocks(args.min_seconds * (0.5 if host_legs else 1.0))
+
+    if args.dump_outputs and rank == 0:
+        # the rows of the LAST timed step: the pipeline's rotating buffer it was submitted with, else the scene cloud
+        last = (state["i"] - 1) % 3 if use_pipe else None
+        dump_outputs(args.dump_outputs, pipe_rows[last] if use_pipe else cloud, pipe_counts[last] if use_pipe else counts)
 
     if use_pipe:
         # the pipeline's rows are the two-call step's rows, bit for bit (all three rotating buffers)
@@ -779,8 +807,6 @@ def main():
     })
     caller = caller_path(scene, sensor, poses, dirs, mesh) if (host_legs and not args.no_caller_path) else {}
     cpu = cpu_baseline(mesh, sensor, poses) if (host_legs and not args.no_cpu_baseline) else None
-    if host_legs:
-        timed_blocks(args.min_seconds * 0.5)          # the second half of the timed blocks, after the host legs
     elapsed = float(np.median(blocks))
     total_rays = n * world * args.steps
     value = total_rays / elapsed
@@ -834,8 +860,8 @@ def main():
                                            "at start-up, the fastest of prim / prim_pipe / range runs the timed blocks"} if dist_path else {}),
                 **({"serial_ms_per_step": serial_ms,
                     "serial_note": "the same step as lrc_scan_poses_dev + lrc_compact_dev on one stream, same box, same run "
-                                   "(median of 12 blocks); roofline.kernel_ms is the trace launch of THESE steps, alone on the "
-                                   "chip"} if serial_ms is not None else {}),
+                                   "(the same --steps / --min-seconds blocks, timed just before the pipelined ones); "
+                                   "roofline.kernel_ms is the trace launch of THESE steps, alone on the chip"} if serial_ms is not None else {}),
                 "caller_path_note": "value is the device-resident loop; caller_path_rays_per_s is what a host caller of "
                                     "the plugin surface gets (kept rows in page-locked host memory, PCIe included)",
                 "step": "in-kernel ray generation + BVH traversal + hit write-back (36 B/ray) + "
@@ -847,7 +873,8 @@ def main():
             "roofline": roofline,
         }
         res["config"].update(caller)
-        res["timed"] = {"blocks": len(blocks), "block_steps": args.steps, "block_ms_median": elapsed * 1e3,
+        res["timed"] = {"blocks": len(blocks), "block_steps": args.steps, "steps": len(blocks) * args.steps,
+                        "block_ms_median": elapsed * 1e3,
                         "block_ms_min": min(blocks) * 1e3, "block_ms_max": max(blocks) * 1e3,
                         "note": "value = rays of one block of --steps steps / the median block time"}
         if cpu is not None:

@@ -2441,8 +2441,15 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
         h.point3 = (float*)(b + off_pt); h.sem = (uint16_t*)(b + off_sem); h.ins = (uint16_t*)(b + off_ins);
         h.tile_count = (uint32_t*)(b + off_tc);
     }
+    // The two trace streams must reach the hardware on queues of their own, or their launches cannot overlap.  The runtime
+    // shares a bounded pool of hardware queues per stream priority among all of the process's streams (GPU_MAX_HW_QUEUES,
+    // 2 on some systems: then both trace streams landed on one queue behind each other and the pipelined step was 2-4 %
+    // SLOWER than the two calls, profiles/pipe_two_hw_queues.txt).  At the least priority they draw from a pool the
+    // process's normal-priority streams do not use, and everything else the caller submits keeps precedence.
+    int prio_least = 0, prio_greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: stream priorities"));
     for (int k = 0; k < 2; ++k) {
-        if (hipStreamCreateWithFlags(&pp->s_trace[k], hipStreamNonBlocking) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: stream"));
+        if (hipStreamCreateWithPriority(&pp->s_trace[k], hipStreamNonBlocking, prio_least) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: stream"));
         if (hipEventCreateWithFlags(&pp->ev_flush[k], hipEventDisableTiming) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
         int rc = ensure_tile_scratch(s->ctx, pp->scratch[k], tiles);
         if (rc) return bail(rc);

@@ -807,13 +807,17 @@ def test_full_size_c3_properties(ctx):
         assert np.array_equal(prim[p][hit[p]], pr[ref_idx])
 
 
-def test_bench_contract():
-    """bench.py prints one JSON line with the driver's keys plus roofline and cpu_baseline objects."""
+def test_bench_contract(tmp_path):
+    """bench.py prints one JSON line with the driver's keys plus roofline and cpu_baseline objects; --steps is the number of
+    timed steps, --dump-outputs writes what the last of them computed."""
     import json
     import subprocess
     import sys
     from conftest import REPO
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "3", "--min-seconds", "0.6"],
+    steps = 2000                     # ~0.8 s of timed steps: a stable figure for the pipelined / serial comparison below
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", "3",
+                          "--dump-outputs", str(dump)],
                          capture_output=True, text=True, timeout=600, check=True).stdout
     line = [l for l in out.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -821,7 +825,7 @@ def test_bench_contract():
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in r, k
-    assert r["n_gpus"] == 1 and r["steps"] == 20 and r["unit"] == "rays/s" and r["vs_baseline"] is None
+    assert r["n_gpus"] == 1 and r["steps"] == steps and r["unit"] == "rays/s" and r["vs_baseline"] is None
     # throughput guards that guard: the round-3 step did 11.3 G rays/s on the slowest box seen (a regression to the round-2
     # kernel or to a host-built scene lands below), and the pipelined step must not be slower than the two calls it replaces
     assert "workload" in r["config"] and r["value"] > 8e9
@@ -834,9 +838,19 @@ def test_bench_contract():
         assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9 and 0.0 < rf["frac"] <= 1.0
         assert abs(rf["frac"] - rf["valu_issue_frac"] * rf["lane_utilisation"]) < 1e-6
         assert rf["traffic"] > 0 and rf["hbm_side"]["frac_of_hbm_peak"] < 1.0
-    assert r["timed"]["blocks"] >= 2 and r["config"]["caller_path_rays_per_s"] > 1.5e9
+    assert r["timed"]["blocks"] == 1 and r["timed"]["steps"] == steps and r["config"]["caller_path_rays_per_s"] > 1.5e9
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(r["cpu_baseline"])
     assert r["cpu_baseline"]["kind"] == ("port" if "not installed" in r["cpu_baseline"].get("open3d", "") else "reference")
+    # the dumped outputs: float32 / float64 .npy files, at most 64 MB, the counts of every pose and the hits they add up to
+    files = {f.name: np.load(f) for f in dump.iterdir()}
+    assert set(files) == {"counts.npy", "row_index.npy", "points.npy", "sem.npy", "ins.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 << 20
+    c = files["counts.npy"]
+    assert c.shape == (64,) and c.sum() == round(r["config"]["hit_fraction"] * r["config"]["rays_per_step_per_gpu"])
+    m = len(files["row_index.npy"])
+    assert files["points.npy"].shape == (m, 3) and len(files["sem.npy"]) == len(files["ins.npy"]) == m
+    assert m == min(int(c.sum()), 1 << 20) and np.isfinite(files["points.npy"]).all()
 
 
 def test_two_rank_launch_of_the_bench_path():
