@@ -545,6 +545,45 @@ int lrc_min_distances(lrc_ctx* ctx, const float* a3, uint64_t n, const float* b3
 int lrc_rbf_kernel_sum(lrc_ctx* ctx, const float* a3, uint64_t n, const float* b3, uint64_t m, double gamma,
                        double* out_sum);
 
+/* ---- detection boxes ---------------------------------------------------------------------------------
+ * Axis-aligned boxes of the object instances of a labelled cloud after a k-nearest-neighbour statistical outlier
+ * filter: lidar_net_bbox_visualizer.py:163-249 of the reference (instances by class and instance id, Open3D's
+ * remove_statistical_outlier(nb_neighbors=k, std_ratio), min / max of what is left), all instances in one call.
+ *   instance : (index of sem in class_ids, ins) with ins != 0; rows of other classes or with ins == 0 are ignored;
+ *              an instance of fewer than min_points rows is dropped, one of fewer than k rows keeps every row.
+ *   avg      : per row of an instance of n >= k rows, (sum of the square roots of the k smallest float64 squared
+ *              distances (dx*dx + dy*dy) + dz*dz to rows of the same instance, itself included, ascending, one after
+ *              the other) / k.
+ *   filter   : mean = sum_{avg>0} avg / n, std = sqrt(sum_{avg>0} (avg - mean)^2 / (n - 1)), threshold = mean +
+ *              std_ratio * std; a row is kept iff avg > 0 && avg < threshold (k or more coincident rows go).
+ * One lrc_box per instance of min_points rows or more, ordered by (position of the class in class_ids, ins); the
+ * call writes min(total, capacity) of them and the total to *out_num_boxes.  The optional per-row outputs (num_rows
+ * entries, input order): avg (-1 where the filter did not run) and keep (1 = the row is in its instance's box).
+ * 1 <= k <= 32, at most 64 distinct class ids, num_rows < 2^31; cell_size <= 0 picks a grid spacing per instance
+ * (results do not depend on it).  Rows are (K,4) x, y, z, label bits (sem | ins<<16) on the device, as the scan
+ * pipeline leaves them, or host float32 xyz plus uint16 sem and ins.  Boxes and the count are HOST memory in both
+ * entry points: lrc_instance_boxes_dev returns after the work it enqueued on `stream` has finished. */
+typedef struct lrc_box {
+    uint16_t sem;
+    uint16_t ins;
+    uint32_t num_points;     /* rows of the instance                                               */
+    uint32_t num_kept;       /* rows inside the box (0: the filter removed all; min3 = +inf, max3 = -inf) */
+    uint32_t filtered;       /* 1: num_points >= k and the filter ran; 0: every row kept             */
+    float    min3[3];        /* float32 minimum of the kept rows                                   */
+    float    max3[3];
+    double   mean;           /* filter statistics; 0 and +inf when filtered == 0                    */
+    double   threshold;
+} lrc_box;                   /* 56 bytes */
+
+int lrc_instance_boxes(lrc_ctx* ctx, const float* points3, const uint16_t* sem, const uint16_t* ins, uint64_t num_rows,
+                       const uint16_t* class_ids, uint32_t num_classes, uint32_t min_points, uint32_t k, double std_ratio,
+                       double cell_size, lrc_box* out_boxes, uint64_t capacity, uint64_t* out_num_boxes,
+                       double* out_avg /* nullable */, uint8_t* out_keep /* nullable */);
+int lrc_instance_boxes_dev(lrc_ctx* ctx, const float* d_xyzl, uint64_t num_rows, const uint16_t* class_ids,
+                           uint32_t num_classes, uint32_t min_points, uint32_t k, double std_ratio, double cell_size,
+                           lrc_box* out_boxes, uint64_t capacity, uint64_t* out_num_boxes,
+                           double* d_out_avg /* nullable */, uint8_t* d_out_keep /* nullable */, void* stream);
+
 /* ---- robot-cube occupancy for the trajectory planner ----------------
  * out_flags[q] = 1 iff some mesh vertex lies inside the axis-aligned cube [p_q - half, p_q + half] (float64,
  * inclusive), for all Q positions at once.  Replaces AutoTrajectoryGenerator._is_point_inside_mesh

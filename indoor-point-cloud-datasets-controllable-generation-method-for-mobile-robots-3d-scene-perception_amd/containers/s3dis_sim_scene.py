@@ -343,9 +343,15 @@ class S3DISSimScene:
     def _export_combined_pointcloud_with_labels(self, output_dir: Path):
         """combined_pointcloud_with_label.ply: np.vstack of the non-empty frames with colour, semantic and instance
         label per point (:339-377)."""
+        cloud = self._labelled_cloud()
+        if cloud is not None:
+            self._save_labeled_ply(Path(output_dir) / "combined_pointcloud_with_label.ply", *cloud)
+
+    def _labelled_cloud(self):
+        """(points, colours uint8, sem, ins) of combined_pointcloud_with_label.ply; None without points."""
         pts = self.combined_points()
         if len(pts) == 0:
-            return
+            return None
         has_frame_labels = any(f.semantic_labels is not None for f in self.frames if len(f.points) > 0)
         # With the annotation source configured (the reference's normal wiring, :379-427) the files decide colours and
         # labels, also when the frames carry the hit triangles' labels: load them before choosing the branch.
@@ -362,7 +368,27 @@ class S3DISSimScene:
         else:                                 # labels written back by the trace kernel; the reference's default grey
             sem, ins = self.combined_labels()
             colors = np.full((len(pts), 3), int(0.5 * 255), dtype=np.uint8)
-        self._save_labeled_ply(Path(output_dir) / "combined_pointcloud_with_label.ply", pts, colors, sem, ins)
+        return pts, colors, sem, ins
+
+    def export_detection_annotations(self, output_dir: Path, semantic_mapping=None):
+        """The detection annotations lidar_net_bbox_visualizer.py derives from combined_pointcloud_with_label.ply, without
+        writing the cloud: output_dir/combined_pointcloud_with_label_detection_annotations.json (the name the reference
+        tool gives it).  semantic_mapping: class name -> semantic id, default S3DIS_SEMANTIC_MAPPING (the ids this
+        simulator writes).  Returns the accepted bbox dicts, or None (no points, or no box accepted; no file then)."""
+        from lidar_net_bbox_visualizer import S3DIS_SEMANTIC_MAPPING, LiDARNetBBoxVisualizer
+        cloud = self._labelled_cloud()
+        if cloud is None:
+            return None
+        pts, colors, sem, ins = cloud
+        vis = LiDARNetBBoxVisualizer(S3DIS_SEMANTIC_MAPPING if semantic_mapping is None else semantic_mapping)
+        # the coordinates as the PLY holds them (float32), so that the boxes are those of the written file
+        bboxes = vis.room_bboxes({"points": np.asarray(pts, np.float32).astype(np.float64), "colors": colors / 255.0,
+                                  "semantic_labels": np.asarray(sem, np.uint16), "instance_labels": np.asarray(ins, np.uint16)})
+        if not bboxes:
+            return None
+        Path(output_dir).mkdir(parents=True, exist_ok=True)
+        vis.generate_detection_annotations(bboxes, Path(output_dir) / "combined_pointcloud_with_label_detection_annotations.json")
+        return bboxes
 
     def _save_labeled_ply(self, output_path: Path, points: np.ndarray, colors: np.ndarray,
                           semantic_labels: np.ndarray, instance_labels: np.ndarray):

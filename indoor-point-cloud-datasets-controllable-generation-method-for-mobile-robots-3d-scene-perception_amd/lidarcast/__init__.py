@@ -2,9 +2,11 @@
 from ._capi import LIB_PATH, LRC_INVALID_PRIM, LidarcastError, load
 from .core import (ATTRS, FRAME_ATTRS, Context, DeviceHits, DirectionTable, NearestIndex, OccupancyIndex, PinnedPool, ScanPipe, Scene,
                    bake_triangle_labels)
+from .boxes import BOX_DTYPE, instance_boxes, instance_boxes_dev
 
 __all__ = ["LIB_PATH", "LRC_INVALID_PRIM", "LidarcastError", "load", "ATTRS", "Context",
-           "DeviceHits", "DirectionTable", "Scene", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "version", "device_count"]
+           "DeviceHits", "DirectionTable", "Scene", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "BOX_DTYPE", "instance_boxes", "instance_boxes_dev", "version",
+           "device_count"]
 
 
 def version():

@@ -37,6 +37,7 @@ SYMBOLS = (
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
     "lrc_min_distances", "lrc_rbf_kernel_sum",
+    "lrc_instance_boxes", "lrc_instance_boxes_dev",
     "lrc_occ_create", "lrc_occ_destroy", "lrc_occ_query",
     "lrc_rng_scan_draws", "lrc_rays_from_trig",
 )
@@ -84,6 +85,12 @@ class LrcFrames(C.Structure):
                 ("incident_deg", C.c_void_p), ("index", C.c_void_p), ("xyzl", C.c_void_p),
                 ("range_origin", C.c_void_p), ("range_origin_mean", C.c_void_p), ("range_origin_std", C.c_void_p),
                 ("incident_mean", C.c_void_p), ("incident_std", C.c_void_p)]
+
+
+class LrcBox(C.Structure):
+    _fields_ = [("sem", C.c_uint16), ("ins", C.c_uint16), ("num_points", C.c_uint32), ("num_kept", C.c_uint32),
+                ("filtered", C.c_uint32), ("min3", C.c_float * 3), ("max3", C.c_float * 3), ("mean", C.c_double),
+                ("threshold", C.c_double)]
 
 
 class LrcMt19937State(C.Structure):
@@ -191,6 +198,10 @@ def load():
         "lrc_occ_query": [vp, vp, u64, dbl, vp],
         "lrc_min_distances": [vp, vp, u64, vp, u64, vp],
         "lrc_rbf_kernel_sum": [vp, vp, u64, vp, u64, dbl, C.POINTER(dbl)],
+        "lrc_instance_boxes": [vp, vp, vp, vp, u64, vp, C.c_uint32, C.c_uint32, C.c_uint32, dbl, dbl, vp, u64,
+                               C.POINTER(u64), vp, vp],
+        "lrc_instance_boxes_dev": [vp, vp, u64, vp, C.c_uint32, C.c_uint32, C.c_uint32, dbl, dbl, vp, u64,
+                                   C.POINTER(u64), vp, vp, vp],
         "lrc_nn_create": [vp, vp, u64, dbl, C.POINTER(vp)],
         "lrc_nn_destroy": [vp],
         "lrc_nn_query": [vp, vp, u64, vp, vp],
