@@ -665,6 +665,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) v
         (void)INLINE_CLAUSE;
         RaySlab sl;
         uint32_t sel_nx = 0, sel_ny = 0, sel_nz = 0, sel_fx = 0, sel_fy = 0, sel_fz = 0;
+        uint32_t oct = 0;     // quantised paths: the wave's direction octant (wave-uniform, SGPR)
         if (Q) {
             // normalised coordinates: n = (x - base) / W per axis, W a power of two (scaling by it is exact)
             const float ix = safe_inv(d.x), iy = safe_inv(d.y), iz = safe_inv(d.z);
@@ -676,7 +677,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) v
             // direction (for ix > 0 fma(lo, ix, -ox) <= fma(hi, ix, -ox) by monotone rounding, so picking by sign IS
             // the min / max of slab_interval, bit for bit)
             constexpr uint32_t kLo = 0x0701000Cu, kHi = 0x0703020Cu;   // {0x40, half word, 0x00}
-            const uint32_t oct = (uint32_t)__builtin_amdgcn_readfirstlane((int)sign_octant(d));
+            oct = (uint32_t)__builtin_amdgcn_readfirstlane((int)sign_octant(d));
             sel_nx = (oct & 1u) ? kHi : kLo; sel_fx = (oct & 1u) ? kLo : kHi;
             sel_ny = (oct & 2u) ? kHi : kLo; sel_fy = (oct & 2u) ? kLo : kHi;
             sel_nz = (oct & 4u) ? kHi : kLo; sel_fz = (oct & 4u) ? kLo : kHi;
@@ -715,6 +716,18 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) v
             slab_interval(sl, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, n0, f0);
             slab_interval(sl, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, n1, f1);
             choose(n0, f0, n1, f1, __float_as_int(q3.x), __float_as_int(q3.y));
+        };
+        // the same on a wave-uniform node (SGPRs).  Quantised path: the normalised image, entry / exit planes picked by
+        // the wave's octant with scalar selects (slab_interval2_oct: slab_interval's bits, twelve vector min / max less)
+        auto step_u = [&](const F4 q0, const F4 q1, const F4 q2, const F4 q3) {
+            if (QM == 1) {
+                const float c0[6] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y}, c1[6] = {q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+                float n0, f0, n1, f1;
+                slab_interval2_oct(sl, oct, c0, c1, n0, f0, n1, f1);
+                choose(n0, f0, n1, f1, __float_as_int(q3.x), __float_as_int(q3.y));
+            } else {
+                step(q0, q1, q2, q3);
+            }
         };
         // one inner-node step on a 32-byte quantised node: per child (lo|hi << 16) x, y, z and the reference
         auto step_q = [&](const uint4 a, const uint4 b) {
@@ -881,7 +894,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) v
 #endif
                         {
                             const float4* n = (Q ? p.nodes_n : p.nodes) + (size_t)uref * 4;
-                            step(ld_uniform(n), ld_uniform(n + 1), ld_uniform(n + 2), ld_uniform(n + 3));
+                            step_u(ld_uniform(n), ld_uniform(n + 1), ld_uniform(n + 2), ld_uniform(n + 3));
                         }
                     } else {
                         fetch_step();

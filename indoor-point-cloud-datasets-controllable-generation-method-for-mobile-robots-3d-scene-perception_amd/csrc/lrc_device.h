@@ -77,6 +77,50 @@ LRC_DI void slab_interval(const RaySlab& s, float lox, float loy, float loz, flo
     tf = fma_(f, kPadRelHi, kPadAbs);
 }
 
+// Entry / exit plane of one axis for two boxes, picked on the scalar unit: (n, f) = (hi, lo) if bit B of oct is set
+// (negative direction component), else (lo, hi).  Every operand is wave-uniform and lives in SGPRs.  Inline assembly
+// because the compiler keeps a loop-invariant condition as a lane mask and selects with v_mov + v_cndmask pairs.
+template <int B>
+LRC_DI void pick_planes_s(uint32_t oct, float lo0, float hi0, float lo1, float hi1, float& n0, float& f0, float& n1,
+                          float& f1) {
+    asm("s_bitcmp1_b32 %4, %9\n\t"
+        "s_cselect_b32 %0, %6, %5\n\t"
+        "s_cselect_b32 %1, %5, %6\n\t"
+        "s_cselect_b32 %2, %8, %7\n\t"
+        "s_cselect_b32 %3, %7, %8"
+        : "=&s"(n0), "=&s"(f0), "=&s"(n1), "=&s"(f1)
+        : "s"(oct), "s"(lo0), "s"(hi0), "s"(lo1), "s"(hi1), "n"(B)
+        : "scc");
+}
+
+// slab_interval of the two children of a wave-uniform node, for the rays of a wave that all point into direction
+// octant `oct` (sign_octant of d, wave-uniform): the plane the rays enter / leave through on each axis is picked by the
+// sign of d (pick_planes_s) instead of ordered by a min / max.  safe_inv keeps the sign of d, of a zero component too,
+// so s.ix has d's sign; for s.ix > 0 and lo <= hi, fma(lo, ix, -ox) <= fma(hi, ix, -ox) by monotone rounding (the
+// reverse for ix < 0), and the picked value IS slab_interval's min / max.  Where the two can differ, they differ in
+// the sign of a zero only, which the pad FMAs remove: tn and tf are slab_interval's, bit for bit, on every box with
+// lo <= hi.  The inverted box of the empty leaf (lo > hi; only a one-leaf mesh has it) is never hit here, as on the per-lane
+// v_perm path; it holds no triangle, so no result depends on it.
+// c0 / c1: lo x, y, z, hi x, y, z of each child.
+LRC_DI void slab_interval2_oct(const RaySlab& s, uint32_t oct, const float* c0, const float* c1, float& tn0, float& tf0,
+                               float& tn1, float& tf1) {
+    float n0[3], f0[3], n1[3], f1[3];
+    pick_planes_s<0>(oct, c0[0], c0[3], c1[0], c1[3], n0[0], f0[0], n1[0], f1[0]);
+    pick_planes_s<1>(oct, c0[1], c0[4], c1[1], c1[4], n0[1], f0[1], n1[1], f1[1]);
+    pick_planes_s<2>(oct, c0[2], c0[5], c1[2], c1[5], n0[2], f0[2], n1[2], f1[2]);
+    auto one = [&](const float* n, const float* f, float& tn, float& tf) {
+        const float nx = fma_(n[0], s.ix, -s.ox), fx = fma_(f[0], s.ix, -s.ox);
+        const float ny = fma_(n[1], s.iy, -s.oy), fy = fma_(f[1], s.iy, -s.oy);
+        const float nz = fma_(n[2], s.iz, -s.oz), fz = fma_(f[2], s.iz, -s.oz);
+        const float nn = max2(max2(nx, ny), max2(nz, 0.0f));
+        const float ff = min2(min2(fx, fy), fz);
+        tn = fma_(nn, kPadRelLo, -kPadAbs);
+        tf = fma_(ff, kPadRelHi, kPadAbs);
+    };
+    one(n0, f0, tn0, tf0);
+    one(n1, f1, tn1, tf1);
+}
+
 // Ray/triangle test on an edge record (v0, e1 = v0 - v1, e2 = v2 - v0, Ng = cross(e2, e1)); the hit definition of
 // DESIGN.md section 3 is tri_mt && box_clause:
 //   den = Ng.D != 0,  U = (C x D).e2,  V = (C x D).e1 (sign-corrected), U,V >= 0, U+V <= |den|,
