@@ -249,8 +249,10 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t num_segments, uint64_t seg_len,
  * The poses of a trajectory are independent (s3dis_simulator.py:254-288), and so are consecutive trajectories over one
  * mesh (the reference's batch driver, s3dis_simulator.py:594-726, runs them one after the other).  A caller that stays on
  * the device -- dataset generation, the multi-GPU step, bench.py -- submits batch after batch; each submit is one pose-batched
- * scan (lrc_scan_poses_dev: the complete 36-byte record per ray, into one of four record sets the pipeline owns) plus the
- * stable compaction (lrc_compact_dev) into the CALLER's rows / counts.  The pipeline arranges the launches so that the trace
+ * scan (lrc_scan_poses_dev, into one of four record sets the pipeline owns) plus the stable compaction (lrc_compact_dev) into
+ * the CALLER's rows / counts.  With rays_per_pose % 64 == 0 a set holds only what the compaction reads -- per ray the packed
+ * (x, y, z, label) row and (t, triangle slot), per 64 rays the keep mask -- and the complete 36-byte record is formed from it
+ * only when lrc_pipe_records asks for it.  The pipeline arranges the launches so that the trace
  * of submit k+1 fills the wave slots the trace of submit k leaves empty while its last, long-running waves finish, and the
  * rows of submit k are scattered by the first workgroups of the trace launch of submit k+2 (DESIGN.md "the launch tail":
  * a 64-pose launch alone loses a sixth of its time to that tail).  Same arithmetic, same bytes as lrc_scan_poses_dev +
@@ -263,7 +265,9 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t num_segments, uint64_t seg_len,
  *                     The buffers of a submit are written up to two submits later: rotate at least three output buffers
  *                     between lrc_pipe_wait calls.  rays_per_pose % 64 != 0 falls back to scan + compaction per stream.
  *   lrc_pipe_records  the fixed-stride records (lrc_hits, device pointers, tile_count included) of submit `ticket`;
- *                     valid until three further submits have been made (four sets rotate).
+ *                     valid until three further submits have been made (four sets rotate).  For a submit that kept only
+ *                     rows (rays_per_pose % 64 == 0) the complete records are rebuilt first, behind that submit's trace,
+ *                     and the host waits for them: the same bytes lrc_scan_poses_dev writes.  A verification surface.
  *   lrc_pipe_trace_ms the time the trace launch of submit `ticket` spent between its stream reaching it and its last wave
  *                     (HIP events on the launch stream; inside the pipeline launches overlap, so this is longer than the
  *                     launch's share of the step).  Synchronises the host with that launch.

@@ -178,6 +178,14 @@ struct RebuildParams {
     uint32_t skip_slab;                      // tiles of this slab are not rebuilt (the caller scatters its own records); ~0u: none
 };
 
+// The lean record set of a pipeline submit (lrc_pipe_submit), as the scatter reads it: per ray the packed row
+// (x, y, z, label bits) exactly as it goes to lrc_compact_io::out_xyzl (zeros for a ray that is not kept), per 64-ray tile
+// the keep mask (bit l: lane l kept).  Only for segments of a multiple of 64 rays: tile t holds rays 64 t ... 64 t + 63.
+struct LeanIn {
+    const float4* row;
+    const uint64_t* keep_mask;
+};
+
 struct TraceParams {
     const float4* nodes;
     const float4* tris;
@@ -214,7 +222,15 @@ struct TraceParams {
         const uint32_t* tile_off;
         const uint32_t* super_total;
         lrc_compact_io io;
+        LeanIn lean;               // plain form: the earlier scan's lean record set (io's t / point3 / sem / ins are not read)
     } pre;
+    // lean record set (scan pipeline): row != NULL -> write_back stores per ray the packed row and (t bits, slot), per wave
+    // the keep mask and tile_count, and no column of `out`.  Wave-uniform: a run-time branch.
+    struct Lean {
+        float4* row;
+        uint2* aux;                // (t bits, slot): t after range noise, slot = 0xFFFFFFFF for a ray that is not kept
+        uint64_t* keep_mask;
+    } lean;
     float qbase[3], qW[3], qinvW[3];   // normalised coordinate n = (x - qbase) * qinvW in [2, 4); qW = 1 / qinvW = 2^k
     // inputs
     const float* rays6;        // explicit rays (GEN = false)
@@ -353,6 +369,13 @@ __device__ __forceinline__ void rebuild_counts(const RebuildParams& q, uint32_t 
     }
 }
 
+// the unit normal of the record from the third float4 of a triangle slot (Ng in y, z, w): write_back and the expansion of a
+// lean pipeline record set (expand_lean_kernel) both form it here, so the two cannot drift by a bit
+__device__ __forceinline__ void slot_normal(float4 c, float& nx, float& ny, float& nz) {
+    const float len = __builtin_sqrtf(fma_(c.w, c.w, fma_(c.z, c.z, c.y * c.y)));
+    nx = c.y / len; ny = c.z / len; nz = c.w / len;
+}
+
 // ---- fused write-back: everything after the closest hit is known (shared by the trace kernels) ------------------
 // best_slot = 0xFFFFFFFF: no hit.  FILTER: apply the max_range filter (scans and casts with a centre).
 // BY_PRIM: `best_slot` is the caller's triangle ROW (sector_kernel keys rays by (t, row)); labels and the normal then
@@ -361,6 +384,7 @@ template <bool FILTER_ALWAYS, bool BY_PRIM = false>
 __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, uint32_t tid, V3 o, V3 d, double cx,
                                            double cy, double cz, float tbest, uint32_t best_slot) {
     constexpr int GEN = FILTER_ALWAYS ? 1 : 0;
+    const bool lean = FILTER_ALWAYS && !BY_PRIM && p.lean.row != nullptr;    // a kernel argument: wave-uniform
     bool keep = best_slot != 0xFFFFFFFFu;
     float t_out = __builtin_inff();
     uint32_t prim = LRC_INVALID_PRIM;
@@ -385,7 +409,10 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
         const double dist = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
         if (p.has_center || GEN != 0) keep = dist < p.max_range;
         if (p.min_range > 0.0) keep = keep & (dist >= p.min_range);     // opt-in; the reference never applies it
-        if (keep) {
+        if (keep && lean) {           // the lean record: no triangle id, no normal
+            t_out = tbest;
+            label = p.slot_label[best_slot];
+        } else if (keep) {
             t_out = tbest;
             if (BY_PRIM) {
                 prim = best_slot;
@@ -398,8 +425,7 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
                 float4 c;
                 if (BY_PRIM) { const float4 g = p.prim_plane[(size_t)best_slot * 2 + 1]; c = make_float4(0.f, g.x, g.y, g.z); }
                 else c = p.tris[(size_t)best_slot * 3 + 2];
-                const float len = __builtin_sqrtf(fma_(c.w, c.w, fma_(c.z, c.z, c.y * c.y)));
-                nx = c.y / len; ny = c.z / len; nz = c.w / len;
+                slot_normal(c, nx, ny, nz);
             }
             if (p.out.incident_deg) {
                 if (p.incident_mode == 1) {   // opt-in: angle between the ray and the surface normal
@@ -416,6 +442,17 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
         } else {
             px = py = pz = 0.f;
         }
+    }
+    if (lean) {
+        // two stores per ray: the row as the scatter copies it, and what the expansion for lrc_pipe_records needs besides
+        const unsigned long long m = __ballot(keep);
+        if ((tid & 63u) == 0) {
+            if (p.out.tile_count) p.out.tile_count[gid >> 6] = (uint32_t)__popcll(m);
+            p.lean.keep_mask[gid >> 6] = m;
+        }
+        p.lean.row[gid] = make_float4(px, py, pz, __uint_as_float(label));
+        p.lean.aux[gid] = make_uint2(__float_as_uint(t_out), keep ? best_slot : 0xFFFFFFFFu);
+        return;
     }
     if (p.out.tile_count) {   // kept rays of this wave's 64 consecutive outputs (feeds lrc_compact_dev)
         const unsigned long long m = __ballot(keep);
@@ -550,6 +587,67 @@ __device__ __forceinline__ void scatter_tiles_xyzl(const lrc_compact_io& io, uin
         }
     }
 }
+// scatter_tile from a lean record set (LeanIn): the tile's keep mask is one scalar load, a kept lane loads its row (one
+// 16-byte load) and every output is a function of that row and the lane -- the same values scatter_tile forms from the
+// 36-byte record.  seg_len % 64 == 0 (a lean set exists only then).
+__device__ __forceinline__ void scatter_tile_lean(const lrc_compact_io& io, const LeanIn& in, uint64_t seg_len, uint64_t tps,
+                                                  uint64_t tile, uint32_t lane, const uint32_t* tile_off,
+                                                  const uint32_t* super_total) {
+    typedef __attribute__((address_space(4))) const uint64_t cu64;
+    const unsigned long long m = ((cu64*)in.keep_mask)[tile];
+    if (m == 0ull) return;
+    const uint64_t sbase = super_prefix_wave(super_total, tile >> 10, lane);
+    if (!((m >> lane) & 1ull)) return;
+    const uint64_t seg = tile / tps, i = (tile - seg * tps) * 64 + lane;
+    const float4 r = in.row[seg * seg_len + i];
+    const uint64_t dst = sbase + tile_off[tile] + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+    const uint32_t lab = __float_as_uint(r.w);
+    if (io.out_xyzl) ((float4*)io.out_xyzl)[dst] = r;
+    if (io.out_point3) {
+        float* q = io.out_point3 + dst * 3;
+        q[0] = r.x; q[1] = r.y; q[2] = r.z;
+    }
+    if (io.out_sem) io.out_sem[dst] = (uint16_t)(lab & 0xFFFFu);
+    if (io.out_ins) io.out_ins[dst] = (uint16_t)(lab >> 16);
+    if (io.out_index) io.out_index[dst] = (uint32_t)i;
+    if (io.out_range_origin) io.out_range_origin[dst] = __builtin_sqrtf((r.x * r.x + r.y * r.y) + r.z * r.z);   // as scatter_tile
+}
+
+// scatter_tiles_xyzl from a lean record set: scalar loads of the keep masks instead of per-lane t loads, then one 16-byte row
+// load per lane instead of five loads per kept lane -- the row IS the output row.  Four tiles at a time: eight rows in flight
+// per lane (32 registers) pushed the trace kernel, whose registers this wave holds, into scratch.
+template <int R>
+__device__ __forceinline__ void scatter_tiles_xyzl_lean(const lrc_compact_io& io, const LeanIn& in, uint64_t ntiles, uint64_t tile0,
+                                                        uint32_t lane, const uint32_t* tile_off, const uint32_t* super_total) {
+    typedef __attribute__((address_space(4))) const uint64_t cu64;
+    typedef __attribute__((address_space(4))) const uint32_t cu32;
+    constexpr int H = R < 4 ? R : 4;
+    static_assert(R % H == 0, "R: a multiple of four, or below four");
+    const uint64_t sbase = super_prefix_wave(super_total, tile0 >> 10, lane);
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int h = 0; h < R; h += H) {
+        unsigned long long m[H];
+        uint32_t off[H];
+#pragma unroll
+        for (int r = 0; r < H; ++r) {
+            const uint64_t tile = tile0 + h + r;
+            const bool valid = tile < ntiles;          // wave-uniform
+            m[r] = valid ? ((cu64*)in.keep_mask)[tile] : 0ull;
+            off[r] = valid ? ((cu32*)tile_off)[tile] : 0u;
+        }
+        // every lane of a tile with a kept ray loads its row: one coalesced 1 KiB read per tile and no divergent branch
+        // between the loads, so all of them are in flight at once (rays that are not kept have zero rows, never stored)
+        float4 row[H];
+#pragma unroll
+        for (int r = 0; r < H; ++r)
+            row[r] = m[r] != 0ull ? in.row[(tile0 + h + r) * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int r = 0; r < H; ++r)
+            if ((m[r] >> lane) & 1ull)
+                ((float4*)io.out_xyzl)[sbase + off[r] + (uint64_t)__popcll(m[r] & below)] = row[r];
+    }
+}
 #ifndef LRC_PRE_TILES
 #define LRC_PRE_TILES 8
 #endif
@@ -586,13 +684,15 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) v
             if (p.pre.io.counts) segment_count(p.pre.io, p.pre.tps, p.pre.ntiles, p.pre.nseg, (uint64_t)blockIdx.x * kTBlock + tid,
                                                p.pre.tile_off, nullptr, p.pre.super_total);
             const uint64_t tile0 = (uint64_t)blockIdx.x * kPreTiles;
-            if (tile0 < p.pre.ntiles) {
+            if (tile0 < p.pre.ntiles) {      // the earlier scan's records are a lean set (only fused submits ride here)
                 if (p.pre.rows_only) {
-                    scatter_tiles_xyzl<kPreTiles>(p.pre.io, p.pre.ntiles, tile0, tid, p.pre.tile_off, p.pre.super_total);
+                    scatter_tiles_xyzl_lean<kPreTiles>(p.pre.io, p.pre.lean, p.pre.ntiles, tile0, tid, p.pre.tile_off,
+                                                       p.pre.super_total);
                 } else {
                     for (int r = 0; r < kPreTiles; ++r)
                         if (tile0 + r < p.pre.ntiles)
-                            scatter_tile(p.pre.io, p.pre.seg_len, p.pre.tps, tile0 + r, tid, p.pre.tile_off, nullptr, 0, p.pre.super_total);
+                            scatter_tile_lean(p.pre.io, p.pre.lean, p.pre.seg_len, p.pre.tps, tile0 + r, tid, p.pre.tile_off,
+                                              p.pre.super_total);
                 }
             }
             return;
@@ -1250,6 +1350,43 @@ __global__ __launch_bounds__(kBlock) void compact_scatter_kernel(const lrc_compa
     const uint64_t tile = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (tile >= ntiles) return;
     scatter_tile(io, seg_len, tps, tile, threadIdx.x & 63u, tile_off, super_base, tile_base, super_total);
+}
+
+// Pass B of the scan pipeline's plain form (lrc_pipe_wait) for a lean record set: as compact_scatter_kernel, tile_base = 0 and
+// the super tile bases summed from the totals
+__global__ __launch_bounds__(kBlock) void compact_scatter_lean_kernel(const lrc_compact_io io, const LeanIn in,
+                                                                      uint64_t seg_len, uint64_t tps,
+                                                                      uint64_t ntiles, uint64_t nseg,
+                                                                      const uint32_t* tile_off,
+                                                                      const uint32_t* super_total) {
+    if (io.counts) segment_count(io, tps, ntiles, nseg, (uint64_t)blockIdx.x * kBlock + threadIdx.x, tile_off, nullptr, super_total);
+    const uint64_t tile = (uint64_t)blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    scatter_tile_lean(io, in, seg_len, tps, tile, threadIdx.x & 63u, tile_off, super_total);
+}
+
+// lrc_pipe_records of a lean set: the 36-byte record of every ray rebuilt from (row, t, slot) -- the triangle id through the
+// scene's slot table, the normal by the helper write_back forms it with; a ray that is not kept gets the miss record
+__global__ __launch_bounds__(kBlock) void expand_lean_kernel(const float4* __restrict__ row, const uint2* __restrict__ aux,
+                                                             const uint32_t* __restrict__ slot_prim, const float4* __restrict__ tris,
+                                                             lrc_hits out, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 r = row[i];
+    const uint2 a = aux[i];
+    const uint32_t lab = __float_as_uint(r.w);
+    uint32_t prim = LRC_INVALID_PRIM;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if (a.y != 0xFFFFFFFFu) {
+        prim = slot_prim[a.y];
+        slot_normal(tris[(size_t)a.y * 3 + 2], nx, ny, nz);
+    }
+    out.t[i] = __uint_as_float(a.x);
+    out.prim[i] = prim;
+    out.normal3[i * 3] = nx; out.normal3[i * 3 + 1] = ny; out.normal3[i * 3 + 2] = nz;
+    out.point3[i * 3] = r.x; out.point3[i * 3 + 1] = r.y; out.point3[i * 3 + 2] = r.z;
+    out.sem[i] = (uint16_t)(lab & 0xFFFFu);
+    out.ins[i] = (uint16_t)(lab >> 16);
 }
 
 // |p| of assembled (x, y, z, label) rows from the WORLD origin, float32, as np.linalg.norm(points, axis=1) forms it
@@ -2376,6 +2513,10 @@ static int ensure_tile_scratch(lrc_ctx* ctx, lrc_ctx::TileScratch& sc, uint64_t 
 // a launch at all: it rides at the FRONT of the trace launch of submit k+2 (same stream, TraceParams::pre: one tile per
 // one-wave workgroup), so it is handed out exactly when the previous launch's tail begins and is gone in microseconds.  Four
 // record sets: set k is read by launch k+2 and written again by launch k+4, both on its own stream.
+// A fused submit writes a set's LEAN form: per ray the packed row and (t, slot), 24 B, per tile the keep mask -- all the
+// scatter reads, two stores per ray instead of ten, no triangle id and no normal in the trace.  The
+// complete 36-byte record, in arrays of its own beside the lean ones, is what the plain fallback and the sharded submits
+// write, and what lrc_pipe_records expands a lean set into on demand.
 struct lrc_pipe {
     lrc_scene* scene = nullptr;
     int device = 0;
@@ -2383,12 +2524,17 @@ struct lrc_pipe {
     static constexpr int kSets = 4;
     void* slab[kSets] = {};                                  // one allocation per record set
     lrc_hits rec[kSets] = {};
+    float4* row[kSets] = {};                                 // the lean form (row, aux, keep_mask; tile_count is rec's)
+    uint2* aux[kSets] = {};
+    uint64_t* keep_mask[kSets] = {};
+    bool lean[kSets] = {};                                   // the set holds its last submit in the lean form ...
+    bool expanded[kSets] = {};                               // ... and lrc_pipe_records has rebuilt rec from it
     lrc_compact_io out[kSets] = {};                          // the caller's output buffers of the submit that used the set
     uint64_t poses[kSets] = {};                              // its pose count
     bool pending[kSets] = {};                                // scanned, scan pass enqueued, rows not yet scattered
     lrc_ctx::TileScratch scratch[2];                         // per trace stream: offsets of the scan waiting for its scatter
     hipStream_t s_trace[2] = {};
-    hipEvent_t ev_in[kSets] = {}, ev_t0[kSets] = {}, ev_trace[kSets] = {}, ev_flush[2] = {};
+    hipEvent_t ev_in[kSets] = {}, ev_t0[kSets] = {}, ev_trace[kSets] = {}, ev_flush[2] = {}, ev_expand = nullptr;
     bool fused = true;                                       // false: N % 64 != 0 or > 512 super tiles: plain chain per stream
     uint64_t ticket = 0;                                     // submits so far; submit k uses set k % 4, trace stream k % 2
     // sharded submits (lrc_pipe_submit_sharded): scratch of the scan over ALL ranks' keep counts, per trace stream, and the
@@ -2407,6 +2553,7 @@ int lrc_pipe_destroy(lrc_pipe* pp) {
         if (pp->slab[k]) (void)hipFree(pp->slab[k]);
         for (hipEvent_t e : {pp->ev_in[k], pp->ev_t0[k], pp->ev_trace[k]}) if (e) (void)hipEventDestroy(e);
     }
+    if (pp->ev_expand) (void)hipEventDestroy(pp->ev_expand);
     for (int k = 0; k < 2; ++k) {
         if (pp->ev_flush[k]) (void)hipEventDestroy(pp->ev_flush[k]);
         for (lrc_ctx::TileScratch* scp : {&pp->scratch[k], &pp->gscratch[k]}) {
@@ -2441,10 +2588,12 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
     pp->fused = rays_per_pose % 64 == 0 && (tiles + 1023) / 1024 <= 512;
     auto bail = [&](int rc) { (void)lrc_pipe_destroy(pp); return rc; };
     auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
-    // a record set: t | prim | normal3 | point3 | sem | ins | tile_count, 36 B per ray + 4 B per 64 rays
+    // a record set: t | prim | normal3 | point3 | sem | ins | tile_count, 36 B per ray + 4 B per 64 rays, and for a fused
+    // pipeline beside it the lean form row | aux | keep_mask, 24 B per ray + 8 B per 64 rays
     const uint64_t off_t = 0, off_prim = off_t + up(4 * n), off_nrm = off_prim + up(4 * n), off_pt = off_nrm + up(12 * n),
                    off_sem = off_pt + up(12 * n), off_ins = off_sem + up(2 * n), off_tc = off_ins + up(2 * n),
-                   bytes = off_tc + up(4 * ((n + 63) / 64));
+                   off_row = off_tc + up(4 * ((n + 63) / 64)), off_aux = off_row + (pp->fused ? up(16 * n) : 0),
+                   off_km = off_aux + (pp->fused ? up(8 * n) : 0), bytes = off_km + (pp->fused ? up(8 * ((n + 63) / 64)) : 0);
     for (int k = 0; k < lrc_pipe::kSets; ++k) {
         hipError_t e = hipMalloc(&pp->slab[k], bytes);
         if (e != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory for the record sets")); }
@@ -2453,6 +2602,9 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
         h.t = (float*)(b + off_t); h.prim = (uint32_t*)(b + off_prim); h.normal3 = (float*)(b + off_nrm);
         h.point3 = (float*)(b + off_pt); h.sem = (uint16_t*)(b + off_sem); h.ins = (uint16_t*)(b + off_ins);
         h.tile_count = (uint32_t*)(b + off_tc);
+        if (pp->fused) {
+            pp->row[k] = (float4*)(b + off_row); pp->aux[k] = (uint2*)(b + off_aux); pp->keep_mask[k] = (uint64_t*)(b + off_km);
+        }
     }
     // The two trace streams must reach the hardware on queues of their own, or their launches cannot overlap.  The runtime
     // shares a bounded pool of hardware queues per stream priority among all of the process's streams (GPU_MAX_HW_QUEUES,
@@ -2472,6 +2624,7 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
             hipEventCreate(&pp->ev_t0[k]) != hipSuccess || hipEventCreate(&pp->ev_trace[k]) != hipSuccess)
             return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
     }
+    if (hipEventCreateWithFlags(&pp->ev_expand, hipEventDisableTiming) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
     *out_pipe = pp;
     return LRC_OK;
 }
@@ -2483,6 +2636,11 @@ lrc_compact_io pipe_io(const lrc_pipe* pp, int set) {
     const lrc_hits& h = pp->rec[set];
     io.t = h.t; io.point3 = h.point3; io.sem = h.sem; io.ins = h.ins; io.incident_deg = nullptr; io.tile_count = h.tile_count;
     return io;
+}
+// ... and its lean form (row == NULL: the set holds complete records)
+LeanIn pipe_lean(const lrc_pipe* pp, int set) {
+    if (!pp->lean[set]) return LeanIn{nullptr, nullptr};
+    return LeanIn{pp->row[set], pp->keep_mask[set]};
 }
 }  // namespace
 
@@ -2510,6 +2668,9 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     p.has_center = 1;
     p.max_range = max_range;
     p.out = pp->rec[set];
+    if (pp->fused) {           // the lean form: only what the scatter reads (the plain fallback below reads the full record)
+        p.lean.row = pp->row[set]; p.lean.aux = pp->aux[set]; p.lean.keep_mask = pp->keep_mask[set];
+    }
     // the rows of submit k - 2 (this stream's previous scan; its scan pass was enqueued behind its trace) ride in front
     const int prev = (int)((k + lrc_pipe::kSets - 2) % lrc_pipe::kSets);
     lrc_compact_io pio{};
@@ -2524,6 +2685,7 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
         p.pre.tile_off = pp->scratch[lane].d_tile_off;
         p.pre.super_total = pp->scratch[lane].d_super_total;
         p.pre.io = pio;
+        p.pre.lean = pipe_lean(pp, prev);
     }
     LRC_HIP(hipEventRecord(pp->ev_t0[set], T));
     int rc = launch_trace(s, p, 1, T);
@@ -2532,6 +2694,8 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     if (p.pre.blocks) pp->pending[prev] = false;
     pp->out[set] = *d_out;
     pp->poses[set] = P;
+    pp->lean[set] = p.lean.row != nullptr;
+    pp->expanded[set] = false;
     if (pp->fused) {
         // the scan pass over this scan's per-wave keep counts: 32-64 one-wave workgroups behind the trace; the rows follow
         // with this stream's next launch (or with lrc_pipe_wait)
@@ -2570,6 +2734,7 @@ int check_gathered(const lrc_pipe* pp, const lrc_gathered* g, const char* who) {
     if (g->slab_stride_bytes % 4 || g->slab_stride_bytes < g->poses_per_slab * pp->rays_per_pose * 4) return bad("slab stride smaller than a slab");
     if (g->own_ticket == 0 || g->own_ticket > pp->ticket || pp->ticket - g->own_ticket >= (uint64_t)lrc_pipe::kSets)
         return bad("the own records of that scan are gone (four sets rotate): assemble within three submits");
+    if (pp->lean[(g->own_ticket - 1) % lrc_pipe::kSets]) return bad("own_ticket is not a submit of lrc_pipe_submit_sharded");
     const uint64_t ntiles = g->num_poses_all * (pp->rays_per_pose / 64);
     if (ntiles > 0x7FFFFFFFull) return bad("too many entries");
     return LRC_OK;
@@ -2675,6 +2840,8 @@ int lrc_pipe_submit_sharded(lrc_pipe* pp, const double* d_poses16, uint64_t P, c
     LRC_HIP(hipEventRecord(pp->ev_trace[set], T));
     pp->out[set] = lrc_compact_io{};
     pp->poses[set] = P;
+    pp->lean[set] = false;                     // the complete record (its id column is the send slab)
+    pp->expanded[set] = false;
     pp->pending[set] = false;                  // nothing local to scatter: the rows appear when the gathered scan is assembled
     pp->ticket = k + 1;
     if (out_ticket) *out_ticket = k + 1;
@@ -2740,9 +2907,15 @@ int lrc_pipe_wait(lrc_pipe* pp, void* stream) {
         const uint64_t N = pp->rays_per_pose, tps = N / 64, ntiles = pp->poses[set] * tps;
         const uint64_t nblocks = (ntiles + kBlock / 64 - 1) / (kBlock / 64);
         const uint64_t need = io.counts ? (pp->poses[set] + kBlock - 1) / kBlock : 0;
-        hipLaunchKernelGGL(compact_scatter_kernel, dim3((uint32_t)(nblocks > need ? nblocks : need)), dim3(kBlock), 0, pp->s_trace[lane],
-                           io, N, tps, ntiles, pp->poses[set], (const uint32_t*)pp->scratch[lane].d_tile_off,
-                           (const uint64_t*)nullptr, (uint64_t)0, (const uint32_t*)pp->scratch[lane].d_super_total);
+        const dim3 grid((uint32_t)(nblocks > need ? nblocks : need));
+        if (pp->lean[set])
+            hipLaunchKernelGGL(compact_scatter_lean_kernel, grid, dim3(kBlock), 0, pp->s_trace[lane], io, pipe_lean(pp, set), N, tps,
+                               ntiles, pp->poses[set], (const uint32_t*)pp->scratch[lane].d_tile_off,
+                               (const uint32_t*)pp->scratch[lane].d_super_total);
+        else
+            hipLaunchKernelGGL(compact_scatter_kernel, grid, dim3(kBlock), 0, pp->s_trace[lane],
+                               io, N, tps, ntiles, pp->poses[set], (const uint32_t*)pp->scratch[lane].d_tile_off,
+                               (const uint64_t*)nullptr, (uint64_t)0, (const uint32_t*)pp->scratch[lane].d_super_total);
         LRC_HIP(hipGetLastError());
         pp->pending[set] = false;
     }
@@ -2753,11 +2926,28 @@ int lrc_pipe_wait(lrc_pipe* pp, void* stream) {
     return LRC_OK;
 }
 
+// the complete 36-byte records of a submit (a verification surface: bench.py and the pipeline never read them).  A lean set is
+// expanded into its full arrays once per submit, behind its trace, and the host waits as lrc_pipe_trace_ms does.
 int lrc_pipe_records(lrc_pipe* pp, uint64_t ticket, lrc_hits* out_records) {
     if (!pp || !out_records) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_records: NULL argument");
     if (ticket == 0 || ticket > pp->ticket || pp->ticket - ticket >= (uint64_t)lrc_pipe::kSets)
         return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_records: the records of that submit are gone (four sets rotate)");
-    *out_records = pp->rec[(ticket - 1) % lrc_pipe::kSets];
+    const int set = (int)((ticket - 1) % lrc_pipe::kSets);
+    if (pp->lean[set] && !pp->expanded[set]) {
+        // a lean set: rebuild the complete records on the set's trace stream behind its trace, and wait for them
+        lrc_scene* s = pp->scene;
+        LRC_HIP(hipSetDevice(s->ctx->device));
+        hipStream_t T = pp->s_trace[(ticket - 1) % 2];
+        const uint64_t n = pp->poses[set] * pp->rays_per_pose;
+        hipLaunchKernelGGL(expand_lean_kernel, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, T,
+                           (const float4*)pp->row[set], (const uint2*)pp->aux[set], (const uint32_t*)s->d_slot_prim,
+                           (const float4*)s->d_tris, pp->rec[set], n);
+        LRC_HIP(hipGetLastError());
+        LRC_HIP(hipEventRecord(pp->ev_expand, T));
+        LRC_HIP(hipEventSynchronize(pp->ev_expand));
+        pp->expanded[set] = true;
+    }
+    *out_records = pp->rec[set];
     return LRC_OK;
 }
 

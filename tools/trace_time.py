@@ -48,6 +48,7 @@ for a, b in ev:
     b.record()
 torch.cuda.synchronize()
 ms = sorted(a.elapsed_time(b) for a, b in ev)
-chk = int(hits["prim"].to(torch.int64).sum().item())
+# checksum over the triangle ids, or over the t bits when the record set carries no ids (LRC_TT_WANT without prim)
+chk = int((hits["prim"] if "prim" in want else hits["t"].view(torch.int32)).to(torch.int64).sum().item())
 print(f"{'packet ' if grid else ''}{scene_name} {lines}x{width} x{P}: {n} rays, median {ms[len(ms)//2]:.4f} ms, min {ms[0]:.4f} ms, "
       f"{n / ms[len(ms)//2] / 1e6:.2f} G rays/s, checksum {chk}")
