@@ -588,6 +588,49 @@ int lrc_instance_boxes_dev(lrc_ctx* ctx, const float* d_xyzl, uint64_t num_rows,
                            lrc_box* out_boxes, uint64_t capacity, uint64_t* out_num_boxes,
                            double* d_out_avg /* nullable */, uint8_t* d_out_keep /* nullable */, void* stream);
 
+/* ---- cloud preprocessing ----------------------------------------------------------------------------
+ * The reference's preprocessing stage (s3dis_data_loader.py:85-158): Open3D's remove_statistical_outlier over a whole
+ * float64 room cloud, then estimate_normals with a hybrid (radius, max_nn) search on the kept rows, in one call.
+ *   avg      : per input row, (sum of the square roots of the min(nb_neighbors, n) smallest float64 squared distances
+ *              (dx*dx + dy*dy) + dz*dz to the rows of the cloud, itself included, ascending, one after the other) /
+ *              min(nb_neighbors, n).
+ *   filter   : mean = sum_{avg>0} avg / n, std = sqrt(sum_{avg>0} (avg - mean)^2 / (n - 1)), threshold = mean +
+ *              std_ratio * std, both reduced in an order fixed by n; a row is kept iff avg > 0 && avg < threshold
+ *              (nb_neighbors or more coincident rows all go; n == 1 keeps nothing).  Kept rows are listed in
+ *              ascending row order (Open3D's `ind`).  remove_outliers == 0 keeps every row (avg = -1, mean = 0,
+ *              threshold = +inf).
+ *   normals  : per kept row, in kept order.  Neighbours are the kept rows with d2 < radius^2 (strict), itself
+ *              included, ordered by (d2, kept index), the first max_nn of them; nn_count is their number.  Fewer than
+ *              3 give (0, 0, 1).  Otherwise Open3D's nine cumulants are summed in neighbour order and divided by the
+ *              count, cov = E[x x^T] - E[x] E[x]^T, and the normal is the unit eigenvector of the smallest eigenvalue
+ *              from the closed-form robust symmetric 3x3 solver (Eberly; Open3D's fast_normal_computation path); a
+ *              zero covariance gives (0, 0, 1).  The sign is the solver's: no orientation is applied.
+ * 1 <= nb_neighbors <= 32 and 1 <= max_nn <= 32 (the lists live in registers; the reference uses 20 and 30), finite
+ * std_ratio > 0 and radius > 0, n < 2^31; a non-finite coordinate fails with LRC_ERR_INVALID_ARG.  cell_size <= 0
+ * picks the grid spacing (about max(nb_neighbors, max_nn) rows per cell); no result depends on it.
+ * out_kept needs n entries; out_normals3 (3 per kept row) is required when estimate_normals != 0; out_avg (n
+ * entries), out_nn_count (one per kept row) and out_stats2 (mean, threshold; HOST memory in both entry points) are
+ * optional.  *out_num_kept is HOST memory; lrc_cloud_preprocess_dev returns after the work it enqueued on `stream`
+ * has finished. */
+typedef struct lrc_preprocess_opts {
+    uint32_t remove_outliers;    /* 1: statistical outlier filter                                      */
+    uint32_t nb_neighbors;       /* k of the filter                                                    */
+    double   std_ratio;
+    uint32_t estimate_normals;   /* 1: PCA normals of the kept rows                                    */
+    uint32_t max_nn;             /* neighbour cap of the hybrid search                                 */
+    double   radius;             /* search radius of the hybrid search                                 */
+    double   cell_size;          /* <= 0: automatic                                                    */
+} lrc_preprocess_opts;           /* 40 bytes */
+
+int lrc_cloud_preprocess(lrc_ctx* ctx, const double* points3, uint64_t n, const lrc_preprocess_opts* opts,
+                         uint32_t* out_kept, uint64_t* out_num_kept, double* out_normals3 /* nullable */,
+                         double* out_avg /* nullable */, uint8_t* out_nn_count /* nullable */,
+                         double* out_stats2 /* nullable */);
+int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, const lrc_preprocess_opts* opts,
+                             uint32_t* d_out_kept, uint64_t* out_num_kept, double* d_out_normals3 /* nullable */,
+                             double* d_out_avg /* nullable */, uint8_t* d_out_nn_count /* nullable */,
+                             double* out_stats2 /* nullable */, void* stream);
+
 /* ---- robot-cube occupancy for the trajectory planner ----------------
  * out_flags[q] = 1 iff some mesh vertex lies inside the axis-aligned cube [p_q - half, p_q + half] (float64,
  * inclusive), for all Q positions at once.  Replaces AutoTrajectoryGenerator._is_point_inside_mesh

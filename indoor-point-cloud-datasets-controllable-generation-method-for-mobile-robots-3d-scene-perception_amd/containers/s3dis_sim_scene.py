@@ -328,17 +328,9 @@ class S3DISSimScene:
                 cols.append(np.tile(_viridis(i / len(self.frames)), (len(frame.points), 1)))
         if not parts:
             return
-        pts = np.vstack(parts).astype(np.float64)
-        rgb = np.clip(np.vstack(cols) * 255.0, 0, 255).astype(np.uint8)
-        rec = np.empty(len(pts), dtype=np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"),
-                                                 ("red", "u1"), ("green", "u1"), ("blue", "u1")]))
-        rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
-        rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
-        with open(Path(output_dir) / "combined_pointcloud.ply", "wb") as f:
-            f.write(b"ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty double x\n"
-                    b"property double y\nproperty double z\nproperty uchar red\nproperty uchar green\n"
-                    b"property uchar blue\nend_header\n" % len(pts))
-            rec.tofile(f)
+        from lidarcast.ply import write_point_cloud
+        write_point_cloud(Path(output_dir) / "combined_pointcloud.ply", np.vstack(parts).astype(np.float64),
+                          colors=np.vstack(cols))
 
     def _export_combined_pointcloud_with_labels(self, output_dir: Path):
         """combined_pointcloud_with_label.ply: np.vstack of the non-empty frames with colour, semantic and instance

@@ -3,9 +3,12 @@ from ._capi import LIB_PATH, LRC_INVALID_PRIM, LidarcastError, load
 from .core import (ATTRS, FRAME_ATTRS, Context, DeviceHits, DirectionTable, NearestIndex, OccupancyIndex, PinnedPool, ScanPipe, Scene,
                    bake_triangle_labels)
 from .boxes import BOX_DTYPE, instance_boxes, instance_boxes_dev
+from .preprocess import (Preprocessed, estimate_normals, preprocess_cloud, preprocess_cloud_dev,
+                         remove_statistical_outlier)
 
 __all__ = ["LIB_PATH", "LRC_INVALID_PRIM", "LidarcastError", "load", "ATTRS", "Context",
-           "DeviceHits", "DirectionTable", "Scene", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "BOX_DTYPE", "instance_boxes", "instance_boxes_dev", "version",
+           "DeviceHits", "DirectionTable", "Scene", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "BOX_DTYPE", "instance_boxes", "instance_boxes_dev",
+           "Preprocessed", "preprocess_cloud", "preprocess_cloud_dev", "remove_statistical_outlier", "estimate_normals", "version",
            "device_count"]
 
 

@@ -38,6 +38,7 @@ SYMBOLS = (
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
     "lrc_min_distances", "lrc_rbf_kernel_sum",
     "lrc_instance_boxes", "lrc_instance_boxes_dev",
+    "lrc_cloud_preprocess", "lrc_cloud_preprocess_dev",
     "lrc_occ_create", "lrc_occ_destroy", "lrc_occ_query",
     "lrc_rng_scan_draws", "lrc_rays_from_trig",
 )
@@ -91,6 +92,12 @@ class LrcBox(C.Structure):
     _fields_ = [("sem", C.c_uint16), ("ins", C.c_uint16), ("num_points", C.c_uint32), ("num_kept", C.c_uint32),
                 ("filtered", C.c_uint32), ("min3", C.c_float * 3), ("max3", C.c_float * 3), ("mean", C.c_double),
                 ("threshold", C.c_double)]
+
+
+class LrcPreprocessOpts(C.Structure):
+    _fields_ = [("remove_outliers", C.c_uint32), ("nb_neighbors", C.c_uint32), ("std_ratio", C.c_double),
+                ("estimate_normals", C.c_uint32), ("max_nn", C.c_uint32), ("radius", C.c_double),
+                ("cell_size", C.c_double)]
 
 
 class LrcMt19937State(C.Structure):
@@ -202,6 +209,8 @@ def load():
                                C.POINTER(u64), vp, vp],
         "lrc_instance_boxes_dev": [vp, vp, u64, vp, C.c_uint32, C.c_uint32, C.c_uint32, dbl, dbl, vp, u64,
                                    C.POINTER(u64), vp, vp, vp],
+        "lrc_cloud_preprocess": [vp, vp, u64, C.POINTER(LrcPreprocessOpts), vp, C.POINTER(u64), vp, vp, vp, vp],
+        "lrc_cloud_preprocess_dev": [vp, vp, u64, C.POINTER(LrcPreprocessOpts), vp, C.POINTER(u64), vp, vp, vp, vp, vp],
         "lrc_nn_create": [vp, vp, u64, dbl, C.POINTER(vp)],
         "lrc_nn_destroy": [vp],
         "lrc_nn_query": [vp, vp, u64, vp, vp],

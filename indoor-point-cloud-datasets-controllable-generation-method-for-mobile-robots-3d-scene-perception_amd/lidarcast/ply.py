@@ -107,3 +107,65 @@ def read_point_cloud(path) -> np.ndarray:
         dt = np.dtype([(p[-1], "<" + _T[p[0]]) for p in props])
         a = np.fromfile(f, dtype=dt, count=count)
         return np.stack([a["x"], a["y"], a["z"]], 1).astype(np.float64)
+
+
+def write_point_cloud(path, points, colors=None, normals=None):
+    """Binary little-endian PLY of a point cloud in the layout Open3D writes for a PointCloud: double x y z, then double
+    nx ny nz when there are normals, then uchar red green blue when there are colours (float colours in [0, 1],
+    converted by clip(c * 255, 0, 255) and truncation).  Stands in for o3d.io.write_point_cloud (reference
+    s3dis_data_loader.py:659-702); read_point_cloud reads it back."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
+    if normals is not None:
+        nrm = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+        if len(nrm) != len(pts):
+            raise ValueError("normals must have one row per point")
+        fields += [("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
+    if colors is not None:
+        rgb = np.clip(np.asarray(colors, dtype=np.float64).reshape(-1, 3) * 255.0, 0, 255).astype(np.uint8)
+        if len(rgb) != len(pts):
+            raise ValueError("colors must have one row per point")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    rec = np.empty(len(pts), dtype=np.dtype(fields))
+    rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    if normals is not None:
+        rec["nx"], rec["ny"], rec["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+    if colors is not None:
+        rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(pts)]
+    header += ["property %s %s" % ("double" if t == "<f8" else "uchar", name) for name, t in fields]
+    header += ["end_header", ""]
+    with open(path, "wb") as f:
+        f.write("\n".join(header).encode("ascii"))
+        rec.tofile(f)
+
+
+def read_point_cloud_attributes(path):
+    """dict of the vertex properties of a binary little-endian point-cloud PLY: points (N,3) float64, and normals (N,3)
+    float64 / colors (N,3) uint8 when the file has them."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("not a PLY file")
+        fmt, count, props = None, 0, []
+        while True:
+            tok = f.readline().decode("ascii", "replace").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element" and tok[1] == "vertex":
+                count = int(tok[2])
+            elif tok[0] == "property":
+                props.append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"unsupported PLY format {fmt}")
+        a = np.fromfile(f, dtype=np.dtype([(p[-1], "<" + _T[p[0]]) for p in props]), count=count)
+    out = {"points": np.stack([a["x"], a["y"], a["z"]], 1).astype(np.float64)}
+    names = a.dtype.names
+    if "nx" in names:
+        out["normals"] = np.stack([a["nx"], a["ny"], a["nz"]], 1).astype(np.float64)
+    if "red" in names:
+        out["colors"] = np.stack([a["red"], a["green"], a["blue"]], 1)
+    return out

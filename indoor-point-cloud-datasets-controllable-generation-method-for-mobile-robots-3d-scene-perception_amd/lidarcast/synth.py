@@ -207,3 +207,57 @@ def quad(z=2.0, half=1.0):
     """Two triangles forming the square |x|,|y| <= half in the plane z."""
     v = np.array([[-half, -half, z], [half, -half, z], [half, half, z], [-half, half, z]], dtype=np.float64)
     return TriangleMesh(vertices=v, triangles=np.array([[0, 1, 2], [0, 2, 3]], dtype=np.int32))
+
+
+# colour per S3DIS class id of make_room's triangles (0 ceiling, 1 floor, 2 wall, 7 table, 8 chair, 10 bookcase)
+_ROOM_RGB = {0: (231, 229, 222), 1: (142, 128, 110), 2: (205, 201, 190), 7: (120, 84, 52), 8: (60, 62, 70),
+             10: (170, 132, 90)}
+
+
+def sample_s3dis_room(mesh=None, density=15000.0, num_points=None, num_outliers=300, seed=0):
+    """An S3DIS-like room scan sampled from a synthetic mesh (make_room() when None): area-uniform points on the
+    triangles at `density` points per square metre (or exactly `num_points`), coordinates rounded to 3 decimals as in
+    the S3DIS text files (which gives coincident rows and distance ties), uint8-valued colours from the triangle's
+    class with a little per-point noise, the triangle's semantic id as label, plus `num_outliers` rows scattered
+    uniformly through the room's box (off the surfaces).  Returns (points float64 (N,3), colors float64 (N,3) in
+    0..255, labels int64 (N,)).  Deterministic in `seed`."""
+    if mesh is None:
+        mesh = make_room()
+    rng = np.random.default_rng(seed)
+    v = np.asarray(mesh.vertices, np.float64)
+    t = np.asarray(mesh.triangles, np.int64)
+    a, b, c = v[t[:, 0]], v[t[:, 1]], v[t[:, 2]]
+    area = 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
+    n = int(num_points) if num_points is not None else int(round(area.sum() * density))
+    tri = np.searchsorted(np.cumsum(area) / area.sum(), rng.random(n), side="right").clip(0, len(t) - 1)
+    u, w = rng.random(n), rng.random(n)
+    flip = u + w > 1.0
+    u[flip], w[flip] = 1.0 - u[flip], 1.0 - w[flip]
+    pts = a[tri] + u[:, None] * (b[tri] - a[tri]) + w[:, None] * (c[tri] - a[tri])
+    sem = (np.asarray(mesh.triangle_sem, np.int64)[tri] if mesh.triangle_sem is not None
+           else np.zeros(n, np.int64))
+    lo, hi = v.min(0), v.max(0)
+    out = lo + rng.random((int(num_outliers), 3)) * (hi - lo)
+    pts = np.round(np.vstack([pts, out]), 3)
+    labels = np.concatenate([sem, np.full(int(num_outliers), 12, np.int64)])      # 12: clutter
+    base = np.array([_ROOM_RGB.get(int(s), (128, 128, 128)) for s in range(max(_ROOM_RGB) + 1)], np.float64)
+    rgb = np.where(labels[:, None] <= max(_ROOM_RGB), base[np.minimum(labels, max(_ROOM_RGB))], 128.0)
+    rgb = np.clip(np.round(rgb + rng.normal(0.0, 6.0, rgb.shape)), 0, 255)
+    perm = rng.permutation(len(pts))                 # S3DIS rows are not sorted by surface
+    return pts[perm], rgb[perm], labels[perm]
+
+
+def write_s3dis_room(root, area_name, room_name, points, colors, labels=None):
+    """<root>/<area_name>/<room_name>/<room_name>.txt in the S3DIS text layout: x y z r g b [label] per row, coordinates
+    with 3 decimals, colours and labels as integers.  Returns the file's path."""
+    import os
+    d = os.path.join(str(root), area_name, room_name)
+    os.makedirs(d, exist_ok=True)
+    path = os.path.join(d, f"{room_name}.txt")
+    cols = [np.asarray(points, np.float64), np.asarray(colors, np.float64)]
+    fmt = "%.3f %.3f %.3f %d %d %d"
+    if labels is not None:
+        cols.append(np.asarray(labels, np.float64).reshape(-1, 1))
+        fmt += " %d"
+    np.savetxt(path, np.hstack(cols), fmt=fmt)
+    return path
