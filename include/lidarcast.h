@@ -631,6 +631,44 @@ int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, 
                              double* d_out_avg /* nullable */, uint8_t* d_out_nn_count /* nullable */,
                              double* out_stats2 /* nullable */, void* stream);
 
+/* ---- object boxes -----------------------------------------------------------------------------------
+ * The reference's ground-truth boxes of S3DIS rooms (s3dis_bbox_visualizer.py:70-116): per Annotations/<class>_<k>.txt
+ * object, Open3D's remove_statistical_outlier(nb_neighbors=k, std_ratio) on float64 points and the min / max of the
+ * kept rows; every object of a room or of an area in one call, with a number of launches and host synchronisations
+ * that does not depend on the number of objects.  Objects are runs of the concatenated rows: object s is rows
+ * [offsets[s], offsets[s+1]) (num_objects + 1 HOST entries, offsets[0] == 0, offsets[num_objects] == n, never
+ * decreasing; empty objects are allowed).
+ *   m < k    : no filter (the reference returns such points as they are): every row is kept, avg = -1, mean = 0,
+ *              threshold = +inf, filtered = 0.
+ *   m >= k   : exactly the outlier stage of lrc_cloud_preprocess(nb_neighbors = k, std_ratio) run on the object's rows
+ *              alone, bit for bit: neighbours come only from the same object, avg = (sum of the square roots of the k
+ *              smallest float64 squared distances (dx*dx + dy*dy) + dz*dz, itself included, ascending) / k, mean and
+ *              std reduced in the order lrc_cloud_preprocess fixes for m rows, keep = avg > 0 && avg < threshold.
+ * One lrc_objbox per object, in object order (HOST memory in both entry points).  The optional per-row outputs: out_kept
+ * (n entries; the kept rows' indices, ascending, so object s's kept rows start at the sum of num_kept over the objects
+ * before it), avg and keep (n entries, input order).  1 <= k <= 32, finite std_ratio > 0, n < 2^31 and num_objects <
+ * 2^31, checked on the host before any launch; a non-finite coordinate fails with LRC_ERR_INVALID_ARG.  cell_size <= 0
+ * picks a grid spacing per object (about k rows per cell); no result depends on it.  lrc_object_boxes_dev takes device
+ * points and device per-row outputs and returns after the work it enqueued on `stream` has finished. */
+typedef struct lrc_objbox {
+    uint64_t num_points;     /* rows of the object                                                  */
+    uint64_t num_kept;       /* rows inside the box (0: the filter removed all; min3 = +inf, max3 = -inf) */
+    uint32_t filtered;       /* 1: num_points >= k and the filter ran; 0: every row kept             */
+    uint32_t reserved_;
+    double   min3[3];        /* float64 minimum of the kept rows                                   */
+    double   max3[3];
+    double   mean;           /* filter statistics; 0 and +inf when filtered == 0                    */
+    double   threshold;
+} lrc_objbox;                /* 88 bytes */
+
+int lrc_object_boxes(lrc_ctx* ctx, const double* points3, uint64_t n, const uint64_t* offsets, uint64_t num_objects,
+                     uint32_t k, double std_ratio, double cell_size, lrc_objbox* out_boxes,
+                     uint32_t* out_kept /* nullable */, double* out_avg /* nullable */, uint8_t* out_keep /* nullable */);
+int lrc_object_boxes_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, const uint64_t* offsets, uint64_t num_objects,
+                         uint32_t k, double std_ratio, double cell_size, lrc_objbox* out_boxes,
+                         uint32_t* d_out_kept /* nullable */, double* d_out_avg /* nullable */,
+                         uint8_t* d_out_keep /* nullable */, void* stream);
+
 /* ---- robot-cube occupancy for the trajectory planner ----------------
  * out_flags[q] = 1 iff some mesh vertex lies inside the axis-aligned cube [p_q - half, p_q + half] (float64,
  * inclusive), for all Q positions at once.  Replaces AutoTrajectoryGenerator._is_point_inside_mesh

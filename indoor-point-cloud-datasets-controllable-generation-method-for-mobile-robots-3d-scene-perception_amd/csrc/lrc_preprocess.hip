@@ -32,52 +32,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lidarcast.h"
+#include "lrc_knn64.h"
 
-extern "C" int lrc_internal_fail(int code, const char* msg);     // lidarcast.hip: sets lrc_last_error()
 extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
 
 namespace {
 
-#define PP_HIP(call)                                                                            \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
-
-constexpr int kBlock = 256;
-constexpr int kRedBlocks = 256;        // chunks of the fixed-order reductions (bounds, mean, std)
 constexpr uint32_t kTie = 0x80000000u; // walk B key bit: d2 == D (indices are < 2^31)
-
-struct Grid {
-    double lo[3];
-    double h, inv_h;
-    int n[3];
-};
-
-// a row in cell order: coordinates and its index in the set the grid was built over
-struct alignas(16) SPt {
-    double x, y, z;
-    uint32_t idx, pad;
-};
-
-__device__ __forceinline__ int cell_of(double x, double lo, double inv_h, int n) {
-    const double f = floor((x - lo) * inv_h);
-    return f < 0.0 ? 0 : (f >= (double)n ? n - 1 : (int)f);
-}
-
-// exponent bits all ones: inf or nan.  The test runs on the integer bits as loaded, never on a double: the device code
-// is built with -fno-honor-nans, and a class test on a double value may be folded to "never nan".
-__device__ __forceinline__ bool non_finite_bits(uint64_t b) { return (b << 1) >= (0xFFEull << 52); }
-
-__device__ __forceinline__ double sq3(double qx, double qy, double qz, double px, double py, double pz) {
-    const double dx = qx - px, dy = qy - py, dz = qz - pz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
 
 // per-block float64 bounds and a non-finite flag; the host folds the blocks (min / max: order-free)
 __global__ __launch_bounds__(kBlock) void pp_bounds_kernel(const double* __restrict__ p, uint64_t n,
@@ -136,40 +97,6 @@ __global__ __launch_bounds__(kBlock) void pp_gather_kernel(const double* __restr
     pts[j] = s;
 }
 
-// rows m of the cells on the surface of the cube of cells [c-r, c+r]^3, clipped to the grid; the statement that follows
-// is the body.  On a z- or y-face of the shell the whole x-run belongs to it; otherwise only its two ends.  (A macro,
-// not a function taking a lambda: a list captured by reference would be kept in scratch.)
-#define PP_SHELL_CELL(x, y, z) (((uint32_t)(z) * (uint32_t)g.n[1] + (uint32_t)(y)) * (uint32_t)g.n[0] + (uint32_t)(x))
-#define PP_FOR_SHELL_ROWS(m)                                                                                        \
-    for (int z = max(cz - r, 0), z1_ = min(cz + r, g.n[2] - 1); z <= z1_; ++z)                                      \
-        for (int y = max(cy - r, 0), y1_ = min(cy + r, g.n[1] - 1); y <= y1_; ++y)                                  \
-            for (int x = cx - r, step_ = ((z == cz - r) | (z == cz + r) | (y == cy - r) | (y == cy + r)) ? 1 : max(2 * r, 1); \
-                 x <= cx + r; x += step_)                                                                           \
-                if (x >= 0 && x < g.n[0])                                                                           \
-                    for (uint32_t m = start[PP_SHELL_CELL(x, y, z)], e_ = start[PP_SHELL_CELL(x, y, z) + 1]; m < e_; ++m)
-
-// everything inside the cube of cells [c-r, c+r]^3 has been searched: a row outside it lies farther from q than this
-// (the distance to the nearest face, shrunk by 1e-6 cell: a row binned by floor((p-lo)/h) may sit one rounding below
-// its cell's edge)
-__device__ __forceinline__ double cube_margin(const Grid& g, double qx, double qy, double qz, int cx, int cy, int cz, int r) {
-    const double mx = fmin(qx - (g.lo[0] + (double)(cx - r) * g.h), (g.lo[0] + (double)(cx + r + 1) * g.h) - qx);
-    const double my = fmin(qy - (g.lo[1] + (double)(cy - r) * g.h), (g.lo[1] + (double)(cy + r + 1) * g.h) - qy);
-    const double mz = fmin(qz - (g.lo[2] + (double)(cz - r) * g.h), (g.lo[2] + (double)(cz + r + 1) * g.h) - qz);
-    return fmin(mx, fmin(my, mz)) - 1.0e-6 * g.h;
-}
-
-// insert v into the ascending list best[0..KC): compile-time indices only
-template <int KC, class T>
-__device__ __forceinline__ void insert_sorted(T (&best)[KC], T v) {
-    if (!(v < best[KC - 1])) return;
-#pragma unroll
-    for (int j = KC - 1; j > 0; --j) {
-        const T prev = best[j - 1];
-        best[j] = v < prev ? prev : (v < best[j] ? v : best[j]);
-    }
-    best[0] = v < best[0] ? v : best[0];
-}
-
 // ---- 2. outlier filter ----------------------------------------------------------------------------------------------
 
 template <int KC>
@@ -178,45 +105,8 @@ __global__ __launch_bounds__(kBlock) void pp_knn_kernel(const SPt* __restrict__ 
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const SPt q = pts[i];
-    const int cx = cell_of(q.x, g.lo[0], g.inv_h, g.n[0]);
-    const int cy = cell_of(q.y, g.lo[1], g.inv_h, g.n[1]);
-    const int cz = cell_of(q.z, g.lo[2], g.inv_h, g.n[2]);
-    // the k-best list is right-aligned in best[KC-k, KC): the slots below hold -inf and never move, so the k-th
-    // smallest is best[KC-1] and every index stays a compile-time constant (a run-time index would put the list in
-    // scratch)
-    double best[KC];
-#pragma unroll
-    for (int j = 0; j < KC; ++j) best[j] = j < KC - k ? -INFINITY : INFINITY;
-    const int rmax = max(max(max(cx, g.n[0] - 1 - cx), max(cy, g.n[1] - 1 - cy)), max(cz, g.n[2] - 1 - cz));
-    for (int r = 0; r <= rmax; ++r) {
-        PP_FOR_SHELL_ROWS(m) {
-            const SPt p = pts[m];
-            insert_sorted<KC>(best, sq3(q.x, q.y, q.z, p.x, p.y, p.z));
-        }
-        const double kth = best[KC - 1];
-        if (kth < INFINITY) {
-            const double margin = cube_margin(g, q.x, q.y, q.z, cx, cy, cz, r);
-            if (margin > 0.0 && kth <= margin * margin) break;
-        }
-    }
     const int found = (uint64_t)k < n ? k : (int)n;
-    double sum = 0.0;
-#pragma unroll
-    for (int j = 0; j < KC; ++j)
-        if (j >= KC - k && j < KC - k + found) sum += sqrt(best[j]);
-    avg[q.idx] = sum / (double)found;
-}
-
-__device__ double block_sum(double v, double* red) {
-    const uint32_t t = threadIdx.x;
-    __syncthreads();
-    red[t] = v;
-    __syncthreads();
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-        if (t < (uint32_t)w) red[t] += red[t + w];
-        __syncthreads();
-    }
-    return red[0];
+    avg[q.idx] = knn_avg<KC>(pts, g, start, q.x, q.y, q.z, k, found);
 }
 
 // kRedBlocks blocks, chunk b = rows [b*ceil(n/kRedBlocks), ...) in row order: sum_{avg>0} avg (stats == nullptr) or
@@ -226,15 +116,7 @@ __global__ __launch_bounds__(kBlock) void pp_sum_kernel(const double* __restrict
     __shared__ double red[kBlock];
     const uint64_t chunk = (n + kRedBlocks - 1) / kRedBlocks;
     const uint64_t a = (uint64_t)blockIdx.x * chunk, e = min(a + chunk, n);
-    const double mean = stats ? stats[0] : 0.0;
-    double acc = 0.0;
-    for (uint64_t j = a + threadIdx.x; j < e; j += kBlock) {
-        const double v = avg[j];
-        if (v > 0.0) {
-            if (stats) { const double d = v - mean; acc += d * d; }
-            else acc += v;
-        }
-    }
+    const double acc = chunk_partial(avg, a, e, stats);
     const double s = block_sum(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
@@ -545,30 +427,6 @@ hipError_t dispatch_normal(uint64_t m, hipStream_t st, const SPt* pts, const dou
     return launch_normal<32>(m, st, pts, pk, g, start, max_nn, radius, nbr, normals, nn);
 }
 
-int bit_width(uint64_t v) {
-    int b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// stream-ordered workspace: one block per phase, freed on every exit path
-struct Arena {
-    hipStream_t st;
-    std::vector<void*> blocks;
-    explicit Arena(hipStream_t s) : st(s) {}
-    ~Arena() {
-        for (void* p : blocks) (void)hipFreeAsync(p, st);
-    }
-    hipError_t get(size_t bytes, void** out) {
-        *out = nullptr;
-        hipError_t e = hipMallocAsync(out, bytes ? bytes : 256, st);
-        if (e == hipSuccess) blocks.push_back(*out);
-        return e;
-    }
-};
-
 // the rows of p (m of them) in cell order and the table of cell starts; LRC_ERR_INVALID_ARG for a non-finite coordinate
 int build_grid(const double* p, uint64_t m, double cell_size, int per_cell, hipStream_t st, Arena& arena, Grid* out_g,
                SPt** out_pts, uint32_t** out_start) {
@@ -577,18 +435,18 @@ int build_grid(const double* p, uint64_t m, double cell_size, int per_cell, hipS
     uint32_t* bad;
     {
         void* q;
-        PP_HIP(arena.get(align256(nb * 6 * 8) + 256, &q));
+        LRC64_HIP(arena.get(align256(nb * 6 * 8) + 256, &q));
         part = (double*)q;
         bad = (uint32_t*)((char*)q + align256(nb * 6 * 8));
     }
-    PP_HIP(hipMemsetAsync(bad, 0, 4, st));
+    LRC64_HIP(hipMemsetAsync(bad, 0, 4, st));
     hipLaunchKernelGGL(pp_bounds_kernel, dim3(nb), dim3(kBlock), 0, st, p, m, part, bad);
-    PP_HIP(hipGetLastError());
+    LRC64_HIP(hipGetLastError());
     std::vector<double> h_part((size_t)nb * 6);
     uint32_t h_bad = 0;
-    PP_HIP(hipMemcpyAsync(h_part.data(), part, h_part.size() * 8, hipMemcpyDeviceToHost, st));
-    PP_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
+    LRC64_HIP(hipMemcpyAsync(h_part.data(), part, h_part.size() * 8, hipMemcpyDeviceToHost, st));
+    LRC64_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
+    LRC64_HIP(hipStreamSynchronize(st));
     if (h_bad) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_cloud_preprocess: non-finite coordinate");
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (uint32_t b = 0; b < nb; ++b)
@@ -633,7 +491,7 @@ int build_grid(const double* p, uint64_t m, double cell_size, int per_cell, hipS
         const size_t sz = align256(m * 4), o_cnt = 4 * sz, o_start = o_cnt + align256((cells + 1) * 4),
                      o_pts = o_start + align256((cells + 1) * 4), total = o_pts + align256(m * sizeof(SPt));
         void* q;
-        PP_HIP(arena.get(total, &q));
+        LRC64_HIP(arena.get(total, &q));
         char* c = (char*)q;
         keys_a = (uint32_t*)c; keys_b = (uint32_t*)(c + sz); vals_a = (uint32_t*)(c + 2 * sz);
         vals_b = (uint32_t*)(c + 3 * sz); counts = (uint32_t*)(c + o_cnt); start = (uint32_t*)(c + o_start);
@@ -641,25 +499,23 @@ int build_grid(const double* p, uint64_t m, double cell_size, int per_cell, hipS
     }
     const uint32_t mblk = (uint32_t)((m + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(pp_key_kernel, dim3(mblk), dim3(kBlock), 0, st, p, m, g, keys_a, vals_a);
-    PP_HIP(hipGetLastError());
-    PP_HIP(hipMemsetAsync(counts, 0, (cells + 1) * 4, st));
+    LRC64_HIP(hipGetLastError());
+    LRC64_HIP(hipMemsetAsync(counts, 0, (cells + 1) * 4, st));
     const int end_bit = std::max(1, bit_width(cells));
     size_t tmp_sort = 0, tmp_scan = 0;
-    PP_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, end_bit, st));
-    PP_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, counts, start, 0u, (size_t)(cells + 1), rocprim::plus<uint32_t>(), st));
+    LRC64_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, end_bit, st));
+    LRC64_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, counts, start, 0u, (size_t)(cells + 1), rocprim::plus<uint32_t>(), st));
     void* tmp;
-    PP_HIP(arena.get(std::max(tmp_sort, tmp_scan), &tmp));
-    PP_HIP(rocprim::radix_sort_pairs(tmp, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, end_bit, st));
+    LRC64_HIP(arena.get(std::max(tmp_sort, tmp_scan), &tmp));
+    LRC64_HIP(rocprim::radix_sort_pairs(tmp, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, end_bit, st));
     hipLaunchKernelGGL(pp_gather_kernel, dim3(mblk), dim3(kBlock), 0, st, p, keys_b, vals_b, m, counts, pts);
-    PP_HIP(hipGetLastError());
-    PP_HIP(rocprim::exclusive_scan(tmp, tmp_scan, counts, start, 0u, (size_t)(cells + 1), rocprim::plus<uint32_t>(), st));
+    LRC64_HIP(hipGetLastError());
+    LRC64_HIP(rocprim::exclusive_scan(tmp, tmp_scan, counts, start, 0u, (size_t)(cells + 1), rocprim::plus<uint32_t>(), st));
     *out_g = g;
     *out_pts = pts;
     *out_start = start;
     return LRC_OK;
 }
-
-bool finite_positive(double v) { return v > 0.0 && v < INFINITY; }
 
 int check_opts(uint64_t n, const lrc_preprocess_opts* o) {
     if (n >= (1ull << 31)) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_cloud_preprocess: need n < 2^31");
@@ -692,7 +548,7 @@ int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, 
     if (out_stats2) { out_stats2[0] = 0.0; out_stats2[1] = INFINITY; }
     if (int rc = check_opts(n, opts)) return rc;
     if (n == 0) return LRC_OK;
-    PP_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC64_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
     const hipStream_t st = (hipStream_t)stream;
     Arena arena(st);
     const int per_cell = std::max(opts->remove_outliers ? (int)opts->nb_neighbors : 1,
@@ -715,39 +571,39 @@ int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, 
                          o_flag = o_stats + 256, o_pos = o_flag + align256(n * 4), o_pk = o_pos + align256(n * 4),
                          total = o_pk + (opts->estimate_normals ? align256(n * 24) : 0);
             void* q;
-            PP_HIP(arena.get(total, &q));
+            LRC64_HIP(arena.get(total, &q));
             char* c = (char*)q;
             avg = (double*)c; part = (double*)(c + o_part); stats = (double*)(c + o_stats);
             flag = (uint32_t*)(c + o_flag); pos = (uint32_t*)(c + o_pos); pkb = (double*)(c + o_pk);
         }
-        PP_HIP(dispatch_knn(n, st, pts, g, start, (int)opts->nb_neighbors, avg));
+        LRC64_HIP(dispatch_knn(n, st, pts, g, start, (int)opts->nb_neighbors, avg));
         hipLaunchKernelGGL(pp_sum_kernel, dim3(kRedBlocks), dim3(kBlock), 0, st, avg, n, (const double*)nullptr, part);
         hipLaunchKernelGGL(pp_final_kernel, dim3(1), dim3(kRedBlocks), 0, st, part, n, 0, opts->std_ratio, stats);
         hipLaunchKernelGGL(pp_sum_kernel, dim3(kRedBlocks), dim3(kBlock), 0, st, avg, n, (const double*)stats, part);
         hipLaunchKernelGGL(pp_final_kernel, dim3(1), dim3(kRedBlocks), 0, st, part, n, 1, opts->std_ratio, stats);
         hipLaunchKernelGGL(pp_keep_kernel, dim3(nblk), dim3(kBlock), 0, st, avg, n, stats, flag);
-        PP_HIP(hipGetLastError());
+        LRC64_HIP(hipGetLastError());
         size_t tmp_scan = 0;
-        PP_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        LRC64_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
         void* tmp;
-        PP_HIP(arena.get(tmp_scan, &tmp));
-        PP_HIP(rocprim::exclusive_scan(tmp, tmp_scan, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        LRC64_HIP(arena.get(tmp_scan, &tmp));
+        LRC64_HIP(rocprim::exclusive_scan(tmp, tmp_scan, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
         hipLaunchKernelGGL(pp_compact_kernel, dim3(nblk), dim3(kBlock), 0, st, d_points3, n, flag, pos, d_out_kept,
                            opts->estimate_normals ? pkb : nullptr);
-        PP_HIP(hipGetLastError());
-        if (d_out_avg) PP_HIP(hipMemcpyAsync(d_out_avg, avg, n * 8, hipMemcpyDeviceToDevice, st));
+        LRC64_HIP(hipGetLastError());
+        if (d_out_avg) LRC64_HIP(hipMemcpyAsync(d_out_avg, avg, n * 8, hipMemcpyDeviceToDevice, st));
         uint32_t last[2];
         double h_stats[2];
-        PP_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        PP_HIP(hipMemcpyAsync(&last[1], flag + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        PP_HIP(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, st));
-        PP_HIP(hipStreamSynchronize(st));
+        LRC64_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        LRC64_HIP(hipMemcpyAsync(&last[1], flag + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        LRC64_HIP(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, st));
+        LRC64_HIP(hipStreamSynchronize(st));
         m = (uint64_t)last[0] + last[1];
         if (out_stats2) { out_stats2[0] = h_stats[0]; out_stats2[1] = h_stats[1]; }
         pk = pkb;
     } else {
         hipLaunchKernelGGL(pp_fill_kernel, dim3(nblk), dim3(kBlock), 0, st, n, d_out_kept, d_out_avg);
-        PP_HIP(hipGetLastError());
+        LRC64_HIP(hipGetLastError());
     }
 
     if (opts->estimate_normals && m > 0) {
@@ -756,11 +612,11 @@ int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, 
             if (int rc = build_grid(pk, m, opts->cell_size, per_cell, st, arena, &g, &pts, &start)) return rc;
         }
         void* nbr;                                    // max_nn neighbour keys per kept row
-        PP_HIP(arena.get(m * opts->max_nn * 4, &nbr));
-        PP_HIP(dispatch_normal(m, st, pts, pk, g, start, (int)opts->max_nn, opts->radius, (uint32_t*)nbr, d_out_normals3,
+        LRC64_HIP(arena.get(m * opts->max_nn * 4, &nbr));
+        LRC64_HIP(dispatch_normal(m, st, pts, pk, g, start, (int)opts->max_nn, opts->radius, (uint32_t*)nbr, d_out_normals3,
                                d_out_nn_count));
     }
-    PP_HIP(hipStreamSynchronize(st));
+    LRC64_HIP(hipStreamSynchronize(st));
     *out_num_kept = m;
     return LRC_OK;
 }
@@ -774,7 +630,7 @@ int lrc_cloud_preprocess(lrc_ctx* ctx, const double* points3, uint64_t n, const 
     if (out_stats2) { out_stats2[0] = 0.0; out_stats2[1] = INFINITY; }
     if (int rc = check_opts(n, opts)) return rc;
     if (n == 0) return LRC_OK;
-    PP_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC64_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
     const bool normals = opts->estimate_normals != 0;
     double *d_p = nullptr, *d_normals = nullptr, *d_avg = nullptr;
     uint32_t* d_kept = nullptr;

@@ -5,10 +5,12 @@ from .core import (ATTRS, FRAME_ATTRS, Context, DeviceHits, DirectionTable, Near
 from .boxes import BOX_DTYPE, instance_boxes, instance_boxes_dev
 from .preprocess import (Preprocessed, estimate_normals, preprocess_cloud, preprocess_cloud_dev,
                          remove_statistical_outlier)
+from .objboxes import OBJBOX_DTYPE, ObjectBoxes, object_boxes, object_boxes_dev
 
 __all__ = ["LIB_PATH", "LRC_INVALID_PRIM", "LidarcastError", "load", "ATTRS", "Context",
            "DeviceHits", "DirectionTable", "Scene", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "BOX_DTYPE", "instance_boxes", "instance_boxes_dev",
-           "Preprocessed", "preprocess_cloud", "preprocess_cloud_dev", "remove_statistical_outlier", "estimate_normals", "version",
+           "Preprocessed", "preprocess_cloud", "preprocess_cloud_dev", "remove_statistical_outlier", "estimate_normals",
+           "OBJBOX_DTYPE", "ObjectBoxes", "object_boxes", "object_boxes_dev", "version",
            "device_count"]
 
 

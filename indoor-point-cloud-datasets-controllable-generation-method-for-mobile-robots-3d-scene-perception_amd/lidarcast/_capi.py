@@ -39,6 +39,7 @@ SYMBOLS = (
     "lrc_min_distances", "lrc_rbf_kernel_sum",
     "lrc_instance_boxes", "lrc_instance_boxes_dev",
     "lrc_cloud_preprocess", "lrc_cloud_preprocess_dev",
+    "lrc_object_boxes", "lrc_object_boxes_dev",
     "lrc_occ_create", "lrc_occ_destroy", "lrc_occ_query",
     "lrc_rng_scan_draws", "lrc_rays_from_trig",
 )
@@ -98,6 +99,11 @@ class LrcPreprocessOpts(C.Structure):
     _fields_ = [("remove_outliers", C.c_uint32), ("nb_neighbors", C.c_uint32), ("std_ratio", C.c_double),
                 ("estimate_normals", C.c_uint32), ("max_nn", C.c_uint32), ("radius", C.c_double),
                 ("cell_size", C.c_double)]
+
+
+class LrcObjBox(C.Structure):
+    _fields_ = [("num_points", C.c_uint64), ("num_kept", C.c_uint64), ("filtered", C.c_uint32), ("reserved_", C.c_uint32),
+                ("min3", C.c_double * 3), ("max3", C.c_double * 3), ("mean", C.c_double), ("threshold", C.c_double)]
 
 
 class LrcMt19937State(C.Structure):
@@ -211,6 +217,8 @@ def load():
                                    C.POINTER(u64), vp, vp, vp],
         "lrc_cloud_preprocess": [vp, vp, u64, C.POINTER(LrcPreprocessOpts), vp, C.POINTER(u64), vp, vp, vp, vp],
         "lrc_cloud_preprocess_dev": [vp, vp, u64, C.POINTER(LrcPreprocessOpts), vp, C.POINTER(u64), vp, vp, vp, vp, vp],
+        "lrc_object_boxes": [vp, vp, u64, vp, u64, C.c_uint32, dbl, dbl, vp, vp, vp, vp],
+        "lrc_object_boxes_dev": [vp, vp, u64, vp, u64, C.c_uint32, dbl, dbl, vp, vp, vp, vp, vp],
         "lrc_nn_create": [vp, vp, u64, dbl, C.POINTER(vp)],
         "lrc_nn_destroy": [vp],
         "lrc_nn_query": [vp, vp, u64, vp, vp],

@@ -214,13 +214,14 @@ _ROOM_RGB = {0: (231, 229, 222), 1: (142, 128, 110), 2: (205, 201, 190), 7: (120
              10: (170, 132, 90)}
 
 
-def sample_s3dis_room(mesh=None, density=15000.0, num_points=None, num_outliers=300, seed=0):
+def sample_s3dis_room(mesh=None, density=15000.0, num_points=None, num_outliers=300, seed=0, return_instances=False):
     """An S3DIS-like room scan sampled from a synthetic mesh (make_room() when None): area-uniform points on the
     triangles at `density` points per square metre (or exactly `num_points`), coordinates rounded to 3 decimals as in
     the S3DIS text files (which gives coincident rows and distance ties), uint8-valued colours from the triangle's
     class with a little per-point noise, the triangle's semantic id as label, plus `num_outliers` rows scattered
     uniformly through the room's box (off the surfaces).  Returns (points float64 (N,3), colors float64 (N,3) in
-    0..255, labels int64 (N,)).  Deterministic in `seed`."""
+    0..255, labels int64 (N,)), and with return_instances also the triangle's instance id per row (int64 (N,); 0 for the
+    scattered rows).  Deterministic in `seed`."""
     if mesh is None:
         mesh = make_room()
     rng = np.random.default_rng(seed)
@@ -244,6 +245,10 @@ def sample_s3dis_room(mesh=None, density=15000.0, num_points=None, num_outliers=
     rgb = np.where(labels[:, None] <= max(_ROOM_RGB), base[np.minimum(labels, max(_ROOM_RGB))], 128.0)
     rgb = np.clip(np.round(rgb + rng.normal(0.0, 6.0, rgb.shape)), 0, 255)
     perm = rng.permutation(len(pts))                 # S3DIS rows are not sorted by surface
+    if return_instances:
+        inst = np.concatenate([(np.asarray(mesh.triangle_ins, np.int64)[tri] if mesh.triangle_ins is not None
+                                else np.zeros(n, np.int64)), np.zeros(int(num_outliers), np.int64)])
+        return pts[perm], rgb[perm], labels[perm], inst[perm]
     return pts[perm], rgb[perm], labels[perm]
 
 
@@ -261,3 +266,60 @@ def write_s3dis_room(root, area_name, room_name, points, colors, labels=None):
         fmt += " %d"
     np.savetxt(path, np.hstack(cols), fmt=fmt)
     return path
+
+
+# S3DIS class names by semantic id (the file stems of Annotations/<class>_<k>.txt)
+S3DIS_CLASSES = ("ceiling", "floor", "wall", "beam", "column", "window", "door", "table", "chair", "sofa", "bookcase",
+                 "board", "clutter")
+
+
+def write_s3dis_annotations(root, area_name, room_name, points, colors, labels, instances):
+    """<root>/<area_name>/<room_name>/Annotations/<class>_<k>.txt, one file per (label, instance) pair in the S3DIS text
+    layout (x y z r g b, coordinates with 3 decimals): k counts the pairs of a class from 1 in ascending instance order,
+    rows keep their order.  Returns the written paths in that order."""
+    import os
+    d = os.path.join(str(root), area_name, room_name, "Annotations")
+    os.makedirs(d, exist_ok=True)
+    labels, instances = np.asarray(labels, np.int64), np.asarray(instances, np.int64)
+    data = np.hstack([np.asarray(points, np.float64), np.asarray(colors, np.float64)])
+    paths = []
+    for sem in np.unique(labels):
+        name = S3DIS_CLASSES[sem] if 0 <= sem < len(S3DIS_CLASSES) else f"class{sem}"
+        for k, ins in enumerate(np.unique(instances[labels == sem]), 1):
+            path = os.path.join(d, f"{name}_{k}.txt")
+            np.savetxt(path, data[(labels == sem) & (instances == ins)], fmt="%.3f %.3f %.3f %d %d %d")
+            paths.append(path)
+    return paths
+
+
+def make_s3dis_area(root, area_name="Area_1", num_rooms=4, seed=0, density=4000.0, num_boxes=6, small_objects=4,
+                    room_types=("office", "conferenceRoom", "hallway", "storage")):
+    """A synthetic S3DIS area: num_rooms rooms <root>/<area_name>/<type>_<i>/ of make_room meshes of varied size (seeded),
+    each sampled by sample_s3dis_room and written as the room file plus its Annotations folder.  small_objects adds
+    that many small windows and boards per room (flat wall patches of 10 to 200 rows), so object sizes span 10 rows
+    to the walls' tens of thousands.  Returns the room directories in creation order."""
+    import os
+    rng = np.random.default_rng(seed)
+    rooms = []
+    for i in range(int(num_rooms)):
+        size = (float(rng.uniform(3.0, 8.0)), float(rng.uniform(3.0, 6.0)), float(rng.uniform(2.6, 3.4)))
+        mesh = make_room(size=size, num_boxes=int(num_boxes), seed=int(seed) * 1000 + i)
+        p, c, l, ins = sample_s3dis_room(mesh, density=density, num_outliers=50, seed=int(seed) * 1000 + i,
+                                         return_instances=True)
+        extra_p, extra_l, extra_i = [p], [l], [ins]
+        for j in range(int(small_objects)):
+            m = int(rng.integers(10, 201))
+            w = rng.uniform(0.2, 1.0, 2)
+            x0 = rng.uniform(0.2, size[0] - 1.2)
+            z0 = rng.uniform(0.5, size[2] - 1.2)
+            patch = np.stack([x0 + rng.random(m) * w[0], np.full(m, 0.01), z0 + rng.random(m) * w[1]], 1)
+            extra_p.append(np.round(patch, 3))
+            extra_l.append(np.full(m, 5 if j % 2 == 0 else 11, np.int64))
+            extra_i.append(np.full(m, 1000 + j, np.int64))
+        p, l, ins = np.vstack(extra_p), np.concatenate(extra_l), np.concatenate(extra_i)
+        c = np.vstack([c, np.full((len(p) - len(c), 3), 128.0)])
+        name = f"{room_types[i % len(room_types)]}_{i // len(room_types) + 1}"
+        write_s3dis_room(root, area_name, name, p, c, l)
+        write_s3dis_annotations(root, area_name, name, p, c, l, ins)
+        rooms.append(os.path.join(str(root), area_name, name))
+    return rooms
