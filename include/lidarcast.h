@@ -264,10 +264,14 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t num_segments, uint64_t seg_len,
  *   d_out             the out_* members and counts of lrc_compact_io (device pointers); the input members are ignored.
  *                     The buffers of a submit are written up to two submits later: rotate at least three output buffers
  *                     between lrc_pipe_wait calls.  rays_per_pose % 64 != 0 falls back to scan + compaction per stream.
+ *   d_poses16, d_dirs3  are read by the submit's trace on an internal stream, which `stream` does not wait for: leave
+ *                     them unchanged until `stream` has passed lrc_pipe_wait, or rotate them like the output buffers.
+ *                     The same holds for the inputs of lrc_pipe_submit_sharded.
  *   lrc_pipe_records  the fixed-stride records (lrc_hits, device pointers, tile_count included) of submit `ticket`;
- *                     valid until three further submits have been made (four sets rotate).  For a submit that kept only
- *                     rows (rays_per_pose % 64 == 0) the complete records are rebuilt first, behind that submit's trace,
- *                     and the host waits for them: the same bytes lrc_scan_poses_dev writes.  A verification surface.
+ *                     valid while at most three further submits have been made (four sets rotate; the fourth rewrites
+ *                     them).  For a submit that kept only rows (rays_per_pose % 64 == 0) the complete records are rebuilt
+ *                     first, behind that submit's trace, and the host waits for them: the same bytes lrc_scan_poses_dev
+ *                     writes.  A verification surface.
  *   lrc_pipe_trace_ms the time the trace launch of submit `ticket` spent between its stream reaching it and its last wave
  *                     (HIP events on the launch stream; inside the pipeline launches overlap, so this is longer than the
  *                     launch's share of the step).  Synchronises the host with that launch.
@@ -290,12 +294,16 @@ int lrc_pipe_trace_ms(lrc_pipe* pipe, uint64_t ticket, float* out_ms);
  *                            from the records of submit `own_ticket` -- rides in the leading workgroups of this trace launch,
  *                            i.e. it runs when the previous launch's tail begins instead of waiting, as a separate kernel of
  *                            4-wave workgroups does, until a trace launch has no workgroup left.  `stream` must already wait
- *                            for the collective that produced the gathered slabs.
+ *                            for the collective that produced the gathered slabs.  At most two submits may lie between
+ *                            `own_ticket` and this one (own_ticket >= this submit's ticket - 3): one more, and this
+ *                            submit's own trace would rewrite the records the assembly reads.
  *   lrc_pipe_trace_done      `stream` waits for the trace of that submit (the send slab is complete: start the collective).
- *   lrc_pipe_scan_gathered   the scan over the gathered keep counts of ALL ranks, to be enqueued on the communication stream
- *                            right behind the collective (two small kernels; the launch that carries the assembly must wait for
- *                            them through `stream` of lrc_pipe_submit_sharded).
- *   lrc_pipe_assemble        the same assembly with the plain kernels on `stream` (the last scans of a run), after the scan.
+ *   lrc_pipe_scan_gathered   the scan over the gathered keep counts of ALL ranks and a transposed copy of d_dirs3 (read as it is
+ *                            at this point of `stream`), into the offset table of gathered->scan_slot: to be enqueued on the
+ *                            communication stream right behind the collective (two small kernels; the launch that carries the
+ *                            assembly must wait for them through `stream` of lrc_pipe_submit_sharded).
+ *   lrc_pipe_assemble        the same assembly with the plain kernels on `stream` (the last scans of a run), after the scan;
+ *                            up to three submits may lie between `own_ticket` and the call.
  * Rows and counts of an assembled scan are complete once the stream has passed lrc_pipe_wait (or lrc_pipe_assemble). */
 typedef struct lrc_gathered {
     const double*   d_all_poses16;     /* (num_poses_all,16) the poses of ALL ranks, slab after slab                    */
@@ -305,7 +313,8 @@ typedef struct lrc_gathered {
     uint64_t        poses_per_slab;
     uint64_t        slab_stride_bytes; /* distance between slabs (ids and counts share it)                               */
     uint64_t        own_slab;          /* this rank's slab                                                               */
-    uint64_t        own_ticket;        /* the submit that scanned it (its records must still be there: <= 3 submits ago) */
+    uint64_t        own_ticket;        /* the submit that scanned it; its records must still be there: at most 2 submits
+                                          after it for lrc_pipe_submit_sharded, 3 for lrc_pipe_assemble / _scan_gathered  */
     uint64_t        scan_slot;         /* 0 / 1: which of the pipeline's two offset tables lrc_pipe_scan_gathered fills for
                                           this scan (alternate with the gather buffers)                                  */
     float*          d_out_xyzl;        /* (K,4) the assembled rows, np.vstack order                                      */

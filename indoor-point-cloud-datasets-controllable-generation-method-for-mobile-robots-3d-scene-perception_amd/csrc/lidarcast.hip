@@ -1273,9 +1273,8 @@ __global__ __launch_bounds__(kBlock) void compact_count_kernel(const float* t, u
 // was not scheduled until that launch had no workgroup left -- 150-170 us for a 5 us kernel, and with it the whole chain
 // trace -> scan -> scatter -> next trace fell into phase with the other stream's (profiles/r04_chain_timeline.txt).
 constexpr int kScanRows = 16;           // 64 lanes x 16 rows = 1024 tiles per wave and super tile
-__global__ __launch_bounds__(64) void compact_scan_kernel(const uint32_t* tile_cnt, uint64_t tiles_per_slab,
-                                                          uint64_t slab_stride, uint32_t* tile_off,
-                                                          uint64_t ntiles, uint32_t* super_total) {
+__device__ __forceinline__ void scan_super_tiles(const uint32_t* tile_cnt, uint64_t tiles_per_slab, uint64_t slab_stride,
+                                                 uint32_t* tile_off, uint64_t ntiles, uint32_t* super_total) {
     const uint32_t lane = threadIdx.x;
     const uint64_t nsuper = (ntiles + 1023) / 1024;
     const bool one_slab = tiles_per_slab >= ntiles;          // a plain array: no slab arithmetic (a 64-bit division per entry)
@@ -1312,6 +1311,25 @@ __global__ __launch_bounds__(64) void compact_scan_kernel(const uint32_t* tile_c
         }
         if (lane == 0) super_total[sup] = carry;
     }
+}
+__global__ __launch_bounds__(64) void compact_scan_kernel(const uint32_t* tile_cnt, uint64_t tiles_per_slab,
+                                                          uint64_t slab_stride, uint32_t* tile_off,
+                                                          uint64_t ntiles, uint32_t* super_total) {
+    scan_super_tiles(tile_cnt, tiles_per_slab, slab_stride, tile_off, ntiles, super_total);
+}
+// the same scan over the gathered counts of all ranks (lrc_pipe_scan_gathered), and in the same waves the direction table
+// (N,3) -> x[N] y[N] z[N] for the rebuild (as dirs_transpose_kernel): one kernel less to find wave slots for beside a running
+// trace launch
+__global__ __launch_bounds__(64) void gathered_scan_kernel(const uint32_t* tile_cnt, uint64_t tiles_per_slab,
+                                                           uint64_t slab_stride, uint32_t* tile_off, uint64_t ntiles,
+                                                           uint32_t* super_total, const double* __restrict__ dirs3, uint32_t n,
+                                                           double* __restrict__ soa) {
+    for (uint32_t i = blockIdx.x * 64u + threadIdx.x; i < n; i += gridDim.x * 64u) {
+        soa[i] = dirs3[(size_t)i * 3];
+        soa[(size_t)n + i] = dirs3[(size_t)i * 3 + 1];
+        soa[2 * (size_t)n + i] = dirs3[(size_t)i * 3 + 2];
+    }
+    scan_super_tiles(tile_cnt, tiles_per_slab, slab_stride, tile_off, ntiles, super_total);
 }
 
 // Pass A2: one wave turns the super-tile totals into exclusive bases (base[nsuper] = grand total).  One wave for the same
@@ -1965,6 +1983,9 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
     static const int leafw = env_int("LRC_LEAFW", kLeafW) == 1 ? 1 : 2, uni = env_int("LRC_UNIFORM", 1), spec = env_int("LRC_SPEC", 0);
     static const int sector = env_int("LRC_SECTOR", 1), refill = env_int("LRC_REFILL", 0);
     p.force_redo = (uint32_t)force_redo;
+    // a pipelined launch (lrc_pipe_*) carries leading workgroups that scatter or assemble an earlier scan: only the product
+    // dispatch sizes its grid for them (nblk + p.pre.blocks); the variants below ignore p.pre
+    if (p.pre.blocks != 0u) return 1;
     const bool qn = s->d_nodes_q != nullptr, wide = s->d_nodes_q4 != nullptr;
 #define LRC_LAB(G, W, U, S, Q) \
     hipLaunchKernelGGL((trace_kernel<G, W, U, S, false, Q>), dim3((uint32_t)nblk), dim3(kTBlock), lds, st, p)
@@ -2537,11 +2558,12 @@ struct lrc_pipe {
     hipEvent_t ev_in[kSets] = {}, ev_t0[kSets] = {}, ev_trace[kSets] = {}, ev_flush[2] = {}, ev_expand = nullptr;
     bool fused = true;                                       // false: N % 64 != 0 or > 512 super tiles: plain chain per stream
     uint64_t ticket = 0;                                     // submits so far; submit k uses set k % 4, trace stream k % 2
-    // sharded submits (lrc_pipe_submit_sharded): scratch of the scan over ALL ranks' keep counts, per trace stream, and the
-    // direction table transposed for the rebuild (once per table)
+    // sharded submits (lrc_pipe_submit_sharded): per scan slot the scan over ALL ranks' keep counts and the direction table
+    // transposed for the rebuild (TileScratch::d_dirs_soa, written by every lrc_pipe_scan_gathered of that slot)
     lrc_ctx::TileScratch gscratch[2];
-    double* d_dirs_soa = nullptr;
-    const double* soa_of = nullptr;
+    // per set: the ticket of the last trace launch that read the set's records as the own rows of an assembly (0: none).  The
+    // submit that writes the set again waits for that launch when it runs on the other trace stream.
+    uint64_t read_by[kSets] = {};
 };
 
 int lrc_pipe_destroy(lrc_pipe* pp) {
@@ -2562,9 +2584,9 @@ int lrc_pipe_destroy(lrc_pipe* pp) {
             if (sc.d_tile_cnt) (void)hipFree(sc.d_tile_cnt);
             if (sc.d_super_total) (void)hipFree(sc.d_super_total);
             if (sc.d_super_base) (void)hipFree(sc.d_super_base);
+            if (sc.d_dirs_soa) (void)hipFree(sc.d_dirs_soa);
         }
     }
-    if (pp->d_dirs_soa) (void)hipFree(pp->d_dirs_soa);
     delete pp;
     return LRC_OK;
 }
@@ -2642,6 +2664,15 @@ LeanIn pipe_lean(const lrc_pipe* pp, int set) {
     if (!pp->lean[set]) return LeanIn{nullptr, nullptr};
     return LeanIn{pp->row[set], pp->keep_mask[set]};
 }
+// before the launch of a submit overwrites `set` on stream T: an assembly that read the set's own records in a launch on the
+// OTHER trace stream (lag 1 or 3) is ordered before this launch only by dispatch, so T waits for that launch's event.  Lag 2
+// shares T and is ordered already.  ev_trace of the reader is still its own: the reader came at most three submits earlier.
+int wait_for_readers(lrc_pipe* pp, int set, hipStream_t T) {
+    const uint64_t r = pp->read_by[set];
+    if (r != 0 && pp->s_trace[(r - 1) % 2] != T) LRC_HIP(hipStreamWaitEvent(T, pp->ev_trace[(r - 1) % lrc_pipe::kSets], 0));
+    pp->read_by[set] = 0;
+    return LRC_OK;
+}
 }  // namespace
 
 int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const double* d_dirs3, double max_range,
@@ -2659,6 +2690,8 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     // inputs (poses, table) and outputs (the caller's rows and counts) are the caller's as of this point of its stream
     LRC_HIP(hipEventRecord(pp->ev_in[set], (hipStream_t)stream));
     LRC_HIP(hipStreamWaitEvent(T, pp->ev_in[set], 0));
+    int rc = wait_for_readers(pp, set, T);
+    if (rc) return rc;
     const uint64_t N = pp->rays_per_pose;
     TraceParams p{};
     p.poses16 = d_poses16;
@@ -2688,7 +2721,7 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
         p.pre.lean = pipe_lean(pp, prev);
     }
     LRC_HIP(hipEventRecord(pp->ev_t0[set], T));
-    int rc = launch_trace(s, p, 1, T);
+    rc = launch_trace(s, p, 1, T);
     if (rc) return rc;
     LRC_HIP(hipEventRecord(pp->ev_trace[set], T));
     if (p.pre.blocks) pp->pending[prev] = false;
@@ -2725,24 +2758,29 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
 // ---- the pipeline on N ranks: the trace writes triangle ids + keep counts into the caller's send slab, the assembly of an
 // EARLIER scan of all ranks (its gathered slabs) rides in the leading workgroups of this trace launch ----------------------
 namespace {
-int check_gathered(const lrc_pipe* pp, const lrc_gathered* g, const char* who) {
+// max_back: how many submits may have followed own_ticket.  3 where the work runs on the caller's stream, ahead of every later
+// submit (lrc_pipe_assemble, lrc_pipe_scan_gathered); 2 where the assembly rides in the launch of the next submit, which must not
+// be own_ticket + 4: that launch's own trace writes the set the assembly reads (lrc_pipe_submit_sharded).
+int check_gathered(const lrc_pipe* pp, const lrc_gathered* g, const char* who, uint64_t max_back) {
     auto bad = [&](const char* m) { return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": " + m); };
     if (!g->d_all_poses16 || !g->d_all_prims || !g->d_all_tile_counts || !g->d_out_xyzl) return bad("NULL member of lrc_gathered");
     if (g->poses_per_slab == 0 || g->poses_per_slab > pp->max_poses || g->num_poses_all == 0 || g->num_poses_all % g->poses_per_slab)
         return bad("num_poses_all must be a multiple of poses_per_slab (<= the pipeline's max_poses)");
     if (g->own_slab >= g->num_poses_all / g->poses_per_slab) return bad("own_slab outside the gathered slabs");
     if (g->slab_stride_bytes % 4 || g->slab_stride_bytes < g->poses_per_slab * pp->rays_per_pose * 4) return bad("slab stride smaller than a slab");
-    if (g->own_ticket == 0 || g->own_ticket > pp->ticket || pp->ticket - g->own_ticket >= (uint64_t)lrc_pipe::kSets)
-        return bad("the own records of that scan are gone (four sets rotate): assemble within three submits");
+    if (g->own_ticket == 0 || g->own_ticket > pp->ticket || pp->ticket - g->own_ticket > max_back)
+        return bad(max_back < 3 ? "the own records of that scan are rewritten by this submit: carry the assembly at most three "
+                                  "submits after own_ticket, or use lrc_pipe_assemble"
+                                : "the own records of that scan are gone (four sets rotate): assemble within three submits");
     if (pp->lean[(g->own_ticket - 1) % lrc_pipe::kSets]) return bad("own_ticket is not a submit of lrc_pipe_submit_sharded");
     const uint64_t ntiles = g->num_poses_all * (pp->rays_per_pose / 64);
     if (ntiles > 0x7FFFFFFFull) return bad("too many entries");
     return LRC_OK;
 }
 
-// scan over all ranks' keep counts (two one-wave kernels on `st`), the rebuild's argument block, the own rows' compaction input
-// the scan over all ranks' keep counts (two one-wave kernels on `st`) into the scratch set of g->scan_slot; also what a first
-// use needs: the plane table, the transposed direction table
+// the scan over all ranks' keep counts (two one-wave kernels on `st`; the first also transposes the direction table for the
+// rebuild) into the scratch set of g->scan_slot: the launch that reads them waits for `st` as it must for the offsets; also what
+// a first use needs: the plane table
 int scan_gathered(lrc_pipe* pp, const lrc_gathered* g, const double* d_dirs3, hipStream_t st, int scan_waves) {
     lrc_scene* s = pp->scene;
     lrc_ctx::TileScratch& sc = pp->gscratch[g->scan_slot & 1u];
@@ -2750,17 +2788,17 @@ int scan_gathered(lrc_pipe* pp, const lrc_gathered* g, const double* d_dirs3, hi
     int rc = ensure_tile_scratch(s->ctx, sc, ntiles);
     if (rc) return rc;
     if ((rc = ensure_prim_plane(s, st))) return rc;
-    if (pp->soa_of != d_dirs3) {
-        if (!pp->d_dirs_soa) LRC_HIP(hipMalloc((void**)&pp->d_dirs_soa, N * 24));
-        hipLaunchKernelGGL(dirs_transpose_kernel, dim3((uint32_t)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_dirs3, (uint32_t)N,
-                           pp->d_dirs_soa);
-        LRC_HIP(hipStreamSynchronize(st));          // once per table: the trace streams read it
-        pp->soa_of = d_dirs3;
+    // every call: the table may have been edited in place, or be a new one at a recycled address
+    if (!sc.d_dirs_soa) {
+        LRC_HIP(hipMalloc((void**)&sc.d_dirs_soa, N * 24));
+        sc.dirs_cap = N;
     }
     const uint64_t stride = g->slab_stride_bytes / 4, nsuper = (ntiles + 1023) / 1024;
-    const uint64_t grid = scan_waves > 0 && nsuper > (uint64_t)scan_waves ? (uint64_t)scan_waves : nsuper;
-    hipLaunchKernelGGL(compact_scan_kernel, dim3((uint32_t)grid), dim3(64), 0, st, g->d_all_tile_counts, g->poses_per_slab * tps, stride,
-                       sc.d_tile_off, ntiles, sc.d_super_total);
+    // one wave per super tile, at least one per 1024 directions (16 rows of the table per lane), at most scan_waves
+    uint64_t grid = nsuper > (N + 1023) / 1024 ? nsuper : (N + 1023) / 1024;
+    if (scan_waves > 0 && grid > (uint64_t)scan_waves) grid = (uint64_t)scan_waves;
+    hipLaunchKernelGGL(gathered_scan_kernel, dim3((uint32_t)grid), dim3(64), 0, st, g->d_all_tile_counts, g->poses_per_slab * tps, stride,
+                       sc.d_tile_off, ntiles, sc.d_super_total, d_dirs3, (uint32_t)N, sc.d_dirs_soa);
     hipLaunchKernelGGL(compact_base_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)sc.d_super_total, sc.d_super_base, nsuper);
     LRC_HIP(hipGetLastError());
     return LRC_OK;
@@ -2772,10 +2810,10 @@ int prepare_gathered(lrc_pipe* pp, const lrc_gathered* g, RebuildParams* q, lrc_
     lrc_scene* s = pp->scene;
     lrc_ctx::TileScratch& sc = pp->gscratch[g->scan_slot & 1u];
     const uint64_t N = pp->rays_per_pose, tps = N / 64, ntiles = g->num_poses_all * tps;
-    if (sc.tile_cap < ntiles + 1 || !pp->d_dirs_soa || !s->d_prim_plane)
+    if (sc.tile_cap < ntiles + 1 || !sc.d_dirs_soa || !s->d_prim_plane)
         return fail(LRC_ERR_INVALID_ARG, "lrc_pipe: the gathered scan has not been through lrc_pipe_scan_gathered");
     const uint64_t stride = g->slab_stride_bytes / 4;
-    q->poses16 = g->d_all_poses16; q->dirs_soa = pp->d_dirs_soa; q->prims = g->d_all_prims;
+    q->poses16 = g->d_all_poses16; q->dirs_soa = sc.d_dirs_soa; q->prims = g->d_all_prims;
     q->pps = (uint32_t)g->poses_per_slab; q->stride = stride; q->seg_len = (uint32_t)N; q->tps = (uint32_t)tps;
     q->ntiles = (uint32_t)ntiles; q->nseg = (uint32_t)g->num_poses_all; q->plane = s->d_prim_plane;
     q->num_prims = (uint32_t)s->info.num_triangles; q->tile_off = sc.d_tile_off; q->super_base = sc.d_super_base;
@@ -2803,13 +2841,14 @@ int lrc_pipe_submit_sharded(lrc_pipe* pp, const double* d_poses16, uint64_t P, c
         return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_submit_sharded: a scan with range noise cannot be rebuilt from triangle ids");
     LRC_HIP(hipSetDevice(s->ctx->device));
     int rc;
-    if (assemble && (rc = check_gathered(pp, assemble, "lrc_pipe_submit_sharded"))) return rc;
+    if (assemble && (rc = check_gathered(pp, assemble, "lrc_pipe_submit_sharded", 2))) return rc;
     const uint64_t k = pp->ticket;
     const int set = (int)(k % lrc_pipe::kSets), lane = (int)(k % 2);
     hipStream_t T = pp->s_trace[lane];
     // inputs, the send slab and -- for the assembly -- the gathered slabs are the caller's as of this point of its stream
     LRC_HIP(hipEventRecord(pp->ev_in[set], (hipStream_t)stream));
     LRC_HIP(hipStreamWaitEvent(T, pp->ev_in[set], 0));
+    if ((rc = wait_for_readers(pp, set, T))) return rc;
     const uint64_t N = pp->rays_per_pose;
     TraceParams p{};
     p.poses16 = d_poses16; p.dirs3 = d_dirs3; p.rays_per_pose = N; p.total = P * N; p.has_center = 1; p.max_range = max_range;
@@ -2838,6 +2877,7 @@ int lrc_pipe_submit_sharded(lrc_pipe* pp, const double* d_poses16, uint64_t P, c
     rc = launch_trace(s, p, 1, T);
     if (rc) return rc;
     LRC_HIP(hipEventRecord(pp->ev_trace[set], T));
+    if (assemble) pp->read_by[(assemble->own_ticket - 1) % lrc_pipe::kSets] = k + 1;
     pp->out[set] = lrc_compact_io{};
     pp->poses[set] = P;
     pp->lean[set] = false;                     // the complete record (its id column is the send slab)
@@ -2862,7 +2902,7 @@ int lrc_pipe_trace_done(lrc_pipe* pp, uint64_t ticket, void* stream) {
 // (between two trace launches of one stream they would hold the second back: DESIGN.md section 5.2)
 int lrc_pipe_scan_gathered(lrc_pipe* pp, const double* d_dirs3, const lrc_gathered* g, void* stream) {
     if (!pp || !g || !d_dirs3) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_scan_gathered: NULL argument");
-    int rc = check_gathered(pp, g, "lrc_pipe_scan_gathered");
+    int rc = check_gathered(pp, g, "lrc_pipe_scan_gathered", 3);
     if (rc) return rc;
     LRC_HIP(hipSetDevice(pp->device));
     return scan_gathered(pp, g, d_dirs3, (hipStream_t)stream, LRC_PIPE_SCAN_WAVES * 4);
@@ -2871,7 +2911,7 @@ int lrc_pipe_scan_gathered(lrc_pipe* pp, const double* d_dirs3, const lrc_gather
 // the assembly of a gathered (and scanned) scan with the plain kernels, on `stream` (the end of a run: no later launch to ride on)
 int lrc_pipe_assemble(lrc_pipe* pp, const double* d_dirs3, const lrc_gathered* g, void* stream) {
     if (!pp || !g || !d_dirs3) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_assemble: NULL argument");
-    int rc = check_gathered(pp, g, "lrc_pipe_assemble");
+    int rc = check_gathered(pp, g, "lrc_pipe_assemble", 3);
     if (rc) return rc;
     LRC_HIP(hipSetDevice(pp->scene->ctx->device));
     hipStream_t st = (hipStream_t)stream;

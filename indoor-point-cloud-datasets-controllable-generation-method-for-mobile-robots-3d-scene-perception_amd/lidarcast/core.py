@@ -790,7 +790,8 @@ class ScanPipe:
               "lrc_pipe_assemble")
 
     def records(self, ticket):
-        """LrcHits (device pointers) of the fixed-stride records of that submit; valid until two further submits."""
+        """LrcHits (device pointers) of the fixed-stride records of that submit; valid while at most three further submits
+        have been made (four sets rotate)."""
         h = _capi.LrcHits()
         check(self._lib.lrc_pipe_records(self._h, int(ticket), C.byref(h)), "lrc_pipe_records")
         return h
