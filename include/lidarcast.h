@@ -392,6 +392,47 @@ int lrc_scan_table_compact(lrc_scene* scene, const double* poses16, uint64_t num
                            const lrc_grid* grid /* nullable */, double max_range, const lrc_frames* out,
                            uint64_t capacity, uint64_t* out_total);
 
+/* ---- moving-sensor sweeps (opt-in) -------------------------------------------------------
+ * A spinning sensor on a moving robot fires its rays one after the other during one sweep (0.1 s at 10 Hz), so every ray
+ * is cast from its own pose.  Sweep k is described by one MOTION RECORD, 24 float64:
+ *   [0..11]  the start pose: the first three rows of the 4x4 matrix, exactly as poses16 holds them
+ *   [12..15] dq = (w, x, y, z), unit, w >= cos(pi/4): the world-frame rotation from the start to the end orientation,
+ *            R_end = R(dq) R_start (a rotation of at most pi/2 per sweep)
+ *   [16..18] dc = c_end - c_start
+ *   [19..23] zero
+ * and ray i by its FIRING FRACTION fire[i] in [0, 1): the fraction of the sweep at which it fires ((i mod W) / W for a
+ * sensor that fires column after column; any table for a sensor that staggers its lasers).  With s = fire[i], ray (k, i) is,
+ * every step a separate float64 operation in this order (csrc/lrc_device.h restates it, the tests restate it in numpy):
+ *   v    = gen_ray's float64 world direction of dirs3[i] under the start rotation (the dgemm FMA chain of lrc_scan_poses)
+ *   qw   = (1 - s) + s*dq.w;   u = (s*dq.x, s*dq.y, s*dq.z)                       nlerp, NOT normalised
+ *   n    = ((qw*qw + ux*ux) + uy*uy) + uz*uz;   k = 2/n
+ *   t    = u x v  (tx = uy*vz - uz*vy, ty = uz*vx - ux*vz, tz = ux*vy - uy*vx);   w = u x t (same form)
+ *   v'_j = v_j + k*(qw*t_j + w_j)                                                 rotation by q/|q|, no square root
+ *   c_j  = (s*dc_j == 0) ? c0_j : c0_j + s*dc_j                                   c0 = the start translation
+ * direction = float32(v'), origin = float32(c), range-filter centre = c in float64; then exactly lrc_cast.
+ * Output index = k*N + i, as lrc_scan_poses_dev.  Properties:
+ *   - s = 0 (or dq = (1, 0, 0, 0) and dc = 0) adds signed zeros only: the static ray of lrc_scan_poses, bit for bit.
+ *   - no transcendental function anywhere: bit-exact against a host restatement.
+ *   - the nlerp angle differs from constant-rate slerp by at most (computed, not measured)
+ *         rotation per sweep   0.05 rad   0.1 rad   0.2 rad   0.5 rad   pi/2
+ *         max angle error      5.1e-7     4.1e-6    3.3e-5    5.1e-4    1.7e-2  rad
+ *   (max over s of |2 atan2(s sin(a/2), 1 - s + s cos(a/2)) - s a| for a rotation a per sweep, rounded up)
+ *   lrc_scan_sweeps_dev      device pointers: d_motion24 (P,24), d_dirs3 (N,3), d_fire (N).  The caller vouches for the
+ *                            records and the fire table (lrc_scan_sweeps_compact and lrc_table_set_fire check them).
+ *   lrc_table_set_fire       attaches a resident fire table (N values in [0, 1), checked) to a direction table; NULL
+ *                            detaches it.  Uploaded once, like the direction table.
+ *   lrc_scan_sweeps_compact  host records, the resident table with its fire table: compacted in HBM exactly like
+ *                            lrc_scan_table_compact (same lrc_frames, counts, index, range_origin, per-pose statistics).
+ *                            Rejects non-finite records, dq.w < cos(pi/4) and a non-unit dq with LRC_ERR_INVALID_ARG
+ *                            before any launch.
+ * lrc_scene_set_options applies unchanged (range_noise_len = num_poses * rays_per_pose). */
+int lrc_scan_sweeps_dev(lrc_scene* scene, const double* d_motion24, uint64_t num_poses, const double* d_dirs3,
+                        const double* d_fire, uint64_t rays_per_pose, double max_range, const lrc_hits* d_out,
+                        void* stream);
+int lrc_table_set_fire(lrc_table* table, const double* fire, uint64_t rays_per_pose);
+int lrc_scan_sweeps_compact(lrc_scene* scene, const double* motion24, uint64_t num_poses, const lrc_table* table,
+                            double max_range, const lrc_frames* out, uint64_t capacity, uint64_t* out_total);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

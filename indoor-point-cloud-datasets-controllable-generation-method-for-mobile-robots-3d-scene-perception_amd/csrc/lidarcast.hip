@@ -126,6 +126,7 @@ struct lrc_table {            // a sensor's direction table resident in HBM (lrc
     lrc_ctx* ctx = nullptr;
     double* d_dirs3 = nullptr;
     uint64_t n = 0;
+    double* d_fire = nullptr;   // optional (lrc_table_set_fire): per ray the fraction of the sweep at which it fires
 };
 
 struct lrc_scene {
@@ -252,6 +253,9 @@ struct TraceParams {
     const float* range_noise;
     int incident_mode;
     lrc_hits out;
+    // GEN = 4 (moving-sensor sweeps, lrc_scan_sweeps_*): (P,24) motion records and the (N) firing fractions of the table
+    const double* motion24;
+    const double* fire;
 };
 
 // workgroup -> tile remap: consecutive tiles land on the same XCD (blocks b, b+8, ... share an L2),
@@ -655,12 +659,13 @@ constexpr int kPreTiles = LRC_PRE_TILES;      // tiles per leading workgroup of 
 
 template <int I> struct IntTag { static constexpr int value = I; };
 
-// GEN: 0 = explicit rays, 1 = pose x direction table, 2 = pose x per-ray scan angles (dual-axis sensor, opt-in)
+// GEN: 0 = explicit rays, 1 = pose x direction table, 2 = pose x per-ray scan angles (dual-axis sensor, opt-in),
+//      4 = motion record x direction table x firing fractions (moving-sensor sweeps, opt-in; same ray order as 1)
 // QN: 1 = walk the quantised node images (32-byte nodes for the per-lane fetches), 2 = walk their
 //     four-wide collapse (64-byte nodes, half the steps); a wave with a ray outside the bound the quantisation margin is
 //     proven for walks the float32 world-space nodes instead
 template <int GEN, int LEAFW, bool UNI, bool SPEC, bool STATS = false, int QN = 0>
-__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) void trace_kernel(const TraceParams p) {
+__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4)) ? 8 : 1) void trace_kernel(const TraceParams p) {
     extern __shared__ int s_stack[];   // [stack depth][kTBlock]: one column per lane, conflict free
     const uint32_t tid = threadIdx.x;
     if (GEN == 1 && p.pre.blocks != 0u && p.pre.sharded != 0u) {
@@ -722,6 +727,11 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) v
         const double2 a = ((const double2*)p.angles2)[gid];
         gen_ray_angles(p.poses16, pose, a.x, a.y, o, d, cx, cy, cz);
         if (p.keep_mask) live = p.keep_mask[gid] != 0;
+        pose32 = (uint32_t)pose;
+    } else if (GEN == 4) {
+        const uint64_t pose = gid / p.rays_per_pose;
+        const uint64_t i = gid - pose * p.rays_per_pose;
+        gen_ray_sweep(p.motion24, p.dirs3, p.fire, pose, i, o, d);
         pose32 = (uint32_t)pose;
     } else {
         const float* r = p.rays6 + gid * 6;
@@ -1074,7 +1084,9 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) v
     }
 
     // ---- fused write-back ----
-    if (GEN != 0) {
+    if (GEN == 4) {
+        // formed below from the record and the ray's firing fraction, after the ray's index
+    } else if (GEN != 0) {
         // the range-filter centre (the pose's translation, float64) is fetched again here instead of being held in six
         // registers through the traversal; the pointer is made opaque so that the fetch is not merged with gen_ray's
         const double* M = p.poses16;
@@ -1094,6 +1106,16 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && GEN == 1) ? 8 : 1) v
     const uint32_t tile_w = p.tile_chunk_log2 ? xcd_tile_chunked(wg - p.pre.blocks, gridDim.x - p.pre.blocks, p.tile_chunk_log2)
                                               : xcd_tile(wg - p.pre.blocks, gridDim.x - p.pre.blocks);
     const uint64_t gid_w = (uint64_t)tile_w * kTBlock + tid;
+    if (GEN == 4) {
+        // the range-filter centre c(s), float64, formed again from the record and fire[i] (as GEN = 1 fetches the pose's
+        // translation again) instead of being held through the traversal; opaque pointers keep the loads from merging
+        const double* M = p.motion24;
+        const double* F = p.fire;
+        asm volatile("" : "+s"(M));
+        asm volatile("" : "+s"(F));
+        M += (size_t)pose32 * 24;
+        sweep_centre(M, F[gid_w - (uint64_t)pose32 * p.rays_per_pose], cx, cy, cz);
+    }
     write_back<GEN != 0>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot);
     if (STATS) {
         if (p.stats) {
@@ -2059,7 +2081,7 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
         return 1;
     }
     const bool plain = leafw == kLeafW && uni && !spec && !(qn && wide);
-    if (plain || gen == 2) return 1;
+    if (plain || gen == 2 || gen == 4) return 1;
     const bool wide_only = qn && wide && leafw == kLeafW && uni && !spec;
     if (gen == 1) { if (wide_only) LRC_LAB(1, kLeafW, true, false, 2); else LRC_LAB_PICK(1); }
     else { if (wide_only) LRC_LAB(0, kLeafW, true, false, 2); else LRC_LAB_PICK(0); }
@@ -2070,7 +2092,8 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
 #endif   // LRC_VARIANTS
 
 // One launch of the trace kernel over p.total rays.  gen: 0 explicit rays, 1 pose x direction table, 2 pose x scan angles,
-// 3 a grid scan (lrc_scan_grid_*: the per-ray kernel here; the packet kernel in the laboratory build).
+// 3 a grid scan (lrc_scan_grid_*: the per-ray kernel here; the packet kernel in the laboratory build), 4 moving-sensor sweeps
+// (motion record x direction table x firing fractions).
 static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, bool stats = false) {
     p.nodes = s->d_nodes;
     p.tris = s->d_tris;
@@ -2109,7 +2132,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     // is worth more than the balance: measured +1...+16 % for the striped order there, -1...-10 % on the cache-resident
     // scenes (profiles/r03_xcd_striping_sweep.txt).
     constexpr uint64_t kStripeSceneBytes = 192ull << 20;
-    if (gen == 1 && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
+    if ((gen == 1 || gen == 4) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
         const uint64_t tpp = p.rays_per_pose / 64;
         if (tpp % 16 == 0) {
             const uint64_t chunk = tpp / 16;
@@ -2157,6 +2180,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
         else if (gen == 0) { if (qn) LRC_LAUNCH(0, true, 1); else LRC_LAUNCH(0, true, 0); }
         else return fail(LRC_ERR_INVALID_ARG, "traversal statistics are not available for the scan-angle generator");
     } else if (gen == 1) { if (qn) LRC_LAUNCH(1, false, 1); else LRC_LAUNCH(1, false, 0); }
+    else if (gen == 4) { if (qn) LRC_LAUNCH(4, false, 1); else LRC_LAUNCH(4, false, 0); }
     else if (gen == 2) { if (qn) LRC_LAUNCH(2, false, 1); else LRC_LAUNCH(2, false, 0); }
     else { if (qn) LRC_LAUNCH(0, false, 1); else LRC_LAUNCH(0, false, 0); }
 #undef LRC_LAUNCH
@@ -2239,6 +2263,24 @@ int lrc_scan_poses_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const 
     p.max_range = max_range;
     p.out = *d_out;
     return launch_trace(s, p, 1, (hipStream_t)stream);
+}
+
+int lrc_scan_sweeps_dev(lrc_scene* s, const double* d_motion24, uint64_t P, const double* d_dirs3, const double* d_fire,
+                        uint64_t N, double max_range, const lrc_hits* d_out, void* stream) {
+    if (!s || !d_out) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_dev: NULL scene or output");
+    if (P && N && (!d_motion24 || !d_dirs3 || !d_fire))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_dev: motion24, dirs3 or fire is NULL");
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    TraceParams p{};
+    p.motion24 = d_motion24;
+    p.dirs3 = d_dirs3;
+    p.fire = d_fire;
+    p.rays_per_pose = N ? N : 1;
+    p.total = P * N;
+    p.has_center = 1;
+    p.max_range = max_range;
+    p.out = *d_out;
+    return launch_trace(s, p, 4, (hipStream_t)stream);
 }
 
 static int check_grid(const char* who, const lrc_grid* g, uint64_t N) {
@@ -3402,7 +3444,8 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
     for (uint64_t c = 0; c < chunks; ++c) {
         const uint64_t p1 = chunk_end(c), np_ = p1 - p0, r0 = p0 * N;
         TraceParams q = p;
-        q.poses16 = p.poses16 + p0 * 16;
+        if (q.poses16) q.poses16 = p.poses16 + p0 * 16;
+        if (q.motion24) q.motion24 = p.motion24 + p0 * 24;
         if (q.angles2) q.angles2 = p.angles2 + r0 * 2;
         if (q.rays6) q.rays6 = p.rays6 + r0 * 6;
         if (q.seg_centers3) q.seg_centers3 = p.seg_centers3 + p0 * 3;
@@ -3549,6 +3592,7 @@ int lrc_table_destroy(lrc_table* t) {
     if (!t) return LRC_OK;
     if (t->ctx) (void)hipSetDevice(t->ctx->device);
     if (t->d_dirs3) (void)hipFree(t->d_dirs3);
+    if (t->d_fire) (void)hipFree(t->d_fire);
     delete t;
     return LRC_OK;
 }
@@ -3563,6 +3607,74 @@ int lrc_scan_table_compact(lrc_scene* s, const double* poses16, uint64_t P, cons
         if (rc) return rc;
     }
     return scan_compact_impl(s, poses16, P, nullptr, table->n, grid, max_range, out, capacity, out_total, table->d_dirs3);
+}
+
+int lrc_table_set_fire(lrc_table* t, const double* fire, uint64_t N) {
+    if (!t) return fail(LRC_ERR_INVALID_ARG, "lrc_table_set_fire: table is NULL");
+    if (!fire) {
+        if (t->d_fire) { (void)hipSetDevice(t->ctx->device); (void)hipFree(t->d_fire); t->d_fire = nullptr; }
+        return LRC_OK;
+    }
+    if (N != t->n) return fail(LRC_ERR_INVALID_ARG, "lrc_table_set_fire: the fire table must have one entry per ray of the table");
+    for (uint64_t i = 0; i < N; ++i)
+        if (!(fire[i] >= 0.0 && fire[i] < 1.0))     // NaN fails both
+            return fail(LRC_ERR_INVALID_ARG, "lrc_table_set_fire: fire[" + std::to_string(i) + "] is outside [0, 1)");
+    LRC_HIP(hipSetDevice(t->ctx->device));
+    if (!t->d_fire) LRC_HIP(hipMalloc((void**)&t->d_fire, N * 8));
+    LRC_HIP(hipMemcpy(t->d_fire, fire, N * 8, hipMemcpyHostToDevice));
+    return LRC_OK;
+}
+
+// Host check of (P,24) motion records (lrc_scan_sweeps_compact): finite, dq.w >= cos(pi/4) (a rotation of at most pi/2 per
+// sweep, where the nlerp error table of include/lidarcast.h holds), |dq| = 1 to 1e-6.
+static int check_motion(const char* who, const double* m, uint64_t P) {
+    constexpr double kCosQuarterPi = 0.70710678118654752440;
+    for (uint64_t k = 0; k < P; ++k) {
+        const double* r = m + k * 24;
+        for (int j = 0; j < 24; ++j)
+            if (!std::isfinite(r[j]))
+                return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) + " is not finite");
+        if (r[12] < kCosQuarterPi)
+            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) +
+                                                 " rotates by more than pi/2 per sweep (dq.w < cos(pi/4))");
+        const double n = ((r[12] * r[12] + r[13] * r[13]) + r[14] * r[14]) + r[15] * r[15];
+        if (!(std::fabs(n - 1.0) <= 1e-6))
+            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) + " has a non-unit dq");
+    }
+    return LRC_OK;
+}
+
+int lrc_scan_sweeps_compact(lrc_scene* s, const double* motion24, uint64_t P, const lrc_table* table, double max_range,
+                            const lrc_frames* out, uint64_t capacity, uint64_t* out_total) {
+    if (out_total) *out_total = 0;
+    if (!s || !out || !table) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_compact: NULL scene, table or output");
+    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_compact: table and scene belong to different contexts");
+    if (!table->d_fire) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_compact: the table has no fire table (lrc_table_set_fire)");
+    const uint64_t N = table->n, n = P * N;
+    if (!n) return LRC_OK;
+    if (!motion24 || !out->counts) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_compact: motion24 or counts is NULL");
+    int rc = check_motion("lrc_scan_sweeps_compact", motion24, P);
+    if (rc) return rc;
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    SyncUnlessOk guard;
+    DevBuf dm;
+    if ((rc = ensure_streams(s->ctx))) return rc;
+    hipStream_t in = s->ctx->s_compute;       // inputs travel on the stream that consumes them
+    if ((rc = dm.get(s->ctx, kPoolPoses, P * 192))) return rc;
+    LRC_HIP(hipMemcpyAsync(dm.p, motion24, P * 192, hipMemcpyHostToDevice, in));
+    FrameStage st;
+    if ((rc = st.alloc(s->ctx, *out, P, n))) return rc;
+    NoiseStage ns;
+    if ((rc = ns.begin(s, n))) return rc;
+    TraceParams p{};
+    p.motion24 = (const double*)dm.p;
+    p.dirs3 = table->d_dirs3;
+    p.fire = table->d_fire;
+    p.rays_per_pose = N;
+    p.total = n;
+    p.has_center = 1;
+    p.max_range = max_range;
+    return guard.done(frames_finish(s, p, 4, st, P, N, out, capacity, out_total));
 }
 
 int lrc_scan_poses_compact(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,

@@ -211,6 +211,50 @@ LRC_DI void gen_ray_angles(const double* poses16, uint64_t pose, double phi, dou
     o.x = (float)cx; o.y = (float)cy; o.z = (float)cz;
 }
 
+// ---- moving-sensor sweeps (lrc_scan_sweeps_*; include/lidarcast.h "moving-sensor sweeps") ----
+// Motion record of sweep k, 24 float64: M[0..11] the start pose's first three rows (as poses16), M[12..15] dq = (w, x, y, z)
+// with R_end = R(dq) R_start and w >= cos(pi/4), M[16..18] dc = c_end - c_start, the rest zero.  s = fire[i] in [0, 1).
+// Every operation is a separate IEEE float64 operation in exactly this order (the file is built with -ffp-contract=off;
+// tests/test_sweep_host.py restates it op for op in numpy):
+//   centre   cs_j = s * dc_j;  c_j = (cs_j == 0) ? c0_j : c0_j + cs_j        (the select keeps a -0.0 start centre bit for bit)
+//   rotation qw = (1 - s) + s * dq.w;  u = (s * dq.x, s * dq.y, s * dq.z)     (nlerp, never normalised)
+//            n = ((qw*qw + ux*ux) + uy*uy) + uz*uz;  k = 2 / n
+//            t = u x v:  tx = uy*vz - uz*vy,  ty = uz*vx - ux*vz,  tz = ux*vy - uy*vx
+//            w = u x t:  wx = uy*tz - uz*ty,  wy = uz*tx - ux*tz,  wz = ux*ty - uy*tx
+//            v'_j = v_j + k * (qw * t_j + w_j)
+// v is gen_ray's float64 world direction (dgemm_row): s = 0 adds only signed zeros to it (dgemm_row never yields -0.0), so the
+// static ray comes out bit for bit.
+LRC_DI void sweep_centre(const double* M, double s, double& cx, double& cy, double& cz) {
+    const double sx = s * M[16], sy = s * M[17], sz = s * M[18];
+    cx = sx == 0.0 ? M[3] : M[3] + sx;
+    cy = sy == 0.0 ? M[7] : M[7] + sy;
+    cz = sz == 0.0 ? M[11] : M[11] + sz;
+}
+
+// Ray (k, i) of a moving-sensor sweep: direction = float32(rotate(v, q(s))), origin = float32(c(s)).
+LRC_DI void gen_ray_sweep(const double* motion24, const double* dirs3, const double* fire, uint64_t k, uint64_t i, V3& o,
+                          V3& d) {
+    const double* M = motion24 + k * 24;
+    const double* dv = dirs3 + i * 3;
+    const double a = dv[0], b = dv[1], c = dv[2];
+    const double vx = dgemm_row(a, b, c, M[0], M[1], M[2]);
+    const double vy = dgemm_row(a, b, c, M[4], M[5], M[6]);
+    const double vz = dgemm_row(a, b, c, M[8], M[9], M[10]);
+    const double s = fire[i];
+    const double qw = (1.0 - s) + s * M[12];
+    const double ux = s * M[13], uy = s * M[14], uz = s * M[15];
+    const double n = ((qw * qw + ux * ux) + uy * uy) + uz * uz;
+    const double kk = 2.0 / n;
+    const double tx = uy * vz - uz * vy, ty = uz * vx - ux * vz, tz = ux * vy - uy * vx;
+    const double wx = uy * tz - uz * ty, wy = uz * tx - ux * tz, wz = ux * ty - uy * tx;
+    d.x = (float)(vx + kk * (qw * tx + wx));
+    d.y = (float)(vy + kk * (qw * ty + wy));
+    d.z = (float)(vz + kk * (qw * tz + wz));
+    double cx, cy, cz;
+    sweep_centre(M, s, cx, cy, cz);
+    o.x = (float)cx; o.y = (float)cy; o.z = (float)cz;
+}
+
 // p = o + (d/|d|)*t : numpy float32, one rounding per operation (reference: raycast_engine_cpu.py:57-62).
 // h receives the normalised direction.
 LRC_DI void hit_point(V3 o, V3 d, float t, V3& h, V3& pt) {

@@ -69,6 +69,14 @@ class IndoorLidar:
             return self.directions_uniform(k.fov_up, k.fov_down, k.vertical_res, k.horizontal_res).astype(np.float64)
         return self.directions_from_vertical_degrees(k.vertical_degrees, k.horizontal_res)
 
+    def firing_fractions(self):
+        """(N,) float64 fraction of the sweep at which each ray of ``sensor_directions()`` fires, in [0, 1): the sensor
+        fires column after column (all lines of a column at once), so ray i = line * W + column fires at column / W.
+        The firing table of a moving-sensor sweep (lidarcast.Scene.scan_sweeps_compact)."""
+        W = max(1, int(self.intrinsics.horizontal_res))
+        N = self.get_total_rays()
+        return (np.arange(N) % W) / W
+
     # -- world-frame rays ---------------------------------------------------------------------------
     def get_rays(self) -> np.ndarray:
         k = self.intrinsics

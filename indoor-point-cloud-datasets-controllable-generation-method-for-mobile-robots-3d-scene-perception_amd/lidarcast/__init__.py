@@ -1,14 +1,14 @@
 """lidarcast -- Python face of liblidarcast, the MI355X-native LiDAR ray-cast scan engine."""
 from ._capi import LIB_PATH, LRC_INVALID_PRIM, LidarcastError, load
 from .core import (ATTRS, FRAME_ATTRS, Context, DeviceHits, DirectionTable, NearestIndex, OccupancyIndex, PinnedPool, ScanPipe, Scene,
-                   bake_triangle_labels)
+                   bake_triangle_labels, motion_records)
 from .boxes import BOX_DTYPE, instance_boxes, instance_boxes_dev
 from .preprocess import (Preprocessed, estimate_normals, preprocess_cloud, preprocess_cloud_dev,
                          remove_statistical_outlier)
 from .objboxes import OBJBOX_DTYPE, ObjectBoxes, object_boxes, object_boxes_dev
 
 __all__ = ["LIB_PATH", "LRC_INVALID_PRIM", "LidarcastError", "load", "ATTRS", "Context",
-           "DeviceHits", "DirectionTable", "Scene", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "BOX_DTYPE", "instance_boxes", "instance_boxes_dev",
+           "DeviceHits", "DirectionTable", "Scene", "motion_records", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "BOX_DTYPE", "instance_boxes", "instance_boxes_dev",
            "Preprocessed", "preprocess_cloud", "preprocess_cloud_dev", "remove_statistical_outlier", "estimate_normals",
            "OBJBOX_DTYPE", "ObjectBoxes", "object_boxes", "object_boxes_dev", "version",
            "device_count"]

@@ -334,9 +334,10 @@ class DeviceHits:
 
 
 class DirectionTable:
-    """A sensor's (N,3) float64 direction table resident in HBM (lrc_table_create): per-pose callers upload it once."""
+    """A sensor's (N,3) float64 direction table resident in HBM (lrc_table_create): per-pose callers upload it once.
+    ``fire``: optional (N,) float64 firing fractions in [0, 1) for moving-sensor sweeps (lrc_table_set_fire), resident too."""
 
-    def __init__(self, ctx, dirs):
+    def __init__(self, ctx, dirs, fire=None):
         self._lib = _capi.load()
         self.ctx = ctx
         d = np.ascontiguousarray(dirs, dtype=np.float64)
@@ -345,6 +346,22 @@ class DirectionTable:
         h = C.c_void_p()
         check(self._lib.lrc_table_create(ctx._h, _ptr(d), len(d), C.byref(h)), "lrc_table_create")
         self._h, self.n = h, len(d)
+        self.fire = None
+        if fire is not None:
+            self.set_fire(fire)
+
+    def set_fire(self, fire):
+        """Attach (or, with None, detach) the firing fractions; checked and uploaded once by the library."""
+        if not self._h:
+            raise ValueError("direction table handle is closed")
+        if fire is None:
+            check(self._lib.lrc_table_set_fire(self._h, None, 0), "lrc_table_set_fire")
+            self.fire = None
+            return
+        f = np.array(fire, dtype=np.float64, copy=True).reshape(-1)
+        check(self._lib.lrc_table_set_fire(self._h, _ptr(f), f.size), "lrc_table_set_fire")
+        f.setflags(write=False)
+        self.fire = f
 
     def __len__(self):
         return self.n
@@ -619,6 +636,38 @@ class Scene:
                                                    C.byref(fr), cap, C.byref(total)), "lrc_scan_poses_compact")
         return self._frames_end(counts, bufs, total.value)
 
+    def scan_sweeps_compact(self, motion, dirs, fire, max_range, want=("point3", "sem", "ins"), capacity=None):
+        """Moving-sensor sweeps straight to frames (lrc_scan_sweeps_compact): ``motion`` (P, 24) records
+        (``motion_records``), ``dirs`` a DirectionTable or an (N, 3) table, ``fire`` (N,) firing fractions in [0, 1) --
+        None takes the DirectionTable's resident ones; a different table than the resident one is uploaded into it.
+        Same return value as ``scan_poses_compact``."""
+        motion = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 24)
+        own = None
+        if isinstance(dirs, DirectionTable):
+            if not dirs._h:
+                raise ValueError("direction table handle is closed")
+            if dirs.ctx is not self.ctx:
+                raise ValueError("direction table belongs to another context (device)")
+            if fire is not None and (dirs.fire is None or not np.array_equal(dirs.fire, np.asarray(fire, np.float64).reshape(-1))):
+                dirs.set_fire(fire)
+            table = dirs
+        else:
+            if fire is None:
+                raise ValueError("fire is required with a plain direction table")
+            table = own = DirectionTable(self.ctx, dirs, fire)
+        if table.fire is None:
+            raise ValueError("the direction table has no firing fractions")
+        try:
+            P, N = motion.shape[0], table.n
+            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
+            total = C.c_uint64(0)
+            check(self._lib.lrc_scan_sweeps_compact(self._h, _ptr(motion), P, table._h, float(max_range), C.byref(fr), cap,
+                                                    C.byref(total)), "lrc_scan_sweeps_compact")
+            return self._frames_end(counts, bufs, total.value)
+        finally:
+            if own is not None:
+                own.close()
+
     def scan_angles_compact(self, poses, angles, keep, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Dual-axis sensor, rays generated in the kernel from host-drawn (phi, theta) (lrc_scan_angles_compact).
         angles: (P, N, 2) float64; keep: (P, N) bool / uint8 or None."""
@@ -696,6 +745,16 @@ class Scene:
                                            C.byref(hits.struct), C.c_void_p(int(stream))),
               "lrc_scan_poses_dev")
 
+    def scan_sweeps_dev(self, motion_t, dirs_t, fire_t, hits, max_range, stream=0):
+        """Moving-sensor sweeps on device tensors (lrc_scan_sweeps_dev): motion_t (P, 24) float64, dirs_t (N, 3) float64,
+        fire_t (N,) float64; the caller vouches for the records and the fire table (see motion_records)."""
+        P, N = motion_t.shape[0], dirs_t.shape[0]
+        if motion_t.numel() != P * 24 or fire_t.numel() != N:
+            raise ValueError("motion_t must be (P, 24) and fire_t (N,)")
+        check(self._lib.lrc_scan_sweeps_dev(self._h, C.c_void_p(motion_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()),
+                                            C.c_void_p(fire_t.data_ptr()), N, float(max_range), C.byref(hits.struct),
+                                            C.c_void_p(int(stream))), "lrc_scan_sweeps_dev")
+
     def cloud_from_prims_dev(self, poses_t, dirs_t, prim_t, out_rows_t, counts_t=None, tile_count_t=None,
                              poses_per_slab=0, slab_stride_bytes=0, stream=0, own_slab=None, own_io=None):
         """Rebuild the compacted (x, y, z, label) rows of a pose-batched scan from its 4-byte triangle ids
@@ -717,6 +776,71 @@ class Scene:
             int(poses_per_slab), int(slab_stride_bytes), C.c_void_p(out_rows_t.data_ptr()),
             None if counts_t is None else C.c_void_p(counts_t.data_ptr()), C.c_void_p(int(stream))),
             "lrc_cloud_from_prims_dev")
+
+
+COS_QUARTER_PI = 0.7071067811865476     # dq.w below this: a rotation of more than pi/2 per sweep
+
+
+def _quat_from_matrix(R):
+    """(P,3,3) rotation matrices -> (P,4) unit quaternions (w, x, y, z), w >= 0: Shepperd's method (the largest of the four
+    diagonal combinations is taken as the pivot, so no division by a small number)."""
+    R = np.asarray(R, dtype=np.float64)
+    m00, m11, m22 = R[:, 0, 0], R[:, 1, 1], R[:, 2, 2]
+    piv = np.stack([m00 + m11 + m22, m00, m11, m22], axis=1).argmax(axis=1)
+    q = np.empty((len(R), 4))
+    for case in range(4):
+        k = piv == case
+        if not k.any():
+            continue
+        r = R[k]
+        a, b, c = r[:, 0, 0], r[:, 1, 1], r[:, 2, 2]
+        if case == 0:
+            w = 0.5 * np.sqrt(np.maximum(1.0 + a + b + c, 0.0))
+            f = 0.25 / w
+            q[k] = np.stack([w, (r[:, 2, 1] - r[:, 1, 2]) * f, (r[:, 0, 2] - r[:, 2, 0]) * f, (r[:, 1, 0] - r[:, 0, 1]) * f], 1)
+        elif case == 1:
+            x = 0.5 * np.sqrt(np.maximum(1.0 + a - b - c, 0.0))
+            f = 0.25 / x
+            q[k] = np.stack([(r[:, 2, 1] - r[:, 1, 2]) * f, x, (r[:, 0, 1] + r[:, 1, 0]) * f, (r[:, 0, 2] + r[:, 2, 0]) * f], 1)
+        elif case == 2:
+            y = 0.5 * np.sqrt(np.maximum(1.0 - a + b - c, 0.0))
+            f = 0.25 / y
+            q[k] = np.stack([(r[:, 0, 2] - r[:, 2, 0]) * f, (r[:, 0, 1] + r[:, 1, 0]) * f, y, (r[:, 1, 2] + r[:, 2, 1]) * f], 1)
+        else:
+            z = 0.5 * np.sqrt(np.maximum(1.0 - a - b + c, 0.0))
+            f = 0.25 / z
+            q[k] = np.stack([(r[:, 1, 0] - r[:, 0, 1]) * f, (r[:, 0, 2] + r[:, 2, 0]) * f, (r[:, 1, 2] + r[:, 2, 1]) * f, z], 1)
+    q[q[:, 0] < 0] *= -1.0
+    return q / np.linalg.norm(q, axis=1, keepdims=True)
+
+
+def motion_records(start_poses, end_poses):
+    """(P, 24) float64 motion records of P sweeps (include/lidarcast.h "moving-sensor sweeps"): the start pose's first three
+    rows, dq = (w, x, y, z) from R_end R_start^T (w >= 0) and dc = c_end - c_start.  Equal start and end poses give
+    dq = (1, 0, 0, 0) and dc = 0 exactly, i.e. the static scan.  Raises ValueError on non-finite poses and on a rotation of
+    more than pi/2 per sweep."""
+    a = np.ascontiguousarray(start_poses, dtype=np.float64).reshape(-1, 4, 4)
+    b = np.ascontiguousarray(end_poses, dtype=np.float64).reshape(-1, 4, 4)
+    if a.shape != b.shape:
+        raise ValueError("start_poses and end_poses must have the same number of (4, 4) poses")
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        raise ValueError("poses must be finite")
+    P = a.shape[0]
+    rec = np.zeros((P, 24))
+    rec[:, :12] = a.reshape(P, 16)[:, :12]
+    if P == 0:
+        return rec
+    dq = _quat_from_matrix(b[:, :3, :3] @ np.swapaxes(a[:, :3, :3], 1, 2))
+    dc = b[:, :3, 3] - a[:, :3, 3]
+    same = (a == b).all(axis=(1, 2))      # R R^T is not bitwise the identity: the static sweep is set exactly
+    dq[same] = (1.0, 0.0, 0.0, 0.0)
+    dc[same] = 0.0
+    if (dq[:, 0] < COS_QUARTER_PI).any():
+        k = int(np.argmax(dq[:, 0] < COS_QUARTER_PI))
+        raise ValueError(f"sweep {k} rotates by {2 * np.arccos(min(dq[k, 0], 1.0)):.3f} rad: at most pi/2 per sweep")
+    rec[:, 12:16] = dq
+    rec[:, 16:19] = dc
+    return rec
 
 
 class ScanPipe:

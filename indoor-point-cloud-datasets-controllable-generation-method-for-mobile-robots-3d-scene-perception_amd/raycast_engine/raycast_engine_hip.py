@@ -168,6 +168,7 @@ class RaycastEngineHIP(RaycastEngineBase):
         self._dir_tables = {}
         self._grids = {}
         self._dev_tables = {}
+        self._fire_tables = {}
         # The packet kernel (lrc_scan_grid_*, csrc/lrc_sector.h) returns the same bytes as the per-ray kernel and is
         # kept as a measured alternative: on the benchmark scenes it is 3-10x SLOWER, so it is
         # off unless asked for.
@@ -361,6 +362,41 @@ class RaycastEngineHIP(RaycastEngineBase):
         return self.scene_for(mesh).scan_poses_compact(poses, self._resident_table(intrinsics),
                                                        intrinsics.max_range, want=want,
                                                        grid=self._grid_of(intrinsics, len(poses)))
+
+    def _firing_fractions(self, intrinsics):
+        """(N,) firing fractions of the sensor's direction table (IndoorLidar.firing_fractions), cached with the table."""
+        from lidar import IndoorLidar
+        tab = self._direction_table(intrinsics)
+        ent = self._fire_tables.get(id(tab))
+        if ent is None or ent[0] is not tab:
+            ent = (tab, IndoorLidar(intrinsics, np.eye(4)).firing_fractions())
+            if len(self._fire_tables) >= 8:
+                self._fire_tables.pop(next(iter(self._fire_tables)))
+            self._fire_tables[id(tab)] = ent
+        return ent[1]
+
+    def sweep_inputs(self, intrinsics, start_poses, end_poses):
+        """(motion records (P, 24), firing fractions (N,), sweep period T) of the moving-sensor sweeps from start_poses[k]
+        to end_poses[k]: what ``scan_sweep_frames`` scans, for callers that rescan the same sweeps."""
+        from lidarcast import motion_records
+        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
+            raise NotImplementedError("moving-sensor sweeps need a sensor with a pose-independent direction table")
+        motion = motion_records(start_poses, end_poses)
+        return motion, self._firing_fractions(intrinsics), 1.0 / float(intrinsics.scan_frequency)
+
+    def scan_sweep_frames(self, intrinsics, start_poses, end_poses, mesh, want=("point3", "sem", "ins"), inputs=None):
+        """Moving-sensor sweeps straight to frames (lrc_scan_sweeps_compact): sweep k moves from start_poses[k] to
+        end_poses[k] during one period T = 1 / scan_frequency, and ray i fires at fraction (i mod W) / W of it.  Same dict
+        as ``scan_frames`` plus ``point_times``: (K,) float64 seconds since the start of the point's sweep.
+        ``inputs``: a ``sweep_inputs`` triple to scan exactly those records again."""
+        motion, fire, T = inputs if inputs is not None else self.sweep_inputs(intrinsics, start_poses, end_poses)
+        ask = tuple(want) + (() if "index" in want else ("index",))
+        fr = self.scene_for(mesh).scan_sweeps_compact(motion, self._resident_table(intrinsics), fire, intrinsics.max_range,
+                                                      want=ask)
+        fr["point_times"] = fire[fr["index"]] * T
+        if "index" not in want:
+            del fr["index"]
+        return fr
 
     def scan_frames_lidars(self, lidars, mesh, want=("point3", "sem", "ins")):
         """The bit-exact default path of the dual-axis sensor, straight to frames: every pose's rays come from the host

@@ -22,7 +22,8 @@ import numpy as np
 from containers import RoomBounds, S3DISScene, S3DISSimFrame, S3DISSimScene, ScanQuality
 from lidar import (DualAxisLidarIntrinsics, Indoor8LineLidarIntrinsics, create_lidar)
 from raycast_engine import RaycastEngineCPU, RaycastEngineGPU
-from trajectory import AutoTrajectoryGenerator, PathType, SmartTrajectoryGenerator, Waypoint, poses_from_waypoints
+from trajectory import (AutoTrajectoryGenerator, PathType, SmartTrajectoryGenerator, Waypoint, poses_from_waypoints,
+                        sweep_end_poses)
 
 
 _POOL = None             # thread pool of _quality_many, created on first use
@@ -231,7 +232,21 @@ class S3DISSimulator:
         fr = None
         from lidarcast.distributed import active_group, scan_frames_sharded, scan_lidars_sharded
         dist, group = (None, None) if process_group is _NO_GROUP else active_group(process_group)
-        if dist is not None and len(waypoints) > 0:
+        # opt-in moving-sensor sweeps (config key ``motion: {speed: m/s}``): every ray is cast from the pose of the sensor at
+        # the moment it fires; frames then carry per-point times.  Without the key nothing changes.
+        motion = self.config.get("motion")
+        sweep = None
+        if motion is not None and len(waypoints) > 0:
+            if dist is not None:
+                raise NotImplementedError("moving-sensor sweeps are not available on a multi-rank process group")
+            if not isinstance(self.lidar_config, Indoor8LineLidarIntrinsics):
+                raise NotImplementedError("moving-sensor sweeps need a multi-line sensor (not the dual-axis sensor)")
+            start_poses = poses_from_waypoints(waypoints)
+            end_poses = sweep_end_poses(waypoints, self.lidar_config.scan_frequency, float(motion.get("speed", 0.0)))
+            sweep = engine.sweep_inputs(self.lidar_config, start_poses, end_poses)
+        if sweep is not None:
+            fr = engine.scan_sweep_frames(self.lidar_config, None, None, mesh, want=want, inputs=sweep)
+        elif dist is not None and len(waypoints) > 0:
             if batched:
                 fr = scan_frames_sharded(engine, self.lidar_config, poses_from_waypoints(waypoints), mesh, dist, group)
             else:
@@ -277,10 +292,10 @@ class S3DISSimulator:
             if "sem" in fr:
                 sem_f, ins_f = ([fr[a][e - c:e] for c, e in zip(counts_l, ends_l)] for a in ("sem", "ins"))
                 src_f = itertools.repeat(None)
-            else:      # labels on demand: one labels-only scan of the trajectory, shared by its frames
+            else:      # labels on demand: one labels-only scan of the trajectory (of the SAME sweeps), shared by its frames
                 sem_f = ins_f = itertools.repeat(None)
                 src_f = itertools.repeat(_LazyTrajectoryLabels(engine, self.lidar_config, poses_from_waypoints(waypoints),
-                                                               mesh, counts_l))
+                                                               mesh, counts_l, sweep))
             if "range_origin_mean" in fr:      # statistics from the device
                 qual = self._quality_from_stats(fr, total, volume)
             else:
@@ -288,8 +303,12 @@ class S3DISSimulator:
                 # the GIL, so the frames of a long trajectory are reduced side by side (same numpy calls, same values)
                 qual = self._quality_many(pts_f, ang_f, total, volume, engine.split_frames(fr, "range_origin"))
         if fr is not None:
+            first = len(sim_scene.frames)
             sim_scene.frames.extend(map(S3DISSimFrame, range(len(waypoints)), pts_f, ang_f, qual, itertools.repeat(None),
                                         sem_f, ins_f, src_f))
+            if "point_times" in fr:        # seconds since the start of the frame's sweep, per point
+                for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
+                    f.point_times = fr["point_times"][e - c:e]
         for i, wp in enumerate(waypoints if fr is None else ()):
             a, b = off[i], off[i + 1]
             keep = seg["t"][a:b] != np.inf
@@ -309,8 +328,10 @@ class _LazyTrajectoryLabels:
     of the same poses over the same mesh (the scan is a pure function of both: same kept rays, same order), whose result
     all frames of the trajectory share."""
 
-    def __init__(self, engine, intrinsics, poses, mesh, counts):
+    def __init__(self, engine, intrinsics, poses, mesh, counts, sweep=None):
+        # sweep: the (motion records, fire table, period) of a moving-sensor scan -- rescanned exactly, never as static poses
         self._args = (engine, intrinsics, np.array(poses, dtype=np.float64, copy=True), mesh)
+        self._sweep = sweep
         self._counts = list(counts)
         self._sem = self._ins = None
         import threading
@@ -320,11 +341,14 @@ class _LazyTrajectoryLabels:
         with self._lock:
             if self._sem is None:
                 engine, intrinsics, poses, mesh = self._args
-                fr = engine.scan_frames(intrinsics, poses, mesh, want=("sem", "ins"))
+                if self._sweep is not None:
+                    fr = engine.scan_sweep_frames(intrinsics, None, None, mesh, want=("sem", "ins"), inputs=self._sweep)
+                else:
+                    fr = engine.scan_frames(intrinsics, poses, mesh, want=("sem", "ins"))
                 if fr["counts"].tolist() != self._counts:
                     raise RuntimeError("the mesh or the scan options changed between the scan and the first look at its labels")
                 self._sem, self._ins, self._ends = fr["sem"], fr["ins"], list(itertools.accumulate(self._counts))
-                self._args = None
+                self._args = self._sweep = None
         e, c = self._ends[i], self._counts[i]
         return self._sem[e - c:e], self._ins[e - c:e]
 

@@ -2,7 +2,7 @@
 from enum import Enum
 
 from .trajectory_generator import (TrajectoryGeneratorBase, Waypoint, TrajectoryQuality, poses_from_waypoints,
-                                   line_trajectory)
+                                   line_trajectory, sweep_end_poses)
 from .auto_trajectory_generator import AutoTrajectoryGenerator, RoomAnalysis, TrajectoryCandidate
 
 
@@ -28,5 +28,5 @@ class SmartTrajectoryGenerator(TrajectoryGeneratorBase):
         return wps, self.evaluate_trajectory_quality(wps)
 
 
-__all__ = ["TrajectoryGeneratorBase", "Waypoint", "TrajectoryQuality", "poses_from_waypoints", "line_trajectory", "AutoTrajectoryGenerator",
+__all__ = ["TrajectoryGeneratorBase", "Waypoint", "TrajectoryQuality", "poses_from_waypoints", "sweep_end_poses", "line_trajectory", "AutoTrajectoryGenerator",
            "RoomAnalysis", "TrajectoryCandidate", "PathType", "SmartTrajectoryGenerator"]

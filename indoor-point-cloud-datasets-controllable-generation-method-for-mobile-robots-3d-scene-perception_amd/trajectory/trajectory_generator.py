@@ -150,6 +150,46 @@ def poses_from_waypoints(waypoints: List[Waypoint]) -> np.ndarray:
     return out
 
 
+def sweep_end_poses(waypoints: List[Waypoint], scan_frequency: float, speed: float) -> np.ndarray:
+    """(P,4,4) float64 end poses of the sweeps of a moving sensor, one per waypoint (the start poses are
+    ``poses_from_waypoints``).  Sweep k lasts T = 1 / scan_frequency and ends at the point of the piecewise-linear path
+    through the waypoints v * T metres past waypoint k, v = waypoint k's ``velocity`` if set, else ``speed``; the yaw is
+    interpolated along each segment by the shortest angle, and waypoint k's ``angular_velocity``, if set, adds w * T of yaw.
+    The path is clamped at the last waypoint, whose sweep is static.  A sweep that moves nothing ends exactly at its start."""
+    start = poses_from_waypoints(waypoints)
+    end = start.copy()
+    n = len(waypoints)
+    if n == 0:
+        return end
+    if not (scan_frequency > 0):
+        raise ValueError("scan_frequency must be positive")
+    T = 1.0 / float(scan_frequency)
+    pts = np.array([[w.x, w.y, w.z] for w in waypoints], dtype=np.float64)
+    seg = np.linalg.norm(pts[1:] - pts[:-1], axis=1) if n > 1 else np.zeros(0)
+    for k in range(n - 1):
+        w = waypoints[k]
+        v = float(w.velocity) if w.velocity is not None else float(speed)
+        if v < 0:
+            raise ValueError("speed and waypoint velocities must be non-negative")
+        dist = v * T
+        turn = float(w.angular_velocity) * T if w.angular_velocity is not None else 0.0
+        if dist == 0.0 and turn == 0.0:
+            continue                                   # static sweep: the end pose IS the start pose
+        j, left = k, dist
+        while j < n - 1 and left > seg[j]:
+            left -= seg[j]
+            j += 1
+        if j == n - 1:                                 # past the end of the path: clamped at the last waypoint
+            p, yaw = pts[-1], float(waypoints[-1].yaw)
+        else:
+            f = left / seg[j] if seg[j] > 0 else 0.0
+            p = pts[j] + f * (pts[j + 1] - pts[j])
+            dyaw = (float(waypoints[j + 1].yaw) - float(waypoints[j].yaw) + np.pi) % (2 * np.pi) - np.pi
+            yaw = float(waypoints[j].yaw) + f * dyaw
+        end[k] = Waypoint(float(p[0]), float(p[1]), float(p[2]), yaw + turn).to_pose_matrix()
+    return end
+
+
 def line_trajectory(start, end, num_waypoints: int, yaw: float = 0.0) -> List[Waypoint]:
     """Evenly spaced, pure-translation waypoints: the shape auto trajectories have in the reference
     (trajectory/auto_trajectory_generator.py:61-62,83,122 -- every waypoint yaw=0, fixed height)."""
