@@ -729,6 +729,81 @@ int lrc_occ_create(lrc_ctx* ctx, const double* verts3, uint64_t num_vertices, lr
 int lrc_occ_destroy(lrc_occ* occ);
 int lrc_occ_query(lrc_occ* occ, const double* points3, uint64_t num_points, double half, uint8_t* out_flags);
 
+/* ---- surface coverage of scans ------------------------------------------------------------
+ * Which triangles of a mesh did a set of scans return points from, how much area is that, per semantic class, and which
+ * few pose sets cover the most.  Definitions:
+ *   returned ray   : a ray returns a point iff its t is finite after the range filter (exactly the rows compaction keeps).
+ *                    A ray with a valid prim but t = +inf (removed by the range filter) returns nothing, nor does
+ *                    prim == LRC_INVALID_PRIM.  A prim >= num_triangles is ignored as well.
+ *   seen triangle  : triangle j is seen by a set of poses iff at least one returned ray of those poses has prim == j.
+ *   hits[j]        : the number of returned rays with prim == j, over all sets (uint32, wraps past 2^32 - 1).
+ *   area           : float64, 0.5 * sqrt((cx*cx + cy*cy) + cz*cz), c = (v1 - v0) x (v2 - v0) component by component as
+ *                    a*b - c*d; no fused multiply-add anywhere, correctly rounded sqrt (computed on the device).
+ *   quantised area : q[j] = uint64(rint(area * 2^32)); every area sum is an exact uint64 sum of q (order-free, bit-
+ *                    reproducible).  A mesh whose total q would exceed 2^63 is refused with LRC_ERR_INVALID_ARG.
+ *   covered area   = covered_q * 2^-32 m^2, ratio = covered_q / total_q, redundancy = returned rays / covered area.
+ * Sampling caveat: a tiny triangle can lie between two scan lines of every pose, so "seen" means "received at least one
+ * return"; the sampled result converges on the visible area as the number of poses grows.  No dilation is applied.
+ *
+ * A coverage object holds num_sets bitsets of ceil(T/32) uint32 words each (bit j of word j/32, LSB first), hits and the
+ * returned-ray count of every set; they start at zero and repeated accumulations add up.  Per-class sums are kept per
+ * distinct tri_sem value (at most 4096), indexed densely in ascending label order (lrc_coverage_classes); without
+ * tri_sem there are no classes.  Vertices (V,3) float64 must be finite, triangles (T,3) int32 in [0, V), 0 < T < 2^32-1.
+ * The object is not thread-safe; "_dev" entry points enqueue on `stream`, the others return after the work finished. */
+typedef struct lrc_coverage lrc_coverage;
+
+typedef struct lrc_coverage_info {
+    uint64_t num_triangles;
+    uint64_t num_sets;
+    uint64_t words_per_set;    /* ceil(num_triangles / 32)                                         */
+    uint64_t total_q;          /* sum of q over the mesh                                           */
+    uint32_t num_classes;      /* distinct tri_sem values (0 without tri_sem)                     */
+    uint32_t reserved_;
+} lrc_coverage_info;           /* 40 bytes */
+
+typedef struct lrc_coverage_stats {
+    uint64_t covered_q;        /* sum of q over the seen triangles                                 */
+    uint64_t total_q;
+    uint64_t seen_triangles;
+    uint64_t returns;          /* returned rays accumulated into the set(s)                        */
+} lrc_coverage_stats;          /* 32 bytes; the _dev summary writes these four words in this order */
+
+int lrc_coverage_create(lrc_ctx* ctx, const double* verts3, uint64_t num_vertices, const int32_t* tris3,
+                        uint64_t num_triangles, const uint16_t* tri_sem /* nullable */, uint64_t num_sets,
+                        lrc_coverage** out_cov);
+int lrc_coverage_destroy(lrc_coverage* cov);
+int lrc_coverage_get_info(const lrc_coverage* cov, lrc_coverage_info* out);
+/* num_classes label values (ascending) and their total q; either pointer may be NULL. */
+int lrc_coverage_classes(const lrc_coverage* cov, uint16_t* out_class_ids, uint64_t* out_total_q);
+/* Zero every bitset, hits and the returned-ray counts. */
+int lrc_coverage_reset(lrc_coverage* cov, void* stream);
+/* d_t (float32) and d_prim (uint32) of num_poses x rays_per_pose rays, pose-major as lrc_scan_poses_dev writes them.
+ * Pose p goes to set d_set_of_pose[p] (device, num_poses entries; an entry >= num_sets drops that pose's rays) or, with
+ * NULL, to set p (then num_poses <= num_sets is required).  Integer atomics only: the result does not depend on order. */
+int lrc_coverage_accumulate_dev(lrc_coverage* cov, const float* d_t, const uint32_t* d_prim, uint64_t num_poses,
+                                uint64_t rays_per_pose, const uint32_t* d_set_of_pose /* nullable */, void* stream);
+/* Summary of set `set_index`, or of the union of all sets for set_index < 0: the stats, the per-class covered q
+ * (num_classes entries; may be NULL only without classes) and, optionally, the set's (or the union's) bitset
+ * (words_per_set words).  The _dev form writes the four stats words, the classes and the bits to device memory. */
+int lrc_coverage_summary(lrc_coverage* cov, int64_t set_index, lrc_coverage_stats* out, uint64_t* out_class_q,
+                         uint32_t* out_bits /* nullable */);
+int lrc_coverage_summary_dev(lrc_coverage* cov, int64_t set_index, uint64_t* d_out4, uint64_t* d_out_class_q,
+                             uint32_t* d_out_bits /* nullable */, void* stream);
+/* Greedy view selection over the object's sets.  covered starts as initial_bits (words_per_set words; NULL = empty);
+ * each round picks the set k with the largest gain_k = sum of q over the bits of (bits_k & ~covered), ties to the
+ * smallest k, and ORs it into covered.  Selection stops after `budget` picks, at a gain of 0, or as soon as
+ * covered_q / total_q >= target_ratio (target_ratio <= 0: no target; an initial cover that already reaches it picks
+ * nothing).  Writes the picks (uint32) and their gains (uint64 q units) in pick order and their number.  The rounds
+ * run on the device, the pick of round r read by the launches of round r + 1; the host form synchronises once. */
+int lrc_coverage_select(lrc_coverage* cov, uint32_t budget, double target_ratio, const uint32_t* initial_bits,
+                        uint32_t* out_picks, uint64_t* out_gains, uint32_t* out_num_picks);
+int lrc_coverage_select_dev(lrc_coverage* cov, uint32_t budget, double target_ratio, const uint32_t* d_initial_bits,
+                            uint32_t* d_out_picks, uint64_t* d_out_gains, uint32_t* d_out_num_picks, void* stream);
+/* Copy out every set's bitset (num_sets * words_per_set words), hits (num_triangles), the returned rays per set
+ * (num_sets) and the quantised area table q (num_triangles); NULL skips one. */
+int lrc_coverage_export(lrc_coverage* cov, uint32_t* out_bits, uint32_t* out_hits, uint64_t* out_returns,
+                        uint64_t* out_q);
+
 /* Resident waves per CU the runtime grants the pose-batched trace kernel on this scene (its LDS stack is sized by
  * the tree depth), its VGPR count and LDS bytes per wave: the occupancy figure bench.py reports. */
 int lrc_scene_get_occupancy(const lrc_scene* scene, int* waves_per_cu, int* vgprs, int* lds_bytes);

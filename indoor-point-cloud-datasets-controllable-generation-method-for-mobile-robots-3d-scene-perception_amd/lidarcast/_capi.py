@@ -41,6 +41,9 @@ SYMBOLS = (
     "lrc_instance_boxes", "lrc_instance_boxes_dev",
     "lrc_cloud_preprocess", "lrc_cloud_preprocess_dev",
     "lrc_object_boxes", "lrc_object_boxes_dev",
+    "lrc_coverage_create", "lrc_coverage_destroy", "lrc_coverage_get_info", "lrc_coverage_classes", "lrc_coverage_reset",
+    "lrc_coverage_accumulate_dev", "lrc_coverage_summary", "lrc_coverage_summary_dev", "lrc_coverage_select",
+    "lrc_coverage_select_dev", "lrc_coverage_export",
     "lrc_occ_create", "lrc_occ_destroy", "lrc_occ_query",
     "lrc_rng_scan_draws", "lrc_rays_from_trig",
 )
@@ -66,6 +69,16 @@ class LrcSceneInfo(C.Structure):
 class LrcScanOptions(C.Structure):
     _fields_ = [("min_range", C.c_double), ("range_noise", C.c_void_p), ("range_noise_len", C.c_uint64),
                 ("incident_mode", C.c_int)]
+
+
+class LrcCoverageInfo(C.Structure):
+    _fields_ = [("num_triangles", C.c_uint64), ("num_sets", C.c_uint64), ("words_per_set", C.c_uint64),
+                ("total_q", C.c_uint64), ("num_classes", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class LrcCoverageStats(C.Structure):
+    _fields_ = [("covered_q", C.c_uint64), ("total_q", C.c_uint64), ("seen_triangles", C.c_uint64),
+                ("returns", C.c_uint64)]
 
 
 class LrcCompactIO(C.Structure):
@@ -223,6 +236,17 @@ def load():
         "lrc_cloud_preprocess_dev": [vp, vp, u64, C.POINTER(LrcPreprocessOpts), vp, C.POINTER(u64), vp, vp, vp, vp, vp],
         "lrc_object_boxes": [vp, vp, u64, vp, u64, C.c_uint32, dbl, dbl, vp, vp, vp, vp],
         "lrc_object_boxes_dev": [vp, vp, u64, vp, u64, C.c_uint32, dbl, dbl, vp, vp, vp, vp, vp],
+        "lrc_coverage_create": [vp, vp, u64, vp, u64, vp, u64, C.POINTER(vp)],
+        "lrc_coverage_destroy": [vp],
+        "lrc_coverage_get_info": [vp, C.POINTER(LrcCoverageInfo)],
+        "lrc_coverage_classes": [vp, vp, vp],
+        "lrc_coverage_reset": [vp, vp],
+        "lrc_coverage_accumulate_dev": [vp, vp, vp, u64, u64, vp, vp],
+        "lrc_coverage_summary": [vp, C.c_int64, C.POINTER(LrcCoverageStats), vp, vp],
+        "lrc_coverage_summary_dev": [vp, C.c_int64, vp, vp, vp, vp],
+        "lrc_coverage_select": [vp, C.c_uint32, dbl, vp, vp, vp, vp],
+        "lrc_coverage_select_dev": [vp, C.c_uint32, dbl, vp, vp, vp, vp, vp],
+        "lrc_coverage_export": [vp, vp, vp, vp, vp],
         "lrc_nn_create": [vp, vp, u64, dbl, C.POINTER(vp)],
         "lrc_nn_destroy": [vp],
         "lrc_nn_query": [vp, vp, u64, vp, vp],

@@ -398,6 +398,44 @@ class RaycastEngineHIP(RaycastEngineBase):
             del fr["index"]
         return fr
 
+    # ---- surface coverage (lidarcast.coverage) --------------------------------------------------
+    def coverage_sets(self, intrinsics, poses, mesh, num_sets=None, set_of_pose=None, max_range=None, chunk_poses=None):
+        """Scan ``poses`` with a multi-line grid sensor and accumulate the returned rays into a new
+        lidarcast.SurfaceCoverage of ``num_sets`` sets (default: one set per pose, pose p -> set p)."""
+        from lidarcast import SurfaceCoverage, scan_coverage
+        if hasattr(intrinsics, "swing_amplitude") or not hasattr(intrinsics, "horizontal_res"):
+            raise NotImplementedError("surface coverage covers multi-line grid sensors only; the dual-axis sensor and "
+                                      "moving-sensor sweeps are outside its scope")
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        v, f, sem, _ = mesh_arrays(mesh)
+        S = len(poses) if num_sets is None else int(num_sets)
+        cov = SurfaceCoverage(self.ctx, v, f, sem, num_sets=max(1, S))
+        scan_coverage(self.scene_for(mesh), cov, poses, self._direction_table(intrinsics),
+                      intrinsics.max_range if max_range is None else float(max_range), set_of_pose=set_of_pose,
+                      chunk_poses=chunk_poses)
+        return cov
+
+    def surface_coverage(self, intrinsics, poses, mesh, max_range=None):
+        """Which triangles of ``mesh`` the scans from ``poses`` (P, 4, 4) returned points from: a
+        lidarcast.CoverageSummary (seen / hits per triangle, covered and total area, ratio, per class, redundancy)."""
+        P = len(np.asarray(poses).reshape(-1, 16))
+        cov = self.coverage_sets(intrinsics, poses, mesh, num_sets=1, set_of_pose=np.zeros(P, np.int64),
+                                 max_range=max_range)
+        try:
+            return cov.summary(0)
+        finally:
+            cov.close()
+
+    def select_views(self, intrinsics, candidate_poses, mesh, budget, target_ratio=None):
+        """Next-best-view list: one set per candidate pose, then greedy selection of at most ``budget`` poses by the area
+        each adds (ties to the smaller index), stopping at a gain of 0 or once covered / total area reaches
+        ``target_ratio``.  Returns (picks, gains_m2, cumulative_ratio), as lidarcast.SurfaceCoverage.select."""
+        cov = self.coverage_sets(intrinsics, candidate_poses, mesh)
+        try:
+            return cov.select(budget, target_ratio=target_ratio)
+        finally:
+            cov.close()
+
     def scan_frames_lidars(self, lidars, mesh, want=("point3", "sem", "ins")):
         """The bit-exact default path of the dual-axis sensor, straight to frames: every pose's rays come from the host
         generator (``all_rays_and_mask``: the reference's arithmetic and RNG draws, written into a page-locked buffer),

@@ -190,6 +190,21 @@ class S3DISSimulator:
             _POOL = ThreadPoolExecutor(max_workers=max(2, min(8, (os.cpu_count() or 2))))
         return list(_POOL.map(one, range(n)))
 
+    def evaluate_surface_coverage(self, waypoints: List[Waypoint]) -> Dict[str, Any]:
+        """What the scan of ``waypoints`` saw of the loaded room, JSON-ready: covered and total area,
+        ratio, seen triangles, returned rays, redundancy (returns per covered m^2) and per-class figures keyed by the S3DIS
+        class name where the label is a known class id.  Scans again on the GPU; run_simulation is not involved."""
+        if self.scene is None:
+            raise ValueError("Scene not loaded. Call load_scene() first.")
+        if self.config.get("motion") is not None:
+            raise NotImplementedError("surface coverage of moving-sensor sweeps is outside its scope")
+        from lidarcast.synth import S3DIS_CLASSES
+        s = self.raycast_engine.surface_coverage(self.lidar_config, poses_from_waypoints(waypoints),
+                                                 self.scene.room_mesh)
+        out = s.to_dict(class_names=dict(enumerate(S3DIS_CLASSES)))
+        out["num_poses"] = len(waypoints)
+        return out
+
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
         rank (one process per GPU, backend "nccl" = RCCL), or with an explicit ``process_group``, the waypoints are

@@ -352,11 +352,45 @@ class AutoTrajectoryGenerator:
             raise ValueError("No available trajectory candidates")
         best, best_score = None, -1
         for c in candidates:
-            score = min(c.length / self.min_trajectory_length, 2.0) * 0.4 + c.smoothness_score * 0.4 \
-                - c.collision_count * 0.1
+            score = self._reference_score(c)
             if score > best_score:
                 best, best_score = c, score
         return best
+
+    def _reference_score(self, c: TrajectoryCandidate) -> float:
+        return min(c.length / self.min_trajectory_length, 2.0) * 0.4 + c.smoothness_score * 0.4 \
+            - c.collision_count * 0.1
+
+    def _select_by_surface_coverage(self, candidates: List[TrajectoryCandidate], mesh, sensor):
+        """Opt-in selection: scan every candidate's waypoints, one coverage set per candidate, and
+        pick the candidate whose scan returned points from the largest quantised area; ties go to the higher reference
+        score, then to the earlier candidate.  Draws no random numbers.  Returns (best, analysis block)."""
+        if not candidates:
+            raise ValueError("No available trajectory candidates")
+        from raycast_engine.raycast_engine_hip import RaycastEngineGPU
+        from .trajectory_generator import poses_from_waypoints
+        if sensor is None:
+            from lidar import Indoor8LineLidarIntrinsics
+            sensor = Indoor8LineLidarIntrinsics.create_standard_8line()
+        engine = getattr(self, "_coverage_engine", None)
+        if engine is None:
+            engine = self._coverage_engine = RaycastEngineGPU(prelock_bytes=())
+        poses = np.concatenate([poses_from_waypoints(c.waypoints) for c in candidates])
+        set_of_pose = np.repeat(np.arange(len(candidates)), [len(c.waypoints) for c in candidates])
+        cov = engine.coverage_sets(sensor, poses, mesh, num_sets=len(candidates), set_of_pose=set_of_pose)
+        try:
+            sums = [cov.summary(k) for k in range(len(candidates))]
+        finally:
+            cov.close()
+            engine.clear_cache()
+        scores = [self._reference_score(c) for c in candidates]
+        win = min(range(len(candidates)), key=lambda k: (-sums[k].covered_q, -scores[k], k))
+        from lidarcast.synth import S3DIS_CLASSES
+        block = {"candidate_ratios": [s.ratio for s in sums],
+                 "candidate_covered_area_m2": [s.covered_area for s in sums],
+                 "winner_index": int(win),
+                 "winner": sums[win].to_dict(class_names=dict(enumerate(S3DIS_CLASSES)))}
+        return candidates[win], block
 
     def _generate_analysis_info(self, candidates, best) -> Dict[str, Any]:
         if not candidates:
@@ -379,10 +413,22 @@ class AutoTrajectoryGenerator:
         }
 
     # ---- entry point ----------------------------------------------------------------------------------
-    def generate_optimal_trajectory(self, mesh, room_bounds: Dict[str, float],
-                                    num_waypoints: int = 20) -> Tuple[List[Waypoint], Dict[str, Any]]:
+    SELECTIONS = ("reference", "surface_coverage")
+
+    def generate_optimal_trajectory(self, mesh, room_bounds: Dict[str, float], num_waypoints: int = 20,
+                                    selection: str = "reference", sensor=None) -> Tuple[List[Waypoint], Dict[str, Any]]:
+        """``selection="reference"`` (default): the reference's score.  ``"surface_coverage"``: the candidate whose scan
+        with ``sensor`` (default: the standard 8-line sensor) saw the largest surface area; ``analysis_info`` then has a
+        ``"surface_coverage"`` block.  Both draw the same random numbers."""
+        if selection not in self.SELECTIONS:
+            raise ValueError(f"unknown selection {selection!r}; expected one of {self.SELECTIONS}")
         self.room_analysis = self._analyze_room_layout(mesh, room_bounds)
         dense = max(int(num_waypoints * self.interpolation_density), self.min_waypoints)
         candidates = self._generate_trajectory_candidates(dense)
-        best = self._select_best_trajectory(candidates)
-        return best.waypoints, self._generate_analysis_info(candidates, best)
+        if selection == "reference":
+            best = self._select_best_trajectory(candidates)
+            return best.waypoints, self._generate_analysis_info(candidates, best)
+        best, block = self._select_by_surface_coverage(candidates, mesh, sensor)
+        info = self._generate_analysis_info(candidates, best)
+        info["surface_coverage"] = block
+        return best.waypoints, info
