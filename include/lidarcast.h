@@ -804,6 +804,88 @@ int lrc_coverage_select_dev(lrc_coverage* cov, uint32_t budget, double target_ra
 int lrc_coverage_export(lrc_coverage* cov, uint32_t* out_bits, uint32_t* out_hits, uint64_t* out_returns,
                         uint64_t* out_q);
 
+/* ---- semantic occupancy grids from scans --------------------------------------------------
+ * Three states per voxel, as semantic scene completion ground truth needs them: OCCUPIED (a return ended in it), FREE
+ * (a ray passed through it), UNKNOWN (no ray reached it).  Only the scan knows "free": it needs the poses and the
+ * per-ray ranges, which a stacked cloud no longer holds.  Not to be confused with lrc_occ_* (the planner's robot-cube
+ * test).  Definitions:
+ *   grid       origin g (3 float64, finite), voxel size s (float64, finite, > 0), dims (nx, ny, nz), each >= 1,
+ *              nx*ny*nz <= 2^31 - 1.  The voxel of a float64 point x is i_a = floor((x_a - g_a) / s) per axis (an f64
+ *              subtract, then an f64 divide, then floor); it is inside iff 0 <= i < n on every axis.  Its linear
+ *              index is (i*ny + j)*nz + k: arrays have shape (nx, ny, nz) in C order, z fastest.
+ *   rays       pose-batched static scans only.  Ray (p, i), entry p*N + i, has origin o, float32 exactly as the scan
+ *              forms it, and end point e, the float32 hit point o + (d/|d|)*t: the row the scene cloud holds.  A ray
+ *              contributes only if its t is finite (it RETURNS: exactly the rows compaction keeps).  Rays without a
+ *              return carve nothing.
+ *   walk       float64, no contraction, o and e widened exactly: a = voxel of o, b = voxel of e, D = e - o.  For each
+ *              axis with b_a != a_a: n_a = |b_a - a_a| steps, step_a = sign(b_a - a_a),
+ *              tMax_a = ((g_a + (a_a + 1)*s) - o_a) / D_a stepping up, ((g_a + a_a*s) - o_a) / D_a stepping down,
+ *              tDelta_a = s / |D_a|; axes with n_a = 0 take no part.  Visit a; then, while any n_a > 0, take the axis
+ *              with the smallest tMax among those with n_a > 0 (ties x, then y, then z), step it, tMax_a += tDelta_a,
+ *              n_a -= 1, and visit the new voxel.  The walk ends in b: 6-connected, Manhattan + 1 voxels.  Every
+ *              visited voxel except b that lies in the grid gets its FREE bit; b, if in the grid, gets one RETURN with
+ *              the ray's (sem, ins) (label bits sem | ins << 16).  a == b carves nothing.  Voxels outside the grid are
+ *              ignored, but the walk is defined over the whole segment.
+ *   limits     a returned ray whose o or e is not finite, whose voxel coordinates leave [-2^31, 2^31) or whose walk
+ *              has more than 2^24 - 1 steps is REJECTED: it carves nothing, records no return, and is counted.
+ *   accumulate additive over calls until reset; the result depends neither on pose order, nor on chunking, nor on the
+ *              order of atomics: free bits are an OR, returns are integer counts.
+ *   finalize   (min_returns >= 1) returns[v] = number of returns in v (uint32).  v is OCCUPIED iff returns[v] >=
+ *              min_returns, else FREE iff its free bit is set, else UNKNOWN (a few returns below min_returns and no
+ *              free bit stay unknown).  sem[v] = most frequent semantic label among v's returns, ties to the smallest;
+ *              ins[v] = most frequent instance among the returns whose sem equals sem[v], ties to the smallest; both 0
+ *              without returns.  Outputs: the sparse list, ascending by linear index, of every voxel with >= 1 return
+ *              (idx u32, sem u16, ins u16, returns u32); an optional dense state u8 array (0 unknown, 1 free,
+ *              2 occupied); the counts.
+ * Every returned ray reserves one 8-byte key slot until the next reset (the key buffer grows, no return is dropped;
+ * at most 2^31 - 1 rays between resets).  The object is not thread-safe and its calls must be ordered on one stream;
+ * "_dev" entry points enqueue on `stream`, the others return after the work finished. */
+typedef struct lrc_voxgrid lrc_voxgrid;
+
+typedef struct lrc_voxgrid_info {
+    double   origin[3];
+    double   voxel_size;
+    int64_t  dims[3];
+    uint64_t num_voxels;       /* nx*ny*nz                                                         */
+    uint64_t words;            /* free bitset words, ceil(num_voxels / 32)                         */
+    uint64_t reserved_keys;    /* rays accumulated since the last reset (key slots)                */
+    uint64_t sparse_bound;     /* min(num_voxels, reserved_keys): capacity the sparse outputs need */
+} lrc_voxgrid_info;            /* 88 bytes */
+
+typedef struct lrc_voxgrid_counts {
+    uint64_t num_sparse;       /* voxels with >= 1 return                                          */
+    uint64_t num_free;
+    uint64_t num_occupied;
+    uint64_t num_unknown;
+    uint64_t rejected_rays;    /* returned rays refused by the limits above                        */
+    uint64_t returns;          /* returns recorded in the grid (the sum of returns[v])             */
+} lrc_voxgrid_counts;          /* 48 bytes; the _dev finalize writes these six words in this order */
+
+/* Rejects a non-finite origin, a voxel size that is not finite and > 0, a dim < 1 and more than 2^31 - 1 voxels with
+ * LRC_ERR_INVALID_ARG. */
+int lrc_voxgrid_create(lrc_ctx* ctx, const double* origin3, double voxel_size, const int64_t* dims3,
+                       lrc_voxgrid** out_vg);
+int lrc_voxgrid_destroy(lrc_voxgrid* vg);
+int lrc_voxgrid_get_info(const lrc_voxgrid* vg, lrc_voxgrid_info* out);
+/* Clear the free bits, the returns and the counters. */
+int lrc_voxgrid_reset(lrc_voxgrid* vg, void* stream);
+/* Walk the rays of a pose-batched scan: d_poses16 (num_poses x 16 float64, row-major 4x4) and d_dirs3
+ * (rays_per_pose x 3 float64) as lrc_scan_poses_dev took them, d_t_label its (num_poses * rays_per_pose) x 8 B
+ * lrc_hits.t_label pairs {float t; uint32 sem | ins << 16}. */
+int lrc_voxgrid_accumulate_dev(lrc_voxgrid* vg, const double* d_poses16, uint64_t num_poses, const double* d_dirs3,
+                               uint64_t rays_per_pose, const void* d_t_label, void* stream);
+/* The sparse list (capacity >= sparse_bound entries each; unused tail entries are left as they were), the dense
+ * state (num_voxels bytes; NULL skips it) and the counts.  The _dev form writes the six count words to d_counts6 and
+ * needs no host synchronisation; the host form synchronises once and copies num_sparse entries. */
+int lrc_voxgrid_finalize_dev(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* d_idx, uint16_t* d_sem, uint16_t* d_ins,
+                             uint32_t* d_returns, uint64_t capacity, uint8_t* d_state /* nullable */,
+                             uint64_t* d_counts6, void* stream);
+int lrc_voxgrid_finalize(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* out_idx, uint16_t* out_sem, uint16_t* out_ins,
+                         uint32_t* out_returns, uint64_t capacity, uint8_t* out_state /* nullable */,
+                         lrc_voxgrid_counts* out_counts);
+/* Copy out the free bitset (words uint32; bit v of word v/32, least significant bit first). */
+int lrc_voxgrid_export_bits(lrc_voxgrid* vg, uint32_t* out_bits);
+
 /* Resident waves per CU the runtime grants the pose-batched trace kernel on this scene (its LDS stack is sized by
  * the tree depth), its VGPR count and LDS bytes per wave: the occupancy figure bench.py reports. */
 int lrc_scene_get_occupancy(const lrc_scene* scene, int* waves_per_cu, int* vgprs, int* lds_bytes);

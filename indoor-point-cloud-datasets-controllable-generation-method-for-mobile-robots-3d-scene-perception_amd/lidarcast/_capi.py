@@ -44,6 +44,8 @@ SYMBOLS = (
     "lrc_coverage_create", "lrc_coverage_destroy", "lrc_coverage_get_info", "lrc_coverage_classes", "lrc_coverage_reset",
     "lrc_coverage_accumulate_dev", "lrc_coverage_summary", "lrc_coverage_summary_dev", "lrc_coverage_select",
     "lrc_coverage_select_dev", "lrc_coverage_export",
+    "lrc_voxgrid_create", "lrc_voxgrid_destroy", "lrc_voxgrid_get_info", "lrc_voxgrid_reset", "lrc_voxgrid_accumulate_dev",
+    "lrc_voxgrid_finalize", "lrc_voxgrid_finalize_dev", "lrc_voxgrid_export_bits",
     "lrc_occ_create", "lrc_occ_destroy", "lrc_occ_query",
     "lrc_rng_scan_draws", "lrc_rays_from_trig",
 )
@@ -79,6 +81,17 @@ class LrcCoverageInfo(C.Structure):
 class LrcCoverageStats(C.Structure):
     _fields_ = [("covered_q", C.c_uint64), ("total_q", C.c_uint64), ("seen_triangles", C.c_uint64),
                 ("returns", C.c_uint64)]
+
+
+class LrcVoxgridInfo(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("voxel_size", C.c_double), ("dims", C.c_int64 * 3),
+                ("num_voxels", C.c_uint64), ("words", C.c_uint64), ("reserved_keys", C.c_uint64),
+                ("sparse_bound", C.c_uint64)]
+
+
+class LrcVoxgridCounts(C.Structure):
+    _fields_ = [("num_sparse", C.c_uint64), ("num_free", C.c_uint64), ("num_occupied", C.c_uint64),
+                ("num_unknown", C.c_uint64), ("rejected_rays", C.c_uint64), ("returns", C.c_uint64)]
 
 
 class LrcCompactIO(C.Structure):
@@ -247,6 +260,14 @@ def load():
         "lrc_coverage_select": [vp, C.c_uint32, dbl, vp, vp, vp, vp],
         "lrc_coverage_select_dev": [vp, C.c_uint32, dbl, vp, vp, vp, vp, vp],
         "lrc_coverage_export": [vp, vp, vp, vp, vp],
+        "lrc_voxgrid_create": [vp, vp, dbl, vp, C.POINTER(vp)],
+        "lrc_voxgrid_destroy": [vp],
+        "lrc_voxgrid_get_info": [vp, C.POINTER(LrcVoxgridInfo)],
+        "lrc_voxgrid_reset": [vp, vp],
+        "lrc_voxgrid_accumulate_dev": [vp, vp, u64, vp, u64, vp, vp],
+        "lrc_voxgrid_finalize": [vp, C.c_uint32, vp, vp, vp, vp, u64, vp, C.POINTER(LrcVoxgridCounts)],
+        "lrc_voxgrid_finalize_dev": [vp, C.c_uint32, vp, vp, vp, vp, u64, vp, vp, vp],
+        "lrc_voxgrid_export_bits": [vp, vp],
         "lrc_nn_create": [vp, vp, u64, dbl, C.POINTER(vp)],
         "lrc_nn_destroy": [vp],
         "lrc_nn_query": [vp, vp, u64, vp, vp],

@@ -436,6 +436,33 @@ class RaycastEngineHIP(RaycastEngineBase):
         finally:
             cov.close()
 
+    # ---- semantic occupancy grids (lidarcast.voxgrid) ---------------------------------------------
+    def occupancy_grid(self, intrinsics, poses, mesh, voxel_size=0.05, origin=None, dims=None, min_returns=1,
+                       max_range=None, chunk_poses=None):
+        """Scan ``poses`` (P, 4, 4) with a multi-line grid sensor, carve free space along every returned ray and
+        finalize: a lidarcast.OccupancyResult (sparse voxels with returns, dense state, counts, per-class occupied
+        voxels).  Default extent (origin and dims both None): the mesh's bounds with a one-voxel margin,
+        origin = min(vertices) - voxel_size, dims = floor((max(vertices) - origin) / voxel_size) + 2 per axis."""
+        from lidarcast import OccupancyGrid, scan_occupancy
+        from lidarcast.voxgrid import check_grid, default_extent
+        if hasattr(intrinsics, "swing_amplitude") or not hasattr(intrinsics, "horizontal_res"):
+            raise NotImplementedError("occupancy grids cover multi-line grid sensors only; the dual-axis sensor and "
+                                      "moving-sensor sweeps are outside their scope")
+        if (origin is None) != (dims is None):
+            raise ValueError("give both origin and dims, or neither (default extent)")
+        if origin is None:
+            origin, dims = default_extent(mesh_arrays(mesh)[0], voxel_size)
+        check_grid(origin, voxel_size, dims)
+        if int(min_returns) < 1:
+            raise ValueError("min_returns must be >= 1")
+        grid = OccupancyGrid(self.ctx, origin, voxel_size, dims)
+        try:
+            scan_occupancy(self.scene_for(mesh), grid, poses, self._direction_table(intrinsics),
+                           intrinsics.max_range if max_range is None else float(max_range), chunk_poses=chunk_poses)
+            return grid.finalize(min_returns=min_returns, dense=True)
+        finally:
+            grid.close()
+
     def scan_frames_lidars(self, lidars, mesh, want=("point3", "sem", "ins")):
         """The bit-exact default path of the dual-axis sensor, straight to frames: every pose's rays come from the host
         generator (``all_rays_and_mask``: the reference's arithmetic and RNG draws, written into a page-locked buffer),

@@ -205,6 +205,36 @@ class S3DISSimulator:
         out["num_poses"] = len(waypoints)
         return out
 
+    def export_occupancy_grid(self, waypoints: List[Waypoint], output_dir, voxel_size: float = 0.05,
+                              min_returns: int = 1) -> Dict[str, Any]:
+        """Semantic occupancy grid of the scan of ``waypoints`` over the loaded room, written to
+        ``output_dir``: <scene>_occupancy.npz (state, sem, ins, returns, origin, voxel_size, dims),
+        <scene>_occupancy.json (counts and per-class occupied voxels keyed by the S3DIS class name where the label is
+        a known class id) and <scene>_occupied_voxels.ply (occupied voxel centres with their labels, the labelled-PLY
+        layout).  The extent is the room mesh's bounds with a one-voxel margin.  Scans again on the GPU; run_simulation
+        is not involved.  Returns the JSON summary."""
+        if self.scene is None:
+            raise ValueError("Scene not loaded. Call load_scene() first.")
+        if self.config.get("motion") is not None:
+            raise NotImplementedError("occupancy grids of moving-sensor sweeps are outside their scope")
+        from containers.s3dis_sim_scene import write_labeled_ply
+        from lidarcast.synth import S3DIS_CLASSES
+        r = self.raycast_engine.occupancy_grid(self.lidar_config, poses_from_waypoints(waypoints), self.scene.room_mesh,
+                                               voxel_size=voxel_size, min_returns=min_returns)
+        out = Path(output_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        name = self.scene.scene_name
+        r.to_npz(out / f"{name}_occupancy.npz")
+        centres, sem, ins = r.occupied_centres()
+        write_labeled_ply(out / f"{name}_occupied_voxels.ply", centres.astype(np.float32),
+                          np.full((len(centres), 3), 127, dtype=np.uint8), sem, ins)
+        summary = r.to_dict(class_names=dict(enumerate(S3DIS_CLASSES)))
+        summary["scene_name"] = name
+        summary["num_poses"] = len(waypoints)
+        with open(out / f"{name}_occupancy.json", "w") as f:
+            json.dump(summary, f, indent=2)
+        return summary
+
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
         rank (one process per GPU, backend "nccl" = RCCL), or with an explicit ``process_group``, the waypoints are
