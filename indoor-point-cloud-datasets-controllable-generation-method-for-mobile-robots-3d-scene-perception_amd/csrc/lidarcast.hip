@@ -617,6 +617,21 @@ __device__ __forceinline__ void scatter_tile_lean(const lrc_compact_io& io, cons
     if (io.out_range_origin) io.out_range_origin[dst] = __builtin_sqrtf((r.x * r.x + r.y * r.y) + r.z * r.z);   // as scatter_tile
 }
 
+// Streaming accesses of the scan pipeline's scatter: a row of a lean record set is read once, two launches after it was
+// written, and the caller's output row is written once and not read again by the library.  With non-temporal loads and stores
+// the pipelined step is 3-4 % faster on every scene (profiles/pipe_fused_scatter.txt, items 4-6) -- presumably because 134 MB
+// per launch no longer pass through L2 and the Infinity Cache in front of the tracing waves, which want the scene's nodes
+// there.  The trace's own stores of the set stay ordinary: streaming them measured slower.
+typedef float nt_float4 __attribute__((ext_vector_type(4)));       // the builtins take the compiler's vector types
+__device__ __forceinline__ void store_streaming(float4* q, float4 v) {
+    const nt_float4 w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, (nt_float4*)q);
+}
+__device__ __forceinline__ float4 load_streaming(const float4* q) {
+    const nt_float4 w = __builtin_nontemporal_load((const nt_float4*)q);
+    return make_float4(w.x, w.y, w.z, w.w);
+}
+
 // scatter_tiles_xyzl from a lean record set: scalar loads of the keep masks instead of per-lane t loads, then one 16-byte row
 // load per lane instead of five loads per kept lane -- the row IS the output row.  Four tiles at a time: eight rows in flight
 // per lane (32 registers) pushed the trace kernel, whose registers this wave holds, into scratch.
@@ -645,11 +660,11 @@ __device__ __forceinline__ void scatter_tiles_xyzl_lean(const lrc_compact_io& io
         float4 row[H];
 #pragma unroll
         for (int r = 0; r < H; ++r)
-            row[r] = m[r] != 0ull ? in.row[(tile0 + h + r) * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+            row[r] = m[r] != 0ull ? load_streaming(&in.row[(tile0 + h + r) * 64 + lane]) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int r = 0; r < H; ++r)
             if ((m[r] >> lane) & 1ull)
-                ((float4*)io.out_xyzl)[sbase + off[r] + (uint64_t)__popcll(m[r] & below)] = row[r];
+                store_streaming(&((float4*)io.out_xyzl)[sbase + off[r] + (uint64_t)__popcll(m[r] & below)], row[r]);
     }
 }
 #ifndef LRC_PRE_TILES

@@ -9,7 +9,7 @@ mkdir -p $R/build_variants/obj_$NAME
 cd $P/csrc
 HIPF="--offload-arch=gfx950 -O3 -ffp-contract=off -Xarch_device -fno-honor-nans -Xarch_device -fno-slp-vectorize -fPIC -std=c++17 -pthread"
 pids=()
-for f in lidarcast.hip lrc_bvh_device.hip lrc_nn.hip lrc_metrics.hip lrc_occupancy.hip lrc_boxes.hip; do
+for f in *.hip; do      # every kernel source (the library does not load with one missing)
   /opt/rocm/bin/hipcc $HIPF "$@" -c $f -o $R/build_variants/obj_$NAME/${f%.*}.o & pids+=($!)
 done
 for f in bvh_build.cpp lrc_qnodes.cpp lrc_nprandom.cpp; do
