@@ -222,14 +222,13 @@ def test_box_clause_never_acts_on_the_baseline_configs(engine):
 def test_c5_six_scenes_full_size(engine):
     """BASELINE config C5: the C3 sensor x 64 poses over synth_A1..A6 through the plugin surface
     (S3DISSimulator.run_simulation -> lrc_scan_poses_compact).  Every ray of every scene through size-independent
-    properties; two poses per scene ray by ray against the oracle; per-scene Chamfer distance (definition of
-    evaluate_single_scene.py:81-96, evaluated on the full clouds of those poses with lrc_min_distances) between the
+    properties; all 64 frames of every scene ray by ray against the oracle; per-scene Chamfer distance (definition of
+    evaluate_single_scene.py:81-96, evaluated on the full clouds of poses 5 and 58 with lrc_min_distances) between the
     HIP cloud and the oracle cloud == 0.0."""
     import bench
-    from lidar import create_lidar
+    import full_parity as fp
     from lidarcast import synth
     from lidarcast.metrics import min_distances
-    from oracle import np_oracle
     from oracle.c_oracle import OracleMesh
     from s3dis_simulator import run_scene_batch
     sensor = bench.c3_sensor()
@@ -252,13 +251,20 @@ def test_c5_six_scenes_full_size(engine):
         sem = np.concatenate([f.semantic_labels for f in sim.frames])
         assert set(np.unique(sem)) <= {0, 1, 2, 7, 8, 10} and (sem == 2).mean() > 0.2
         om = OracleMesh(mesh.vertices, mesh.triangles).build()
+        # all 64 frames against the oracle (tests/full_parity.py): per-frame sizes, points, semantic and instance labels
+        want = fp.expected_sensor_scan(om, mesh, sensor, poses, threads=16)
+        rows = np.empty((len(cloud), 4), np.float32)
+        rows[:, :3] = cloud
+        rows[:, 3] = fp.pack_labels(sem, np.concatenate([f.instance_labels for f in sim.frames]))
+        n = fp.assert_scan_equal({"rows": rows, "counts": counts.astype(np.int64)}, want, f"C5 {name}", fields=fp.CLOUD)
+        assert n == 64 * 65536 and want["keep"].mean() > 0.99
+        fp.report(f"C5 {name}, all 64 frames", want, rays=n)
+        expected = list(fp.frames(want))
         ref, mine = [], []
         for p in (5, 58):
-            lidar = create_lidar(sensor, poses[p])
-            rp, _, ridx = np_oracle.lidar_intersect_mesh(om, lidar, threads=16, return_index=True)
+            ridx, rp, rsem, _ = expected[p]
             assert_bit_equal(sim.frames[p].points, rp, f"{name} pose {p}")
-            _, prim = om.cast(lidar.get_rays(), threads=16)
-            assert np.array_equal(sim.frames[p].semantic_labels, mesh.triangle_sem[prim[ridx]])
+            assert np.array_equal(sim.frames[p].semantic_labels, rsem) and len(ridx) == len(rp)
             ref.append(rp)
             mine.append(sim.frames[p].points)
         ref, mine = np.concatenate(ref), np.concatenate(mine)
@@ -289,7 +295,7 @@ def _c4_hash(points, sem, ins, counts):
 
 def test_c4_blk2go_256_poses_and_two_rank_gather(engine, tmp_path):
     """BASELINE config C4 as stated: create_blk2go_dual_axis, np.random.seed(0) once, 256 poses on a line through
-    synth_A1_office, ONE lrc_cast_segments launch per rank; a sample of poses ray by ray against the oracle; then the
+    synth_A1_office, ONE lrc_cast_segments launch per rank; all 256 poses ray by ray against the oracle; then the
     same job as a 2-rank launch (torch.distributed.run, gloo, both ranks on this one GPU) through
     S3DISSimulator.run_simulation: SHA-256 of the assembled scene equal to the 1-rank run's."""
     from lidar import DualAxisLidarIntrinsics, create_lidar
@@ -309,17 +315,26 @@ def test_c4_blk2go_256_poses_and_two_rank_gather(engine, tmp_path):
     counts = np.array([len(f.points) for f in scene.frames])
     assert len(scene.frames) == 256 and 0.97 * 64000 * 0.98 < counts.mean() < 64000
     one_rank = _c4_hash(scene.combined_points(), *scene.combined_labels(), counts)
-    # the oracle on the same seeded stream: poses 0, 100 and 255 (the stream is sequential: draw all, keep three)
+    # the oracle on the same seeded stream, all 256 poses in stream order
     kd = DualAxisLidarIntrinsics.create_blk2go_dual_axis()
     om = OracleMesh(mesh.vertices, mesh.triangles).build()
     np.random.seed(0)
+    rays_compared = kept = 0
     for i, wp in enumerate(wps):
         lidar = create_lidar(kd, wp.to_pose_matrix())
-        if i in (0, 100, 255):
-            rp, _ = np_oracle.lidar_intersect_mesh(om, lidar, threads=16)        # draws this pose's rays
-            assert_bit_equal(scene.frames[i].points, rp, f"pose {i}")
-        else:
-            lidar.get_rays()
+        rays = lidar.get_rays()                                                  # draws this pose's rays
+
+        class Frozen:
+            intrinsics, pose = kd, lidar.pose
+            def get_rays(self):
+                return rays
+        rp, _ = np_oracle.lidar_intersect_mesh(om, Frozen(), threads=16)
+        assert_bit_equal(scene.frames[i].points, rp, f"pose {i}")
+        rays_compared += len(rays)
+        kept += len(rp)
+    assert rays_compared > 256 * 64000 * 0.97 and kept == counts.sum()
+    print(f"\n[full parity] C4 all 256 poses: rays compared {rays_compared}, kept share {kept / rays_compared:.5f}, "
+          "rays that differ 0")
     # two ranks on the one GPU, launched the way the driver launches bench.py
     out = tmp_path / "c4.json"
     env = dict(os.environ, LRC_DIST_BACKEND="gloo")

@@ -745,16 +745,15 @@ def test_many_short_poses(ctx):
 
 def test_full_size_c3_properties(ctx):
     """BASELINE config C3 at full size (64 poses x 65 536 rays, T = 605 328), device-resident path.
-    Size-independent properties + four poses checked ray by ray against the oracle."""
+    Size-independent properties + every ray of all 64 poses against the oracle."""
     import hashlib
     import torch
     import bench
+    import full_parity as fp
     import lidarcast
-    from lidar import IndoorLidar, create_lidar
+    from lidar import IndoorLidar
     from lidarcast import synth
     from lidarcast._capi import LrcCompactIO
-    from oracle import np_oracle
-    from oracle.c_oracle import OracleMesh
     mesh = synth.make_scene(bench.SCENE)
     scene = lidarcast.Scene(ctx, mesh.vertices, mesh.triangles, mesh.triangle_sem, mesh.triangle_ins)
     sensor = bench.c3_sensor()
@@ -796,15 +795,16 @@ def test_full_size_c3_properties(ctx):
     rng = np.linalg.norm(pts - poses[:, None, :3, 3], axis=2)
     assert (rng[hit] < sensor.max_range).all() and np.abs(rng[hit] - t[hit]).max() < 1e-4   # unit directions
     assert np.array_equal(rows[:k, :3].cpu().numpy(), pts[hit])         # cloud = np.vstack of the frames
-    om = OracleMesh(mesh.vertices, mesh.triangles).build()
-    for p in (0, 21, 42, 63):
-        lidar = create_lidar(sensor, poses[p])
-        ref_pts, _, ref_idx = np_oracle.lidar_intersect_mesh(om, lidar, threads=16, return_index=True)
-        assert np.array_equal(np.flatnonzero(hit[p]), ref_idx)
-        assert_bit_equal(pts[p][hit[p]], ref_pts)
-        tr, pr = om.cast(lidar.get_rays(), threads=16)
-        assert_bit_equal(t[p][hit[p]], tr[ref_idx])
-        assert np.array_equal(prim[p][hit[p]], pr[ref_idx])
+    # all 64 poses ray by ray against the oracle (tests/full_parity.py): surviving indices (the positions of the finite t),
+    # points, t and triangle ids as the four-pose loop compared them, plus normals, labels, counts and the compacted rows;
+    # a difference is reported with its pose, tile and lane
+    want = fp.c3_expected()
+    assert np.array_equal(hit.reshape(-1), want["keep"])
+    got = {"t": t, "prim": prim, "point3": pts, "normal3": nrm,
+           "sem": hits["sem"].cpu().numpy().view(np.uint16), "ins": hits["ins"].cpu().numpy().view(np.uint16),
+           "counts": counts.cpu().numpy(), "rows": rows.cpu().numpy(), "fill": 0.0}
+    assert fp.assert_scan_equal(got, want, "C3 full size") == P * N == 64 * 65536
+    fp.report("C3 properties test, all 64 poses", want)
 
 
 def test_bench_contract(tmp_path):

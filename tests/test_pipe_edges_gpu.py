@@ -211,12 +211,16 @@ class Sharded:
         return ScanPipe.gathered(s["poses"], g.all_prims, g.all_tile_counts, self.P, g.stride_bytes, self.own, s["ticket"],
                                  s["cloud"], s["counts"], scan_slot=j % 2)
 
+    def poses_of_step(self, j):
+        """(W * P, 16) device poses of all ranks for step j, slab after slab (a subclass may hand in poses of its own)."""
+        return random_poses(self.rng, self.W * self.P)
+
     def trace(self, carry=None):
         """One step: the own submit (carrying the assembly of step `carry`), then the collective of its slabs."""
         import torch
         j = len(self.steps)
         P, W, N, own = self.P, self.W, self.N, self.own
-        all_poses = random_poses(self.rng, W * P)
+        all_poses = self.poses_of_step(j)
         self.steps.append({"poses": all_poses, "dirs": self.dirs_host,
                            "cloud": torch.full((W * P * N, 4), -7.0, dtype=torch.float32, device="cuda"),
                            "counts": torch.full((W * P,), -1, dtype=torch.int64, device="cuda"), "scanned": None})
