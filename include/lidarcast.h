@@ -275,6 +275,17 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t num_segments, uint64_t seg_len,
  *   lrc_pipe_trace_ms the time the trace launch of submit `ticket` spent between its stream reaching it and its last wave
  *                     (HIP events on the launch stream; inside the pipeline launches overlap, so this is longer than the
  *                     launch's share of the step).  Synchronises the host with that launch.
+ *   lrc_pipe_set_line_width  a hint for submits with rays_per_pose % 64 == 0: the rays of a pose come in scan lines of
+ *                     `line_width` consecutive table rows (one elevation each).  A tracing wave then takes 32 columns of two
+ *                     adjacent lines instead of 64 columns of one, which keeps its rays together for longer.  0 (the default):
+ *                     automatic -- the length of the first run of equal z in the table, read once per table address the
+ *                     pipeline has not seen (the first such submit synchronises the host with `stream` for a 4-byte
+ *                     read-back; later submits add nothing -- so that first submit must not be made while `stream` is being
+ *                     captured into a graph: give the width as a hint there, a hinted pipeline never synchronises).  A width is used when it is a multiple of 64 that divides
+ *                     rays_per_pose into at least two lines; otherwise waves take 64 consecutive rays as before.  The width
+ *                     only regroups rays into waves, and the regrouping is a bijection of the pose's rays for ANY width: a
+ *                     wrong or stale one (another table at a recycled address, a table edited in place) can cost speed,
+ *                     never a byte of the rows, counts or records.
  * Destroy the pipeline before its scene. */
 typedef struct lrc_pipe lrc_pipe;
 int lrc_pipe_create(lrc_scene* scene, uint64_t max_poses, uint64_t rays_per_pose, lrc_pipe** out_pipe);
@@ -284,6 +295,7 @@ int lrc_pipe_submit(lrc_pipe* pipe, const double* d_poses16, uint64_t num_poses,
 int lrc_pipe_wait(lrc_pipe* pipe, void* stream);
 int lrc_pipe_records(lrc_pipe* pipe, uint64_t ticket, lrc_hits* out_records);
 int lrc_pipe_trace_ms(lrc_pipe* pipe, uint64_t ticket, float* out_ms);
+int lrc_pipe_set_line_width(lrc_pipe* pipe, uint64_t line_width);
 
 /* The pipeline on N ranks (one process per GPU; the collective itself is the caller's: RCCL all-gather of the send slabs).
  *   lrc_pipe_submit_sharded  traces this rank's pose block like lrc_pipe_submit, with the triangle ids and per-wave keep counts

@@ -195,6 +195,10 @@ struct TraceParams {
     const float* slot_box;     // per slot lo xyz, hi xyz of the triangle's vertices
     const float4* prim_plane;  // per caller's triangle row: (v0, label bits), (Ng, 0)
     uint32_t num_nodes;
+    // GEN = 1 with rays_per_pose % 64 == 0: tiles (workgroups) per pose -- a tile then lies in one pose, and the pose and the
+    // tile's first in-pose index are scalar arithmetic on the 32-bit tile number.  0: per-lane 64-bit division, as for every other
+    // GEN.  (Placed in the padding behind num_nodes: the argument block keeps its size.)
+    uint32_t tiles_per_pose;
     const uint4* nodes_q;      // QN kernels: 32-byte quantised nodes (per-lane fetches) ...
     const float4* nodes_n;     // ... and the same boxes as normalised float32 (scalar fetches)
     const uint4* nodes_q4;     // QN = 2: the tree collapsed to four children per node, 64 B per node ...
@@ -202,6 +206,10 @@ struct TraceParams {
     uint32_t stack_cap;        // entries of the per-lane LDS stack
     uint32_t tile_chunk_log2;  // 0: eight contiguous tile ranges, one per XCD; k + 1: chunks of 2^k tiles round robin
     uint32_t force_redo;       // test hook (LRC_DEBUG_FORCE_REDO=m): rays with gid % m == 0 take the redo path as well
+    // lean record set with tiles_per_pose != 0 only (lrc_pipe_submit): lines of the scan pattern are 64 * line_tiles rays long
+    // and a tile takes 32 columns of two adjacent lines (lrc_device.h, tile_ray).  0: 64 consecutive rays.  (In the padding
+    // behind force_redo.)
+    uint32_t line_tiles;
     uint64_t* chain_word;      // launch chain (lrc_ctx::chain_word): the last workgroup stores chain_seq here when it starts
     uint64_t chain_seq;
     // scan pipeline (lrc_pipe): the first pre.blocks workgroups of the launch do not trace -- each compacts one 64-entry
@@ -226,7 +234,7 @@ struct TraceParams {
         LeanIn lean;               // plain form: the earlier scan's lean record set (io's t / point3 / sem / ins are not read)
     } pre;
     // lean record set (scan pipeline): row != NULL -> write_back stores per ray the packed row and (t bits, slot), per wave
-    // the keep mask and tile_count, and no column of `out`.  Wave-uniform: a run-time branch.
+    // the keep mask, and no column of `out`.  Wave-uniform: a run-time branch.
     struct Lean {
         float4* row;
         uint2* aux;                // (t bits, slot): t after range noise, slot = 0xFFFFFFFF for a ray that is not kept
@@ -380,13 +388,34 @@ __device__ __forceinline__ void slot_normal(float4 c, float& nx, float& ny, floa
     nx = c.y / len; ny = c.z / len; nz = c.w / len;
 }
 
+// The range filter of a ray that has a hit, shared by the lean and the plain write-back: keep &= sqrt(s) < max_range (and >=
+// min_range, opt-in), s the squared float64 distance to the filter centre.  Where the launch has bounds around max_range^2
+// (lrc_device.h, range_band), no opt-in needs the distance itself and no ray of the wave falls between the bounds, s is compared
+// with the lower bound and the float64 square root (v_rsq_f64 and its Newton steps, at half rate) is never formed; otherwise the
+// whole wave takes the square root.  Returns the distance, or 0 where it was not formed (then no output reads it).
+template <bool FILTER>
+__device__ __forceinline__ double range_filter(const TraceParams& p, double s, bool& keep) {
+    const bool filter = FILTER || p.has_center;
+    const RangeBand rb = range_band(p.max_range);      // wave-uniform: a handful of instructions on a kernel argument
+    const bool need_dist = !rb.fast | !filter | (p.min_range > 0.0) | (p.out.incident_deg != nullptr);   // wave-uniform
+    if (!need_dist && __builtin_amdgcn_ballot_w64(range_in_band(s, rb.lo, rb.hi)) == 0ull) {
+        keep = range_below(s, rb.lo);
+        return 0.0;
+    }
+    const double dist = __builtin_sqrt(s);
+    if (filter) keep = dist < p.max_range;
+    if (p.min_range > 0.0) keep = keep & (dist >= p.min_range);     // opt-in; the reference never applies it
+    return dist;
+}
+
 // ---- fused write-back: everything after the closest hit is known (shared by the trace kernels) ------------------
 // best_slot = 0xFFFFFFFF: no hit.  FILTER: apply the max_range filter (scans and casts with a centre).
 // BY_PRIM: `best_slot` is the caller's triangle ROW (sector_kernel keys rays by (t, row)); labels and the normal then
 // come from the per-row plane table instead of the per-slot arrays -- same values.
-template <bool FILTER_ALWAYS, bool BY_PRIM = false>
+// HAVE_LABEL: the caller has slot_label[best_slot] already (trace_kernel issues the load together with the box clause's).
+template <bool FILTER_ALWAYS, bool BY_PRIM = false, bool HAVE_LABEL = false>
 __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, uint32_t tid, V3 o, V3 d, double cx,
-                                           double cy, double cz, float tbest, uint32_t best_slot) {
+                                           double cy, double cz, float tbest, uint32_t best_slot, uint32_t slot_label_in = 0u) {
     constexpr int GEN = FILTER_ALWAYS ? 1 : 0;
     const bool lean = FILTER_ALWAYS && !BY_PRIM && p.lean.row != nullptr;    // a kernel argument: wave-uniform
     bool keep = best_slot != 0xFFFFFFFFu;
@@ -410,12 +439,10 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
         px = pp.x; py = pp.y; pz = pp.z;
         // range filter + incident angle in float64 (raycast_engine_cpu.py:95-107)
         const double ex = (double)px - cx, ey = (double)py - cy, ez = (double)pz - cz;
-        const double dist = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
-        if (p.has_center || GEN != 0) keep = dist < p.max_range;
-        if (p.min_range > 0.0) keep = keep & (dist >= p.min_range);     // opt-in; the reference never applies it
+        const double dist = range_filter<GEN != 0>(p, (ex * ex + ey * ey) + ez * ez, keep);
         if (keep && lean) {           // the lean record: no triangle id, no normal
             t_out = tbest;
-            label = p.slot_label[best_slot];
+            label = HAVE_LABEL ? slot_label_in : p.slot_label[best_slot];
         } else if (keep) {
             t_out = tbest;
             if (BY_PRIM) {
@@ -423,7 +450,7 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
                 label = __float_as_uint(p.prim_plane[(size_t)best_slot * 2].w);
             } else {
                 prim = p.slot_prim[best_slot];
-                label = p.slot_label[best_slot];
+                label = HAVE_LABEL ? slot_label_in : p.slot_label[best_slot];
             }
             if (p.out.normal3 || p.out.intensity || (p.out.incident_deg && p.incident_mode == 1)) {
                 float4 c;
@@ -449,11 +476,11 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
     }
     if (lean) {
         // two stores per ray: the row as the scatter copies it, and what the expansion for lrc_pipe_records needs besides
+        // the keep mask as two 32-bit words: each half of the wave is half of a 1-D tile (of two different ones in a two-line
+        // tile, lrc_device.h tile_ray), so two waves fill one mask, no atomics, nothing to zero.  The per-tile counts of a lean
+        // set are the scan pass's to form (popcount of the masks, compact_scan_masks_kernel).
         const unsigned long long m = __ballot(keep);
-        if ((tid & 63u) == 0) {
-            if (p.out.tile_count) p.out.tile_count[gid >> 6] = (uint32_t)__popcll(m);
-            p.lean.keep_mask[gid >> 6] = m;
-        }
+        if ((tid & 31u) == 0) ((uint32_t*)p.lean.keep_mask)[gid >> 5] = (uint32_t)(m >> (tid & 32u));
         p.lean.row[gid] = make_float4(px, py, pz, __uint_as_float(label));
         p.lean.aux[gid] = make_uint2(__float_as_uint(t_out), keep ? best_slot : 0xFFFFFFFFu);
         return;
@@ -733,8 +760,18 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
     bool live = true;          // false: not cast at all (dropped by the sensor, or a non-finite ray)
     uint32_t pose32 = 0;
     if (GEN == 1) {
-        const uint64_t pose = gid / p.rays_per_pose;
-        const uint64_t i = gid - pose * p.rays_per_pose;
+        uint64_t pose, i;
+        if (p.tiles_per_pose != 0u) {
+            // a tile lies in one pose: pose and in-pose index from the 32-bit tile number, one 32-bit division of
+            // workgroup-uniform values instead of a 64-bit division per lane
+            const uint32_t pu = tile / p.tiles_per_pose;
+            pose = pu;
+            const uint32_t u = tile - pu * p.tiles_per_pose;
+            i = p.line_tiles != 0u ? tile_ray(u, tid, p.line_tiles, p.tiles_per_pose) : u * (uint32_t)kTBlock + tid;
+        } else {
+            pose = gid / p.rays_per_pose;
+            i = gid - pose * p.rays_per_pose;
+        }
         gen_ray(p.poses16, p.dirs3, pose, i, o, d, cx, cy, cz);
         pose32 = (uint32_t)pose;
     } else if (GEN == 2) {
@@ -771,6 +808,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
     float tbest = __builtin_inff();
     uint32_t best_slot = 0xFFFFFFFFu;
     uint32_t best_prim = 0xFFFFFFFFu;   // loaded lazily, only to break exact ties
+    uint32_t best_label = 0u;           // slot_label[best_slot], fetched together with the box of the deferred clause
 
     uint32_t st_nodes = 0, st_tris = 0, st_uni = 0, st_dead = 0, st_pad = 0;   // STATS build only (lrc_debug_scan_stats)
     live = live & finite_ray(o, d);
@@ -1046,6 +1084,9 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         if (!INLINE_CLAUSE) {
             if (best_slot != 0xFFFFFFFFu) {       // the box clause of the closest candidate, in world coordinates
                 const float* bx = p.slot_box + (size_t)best_slot * 6;
+                // the label the write-back needs has the same index: issued here, it comes back with the box instead of
+                // costing a second dependent round trip after the redo ballot (unused if the ray is dropped or redone)
+                best_label = p.slot_label[best_slot];
                 RaySlab w = sl;
                 if (Q) {        // ix = ix' / W exactly (W a power of two); ox = o * ix as make_slab forms it
                     w.ix = sl.ix * p.qinvW[0]; w.iy = sl.iy * p.qinvW[1]; w.iz = sl.iz * p.qinvW[2];
@@ -1095,6 +1136,9 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
                 tbest = __builtin_inff(); best_slot = 0xFFFFFFFFu; best_prim = 0xFFFFFFFFu;
                 traverse(IntTag<0>{}, IntTag<1>{});
             }
+            // every lane of such a wave loads its label again: the one fetched with the box is not held through the redo
+            // traversal, which has no register for it
+            best_label = best_slot != 0xFFFFFFFFu ? p.slot_label[best_slot] : 0u;
         }
     }
 
@@ -1120,7 +1164,11 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
     asm volatile("" : "+s"(wg));
     const uint32_t tile_w = p.tile_chunk_log2 ? xcd_tile_chunked(wg - p.pre.blocks, gridDim.x - p.pre.blocks, p.tile_chunk_log2)
                                               : xcd_tile(wg - p.pre.blocks, gridDim.x - p.pre.blocks);
-    const uint64_t gid_w = (uint64_t)tile_w * kTBlock + tid;
+    uint64_t gid_w = (uint64_t)tile_w * kTBlock + tid;
+    if (GEN == 1 && p.tiles_per_pose != 0u && p.line_tiles != 0u) {      // two-line tile: the same mapping as in front of the traversal
+        const uint32_t pu = tile_w / p.tiles_per_pose;
+        gid_w = (uint64_t)pu * p.rays_per_pose + tile_ray(tile_w - pu * p.tiles_per_pose, tid, p.line_tiles, p.tiles_per_pose);
+    }
     if (GEN == 4) {
         // the range-filter centre c(s), float64, formed again from the record and fire[i] (as GEN = 1 fetches the pose's
         // translation again) instead of being held through the traversal; opaque pointers keep the loads from merging
@@ -1131,7 +1179,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         M += (size_t)pose32 * 24;
         sweep_centre(M, F[gid_w - (uint64_t)pose32 * p.rays_per_pose], cx, cy, cz);
     }
-    write_back<GEN != 0>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot);
+    write_back<GEN != 0, false, true>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot, best_label);
     if (STATS) {
         if (p.stats) {
             uint32_t* q = p.stats + gid_w * kStatsWords;
@@ -1310,8 +1358,11 @@ __global__ __launch_bounds__(kBlock) void compact_count_kernel(const float* t, u
 // was not scheduled until that launch had no workgroup left -- 150-170 us for a 5 us kernel, and with it the whole chain
 // trace -> scan -> scatter -> next trace fell into phase with the other stream's (profiles/r04_chain_timeline.txt).
 constexpr int kScanRows = 16;           // 64 lanes x 16 rows = 1024 tiles per wave and super tile
+// MASKS: tile_cnt is an array of 64-bit keep masks (one slab), a tile's count the popcount of its mask, written to cnt_out too
+template <bool MASKS = false>
 __device__ __forceinline__ void scan_super_tiles(const uint32_t* tile_cnt, uint64_t tiles_per_slab, uint64_t slab_stride,
-                                                 uint32_t* tile_off, uint64_t ntiles, uint32_t* super_total) {
+                                                 uint32_t* tile_off, uint64_t ntiles, uint32_t* super_total,
+                                                 uint32_t* cnt_out = nullptr) {
     const uint32_t lane = threadIdx.x;
     const uint64_t nsuper = (ntiles + 1023) / 1024;
     const bool one_slab = tiles_per_slab >= ntiles;          // a plain array: no slab arithmetic (a 64-bit division per entry)
@@ -1330,7 +1381,12 @@ __device__ __forceinline__ void scan_super_tiles(const uint32_t* tile_cnt, uint6
                     const uint64_t sb = tile / tiles_per_slab;
                     idx = sb * slab_stride + (tile - sb * tiles_per_slab);
                 }
-                c[r] = tile_cnt[idx];
+                if (MASKS) {
+                    c[r] = (uint32_t)__popcll(((const unsigned long long*)tile_cnt)[tile]);
+                    cnt_out[tile] = c[r];
+                } else {
+                    c[r] = tile_cnt[idx];
+                }
             }
         }
         uint32_t carry = 0u;
@@ -1353,6 +1409,27 @@ __global__ __launch_bounds__(64) void compact_scan_kernel(const uint32_t* tile_c
                                                           uint64_t slab_stride, uint32_t* tile_off,
                                                           uint64_t ntiles, uint32_t* super_total) {
     scan_super_tiles(tile_cnt, tiles_per_slab, slab_stride, tile_off, ntiles, super_total);
+}
+// Length of the first run of equal z in a direction table of n rows: the scan line width of a sensor whose table is laid
+// out line by line at constant elevation (lrc_pipe_submit, automatic line width).  One wave, once per table.
+__global__ __launch_bounds__(64) void first_line_kernel(const double* __restrict__ dirs3, uint64_t n, uint32_t* out) {
+    const uint32_t lane = threadIdx.x;
+    const double z0 = dirs3[2];
+    uint64_t w = n;
+    for (uint64_t base = 0; base < n; base += 64) {
+        const uint64_t i = base + lane;
+        const unsigned long long m = __ballot(i < n && dirs3[i * 3 + 2] != z0);
+        if (m != 0ull) { w = base + (uint64_t)__builtin_ctzll(m); break; }
+    }
+    if (lane == 0) *out = w > 0xFFFFFFFFull ? 0u : (uint32_t)w;
+}
+
+// the scan pass of a lean record set (lrc_pipe_submit): the counts are the popcounts of the tiles' keep masks -- the tracing
+// waves of a two-line tile each hold halves of two tiles and write no counts -- and go to tile_cnt_out as a by-product (what
+// lrc_pipe_records hands out as lrc_hits.tile_count)
+__global__ __launch_bounds__(64) void compact_scan_masks_kernel(const uint64_t* keep_mask, uint32_t* tile_cnt_out, uint32_t* tile_off,
+                                                                uint64_t ntiles, uint32_t* super_total) {
+    scan_super_tiles<true>((const uint32_t*)keep_mask, ntiles, 0, tile_off, ntiles, super_total, tile_cnt_out);
 }
 // the same scan over the gathered counts of all ranks (lrc_pipe_scan_gathered), and in the same waves the direction table
 // (N,3) -> x[N] y[N] z[N] for the rebuild (as dirs_transpose_kernel): one kernel less to find wave slots for beside a running
@@ -1596,6 +1673,27 @@ extern "C" {
 // shared with the other translation units of the library (not part of the public ABI)
 int lrc_internal_fail(int code, const char* msg) { return fail(code, msg ? msg : ""); }
 int lrc_internal_ctx_device(const lrc_ctx* ctx) { return ctx ? ctx->device : 0; }
+// test hook (tests/test_tile_mapping.py): the ray of every (tile, lane) of a pose of tpp tiles for a line width hint (in rays)
+// and the line width in tiles the pipeline would use for it -- the host compilation of the kernel's mapping (lrc_device.h)
+uint32_t lrc_internal_tile_map(uint64_t line_width, uint32_t tpp, uint32_t* out_ray) {
+    const uint32_t wt = line_tiles_for(line_width, (uint64_t)tpp * 64u);
+    if (out_ray)
+        for (uint32_t u = 0; u < tpp; ++u)
+            for (uint32_t l = 0; l < 64u; ++l) out_ray[(size_t)u * 64u + l] = tile_ray(u, l, wt, tpp);
+    return wt;
+}
+// test hook (tests/test_range_band.py): the range filter's decision for squared distances s[0..n) against max_range, made by the
+// host compilation of the very functions the kernel calls (lrc_device.h, range_band): keep[i] = the filter keeps s[i];
+// in_band[i] = the square root decided (also when the bounds are not used at all).  bounds3: lo, hi, fast.
+void lrc_internal_range_decide(double max_range, const double* s, uint64_t n, uint8_t* keep, uint8_t* in_band, double* bounds3) {
+    const RangeBand rb = range_band(max_range);
+    if (bounds3) { bounds3[0] = rb.lo; bounds3[1] = rb.hi; bounds3[2] = (double)rb.fast; }
+    for (uint64_t i = 0; i < n; ++i) {
+        const bool band = !rb.fast || range_in_band(s[i], rb.lo, rb.hi);
+        keep[i] = band ? (uint8_t)(std::sqrt(s[i]) < max_range) : (uint8_t)range_below(s[i], rb.lo);
+        if (in_band) in_band[i] = (uint8_t)band;
+    }
+}
 
 const char* lrc_version(void) { return "lidarcast 0.1.0 (gfx950)"; }
 
@@ -2133,6 +2231,13 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     if (p.total == 0) return LRC_OK;
     const uint64_t nblk = (p.total + kTBlock - 1) / kTBlock;
     if (nblk + p.pre.blocks > 0x7FFFFFFFull) return fail(LRC_ERR_INVALID_ARG, "too many rays for one launch");
+    // pose-batched scans whose poses are whole tiles: the kernel forms pose and in-pose index from the tile number (in 32 bits:
+    // poses of less than 2^32 rays)
+    p.tiles_per_pose = ((gen == 1 || gen == 3) && p.rays_per_pose % kTBlock == 0 && p.rays_per_pose <= 0xFFFFFFFFull)
+                           ? (uint32_t)(p.rays_per_pose / kTBlock) : 0u;
+    // two-line tiles: lean record sets only (the serial calls' tile_count is per 64 consecutive outputs), and the counters of
+    // the instrumented kernel, which has no tile_count
+    if (p.tiles_per_pose == 0u || (p.lean.row == nullptr && !stats)) p.line_tiles = 0u;
     // stack entries needed = deepest leaf depth (one pending sibling per inner level above it)
     const uint32_t depth = s->info.max_depth < 1 ? 1 : s->info.max_depth;
     const size_t lds = (size_t)depth * kTBlock * sizeof(int);
@@ -2621,6 +2726,13 @@ struct lrc_pipe {
     // per set: the ticket of the last trace launch that read the set's records as the own rows of an assembly (0: none).  The
     // submit that writes the set again waits for that launch when it runs on the other trace stream.
     uint64_t read_by[kSets] = {};
+    // two-line tiles (lrc_pipe_set_line_width; lrc_device.h, tile_ray): the caller's hint, or, automatic, the width detected on
+    // the first submit of a table address the pipeline has not seen (one one-wave kernel and a 4-byte read-back, then nothing)
+    uint64_t line_hint = 0;                                  // 0: automatic
+    const double* line_table = nullptr;                      // the table line_auto was detected on
+    uint32_t line_auto = 0;                                  // its line width in tiles, 0: 1-D tiles
+    uint32_t* d_line = nullptr;
+    uint32_t line_last = 0;                                  // line width in tiles the last submit's launch ran with
 };
 
 int lrc_pipe_destroy(lrc_pipe* pp) {
@@ -2633,6 +2745,7 @@ int lrc_pipe_destroy(lrc_pipe* pp) {
         for (hipEvent_t e : {pp->ev_in[k], pp->ev_t0[k], pp->ev_trace[k]}) if (e) (void)hipEventDestroy(e);
     }
     if (pp->ev_expand) (void)hipEventDestroy(pp->ev_expand);
+    if (pp->d_line) (void)hipFree(pp->d_line);
     for (int k = 0; k < 2; ++k) {
         if (pp->ev_flush[k]) (void)hipEventDestroy(pp->ev_flush[k]);
         for (lrc_ctx::TileScratch* scp : {&pp->scratch[k], &pp->gscratch[k]}) {
@@ -2704,6 +2817,7 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
             return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
     }
     if (hipEventCreateWithFlags(&pp->ev_expand, hipEventDisableTiming) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
+    if (pp->fused && hipMalloc((void**)&pp->d_line, sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory")); }
     *out_pipe = pp;
     return LRC_OK;
 }
@@ -2731,6 +2845,17 @@ int wait_for_readers(lrc_pipe* pp, int set, hipStream_t T) {
     return LRC_OK;
 }
 }  // namespace
+
+// test hook (tests/test_pipe_two_line_gpu.py): the line width, in tiles of 64 rays, the trace launch of the pipeline's last
+// lrc_pipe_submit ran with (0: 1-D tiles) -- the regrouping changes no byte, so no output can tell whether it happened
+uint32_t lrc_internal_pipe_line_tiles(const lrc_pipe* pp) { return pp ? pp->line_last : 0u; }
+
+int lrc_pipe_set_line_width(lrc_pipe* pp, uint64_t line_width) {
+    if (!pp) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_set_line_width: pipe is NULL");
+    pp->line_hint = line_width;
+    pp->line_table = nullptr;      // a return to automatic detects again on the next submit
+    return LRC_OK;
+}
 
 int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const double* d_dirs3, double max_range,
                     const lrc_compact_io* d_out, void* stream, uint64_t* out_ticket) {
@@ -2760,6 +2885,19 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     p.out = pp->rec[set];
     if (pp->fused) {           // the lean form: only what the scatter reads (the plain fallback below reads the full record)
         p.lean.row = pp->row[set]; p.lean.aux = pp->aux[set]; p.lean.keep_mask = pp->keep_mask[set];
+        // two-line tiles: the hinted line width, or the table's own, detected once per table address -- on the caller's
+        // stream, whose position the table is valid at, with a 4-byte read-back; nothing afterwards.  A stale width (a new
+        // table at a recycled address, a table edited in place) maps the rays as well as the right one: same bytes.
+        if (pp->line_hint == 0 && pp->line_table != d_dirs3) {
+            uint32_t w = 0;
+            hipLaunchKernelGGL(first_line_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_dirs3, N, pp->d_line);
+            LRC_HIP(hipGetLastError());
+            LRC_HIP(hipMemcpyAsync(&w, pp->d_line, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream));
+            LRC_HIP(hipStreamSynchronize((hipStream_t)stream));
+            pp->line_auto = line_tiles_for(w, N);
+            pp->line_table = d_dirs3;
+        }
+        p.line_tiles = kTBlock == 64 ? (pp->line_hint ? line_tiles_for(pp->line_hint, N) : pp->line_auto) : 0u;
     }
     // the rows of submit k - 2 (this stream's previous scan; its scan pass was enqueued behind its trace) ride in front
     const int prev = (int)((k + lrc_pipe::kSets - 2) % lrc_pipe::kSets);
@@ -2781,6 +2919,7 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     rc = launch_trace(s, p, 1, T);
     if (rc) return rc;
     LRC_HIP(hipEventRecord(pp->ev_trace[set], T));
+    pp->line_last = p.line_tiles;
     if (p.pre.blocks) pp->pending[prev] = false;
     pp->out[set] = *d_out;
     pp->poses[set] = P;
@@ -2798,8 +2937,10 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
 #ifndef LRC_PIPE_SCAN_WAVES
 #define LRC_PIPE_SCAN_WAVES 64
 #endif
-        hipLaunchKernelGGL(compact_scan_kernel, dim3((uint32_t)(nsuper < LRC_PIPE_SCAN_WAVES ? nsuper : LRC_PIPE_SCAN_WAVES)), dim3(64), 0, T, (const uint32_t*)pp->rec[set].tile_count,
-                           ntiles, (uint64_t)0, pp->scratch[lane].d_tile_off, ntiles, pp->scratch[lane].d_super_total);
+        // (a lean set's counts are the popcounts of its keep masks; rec's tile_count is filled on the way for lrc_pipe_records)
+        hipLaunchKernelGGL(compact_scan_masks_kernel, dim3((uint32_t)(nsuper < LRC_PIPE_SCAN_WAVES ? nsuper : LRC_PIPE_SCAN_WAVES)), dim3(64), 0, T,
+                           (const uint64_t*)pp->keep_mask[set], pp->rec[set].tile_count, pp->scratch[lane].d_tile_off, ntiles,
+                           pp->scratch[lane].d_super_total);
         LRC_HIP(hipGetLastError());
         pp->pending[set] = true;
     } else {
@@ -3860,6 +4001,9 @@ int lrc_debug_scan_stats(lrc_scene* s, const double* poses16, uint64_t P, const 
     p.has_center = 1;
     p.max_range = max_range;
     p.stats = (uint32_t*)ds.p;
+    // LRC_STATS_LINE_WIDTH=W: the waves grouped as the scan pipeline groups them for lines of W rays (tools/trav_stats.py);
+    // the counters stay indexed by ray
+    p.line_tiles = kTBlock == 64 ? line_tiles_for((uint64_t)env_int("LRC_STATS_LINE_WIDTH", 0), N) : 0u;
     if ((rc = launch_trace(s, p, 1, nullptr, true))) return rc;
     LRC_HIP(hipDeviceSynchronize());
     LRC_HIP(hipMemcpy(stats, ds.p, n * kStatsWords * 4, hipMemcpyDeviceToHost));

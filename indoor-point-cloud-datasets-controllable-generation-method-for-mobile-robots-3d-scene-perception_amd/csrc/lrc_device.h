@@ -263,4 +263,57 @@ LRC_DI void hit_point(V3 o, V3 d, float t, V3& h, V3& pt) {
     pt.x = o.x + h.x * t; pt.y = o.y + h.y * t; pt.z = o.z + h.z * t;
 }
 
+// ---- two-line tiles of the scan pipeline ----------------------------------------------------------
+// A pose of tpp tiles of 64 rays, its rays in scan lines of W = 64 * wt consecutive table rows.  Tile u of the pose does not
+// take 64 consecutive rays of one line (11.25 degrees x 0 for the benchmark sensor) but 32 consecutive columns of two adjacent
+// lines (5.6 x 1.1 degrees): the wave's rays stay together for more of the descent.  With g = u / (2 wt) the line pair and
+// c0 = (u % (2 wt)) * 32 the first column, lanes 0-31 take ray (2g) W + c0 + lane and lanes 32-63 ray (2g + 1) W + c0 + lane - 32.
+// The 2 wt tiles of pair g cover its 2 W rays exactly once (2 wt column blocks of 32, two lines each); tiles past the last
+// whole pair (an odd last line, or rays behind the last whole line when W does not divide the pose) keep the 1-D mapping, which
+// covers exactly their own 64 rays.  So the mapping is a bijection of the pose's rays for ANY wt: a width that is not the
+// table's costs coherence, never a byte.  wt = 0: 1-D tiles.  Each half of a wave is half of a 1-D tile: rays
+// 64 t + 32 h ... + 31 of 1-D tile t, whose keep mask it fills as one 32-bit word.
+#ifndef LRC_HDI
+#define LRC_HDI __host__ __device__ __forceinline__
+#endif
+LRC_HDI uint32_t tile_ray(uint32_t u, uint32_t lane, uint32_t wt, uint32_t tpp) {
+    if (wt == 0u) return u * 64u + lane;
+    const uint32_t g = u / (2u * wt);
+    if ((g + 1u) * 2u * wt > tpp) return u * 64u + lane;
+    return ((2u * g + (lane >> 5)) * wt) * 64u + (u - g * 2u * wt) * 32u + (lane & 31u);
+}
+// the line width (in tiles) a pipeline uses for a table of N rays whose lines are W rays long: whole tiles per line, whole
+// lines per pose, at least one pair -- else 1-D tiles (0)
+LRC_HDI uint32_t line_tiles_for(uint64_t W, uint64_t N) {
+    if (W == 0 || W % 64u != 0 || N % W != 0 || N / W < 2u || N > 0xFFFFFFFFull) return 0u;
+    return (uint32_t)(W / 64u);
+}
+
+// ---- range filter without the float64 square root ----------------------------------------------------------------------
+// The reference keeps a return when dist < R with dist = sqrt(s), s = (ex*ex + ey*ey) + ez*ez, all float64 (raycast_engine_cpu.py:
+// 95-107).  The square root is only there to be compared, and it is correctly rounded and monotone, so away from R*R the
+// comparison can be made on s itself.  With u = 2^-53 (a float64 rounding is off by at most a factor 1 +- u):
+//   lo = fl(fl(R*R) * (1 - 2^-48)) <= R^2 (1 + u)^2 (1 - 2^-48) < R^2 (1 - 2^-52)^2.  For s < lo the exact root is below
+//        R (1 - 2^-52) <= pred(R) (neighbouring float64 are at most 2^-52 relative apart), and rounding is monotone:
+//        fl(sqrt(s)) <= pred(R) < R -- kept, as the reference keeps it.
+//   hi = fl(fl(R*R) * (1 + 2^-48)) >= R^2 (1 - u)^2 (1 + 2^-48) > R^2.  For s > hi the exact root is above R, so
+//        fl(sqrt(s)) >= R -- dropped, as the reference drops it.
+// s in [lo, hi] (about 2^-47 relative: a few tens of ulp either side of R*R) is decided by the square root itself, as before.
+// The bounds are formed in the kernel from the launch's max_range (four wave-uniform operations: the trace kernel's argument
+// block has no room for two more doubles without the register allocation changing, and the host test hook calls the same
+// function); fast = 0 (R not positive and finite, or R*R outside the normal range with room to spare) sends every ray to the
+// square root.  A NaN s is in no class that keeps it, with or without the root.
+struct RangeBand { double lo, hi; int fast; };
+LRC_HDI RangeBand range_band(double R) {
+    RangeBand b{0.0, 0.0, 0};
+    if (!(R >= 0x1p-500) || !(R <= 0x1p500)) return b;
+    const double r2 = R * R;
+    b.lo = r2 * (1.0 - 0x1p-48);
+    b.hi = r2 * (1.0 + 0x1p-48);
+    b.fast = 1;
+    return b;
+}
+LRC_HDI bool range_in_band(double s, double lo, double hi) { return (s >= lo) & (s <= hi); }   // the square root decides
+LRC_HDI bool range_below(double s, double lo) { return s < lo; }                               // outside the band: kept iff below
+
 }  // namespace lrcdev

@@ -877,6 +877,11 @@ class ScanPipe:
     def wait(self, stream=0):
         check(self._lib.lrc_pipe_wait(self._h, C.c_void_p(int(stream))), "lrc_pipe_wait")
 
+    def set_line_width(self, line_width):
+        """Hint: the table's rays come in scan lines of `line_width` rows (0: detect it from the table).  Regroups rays into
+        waves only; results do not depend on it (lrc_pipe_set_line_width)."""
+        check(self._lib.lrc_pipe_set_line_width(self._h, int(line_width)), "lrc_pipe_set_line_width")
+
     # ---- N ranks: ids + keep counts into the caller's send slab, an earlier gathered scan assembled in the launch's front ----
     @staticmethod
     def gathered(all_poses_t, all_prims_t, all_tile_counts_t, poses_per_slab, slab_stride_bytes, own_slab, own_ticket,

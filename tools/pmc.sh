@@ -30,7 +30,7 @@ for grp in \
   "FETCH_SIZE" \
   "WRITE_SIZE SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" ; do
   i=$((i+1))
-  timeout -k 10 240 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/p$i -- python3 $TARGET > $OUT/p$i.log 2>&1 || { echo "pass $i FAILED: $grp"; FAILED=1; }
+  timeout -k 10 240 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/p$i -- python3 $TARGET > $OUT/p$i.log 2>&1 || { echo "pass $i FAILED: $grp"; FAILED=1; break; }      # nothing more on the GPU after a failed pass
 done
 python3 $R/tools/pmc_summary.py $OUT $PAT > $OUT/summary.txt 2>&1
 cat $OUT/summary.txt

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-ray traversal counters of the C3 workload (instrumented kernel, lrc_debug_scan_stats): how many inner-node
-steps and triangle tests each ray takes, and how well the 64 lanes of a wave agree."""
+steps and triangle tests each ray takes, and how well the 64 lanes of a wave agree.
+TRAV_LINE_WIDTH=W (e.g. 2048): the waves are the scan pipeline's two-line tiles (32 columns x 2 adjacent lines of W rays,
+csrc/lrc_device.h tile_ray) instead of 64 consecutive rays -- in the kernel (LRC_STATS_LINE_WIDTH) and in the grouping here."""
 import os
 import sys
 
@@ -21,13 +23,25 @@ Lx, Ly, _ = synth.scene_size(name)
 from trajectory import line_trajectory, poses_from_waypoints  # noqa: E402
 poses = poses_from_waypoints(line_trajectory((1.0, Ly / 2, 1.0), (Lx - 1.0, Ly / 2, 1.0), 64))[:8]
 dirs = IndoorLidar(intrinsics=sensor, pose=np.eye(4)).sensor_directions()
-st = scene.scan_stats(poses, dirs, sensor.max_range).reshape(-1, 64, 5).astype(np.float64)   # waves of 64 consecutive rays
+LW = int(os.environ.get("TRAV_LINE_WIDTH", "0"))
+if LW:
+    os.environ["LRC_STATS_LINE_WIDTH"] = str(LW)
+st = scene.scan_stats(poses, dirs, sensor.max_range).reshape(len(poses), -1, 5)
+if LW:      # ray -> (tile, lane) as tile_ray maps it: tile u of line pair g takes 32 columns of lines 2g and 2g + 1
+    N, H = len(dirs), len(dirs) // LW
+    assert LW % 64 == 0 and N % LW == 0 and H >= 2
+    pairs = st[:, :(H // 2) * 2 * LW].reshape(len(poses), H // 2, 2, LW // 32, 32, 5).transpose(0, 1, 3, 2, 4, 5)
+    st = np.concatenate([pairs.reshape(len(poses), -1, 5), st[:, (H // 2) * 2 * LW:]], axis=1)
+st = st.reshape(-1, 64, 5).astype(np.float64)   # waves: 64 consecutive rays, or two-line tiles
 nodes, tris, uni, dead = st[..., 0], st[..., 1], st[..., 2], st[..., 3]
 print("scene", name, "pad-clause rejections", int(st[..., 4].sum()))
 print("rays", st.shape[0] * 64, "info", scene.info["max_depth"], scene.info["num_nodes"])
 for name, a in (("node steps", nodes), ("tri tests", tris)):
     print(f"{name:10s} per ray: mean {a.mean():6.2f}  p50 {np.median(a):5.1f}  p99 {np.percentile(a, 99):6.1f}  max {a.max():5.0f}"
           f"   per wave: mean-of-max {a.max(1).mean():6.2f}  ->  lane efficiency mean/max {a.mean() / a.max(1).mean():.2f}")
+# per wave, from the busiest lane (a lower bound of the wave's own count: a step is counted by the lanes live in it)
+print(f"tile {'32x2' if LW else '64x1'}: per wave uniform steps >= {uni.max(1).mean():.1f}, divergent steps >= {(nodes - uni).max(1).mean():.1f}, "
+      f"node iterations >= {nodes.max(1).mean():.1f}, lane use (nodes) {nodes.mean() / nodes.max(1).mean():.3f}")
 print(f"uniform (scalar) node steps per ray: {uni.mean():.2f} = {uni.mean() / nodes.mean():.0%} of node steps")
 print(f"dead node steps (no child hit) per ray: {dead.mean():.2f} = {dead.mean() / nodes.mean():.0%} of node steps")
 work = nodes * 45 + tris * 40
