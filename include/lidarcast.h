@@ -279,13 +279,20 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t num_segments, uint64_t seg_len,
  *                     `line_width` consecutive table rows (one elevation each).  A tracing wave then takes 32 columns of two
  *                     adjacent lines instead of 64 columns of one, which keeps its rays together for longer.  0 (the default):
  *                     automatic -- the length of the first run of equal z in the table, read once per table address the
- *                     pipeline has not seen (the first such submit synchronises the host with `stream` for a 4-byte
+ *                     pipeline has not seen (the first such submit synchronises the host with `stream` for an 8-byte
  *                     read-back; later submits add nothing -- so that first submit must not be made while `stream` is being
  *                     captured into a graph: give the width as a hint there, a hinted pipeline never synchronises).  A width is used when it is a multiple of 64 that divides
  *                     rays_per_pose into at least two lines; otherwise waves take 64 consecutive rays as before.  The width
  *                     only regroups rays into waves, and the regrouping is a bijection of the pose's rays for ANY width: a
  *                     wrong or stale one (another table at a recycled address, a table edited in place) can cost speed,
  *                     never a byte of the rows, counts or records.
+ *   lrc_pipe_set_tile_lines  how many adjacent scan lines a tracing wave takes when a line width is in use: 4 (16 columns of
+ *                     four lines), 2 (32 columns of two), 1 (64 consecutive rays, whatever the width), or 0 (the default):
+ *                     automatic.  Lines are grouped from line 0 and again from the first line whose direction has another z
+ *                     sign than line 0's (found with the automatic line width, in the same read-back; a hinted width has no
+ *                     such split), so that no wave holds lines above and below the horizon: by fours, then a pair if two or
+ *                     three lines remain, then an odd last line as 64 consecutive rays.  Like the width, this only regroups rays
+ *                     into waves, bijectively for any value: it never changes a byte.
  * Destroy the pipeline before its scene. */
 typedef struct lrc_pipe lrc_pipe;
 int lrc_pipe_create(lrc_scene* scene, uint64_t max_poses, uint64_t rays_per_pose, lrc_pipe** out_pipe);
@@ -296,6 +303,7 @@ int lrc_pipe_wait(lrc_pipe* pipe, void* stream);
 int lrc_pipe_records(lrc_pipe* pipe, uint64_t ticket, lrc_hits* out_records);
 int lrc_pipe_trace_ms(lrc_pipe* pipe, uint64_t ticket, float* out_ms);
 int lrc_pipe_set_line_width(lrc_pipe* pipe, uint64_t line_width);
+int lrc_pipe_set_tile_lines(lrc_pipe* pipe, uint32_t lines);
 
 /* The pipeline on N ranks (one process per GPU; the collective itself is the caller's: RCCL all-gather of the send slabs).
  *   lrc_pipe_submit_sharded  traces this rank's pose block like lrc_pipe_submit, with the triangle ids and per-wave keep counts

@@ -207,8 +207,8 @@ struct TraceParams {
     uint32_t tile_chunk_log2;  // 0: eight contiguous tile ranges, one per XCD; k + 1: chunks of 2^k tiles round robin
     uint32_t force_redo;       // test hook (LRC_DEBUG_FORCE_REDO=m): rays with gid % m == 0 take the redo path as well
     // lean record set with tiles_per_pose != 0 only (lrc_pipe_submit): lines of the scan pattern are 64 * line_tiles rays long
-    // and a tile takes 32 columns of two adjacent lines (lrc_device.h, tile_ray).  0: 64 consecutive rays.  (In the padding
-    // behind force_redo.)
+    // and a tile takes 64 / L columns of L = 2 or 4 adjacent lines (lrc_device.h, tile_ray; line_group below).  0: 64
+    // consecutive rays.  (In the padding behind force_redo.)
     uint32_t line_tiles;
     uint64_t* chain_word;      // launch chain (lrc_ctx::chain_word): the last workgroup stores chain_seq here when it starts
     uint64_t chain_seq;
@@ -246,6 +246,9 @@ struct TraceParams {
     const uint64_t* seg_offsets;   // explicit rays in S segments (poses): (S+1) ray offsets, or NULL
     const double* seg_centers3;    // (S,3) range-filter centres of the segments
     uint32_t num_segments;
+    // with line_tiles != 0: the line grouping of the tiles (lrc_device.h, tile_ray: bit 31 = groups of four lines, bits 0-30 =
+    // the first line of the other elevation sign).  0: groups of two from line 0.  (In the padding behind num_segments.)
+    uint32_t line_group;
     const double* poses16;     // GEN = 1, 2
     const double* dirs3;       // GEN = 1: (N,3) sensor-frame direction table
     const double* angles2;     // GEN = 2: (P*N,2) noisy (phi, theta) of the dual-axis sensor
@@ -476,11 +479,11 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
     }
     if (lean) {
         // two stores per ray: the row as the scatter copies it, and what the expansion for lrc_pipe_records needs besides
-        // the keep mask as two 32-bit words: each half of the wave is half of a 1-D tile (of two different ones in a two-line
-        // tile, lrc_device.h tile_ray), so two waves fill one mask, no atomics, nothing to zero.  The per-tile counts of a lean
-        // set are the scan pass's to form (popcount of the masks, compact_scan_masks_kernel).
+        // the keep mask as four 16-bit words: each quarter of the wave is a quarter of a 1-D tile (of four different ones in a
+        // four-line tile, lrc_device.h tile_ray), so up to four waves fill one mask, no atomics, nothing to zero.  The per-tile
+        // counts of a lean set are the scan pass's to form (popcount of the masks, compact_scan_masks_kernel).
         const unsigned long long m = __ballot(keep);
-        if ((tid & 31u) == 0) ((uint32_t*)p.lean.keep_mask)[gid >> 5] = (uint32_t)(m >> (tid & 32u));
+        if ((tid & 15u) == 0) ((uint16_t*)p.lean.keep_mask)[gid >> 4] = (uint16_t)(m >> (tid & 48u));
         p.lean.row[gid] = make_float4(px, py, pz, __uint_as_float(label));
         p.lean.aux[gid] = make_uint2(__float_as_uint(t_out), keep ? best_slot : 0xFFFFFFFFu);
         return;
@@ -767,7 +770,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
             const uint32_t pu = tile / p.tiles_per_pose;
             pose = pu;
             const uint32_t u = tile - pu * p.tiles_per_pose;
-            i = p.line_tiles != 0u ? tile_ray(u, tid, p.line_tiles, p.tiles_per_pose) : u * (uint32_t)kTBlock + tid;
+            i = p.line_tiles != 0u ? tile_ray(u, tid, p.line_tiles, p.tiles_per_pose, p.line_group) : u * (uint32_t)kTBlock + tid;
         } else {
             pose = gid / p.rays_per_pose;
             i = gid - pose * p.rays_per_pose;
@@ -1165,9 +1168,9 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
     const uint32_t tile_w = p.tile_chunk_log2 ? xcd_tile_chunked(wg - p.pre.blocks, gridDim.x - p.pre.blocks, p.tile_chunk_log2)
                                               : xcd_tile(wg - p.pre.blocks, gridDim.x - p.pre.blocks);
     uint64_t gid_w = (uint64_t)tile_w * kTBlock + tid;
-    if (GEN == 1 && p.tiles_per_pose != 0u && p.line_tiles != 0u) {      // two-line tile: the same mapping as in front of the traversal
+    if (GEN == 1 && p.tiles_per_pose != 0u && p.line_tiles != 0u) {      // line-group tile: the same mapping as in front of the traversal
         const uint32_t pu = tile_w / p.tiles_per_pose;
-        gid_w = (uint64_t)pu * p.rays_per_pose + tile_ray(tile_w - pu * p.tiles_per_pose, tid, p.line_tiles, p.tiles_per_pose);
+        gid_w = (uint64_t)pu * p.rays_per_pose + tile_ray(tile_w - pu * p.tiles_per_pose, tid, p.line_tiles, p.tiles_per_pose, p.line_group);
     }
     if (GEN == 4) {
         // the range-filter centre c(s), float64, formed again from the record and fire[i] (as GEN = 1 fetches the pose's
@@ -1421,11 +1424,23 @@ __global__ __launch_bounds__(64) void first_line_kernel(const double* __restrict
         const unsigned long long m = __ballot(i < n && dirs3[i * 3 + 2] != z0);
         if (m != 0ull) { w = base + (uint64_t)__builtin_ctzll(m); break; }
     }
-    if (lane == 0) *out = w > 0xFFFFFFFFull ? 0u : (uint32_t)w;
+    // out[1]: the first line (of w rays) whose z has another sign than line 0's -- the split of the line groups (lrc_device.h,
+    // tile_ray); the number of whole lines if there is none
+    const uint64_t h = w != 0 ? n / w : 0;
+    uint64_t sp = h;
+    for (uint64_t base = 0; base < h; base += 64) {
+        const uint64_t j = base + lane;
+        const unsigned long long m = __ballot(j < h && (dirs3[j * w * 3 + 2] < 0.0) != (z0 < 0.0));
+        if (m != 0ull) { sp = base + (uint64_t)__builtin_ctzll(m); break; }
+    }
+    if (lane == 0) {
+        out[0] = w > 0xFFFFFFFFull ? 0u : (uint32_t)w;
+        out[1] = sp > 0x7FFFFFFFull ? 0u : (uint32_t)sp;
+    }
 }
 
 // the scan pass of a lean record set (lrc_pipe_submit): the counts are the popcounts of the tiles' keep masks -- the tracing
-// waves of a two-line tile each hold halves of two tiles and write no counts -- and go to tile_cnt_out as a by-product (what
+// waves of a line-group tile each hold halves or quarters of several tiles and write no counts -- and go to tile_cnt_out as a by-product (what
 // lrc_pipe_records hands out as lrc_hits.tile_count)
 __global__ __launch_bounds__(64) void compact_scan_masks_kernel(const uint64_t* keep_mask, uint32_t* tile_cnt_out, uint32_t* tile_off,
                                                                 uint64_t ntiles, uint32_t* super_total) {
@@ -1681,6 +1696,16 @@ uint32_t lrc_internal_tile_map(uint64_t line_width, uint32_t tpp, uint32_t* out_
         for (uint32_t u = 0; u < tpp; ++u)
             for (uint32_t l = 0; l < 64u; ++l) out_ray[(size_t)u * 64u + l] = tile_ray(u, l, wt, tpp);
     return wt;
+}
+// ... and its line-group form (tests/test_tile_groups.py): `lines` (1, 2, 4) lines per tile, groups kept on either side of line
+// `split`.  Returns the lines per tile of the widest group the mapping forms.
+uint32_t lrc_internal_tile_map_groups(uint64_t line_width, uint32_t tpp, uint32_t split, uint32_t lines, uint32_t* out_ray) {
+    const uint32_t wt = lines >= 2u ? line_tiles_for(line_width, (uint64_t)tpp * 64u) : 0u;
+    const uint32_t grp = line_group_for(split, lines);
+    if (out_ray)
+        for (uint32_t u = 0; u < tpp; ++u)
+            for (uint32_t l = 0; l < 64u; ++l) out_ray[(size_t)u * 64u + l] = tile_ray(u, l, wt, tpp, grp);
+    return tile_lines_of(wt, tpp, grp);
 }
 // test hook (tests/test_range_band.py): the range filter's decision for squared distances s[0..n) against max_range, made by the
 // host compilation of the very functions the kernel calls (lrc_device.h, range_band): keep[i] = the filter keeps s[i];
@@ -2238,6 +2263,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     // two-line tiles: lean record sets only (the serial calls' tile_count is per 64 consecutive outputs), and the counters of
     // the instrumented kernel, which has no tile_count
     if (p.tiles_per_pose == 0u || (p.lean.row == nullptr && !stats)) p.line_tiles = 0u;
+    if (p.line_tiles == 0u) p.line_group = 0u;
     // stack entries needed = deepest leaf depth (one pending sibling per inner level above it)
     const uint32_t depth = s->info.max_depth < 1 ? 1 : s->info.max_depth;
     const size_t lds = (size_t)depth * kTBlock * sizeof(int);
@@ -2700,6 +2726,9 @@ static int ensure_tile_scratch(lrc_ctx* ctx, lrc_ctx::TileScratch& sc, uint64_t 
 // scatter reads, two stores per ray instead of ten, no triangle id and no normal in the trace.  The
 // complete 36-byte record, in arrays of its own beside the lean ones, is what the plain fallback and the sharded submits
 // write, and what lrc_pipe_records expands a lean set into on demand.
+#ifndef LRC_PIPE_TILE_LINES
+#define LRC_PIPE_TILE_LINES 4      // lines per tile of an automatic submit (profiles/trace_line_group_tiles.txt)
+#endif
 struct lrc_pipe {
     lrc_scene* scene = nullptr;
     int device = 0;
@@ -2733,6 +2762,9 @@ struct lrc_pipe {
     uint32_t line_auto = 0;                                  // its line width in tiles, 0: 1-D tiles
     uint32_t* d_line = nullptr;
     uint32_t line_last = 0;                                  // line width in tiles the last submit's launch ran with
+    // line-group tiles (lrc_pipe_set_tile_lines): lines per tile asked for (0: automatic = 4 where the table has a group of
+    // four), the split line detected with line_auto, and what the last launch ran with
+    uint32_t lines_hint = 0, split_auto = 0, lines_last = 1, group_last = 0;
 };
 
 int lrc_pipe_destroy(lrc_pipe* pp) {
@@ -2817,7 +2849,7 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
             return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
     }
     if (hipEventCreateWithFlags(&pp->ev_expand, hipEventDisableTiming) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
-    if (pp->fused && hipMalloc((void**)&pp->d_line, sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory")); }
+    if (pp->fused && hipMalloc((void**)&pp->d_line, 2 * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory")); }
     *out_pipe = pp;
     return LRC_OK;
 }
@@ -2849,6 +2881,17 @@ int wait_for_readers(lrc_pipe* pp, int set, hipStream_t T) {
 // test hook (tests/test_pipe_two_line_gpu.py): the line width, in tiles of 64 rays, the trace launch of the pipeline's last
 // lrc_pipe_submit ran with (0: 1-D tiles) -- the regrouping changes no byte, so no output can tell whether it happened
 uint32_t lrc_internal_pipe_line_tiles(const lrc_pipe* pp) { return pp ? pp->line_last : 0u; }
+
+// ... and its lines per tile (4, 2, or 1 for 1-D tiles) and line grouping word (lrc_device.h, tile_ray)
+uint32_t lrc_internal_pipe_tile_lines(const lrc_pipe* pp) { return pp ? pp->lines_last : 0u; }
+uint32_t lrc_internal_pipe_line_group(const lrc_pipe* pp) { return pp ? pp->group_last : 0u; }
+
+int lrc_pipe_set_tile_lines(lrc_pipe* pp, uint32_t lines) {
+    if (!pp) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_set_tile_lines: pipe is NULL");
+    if (lines != 0u && lines != 1u && lines != 2u && lines != 4u) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_set_tile_lines: lines must be 0, 1, 2 or 4");
+    pp->lines_hint = lines;
+    return LRC_OK;
+}
 
 int lrc_pipe_set_line_width(lrc_pipe* pp, uint64_t line_width) {
     if (!pp) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_set_line_width: pipe is NULL");
@@ -2885,19 +2928,26 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     p.out = pp->rec[set];
     if (pp->fused) {           // the lean form: only what the scatter reads (the plain fallback below reads the full record)
         p.lean.row = pp->row[set]; p.lean.aux = pp->aux[set]; p.lean.keep_mask = pp->keep_mask[set];
-        // two-line tiles: the hinted line width, or the table's own, detected once per table address -- on the caller's
+        // line-group tiles: the hinted line width, or the table's own, detected once per table address -- on the caller's
         // stream, whose position the table is valid at, with a 4-byte read-back; nothing afterwards.  A stale width (a new
         // table at a recycled address, a table edited in place) maps the rays as well as the right one: same bytes.
         if (pp->line_hint == 0 && pp->line_table != d_dirs3) {
-            uint32_t w = 0;
+            uint32_t w[2] = {0, 0};
             hipLaunchKernelGGL(first_line_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_dirs3, N, pp->d_line);
             LRC_HIP(hipGetLastError());
-            LRC_HIP(hipMemcpyAsync(&w, pp->d_line, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream));
+            LRC_HIP(hipMemcpyAsync(w, pp->d_line, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream));
             LRC_HIP(hipStreamSynchronize((hipStream_t)stream));
-            pp->line_auto = line_tiles_for(w, N);
+            pp->line_auto = line_tiles_for(w[0], N);
+            pp->split_auto = w[1];
             pp->line_table = d_dirs3;
         }
-        p.line_tiles = kTBlock == 64 ? (pp->line_hint ? line_tiles_for(pp->line_hint, N) : pp->line_auto) : 0u;
+        p.line_tiles = kTBlock == 64 && pp->lines_hint != 1u ? (pp->line_hint ? line_tiles_for(pp->line_hint, N) : pp->line_auto) : 0u;
+        // line groups: of four lines unless two are asked for, on either side of the split detected with the width (a hinted
+        // width has no detection behind it -- a hinted pipeline never synchronises -- and no split).  Where the table has no
+        // group of four the word yields the two-line mapping.
+        if (p.line_tiles != 0u)
+            p.line_group = line_group_for(pp->line_hint == 0 ? pp->split_auto : 0u,
+                                          pp->lines_hint == 0u ? (uint32_t)LRC_PIPE_TILE_LINES : pp->lines_hint);
     }
     // the rows of submit k - 2 (this stream's previous scan; its scan pass was enqueued behind its trace) ride in front
     const int prev = (int)((k + lrc_pipe::kSets - 2) % lrc_pipe::kSets);
@@ -2920,6 +2970,8 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     if (rc) return rc;
     LRC_HIP(hipEventRecord(pp->ev_trace[set], T));
     pp->line_last = p.line_tiles;
+    pp->group_last = p.line_group;
+    pp->lines_last = tile_lines_of(p.line_tiles, (uint32_t)(N / 64), p.line_group);
     if (p.pre.blocks) pp->pending[prev] = false;
     pp->out[set] = *d_out;
     pp->poses[set] = P;
@@ -4003,7 +4055,9 @@ int lrc_debug_scan_stats(lrc_scene* s, const double* poses16, uint64_t P, const 
     p.stats = (uint32_t*)ds.p;
     // LRC_STATS_LINE_WIDTH=W: the waves grouped as the scan pipeline groups them for lines of W rays (tools/trav_stats.py);
     // the counters stay indexed by ray
+    // LRC_STATS_TILE_LINES=4 with LRC_STATS_LINE_SPLIT=s: groups of four lines on either side of line s
     p.line_tiles = kTBlock == 64 ? line_tiles_for((uint64_t)env_int("LRC_STATS_LINE_WIDTH", 0), N) : 0u;
+    p.line_group = line_group_for((uint32_t)env_int("LRC_STATS_LINE_SPLIT", 0), (uint32_t)env_int("LRC_STATS_TILE_LINES", 2));
     if ((rc = launch_trace(s, p, 1, nullptr, true))) return rc;
     LRC_HIP(hipDeviceSynchronize());
     LRC_HIP(hipMemcpy(stats, ds.p, n * kStatsWords * 4, hipMemcpyDeviceToHost));

@@ -276,11 +276,48 @@ LRC_DI void hit_point(V3 o, V3 d, float t, V3& h, V3& pt) {
 #ifndef LRC_HDI
 #define LRC_HDI __host__ __device__ __forceinline__
 #endif
-LRC_HDI uint32_t tile_ray(uint32_t u, uint32_t lane, uint32_t wt, uint32_t tpp) {
+//
+// Line-group tiles generalise this to 64 / L columns of L adjacent lines, L in {1, 2, 4}.  `grp` packs the grouping: bit 31
+// set = groups of four lines where there are four, bits 0-30 = split, the first line whose elevation sign differs from line
+// 0's (0, or anything not below the number of whole lines: no split).  Lines [0, split) and [split, H) are grouped each from
+// its own start, so that no group holds lines of both signs (a wave of both points into two direction octants and walks
+// the float32 nodes): groups of 4 (bit 31), then one group of 2 if 2 or 3 lines remain (without bit 31: groups of 2 all the
+// way), then 1-D tiles for an odd last line.  A group of L lines starting at line a owns tiles [a wt, (a + L) wt) and rays
+// [a W, (a + L) W); its tile r takes columns [r 64 / L, (r + 1) 64 / L) of each of its lines, lanes [j 64 / L, (j + 1) 64 / L)
+// line a + j: every ray of the group once.  Groups, odd lines and the tiles behind the last whole line partition the pose's
+// tiles and, range for range, its rays: a bijection for ANY (wt, tpp, grp).  grp = 0 is the two-line mapping above.  Each
+// quarter of a wave is a quarter of a 1-D tile: rays 64 t + 16 q ... + 15, 16 bits of tile t's keep mask.
+// One division (the tile's line); whether a group is whole is decided by products against the run's last tile -- the
+// mapping runs twice per wave, in front of and behind the traversal, and a scalar division costs some twenty instructions.
+LRC_HDI uint32_t tile_ray(uint32_t u, uint32_t lane, uint32_t wt, uint32_t tpp, uint32_t grp = 0u) {
     if (wt == 0u) return u * 64u + lane;
-    const uint32_t g = u / (2u * wt);
-    if ((g + 1u) * 2u * wt > tpp) return u * 64u + lane;
-    return ((2u * g + (lane >> 5)) * wt) * 64u + (u - g * 2u * wt) * 32u + (lane & 31u);
+    const uint32_t line = u / wt, c = u - line * wt;          // this tile's line as a 1-D tile, its place in the line
+    const uint32_t s = grp & 0x7FFFFFFFu;
+    const uint64_t sw = (uint64_t)s * wt;
+    // the run of lines of one sign this tile lies in: first line l0, tiles end at `lim` (s beyond the whole lines: one run)
+    const uint32_t l0 = line < s ? 0u : s;
+    const uint32_t lim = (line < s && sw < tpp) ? (uint32_t)sw : tpp;
+    const uint32_t k = line - l0;
+    const uint32_t b4 = (grp >> 31) != 0u ? (k & ~3u) : 0u;   // first line (in the run) of the would-be group of four, ...
+    if ((grp >> 31) != 0u && (l0 + b4 + 4u) * wt <= lim)
+        return ((l0 + b4 + (lane >> 4)) * wt) * 64u + ((k & 3u) * wt + c) * 16u + (lane & 15u);
+    const uint32_t b2 = b4 + ((k - b4) & ~1u);                // ... of the would-be pair behind the run's groups of four
+    if ((l0 + b2 + 2u) * wt <= lim)
+        return ((l0 + b2 + (lane >> 5)) * wt) * 64u + (((k - b4) & 1u) * wt + c) * 32u + (lane & 31u);
+    return u * 64u + lane;
+}
+// the grouping word for `lines` (4: groups of four; anything else: of two) lines per tile and a split line
+LRC_HDI uint32_t line_group_for(uint32_t split, uint32_t lines) {
+    return (split > 0x7FFFFFFFu ? 0u : split) | (lines == 4u ? 0x80000000u : 0u);
+}
+// lines per tile the mapping above yields at its widest for (wt, tpp, grp): 4, 2, or 1 (no group at all)
+LRC_HDI uint32_t tile_lines_of(uint32_t wt, uint32_t tpp, uint32_t grp) {
+    if (wt == 0u) return 1u;
+    const uint32_t hf = tpp / wt;
+    uint32_t s = grp & 0x7FFFFFFFu;
+    if (s >= hf) s = 0u;
+    const uint32_t a = s, b = hf - s, m = a > b ? a : b;
+    return ((grp >> 31) != 0u && m >= 4u) ? 4u : (m >= 2u ? 2u : 1u);
 }
 // the line width (in tiles) a pipeline uses for a table of N rays whose lines are W rays long: whole tiles per line, whole
 // lines per pose, at least one pair -- else 1-D tiles (0)

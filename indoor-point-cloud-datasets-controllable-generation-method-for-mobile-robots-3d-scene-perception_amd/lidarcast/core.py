@@ -882,6 +882,11 @@ class ScanPipe:
         waves only; results do not depend on it (lrc_pipe_set_line_width)."""
         check(self._lib.lrc_pipe_set_line_width(self._h, int(line_width)), "lrc_pipe_set_line_width")
 
+    def set_tile_lines(self, lines):
+        """Adjacent scan lines per tracing wave: 4, 2, 1 (64 consecutive rays) or 0 (automatic).  Regroups rays into waves
+        only; results do not depend on it (lrc_pipe_set_tile_lines)."""
+        check(self._lib.lrc_pipe_set_tile_lines(self._h, int(lines)), "lrc_pipe_set_tile_lines")
+
     # ---- N ranks: ids + keep counts into the caller's send slab, an earlier gathered scan assembled in the launch's front ----
     @staticmethod
     def gathered(all_poses_t, all_prims_t, all_tile_counts_t, poses_per_slab, slab_stride_bytes, own_slab, own_ticket,

@@ -8,9 +8,12 @@ together (near child first, the far one pushed, pruned by the closest hit so far
 leaf, two triangle records per round; then every lane pops.  A step is uniform when all live lanes are at the same node.
 Rays: the C3 table (32 x 2048) at the given poses of the bench trajectory (default 0 21 42 63).  No GPU, numpy only.
 
-Output per tile shape (columns x lines): uniform / divergent steps and leaf rounds per wave, lane use of the node steps,
-waves whose rays point into more than one octant, and modelled vector instructions and per-lane vector loads per wave
-(40 / 48 / 110 instructions and 0 / 2 / 6 loads per uniform step / divergent step / leaf round)."""
+Output per tile shape (columns x lines x poses): uniform / divergent steps and leaf rounds per wave, lane use of the node
+steps, waves whose rays point into more than one octant, and modelled vector instructions and per-lane vector loads per wave
+(28 / 42 / 110 instructions -- the counts of the compiled product kernel -- and 0 / 2 / 6 loads per uniform step / divergent
+step / leaf round).  "16x4 split" is the pipeline's grouping (csrc/lrc_device.h, tile_ray): lines above and below the horizon
+grouped separately, by fours, then a pair, then an odd line.  The shapes that span two poses (rejected: DESIGN.md section 10)
+pair each given pose with the one MODEL_POSE_STRIDE (default 1 = 4.8 cm) further along the bench trajectory."""
 import os
 import sys
 
@@ -189,6 +192,25 @@ def groups_for(P, H, Wd, cols, lines):
     return idx.transpose(0, 1, 3, 2, 4).reshape(-1, 64)
 
 
+def groups_split(P, H, Wd, lines, split):
+    """The pipeline's line groups: runs [0, split) and [split, H) cut into groups of `lines` (4: then a pair, then an odd line)."""
+    tiles = []
+    for a, b in (((0, split), (split, H)) if 0 < split < H else ((0, H),)):
+        line = a
+        while line < b:
+            g = 4 if (lines == 4 and b - line >= 4) else (2 if (lines >= 2 and b - line >= 2) else 1)
+            tiles.append((np.arange(g * Wd).reshape(g, g * Wd // 64, 64 // g).transpose(1, 0, 2) + line * Wd).reshape(-1, 64))
+            line += g
+    one = np.concatenate(tiles)
+    return (one[None] + (np.arange(P) * H * Wd)[:, None, None]).reshape(-1, 64)
+
+
+def groups_pose_span(P, H, Wd, cols, lines):
+    """Tiles of cols x lines x 2 adjacent poses (cols * lines * 2 == 64): poses (0, 1), (2, 3), ..."""
+    idx = np.arange(P * H * Wd).reshape(P // 2, 2, H // lines, lines, Wd // cols, cols)
+    return idx.transpose(0, 2, 4, 1, 3, 5).reshape(-1, 64)
+
+
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else bench.SCENE
     sel = [int(a) for a in sys.argv[2:]] or [0, 21, 42, 63]
@@ -199,21 +221,32 @@ def main():
     tv = v[t[order]]
     sensor = bench.c3_sensor()
     dirs = IndoorLidar(sensor, np.eye(4)).sensor_directions()
+    stride = int(os.environ.get("MODEL_POSE_STRIDE", "1"))
+    span = os.environ.get("MODEL_POSE_SPAN", "0") == "1"      # also the shapes over two poses: every pose with its partner
+    if span:
+        sel = [q for s_ in sel for q in (min(s_, 63 - stride), min(s_, 63 - stride) + stride)]
     poses = bench.c3_poses(0, 1)[sel]
     H, Wd = 32, len(dirs) // 32
     o = np.repeat(poses[:, :3, 3].astype(np.float32).astype(np.float64), len(dirs), axis=0)
     d = np.concatenate([(dirs @ p[:3, :3].T).astype(np.float32).astype(np.float64) for p in poses])
     octant = (d[:, 0] < 0) | ((d[:, 1] < 0) << 1) | ((d[:, 2] < 0) << 2)
     print("tile   uniform/wave  divergent/wave  leaf rounds/wave  lane use  mixed octants  model VALU/wave  vector loads/wave  node steps/ray")
-    for cols, lines in ((64, 1), (32, 2), (16, 4)):
-        g = groups_for(len(poses), H, Wd, cols, lines)
+    z = dirs[::Wd, 2]
+    split = int(np.argmax((z < 0) != (z[0] < 0)))
+    shapes = [("64x1", lambda: groups_for(len(poses), H, Wd, 64, 1)), ("32x2", lambda: groups_for(len(poses), H, Wd, 32, 2)),
+              ("16x4", lambda: groups_for(len(poses), H, Wd, 16, 4)),
+              (f"16x4 split {split}", lambda: groups_split(len(poses), H, Wd, 4, split))]
+    if span:
+        shapes += [("16x2x2", lambda: groups_pose_span(len(poses), H, Wd, 16, 2)), ("8x4x2", lambda: groups_pose_span(len(poses), H, Wd, 8, 4))]
+    for label, make in shapes:
+        g = make()
         uni, div, rounds, steps = lockstep(o, d, g, boxes, kids, tv)
         per_wave_steps = steps[np.arange(g.size)].reshape(-1, 64)
         use = per_wave_steps.sum() / ((uni + div).sum() * 64.0)
         mixed = (octant[g].min(1) != octant[g].max(1)).mean()
-        valu = 40 * uni.mean() + 48 * div.mean() + 110 * rounds.mean()
+        valu = 28 * uni.mean() + 42 * div.mean() + 110 * rounds.mean()
         loads = 2 * div.mean() + 6 * rounds.mean()
-        print(f"{cols}x{lines:<3d} {uni.mean():12.1f} {div.mean():15.1f} {rounds.mean():17.2f} {use:9.3f} {mixed:13.2%} {valu:16.0f} "
+        print(f"{label:14s} {uni.mean():12.1f} {div.mean():15.1f} {rounds.mean():17.2f} {use:9.3f} {mixed:13.2%} {valu:16.0f} "
               f"{loads:18.0f} {steps.mean():15.1f}", flush=True)
 
 
