@@ -906,6 +906,65 @@ int lrc_voxgrid_finalize(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* out_id
 /* Copy out the free bitset (words uint32; bit v of word v/32, least significant bit first). */
 int lrc_voxgrid_export_bits(lrc_voxgrid* vg, uint32_t* out_bits);
 
+/* ---- per-frame object annotations of scans ----------------------------------------------------
+ * What a detector that trains on one sweep at a time needs, per (frame, object), in the SENSOR's frame: how many returns
+ * the object got, how much of it is visible and where the visible part lies.  Definitions:
+ *   object        object k is the k-th distinct label word key = sem | ins << 16 among the mesh's triangles, ascending
+ *                 (the label-bit layout of lrc_hits.t_label).  Without label arrays there is one object, key 0; a NULL
+ *                 tri_sem or tri_ins counts as all zero.  More than 4096 objects are refused (LRC_ERR_INVALID_ARG).
+ *   static table  per object: key, tri_count (uint32), total_q (uint64: the sum of the quantised areas q of section 5e,
+ *                 the same numbers lrc_coverage_export returns), wmin[3] / wmax[3] (float64: the AABB of the vertices of
+ *                 the object's triangles, as given).  Built on the device at create; input checks as lrc_coverage_create.
+ *   returned ray  as in section 5e: t finite and prim < num_triangles.  A returned ray whose point3 row has a non-finite
+ *                 coordinate is ignored and counted in rejected_rays.  Rows of rays that do not return are never read.
+ *   sensor frame  pose M (row-major 4x4 float64), R = M[:3,:3], c = M[:3,3], x = the ray's float32 point3 row widened
+ *                 exactly: e = x - c, s_a = (R[0][a]*e_0 + R[1][a]*e_1) + R[2][a]*e_2, float64, no fused multiply-add.
+ *   accumulators  returns (uint32): returned rays whose triangle belongs to k.  seen_tris (uint32): triangles of k with
+ *                 at least one return in the frame.  seen_q (uint64): the sum of q over those triangles, each once per
+ *                 frame however many rays hit it and however many calls deliver them.  vmin[3] / vmax[3] (float64): min
+ *                 and max of s over the returns in the IEEE total order on finite values (-0.0 below +0.0); +inf / -inf
+ *                 while returns == 0.
+ *   accumulate    pose p of a call goes to frame first_frame + p; calls add up until reset.  Accumulating a frame twice
+ *                 doubles returns and leaves seen_tris, seen_q, vmin and vmax as they were.  The result depends neither on
+ *                 pose order, nor on chunking, nor on the order of atomics (integer counts and sums, an OR-ed bitset of
+ *                 words_per_frame = ceil(T/32) words per frame, integer min / max on an order-preserving image).
+ * The object is not thread-safe and its calls must be ordered on one stream; "_dev" entry points enqueue on `stream`,
+ * the others return after the work finished. */
+typedef struct lrc_frameobj lrc_frameobj;
+
+typedef struct lrc_frameobj_info {
+    uint64_t num_triangles;
+    uint64_t num_frames;
+    uint64_t num_objects;
+    uint64_t words_per_frame;  /* ceil(num_triangles / 32)                                         */
+    uint64_t rejected_rays;    /* returned rays with a non-finite point since the last reset       */
+} lrc_frameobj_info;           /* 40 bytes */
+
+int lrc_frameobj_create(lrc_ctx* ctx, const double* verts3, uint64_t num_vertices, const int32_t* tris3,
+                        uint64_t num_triangles, const uint16_t* tri_sem /* nullable */,
+                        const uint16_t* tri_ins /* nullable */, uint64_t num_frames, lrc_frameobj** out_fo);
+int lrc_frameobj_destroy(lrc_frameobj* fo);
+/* Synchronises the device (rejected_rays is read back). */
+int lrc_frameobj_get_info(const lrc_frameobj* fo, lrc_frameobj_info* out);
+/* The static table, num_objects rows: key, tri_count, total_q, wmin (K,3), wmax (K,3); any pointer may be NULL. */
+int lrc_frameobj_objects(const lrc_frameobj* fo, uint32_t* out_key, uint32_t* out_tri_count, uint64_t* out_total_q,
+                         double* out_wmin, double* out_wmax);
+/* Zero the counts, the bitsets and rejected_rays; vmin / vmax back to +inf / -inf. */
+int lrc_frameobj_reset(lrc_frameobj* fo, void* stream);
+/* d_poses16 (num_poses x 16 float64, row-major 4x4) and the d_t / d_prim / d_point3 records of num_poses x rays_per_pose
+ * rays, pose-major as lrc_scan_poses_dev writes them.  first_frame + num_poses > num_frames and NULL pointers are
+ * refused with LRC_ERR_INVALID_ARG before anything is launched. */
+int lrc_frameobj_accumulate_dev(lrc_frameobj* fo, const double* d_poses16, uint64_t num_poses, uint64_t rays_per_pose,
+                                const float* d_t, const uint32_t* d_prim, const float* d_point3, uint64_t first_frame,
+                                void* stream);
+/* The per-(frame, object) arrays in C order: returns, seen_tris, seen_q (F, K); vmin, vmax (F, K, 3).  NULL skips one.
+ * The host form waits for the device, then copies (blocking; rejected_rays is a separate lrc_frameobj_get_info call, which
+ * waits again); the _dev form writes device memory on `stream`. */
+int lrc_frameobj_export(lrc_frameobj* fo, uint32_t* out_returns, uint32_t* out_seen_tris, uint64_t* out_seen_q,
+                        double* out_vmin, double* out_vmax);
+int lrc_frameobj_export_dev(lrc_frameobj* fo, uint32_t* d_returns, uint32_t* d_seen_tris, uint64_t* d_seen_q,
+                            double* d_vmin, double* d_vmax, void* stream);
+
 /* Resident waves per CU the runtime grants the pose-batched trace kernel on this scene (its LDS stack is sized by
  * the tree depth), its VGPR count and LDS bytes per wave: the occupancy figure bench.py reports. */
 int lrc_scene_get_occupancy(const lrc_scene* scene, int* waves_per_cu, int* vgprs, int* lds_bytes);

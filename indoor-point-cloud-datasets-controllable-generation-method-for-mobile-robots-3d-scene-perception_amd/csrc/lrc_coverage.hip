@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/lidarcast.h"
+#include "lrc_area.h"
 
 extern "C" int lrc_internal_fail(int code, const char* msg);
 extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
@@ -59,20 +60,7 @@ __global__ __launch_bounds__(kBlock) void area_kernel(const double* __restrict__
                                                       uint64_t T, uint64_t* __restrict__ q, uint32_t* __restrict__ flag) {
     const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= T) return;
-    const uint64_t a = (uint32_t)f[3 * j], b = (uint32_t)f[3 * j + 1], c = (uint32_t)f[3 * j + 2];
-    const double ux = v[3 * b] - v[3 * a], uy = v[3 * b + 1] - v[3 * a + 1], uz = v[3 * b + 2] - v[3 * a + 2];
-    const double wx = v[3 * c] - v[3 * a], wy = v[3 * c + 1] - v[3 * a + 1], wz = v[3 * c + 2] - v[3 * a + 2];
-    const double cx = uy * wz - uz * wy;
-    const double cy = uz * wx - ux * wz;
-    const double cz = ux * wy - uy * wx;
-    const double area = 0.5 * __builtin_sqrt((cx * cx + cy * cy) + cz * cz);
-    const double s = area * 4294967296.0;                 // exact: a power of two
-    if (s < 9223372036854775808.0) {                      // 2^63; vertices are finite (checked on the host)
-        q[j] = (uint64_t)__builtin_rint(s);
-    } else {
-        q[j] = 0;
-        atomicOr(flag, 1u);
-    }
+    if (!lrc_area_q(v, f, j, &q[j])) atomicOr(flag, 1u);  // lrc_area.h: the one definition of q
 }
 
 // ---- accumulate -------------------------------------------------------------------------------------------------

@@ -47,6 +47,8 @@ SYMBOLS = (
     "lrc_coverage_select_dev", "lrc_coverage_export",
     "lrc_voxgrid_create", "lrc_voxgrid_destroy", "lrc_voxgrid_get_info", "lrc_voxgrid_reset", "lrc_voxgrid_accumulate_dev",
     "lrc_voxgrid_finalize", "lrc_voxgrid_finalize_dev", "lrc_voxgrid_export_bits",
+    "lrc_frameobj_create", "lrc_frameobj_destroy", "lrc_frameobj_get_info", "lrc_frameobj_objects", "lrc_frameobj_reset",
+    "lrc_frameobj_accumulate_dev", "lrc_frameobj_export", "lrc_frameobj_export_dev",
     "lrc_occ_create", "lrc_occ_destroy", "lrc_occ_query",
     "lrc_rng_scan_draws", "lrc_rays_from_trig",
 )
@@ -93,6 +95,11 @@ class LrcVoxgridInfo(C.Structure):
 class LrcVoxgridCounts(C.Structure):
     _fields_ = [("num_sparse", C.c_uint64), ("num_free", C.c_uint64), ("num_occupied", C.c_uint64),
                 ("num_unknown", C.c_uint64), ("rejected_rays", C.c_uint64), ("returns", C.c_uint64)]
+
+
+class LrcFrameobjInfo(C.Structure):
+    _fields_ = [("num_triangles", C.c_uint64), ("num_frames", C.c_uint64), ("num_objects", C.c_uint64),
+                ("words_per_frame", C.c_uint64), ("rejected_rays", C.c_uint64)]
 
 
 class LrcCompactIO(C.Structure):
@@ -271,6 +278,14 @@ def load():
         "lrc_voxgrid_finalize": [vp, C.c_uint32, vp, vp, vp, vp, u64, vp, C.POINTER(LrcVoxgridCounts)],
         "lrc_voxgrid_finalize_dev": [vp, C.c_uint32, vp, vp, vp, vp, u64, vp, vp, vp],
         "lrc_voxgrid_export_bits": [vp, vp],
+        "lrc_frameobj_create": [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(vp)],
+        "lrc_frameobj_destroy": [vp],
+        "lrc_frameobj_get_info": [vp, C.POINTER(LrcFrameobjInfo)],
+        "lrc_frameobj_objects": [vp, vp, vp, vp, vp, vp],
+        "lrc_frameobj_reset": [vp, vp],
+        "lrc_frameobj_accumulate_dev": [vp, vp, u64, u64, vp, vp, vp, u64, vp],
+        "lrc_frameobj_export": [vp, vp, vp, vp, vp, vp],
+        "lrc_frameobj_export_dev": [vp, vp, vp, vp, vp, vp, vp],
         "lrc_nn_create": [vp, vp, u64, dbl, C.POINTER(vp)],
         "lrc_nn_destroy": [vp],
         "lrc_nn_query": [vp, vp, u64, vp, vp],

@@ -463,6 +463,29 @@ class RaycastEngineHIP(RaycastEngineBase):
         finally:
             grid.close()
 
+    # ---- per-frame object annotations (lidarcast.frameobj) ----------------------------------------
+    def frame_objects(self, intrinsics, poses, mesh, max_range=None, chunk_poses=None):
+        """Scan ``poses`` (P, 4, 4) with a multi-line grid sensor and reduce every frame's returned rays per object
+        (distinct sem | ins << 16 of the mesh's triangle labels) in HBM: a lidarcast.FrameObjectsResult with P frames
+        (returns, seen triangles and area, visible box in the sensor frame, and the static object table)."""
+        from lidarcast import FrameObjects, scan_frame_objects
+        if hasattr(intrinsics, "swing_amplitude") or not hasattr(intrinsics, "horizontal_res"):
+            raise NotImplementedError("frame annotations cover multi-line grid sensors only; the dual-axis sensor and "
+                                      "moving-sensor sweeps are outside their scope")
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        v, f, sem, ins = mesh_arrays(mesh)
+        fo = FrameObjects(self.ctx, v, f, sem, ins, num_frames=max(1, len(poses)))
+        try:
+            scan_frame_objects(self.scene_for(mesh), fo, poses, self._direction_table(intrinsics),
+                               intrinsics.max_range if max_range is None else float(max_range), chunk_poses=chunk_poses)
+            r = fo.export()
+        finally:
+            fo.close()
+        if len(poses) == 0:                 # the one frame the object needs to exist is not a scanned one
+            for name in ("returns", "seen_tris", "seen_q", "vmin", "vmax"):
+                setattr(r, name, getattr(r, name)[:0])
+        return r
+
     def scan_frames_lidars(self, lidars, mesh, want=("point3", "sem", "ins")):
         """The bit-exact default path of the dual-axis sensor, straight to frames: every pose's rays come from the host
         generator (``all_rays_and_mask``: the reference's arithmetic and RNG draws, written into a page-locked buffer),

@@ -235,6 +235,59 @@ class S3DISSimulator:
             json.dump(summary, f, indent=2)
         return summary
 
+    def export_frame_annotations(self, waypoints: List[Waypoint], output_dir, min_points: int = 10,
+                                 semantic_mapping: Optional[Dict[str, int]] = None) -> Dict[str, Any]:
+        """Per-frame detection annotations of the scan of ``waypoints`` over the loaded room,
+        written to ``output_dir``/<scene>_frame_annotations.json: the object table (key, sem, class name where known,
+        ins, tri_count, area in m^2, world AABB) and, per frame, the pose and every listed object with ``num_points``,
+        ``seen_ratio``, ``box7`` (the amodal box in the sensor frame: cx, cy, cz, dx, dy, dz, heading) and the visible
+        box ``visible_min`` / ``visible_max``.  An object is listed when it has at least ``min_points`` returns in the
+        frame, its class is in ``semantic_mapping`` (class name -> semantic id, default S3DIS_SEMANTIC_MAPPING: the
+        classes of export_detection_annotations) and its instance id is not 0.  Scans again on the GPU; run_simulation
+        is not involved.  Returns the dict."""
+        if self.scene is None:
+            raise ValueError("Scene not loaded. Call load_scene() first.")
+        if self.config.get("motion") is not None:
+            raise NotImplementedError("frame annotations of moving-sensor sweeps are outside their scope")
+        from lidar_net_bbox_visualizer import S3DIS_SEMANTIC_MAPPING
+        from lidarcast.synth import S3DIS_CLASSES
+        mapping = S3DIS_SEMANTIC_MAPPING if semantic_mapping is None else semantic_mapping
+        name_of = {int(s): n for n, s in mapping.items()}
+        poses = np.ascontiguousarray(poses_from_waypoints(waypoints), dtype=np.float64).reshape(-1, 4, 4)
+        r = self.raycast_engine.frame_objects(self.lidar_config, poses, self.scene.room_mesh)
+        boxes = r.boxes7(poses)
+        ratio = r.seen_ratio
+        sem, ins, area = r.sem, r.ins, r.total_area
+        objects = []
+        for k in range(r.num_objects):
+            s = int(sem[k])
+            cls = name_of.get(s, S3DIS_CLASSES[s] if s < len(S3DIS_CLASSES) else None)
+            objects.append({"index": k, "key": int(r.key[k]), "sem": s, "class": cls, "ins": int(ins[k]),
+                            "tri_count": int(r.tri_count[k]), "area_m2": float(area[k]),
+                            "world_min": [float(x) for x in r.wmin[k]], "world_max": [float(x) for x in r.wmax[k]]})
+        listed = [k for k in range(r.num_objects) if int(sem[k]) in name_of and int(ins[k]) != 0]
+        frames = []
+        for f in range(len(poses)):
+            objs = []
+            for k in listed:
+                n = int(r.returns[f, k])
+                if n < int(min_points):
+                    continue
+                objs.append({"object": k, "class": name_of[int(sem[k])], "sem": int(sem[k]), "ins": int(ins[k]),
+                             "num_points": n, "seen_ratio": float(ratio[f, k]),
+                             "box7": [float(x) for x in boxes[f, k]],
+                             "visible_min": [float(x) for x in r.vmin[f, k]],
+                             "visible_max": [float(x) for x in r.vmax[f, k]]})
+            frames.append({"frame": f, "pose": [[float(x) for x in row] for row in poses[f]], "objects": objs})
+        name = self.scene.scene_name
+        summary = {"scene_name": name, "num_frames": len(poses), "min_points": int(min_points),
+                   "rejected_rays": int(r.rejected_rays), "objects": objects, "frames": frames}
+        out = Path(output_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        with open(out / f"{name}_frame_annotations.json", "w") as fh:
+            json.dump(summary, fh, indent=2)
+        return summary
+
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
         rank (one process per GPU, backend "nccl" = RCCL), or with an explicit ``process_group``, the waypoints are
