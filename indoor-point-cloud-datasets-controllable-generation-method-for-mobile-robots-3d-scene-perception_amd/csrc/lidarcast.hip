@@ -26,136 +26,41 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lidarcast.h"
+#include "lrc_internal.h"
 #include "lrc_bvh.h"
-#include "lrc_bvh_device.h"
 #include "lrc_qnodes.h"
 #include "lrc_device.h"
 
 using namespace lrcdev;
 
 // ------------------------------------------------------------------------------------------------
-// error plumbing
+// error plumbing (declared in lrc_internal.h)
 // ------------------------------------------------------------------------------------------------
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
 
-#define LRC_HIP(call)                                                                      \
-    do {                                                                                   \
-        hipError_t e__ = (call);                                                           \
-        if (e__ != hipSuccess) {                                                           \
-            (void)hipGetLastError();                                                       \
-            return fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,            \
-                        std::string(#call) + ": " + hipGetErrorString(e__));               \
-        }                                                                                  \
-    } while (0)
+// ------------------------------------------------------------------------------------------------
+// argument checks shared with other units (declared in lrc_internal.h)
+// ------------------------------------------------------------------------------------------------
+// The mesh checks of lrc_coverage_create and lrc_frameobj_create; `who` is the entry point's name, the message's prefix.
+int check_mesh(const char* who, const double* verts3, uint64_t V, const int32_t* tris3, uint64_t T) {
+    for (uint64_t i = 0; i < 3 * V; ++i)
+        if (!__builtin_isfinite(verts3[i])) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": non-finite vertex");
+    for (uint64_t i = 0; i < 3 * T; ++i)
+        if (tris3[i] < 0 || (uint64_t)tris3[i] >= V)
+            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": triangle index out of range");
+    return LRC_OK;
+}
 
-constexpr int kBlock = 256;          // compaction kernels
-#ifndef LRC_TRACE_BLOCK
-#define LRC_TRACE_BLOCK 64
-#endif
-constexpr int kTBlock = LRC_TRACE_BLOCK;   // trace kernel workgroup (rays per tile)
-
-}  // namespace
-
-enum PoolSlot { kPoolRays = 0, kPoolT, kPoolPrim, kPoolNormal, kPoolPoint, kPoolSem, kPoolIns, kPoolInc, kPoolInten,
-                kPoolPoses, kPoolDirs, kPoolOffs, kPoolCen, kPoolNoise,
-                // *_compact entry points: scan angles in, per-wave keep counts, compacted frame arrays out
-                kPoolAngles, kPoolKeep, kPoolTile, kPoolCounts, kPoolOutPoint, kPoolOutSem, kPoolOutIns, kPoolOutInc,
-                kPoolOutIdx, kPoolOutXyzl, kPoolOutRange, kPoolStats, kPoolFrameStats, kPoolSlots };
-
-// triangle records fetched per leaf round trip by the product kernels.  With edge records the pair fits 64 VGPRs, i.e. 8
-// waves per SIMD: -2...-4 % trace time on all benchmark scenes against one record per round trip.
-constexpr int kLeafW = 2;
 #ifndef LRC_REBUILD_R
 #define LRC_REBUILD_R 2      // tiles (of 64 entries) one wave of the cloud rebuild handles (1, 2, 4, 8 measured equal)
 #endif
-
-struct lrc_ctx {
-    int device = 0;
-    // staging buffers of the host-pointer entry points, grown on demand and reused (a per-waypoint caller
-    // such as the reference loop, s3dis_simulator.py:254-264, would otherwise pay hipMalloc/hipFree per pose)
-    void* pool[kPoolSlots] = {};
-    size_t pool_cap[kPoolSlots] = {};
-    // compaction scratch (grown on demand, reused): per-tile counts and exclusive offsets.  Two sets: the
-    // cloud rebuild of the multi-GPU path runs on its own stream next to the compaction of the local scan.
-    struct TileScratch {
-        uint32_t* d_tile_off = nullptr;     // offset of a tile inside its super tile (1024 tiles)
-        uint32_t* d_tile_cnt = nullptr;
-        uint32_t* d_super_total = nullptr;  // kept entries per super tile
-        uint64_t* d_super_base = nullptr;   // exclusive prefix of d_super_total (+ grand total)
-        uint64_t tile_cap = 0;
-        double* d_dirs_soa = nullptr;       // direction table transposed to x[N] y[N] z[N] (cloud rebuild only)
-        uint64_t dirs_cap = 0;
-    };
-    TileScratch cloud_scratch;
-    // lrc_compact_dev: one scratch set per caller stream (a caller that keeps two scans in flight on two streams compacts on
-    // both); a set handed on to another stream is first ordered behind its last use (scratch_for)
-    static constexpr int kCompactSets = 4;
-    TileScratch compact_scratch[kCompactSets];
-    hipStream_t compact_stream[kCompactSets] = {};
-    hipEvent_t compact_done[kCompactSets] = {};
-    bool compact_used[kCompactSets] = {};
-    int compact_next = 0;
-    // Dispatch chaining of trace launches ("the launch tail"): the LAST workgroup of every trace launch writes the
-    // launch's sequence number to this signal word at its first instruction; a trace launch on ANOTHER stream than the
-    // previous one is held behind hipStreamWaitValue64(word >= previous sequence number), i.e. it starts the moment the
-    // previous launch has handed out its last workgroup -- its waves fill the slots the previous launch's tail leaves empty,
-    // and launches that a caller keeps in flight on two streams run staggered instead of falling into phase.
-    uint64_t* chain_word = nullptr;     // hipMallocSignalMemory; NULL: not supported here, launches are never chained
-    uint64_t chain_seq = 0;             // sequence number of the last chained trace launch
-    hipStream_t chain_stream = nullptr; // ... and the stream it went to
-    bool chain_enabled = false;         // lrc_ctx_set_launch_chaining (opt-in: measured equal to what the dispatcher does itself)
-    // *_compact entry points: kernels on one stream, the transfers of finished pose chunks on another
-    hipStream_t s_compute = nullptr, s_copy = nullptr, s_stats = nullptr;
-    hipEvent_t ev_chunk[8] = {}, ev_compact[8] = {};
-    uint64_t* h_counts = nullptr;       // page-locked landing area of the per-pose counts and statistics (async copies
-    uint64_t h_counts_cap = 0;          // need one): counts (P u64) | 4 x P doubles of per-pose statistics
-    lrc::DeviceArena build_arena;       // scratch of the device scene build, reused from scene to scene
-    float* stat_scratch = nullptr;      // chunk sums of lrc_cloud_range_stats_dev (calls of one context must not overlap
-    uint64_t stat_scratch_cap = 0;      // on different streams: handles are not thread-safe)
-};
-
-struct lrc_table {            // a sensor's direction table resident in HBM (lrc_table_create)
-    lrc_ctx* ctx = nullptr;
-    double* d_dirs3 = nullptr;
-    uint64_t n = 0;
-    double* d_fire = nullptr;   // optional (lrc_table_set_fire): per ray the fraction of the sweep at which it fires
-};
-
-struct lrc_scene {
-    lrc_ctx* ctx = nullptr;
-    void* slab = nullptr;             // device-built scenes: ONE allocation holds every array below except d_slot_sphere / *4
-    float4* d_nodes = nullptr;
-    float4* d_tris = nullptr;
-    uint32_t* d_slot_prim = nullptr;
-    uint32_t* d_slot_label = nullptr;
-    float* d_slot_box = nullptr;      // per leaf slot the triangle's exact vertex box (lo xyz, hi xyz)
-    float4* d_prim_plane = nullptr;   // per caller's triangle row: (v0, label bits), (Ng, 0): lrc_cloud_from_prims_dev
-    std::mutex plane_mutex;           // ... built on first use, published complete (ensure_prim_plane)
-    float4* d_slot_sphere = nullptr;  // per leaf slot: centre of the triangle's box + bounding radius (sector_kernel)
-    // quantised node images of the SAME tree ("32-byte nodes"): child boxes on a 15-bit grid
-    // per axis, rounded outward (margin 1/16 cell).  d_nodes_q: 32 B per node for the per-lane fetches; d_nodes_n: the same
-    // boxes as normalised float32 (64 B per node) for the scalar fetches.  NULL when the grid does not fit the scene.
-    uint4* d_nodes_q = nullptr;
-    float4* d_nodes_n = nullptr;
-    // the same tree collapsed to four children per node (every second level removed), on the same grid:
-    // d_nodes_q4 64 B per node (per child lo|hi<<16 x, y, z + reference), d_nodes_n4 128 B (per child lo, hi, ref, pad)
-    uint4* d_nodes_q4 = nullptr;
-    float4* d_nodes_n4 = nullptr;
-    uint64_t num_nodes4 = 0;
-    float qbase[3] = {0, 0, 0}, qW[3] = {1, 1, 1}, qinvW[3] = {1, 1, 1};
-    const lrc_grid* cur_grid = nullptr;   // set around a grid scan (launch_trace gen == 3)
-    lrc_scene_info info{};
-    lrc_scan_options opts{};          // sticky opt-in options (lrc_scene_set_options)
-    uint64_t launches = 0, rays = 0;
-};
 
 // ------------------------------------------------------------------------------------------------
 // device code
@@ -1687,7 +1592,6 @@ extern "C" {
 
 // shared with the other translation units of the library (not part of the public ABI)
 int lrc_internal_fail(int code, const char* msg) { return fail(code, msg ? msg : ""); }
-int lrc_internal_ctx_device(const lrc_ctx* ctx) { return ctx ? ctx->device : 0; }
 // test hook (tests/test_tile_mapping.py): the ray of every (tile, lane) of a pose of tpp tiles for a line width hint (in rays)
 // and the line width in tiles the pipeline would use for it -- the host compilation of the kernel's mapping (lrc_device.h)
 uint32_t lrc_internal_tile_map(uint64_t line_width, uint32_t tpp, uint32_t* out_ray) {
@@ -1827,9 +1731,9 @@ int lrc_scene_destroy(lrc_scene* s) {
     return LRC_OK;
 }
 
-namespace {
+}  // extern "C"
 
-int env_int(const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; }
+namespace {
 
 void build_options_from_env(lrc::BuildOptions& opt) {
     opt.max_leaf = env_int("LRC_MAX_LEAF", opt.max_leaf);
@@ -1859,14 +1763,13 @@ int scene_create_device(lrc_ctx* ctx, const float* verts3, uint64_t V, const uin
     if (!s) return fail(LRC_ERR_OOM, "lrc_scene_create: out of host memory");
     s->ctx = ctx;
     lrc::DeviceScene d;
-    std::string err;
     lrc::BuildOptions opt;
     build_options_from_env(opt);
     const int rc = lrc::build_bvh_device(&ctx->build_arena, verts3, V, tris3, T, tri_sem, tri_ins, on_device, opt,
-                                         qnodes_mode(), &d, &err);
+                                         qnodes_mode(), &d);
     if (rc != lrc::kDevBuildOk) {
         delete s;
-        return rc < 0 ? fail(rc, err) : rc;
+        return rc;
     }
     s->slab = d.slab;
     s->d_nodes = (float4*)d.nodes;
@@ -1998,6 +1901,8 @@ bool want_device_build() {
 }
 
 }  // namespace
+
+extern "C" {
 
 int lrc_scene_create(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T,
                      const uint16_t* tri_sem, const uint16_t* tri_ins, lrc_scene** out_scene) {
@@ -2462,25 +2367,10 @@ int lrc_scan_grid_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const d
     return rc;
 }
 
+}  // extern "C"
+
 // ---- host-pointer convenience wrappers ---------------------------------------------------------
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    bool pooled = false;
-    ~DevBuf() { if (p && !pooled) (void)hipFree(p); }
-    // buffer of the context's staging pool (kept for the next call)
-    int get(lrc_ctx* ctx, int slot, size_t bytes) {
-        if (ctx->pool_cap[slot] < bytes) {
-            if (ctx->pool[slot]) { (void)hipFree(ctx->pool[slot]); ctx->pool[slot] = nullptr; ctx->pool_cap[slot] = 0; }
-            const size_t cap = bytes + bytes / 8;
-            LRC_HIP(hipMalloc(&ctx->pool[slot], cap));
-            ctx->pool_cap[slot] = cap;
-        }
-        p = ctx->pool[slot];
-        pooled = true;
-        return LRC_OK;
-    }
-};
 struct HitsStage {
     DevBuf t, prim, normal3, point3, sem, ins, inc, inten;
     lrc_hits d{};
@@ -2530,6 +2420,8 @@ struct NoiseStage {
     ~NoiseStage() { if (s) s->opts.range_noise = host; }
 };
 }  // namespace
+
+extern "C" {
 
 int lrc_cast(lrc_scene* s, const float* rays6, uint64_t n, const double* center3, double max_range,
              const lrc_hits* out) {
@@ -2854,6 +2746,8 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
     return LRC_OK;
 }
 
+}  // extern "C"
+
 namespace {
 // the compaction input of the records in set `set`
 lrc_compact_io pipe_io(const lrc_pipe* pp, int set) {
@@ -2877,6 +2771,8 @@ int wait_for_readers(lrc_pipe* pp, int set, hipStream_t T) {
     return LRC_OK;
 }
 }  // namespace
+
+extern "C" {
 
 // test hook (tests/test_pipe_two_line_gpu.py): the line width, in tiles of 64 rays, the trace launch of the pipeline's last
 // lrc_pipe_submit ran with (0: 1-D tiles) -- the regrouping changes no byte, so no output can tell whether it happened
@@ -3005,6 +2901,8 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     return LRC_OK;
 }
 
+}  // extern "C"
+
 // ---- the pipeline on N ranks: the trace writes triangle ids + keep counts into the caller's send slab, the assembly of an
 // EARLIER scan of all ranks (its gathered slabs) rides in the leading workgroups of this trace launch ----------------------
 namespace {
@@ -3077,6 +2975,8 @@ int prepare_gathered(lrc_pipe* pp, const lrc_gathered* g, RebuildParams* q, lrc_
     return LRC_OK;
 }
 }  // namespace
+
+extern "C" {
 
 int lrc_pipe_submit_sharded(lrc_pipe* pp, const double* d_poses16, uint64_t P, const double* d_dirs3, double max_range,
                             uint32_t* d_send_prim, uint32_t* d_send_tile_count, const lrc_gathered* assemble, void* stream,
@@ -3475,6 +3375,8 @@ int lrc_compact(lrc_ctx* ctx, uint64_t nseg, uint64_t seg_len, const lrc_compact
 }
 
 
+}  // extern "C"
+
 // ---- scan straight to the reference's variable-length frames ----------------------------------------------------
 namespace {
 // The *_compact entry points enqueue their input copies (on the context's compute stream, which consumes them) before
@@ -3754,6 +3656,8 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
     return LRC_OK;
 }
 }  // namespace
+
+extern "C" {
 
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr) {
     if (!ctx || !out_ptr) return fail(LRC_ERR_INVALID_ARG, "lrc_host_alloc: NULL argument");

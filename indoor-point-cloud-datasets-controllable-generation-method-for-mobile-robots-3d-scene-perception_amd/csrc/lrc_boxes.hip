@@ -28,26 +28,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lidarcast.h"
-
-extern "C" int lrc_internal_fail(int code, const char* msg);     // lidarcast.hip: sets lrc_last_error()
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
+#include "lrc_internal.h"
 
 namespace {
 
-#define BX_HIP(call)                                                                            \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
-
 constexpr uint32_t kIgnored = 0xFFFFFFFFu;
 constexpr int kMaxClasses = 64;
-constexpr int kBlock = 256;
 
 struct ClassList {
     uint32_t n;
@@ -427,7 +413,7 @@ int lrc_instance_boxes_dev(lrc_ctx* ctx, const float* d_xyzl, uint64_t num_rows,
     ClassList cl;
     if (int rc = check_params(num_rows, class_ids, num_classes, k, &cl)) return rc;
     if (num_rows == 0) return LRC_OK;
-    BX_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC_HIP(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     const uint64_t K = num_rows;
     const float4* xyzl = reinterpret_cast<const float4*>(d_xyzl);
@@ -438,7 +424,7 @@ int lrc_instance_boxes_dev(lrc_ctx* ctx, const float* d_xyzl, uint64_t num_rows,
     {
         void* p;
         const size_t sz = align256(K * 4);
-        BX_HIP(arena.get(6 * sz + 256, &p));
+        LRC_HIP(arena.get(6 * sz + 256, &p));
         char* c = (char*)p;
         keys_a = (uint32_t*)c; keys_b = (uint32_t*)(c + sz); rows_a = (uint32_t*)(c + 2 * sz);
         rows_b = (uint32_t*)(c + 3 * sz); ukeys = (uint32_t*)(c + 4 * sz); counts = (uint32_t*)(c + 5 * sz);
@@ -446,23 +432,23 @@ int lrc_instance_boxes_dev(lrc_ctx* ctx, const float* d_xyzl, uint64_t num_rows,
     }
     const uint32_t nblk = (uint32_t)((K + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(box_key_kernel, dim3(nblk), dim3(kBlock), 0, st, xyzl, K, cl, keys_a, rows_a, d_out_avg, d_out_keep);
-    BX_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     const int end_bit1 = 16 + bit_width(num_classes);        // the ignored key's bits above all class indices
     size_t tmp1 = 0, tmp_rle = 0;
-    BX_HIP(rocprim::radix_sort_pairs(nullptr, tmp1, keys_a, keys_b, rows_a, rows_b, (size_t)K, 0, end_bit1, st));
-    BX_HIP(rocprim::run_length_encode(nullptr, tmp_rle, keys_b, (unsigned int)K, ukeys, counts, nruns, st));
+    LRC_HIP(rocprim::radix_sort_pairs(nullptr, tmp1, keys_a, keys_b, rows_a, rows_b, (size_t)K, 0, end_bit1, st));
+    LRC_HIP(rocprim::run_length_encode(nullptr, tmp_rle, keys_b, (unsigned int)K, ukeys, counts, nruns, st));
     void* tmp;
-    BX_HIP(arena.get(std::max(tmp1, tmp_rle), &tmp));
-    BX_HIP(rocprim::radix_sort_pairs(tmp, tmp1, keys_a, keys_b, rows_a, rows_b, (size_t)K, 0, end_bit1, st));
-    BX_HIP(rocprim::run_length_encode(tmp, tmp_rle, keys_b, (unsigned int)K, ukeys, counts, nruns, st));
+    LRC_HIP(arena.get(std::max(tmp1, tmp_rle), &tmp));
+    LRC_HIP(rocprim::radix_sort_pairs(tmp, tmp1, keys_a, keys_b, rows_a, rows_b, (size_t)K, 0, end_bit1, st));
+    LRC_HIP(rocprim::run_length_encode(tmp, tmp_rle, keys_b, (unsigned int)K, ukeys, counts, nruns, st));
     uint32_t runs = 0;
-    BX_HIP(hipMemcpyAsync(&runs, nruns, 4, hipMemcpyDeviceToHost, st));
-    BX_HIP(hipStreamSynchronize(st));
+    LRC_HIP(hipMemcpyAsync(&runs, nruns, 4, hipMemcpyDeviceToHost, st));
+    LRC_HIP(hipStreamSynchronize(st));
     std::vector<uint32_t> h_ukeys(runs), h_counts(runs);
     if (runs) {
-        BX_HIP(hipMemcpyAsync(h_ukeys.data(), ukeys, (size_t)runs * 4, hipMemcpyDeviceToHost, st));
-        BX_HIP(hipMemcpyAsync(h_counts.data(), counts, (size_t)runs * 4, hipMemcpyDeviceToHost, st));
-        BX_HIP(hipStreamSynchronize(st));
+        LRC_HIP(hipMemcpyAsync(h_ukeys.data(), ukeys, (size_t)runs * 4, hipMemcpyDeviceToHost, st));
+        LRC_HIP(hipMemcpyAsync(h_counts.data(), counts, (size_t)runs * 4, hipMemcpyDeviceToHost, st));
+        LRC_HIP(hipStreamSynchronize(st));
     }
     const uint32_t S = (runs && h_ukeys[runs - 1] == kIgnored) ? runs - 1 : runs;
     if (S == 0) return LRC_OK;
@@ -491,41 +477,41 @@ int lrc_instance_boxes_dev(lrc_ctx* ctx, const float* d_xyzl, uint64_t num_rows,
                      o_table = o_avg + align256(M * 8), o_starts = o_table + align256((T + 1) * 4),
                      total = o_starts + align256((T + 1) * 4);
         void* p;
-        BX_HIP(arena.get(total, &p));
+        LRC_HIP(arena.get(total, &p));
         char* c = (char*)p;
         seg_start = (uint32_t*)c; seg_count = (uint32_t*)(c + o_count); seg_table = (uint64_t*)(c + o_tab);
         grids = (SegGrid*)(c + o_grid); boxes = (lrc_box*)(c + o_box); key_a = (uint64_t*)(c + o_ka);
         key_b = (uint64_t*)(c + o_kb); pts = (float4*)(c + o_pts); avg = (double*)(c + o_avg); table = (uint32_t*)(c + o_table);
         starts = (uint32_t*)(c + o_starts);
     }
-    BX_HIP(hipMemcpyAsync(seg_start, h_start.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
-    BX_HIP(hipMemcpyAsync(seg_count, h_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
-    BX_HIP(hipMemcpyAsync(seg_table, h_table.data(), (size_t)S * 8, hipMemcpyHostToDevice, st));
-    BX_HIP(hipMemsetAsync(table, 0, (T + 1) * 4, st));
+    LRC_HIP(hipMemcpyAsync(seg_start, h_start.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
+    LRC_HIP(hipMemcpyAsync(seg_count, h_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
+    LRC_HIP(hipMemcpyAsync(seg_table, h_table.data(), (size_t)S * 8, hipMemcpyHostToDevice, st));
+    LRC_HIP(hipMemsetAsync(table, 0, (T + 1) * 4, st));
     hipLaunchKernelGGL(box_grid_kernel, dim3(S), dim3(kBlock), 0, st, xyzl, rows_b, seg_start, seg_count, seg_table,
                        min_points, k, cell_size, grids, key_a, rows_a);
-    BX_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     const int end_bit2 = 32 + bit_width(S);
     size_t tmp2 = 0, tmp_scan = 0;
     // values: positions in instance order (rows_a, written by box_grid_kernel) -> keys_a (free since the first sort)
-    BX_HIP(rocprim::radix_sort_pairs(nullptr, tmp2, key_a, key_b, rows_a, keys_a, (size_t)M, 0, end_bit2, st));
-    BX_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, table, starts, 0u, (size_t)(T + 1), rocprim::plus<uint32_t>(), st));
+    LRC_HIP(rocprim::radix_sort_pairs(nullptr, tmp2, key_a, key_b, rows_a, keys_a, (size_t)M, 0, end_bit2, st));
+    LRC_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, table, starts, 0u, (size_t)(T + 1), rocprim::plus<uint32_t>(), st));
     void* tmpb;
-    BX_HIP(arena.get(std::max(tmp2, tmp_scan), &tmpb));
-    BX_HIP(rocprim::radix_sort_pairs(tmpb, tmp2, key_a, key_b, rows_a, keys_a, (size_t)M, 0, end_bit2, st));
+    LRC_HIP(arena.get(std::max(tmp2, tmp_scan), &tmpb));
+    LRC_HIP(rocprim::radix_sort_pairs(tmpb, tmp2, key_a, key_b, rows_a, keys_a, (size_t)M, 0, end_bit2, st));
     const uint32_t mblk = (uint32_t)((M + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(box_count_kernel, dim3(mblk), dim3(kBlock), 0, st, xyzl, key_b, keys_a, rows_b, M, grids, table, pts);
-    BX_HIP(hipGetLastError());
-    BX_HIP(rocprim::exclusive_scan(tmpb, tmp_scan, table, starts, 0u, (size_t)(T + 1), rocprim::plus<uint32_t>(), st));
+    LRC_HIP(hipGetLastError());
+    LRC_HIP(rocprim::exclusive_scan(tmpb, tmp_scan, table, starts, 0u, (size_t)(T + 1), rocprim::plus<uint32_t>(), st));
 
     // ---- 3. neighbours, 4. statistics and boxes ----
-    BX_HIP(dispatch_knn(M, st, pts, key_b, grids, starts, (int)k, avg));
+    LRC_HIP(dispatch_knn(M, st, pts, key_b, grids, starts, (int)k, avg));
     hipLaunchKernelGGL(box_stats_kernel, dim3(S), dim3(kBlock), 0, st, xyzl, rows_b, avg, seg_start, seg_count, grids, min_points,
                        std_ratio, boxes, d_out_avg, d_out_keep);
-    BX_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     std::vector<lrc_box> h_boxes(S);
-    BX_HIP(hipMemcpyAsync(h_boxes.data(), boxes, (size_t)S * sizeof(lrc_box), hipMemcpyDeviceToHost, st));
-    BX_HIP(hipStreamSynchronize(st));
+    LRC_HIP(hipMemcpyAsync(h_boxes.data(), boxes, (size_t)S * sizeof(lrc_box), hipMemcpyDeviceToHost, st));
+    LRC_HIP(hipStreamSynchronize(st));
     uint64_t nb = 0;
     for (uint32_t s = 0; s < S; ++s) {
         if (h_counts[s] < min_points) continue;
@@ -562,7 +548,7 @@ int lrc_instance_boxes(lrc_ctx* ctx, const float* points3, const uint16_t* sem, 
         const uint32_t lab = (uint32_t)sem[i] | ((uint32_t)ins[i] << 16);
         std::memcpy(&rows[4 * i + 3], &lab, 4);
     }
-    BX_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC_HIP(hipSetDevice(ctx->device));
     float* d_rows = nullptr;
     double* d_avg = nullptr;
     uint8_t* d_keep = nullptr;

@@ -43,7 +43,7 @@ struct DeviceScene {               // one allocation (`slab`), the arrays point 
     double ms_upload = 0, ms_hierarchy = 0, ms_emit = 0;
 };
 
-enum { kDevBuildOk = 0, kDevBuildUnsupported = 1 };    // negative: an LRC_ERR_* code, text in *err
+enum { kDevBuildOk = 0, kDevBuildUnsupported = 1 };    // negative: an LRC_ERR_* code, text set by fail()
 
 // verts3 / tris3 / labels: HOST pointers when on_device is false (they are uploaded), device pointers otherwise.
 // qmode: 0 = float32 nodes only, 1 = quantised images when the grid is fine enough, 2 = whenever the grid fits.
@@ -51,6 +51,6 @@ enum { kDevBuildOk = 0, kDevBuildUnsupported = 1 };    // negative: an LRC_ERR_*
 // (a mesh of <= max_leaf triangles).
 int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T,
                      const uint16_t* tri_sem, const uint16_t* tri_ins, bool on_device, const BuildOptions& opt,
-                     int qmode, DeviceScene* out, std::string* err);
+                     int qmode, DeviceScene* out);
 
 }  // namespace lrc

@@ -30,9 +30,11 @@
 #include <cmath>
 #include <vector>
 
-#include "../../include/lidarcast.h"
-#include "lrc_bvh_device.h"
+#include "lrc_internal.h"
 #include "lrc_qnodes.h"
+
+#undef LRC_HIP_WHERE
+#define LRC_HIP_WHERE "device BVH build: "      // what LRC_HIP puts in front of the call text in this unit
 
 namespace lrc {
 namespace {
@@ -1494,16 +1496,6 @@ struct Carver {                      // sub-allocation of the arena, 256-byte al
     }
 };
 
-#define DB_HIP(call)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e__ = (call);                                                                         \
-        if (e__ != hipSuccess) {                                                                         \
-            (void)hipGetLastError();                                                                     \
-            if (err) *err = std::string("device BVH build: ") + #call + ": " + hipGetErrorString(e__);   \
-            return e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP;                               \
-        }                                                                                                \
-    } while (0)
-
 inline int ceil_log2_u64(uint64_t x) { int k = 0; uint64_t p = 1; while (p < x) { p <<= 1; ++k; } return k; }
 
 }  // namespace
@@ -1518,7 +1510,7 @@ void arena_release(DeviceArena* a) {
 
 int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T64,
                      const uint16_t* tri_sem, const uint16_t* tri_ins, bool on_device, const BuildOptions& opt,
-                     int qmode, DeviceScene* out, std::string* err) {
+                     int qmode, DeviceScene* out) {
     *out = DeviceScene();
     const int max_leaf = std::min(std::max(opt.max_leaf, 1), kMaxLeaf);
     if (T64 <= (uint64_t)max_leaf || T64 >= (1ull << 28)) return kDevBuildUnsupported;
@@ -1547,10 +1539,10 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
     }
     if (arena->cap < need) {
         if (arena->dev) { (void)hipFree(arena->dev); arena->dev = nullptr; arena->cap = 0; }
-        DB_HIP(hipMalloc(&arena->dev, need + need / 8));
+        LRC_HIP(hipMalloc(&arena->dev, need + need / 8));
         arena->cap = need + need / 8;
     }
-    if (!arena->pinned) DB_HIP(hipHostMalloc(&arena->pinned, 4096, hipHostMallocDefault));
+    if (!arena->pinned) LRC_HIP(hipHostMalloc(&arena->pinned, 4096, hipHostMallocDefault));
     Carver c{(char*)arena->dev};
     const float* d_verts = verts3;
     const uint32_t* d_tris = tris3;
@@ -1561,10 +1553,10 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
         uint32_t* dt = c.take<uint32_t>(3 * (size_t)T);
         uint16_t* ds = c.take<uint16_t>(T);
         uint16_t* di = c.take<uint16_t>(T);
-        DB_HIP(hipMemcpyAsync(dv, verts3, 3 * V * 4, hipMemcpyHostToDevice, st));
-        DB_HIP(hipMemcpyAsync(dt, tris3, 3 * (size_t)T * 4, hipMemcpyHostToDevice, st));
-        if (tri_sem) DB_HIP(hipMemcpyAsync(ds, tri_sem, (size_t)T * 2, hipMemcpyHostToDevice, st));
-        if (tri_ins) DB_HIP(hipMemcpyAsync(di, tri_ins, (size_t)T * 2, hipMemcpyHostToDevice, st));
+        LRC_HIP(hipMemcpyAsync(dv, verts3, 3 * V * 4, hipMemcpyHostToDevice, st));
+        LRC_HIP(hipMemcpyAsync(dt, tris3, 3 * (size_t)T * 4, hipMemcpyHostToDevice, st));
+        if (tri_sem) LRC_HIP(hipMemcpyAsync(ds, tri_sem, (size_t)T * 2, hipMemcpyHostToDevice, st));
+        if (tri_ins) LRC_HIP(hipMemcpyAsync(di, tri_ins, (size_t)T * 2, hipMemcpyHostToDevice, st));
         d_verts = dv; d_tris = dt; d_sem = tri_sem ? ds : nullptr; d_ins = tri_ins ? di : nullptr;
     }
     PrimRec* bufA = c.take<PrimRec>(T);
@@ -1600,7 +1592,7 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
         (void)rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)T, 0, 64, st);
         if (arena->sort_cap < tmp) {
             if (arena->sort_tmp) { (void)hipFree(arena->sort_tmp); arena->sort_tmp = nullptr; arena->sort_cap = 0; }
-            DB_HIP(hipMalloc(&arena->sort_tmp, tmp + 256));
+            LRC_HIP(hipMalloc(&arena->sort_tmp, tmp + 256));
             arena->sort_cap = tmp + 256;
         }
     }
@@ -1617,12 +1609,12 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
                        counters);
     struct Landing { LevelCounters b_lc[2]; LevelCounters lc; LevelCounters lc_pair[2]; int bounds[8]; uint32_t median[64]; };
     Landing* land = (Landing*)arena->pinned;
-    DB_HIP(hipMemcpyAsync(land->b_lc, counters - 1, 2 * sizeof(LevelCounters), hipMemcpyDeviceToHost, st));
-    DB_HIP(hipStreamSynchronize(st));
+    LRC_HIP(hipMemcpyAsync(land->b_lc, counters - 1, 2 * sizeof(LevelCounters), hipMemcpyDeviceToHost, st));
+    LRC_HIP(hipStreamSynchronize(st));
     std::memcpy(land->bounds, &land->b_lc[0], 32);
     land->lc = land->b_lc[1];
-    if (land->lc.error & 1u) { if (err) *err = "lrc_scene_create: triangle index out of range"; return LRC_ERR_INVALID_ARG; }
-    if (land->lc.error & 2u) { if (err) *err = "lrc_scene_create: vertex coordinate is not finite or exceeds 1e6"; return LRC_ERR_INVALID_ARG; }
+    if (land->lc.error & 1u) return fail(LRC_ERR_INVALID_ARG, "lrc_scene_create: triangle index out of range");
+    if (land->lc.error & 2u) return fail(LRC_ERR_INVALID_ARG, "lrc_scene_create: vertex coordinate is not finite or exceeds 1e6");
     auto host_dec = [](int i) { int u = i ^ ((i >> 31) & 0x7FFFFFFF); float f; std::memcpy(&f, &u, 4); return f; };
     for (int k = 0; k < 3; ++k) { out->bounds_lo[k] = host_dec(land->bounds[k]); out->bounds_hi[k] = host_dec(land->bounds[3 + k]); }
     const auto t_uploaded = std::chrono::steady_clock::now();
@@ -1645,10 +1637,8 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
     LevelCounters lc = land->lc;
     bool bins_clean = false;
     while (lc.n_nodes > 0) {
-        if (level + 1 >= (uint32_t)kMaxLevels || (uint64_t)base + lc.n_nodes > T) {
-            if (err) *err = "device BVH build: level bookkeeping out of range";
-            return LRC_ERR_INTERNAL;
-        }
+        if (level + 1 >= (uint32_t)kMaxLevels || (uint64_t)base + lc.n_nodes > T)
+            return fail(LRC_ERR_INTERNAL, "device BVH build: level bookkeeping out of range");
         P.cur = cur; P.nxt = nxt;
         uint32_t** L = lists[level & 1];
         uint32_t** Ln = lists[(level + 1) & 1];
@@ -1688,44 +1678,42 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
                                sub_mode, sub_roots, sub_count, (level + 1) & 1u);
         };
         emit();
-        DB_HIP(hipMemcpyAsync(land->lc_pair, cl, 2 * sizeof(LevelCounters), hipMemcpyDeviceToHost, st));
-        DB_HIP(hipStreamSynchronize(st));
+        LRC_HIP(hipMemcpyAsync(land->lc_pair, cl, 2 * sizeof(LevelCounters), hipMemcpyDeviceToHost, st));
+        LRC_HIP(hipStreamSynchronize(st));
         if (nb && land->lc_pair[0].n_median) {
             const uint32_t nmed = land->lc_pair[0].n_median;
             std::vector<uint32_t> slots(nmed);
             std::vector<BigWork> hw(nb);
-            DB_HIP(hipMemcpy(slots.data(), median_list, nmed * 4, hipMemcpyDeviceToHost));
-            DB_HIP(hipMemcpy(hw.data(), work, nb * sizeof(BigWork), hipMemcpyDeviceToHost));
+            LRC_HIP(hipMemcpy(slots.data(), median_list, nmed * 4, hipMemcpyDeviceToHost));
+            LRC_HIP(hipMemcpy(hw.data(), work, nb * sizeof(BigWork), hipMemcpyDeviceToHost));
             for (uint32_t q = 0; q < nmed; ++q) {
                 const BigWork& w = hw[slots[q]];
                 TNode hn;
-                DB_HIP(hipMemcpy(&hn, nodes + w.g, sizeof(TNode), hipMemcpyDeviceToHost));
+                LRC_HIP(hipMemcpy(&hn, nodes + w.g, sizeof(TNode), hipMemcpyDeviceToHost));
                 const uint32_t n = hn.end - hn.begin;
                 hipLaunchKernelGGL(k_median_keys, dim3((n + 255) / 256), dim3(256), 0, st, (const PrimRec*)cur, hn.begin,
                                    n, w.axis, keys_in, vals_in);
                 size_t tmp = arena->sort_cap;
                 hipError_t se = rocprim::radix_sort_pairs(arena->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out,
                                                           (size_t)n, 0, 64, st);
-                DB_HIP(se);
+                LRC_HIP(se);
                 hipLaunchKernelGGL(k_median_gather, dim3((n + 255) / 256), dim3(256), 0, st, P, work + slots[q], n,
                                    (const uint32_t*)vals_out);
             }
             // the emission again, from the state before it: the next level's counters and the running count of subtree roots
-            DB_HIP(hipMemsetAsync(counters + level + 1, 0, sizeof(LevelCounters), st));
-            DB_HIP(hipMemcpyAsync(sub_count, &n_sub_roots, 4, hipMemcpyHostToDevice, st));
+            LRC_HIP(hipMemsetAsync(counters + level + 1, 0, sizeof(LevelCounters), st));
+            LRC_HIP(hipMemcpyAsync(sub_count, &n_sub_roots, 4, hipMemcpyHostToDevice, st));
             emit();
-            DB_HIP(hipMemcpyAsync(land->lc_pair, cl, 2 * sizeof(LevelCounters), hipMemcpyDeviceToHost, st));
-            DB_HIP(hipStreamSynchronize(st));
+            LRC_HIP(hipMemcpyAsync(land->lc_pair, cl, 2 * sizeof(LevelCounters), hipMemcpyDeviceToHost, st));
+            LRC_HIP(hipStreamSynchronize(st));
         }
         land->lc = land->lc_pair[1];
         base += lc.n_nodes;
         lc = land->lc;
         num_leaves += lc.n_leaves;
         max_leaf_seen = std::max(max_leaf_seen, lc.max_leaf);
-        if (lc.n_tiny + lc.n_small + lc.n_medium + lc.n_big + lc.n_sub != lc.n_nodes) {
-            if (err) *err = "device BVH build: work lists do not add up";
-            return LRC_ERR_INTERNAL;
-        }
+        if (lc.n_tiny + lc.n_small + lc.n_medium + lc.n_big + lc.n_sub != lc.n_nodes)
+            return fail(LRC_ERR_INTERNAL, "device BVH build: work lists do not add up");
         n_sub_roots += lc.n_sub;
         std::swap(cur, nxt);
         ++level;
@@ -1735,7 +1723,7 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
             break;
         }
     }
-    DB_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     uint32_t nn = base;
     if (n_sub_roots) {
         // everything below the subtree roots in one launch; then the staged nodes get their numbers behind the level-numbered ones
@@ -1745,14 +1733,12 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
                            (SubTotals*)(sub_count + 4));
         hipLaunchKernelGGL(k_sub_place, dim3((n_sub_roots + 3) / 4), dim3(256), 0, st, nodes, (const SubRoot*)sub_roots, n_sub_roots,
                            (const SNode*)sub_stage, (const SubInfo*)sub_info, (const uint32_t*)sub_bases, nn);
-        DB_HIP(hipMemcpyAsync(land->median, sub_count + 4, sizeof(SubTotals), hipMemcpyDeviceToHost, st));
-        DB_HIP(hipStreamSynchronize(st));
+        LRC_HIP(hipMemcpyAsync(land->median, sub_count + 4, sizeof(SubTotals), hipMemcpyDeviceToHost, st));
+        LRC_HIP(hipStreamSynchronize(st));
         SubTotals tot;
         std::memcpy(&tot, land->median, sizeof(tot));
-        if ((uint64_t)nn + tot.nodes > T) {
-            if (err) *err = "device BVH build: subtree bookkeeping out of range";
-            return LRC_ERR_INTERNAL;
-        }
+        if ((uint64_t)nn + tot.nodes > T)
+            return fail(LRC_ERR_INTERNAL, "device BVH build: subtree bookkeeping out of range");
         nn += tot.nodes;
         num_leaves += tot.leaves;
         max_leaf_seen = std::max(max_leaf_seen, tot.max_leaf);
@@ -1774,7 +1760,7 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
     const size_t b_box = al((size_t)T * 24);
     const size_t slab_bytes = b_nodes + b_q + b_n + b_tris + 2 * b_id + b_box;
     void* slab = nullptr;
-    DB_HIP(hipMalloc(&slab, slab_bytes));
+    LRC_HIP(hipMalloc(&slab, slab_bytes));
     char* sp = (char*)slab;
     out->slab = slab; out->slab_bytes = slab_bytes;
     out->nodes = sp; sp += b_nodes;
@@ -1792,7 +1778,7 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
         hipLaunchKernelGGL(k_tail_keys, dim3((nt + 255) / 256), dim3(256), 0, st, (const TNode*)nodes, head, nn, keys_in, vals_in);
         size_t tmp = arena->sort_cap;
         hipError_t se = rocprim::radix_sort_pairs(arena->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)nt, 0, 41, st);
-        if (se != hipSuccess) { if (err) *err = std::string("device BVH build: radix sort: ") + hipGetErrorString(se); return bail(LRC_ERR_HIP); }
+        if (se != hipSuccess) { return bail(fail(LRC_ERR_HIP, std::string("device BVH build: radix sort: ") + hipGetErrorString(se))); }
     }
     const uint32_t nblk = (nn + 255) / 256;
     hipLaunchKernelGGL(k_new_index, dim3(nblk), dim3(256), 0, st, head, nn, (const uint32_t*)vals_out, new_of_old);
@@ -1806,7 +1792,7 @@ int build_bvh_device(DeviceArena* arena, const float* verts3, uint64_t V, const 
     {
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = e_copy != hipSuccess ? e_copy : e_sync;
-        if (e != hipSuccess) { (void)hipGetLastError(); if (err) *err = std::string("device BVH build: ") + hipGetErrorString(e); return bail(LRC_ERR_HIP); }
+        if (e != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_HIP, std::string("device BVH build: ") + hipGetErrorString(e))); }
     }
     QSummary qs;
     std::memcpy(&qs, land->median, sizeof(qs));

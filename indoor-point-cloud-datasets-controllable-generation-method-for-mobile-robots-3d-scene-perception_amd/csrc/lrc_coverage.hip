@@ -22,30 +22,16 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lidarcast.h"
+#include "lrc_internal.h"
 #include "lrc_area.h"
-
-extern "C" int lrc_internal_fail(int code, const char* msg);
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kRaysPerThread = 4;
 constexpr uint64_t kRaysPerBlock = (uint64_t)kBlock * kRaysPerThread;
 constexpr int kWordsPerThread = 4;           // gain kernel
 constexpr uint32_t kMaxClasses = 4096;       // distinct tri_sem values (per-class partials live in LDS)
 constexpr uint32_t kNoPick = 0xFFFFFFFFu;
-
-#define C_HIP(call)                                                                             \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
 
 struct SelectState {
     uint32_t done;           // 1: no further round picks
@@ -299,13 +285,6 @@ __global__ __launch_bounds__(kBlock) void or_kernel(const uint32_t* __restrict__
     if (w < W) covered[w] |= bits[(uint64_t)k * W + w];
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
-uint64_t blocks_of(uint64_t n, uint64_t per) { return (n + per - 1) / per; }
-
 }  // namespace
 
 struct lrc_coverage {
@@ -340,12 +319,12 @@ void release(lrc_coverage* c) {
 int launch_summary(lrc_coverage* c, const uint32_t* bits, uint64_t nsets, const unsigned long long* returns,
                    uint64_t nret, const unsigned long long* total_q, uint32_t* out_bits, unsigned long long* out,
                    unsigned long long* out_cls, uint32_t* flag, hipStream_t st) {
-    C_HIP(hipMemsetAsync(out, 0, 32, st));
-    if (c->C) C_HIP(hipMemsetAsync(out_cls, 0, (size_t)c->C * 8, st));
+    LRC_HIP(hipMemsetAsync(out, 0, 32, st));
+    if (c->C) LRC_HIP(hipMemsetAsync(out_cls, 0, (size_t)c->C * 8, st));
     hipLaunchKernelGGL(summary_kernel, dim3((uint32_t)blocks_of(c->W, kBlock)), dim3(kBlock), (size_t)c->C * 8, st, bits,
                        nsets, c->W, c->T, (const uint64_t*)c->d_q, (const uint16_t*)c->d_cls, c->C, returns, nret, total_q,
                        out_bits, out, out_cls, flag);
-    C_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 
@@ -376,17 +355,12 @@ int lrc_coverage_create(lrc_ctx* ctx, const double* verts3, uint64_t V, const in
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_create: need 0 < num_triangles < 2^32 - 1 and vertices");
     if (num_sets == 0 || num_sets >= (1ull << 31))
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_create: need 0 < num_sets < 2^31");
-    for (uint64_t i = 0; i < 3 * V; ++i)
-        if (!__builtin_isfinite(verts3[i]))
-            return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_create: non-finite vertex");
-    for (uint64_t i = 0; i < 3 * T; ++i)
-        if (tris3[i] < 0 || (uint64_t)tris3[i] >= V)
-            return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_create: triangle index out of range");
+    if (int rc = check_mesh("lrc_coverage_create", verts3, V, tris3, T)) return rc;
     const uint64_t W = (T + 31) / 32;
     if (num_sets > (~0ull / 4) / W) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_create: too many sets");
     lrc_coverage* c = new (std::nothrow) lrc_coverage();
     if (!c) return lrc_internal_fail(LRC_ERR_OOM, "lrc_coverage_create: out of host memory");
-    c->device = lrc_internal_ctx_device(ctx);
+    c->device = ctx->device;
     c->T = T;
     c->S = num_sets;
     c->W = W;
@@ -416,42 +390,42 @@ int lrc_coverage_create(lrc_ctx* ctx, const double* verts3, uint64_t V, const in
     }
     int rc = LRC_OK;
     auto run = [&]() -> int {
-        C_HIP(hipSetDevice(c->device));
-        C_HIP(hipMalloc((void**)&c->d_q, T * 8));
-        if (c->C) C_HIP(hipMalloc((void**)&c->d_cls, T * 2));
-        C_HIP(hipMalloc((void**)&c->d_bits, c->S * W * 4));
-        C_HIP(hipMalloc((void**)&c->d_hits, T * 4));
-        C_HIP(hipMalloc((void**)&c->d_returns, c->S * 8));
-        C_HIP(hipMalloc((void**)&c->d_scratch, (8 + (size_t)c->C) * 8));
-        C_HIP(hipMalloc((void**)&c->d_covered, W * 4));
-        C_HIP(hipMalloc((void**)&c->d_gains, c->S * 8));
-        C_HIP(hipMalloc((void**)&c->d_picked, c->S * 4));
-        C_HIP(hipMalloc((void**)&c->d_state, sizeof(SelectState)));
+        LRC_HIP(hipSetDevice(c->device));
+        LRC_HIP(hipMalloc((void**)&c->d_q, T * 8));
+        if (c->C) LRC_HIP(hipMalloc((void**)&c->d_cls, T * 2));
+        LRC_HIP(hipMalloc((void**)&c->d_bits, c->S * W * 4));
+        LRC_HIP(hipMalloc((void**)&c->d_hits, T * 4));
+        LRC_HIP(hipMalloc((void**)&c->d_returns, c->S * 8));
+        LRC_HIP(hipMalloc((void**)&c->d_scratch, (8 + (size_t)c->C) * 8));
+        LRC_HIP(hipMalloc((void**)&c->d_covered, W * 4));
+        LRC_HIP(hipMalloc((void**)&c->d_gains, c->S * 8));
+        LRC_HIP(hipMalloc((void**)&c->d_picked, c->S * 4));
+        LRC_HIP(hipMalloc((void**)&c->d_state, sizeof(SelectState)));
         Buf dv, df;
-        C_HIP(hipMalloc(&dv.p, V * 24));
-        C_HIP(hipMalloc(&df.p, T * 12));
-        C_HIP(hipMemcpy(dv.p, verts3, V * 24, hipMemcpyHostToDevice));
-        C_HIP(hipMemcpy(df.p, tris3, T * 12, hipMemcpyHostToDevice));
-        if (c->C) C_HIP(hipMemcpy(c->d_cls, dense.data(), T * 2, hipMemcpyHostToDevice));
-        C_HIP(hipMemset(c->d_bits, 0, c->S * W * 4));
-        C_HIP(hipMemset(c->d_hits, 0, T * 4));
-        C_HIP(hipMemset(c->d_returns, 0, c->S * 8));
-        C_HIP(hipMemset(c->d_scratch, 0, (8 + (size_t)c->C) * 8));
+        LRC_HIP(hipMalloc(&dv.p, V * 24));
+        LRC_HIP(hipMalloc(&df.p, T * 12));
+        LRC_HIP(hipMemcpy(dv.p, verts3, V * 24, hipMemcpyHostToDevice));
+        LRC_HIP(hipMemcpy(df.p, tris3, T * 12, hipMemcpyHostToDevice));
+        if (c->C) LRC_HIP(hipMemcpy(c->d_cls, dense.data(), T * 2, hipMemcpyHostToDevice));
+        LRC_HIP(hipMemset(c->d_bits, 0, c->S * W * 4));
+        LRC_HIP(hipMemset(c->d_hits, 0, T * 4));
+        LRC_HIP(hipMemset(c->d_returns, 0, c->S * 8));
+        LRC_HIP(hipMemset(c->d_scratch, 0, (8 + (size_t)c->C) * 8));
         uint32_t* flag = (uint32_t*)(c->d_scratch + 5);
         hipLaunchKernelGGL(area_kernel, dim3((uint32_t)blocks_of(T, kBlock)), dim3(kBlock), 0, nullptr,
                            (const double*)dv.p, (const int32_t*)df.p, T, c->d_q, flag);
-        C_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
         int r = launch_summary(c, nullptr, 0, c->d_returns, 0, nullptr, nullptr, c->d_scratch, c->d_scratch + 8, flag,
                                nullptr);
         if (r != LRC_OK) return r;
-        C_HIP(hipDeviceSynchronize());
+        LRC_HIP(hipDeviceSynchronize());
         std::vector<unsigned long long> host(8 + c->C);
-        C_HIP(hipMemcpy(host.data(), c->d_scratch, host.size() * 8, hipMemcpyDeviceToHost));
+        LRC_HIP(hipMemcpy(host.data(), c->d_scratch, host.size() * 8, hipMemcpyDeviceToHost));
         if (host[5] || host[0] > (1ull << 63))
             return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_create: total quantised area exceeds 2^63");
         c->total_q = host[0];
         c->class_total_q.assign(host.begin() + 8, host.end());
-        C_HIP(hipMemcpy(c->d_scratch + 4, &c->total_q, 8, hipMemcpyHostToDevice));
+        LRC_HIP(hipMemcpy(c->d_scratch + 4, &c->total_q, 8, hipMemcpyHostToDevice));
         return LRC_OK;
     };
     rc = run();
@@ -486,10 +460,10 @@ int lrc_coverage_classes(const lrc_coverage* cov, uint16_t* out_class_ids, uint6
 int lrc_coverage_reset(lrc_coverage* cov, void* stream) {
     if (!cov) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_reset: NULL argument");
     const hipStream_t st = (hipStream_t)stream;
-    C_HIP(hipSetDevice(cov->device));
-    C_HIP(hipMemsetAsync(cov->d_bits, 0, cov->S * cov->W * 4, st));
-    C_HIP(hipMemsetAsync(cov->d_hits, 0, cov->T * 4, st));
-    C_HIP(hipMemsetAsync(cov->d_returns, 0, cov->S * 8, st));
+    LRC_HIP(hipSetDevice(cov->device));
+    LRC_HIP(hipMemsetAsync(cov->d_bits, 0, cov->S * cov->W * 4, st));
+    LRC_HIP(hipMemsetAsync(cov->d_hits, 0, cov->T * 4, st));
+    LRC_HIP(hipMemsetAsync(cov->d_returns, 0, cov->S * 8, st));
     return LRC_OK;
 }
 
@@ -504,11 +478,11 @@ int lrc_coverage_accumulate_dev(lrc_coverage* cov, const float* d_t, const uint3
     const uint64_t bpp = blocks_of(rays_per_pose, kRaysPerBlock);
     if (num_poses > 0x7FFFFFFFull / bpp)
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_accumulate_dev: too many rays for one call");
-    C_HIP(hipSetDevice(cov->device));
+    LRC_HIP(hipSetDevice(cov->device));
     hipLaunchKernelGGL(accumulate_kernel, dim3((uint32_t)(num_poses * bpp)), dim3(kBlock), 0, (hipStream_t)stream, d_t,
                        d_prim, rays_per_pose, bpp, d_set_of_pose, cov->S, cov->T, cov->W, cov->d_bits, cov->d_hits,
                        cov->d_returns);
-    C_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 
@@ -518,7 +492,7 @@ int lrc_coverage_summary_dev(lrc_coverage* cov, int64_t set_index, uint64_t* d_o
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_summary_dev: NULL argument");
     int rc = check_set(cov, set_index, "lrc_coverage_summary_dev");
     if (rc != LRC_OK) return rc;
-    C_HIP(hipSetDevice(cov->device));
+    LRC_HIP(hipSetDevice(cov->device));
     const bool all = set_index < 0;
     const uint64_t k = all ? 0 : (uint64_t)set_index;
     return launch_summary(cov, cov->d_bits + k * cov->W, all ? cov->S : 1, cov->d_returns + k, all ? cov->S : 1,
@@ -532,24 +506,24 @@ int lrc_coverage_summary(lrc_coverage* cov, int64_t set_index, lrc_coverage_stat
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_summary: NULL argument");
     int rc = check_set(cov, set_index, "lrc_coverage_summary");
     if (rc != LRC_OK) return rc;
-    C_HIP(hipSetDevice(cov->device));
+    LRC_HIP(hipSetDevice(cov->device));
     Buf db;
-    if (out_bits) C_HIP(hipMalloc(&db.p, cov->W * 4));
-    C_HIP(hipDeviceSynchronize());          // work the caller enqueued on other streams
+    if (out_bits) LRC_HIP(hipMalloc(&db.p, cov->W * 4));
+    LRC_HIP(hipDeviceSynchronize());          // work the caller enqueued on other streams
     // the object's scratch holds the per-class totals of the mesh: summaries go to a buffer of their own
     Buf dout;
-    C_HIP(hipMalloc(&dout.p, (4 + (size_t)cov->C) * 8));
+    LRC_HIP(hipMalloc(&dout.p, (4 + (size_t)cov->C) * 8));
     uint64_t* d4 = (uint64_t*)dout.p;
     rc = lrc_coverage_summary_dev(cov, set_index, d4, d4 + 4, (uint32_t*)db.p, nullptr);
     if (rc != LRC_OK) return rc;
     std::vector<uint64_t> host(4 + cov->C);
-    C_HIP(hipMemcpy(host.data(), d4, host.size() * 8, hipMemcpyDeviceToHost));
+    LRC_HIP(hipMemcpy(host.data(), d4, host.size() * 8, hipMemcpyDeviceToHost));
     out->covered_q = host[0];
     out->total_q = host[1];
     out->seen_triangles = host[2];
     out->returns = host[3];
     for (uint32_t i = 0; i < cov->C; ++i) out_class_q[i] = host[4 + i];
-    if (out_bits) C_HIP(hipMemcpy(out_bits, db.p, cov->W * 4, hipMemcpyDeviceToHost));
+    if (out_bits) LRC_HIP(hipMemcpy(out_bits, db.p, cov->W * 4, hipMemcpyDeviceToHost));
     return LRC_OK;
 }
 
@@ -560,14 +534,14 @@ int lrc_coverage_select_dev(lrc_coverage* cov, uint32_t budget, double target_ra
     if (!(target_ratio == target_ratio))
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_select_dev: target_ratio is NaN");
     const hipStream_t st = (hipStream_t)stream;
-    C_HIP(hipSetDevice(cov->device));
+    LRC_HIP(hipSetDevice(cov->device));
     const uint64_t W = cov->W, S = cov->S;
-    if (d_initial_bits) C_HIP(hipMemcpyAsync(cov->d_covered, d_initial_bits, W * 4, hipMemcpyDeviceToDevice, st));
-    else C_HIP(hipMemsetAsync(cov->d_covered, 0, W * 4, st));
-    C_HIP(hipMemsetAsync(cov->d_gains, 0, S * 8, st));
-    C_HIP(hipMemsetAsync(cov->d_picked, 0, S * 4, st));
-    C_HIP(hipMemsetAsync(cov->d_state, 0, sizeof(SelectState), st));
-    C_HIP(hipMemsetAsync(d_out_num_picks, 0, 4, st));
+    if (d_initial_bits) LRC_HIP(hipMemcpyAsync(cov->d_covered, d_initial_bits, W * 4, hipMemcpyDeviceToDevice, st));
+    else LRC_HIP(hipMemsetAsync(cov->d_covered, 0, W * 4, st));
+    LRC_HIP(hipMemsetAsync(cov->d_gains, 0, S * 8, st));
+    LRC_HIP(hipMemsetAsync(cov->d_picked, 0, S * 4, st));
+    LRC_HIP(hipMemsetAsync(cov->d_state, 0, sizeof(SelectState), st));
+    LRC_HIP(hipMemsetAsync(d_out_num_picks, 0, 4, st));
     // covered_q of the initial cover (masked to the mesh's triangles) -> d_scratch[0]; the caller's bits stay as given
     unsigned long long* cq = cov->d_scratch;
     if (d_initial_bits) {
@@ -575,7 +549,7 @@ int lrc_coverage_select_dev(lrc_coverage* cov, uint32_t budget, double target_ra
                                 cov->d_scratch + 8, nullptr, st);
         if (rc != LRC_OK) return rc;
     } else {
-        C_HIP(hipMemsetAsync(cq, 0, 8, st));
+        LRC_HIP(hipMemsetAsync(cq, 0, 8, st));
     }
     const uint64_t per_set = blocks_of(W, (uint64_t)kBlock * kWordsPerThread);
     if (S > 0x7FFFFFFFull / per_set) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_select_dev: too many sets");
@@ -589,7 +563,7 @@ int lrc_coverage_select_dev(lrc_coverage* cov, uint32_t budget, double target_ra
                            (unsigned long long*)d_out_gains, d_out_num_picks);
         hipLaunchKernelGGL(or_kernel, dim3((uint32_t)blocks_of(W, kBlock)), dim3(kBlock), 0, st,
                            (const uint32_t*)cov->d_bits, W, (const SelectState*)cov->d_state, cov->d_covered);
-        C_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
     }
     return LRC_OK;
 }
@@ -598,24 +572,24 @@ int lrc_coverage_select(lrc_coverage* cov, uint32_t budget, double target_ratio,
                         uint32_t* out_picks, uint64_t* out_gains, uint32_t* out_num_picks) {
     if (!cov || !out_num_picks || (budget && (!out_picks || !out_gains)))
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_select: NULL argument");
-    C_HIP(hipSetDevice(cov->device));
-    C_HIP(hipDeviceSynchronize());
+    LRC_HIP(hipSetDevice(cov->device));
+    LRC_HIP(hipDeviceSynchronize());
     Buf di, dp, dg, dn;
     if (initial_bits) {
-        C_HIP(hipMalloc(&di.p, cov->W * 4));
-        C_HIP(hipMemcpy(di.p, initial_bits, cov->W * 4, hipMemcpyHostToDevice));
+        LRC_HIP(hipMalloc(&di.p, cov->W * 4));
+        LRC_HIP(hipMemcpy(di.p, initial_bits, cov->W * 4, hipMemcpyHostToDevice));
     }
     const uint64_t m = budget ? budget : 1;
-    C_HIP(hipMalloc(&dp.p, m * 4));
-    C_HIP(hipMalloc(&dg.p, m * 8));
-    C_HIP(hipMalloc(&dn.p, 4));
+    LRC_HIP(hipMalloc(&dp.p, m * 4));
+    LRC_HIP(hipMalloc(&dg.p, m * 8));
+    LRC_HIP(hipMalloc(&dn.p, 4));
     int rc = lrc_coverage_select_dev(cov, budget, target_ratio, (const uint32_t*)di.p, (uint32_t*)dp.p, (uint64_t*)dg.p,
                                      (uint32_t*)dn.p, nullptr);
     if (rc != LRC_OK) return rc;
-    C_HIP(hipMemcpy(out_num_picks, dn.p, 4, hipMemcpyDeviceToHost));      // the one synchronisation
+    LRC_HIP(hipMemcpy(out_num_picks, dn.p, 4, hipMemcpyDeviceToHost));      // the one synchronisation
     if (*out_num_picks) {
-        C_HIP(hipMemcpy(out_picks, dp.p, (size_t)*out_num_picks * 4, hipMemcpyDeviceToHost));
-        C_HIP(hipMemcpy(out_gains, dg.p, (size_t)*out_num_picks * 8, hipMemcpyDeviceToHost));
+        LRC_HIP(hipMemcpy(out_picks, dp.p, (size_t)*out_num_picks * 4, hipMemcpyDeviceToHost));
+        LRC_HIP(hipMemcpy(out_gains, dg.p, (size_t)*out_num_picks * 8, hipMemcpyDeviceToHost));
     }
     return LRC_OK;
 }
@@ -623,12 +597,12 @@ int lrc_coverage_select(lrc_coverage* cov, uint32_t budget, double target_ratio,
 int lrc_coverage_export(lrc_coverage* cov, uint32_t* out_bits, uint32_t* out_hits, uint64_t* out_returns,
                         uint64_t* out_q) {
     if (!cov) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_coverage_export: NULL argument");
-    C_HIP(hipSetDevice(cov->device));
-    C_HIP(hipDeviceSynchronize());
-    if (out_bits) C_HIP(hipMemcpy(out_bits, cov->d_bits, cov->S * cov->W * 4, hipMemcpyDeviceToHost));
-    if (out_hits) C_HIP(hipMemcpy(out_hits, cov->d_hits, cov->T * 4, hipMemcpyDeviceToHost));
-    if (out_returns) C_HIP(hipMemcpy(out_returns, cov->d_returns, cov->S * 8, hipMemcpyDeviceToHost));
-    if (out_q) C_HIP(hipMemcpy(out_q, cov->d_q, cov->T * 8, hipMemcpyDeviceToHost));
+    LRC_HIP(hipSetDevice(cov->device));
+    LRC_HIP(hipDeviceSynchronize());
+    if (out_bits) LRC_HIP(hipMemcpy(out_bits, cov->d_bits, cov->S * cov->W * 4, hipMemcpyDeviceToHost));
+    if (out_hits) LRC_HIP(hipMemcpy(out_hits, cov->d_hits, cov->T * 4, hipMemcpyDeviceToHost));
+    if (out_returns) LRC_HIP(hipMemcpy(out_returns, cov->d_returns, cov->S * 8, hipMemcpyDeviceToHost));
+    if (out_q) LRC_HIP(hipMemcpy(out_q, cov->d_q, cov->T * 8, hipMemcpyDeviceToHost));
     return LRC_OK;
 }
 

@@ -35,17 +35,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lidarcast.h"
+#include "lrc_internal.h"
 #include "lrc_area.h"
-
-extern "C" int lrc_internal_fail(int code, const char* msg);
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int kBlock = 256;
 constexpr int kRaysPerThread = 4;
 constexpr uint64_t kRaysPerBlock = (uint64_t)kBlock * kRaysPerThread;
 constexpr uint32_t kMaxObjects = 4096;
@@ -53,16 +49,6 @@ constexpr uint32_t kSlots = 128;             // LDS rows per workgroup (68 B eac
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;     // tag of an unclaimed row (object indices are < 4096)
 constexpr u64 kImgPosInf = 0xFFF0000000000000ull;   // img_of(+inf): the identity of min
 constexpr u64 kImgNegInf = 0x000FFFFFFFFFFFFFull;   // img_of(-inf): the identity of max
-
-#define F_HIP(call)                                                                             \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
 
 // Order-preserving image of a double: unsigned comparison of images is the IEEE total order (-0.0 below +0.0).
 __host__ __device__ inline u64 img_of(double x) {
@@ -341,13 +327,6 @@ __global__ __launch_bounds__(kBlock) void export_kernel(uint64_t rows, const uin
     }
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
-uint64_t blocks_of(uint64_t n, uint64_t per) { return (n + per - 1) / per; }
-
 }  // namespace
 
 struct lrc_frameobj {
@@ -378,14 +357,14 @@ void release(lrc_frameobj* o) {
 
 int enqueue_reset(lrc_frameobj* o, hipStream_t st) {
     const uint64_t rows = o->F * o->K;
-    F_HIP(hipMemsetAsync(o->d_bits, 0, o->F * o->W * 4, st));
-    F_HIP(hipMemsetAsync(o->d_ret, 0, rows * 4, st));
-    F_HIP(hipMemsetAsync(o->d_tris, 0, rows * 4, st));
-    F_HIP(hipMemsetAsync(o->d_sq, 0, rows * 8, st));
-    F_HIP(hipMemsetAsync(o->d_rej, 0, 8, st));
+    LRC_HIP(hipMemsetAsync(o->d_bits, 0, o->F * o->W * 4, st));
+    LRC_HIP(hipMemsetAsync(o->d_ret, 0, rows * 4, st));
+    LRC_HIP(hipMemsetAsync(o->d_tris, 0, rows * 4, st));
+    LRC_HIP(hipMemsetAsync(o->d_sq, 0, rows * 8, st));
+    LRC_HIP(hipMemsetAsync(o->d_rej, 0, 8, st));
     hipLaunchKernelGGL(fill_boxes_kernel, dim3((uint32_t)blocks_of(rows * 3, kBlock)), dim3(kBlock), 0, st, o->d_lo,
                        o->d_hi, rows * 3);
-    F_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 
@@ -410,12 +389,7 @@ int lrc_frameobj_create(lrc_ctx* ctx, const double* verts3, uint64_t V, const in
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_create: need 0 < num_triangles < 2^32 - 1 and vertices");
     if (num_frames == 0 || num_frames >= (1ull << 31))
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_create: need 0 < num_frames < 2^31");
-    for (uint64_t i = 0; i < 3 * V; ++i)
-        if (!__builtin_isfinite(verts3[i]))
-            return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_create: non-finite vertex");
-    for (uint64_t i = 0; i < 3 * T; ++i)
-        if (tris3[i] < 0 || (uint64_t)tris3[i] >= V)
-            return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_create: triangle index out of range");
+    if (int rc = check_mesh("lrc_frameobj_create", verts3, V, tris3, T)) return rc;
     const uint64_t W = (T + 31) / 32;
     if (num_frames > (~0ull / 4) / W) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_create: too many frames");
     // objects: the distinct label words, ascending
@@ -433,7 +407,7 @@ int lrc_frameobj_create(lrc_ctx* ctx, const double* verts3, uint64_t V, const in
         obj[j] = (uint16_t)(std::lower_bound(keys.begin(), keys.end(), key[j]) - keys.begin());
     lrc_frameobj* o = new (std::nothrow) lrc_frameobj();
     if (!o) return lrc_internal_fail(LRC_ERR_OOM, "lrc_frameobj_create: out of host memory");
-    o->device = lrc_internal_ctx_device(ctx);
+    o->device = ctx->device;
     o->T = T;
     o->F = num_frames;
     o->W = W;
@@ -441,41 +415,41 @@ int lrc_frameobj_create(lrc_ctx* ctx, const double* verts3, uint64_t V, const in
     o->keys = keys;
     const uint64_t K = o->K, rows = o->F * K;
     auto run = [&]() -> int {
-        F_HIP(hipSetDevice(o->device));
-        F_HIP(hipMalloc((void**)&o->d_q, T * 8));
-        F_HIP(hipMalloc((void**)&o->d_obj, T * 2));
-        F_HIP(hipMalloc((void**)&o->d_bits, o->F * W * 4));
-        F_HIP(hipMalloc((void**)&o->d_ret, rows * 4));
-        F_HIP(hipMalloc((void**)&o->d_tris, rows * 4));
-        F_HIP(hipMalloc((void**)&o->d_sq, rows * 8));
-        F_HIP(hipMalloc((void**)&o->d_lo, rows * 24));
-        F_HIP(hipMalloc((void**)&o->d_hi, rows * 24));
-        F_HIP(hipMalloc((void**)&o->d_rej, 8));
+        LRC_HIP(hipSetDevice(o->device));
+        LRC_HIP(hipMalloc((void**)&o->d_q, T * 8));
+        LRC_HIP(hipMalloc((void**)&o->d_obj, T * 2));
+        LRC_HIP(hipMalloc((void**)&o->d_bits, o->F * W * 4));
+        LRC_HIP(hipMalloc((void**)&o->d_ret, rows * 4));
+        LRC_HIP(hipMalloc((void**)&o->d_tris, rows * 4));
+        LRC_HIP(hipMalloc((void**)&o->d_sq, rows * 8));
+        LRC_HIP(hipMalloc((void**)&o->d_lo, rows * 24));
+        LRC_HIP(hipMalloc((void**)&o->d_hi, rows * 24));
+        LRC_HIP(hipMalloc((void**)&o->d_rej, 8));
         Buf dv, df, dtab;
-        F_HIP(hipMalloc(&dv.p, V * 24));
-        F_HIP(hipMalloc(&df.p, T * 12));
+        LRC_HIP(hipMalloc(&dv.p, V * 24));
+        LRC_HIP(hipMalloc(&df.p, T * 12));
         // the static table: tri_count (K u32, padded to 8 B), total_q (K), wlo / whi (3 K each), flag
         const uint64_t kpad = (K + 1) / 2;
-        F_HIP(hipMalloc(&dtab.p, (kpad + K + 6 * K + 1) * 8));
+        LRC_HIP(hipMalloc(&dtab.p, (kpad + K + 6 * K + 1) * 8));
         u64* base = (u64*)dtab.p;
         uint32_t* d_cnt = (uint32_t*)base;
         u64 *d_tq = base + kpad, *d_wlo = d_tq + K, *d_whi = d_wlo + 3 * K;
         uint32_t* d_flag = (uint32_t*)(d_whi + 3 * K);
-        F_HIP(hipMemcpy(dv.p, verts3, V * 24, hipMemcpyHostToDevice));
-        F_HIP(hipMemcpy(df.p, tris3, T * 12, hipMemcpyHostToDevice));
-        F_HIP(hipMemcpy(o->d_obj, obj.data(), T * 2, hipMemcpyHostToDevice));
-        F_HIP(hipMemset(dtab.p, 0, (kpad + K + 6 * K + 1) * 8));
+        LRC_HIP(hipMemcpy(dv.p, verts3, V * 24, hipMemcpyHostToDevice));
+        LRC_HIP(hipMemcpy(df.p, tris3, T * 12, hipMemcpyHostToDevice));
+        LRC_HIP(hipMemcpy(o->d_obj, obj.data(), T * 2, hipMemcpyHostToDevice));
+        LRC_HIP(hipMemset(dtab.p, 0, (kpad + K + 6 * K + 1) * 8));
         hipLaunchKernelGGL(fill_boxes_kernel, dim3((uint32_t)blocks_of(3 * K, kBlock)), dim3(kBlock), 0, nullptr, d_wlo,
                            d_whi, 3 * K);
         hipLaunchKernelGGL(static_kernel, dim3((uint32_t)blocks_of(T, kBlock)), dim3(kBlock), 0, nullptr,
                            (const double*)dv.p, (const int32_t*)df.p, T, (const uint16_t*)o->d_obj, o->d_q, d_cnt, d_tq,
                            d_wlo, d_whi, d_flag);
-        F_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
         int rc = enqueue_reset(o, nullptr);
         if (rc != LRC_OK) return rc;
-        F_HIP(hipDeviceSynchronize());
+        LRC_HIP(hipDeviceSynchronize());
         std::vector<u64> host(kpad + 7 * K + 1);
-        F_HIP(hipMemcpy(host.data(), dtab.p, host.size() * 8, hipMemcpyDeviceToHost));
+        LRC_HIP(hipMemcpy(host.data(), dtab.p, host.size() * 8, hipMemcpyDeviceToHost));
         const uint32_t* h_cnt = (const uint32_t*)host.data();
         const u64 *h_tq = host.data() + kpad, *h_wlo = h_tq + K, *h_whi = h_wlo + 3 * K;
         bool over = (host[kpad + 7 * K] & 0xFFFFFFFFull) != 0;
@@ -507,10 +481,10 @@ int lrc_frameobj_create(lrc_ctx* ctx, const double* verts3, uint64_t V, const in
 
 int lrc_frameobj_get_info(const lrc_frameobj* fo, lrc_frameobj_info* out) {
     if (!fo || !out) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_get_info: NULL argument");
-    F_HIP(hipSetDevice(fo->device));
-    F_HIP(hipDeviceSynchronize());
+    LRC_HIP(hipSetDevice(fo->device));
+    LRC_HIP(hipDeviceSynchronize());
     u64 rej = 0;
-    F_HIP(hipMemcpy(&rej, fo->d_rej, 8, hipMemcpyDeviceToHost));
+    LRC_HIP(hipMemcpy(&rej, fo->d_rej, 8, hipMemcpyDeviceToHost));
     out->num_triangles = fo->T;
     out->num_frames = fo->F;
     out->num_objects = fo->K;
@@ -533,7 +507,7 @@ int lrc_frameobj_objects(const lrc_frameobj* fo, uint32_t* out_key, uint32_t* ou
 
 int lrc_frameobj_reset(lrc_frameobj* fo, void* stream) {
     if (!fo) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_reset: NULL argument");
-    F_HIP(hipSetDevice(fo->device));
+    LRC_HIP(hipSetDevice(fo->device));
     return enqueue_reset(fo, (hipStream_t)stream);
 }
 
@@ -548,46 +522,46 @@ int lrc_frameobj_accumulate_dev(lrc_frameobj* fo, const double* d_poses16, uint6
     const uint64_t bpp = blocks_of(rays_per_pose, kRaysPerBlock);
     if (num_poses > 0x7FFFFFFFull / bpp)
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_accumulate_dev: too many rays for one call");
-    F_HIP(hipSetDevice(fo->device));
+    LRC_HIP(hipSetDevice(fo->device));
     hipLaunchKernelGGL(accumulate_kernel, dim3((uint32_t)(num_poses * bpp)), dim3(kBlock), 0, (hipStream_t)stream,
                        d_poses16, d_t, d_prim, (const uint32_t*)d_point3, rays_per_pose, bpp, first_frame, fo->T, fo->W,
                        fo->K, (const uint16_t*)fo->d_obj, (const uint64_t*)fo->d_q, fo->d_bits, fo->d_ret, fo->d_tris,
                        fo->d_sq, fo->d_lo, fo->d_hi, fo->d_rej);
-    F_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 
 int lrc_frameobj_export_dev(lrc_frameobj* fo, uint32_t* d_returns, uint32_t* d_seen_tris, uint64_t* d_seen_q,
                             double* d_vmin, double* d_vmax, void* stream) {
     if (!fo) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_export_dev: NULL argument");
-    F_HIP(hipSetDevice(fo->device));
+    LRC_HIP(hipSetDevice(fo->device));
     const uint64_t rows = fo->F * fo->K;
     hipLaunchKernelGGL(export_kernel, dim3((uint32_t)blocks_of(rows, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, rows,
                        (const uint32_t*)fo->d_ret, (const uint32_t*)fo->d_tris, (const u64*)fo->d_sq, (const u64*)fo->d_lo,
                        (const u64*)fo->d_hi, d_returns, d_seen_tris, d_seen_q, d_vmin, d_vmax);
-    F_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 
 int lrc_frameobj_export(lrc_frameobj* fo, uint32_t* out_returns, uint32_t* out_seen_tris, uint64_t* out_seen_q,
                         double* out_vmin, double* out_vmax) {
     if (!fo) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_frameobj_export: NULL argument");
-    F_HIP(hipSetDevice(fo->device));
+    LRC_HIP(hipSetDevice(fo->device));
     const uint64_t rows = fo->F * fo->K;
     Buf dlo, dhi;
-    if (out_vmin) F_HIP(hipMalloc(&dlo.p, rows * 24));
-    if (out_vmax) F_HIP(hipMalloc(&dhi.p, rows * 24));
-    F_HIP(hipDeviceSynchronize());          // work the caller enqueued on other streams
+    if (out_vmin) LRC_HIP(hipMalloc(&dlo.p, rows * 24));
+    if (out_vmax) LRC_HIP(hipMalloc(&dhi.p, rows * 24));
+    LRC_HIP(hipDeviceSynchronize());          // work the caller enqueued on other streams
     if (out_vmin || out_vmax) {
         const int rc = lrc_frameobj_export_dev(fo, nullptr, nullptr, nullptr, (double*)dlo.p, (double*)dhi.p, nullptr);
         if (rc != LRC_OK) return rc;
     }
     // the copies on the null stream follow the decode kernel
-    if (out_returns) F_HIP(hipMemcpy(out_returns, fo->d_ret, rows * 4, hipMemcpyDeviceToHost));
-    if (out_seen_tris) F_HIP(hipMemcpy(out_seen_tris, fo->d_tris, rows * 4, hipMemcpyDeviceToHost));
-    if (out_seen_q) F_HIP(hipMemcpy(out_seen_q, fo->d_sq, rows * 8, hipMemcpyDeviceToHost));
-    if (out_vmin) F_HIP(hipMemcpy(out_vmin, dlo.p, rows * 24, hipMemcpyDeviceToHost));
-    if (out_vmax) F_HIP(hipMemcpy(out_vmax, dhi.p, rows * 24, hipMemcpyDeviceToHost));
+    if (out_returns) LRC_HIP(hipMemcpy(out_returns, fo->d_ret, rows * 4, hipMemcpyDeviceToHost));
+    if (out_seen_tris) LRC_HIP(hipMemcpy(out_seen_tris, fo->d_tris, rows * 4, hipMemcpyDeviceToHost));
+    if (out_seen_q) LRC_HIP(hipMemcpy(out_seen_q, fo->d_sq, rows * 8, hipMemcpyDeviceToHost));
+    if (out_vmin) LRC_HIP(hipMemcpy(out_vmin, dlo.p, rows * 24, hipMemcpyDeviceToHost));
+    if (out_vmax) LRC_HIP(hipMemcpy(out_vmax, dhi.p, rows * 24, hipMemcpyDeviceToHost));
     return LRC_OK;
 }
 

@@ -1,0 +1,162 @@
+// lrc_internal.h -- what the translation units of liblidarcast share and include/lidarcast.h does not declare: the
+// handles behind the opaque types, the error plumbing, the HIP status macro, the owning device buffers and the small
+// host helpers.  Everything in here is hidden: only the C ABI of include/lidarcast.h and the lrc_internal_* test hooks
+// are dynamic symbols of the library.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <mutex>
+#include <string>
+
+#include "../../include/lidarcast.h"
+#include "lrc_bvh_device.h"
+
+// sets lrc_last_error() (lidarcast.hip).  Exported: lrc_nprandom.cpp, built without HIP headers, reports through it.
+extern "C" int lrc_internal_fail(int code, const char* msg);
+
+#pragma GCC visibility push(hidden)
+
+int fail(int code, const std::string& msg);      // lidarcast.hip: sets the thread's lrc_last_error() text, returns code
+
+// LRC_HIP_WHERE is read where LRC_HIP is used, not here: a unit that names the stage its HIP calls belong to in front of
+// the call text redefines it after this include (lrc_bvh_device.hip)
+#define LRC_HIP_WHERE ""
+#define LRC_HIP(call)                                                                      \
+    do {                                                                                   \
+        hipError_t e__ = (call);                                                           \
+        if (e__ != hipSuccess) {                                                           \
+            (void)hipGetLastError();                                                       \
+            return fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,            \
+                        std::string(LRC_HIP_WHERE #call) + ": " + hipGetErrorString(e__)); \
+        }                                                                                  \
+    } while (0)
+
+constexpr int kBlock = 256;          // compaction kernels
+#ifndef LRC_TRACE_BLOCK
+#define LRC_TRACE_BLOCK 64
+#endif
+constexpr int kTBlock = LRC_TRACE_BLOCK;   // trace kernel workgroup (rays per tile)
+
+enum PoolSlot { kPoolRays = 0, kPoolT, kPoolPrim, kPoolNormal, kPoolPoint, kPoolSem, kPoolIns, kPoolInc, kPoolInten,
+                kPoolPoses, kPoolDirs, kPoolOffs, kPoolCen, kPoolNoise,
+                // *_compact entry points: scan angles in, per-wave keep counts, compacted frame arrays out
+                kPoolAngles, kPoolKeep, kPoolTile, kPoolCounts, kPoolOutPoint, kPoolOutSem, kPoolOutIns, kPoolOutInc,
+                kPoolOutIdx, kPoolOutXyzl, kPoolOutRange, kPoolStats, kPoolFrameStats, kPoolSlots };
+
+// triangle records fetched per leaf round trip by the product kernels.  With edge records the pair fits 64 VGPRs, i.e. 8
+// waves per SIMD: -2...-4 % trace time on all benchmark scenes against one record per round trip.
+constexpr int kLeafW = 2;
+
+struct lrc_ctx {
+    int device = 0;
+    // staging buffers of the host-pointer entry points, grown on demand and reused (a per-waypoint caller
+    // such as the reference loop, s3dis_simulator.py:254-264, would otherwise pay hipMalloc/hipFree per pose)
+    void* pool[kPoolSlots] = {};
+    size_t pool_cap[kPoolSlots] = {};
+    // compaction scratch (grown on demand, reused): per-tile counts and exclusive offsets.  Two sets: the
+    // cloud rebuild of the multi-GPU path runs on its own stream next to the compaction of the local scan.
+    struct TileScratch {
+        uint32_t* d_tile_off = nullptr;     // offset of a tile inside its super tile (1024 tiles)
+        uint32_t* d_tile_cnt = nullptr;
+        uint32_t* d_super_total = nullptr;  // kept entries per super tile
+        uint64_t* d_super_base = nullptr;   // exclusive prefix of d_super_total (+ grand total)
+        uint64_t tile_cap = 0;
+        double* d_dirs_soa = nullptr;       // direction table transposed to x[N] y[N] z[N] (cloud rebuild only)
+        uint64_t dirs_cap = 0;
+    };
+    TileScratch cloud_scratch;
+    // lrc_compact_dev: one scratch set per caller stream (a caller that keeps two scans in flight on two streams compacts on
+    // both); a set handed on to another stream is first ordered behind its last use (scratch_for)
+    static constexpr int kCompactSets = 4;
+    TileScratch compact_scratch[kCompactSets];
+    hipStream_t compact_stream[kCompactSets] = {};
+    hipEvent_t compact_done[kCompactSets] = {};
+    bool compact_used[kCompactSets] = {};
+    int compact_next = 0;
+    // Dispatch chaining of trace launches ("the launch tail"): the LAST workgroup of every trace launch writes the
+    // launch's sequence number to this signal word at its first instruction; a trace launch on ANOTHER stream than the
+    // previous one is held behind hipStreamWaitValue64(word >= previous sequence number), i.e. it starts the moment the
+    // previous launch has handed out its last workgroup -- its waves fill the slots the previous launch's tail leaves empty,
+    // and launches that a caller keeps in flight on two streams run staggered instead of falling into phase.
+    uint64_t* chain_word = nullptr;     // hipMallocSignalMemory; NULL: not supported here, launches are never chained
+    uint64_t chain_seq = 0;             // sequence number of the last chained trace launch
+    hipStream_t chain_stream = nullptr; // ... and the stream it went to
+    bool chain_enabled = false;         // lrc_ctx_set_launch_chaining (opt-in: measured equal to what the dispatcher does itself)
+    // *_compact entry points: kernels on one stream, the transfers of finished pose chunks on another
+    hipStream_t s_compute = nullptr, s_copy = nullptr, s_stats = nullptr;
+    hipEvent_t ev_chunk[8] = {}, ev_compact[8] = {};
+    uint64_t* h_counts = nullptr;       // page-locked landing area of the per-pose counts and statistics (async copies
+    uint64_t h_counts_cap = 0;          // need one): counts (P u64) | 4 x P doubles of per-pose statistics
+    lrc::DeviceArena build_arena;       // scratch of the device scene build, reused from scene to scene
+    float* stat_scratch = nullptr;      // chunk sums of lrc_cloud_range_stats_dev (calls of one context must not overlap
+    uint64_t stat_scratch_cap = 0;      // on different streams: handles are not thread-safe)
+};
+
+struct lrc_table {            // a sensor's direction table resident in HBM (lrc_table_create)
+    lrc_ctx* ctx = nullptr;
+    double* d_dirs3 = nullptr;
+    uint64_t n = 0;
+    double* d_fire = nullptr;   // optional (lrc_table_set_fire): per ray the fraction of the sweep at which it fires
+};
+
+struct lrc_scene {
+    lrc_ctx* ctx = nullptr;
+    void* slab = nullptr;             // device-built scenes: ONE allocation holds every array below except d_slot_sphere / *4
+    float4* d_nodes = nullptr;
+    float4* d_tris = nullptr;
+    uint32_t* d_slot_prim = nullptr;
+    uint32_t* d_slot_label = nullptr;
+    float* d_slot_box = nullptr;      // per leaf slot the triangle's exact vertex box (lo xyz, hi xyz)
+    float4* d_prim_plane = nullptr;   // per caller's triangle row: (v0, label bits), (Ng, 0): lrc_cloud_from_prims_dev
+    std::mutex plane_mutex;           // ... built on first use, published complete (ensure_prim_plane)
+    float4* d_slot_sphere = nullptr;  // per leaf slot: centre of the triangle's box + bounding radius (sector_kernel)
+    // quantised node images of the SAME tree ("32-byte nodes"): child boxes on a 15-bit grid
+    // per axis, rounded outward (margin 1/16 cell).  d_nodes_q: 32 B per node for the per-lane fetches; d_nodes_n: the same
+    // boxes as normalised float32 (64 B per node) for the scalar fetches.  NULL when the grid does not fit the scene.
+    uint4* d_nodes_q = nullptr;
+    float4* d_nodes_n = nullptr;
+    // the same tree collapsed to four children per node (every second level removed), on the same grid:
+    // d_nodes_q4 64 B per node (per child lo|hi<<16 x, y, z + reference), d_nodes_n4 128 B (per child lo, hi, ref, pad)
+    uint4* d_nodes_q4 = nullptr;
+    float4* d_nodes_n4 = nullptr;
+    uint64_t num_nodes4 = 0;
+    float qbase[3] = {0, 0, 0}, qW[3] = {1, 1, 1}, qinvW[3] = {1, 1, 1};
+    const lrc_grid* cur_grid = nullptr;   // set around a grid scan (launch_trace gen == 3)
+    lrc_scene_info info{};
+    lrc_scan_options opts{};          // sticky opt-in options (lrc_scene_set_options)
+    uint64_t launches = 0, rays = 0;
+};
+
+// device buffer of a host-pointer entry point: its own allocation, or a slot of the context's staging pool
+struct DevBuf {
+    void* p = nullptr;
+    bool pooled = false;
+    ~DevBuf() { if (p && !pooled) (void)hipFree(p); }
+    // buffer of the context's staging pool (kept for the next call)
+    int get(lrc_ctx* ctx, int slot, size_t bytes) {
+        if (ctx->pool_cap[slot] < bytes) {
+            if (ctx->pool[slot]) { (void)hipFree(ctx->pool[slot]); ctx->pool[slot] = nullptr; ctx->pool_cap[slot] = 0; }
+            const size_t cap = bytes + bytes / 8;
+            LRC_HIP(hipMalloc(&ctx->pool[slot], cap));
+            ctx->pool_cap[slot] = cap;
+        }
+        p = ctx->pool[slot];
+        pooled = true;
+        return LRC_OK;
+    }
+};
+// plain owning device allocation
+struct Buf {
+    void* p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+};
+
+inline uint64_t blocks_of(uint64_t n, uint64_t per) { return (n + per - 1) / per; }
+inline int env_int(const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; }
+
+// the mesh checks of lrc_coverage_create and lrc_frameobj_create (non-finite vertex, triangle index out of range); `who`
+// prefixes the message.  Defined in lidarcast.hip, beside fail(): host code with no unit of its own.
+int check_mesh(const char* who, const double* verts3, uint64_t V, const int32_t* tris3, uint64_t T);
+
+#pragma GCC visibility pop

@@ -17,23 +17,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lidarcast.h"
-
-extern "C" int lrc_internal_fail(int code, const char* msg);     // lidarcast.hip: sets lrc_last_error()
-
-#define LRC64_HIP(call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
+#include "lrc_internal.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kRedBlocks = 256;        // chunks of the fixed-order reductions (bounds, mean, std)
 
 struct Grid {

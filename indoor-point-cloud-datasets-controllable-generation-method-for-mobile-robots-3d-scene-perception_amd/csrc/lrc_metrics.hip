@@ -13,24 +13,11 @@
 
 #include <string>
 
-#include "../../include/lidarcast.h"
-
-extern "C" int lrc_internal_fail(int code, const char* msg);
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
+#include "lrc_internal.h"
 
 namespace {
 
 constexpr int kTile = 1024;
-
-#define M_HIP(call)                                                                             \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
 
 __global__ __launch_bounds__(256) void min_dist_kernel(const float* A, uint64_t n, const float* B, uint64_t m,
                                                        float* out) {
@@ -91,11 +78,6 @@ __global__ __launch_bounds__(256) void rbf_sum_kernel(const float* A, uint64_t n
     if (threadIdx.x == 0) out_partial[blockIdx.x] = red[0];
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -105,18 +87,18 @@ int lrc_min_distances(lrc_ctx* ctx, const float* a3, uint64_t n, const float* b3
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_min_distances: NULL argument");
     if (n == 0) return LRC_OK;
     if (m == 0) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_min_distances: the target cloud is empty");
-    M_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC_HIP(hipSetDevice(ctx->device));
     Buf da, db, dout;
-    M_HIP(hipMalloc(&da.p, n * 12));
-    M_HIP(hipMalloc(&db.p, m * 12));
-    M_HIP(hipMalloc(&dout.p, n * 4));
-    M_HIP(hipMemcpy(da.p, a3, n * 12, hipMemcpyHostToDevice));
-    M_HIP(hipMemcpy(db.p, b3, m * 12, hipMemcpyHostToDevice));
+    LRC_HIP(hipMalloc(&da.p, n * 12));
+    LRC_HIP(hipMalloc(&db.p, m * 12));
+    LRC_HIP(hipMalloc(&dout.p, n * 4));
+    LRC_HIP(hipMemcpy(da.p, a3, n * 12, hipMemcpyHostToDevice));
+    LRC_HIP(hipMemcpy(db.p, b3, m * 12, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(min_dist_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, nullptr, (const float*)da.p, n,
                        (const float*)db.p, m, (float*)dout.p);
-    M_HIP(hipGetLastError());
-    M_HIP(hipDeviceSynchronize());
-    M_HIP(hipMemcpy(out_min, dout.p, n * 4, hipMemcpyDeviceToHost));
+    LRC_HIP(hipGetLastError());
+    LRC_HIP(hipDeviceSynchronize());
+    LRC_HIP(hipMemcpy(out_min, dout.p, n * 4, hipMemcpyDeviceToHost));
     return LRC_OK;
 }
 
@@ -126,18 +108,18 @@ int lrc_rbf_kernel_sum(lrc_ctx* ctx, const float* a3, uint64_t n, const float* b
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_rbf_kernel_sum: NULL argument");
     *out_sum = 0.0;
     if (n == 0 || m == 0) return LRC_OK;
-    M_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC_HIP(hipSetDevice(ctx->device));
     const uint32_t nblk = (uint32_t)((n + 255) / 256);
     Buf da, db, dp;
-    M_HIP(hipMalloc(&da.p, n * 12));
-    M_HIP(hipMalloc(&db.p, m * 12));
-    M_HIP(hipMalloc(&dp.p, (size_t)nblk * 8));
-    M_HIP(hipMemcpy(da.p, a3, n * 12, hipMemcpyHostToDevice));
-    M_HIP(hipMemcpy(db.p, b3, m * 12, hipMemcpyHostToDevice));
+    LRC_HIP(hipMalloc(&da.p, n * 12));
+    LRC_HIP(hipMalloc(&db.p, m * 12));
+    LRC_HIP(hipMalloc(&dp.p, (size_t)nblk * 8));
+    LRC_HIP(hipMemcpy(da.p, a3, n * 12, hipMemcpyHostToDevice));
+    LRC_HIP(hipMemcpy(db.p, b3, m * 12, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(rbf_sum_kernel, dim3(nblk), dim3(256), 0, nullptr, (const float*)da.p, n, (const float*)db.p, m,
                        gamma, (double*)dp.p);
-    M_HIP(hipGetLastError());
-    M_HIP(hipDeviceSynchronize());
+    LRC_HIP(hipGetLastError());
+    LRC_HIP(hipDeviceSynchronize());
     double* part = new (std::nothrow) double[nblk];
     if (!part) return lrc_internal_fail(LRC_ERR_OOM, "lrc_rbf_kernel_sum: out of host memory");
     hipError_t e = hipMemcpy(part, dp.p, (size_t)nblk * 8, hipMemcpyDeviceToHost);

@@ -20,22 +20,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lidarcast.h"
-
-extern "C" int lrc_internal_fail(int code, const char* msg);     // lidarcast.hip: sets lrc_last_error()
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
+#include "lrc_internal.h"
 
 namespace {
-
-#define NN_HIP(call)                                                                            \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
 
 struct GridDev {
     const double* pts;        // (M,3) points sorted by cell
@@ -186,7 +173,7 @@ int lrc_nn_create(lrc_ctx* ctx, const double* points3, uint64_t M, double cell_s
     lrc_nn* nn = new (std::nothrow) lrc_nn();
     if (!nn) return lrc_internal_fail(LRC_ERR_OOM, "lrc_nn_create: out of host memory");
     nn->ctx = ctx;
-    nn->device = lrc_internal_ctx_device(ctx);
+    nn->device = ctx->device;
     nn->M = M;
     nn->ncells = ncells;
     auto bail = [&](int rc) { lrc_nn_destroy(nn); return rc; };
@@ -211,12 +198,12 @@ int lrc_nn_query_dev(lrc_nn* nn, const float* d_query3, uint64_t K, uint32_t* d_
     if (!nn || (K && (!d_query3 || !d_out_index)))
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_nn_query_dev: NULL argument");
     if (K == 0) return LRC_OK;
-    NN_HIP(hipSetDevice(nn->device));
+    LRC_HIP(hipSetDevice(nn->device));
     const uint64_t nblk = (K + 255) / 256;
     if (nblk > 0x7FFFFFFFull) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_nn_query_dev: too many queries");
     hipLaunchKernelGGL(nn_query_kernel, dim3((uint32_t)nblk), dim3(256), 0, (hipStream_t)stream, nn->g, d_query3, K,
                        d_out_index, d_out_dist);
-    NN_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 
@@ -224,7 +211,7 @@ int lrc_nn_query(lrc_nn* nn, const float* query3, uint64_t K, uint32_t* out_inde
     if (!nn || (K && (!query3 || !out_index)))
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_nn_query: NULL argument");
     if (K == 0) return LRC_OK;
-    NN_HIP(hipSetDevice(nn->device));
+    LRC_HIP(hipSetDevice(nn->device));
     float* dq = nullptr; uint32_t* di = nullptr; double* dd = nullptr;
     int rc = LRC_OK;
     if (hipMalloc((void**)&dq, K * 12) != hipSuccess || hipMalloc((void**)&di, K * 4) != hipSuccess ||

@@ -32,8 +32,6 @@
 
 #include "lrc_knn64.h"
 
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
-
 namespace {
 
 constexpr uint32_t kMaxRowsY = 65535;   // objects per grid row of the (object, chunk) launches; blocks stride beyond
@@ -340,7 +338,7 @@ int lrc_object_boxes_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, cons
     if (int rc = check_args("lrc_object_boxes_dev", n, offsets, num_objects, k, std_ratio)) return rc;
     const uint32_t S = (uint32_t)num_objects;
     if (S == 0) return LRC_OK;
-    LRC64_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC_HIP(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     Arena arena(st);
 
@@ -369,35 +367,35 @@ int lrc_object_boxes_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, cons
                      o_bad = o_box + align256((size_t)S * sizeof(lrc_objbox)), o_part = o_bad + 256,
                      total = o_part + align256((size_t)S * kRedBlocks * 8);
         void* q;
-        LRC64_HIP(arena.get(total, &q));
+        LRC_HIP(arena.get(total, &q));
         char* c = (char*)q;
         off = (uint64_t*)c; base = (uint32_t*)(c + o_base); keys = (unsigned long long*)(c + o_keys);
         kkeys = (unsigned long long*)(c + o_kkeys); zrow = (unsigned long long*)(c + o_zrow); grids = (Grid*)(c + o_grid); stats = (double*)(c + o_stats);
         boxes = (lrc_objbox*)(c + o_box); bad = (uint32_t*)(c + o_bad); part = (double*)(c + o_part);
     }
-    LRC64_HIP(hipMemcpyAsync(off, offsets, (S + 1) * 8, hipMemcpyHostToDevice, st));
-    LRC64_HIP(hipMemcpyAsync(base, h_base.data(), (S + 1) * 4, hipMemcpyHostToDevice, st));
+    LRC_HIP(hipMemcpyAsync(off, offsets, (S + 1) * 8, hipMemcpyHostToDevice, st));
+    LRC_HIP(hipMemcpyAsync(base, h_base.data(), (S + 1) * 4, hipMemcpyHostToDevice, st));
     // lo keys start at all ones, hi keys at zero: 6 words per object, three of each
     {
         std::vector<unsigned long long> init((size_t)S * 6);
         for (size_t j = 0; j < init.size(); ++j) init[j] = (j % 6) < 3 ? ~0ull : 0ull;
-        LRC64_HIP(hipMemcpyAsync(keys, init.data(), init.size() * 8, hipMemcpyHostToDevice, st));
-        LRC64_HIP(hipMemcpyAsync(kkeys, init.data(), init.size() * 8, hipMemcpyHostToDevice, st));
-        LRC64_HIP(hipMemsetAsync(zrow, 0, (size_t)S * 24, st));
-        LRC64_HIP(hipMemsetAsync(bad, 0, 4, st));
+        LRC_HIP(hipMemcpyAsync(keys, init.data(), init.size() * 8, hipMemcpyHostToDevice, st));
+        LRC_HIP(hipMemcpyAsync(kkeys, init.data(), init.size() * 8, hipMemcpyHostToDevice, st));
+        LRC_HIP(hipMemsetAsync(zrow, 0, (size_t)S * 24, st));
+        LRC_HIP(hipMemsetAsync(bad, 0, 4, st));
         const dim3 og(kRedBlocks, std::min(S, kMaxRowsY));
         if (n) hipLaunchKernelGGL(ob_bounds_kernel, og, dim3(kBlock), 0, st, d_points3, (const uint64_t*)off, S,
                                   (const uint32_t*)nullptr, keys, bad, (unsigned long long*)nullptr);
-        LRC64_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
         uint32_t h_bad = 0;
-        LRC64_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
-        LRC64_HIP(hipStreamSynchronize(st));          // `init` stays alive until the copies above have run
+        LRC_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
+        LRC_HIP(hipStreamSynchronize(st));          // `init` stays alive until the copies above have run
         if (h_bad) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_object_boxes: non-finite coordinate");
     }
     const uint32_t sblk = (S + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(ob_grid_kernel, dim3(sblk), dim3(kBlock), 0, st, (const unsigned long long*)keys,
                        (const uint64_t*)off, S, (int)k, cell_size, grids);
-    LRC64_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
 
     if (n) {
         const uint32_t nblk = (uint32_t)((n + kBlock - 1) / kBlock);
@@ -409,7 +407,7 @@ int lrc_object_boxes_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, cons
                          o_pts = o_start + align256((cells + 1) * 4), o_avg = o_pts + align256(n * sizeof(SPt)),
                          total = o_avg + (d_out_avg ? 0 : align256(n * 8));
             void* q;
-            LRC64_HIP(arena.get(total, &q));
+            LRC_HIP(arena.get(total, &q));
             char* c = (char*)q;
             keys_a = (uint32_t*)c; keys_b = (uint32_t*)(c + sz); vals_a = (uint32_t*)(c + 2 * sz);
             vals_b = (uint32_t*)(c + 3 * sz); seg = (uint32_t*)(c + 4 * sz); flag = (uint32_t*)(c + 5 * sz);
@@ -419,24 +417,24 @@ int lrc_object_boxes_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, cons
         }
         hipLaunchKernelGGL(ob_key_kernel, dim3(nblk), dim3(kBlock), 0, st, d_points3, n, (const uint64_t*)off, S,
                            (const Grid*)grids, (const uint32_t*)base, keys_a, vals_a, seg);
-        LRC64_HIP(hipGetLastError());
-        LRC64_HIP(hipMemsetAsync(counts, 0, (cells + 1) * 4, st));
+        LRC_HIP(hipGetLastError());
+        LRC_HIP(hipMemsetAsync(counts, 0, (cells + 1) * 4, st));
         const int end_bit = std::max(1, bit_width(cells));
         size_t tmp_sort = 0, tmp_scan = 0, tmp_flag = 0;
-        LRC64_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)n, 0, end_bit, st));
-        LRC64_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, counts, start, 0u, (size_t)(cells + 1),
+        LRC_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)n, 0, end_bit, st));
+        LRC_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, counts, start, 0u, (size_t)(cells + 1),
                                           rocprim::plus<uint32_t>(), st));
-        LRC64_HIP(rocprim::exclusive_scan(nullptr, tmp_flag, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        LRC_HIP(rocprim::exclusive_scan(nullptr, tmp_flag, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
         void* tmp;
-        LRC64_HIP(arena.get(std::max(tmp_sort, std::max(tmp_scan, tmp_flag)), &tmp));
-        LRC64_HIP(rocprim::radix_sort_pairs(tmp, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)n, 0, end_bit, st));
+        LRC_HIP(arena.get(std::max(tmp_sort, std::max(tmp_scan, tmp_flag)), &tmp));
+        LRC_HIP(rocprim::radix_sort_pairs(tmp, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)n, 0, end_bit, st));
         hipLaunchKernelGGL(ob_gather_kernel, dim3(nblk), dim3(kBlock), 0, st, d_points3, keys_b, vals_b,
                            (const uint32_t*)seg, n, counts, pts);
-        LRC64_HIP(hipGetLastError());
-        LRC64_HIP(rocprim::exclusive_scan(tmp, tmp_scan, counts, start, 0u, (size_t)(cells + 1),
+        LRC_HIP(hipGetLastError());
+        LRC_HIP(rocprim::exclusive_scan(tmp, tmp_scan, counts, start, 0u, (size_t)(cells + 1),
                                           rocprim::plus<uint32_t>(), st));
 
-        LRC64_HIP(dispatch_knn(n, st, pts, off, grids, base, start, (int)k, avg));
+        LRC_HIP(dispatch_knn(n, st, pts, off, grids, base, start, (int)k, avg));
         const dim3 og(kRedBlocks, std::min(S, kMaxRowsY));
         const dim3 fg(std::min(S, kMaxRowsY));
         hipLaunchKernelGGL(ob_sum_kernel, og, dim3(kBlock), 0, st, (const double*)avg, (const uint64_t*)off, S, (int)k,
@@ -449,8 +447,8 @@ int lrc_object_boxes_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, cons
                            (int)k, 1, std_ratio, stats);
         hipLaunchKernelGGL(ob_keep_kernel, dim3(nblk), dim3(kBlock), 0, st, (const double*)avg, (const uint32_t*)seg,
                            (const uint64_t*)off, n, (int)k, (const double*)stats, flag, d_out_keep);
-        LRC64_HIP(hipGetLastError());
-        LRC64_HIP(rocprim::exclusive_scan(tmp, tmp_flag, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        LRC_HIP(hipGetLastError());
+        LRC_HIP(rocprim::exclusive_scan(tmp, tmp_flag, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
         if (d_out_kept)
             hipLaunchKernelGGL(ob_compact_kernel, dim3(nblk), dim3(kBlock), 0, st, n, (const uint32_t*)flag,
                                (const uint32_t*)pos, d_out_kept);
@@ -460,16 +458,16 @@ int lrc_object_boxes_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, cons
                            (const unsigned long long*)zrow,
                            (const uint32_t*)flag, (const uint32_t*)pos, (const unsigned long long*)kkeys,
                            (const double*)stats, boxes);
-        LRC64_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
     } else {
         // every object is empty: the box kernel reads no row
         hipLaunchKernelGGL(ob_box_kernel, dim3(sblk), dim3(kBlock), 0, st, d_points3, (const uint64_t*)off, S, (int)k,
                            (const unsigned long long*)zrow, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const unsigned long long*)kkeys,
                            (const double*)stats, boxes);
-        LRC64_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
     }
-    LRC64_HIP(hipMemcpyAsync(out_boxes, boxes, (size_t)S * sizeof(lrc_objbox), hipMemcpyDeviceToHost, st));
-    LRC64_HIP(hipStreamSynchronize(st));
+    LRC_HIP(hipMemcpyAsync(out_boxes, boxes, (size_t)S * sizeof(lrc_objbox), hipMemcpyDeviceToHost, st));
+    LRC_HIP(hipStreamSynchronize(st));
     return LRC_OK;
 }
 
@@ -480,7 +478,7 @@ int lrc_object_boxes(lrc_ctx* ctx, const double* points3, uint64_t n, const uint
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_object_boxes: NULL argument");
     if (int rc = check_args("lrc_object_boxes", n, offsets, num_objects, k, std_ratio)) return rc;
     if (num_objects == 0) return LRC_OK;
-    LRC64_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC_HIP(hipSetDevice(ctx->device));
     double *d_p = nullptr, *d_avg = nullptr;
     uint32_t* d_kept = nullptr;
     uint8_t* d_keep = nullptr;

@@ -11,25 +11,12 @@
 #include <new>
 #include <string>
 
-#include "../../include/lidarcast.h"
-
-extern "C" int lrc_internal_fail(int code, const char* msg);
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
+#include "lrc_internal.h"
 
 namespace {
 
 constexpr int kQ = 64;       // positions per block
 constexpr int kVPT = 8;      // vertices per thread
-
-#define O_HIP(call)                                                                             \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
 
 __global__ __launch_bounds__(256) void occupancy_kernel(const double* verts, uint64_t V, const double* pts,
                                                         uint64_t Q, double half, uint32_t* flags) {
@@ -59,11 +46,6 @@ __global__ __launch_bounds__(256) void occupancy_kernel(const double* verts, uin
     if (threadIdx.x < nq && s_hit[threadIdx.x]) atomicOr(&flags[q0 + threadIdx.x], 1u);
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 struct lrc_occ {
@@ -88,7 +70,7 @@ int lrc_occ_create(lrc_ctx* ctx, const double* verts3, uint64_t V, lrc_occ** out
     if (!ctx || (V && !verts3)) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_occ_create: NULL argument");
     lrc_occ* o = new (std::nothrow) lrc_occ();
     if (!o) return lrc_internal_fail(LRC_ERR_OOM, "lrc_occ_create: out of host memory");
-    o->device = lrc_internal_ctx_device(ctx);
+    o->device = ctx->device;
     o->V = V;
     if (hipSetDevice(o->device) != hipSuccess) { delete o; return lrc_internal_fail(LRC_ERR_HIP, "hipSetDevice failed"); }
     if (V) {
@@ -110,18 +92,18 @@ int lrc_occ_query(lrc_occ* occ, const double* points3, uint64_t Q, double half, 
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_occ_query: NULL argument");
     if (Q == 0) return LRC_OK;
     if (occ->V == 0) { for (uint64_t i = 0; i < Q; ++i) out_flags[i] = 0; return LRC_OK; }
-    O_HIP(hipSetDevice(occ->device));
+    LRC_HIP(hipSetDevice(occ->device));
     Buf dp, df;
-    O_HIP(hipMalloc(&dp.p, Q * 24));
-    O_HIP(hipMalloc(&df.p, Q * 4));
-    O_HIP(hipMemcpy(dp.p, points3, Q * 24, hipMemcpyHostToDevice));
-    O_HIP(hipMemset(df.p, 0, Q * 4));
+    LRC_HIP(hipMalloc(&dp.p, Q * 24));
+    LRC_HIP(hipMalloc(&df.p, Q * 4));
+    LRC_HIP(hipMemcpy(dp.p, points3, Q * 24, hipMemcpyHostToDevice));
+    LRC_HIP(hipMemset(df.p, 0, Q * 4));
     const uint64_t gx = (occ->V + 256ull * kVPT - 1) / (256ull * kVPT), gy = (Q + kQ - 1) / kQ;
     if (gx > 0x7FFFFFFFull || gy > 65535ull) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_occ_query: too large");
     hipLaunchKernelGGL(occupancy_kernel, dim3((uint32_t)gx, (uint32_t)gy), dim3(256), 0, nullptr,
                        (const double*)occ->d_verts, occ->V, (const double*)dp.p, Q, half, (uint32_t*)df.p);
-    O_HIP(hipGetLastError());
-    O_HIP(hipDeviceSynchronize());
+    LRC_HIP(hipGetLastError());
+    LRC_HIP(hipDeviceSynchronize());
     uint32_t* tmp = new (std::nothrow) uint32_t[Q];
     if (!tmp) return lrc_internal_fail(LRC_ERR_OOM, "lrc_occ_query: out of host memory");
     hipError_t e = hipMemcpy(tmp, df.p, Q * 4, hipMemcpyDeviceToHost);

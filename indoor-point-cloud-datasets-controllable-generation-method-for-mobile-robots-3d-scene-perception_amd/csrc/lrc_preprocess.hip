@@ -34,8 +34,6 @@
 
 #include "lrc_knn64.h"
 
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
-
 namespace {
 
 constexpr uint32_t kTie = 0x80000000u; // walk B key bit: d2 == D (indices are < 2^31)
@@ -435,18 +433,18 @@ int build_grid(const double* p, uint64_t m, double cell_size, int per_cell, hipS
     uint32_t* bad;
     {
         void* q;
-        LRC64_HIP(arena.get(align256(nb * 6 * 8) + 256, &q));
+        LRC_HIP(arena.get(align256(nb * 6 * 8) + 256, &q));
         part = (double*)q;
         bad = (uint32_t*)((char*)q + align256(nb * 6 * 8));
     }
-    LRC64_HIP(hipMemsetAsync(bad, 0, 4, st));
+    LRC_HIP(hipMemsetAsync(bad, 0, 4, st));
     hipLaunchKernelGGL(pp_bounds_kernel, dim3(nb), dim3(kBlock), 0, st, p, m, part, bad);
-    LRC64_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     std::vector<double> h_part((size_t)nb * 6);
     uint32_t h_bad = 0;
-    LRC64_HIP(hipMemcpyAsync(h_part.data(), part, h_part.size() * 8, hipMemcpyDeviceToHost, st));
-    LRC64_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
-    LRC64_HIP(hipStreamSynchronize(st));
+    LRC_HIP(hipMemcpyAsync(h_part.data(), part, h_part.size() * 8, hipMemcpyDeviceToHost, st));
+    LRC_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
+    LRC_HIP(hipStreamSynchronize(st));
     if (h_bad) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_cloud_preprocess: non-finite coordinate");
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (uint32_t b = 0; b < nb; ++b)
@@ -491,7 +489,7 @@ int build_grid(const double* p, uint64_t m, double cell_size, int per_cell, hipS
         const size_t sz = align256(m * 4), o_cnt = 4 * sz, o_start = o_cnt + align256((cells + 1) * 4),
                      o_pts = o_start + align256((cells + 1) * 4), total = o_pts + align256(m * sizeof(SPt));
         void* q;
-        LRC64_HIP(arena.get(total, &q));
+        LRC_HIP(arena.get(total, &q));
         char* c = (char*)q;
         keys_a = (uint32_t*)c; keys_b = (uint32_t*)(c + sz); vals_a = (uint32_t*)(c + 2 * sz);
         vals_b = (uint32_t*)(c + 3 * sz); counts = (uint32_t*)(c + o_cnt); start = (uint32_t*)(c + o_start);
@@ -499,18 +497,18 @@ int build_grid(const double* p, uint64_t m, double cell_size, int per_cell, hipS
     }
     const uint32_t mblk = (uint32_t)((m + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(pp_key_kernel, dim3(mblk), dim3(kBlock), 0, st, p, m, g, keys_a, vals_a);
-    LRC64_HIP(hipGetLastError());
-    LRC64_HIP(hipMemsetAsync(counts, 0, (cells + 1) * 4, st));
+    LRC_HIP(hipGetLastError());
+    LRC_HIP(hipMemsetAsync(counts, 0, (cells + 1) * 4, st));
     const int end_bit = std::max(1, bit_width(cells));
     size_t tmp_sort = 0, tmp_scan = 0;
-    LRC64_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, end_bit, st));
-    LRC64_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, counts, start, 0u, (size_t)(cells + 1), rocprim::plus<uint32_t>(), st));
+    LRC_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, end_bit, st));
+    LRC_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, counts, start, 0u, (size_t)(cells + 1), rocprim::plus<uint32_t>(), st));
     void* tmp;
-    LRC64_HIP(arena.get(std::max(tmp_sort, tmp_scan), &tmp));
-    LRC64_HIP(rocprim::radix_sort_pairs(tmp, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, end_bit, st));
+    LRC_HIP(arena.get(std::max(tmp_sort, tmp_scan), &tmp));
+    LRC_HIP(rocprim::radix_sort_pairs(tmp, tmp_sort, keys_a, keys_b, vals_a, vals_b, (size_t)m, 0, end_bit, st));
     hipLaunchKernelGGL(pp_gather_kernel, dim3(mblk), dim3(kBlock), 0, st, p, keys_b, vals_b, m, counts, pts);
-    LRC64_HIP(hipGetLastError());
-    LRC64_HIP(rocprim::exclusive_scan(tmp, tmp_scan, counts, start, 0u, (size_t)(cells + 1), rocprim::plus<uint32_t>(), st));
+    LRC_HIP(hipGetLastError());
+    LRC_HIP(rocprim::exclusive_scan(tmp, tmp_scan, counts, start, 0u, (size_t)(cells + 1), rocprim::plus<uint32_t>(), st));
     *out_g = g;
     *out_pts = pts;
     *out_start = start;
@@ -548,7 +546,7 @@ int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, 
     if (out_stats2) { out_stats2[0] = 0.0; out_stats2[1] = INFINITY; }
     if (int rc = check_opts(n, opts)) return rc;
     if (n == 0) return LRC_OK;
-    LRC64_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC_HIP(hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     Arena arena(st);
     const int per_cell = std::max(opts->remove_outliers ? (int)opts->nb_neighbors : 1,
@@ -571,39 +569,39 @@ int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, 
                          o_flag = o_stats + 256, o_pos = o_flag + align256(n * 4), o_pk = o_pos + align256(n * 4),
                          total = o_pk + (opts->estimate_normals ? align256(n * 24) : 0);
             void* q;
-            LRC64_HIP(arena.get(total, &q));
+            LRC_HIP(arena.get(total, &q));
             char* c = (char*)q;
             avg = (double*)c; part = (double*)(c + o_part); stats = (double*)(c + o_stats);
             flag = (uint32_t*)(c + o_flag); pos = (uint32_t*)(c + o_pos); pkb = (double*)(c + o_pk);
         }
-        LRC64_HIP(dispatch_knn(n, st, pts, g, start, (int)opts->nb_neighbors, avg));
+        LRC_HIP(dispatch_knn(n, st, pts, g, start, (int)opts->nb_neighbors, avg));
         hipLaunchKernelGGL(pp_sum_kernel, dim3(kRedBlocks), dim3(kBlock), 0, st, avg, n, (const double*)nullptr, part);
         hipLaunchKernelGGL(pp_final_kernel, dim3(1), dim3(kRedBlocks), 0, st, part, n, 0, opts->std_ratio, stats);
         hipLaunchKernelGGL(pp_sum_kernel, dim3(kRedBlocks), dim3(kBlock), 0, st, avg, n, (const double*)stats, part);
         hipLaunchKernelGGL(pp_final_kernel, dim3(1), dim3(kRedBlocks), 0, st, part, n, 1, opts->std_ratio, stats);
         hipLaunchKernelGGL(pp_keep_kernel, dim3(nblk), dim3(kBlock), 0, st, avg, n, stats, flag);
-        LRC64_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
         size_t tmp_scan = 0;
-        LRC64_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        LRC_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
         void* tmp;
-        LRC64_HIP(arena.get(tmp_scan, &tmp));
-        LRC64_HIP(rocprim::exclusive_scan(tmp, tmp_scan, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        LRC_HIP(arena.get(tmp_scan, &tmp));
+        LRC_HIP(rocprim::exclusive_scan(tmp, tmp_scan, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
         hipLaunchKernelGGL(pp_compact_kernel, dim3(nblk), dim3(kBlock), 0, st, d_points3, n, flag, pos, d_out_kept,
                            opts->estimate_normals ? pkb : nullptr);
-        LRC64_HIP(hipGetLastError());
-        if (d_out_avg) LRC64_HIP(hipMemcpyAsync(d_out_avg, avg, n * 8, hipMemcpyDeviceToDevice, st));
+        LRC_HIP(hipGetLastError());
+        if (d_out_avg) LRC_HIP(hipMemcpyAsync(d_out_avg, avg, n * 8, hipMemcpyDeviceToDevice, st));
         uint32_t last[2];
         double h_stats[2];
-        LRC64_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        LRC64_HIP(hipMemcpyAsync(&last[1], flag + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        LRC64_HIP(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, st));
-        LRC64_HIP(hipStreamSynchronize(st));
+        LRC_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        LRC_HIP(hipMemcpyAsync(&last[1], flag + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        LRC_HIP(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, st));
+        LRC_HIP(hipStreamSynchronize(st));
         m = (uint64_t)last[0] + last[1];
         if (out_stats2) { out_stats2[0] = h_stats[0]; out_stats2[1] = h_stats[1]; }
         pk = pkb;
     } else {
         hipLaunchKernelGGL(pp_fill_kernel, dim3(nblk), dim3(kBlock), 0, st, n, d_out_kept, d_out_avg);
-        LRC64_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
     }
 
     if (opts->estimate_normals && m > 0) {
@@ -612,11 +610,11 @@ int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, 
             if (int rc = build_grid(pk, m, opts->cell_size, per_cell, st, arena, &g, &pts, &start)) return rc;
         }
         void* nbr;                                    // max_nn neighbour keys per kept row
-        LRC64_HIP(arena.get(m * opts->max_nn * 4, &nbr));
-        LRC64_HIP(dispatch_normal(m, st, pts, pk, g, start, (int)opts->max_nn, opts->radius, (uint32_t*)nbr, d_out_normals3,
+        LRC_HIP(arena.get(m * opts->max_nn * 4, &nbr));
+        LRC_HIP(dispatch_normal(m, st, pts, pk, g, start, (int)opts->max_nn, opts->radius, (uint32_t*)nbr, d_out_normals3,
                                d_out_nn_count));
     }
-    LRC64_HIP(hipStreamSynchronize(st));
+    LRC_HIP(hipStreamSynchronize(st));
     *out_num_kept = m;
     return LRC_OK;
 }
@@ -630,7 +628,7 @@ int lrc_cloud_preprocess(lrc_ctx* ctx, const double* points3, uint64_t n, const 
     if (out_stats2) { out_stats2[0] = 0.0; out_stats2[1] = INFINITY; }
     if (int rc = check_opts(n, opts)) return rc;
     if (n == 0) return LRC_OK;
-    LRC64_HIP(hipSetDevice(lrc_internal_ctx_device(ctx)));
+    LRC_HIP(hipSetDevice(ctx->device));
     const bool normals = opts->estimate_normals != 0;
     double *d_p = nullptr, *d_normals = nullptr, *d_avg = nullptr;
     uint32_t* d_kept = nullptr;

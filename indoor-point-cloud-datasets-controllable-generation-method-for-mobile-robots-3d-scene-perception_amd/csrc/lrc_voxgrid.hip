@@ -38,30 +38,16 @@
 #include <new>
 #include <string>
 
-#include "../../include/lidarcast.h"
+#include "lrc_internal.h"
 #include "lrc_device.h"
-
-extern "C" int lrc_internal_fail(int code, const char* msg);
-extern "C" int lrc_internal_ctx_device(const lrc_ctx* ctx);
 
 namespace {
 
 using namespace lrcdev;
 
-constexpr int kBlock = 256;
 constexpr int64_t kMaxWalk = 1ll << 24;                      // steps per ray (the Manhattan distance) refused
 constexpr uint64_t kMaxKeys = 0x7FFFFFFFull;                // reserved key slots between resets
 constexpr double kCoordLimit = 2147483648.0;                // voxel coordinates in [-2^31, 2^31)
-
-#define V_HIP(call)                                                                             \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                            \
-            return lrc_internal_fail(e__ == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP,    \
-                                     (std::string(#call) + ": " + hipGetErrorString(e__)).c_str()); \
-        }                                                                                       \
-    } while (0)
 
 struct GridDesc {
     double gx, gy, gz, s;
@@ -310,8 +296,6 @@ __global__ void counts_kernel(const uint32_t* __restrict__ pos, uint64_t R, uint
     out[5] = acc[kAccKeys];
 }
 
-uint64_t blocks_of(uint64_t n, uint64_t per) { return (n + per - 1) / per; }
-
 }  // namespace
 
 struct lrc_voxgrid {
@@ -365,25 +349,25 @@ uint32_t key_end_bit(uint64_t V) {                   // V < 2^b: every valid key
 
 int ensure_fin(lrc_voxgrid* v, uint64_t R, hipStream_t st) {
     if (R <= v->fin_cap) return LRC_OK;
-    V_HIP(hipStreamSynchronize(st));                  // the old scratch may still be read by enqueued work
+    LRC_HIP(hipStreamSynchronize(st));                  // the old scratch may still be read by enqueued work
     release_fin(v);
     const uint64_t cap = R;
-    V_HIP(hipMalloc((void**)&v->d_sorted, cap * 8));
-    V_HIP(hipMalloc((void**)&v->d_ukeys, cap * 8));
-    V_HIP(hipMalloc((void**)&v->d_counts, cap * 4));
-    V_HIP(hipMalloc((void**)&v->d_flag, (cap + 1) * 4));
-    V_HIP(hipMalloc((void**)&v->d_pos, (cap + 1) * 4));
-    V_HIP(hipMalloc((void**)&v->d_nruns, 4));
+    LRC_HIP(hipMalloc((void**)&v->d_sorted, cap * 8));
+    LRC_HIP(hipMalloc((void**)&v->d_ukeys, cap * 8));
+    LRC_HIP(hipMalloc((void**)&v->d_counts, cap * 4));
+    LRC_HIP(hipMalloc((void**)&v->d_flag, (cap + 1) * 4));
+    LRC_HIP(hipMalloc((void**)&v->d_pos, (cap + 1) * 4));
+    LRC_HIP(hipMalloc((void**)&v->d_nruns, 4));
     size_t a = 0, b = 0, c = 0;
     const uint32_t eb = key_end_bit(v->V);
-    V_HIP(rocprim::radix_sort_keys(nullptr, a, (const unsigned long long*)v->d_keys, v->d_sorted, (size_t)cap, 0, eb, st));
-    V_HIP(rocprim::run_length_encode(nullptr, b, (const unsigned long long*)v->d_sorted, (unsigned int)cap, v->d_ukeys,
+    LRC_HIP(rocprim::radix_sort_keys(nullptr, a, (const unsigned long long*)v->d_keys, v->d_sorted, (size_t)cap, 0, eb, st));
+    LRC_HIP(rocprim::run_length_encode(nullptr, b, (const unsigned long long*)v->d_sorted, (unsigned int)cap, v->d_ukeys,
                                      v->d_counts, v->d_nruns, st));
-    V_HIP(rocprim::exclusive_scan(nullptr, c, (const uint32_t*)v->d_flag, v->d_pos, 0u, (size_t)(cap + 1),
+    LRC_HIP(rocprim::exclusive_scan(nullptr, c, (const uint32_t*)v->d_flag, v->d_pos, 0u, (size_t)(cap + 1),
                                   rocprim::plus<uint32_t>(), st));
     v->tmp_bytes = a > b ? a : b;
     if (c > v->tmp_bytes) v->tmp_bytes = c;
-    V_HIP(hipMalloc(&v->d_tmp, v->tmp_bytes ? v->tmp_bytes : 1));
+    LRC_HIP(hipMalloc(&v->d_tmp, v->tmp_bytes ? v->tmp_bytes : 1));
     v->fin_cap = cap;
     return LRC_OK;
 }
@@ -420,7 +404,7 @@ int lrc_voxgrid_create(lrc_ctx* ctx, const double* origin3, double voxel_size, c
     }
     lrc_voxgrid* v = new (std::nothrow) lrc_voxgrid();
     if (!v) return lrc_internal_fail(LRC_ERR_OOM, "lrc_voxgrid_create: out of host memory");
-    v->device = lrc_internal_ctx_device(ctx);
+    v->device = ctx->device;
     v->g.gx = origin3[0];
     v->g.gy = origin3[1];
     v->g.gz = origin3[2];
@@ -432,11 +416,11 @@ int lrc_voxgrid_create(lrc_ctx* ctx, const double* origin3, double voxel_size, c
     v->V = V;
     v->W = (V + 31) / 32;
     auto run = [&]() -> int {
-        V_HIP(hipSetDevice(v->device));
-        V_HIP(hipMalloc((void**)&v->d_bits, v->W * 4));
-        V_HIP(hipMalloc((void**)&v->d_acc, kAccWords * 8));
-        V_HIP(hipMemset(v->d_bits, 0, v->W * 4));
-        V_HIP(hipMemset(v->d_acc, 0, kAccWords * 8));
+        LRC_HIP(hipSetDevice(v->device));
+        LRC_HIP(hipMalloc((void**)&v->d_bits, v->W * 4));
+        LRC_HIP(hipMalloc((void**)&v->d_acc, kAccWords * 8));
+        LRC_HIP(hipMemset(v->d_bits, 0, v->W * 4));
+        LRC_HIP(hipMemset(v->d_acc, 0, kAccWords * 8));
         return LRC_OK;
     };
     const int rc = run();
@@ -467,9 +451,9 @@ int lrc_voxgrid_get_info(const lrc_voxgrid* vg, lrc_voxgrid_info* out) {
 int lrc_voxgrid_reset(lrc_voxgrid* vg, void* stream) {
     if (!vg) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_voxgrid_reset: NULL argument");
     const hipStream_t st = (hipStream_t)stream;
-    V_HIP(hipSetDevice(vg->device));
-    V_HIP(hipMemsetAsync(vg->d_bits, 0, vg->W * 4, st));
-    V_HIP(hipMemsetAsync(vg->d_acc, 0, kAccWords * 8, st));
+    LRC_HIP(hipSetDevice(vg->device));
+    LRC_HIP(hipMemsetAsync(vg->d_bits, 0, vg->W * 4, st));
+    LRC_HIP(hipMemsetAsync(vg->d_acc, 0, kAccWords * 8, st));
     vg->reserved = 0;
     return LRC_OK;
 }
@@ -485,32 +469,32 @@ int lrc_voxgrid_accumulate_dev(lrc_voxgrid* vg, const double* d_poses16, uint64_
                                  "lrc_voxgrid_accumulate_dev: more than 2^31 - 1 rays between resets");
     const uint64_t total = num_poses * rays_per_pose;
     const hipStream_t st = (hipStream_t)stream;
-    V_HIP(hipSetDevice(vg->device));
+    LRC_HIP(hipSetDevice(vg->device));
     const uint64_t need = vg->reserved + total;
     if (need > vg->key_cap) {                            // grow: no return is ever dropped
         uint64_t cap = vg->key_cap * 2;
         if (cap < need) cap = need;
         if (cap > kMaxKeys) cap = kMaxKeys;
         unsigned long long* nk = nullptr;
-        V_HIP(hipMalloc((void**)&nk, cap * 8));
+        LRC_HIP(hipMalloc((void**)&nk, cap * 8));
         if (vg->reserved) {
             hipError_t e = hipMemcpyAsync(nk, vg->d_keys, vg->reserved * 8, hipMemcpyDeviceToDevice, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) {
                 (void)hipFree(nk);
-                V_HIP(e);
+                LRC_HIP(e);
             }
         }
-        if (vg->d_keys) V_HIP(hipFree(vg->d_keys));
+        if (vg->d_keys) LRC_HIP(hipFree(vg->d_keys));
         vg->d_keys = nk;
         vg->key_cap = cap;
     }
-    V_HIP(hipMemsetAsync(vg->d_keys + vg->reserved, 0xFF, total * 8, st));   // unfilled slots sort last
+    LRC_HIP(hipMemsetAsync(vg->d_keys + vg->reserved, 0xFF, total * 8, st));   // unfilled slots sort last
     vg->reserved = need;
     hipLaunchKernelGGL(walk_kernel, dim3((uint32_t)blocks_of(total, kBlock)), dim3(kBlock), 0, st, d_poses16, d_dirs3,
                        (const uint2*)d_t_label, rays_per_pose, total, vg->g, vg->d_bits, vg->d_keys, vg->reserved,
                        vg->d_acc);
-    V_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 
@@ -525,8 +509,8 @@ int lrc_voxgrid_finalize_dev(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* d_
     if (capacity < bound)
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_voxgrid_finalize_dev: capacity below sparse_bound");
     const hipStream_t st = (hipStream_t)stream;
-    V_HIP(hipSetDevice(vg->device));
-    V_HIP(hipMemsetAsync(vg->d_acc + kAccFree, 0, 3 * 8, st));
+    LRC_HIP(hipSetDevice(vg->device));
+    LRC_HIP(hipMemsetAsync(vg->d_acc + kAccFree, 0, 3 * 8, st));
     if (d_state)
         hipLaunchKernelGGL(dense_kernel, dim3((uint32_t)blocks_of(vg->V, kBlock)), dim3(kBlock), 0, st,
                            (const uint32_t*)vg->d_bits, vg->g.V, d_state);
@@ -534,16 +518,16 @@ int lrc_voxgrid_finalize_dev(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* d_
         int rc = ensure_fin(vg, R, st);
         if (rc != LRC_OK) return rc;
         size_t tb = vg->tmp_bytes;
-        V_HIP(rocprim::radix_sort_keys(vg->d_tmp, tb, (const unsigned long long*)vg->d_keys, vg->d_sorted, (size_t)R, 0,
+        LRC_HIP(rocprim::radix_sort_keys(vg->d_tmp, tb, (const unsigned long long*)vg->d_keys, vg->d_sorted, (size_t)R, 0,
                                        key_end_bit(vg->V), st));
         tb = vg->tmp_bytes;
-        V_HIP(rocprim::run_length_encode(vg->d_tmp, tb, (const unsigned long long*)vg->d_sorted, (unsigned int)R,
+        LRC_HIP(rocprim::run_length_encode(vg->d_tmp, tb, (const unsigned long long*)vg->d_sorted, (unsigned int)R,
                                          vg->d_ukeys, vg->d_counts, vg->d_nruns, st));
         hipLaunchKernelGGL(head_kernel, dim3((uint32_t)blocks_of(R + 1, kBlock)), dim3(kBlock), 0, st,
                            (const unsigned long long*)vg->d_ukeys, (const uint32_t*)vg->d_nruns, R, vg->g.V, vg->d_flag);
-        V_HIP(hipGetLastError());
+        LRC_HIP(hipGetLastError());
         tb = vg->tmp_bytes;
-        V_HIP(rocprim::exclusive_scan(vg->d_tmp, tb, (const uint32_t*)vg->d_flag, vg->d_pos, 0u, (size_t)(R + 1),
+        LRC_HIP(rocprim::exclusive_scan(vg->d_tmp, tb, (const uint32_t*)vg->d_flag, vg->d_pos, 0u, (size_t)(R + 1),
                                       rocprim::plus<uint32_t>(), st));
         hipLaunchKernelGGL(vote_kernel, dim3((uint32_t)blocks_of(R, kBlock)), dim3(kBlock), 0, st,
                            (const unsigned long long*)vg->d_ukeys, (const uint32_t*)vg->d_counts,
@@ -554,7 +538,7 @@ int lrc_voxgrid_finalize_dev(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* d_
                        (const uint32_t*)vg->d_bits, vg->W, vg->g.V, vg->d_acc);
     hipLaunchKernelGGL(counts_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)vg->d_pos, R, vg->V,
                        (const unsigned long long*)vg->d_acc, d_counts6);
-    V_HIP(hipGetLastError());
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 
@@ -566,12 +550,12 @@ int lrc_voxgrid_finalize(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* out_id
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_voxgrid_finalize: NULL sparse output");
     if (capacity < bound)
         return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_voxgrid_finalize: capacity below sparse_bound");
-    V_HIP(hipSetDevice(vg->device));
-    V_HIP(hipDeviceSynchronize());                      // work the caller enqueued on other streams
+    LRC_HIP(hipSetDevice(vg->device));
+    LRC_HIP(hipDeviceSynchronize());                      // work the caller enqueued on other streams
     void* buf = nullptr;
     const uint64_t n = bound ? bound : 1;
     const size_t bytes = 6 * 8 + n * 12 + (out_state ? vg->V : 0);
-    V_HIP(hipMalloc(&buf, bytes));
+    LRC_HIP(hipMalloc(&buf, bytes));
     struct Free {
         void* p;
         ~Free() { (void)hipFree(p); }
@@ -585,7 +569,7 @@ int lrc_voxgrid_finalize(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* out_id
     int rc = lrc_voxgrid_finalize_dev(vg, min_returns, di, ds, dn, dr, n, dst, dc, nullptr);
     if (rc != LRC_OK) return rc;
     uint64_t c[6];
-    V_HIP(hipMemcpy(c, dc, sizeof(c), hipMemcpyDeviceToHost));     // the one synchronisation
+    LRC_HIP(hipMemcpy(c, dc, sizeof(c), hipMemcpyDeviceToHost));     // the one synchronisation
     out_counts->num_sparse = c[0];
     out_counts->num_free = c[1];
     out_counts->num_occupied = c[2];
@@ -593,20 +577,20 @@ int lrc_voxgrid_finalize(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* out_id
     out_counts->rejected_rays = c[4];
     out_counts->returns = c[5];
     if (c[0]) {
-        V_HIP(hipMemcpy(out_idx, di, c[0] * 4, hipMemcpyDeviceToHost));
-        V_HIP(hipMemcpy(out_sem, ds, c[0] * 2, hipMemcpyDeviceToHost));
-        V_HIP(hipMemcpy(out_ins, dn, c[0] * 2, hipMemcpyDeviceToHost));
-        V_HIP(hipMemcpy(out_returns, dr, c[0] * 4, hipMemcpyDeviceToHost));
+        LRC_HIP(hipMemcpy(out_idx, di, c[0] * 4, hipMemcpyDeviceToHost));
+        LRC_HIP(hipMemcpy(out_sem, ds, c[0] * 2, hipMemcpyDeviceToHost));
+        LRC_HIP(hipMemcpy(out_ins, dn, c[0] * 2, hipMemcpyDeviceToHost));
+        LRC_HIP(hipMemcpy(out_returns, dr, c[0] * 4, hipMemcpyDeviceToHost));
     }
-    if (out_state) V_HIP(hipMemcpy(out_state, dst, vg->V, hipMemcpyDeviceToHost));
+    if (out_state) LRC_HIP(hipMemcpy(out_state, dst, vg->V, hipMemcpyDeviceToHost));
     return LRC_OK;
 }
 
 int lrc_voxgrid_export_bits(lrc_voxgrid* vg, uint32_t* out_bits) {
     if (!vg || !out_bits) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_voxgrid_export_bits: NULL argument");
-    V_HIP(hipSetDevice(vg->device));
-    V_HIP(hipDeviceSynchronize());
-    V_HIP(hipMemcpy(out_bits, vg->d_bits, vg->W * 4, hipMemcpyDeviceToHost));
+    LRC_HIP(hipSetDevice(vg->device));
+    LRC_HIP(hipDeviceSynchronize());
+    LRC_HIP(hipMemcpy(out_bits, vg->d_bits, vg->W * 4, hipMemcpyDeviceToHost));
     return LRC_OK;
 }
 

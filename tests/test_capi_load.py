@@ -22,6 +22,23 @@ def test_header_and_library_agree():
     assert os.path.dirname(lidarcast.LIB_PATH).endswith("_amd")          # in-tree build
 
 
+def test_libraries_export_only_the_api():
+    """Every defined dynamic symbol of both libraries is an lrc_ name, a mangled C++ name or the HIP compiler's unit id: a
+    helper that leaks out unmangled (env_int, frames_finish, ...) could be interposed by another library's symbol."""
+    import subprocess
+    import __graft_entry__ as entry
+    from lidarcast import _capi
+    for lib in (entry.LIB, entry.LAB_LIB):
+        r = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        names = [line.split()[-1] for line in r.stdout.splitlines() if line.strip()]
+        assert names, lib
+        stray = sorted(n for n in names if not re.match(r"lrc_|_Z|__hip_cuid_", n))
+        assert not stray, (os.path.basename(lib), stray)
+        lost = sorted(set(_capi.SYMBOLS) - set(names))                     # ... and hiding must not take an API name along
+        assert not lost, (os.path.basename(lib), lost)
+
+
 def test_struct_layouts_match_header():
     import ctypes as C
     from lidarcast._capi import LrcCompactIO, LrcFrames, LrcHits, LrcSceneInfo
