@@ -453,6 +453,55 @@ int lrc_table_set_fire(lrc_table* table, const double* fire, uint64_t rays_per_p
 int lrc_scan_sweeps_compact(lrc_scene* scene, const double* motion24, uint64_t num_poses, const lrc_table* table,
                             double max_range, const lrc_frames* out, uint64_t capacity, uint64_t* out_total);
 
+/* ---- seeded sensor noise (opt-in) ------------------------------------------------------------
+ * A pose-batched scan whose range noise, angle jitter and dropout are drawn in the kernel, where the ray is made, from a
+ * counter-based generator: the noise of ray i of pose p is a pure function of (seed, first_frame + p, i).  It does not
+ * depend on call order or chunking, nothing is uploaded, and any frame can be scanned again with its exact noise (P = 6
+ * in one call = P = 2 and then P = 4 with first_frame + 2).  The reference declares range_noise_std, angle_noise_std and
+ * dropout_probability for the multi-line sensor and never applies them; this is the project's model:
+ *   words     Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85),
+ *             key = (seed lo, seed hi), counter = (i, frame lo, frame hi, 0), frame = first_frame + p in 64 bits.
+ *             w0: range, w1: azimuth jitter, w2: elevation jitter, w3: dropout.  rays_per_pose < 2^32.
+ *   normal    z of ONE word w: sign = w >> 31 (set: negative), r = w & 0x7FFFFFFF.  r < 128: |z| = B[23][0] (5.42).  Else
+ *             L = leading one of r (7..30), e = 30 - L, below = r - 2^L, c = below >> (L-6),
+ *             f = float32(below & (2^(L-6) - 1)) * 2^-(L-6), |z| = fmaf(f, D[e][c], B[e][c]) in float32, with
+ *             B[e][c] = float32(Phi^-1(1 - q/2)) at q = 2^-(e+1) (1 + c/64), D[e][c] = (next cell's B) - B[e][c] in float32
+ *             (behind c = 63 comes B[e-1][0]; 0 for e = 0).  |z - exact quantile| <= 4.6e-5 + rounding.  Integer and
+ *             float32 operations only: the same bits on the host (lrc_noise_draws) and in the kernel.
+ *   dropout   the ray is dropped iff w3 < min(floor(dropout * 2^32), 2^32 - 1): never cast, reported as a miss.
+ *   jitter    on the float64 table row (a, b, c) in the sensor frame, before the rotation into the world, one float64
+ *             operation per step: dp = angle_std*z(w1), dt = angle_std*z(w2), h = sqrt(a*a + b*b), ca = (c*a)/h,
+ *             cb = (c*b)/h, a1 = (a - dp*b) - dt*ca, b1 = (b + dp*a) - dt*cb, c1 = c + dt*h,
+ *             n = sqrt((a1*a1 + b1*b1) + c1*c1), row = (a1/n, b1/n, c1/n).  A row with h == 0 is left as it is.
+ *   range     t' = t + float32(range_std) * z(w0), a float32 multiply then an add; t' <= 0 drops the return; point, range
+ *             filter, min_range and incident angle use t' -- the semantics of lrc_scan_options.range_noise.
+ * A zero range_std, angle_std or dropout skips its step: the all-zero model returns the bytes of lrc_scan_poses_dev.
+ * Negative or non-finite standard deviations, dropout outside [0, 1) and rays_per_pose >= 2^32 fail with
+ * LRC_ERR_INVALID_ARG before any launch, and so does a call while a range_noise option is set (one noise source per
+ * call); min_range and incident_mode apply unchanged.
+ *   lrc_scan_noisy_dev      device pointers, fixed-stride records, as lrc_scan_poses_dev
+ *   lrc_scan_noisy_compact  host poses and a resident table: compacted in HBM exactly like lrc_scan_table_compact (same
+ *                           lrc_frames, counts, index, range_origin, per-pose statistics)
+ *   lrc_noise_draws         host, no GPU: the variates and the keep flags (1 = not dropped) of P x N rays; any output
+ *                           may be NULL
+ *   lrc_noise_table         host: the table in use, base B and slope D, entry [e*64 + c] */
+typedef struct lrc_noise {
+    uint64_t seed;
+    uint64_t first_frame;   /* frame id of pose 0 of the call */
+    double   range_std;     /* metres */
+    double   angle_std;     /* radians, azimuth and elevation alike */
+    double   dropout;       /* probability in [0, 1) */
+} lrc_noise;
+int lrc_scan_noisy_dev(lrc_scene* scene, const double* d_poses16, uint64_t num_poses, const double* d_dirs3,
+                       uint64_t rays_per_pose, double max_range, const lrc_noise* noise, const lrc_hits* d_out,
+                       void* stream);
+int lrc_scan_noisy_compact(lrc_scene* scene, const double* poses16, uint64_t num_poses, const lrc_table* table,
+                           double max_range, const lrc_noise* noise, const lrc_frames* out, uint64_t capacity,
+                           uint64_t* out_total);
+int lrc_noise_draws(const lrc_noise* noise, uint64_t num_poses, uint64_t rays_per_pose, float* z_range, float* z_az,
+                    float* z_el, uint8_t* keep);
+int lrc_noise_table(float* base1536, float* slope1536);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);
@@ -535,6 +584,7 @@ int lrc_debug_scan_stats(lrc_scene* scene, const double* poses16, uint64_t num_p
  *                  t' = t + noise (float32); t' <= 0 drops the return; point, range filter and incident
  *                  angle use t'.  Host entry points take a host array, _dev entry points a device array;
  *                  range_noise_len must equal the number of rays of the call.
+ *                  (Noise drawn in the kernel from a seed, with angle jitter and dropout: lrc_scan_noisy_dev.)
  *   incident_mode  0: reference (angle between centre->point and the vertical axis)
  *                  1: angle between the ray and the hit triangle's normal, acos(|d^.n|) in degrees */
 typedef struct lrc_scan_options {

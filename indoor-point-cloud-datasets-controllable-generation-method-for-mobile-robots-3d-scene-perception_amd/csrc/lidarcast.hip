@@ -172,6 +172,8 @@ struct TraceParams {
     // GEN = 4 (moving-sensor sweeps, lrc_scan_sweeps_*): (P,24) motion records and the (N) firing fractions of the table
     const double* motion24;
     const double* fire;
+    // GEN = 5 (seeded sensor noise, lrc_scan_noisy_*): generator parameters and the resident quantile table
+    lrcnoise::Params noise;
 };
 
 // workgroup -> tile remap: consecutive tiles land on the same XCD (blocks b, b+8, ... share an L2),
@@ -610,12 +612,13 @@ constexpr int kPreTiles = LRC_PRE_TILES;      // tiles per leading workgroup of 
 template <int I> struct IntTag { static constexpr int value = I; };
 
 // GEN: 0 = explicit rays, 1 = pose x direction table, 2 = pose x per-ray scan angles (dual-axis sensor, opt-in),
-//      4 = motion record x direction table x firing fractions (moving-sensor sweeps, opt-in; same ray order as 1)
+//      4 = motion record x direction table x firing fractions (moving-sensor sweeps, opt-in; same ray order as 1),
+//      5 = pose x direction table with seeded range noise, angle jitter and dropout drawn per ray (opt-in; same ray order as 1)
 // QN: 1 = walk the quantised node images (32-byte nodes for the per-lane fetches), 2 = walk their
 //     four-wide collapse (64-byte nodes, half the steps); a wave with a ray outside the bound the quantisation margin is
 //     proven for walks the float32 world-space nodes instead
 template <int GEN, int LEAFW, bool UNI, bool SPEC, bool STATS = false, int QN = 0>
-__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4)) ? 8 : 1) void trace_kernel(const TraceParams p) {
+__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4 || GEN == 5)) ? 8 : 1) void trace_kernel(const TraceParams p) {
     extern __shared__ int s_stack[];   // [stack depth][kTBlock]: one column per lane, conflict free
     const uint32_t tid = threadIdx.x;
     if (GEN == 1 && p.pre.blocks != 0u && p.pre.sharded != 0u) {
@@ -692,6 +695,11 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         const uint64_t pose = gid / p.rays_per_pose;
         const uint64_t i = gid - pose * p.rays_per_pose;
         gen_ray_sweep(p.motion24, p.dirs3, p.fire, pose, i, o, d);
+        pose32 = (uint32_t)pose;
+    } else if (GEN == 5) {
+        const uint64_t pose = gid / p.rays_per_pose;
+        const uint64_t i = gid - pose * p.rays_per_pose;
+        gen_ray_noisy(p.poses16, p.dirs3, p.noise, pose, i, o, d, cx, cy, cz, live);
         pose32 = (uint32_t)pose;
     } else {
         const float* r = p.rays6 + gid * 6;
@@ -1086,6 +1094,12 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         asm volatile("" : "+s"(F));
         M += (size_t)pose32 * 24;
         sweep_centre(M, F[gid_w - (uint64_t)pose32 * p.rays_per_pose], cx, cy, cz);
+    }
+    if (GEN == 5 && p.noise.range_std != 0.0f && best_slot != 0xFFFFFFFFu) {
+        // the range draw: the ray's Philox block is formed again here instead of z0 being held through the traversal; a
+        // non-positive range is no return
+        tbest = noisy_range(p.noise, p.noise.first_frame + pose32, (uint32_t)(gid_w - (uint64_t)pose32 * p.rays_per_pose), tbest);
+        if (!(tbest > 0.0f)) best_slot = 0xFFFFFFFFu;
     }
     write_back<GEN != 0, false, true>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot, best_label);
     if (STATS) {
@@ -1689,6 +1703,7 @@ int lrc_ctx_destroy(lrc_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_compact) if (e) (void)hipEventDestroy(e);
     if (ctx->chain_word) (void)hipFree(ctx->chain_word);
     if (ctx->stat_scratch) (void)hipFree(ctx->stat_scratch);
+    if (ctx->d_noise_tab) (void)hipFree(ctx->d_noise_tab);
     for (hipEvent_t e : ctx->compact_done) if (e) (void)hipEventDestroy(e);
     for (lrc_ctx::TileScratch* sc : {&ctx->compact_scratch[0], &ctx->compact_scratch[1], &ctx->compact_scratch[2],
                                      &ctx->compact_scratch[3], &ctx->cloud_scratch}) {
@@ -2124,7 +2139,7 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
         return 1;
     }
     const bool plain = leafw == kLeafW && uni && !spec && !(qn && wide);
-    if (plain || gen == 2 || gen == 4) return 1;
+    if (plain || gen == 2 || gen == 4 || gen == 5) return 1;
     const bool wide_only = qn && wide && leafw == kLeafW && uni && !spec;
     if (gen == 1) { if (wide_only) LRC_LAB(1, kLeafW, true, false, 2); else LRC_LAB_PICK(1); }
     else { if (wide_only) LRC_LAB(0, kLeafW, true, false, 2); else LRC_LAB_PICK(0); }
@@ -2136,7 +2151,7 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
 
 // One launch of the trace kernel over p.total rays.  gen: 0 explicit rays, 1 pose x direction table, 2 pose x scan angles,
 // 3 a grid scan (lrc_scan_grid_*: the per-ray kernel here; the packet kernel in the laboratory build), 4 moving-sensor sweeps
-// (motion record x direction table x firing fractions).
+// (motion record x direction table x firing fractions), 5 pose x direction table with seeded sensor noise (p.noise).
 static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, bool stats = false) {
     p.nodes = s->d_nodes;
     p.tris = s->d_tris;
@@ -2183,7 +2198,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     // is worth more than the balance: measured +1...+16 % for the striped order there, -1...-10 % on the cache-resident
     // scenes (profiles/r03_xcd_striping_sweep.txt).
     constexpr uint64_t kStripeSceneBytes = 192ull << 20;
-    if ((gen == 1 || gen == 4) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
+    if ((gen == 1 || gen == 4 || gen == 5) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
         const uint64_t tpp = p.rays_per_pose / 64;
         if (tpp % 16 == 0) {
             const uint64_t chunk = tpp / 16;
@@ -2232,6 +2247,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
         else return fail(LRC_ERR_INVALID_ARG, "traversal statistics are not available for the scan-angle generator");
     } else if (gen == 1) { if (qn) LRC_LAUNCH(1, false, 1); else LRC_LAUNCH(1, false, 0); }
     else if (gen == 4) { if (qn) LRC_LAUNCH(4, false, 1); else LRC_LAUNCH(4, false, 0); }
+    else if (gen == 5) { if (qn) LRC_LAUNCH(5, false, 1); else LRC_LAUNCH(5, false, 0); }
     else if (gen == 2) { if (qn) LRC_LAUNCH(2, false, 1); else LRC_LAUNCH(2, false, 0); }
     else { if (qn) LRC_LAUNCH(0, false, 1); else LRC_LAUNCH(0, false, 0); }
 #undef LRC_LAUNCH
@@ -2332,6 +2348,27 @@ int lrc_scan_sweeps_dev(lrc_scene* s, const double* d_motion24, uint64_t P, cons
     p.max_range = max_range;
     p.out = *d_out;
     return launch_trace(s, p, 4, (hipStream_t)stream);
+}
+
+int lrc_scan_noisy_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N, double max_range,
+                       const lrc_noise* noise, const lrc_hits* d_out, void* stream) {
+    if (!s || !d_out) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_dev: NULL scene or output");
+    if (P && N && (!d_poses16 || !d_dirs3))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_dev: poses16 or dirs3 is NULL");
+    if (s->opts.range_noise)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_dev: a range_noise option is set (one noise source per call)");
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    TraceParams p{};
+    int rc = noise_params(s->ctx, "lrc_scan_noisy_dev", noise, N, &p.noise);
+    if (rc) return rc;
+    p.poses16 = d_poses16;
+    p.dirs3 = d_dirs3;
+    p.rays_per_pose = N ? N : 1;
+    p.total = P * N;
+    p.has_center = 1;
+    p.max_range = max_range;
+    p.out = *d_out;
+    return launch_trace(s, p, 5, (hipStream_t)stream);
 }
 
 static int check_grid(const char* who, const lrc_grid* g, uint64_t N) {
@@ -3556,6 +3593,7 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
         TraceParams q = p;
         if (q.poses16) q.poses16 = p.poses16 + p0 * 16;
         if (q.motion24) q.motion24 = p.motion24 + p0 * 24;
+        q.noise.first_frame = p.noise.first_frame + p0;      // gen == 5: the chunk's first frame id
         if (q.angles2) q.angles2 = p.angles2 + r0 * 2;
         if (q.rays6) q.rays6 = p.rays6 + r0 * 6;
         if (q.seg_centers3) q.seg_centers3 = p.seg_centers3 + p0 * 3;
@@ -3787,6 +3825,37 @@ int lrc_scan_sweeps_compact(lrc_scene* s, const double* motion24, uint64_t P, co
     p.has_center = 1;
     p.max_range = max_range;
     return guard.done(frames_finish(s, p, 4, st, P, N, out, capacity, out_total));
+}
+
+int lrc_scan_noisy_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, double max_range,
+                           const lrc_noise* noise, const lrc_frames* out, uint64_t capacity, uint64_t* out_total) {
+    if (out_total) *out_total = 0;
+    if (!s || !out || !table) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_compact: NULL scene, table or output");
+    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_compact: table and scene belong to different contexts");
+    if (s->opts.range_noise)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_compact: a range_noise option is set (one noise source per call)");
+    const uint64_t N = table->n, n = P * N;
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    TraceParams p{};
+    int rc = noise_params(s->ctx, "lrc_scan_noisy_compact", noise, N, &p.noise);
+    if (rc) return rc;
+    if (!n) return LRC_OK;
+    if (!poses16 || !out->counts) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_compact: poses16 or counts is NULL");
+    SyncUnlessOk guard;
+    DevBuf dp;
+    if ((rc = ensure_streams(s->ctx))) return rc;
+    hipStream_t in = s->ctx->s_compute;       // inputs travel on the stream that consumes them
+    if ((rc = dp.get(s->ctx, kPoolPoses, P * 128))) return rc;
+    LRC_HIP(hipMemcpyAsync(dp.p, poses16, P * 128, hipMemcpyHostToDevice, in));
+    FrameStage st;
+    if ((rc = st.alloc(s->ctx, *out, P, n))) return rc;
+    p.poses16 = (const double*)dp.p;
+    p.dirs3 = table->d_dirs3;
+    p.rays_per_pose = N;
+    p.total = n;
+    p.has_center = 1;
+    p.max_range = max_range;
+    return guard.done(frames_finish(s, p, 5, st, P, N, out, capacity, out_total));
 }
 
 int lrc_scan_poses_compact(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,

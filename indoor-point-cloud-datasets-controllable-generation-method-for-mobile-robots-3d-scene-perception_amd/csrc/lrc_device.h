@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lrc_noise.h"
+
 namespace lrcdev {
 
 #define LRC_DI __device__ __forceinline__
@@ -253,6 +255,38 @@ LRC_DI void gen_ray_sweep(const double* motion24, const double* dirs3, const dou
     double cx, cy, cz;
     sweep_centre(M, s, cx, cy, cz);
     o.x = (float)cx; o.y = (float)cy; o.z = (float)cz;
+}
+
+// ---- seeded sensor noise (lrc_scan_noisy_*; include/lidarcast.h "seeded sensor noise") ----------
+// Ray (pose, i) of a noisy scan: gen_ray with the table row jittered in the sensor frame BEFORE the dgemm chain
+// (lrc_noise.h jitter_row; dp = angle_std * z(w1), dt = angle_std * z(w2), the float32 variates widened), and
+// live = false for a ray the dropout word drops (w3 < drop_thr): never cast, reported as a miss.  The words are the Philox
+// block of (seed, first_frame + pose, i).  Zero parameters skip their step (kernel arguments: wave-uniform), so a row passes
+// through bit for bit when angle_std == 0.
+LRC_DI void gen_ray_noisy(const double* poses16, const double* dirs3, const lrcnoise::Params& np, uint64_t pose, uint64_t i,
+                          V3& o, V3& d, double& cx, double& cy, double& cz, bool& live) {
+    const double* M = poses16 + pose * 16;
+    const double* dv = dirs3 + i * 3;
+    double a = dv[0], b = dv[1], c = dv[2];
+    if (np.angle_std != 0.0 || np.drop_thr != 0u) {
+        const lrcnoise::Words w = lrcnoise::ray_words(np.seed, np.first_frame + pose, (uint32_t)i);
+        if (np.drop_thr != 0u) live = w.w3 >= np.drop_thr;
+        if (np.angle_std != 0.0) {
+            const double dp = np.angle_std * (double)lrcnoise::normal_of(w.w1, np.tab);
+            const double dt = np.angle_std * (double)lrcnoise::normal_of(w.w2, np.tab);
+            lrcnoise::jitter_row(a, b, c, dp, dt);
+        }
+    }
+    d.x = (float)dgemm_row(a, b, c, M[0], M[1], M[2]);
+    d.y = (float)dgemm_row(a, b, c, M[4], M[5], M[6]);
+    d.z = (float)dgemm_row(a, b, c, M[8], M[9], M[10]);
+    cx = M[3]; cy = M[7]; cz = M[11];
+    o.x = (float)cx; o.y = (float)cy; o.z = (float)cz;
+}
+// The range draw of ray (frame, i): t' = t + range_std * z(w0), a float32 multiply then an add.
+LRC_DI float noisy_range(const lrcnoise::Params& np, uint64_t frame, uint32_t i, float t) {
+    const lrcnoise::Words w = lrcnoise::ray_words(np.seed, frame, i);
+    return t + np.range_std * lrcnoise::normal_of(w.w0, np.tab);
 }
 
 // p = o + (d/|d|)*t : numpy float32, one rounding per operation (reference: raycast_engine_cpu.py:57-62).

@@ -11,6 +11,7 @@
 
 #include "../../include/lidarcast.h"
 #include "lrc_bvh_device.h"
+#include "lrc_noise.h"
 
 // sets lrc_last_error() (lidarcast.hip).  Exported: lrc_nprandom.cpp, built without HIP headers, reports through it.
 extern "C" int lrc_internal_fail(int code, const char* msg);
@@ -91,6 +92,7 @@ struct lrc_ctx {
     lrc::DeviceArena build_arena;       // scratch of the device scene build, reused from scene to scene
     float* stat_scratch = nullptr;      // chunk sums of lrc_cloud_range_stats_dev (calls of one context must not overlap
     uint64_t stat_scratch_cap = 0;      // on different streams: handles are not thread-safe)
+    float* d_noise_tab = nullptr;       // lrc_scan_noisy_*: the normal quantile table (lrc_noise.h), uploaded on first use
 };
 
 struct lrc_table {            // a sensor's direction table resident in HBM (lrc_table_create)
@@ -158,5 +160,9 @@ inline int env_int(const char* name, int dflt) { const char* e = std::getenv(nam
 // the mesh checks of lrc_coverage_create and lrc_frameobj_create (non-finite vertex, triangle index out of range); `who`
 // prefixes the message.  Defined in lidarcast.hip, beside fail(): host code with no unit of its own.
 int check_mesh(const char* who, const double* verts3, uint64_t V, const int32_t* tris3, uint64_t T);
+
+// lrc_noise.hip: checks an lrc_noise for a table of N rays (LRC_ERR_INVALID_ARG, `who` prefixes the message), makes the
+// context's quantile table resident and fills the kernel's parameter block
+int noise_params(lrc_ctx* ctx, const char* who, const lrc_noise* nz, uint64_t N, lrcnoise::Params* out);
 
 #pragma GCC visibility pop

@@ -9,13 +9,14 @@ from .objboxes import OBJBOX_DTYPE, ObjectBoxes, object_boxes, object_boxes_dev
 from .coverage import CoverageSummary, SurfaceCoverage, scan_coverage
 from .voxgrid import OccupancyGrid, OccupancyResult, scan_occupancy
 from .frameobj import FrameObjects, FrameObjectsResult, scan_frame_objects
+from .noise import NoiseModel
 
 __all__ = ["LIB_PATH", "LRC_INVALID_PRIM", "LidarcastError", "load", "ATTRS", "Context",
            "DeviceHits", "DirectionTable", "Scene", "motion_records", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "BOX_DTYPE", "instance_boxes", "instance_boxes_dev",
            "Preprocessed", "preprocess_cloud", "preprocess_cloud_dev", "remove_statistical_outlier", "estimate_normals",
            "OBJBOX_DTYPE", "ObjectBoxes", "object_boxes", "object_boxes_dev", "CoverageSummary", "SurfaceCoverage",
            "scan_coverage", "OccupancyGrid", "OccupancyResult", "scan_occupancy", "FrameObjects",
-           "FrameObjectsResult", "scan_frame_objects", "version",
+           "FrameObjectsResult", "scan_frame_objects", "NoiseModel", "version",
            "device_count"]
 
 

@@ -35,6 +35,7 @@ SYMBOLS = (
     "lrc_scan_grid_dev", "lrc_scan_grid_compact", "lrc_scan_rays_compact",
     "lrc_table_create", "lrc_table_destroy", "lrc_scan_table_compact",
     "lrc_scan_sweeps_dev", "lrc_table_set_fire", "lrc_scan_sweeps_compact",
+    "lrc_scan_noisy_dev", "lrc_scan_noisy_compact", "lrc_noise_draws", "lrc_noise_table",
     "lrc_compact", "lrc_compact_dev", "lrc_cloud_from_ranges_dev", "lrc_cloud_from_prims_dev",
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
@@ -74,6 +75,11 @@ class LrcSceneInfo(C.Structure):
 class LrcScanOptions(C.Structure):
     _fields_ = [("min_range", C.c_double), ("range_noise", C.c_void_p), ("range_noise_len", C.c_uint64),
                 ("incident_mode", C.c_int)]
+
+
+class LrcNoise(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_frame", C.c_uint64), ("range_std", C.c_double), ("angle_std", C.c_double),
+                ("dropout", C.c_double)]
 
 
 class LrcCoverageInfo(C.Structure):
@@ -246,6 +252,10 @@ def load():
         "lrc_table_set_fire": [vp, vp, u64],
         "lrc_scan_sweeps_compact": [vp, vp, u64, vp, dbl, C.POINTER(LrcFrames), u64, C.POINTER(u64)],
         "lrc_scan_grid_compact": [vp, vp, u64, vp, C.POINTER(LrcGrid), dbl, C.POINTER(LrcFrames), u64, C.POINTER(u64)],
+        "lrc_scan_noisy_dev": [vp, vp, u64, vp, u64, dbl, C.POINTER(LrcNoise), C.POINTER(LrcHits), vp],
+        "lrc_scan_noisy_compact": [vp, vp, u64, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcFrames), u64, C.POINTER(u64)],
+        "lrc_noise_draws": [C.POINTER(LrcNoise), u64, u64, vp, vp, vp, vp],
+        "lrc_noise_table": [vp, vp],
         "lrc_occ_create": [vp, vp, u64, C.POINTER(vp)],
         "lrc_occ_destroy": [vp],
         "lrc_occ_query": [vp, vp, u64, dbl, vp],

@@ -668,6 +668,32 @@ class Scene:
             if own is not None:
                 own.close()
 
+    def scan_noisy_compact(self, poses, dirs, max_range, noise, want=("point3", "sem", "ins"), capacity=None):
+        """Pose-batched scan with seeded sensor noise straight to frames (lrc_scan_noisy_compact): ``noise`` a
+        ``lidarcast.noise.NoiseModel`` (pose p of the call is frame ``noise.first_frame + p``), ``dirs`` a DirectionTable or
+        an (N, 3) table.  Same return value as ``scan_poses_compact``."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
+        own = None
+        if isinstance(dirs, DirectionTable):
+            if not dirs._h:
+                raise ValueError("direction table handle is closed")
+            if dirs.ctx is not self.ctx:
+                raise ValueError("direction table belongs to another context (device)")
+            table = dirs
+        else:
+            table = own = DirectionTable(self.ctx, dirs)
+        try:
+            P, N = poses.shape[0], table.n
+            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
+            total = C.c_uint64(0)
+            nz = noise.struct()
+            check(self._lib.lrc_scan_noisy_compact(self._h, _ptr(poses), P, table._h, float(max_range), C.byref(nz),
+                                                   C.byref(fr), cap, C.byref(total)), "lrc_scan_noisy_compact")
+            return self._frames_end(counts, bufs, total.value)
+        finally:
+            if own is not None:
+                own.close()
+
     def scan_angles_compact(self, poses, angles, keep, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Dual-axis sensor, rays generated in the kernel from host-drawn (phi, theta) (lrc_scan_angles_compact).
         angles: (P, N, 2) float64; keep: (P, N) bool / uint8 or None."""
@@ -744,6 +770,15 @@ class Scene:
                                            C.c_void_p(dirs_t.data_ptr()), N, float(max_range),
                                            C.byref(hits.struct), C.c_void_p(int(stream))),
               "lrc_scan_poses_dev")
+
+    def scan_noisy_dev(self, poses_t, dirs_t, hits, max_range, noise, stream=0):
+        """Pose-batched scan with seeded sensor noise on device tensors (lrc_scan_noisy_dev): poses_t (P, 16) float64,
+        dirs_t (N, 3) float64, ``noise`` a ``lidarcast.noise.NoiseModel``; records as ``scan_poses_dev``."""
+        P, N = poses_t.shape[0], dirs_t.shape[0]
+        nz = noise.struct()
+        check(self._lib.lrc_scan_noisy_dev(self._h, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
+                                           float(max_range), C.byref(nz), C.byref(hits.struct), C.c_void_p(int(stream))),
+              "lrc_scan_noisy_dev")
 
     def scan_sweeps_dev(self, motion_t, dirs_t, fire_t, hits, max_range, stream=0):
         """Moving-sensor sweeps on device tensors (lrc_scan_sweeps_dev): motion_t (P, 24) float64, dirs_t (N, 3) float64,

@@ -363,6 +363,16 @@ class RaycastEngineHIP(RaycastEngineBase):
                                                        intrinsics.max_range, want=want,
                                                        grid=self._grid_of(intrinsics, len(poses)))
 
+    def scan_noisy_frames(self, intrinsics, poses, mesh, noise, want=("point3", "sem", "ins")):
+        """``scan_frames`` with seeded sensor noise drawn in the kernel (lrc_scan_noisy_compact):
+        ``noise`` a ``lidarcast.noise.NoiseModel``; pose p is frame ``noise.first_frame + p``, so any subset of a trajectory
+        can be scanned again with its exact noise.  Same dict as ``scan_frames``."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
+            raise ValueError("seeded sensor noise needs a sensor with a pose-independent direction table")
+        return self.scene_for(mesh).scan_noisy_compact(poses, self._resident_table(intrinsics), intrinsics.max_range, noise,
+                                                       want=want)
+
     def _firing_fractions(self, intrinsics):
         """(N,) firing fractions of the sensor's direction table (IndoorLidar.firing_fractions), cached with the table."""
         from lidar import IndoorLidar

@@ -198,6 +198,8 @@ class S3DISSimulator:
             raise ValueError("Scene not loaded. Call load_scene() first.")
         if self.config.get("motion") is not None:
             raise NotImplementedError("surface coverage of moving-sensor sweeps is outside its scope")
+        if self.config.get("noise") is not None:
+            raise NotImplementedError("surface coverage under the noise key is outside its scope")
         from lidarcast.synth import S3DIS_CLASSES
         s = self.raycast_engine.surface_coverage(self.lidar_config, poses_from_waypoints(waypoints),
                                                  self.scene.room_mesh)
@@ -217,6 +219,8 @@ class S3DISSimulator:
             raise ValueError("Scene not loaded. Call load_scene() first.")
         if self.config.get("motion") is not None:
             raise NotImplementedError("occupancy grids of moving-sensor sweeps are outside their scope")
+        if self.config.get("noise") is not None:
+            raise NotImplementedError("occupancy grids under the noise key are outside their scope")
         from containers.s3dis_sim_scene import write_labeled_ply
         from lidarcast.synth import S3DIS_CLASSES
         r = self.raycast_engine.occupancy_grid(self.lidar_config, poses_from_waypoints(waypoints), self.scene.room_mesh,
@@ -249,6 +253,8 @@ class S3DISSimulator:
             raise ValueError("Scene not loaded. Call load_scene() first.")
         if self.config.get("motion") is not None:
             raise NotImplementedError("frame annotations of moving-sensor sweeps are outside their scope")
+        if self.config.get("noise") is not None:
+            raise NotImplementedError("frame annotations under the noise key are outside their scope")
         from lidar_net_bbox_visualizer import S3DIS_SEMANTIC_MAPPING
         from lidarcast.synth import S3DIS_CLASSES
         mapping = S3DIS_SEMANTIC_MAPPING if semantic_mapping is None else semantic_mapping
@@ -287,6 +293,25 @@ class S3DISSimulator:
         with open(out / f"{name}_frame_annotations.json", "w") as fh:
             json.dump(summary, fh, indent=2)
         return summary
+
+    def _noise_model(self):
+        """The NoiseModel of the config key ``noise`` (None without the key): ``seed`` is required; ``range_std`` (m),
+        ``angle_std_deg`` and ``dropout`` default to the sensor record's range_noise_std, angle_noise_std (degrees) and
+        dropout_probability.  first_frame = 0: frame p of a run has frame id p."""
+        cfg = self.config.get("noise")
+        if cfg is None:
+            return None
+        if "seed" not in cfg:
+            raise ValueError("the noise key needs a seed")
+        unknown = set(cfg) - {"seed", "range_std", "angle_std_deg", "dropout"}
+        if unknown:
+            raise ValueError(f"unknown entries under the noise key: {sorted(unknown)}")
+        from lidarcast.noise import NoiseModel
+        k = self.lidar_config
+        return NoiseModel(seed=int(cfg["seed"]),
+                          range_std=float(cfg.get("range_std", getattr(k, "range_noise_std", 0.0))),
+                          angle_std=float(np.deg2rad(float(cfg.get("angle_std_deg", getattr(k, "angle_noise_std", 0.0))))),
+                          dropout=float(cfg.get("dropout", getattr(k, "dropout_probability", 0.0))))
 
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
@@ -342,7 +367,20 @@ class S3DISSimulator:
             start_poses = poses_from_waypoints(waypoints)
             end_poses = sweep_end_poses(waypoints, self.lidar_config.scan_frequency, float(motion.get("speed", 0.0)))
             sweep = engine.sweep_inputs(self.lidar_config, start_poses, end_poses)
-        if sweep is not None:
+        # opt-in seeded sensor noise (config key ``noise: {seed, range_std?, angle_std_deg?, dropout?}``): range noise, angle
+        # jitter and dropout drawn in the kernel; frame p of the run has frame id p, so scanning any
+        # subset again reproduces it.  Without the key nothing changes.
+        noise = self._noise_model() if len(waypoints) > 0 else None
+        if noise is not None:
+            if motion is not None:
+                raise ValueError("the noise key cannot be combined with moving-sensor sweeps (motion)")
+            if dist is not None:
+                raise ValueError("the noise key is not available on a multi-rank process group")
+            if not batched:
+                raise ValueError("the noise key needs a multi-line sensor with a direction table (not the dual-axis sensor)")
+        if noise is not None:
+            fr = engine.scan_noisy_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, noise, want=want)
+        elif sweep is not None:
             fr = engine.scan_sweep_frames(self.lidar_config, None, None, mesh, want=want, inputs=sweep)
         elif dist is not None and len(waypoints) > 0:
             if batched:
@@ -393,7 +431,7 @@ class S3DISSimulator:
             else:      # labels on demand: one labels-only scan of the trajectory (of the SAME sweeps), shared by its frames
                 sem_f = ins_f = itertools.repeat(None)
                 src_f = itertools.repeat(_LazyTrajectoryLabels(engine, self.lidar_config, poses_from_waypoints(waypoints),
-                                                               mesh, counts_l, sweep))
+                                                               mesh, counts_l, sweep, noise))
             if "range_origin_mean" in fr:      # statistics from the device
                 qual = self._quality_from_stats(fr, total, volume)
             else:
@@ -426,10 +464,12 @@ class _LazyTrajectoryLabels:
     of the same poses over the same mesh (the scan is a pure function of both: same kept rays, same order), whose result
     all frames of the trajectory share."""
 
-    def __init__(self, engine, intrinsics, poses, mesh, counts, sweep=None):
+    def __init__(self, engine, intrinsics, poses, mesh, counts, sweep=None, noise=None):
         # sweep: the (motion records, fire table, period) of a moving-sensor scan -- rescanned exactly, never as static poses
+        # noise: the NoiseModel of a noisy scan -- rescanned with the same seed and frame ids, never as the clean scan
         self._args = (engine, intrinsics, np.array(poses, dtype=np.float64, copy=True), mesh)
         self._sweep = sweep
+        self._noise = noise
         self._counts = list(counts)
         self._sem = self._ins = None
         import threading
@@ -439,14 +479,16 @@ class _LazyTrajectoryLabels:
         with self._lock:
             if self._sem is None:
                 engine, intrinsics, poses, mesh = self._args
-                if self._sweep is not None:
+                if self._noise is not None:
+                    fr = engine.scan_noisy_frames(intrinsics, poses, mesh, self._noise, want=("sem", "ins"))
+                elif self._sweep is not None:
                     fr = engine.scan_sweep_frames(intrinsics, None, None, mesh, want=("sem", "ins"), inputs=self._sweep)
                 else:
                     fr = engine.scan_frames(intrinsics, poses, mesh, want=("sem", "ins"))
                 if fr["counts"].tolist() != self._counts:
                     raise RuntimeError("the mesh or the scan options changed between the scan and the first look at its labels")
                 self._sem, self._ins, self._ends = fr["sem"], fr["ins"], list(itertools.accumulate(self._counts))
-                self._args = self._sweep = None
+                self._args = self._sweep = self._noise = None
         e, c = self._ends[i], self._counts[i]
         return self._sem[e - c:e], self._ins[e - c:e]
 
