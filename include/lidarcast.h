@@ -293,6 +293,12 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t num_segments, uint64_t seg_len,
  *                     such split), so that no wave holds lines above and below the horizon: by fours, then a pair if two or
  *                     three lines remain, then an odd last line as 64 consecutive rays.  Like the width, this only regroups rays
  *                     into waves, bijectively for any value: it never changes a byte.
+ *   lrc_pipe_set_ray_table  1 (the default) or 0.  The ray table holds, per row of the direction table, the float32 world
+ *                     direction, its guarded reciprocal and its unit vector for the rotation of pose 0 of a submit, so that
+ *                     the tracing waves load them instead of forming them per ray in float64.  It is rebuilt on the device for
+ *                     every submit with rays_per_pose % 64 == 0 from that submit's own poses and table (nothing is cached by
+ *                     address).  A pose whose nine rotation entries are not bit for bit those of pose 0 is traced as without
+ *                     a table, pose by pose inside one launch: mixed rotations cost the gain for those poses, never a byte.
  * Destroy the pipeline before its scene. */
 typedef struct lrc_pipe lrc_pipe;
 int lrc_pipe_create(lrc_scene* scene, uint64_t max_poses, uint64_t rays_per_pose, lrc_pipe** out_pipe);
@@ -304,6 +310,7 @@ int lrc_pipe_records(lrc_pipe* pipe, uint64_t ticket, lrc_hits* out_records);
 int lrc_pipe_trace_ms(lrc_pipe* pipe, uint64_t ticket, float* out_ms);
 int lrc_pipe_set_line_width(lrc_pipe* pipe, uint64_t line_width);
 int lrc_pipe_set_tile_lines(lrc_pipe* pipe, uint32_t lines);
+int lrc_pipe_set_ray_table(lrc_pipe* pipe, int enable);
 
 /* The pipeline on N ranks (one process per GPU; the collective itself is the caller's: RCCL all-gather of the send slabs).
  *   lrc_pipe_submit_sharded  traces this rank's pose block like lrc_pipe_submit, with the triangle ids and per-wave keep counts

@@ -156,7 +156,13 @@ struct TraceParams {
     uint32_t line_group;
     const double* poses16;     // GEN = 1, 2
     const double* dirs3;       // GEN = 1: (N,3) sensor-frame direction table
-    const double* angles2;     // GEN = 2: (P*N,2) noisy (phi, theta) of the dual-axis sensor
+    // GEN = 2: (P*N,2) noisy (phi, theta) of the dual-axis sensor.  GEN = 1 never reads them, and only GEN = 1 reads the ray
+    // table of a prepared pipeline submit (RayPose below; NULL: none), so the two share one slot: the argument block keeps its
+    // size, on which the register allocation of the product kernel has depended before.
+    union {
+        const double* angles2;
+        const float4* ray_tab;
+    };
     const uint8_t* keep_mask;  // GEN = 2, nullable: 0 = ray dropped by the sensor (never cast, reported as a miss)
     uint32_t* stats;           // STATS build only: kStatsWords counters per ray
     uint64_t rays_per_pose;
@@ -325,7 +331,8 @@ __device__ __forceinline__ double range_filter(const TraceParams& p, double s, b
 // HAVE_LABEL: the caller has slot_label[best_slot] already (trace_kernel issues the load together with the box clause's).
 template <bool FILTER_ALWAYS, bool BY_PRIM = false, bool HAVE_LABEL = false>
 __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, uint32_t tid, V3 o, V3 d, double cx,
-                                           double cy, double cz, float tbest, uint32_t best_slot, uint32_t slot_label_in = 0u) {
+                                           double cy, double cz, float tbest, uint32_t best_slot, uint32_t slot_label_in = 0u,
+                                           bool have_h = false, V3 h_in = V3{0.f, 0.f, 0.f}) {
     constexpr int GEN = FILTER_ALWAYS ? 1 : 0;
     const bool lean = FILTER_ALWAYS && !BY_PRIM && p.lean.row != nullptr;    // a kernel argument: wave-uniform
     bool keep = best_slot != 0xFFFFFFFFu;
@@ -343,8 +350,14 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
     }
     if (keep) {
         // p = o + (d/|d|)*t : numpy float32, one rounding per operation (raycast_engine_cpu.py:57-62)
+        // have_h (wave-uniform): the unit direction comes from the ray table of a prepared submit -- unit_dir's own bits
         V3 hh, pp;
-        hit_point(o, d, tbest, hh, pp);
+        if (have_h) {
+            hh = h_in;
+            pp.x = o.x + hh.x * tbest; pp.y = o.y + hh.y * tbest; pp.z = o.z + hh.z * tbest;
+        } else {
+            hit_point(o, d, tbest, hh, pp);
+        }
         const float hx = hh.x, hy = hh.y, hz = hh.z;
         px = pp.x; py = pp.y; pz = pp.z;
         // range filter + incident angle in float64 (raycast_engine_cpu.py:95-107)
@@ -611,6 +624,56 @@ constexpr int kPreTiles = LRC_PRE_TILES;      // tiles per leading workgroup of 
 
 template <int I> struct IntTag { static constexpr int value = I; };
 
+// ---- the ray table of a prepared pipeline submit (lrc_pipe_submit; lrc_device.h ray_row) -------------
+// One buffer behind TraceParams::ray_tab, for a table of N rows and P poses, in units of 16 bytes:
+//   [0, 2N)        per row i two records: (d.x, d.y, d.z, 0) and (inv.x, inv.y, inv.z, 0)      -- the prologue's two loads
+//   [2N, 3N)       per row i (h.x, h.y, h.z, 0)                                                -- the epilogue's one load
+//   [3N, 3N + 4P)  per pose p a RayPose: whether its rotation block is pose 0's bit for bit (then the rows are its rays'),
+//                  its float32 origin and its float64 range-filter centre; read through the scalar cache
+// All of it is rebuilt for every submit from that submit's poses and table (ray_table_kernel): nothing is keyed on an
+// address, so a table edited in place or a new one at a recycled address cannot leave stale rows behind.
+struct alignas(64) RayPose {
+    double cx, cy, cz;
+    uint32_t same;             // 1: the nine rotation doubles equal pose 0's as bit patterns (-0.0 != +0.0; a NaN equals only a NaN of the same bits)
+    float ox, oy, oz;          // (the flag between the two: centre + flag are one 32-byte load, flag + origin one of 16)
+    uint32_t pad[6];
+};
+static_assert(sizeof(RayPose) == 64, "RayPose: four 16-byte units");
+// (the kernel derives the offsets 2N and 3N from tiles_per_pose as N = 64 * tiles_per_pose: a pipeline allocates its tables,
+// and hence carries one, only in a build with kTBlock == 64 -- lrc_pipe_create)
+constexpr uint64_t kRayTabMaxRows = 1ull << 24;     // rows a pipeline prepares a table for (the offsets stay in 32 bits)
+__host__ __device__ inline uint64_t ray_tab_bytes(uint64_t N, uint64_t P) { return N * 48u + P * sizeof(RayPose); }
+
+// One-wave workgroups, like the scan pass: beside the other stream's running trace launch they are handed wave slots one by
+// one.  Lane-strided over the rows, then over the poses.
+__global__ __launch_bounds__(64) void ray_table_kernel(const double* __restrict__ poses16, uint32_t P,
+                                                       const double* __restrict__ dirs3, uint32_t N, float4* __restrict__ tab) {
+    const uint32_t first = blockIdx.x * 64u + threadIdx.x, step = gridDim.x * 64u;
+    const double R[9] = {poses16[0], poses16[1], poses16[2], poses16[4], poses16[5], poses16[6], poses16[8], poses16[9], poses16[10]};
+    for (uint32_t i = first; i < N; i += step) {
+        const double* dv = dirs3 + (size_t)i * 3;
+        const RayRow r = ray_row(R, dv[0], dv[1], dv[2]);
+        tab[(size_t)i * 2] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
+        tab[(size_t)i * 2 + 1] = make_float4(r.inv.x, r.inv.y, r.inv.z, 0.0f);
+        tab[(size_t)N * 2 + i] = make_float4(r.h.x, r.h.y, r.h.z, 0.0f);
+    }
+    RayPose* rp = (RayPose*)(tab + (size_t)N * 3);
+    const uint64_t* B = (const uint64_t*)poses16;
+    for (uint32_t q = first; q < P; q += step) {
+        const double* M = poses16 + (size_t)q * 16;
+        const uint64_t* A = (const uint64_t*)M;
+        bool same = true;
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            if ((k & 3) != 3) same = same & (A[k] == B[k]);
+        RayPose o{};
+        o.cx = M[3]; o.cy = M[7]; o.cz = M[11];
+        o.ox = (float)M[3]; o.oy = (float)M[7]; o.oz = (float)M[11];
+        o.same = same ? 1u : 0u;
+        rp[q] = o;
+    }
+}
+
 // GEN: 0 = explicit rays, 1 = pose x direction table, 2 = pose x per-ray scan angles (dual-axis sensor, opt-in),
 //      4 = motion record x direction table x firing fractions (moving-sensor sweeps, opt-in; same ray order as 1),
 //      5 = pose x direction table with seeded range noise, angle jitter and dropout drawn per ray (opt-in; same ray order as 1)
@@ -667,6 +730,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
 
     // ---- the ray ----
     V3 o, d;
+    V3 inv;                    // safe_inv of d per axis: formed with the ray (GEN = 1 may take it from a prepared table)
     double cx, cy, cz;
     bool live = true;          // false: not cast at all (dropped by the sensor, or a non-finite ray)
     uint32_t pose32 = 0;
@@ -683,7 +747,32 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
             pose = gid / p.rays_per_pose;
             i = gid - pose * p.rays_per_pose;
         }
-        gen_ray(p.poses16, p.dirs3, pose, i, o, d, cx, cy, cz);
+        // prepared submit (ray_table_kernel): a wave whose pose has pose 0's rotation takes d and 1/d from the table and its
+        // origin from the pose record -- no pose matrix, no float64, no division.  Wave-uniform: a tile lies in one pose.
+        typedef __attribute__((address_space(4))) const RayPose cpose;
+        bool prepared = false;
+        if (p.tiles_per_pose != 0u && p.ray_tab != nullptr) {
+            cpose* rp = (cpose*)(p.ray_tab + (size_t)p.tiles_per_pose * 192u) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pose);
+            // the row's records are fetched beside the pose record, not behind its flag: one round trip, and a wave that
+            // falls back (a turning trajectory) merely drops them
+            const uint32_t same = rp->same;
+            const float ox = rp->ox, oy = rp->oy, oz = rp->oz;
+            const float4 ta = p.ray_tab[(size_t)(uint32_t)i * 2], tb = p.ray_tab[(size_t)(uint32_t)i * 2 + 1];
+            prepared = same != 0u;
+            if (prepared) {
+                o.x = ox; o.y = oy; o.z = oz;
+                d.x = ta.x; d.y = ta.y; d.z = ta.z;
+                inv.x = tb.x; inv.y = tb.y; inv.z = tb.z;
+            } else {
+                // a use on this side as well, or the compiler sinks the loads behind the flag's branch: two round trips
+                asm volatile("" :: "v"(ta.x), "v"(ta.y), "v"(ta.z), "v"(tb.x), "v"(tb.y), "v"(tb.z), "s"(ox), "s"(oy), "s"(oz));
+            }
+        }
+        if (!prepared) {
+            double ux, uy, uz;      // the centre is fetched again behind the traversal
+            gen_ray(p.poses16, p.dirs3, pose, i, o, d, ux, uy, uz);
+            inv = V3{safe_inv(d.x), safe_inv(d.y), safe_inv(d.z)};
+        }
         pose32 = (uint32_t)pose;
     } else if (GEN == 2) {
         const uint64_t pose = gid / p.rays_per_pose;
@@ -728,6 +817,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
 
     uint32_t st_nodes = 0, st_tris = 0, st_uni = 0, st_dead = 0, st_pad = 0;   // STATS build only (lrc_debug_scan_stats)
     live = live & finite_ray(o, d);
+    if (GEN != 1) inv = V3{safe_inv(d.x), safe_inv(d.y), safe_inv(d.z)};
 
     // The traversal, once per node image: Q = false walks the float32 world-space nodes with the ray's world-space slab
     // constants; Q = true walks the quantised images with the slab constants in normalised coordinates.  Which boxes
@@ -747,7 +837,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         uint32_t oct = 0;     // quantised paths: the wave's direction octant (wave-uniform, SGPR)
         if (Q) {
             // normalised coordinates: n = (x - base) / W per axis, W a power of two (scaling by it is exact)
-            const float ix = safe_inv(d.x), iy = safe_inv(d.y), iz = safe_inv(d.z);
+            const float ix = inv.x, iy = inv.y, iz = inv.z;
             sl.ix = ix * p.qW[0]; sl.iy = iy * p.qW[1]; sl.iz = iz * p.qW[2];
             sl.ox = ((o.x - p.qbase[0]) * p.qinvW[0]) * sl.ix;
             sl.oy = ((o.y - p.qbase[1]) * p.qinvW[1]) * sl.iy;
@@ -760,8 +850,15 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
             sel_nx = (oct & 1u) ? kHi : kLo; sel_fx = (oct & 1u) ? kLo : kHi;
             sel_ny = (oct & 2u) ? kHi : kLo; sel_fy = (oct & 2u) ? kLo : kHi;
             sel_nz = (oct & 4u) ? kHi : kLo; sel_fz = (oct & 4u) ? kLo : kHi;
+        } else if (INLINE_CLAUSE) {
+            // the redo route forms 1/d again, from a copy of d the compiler cannot connect with the prologue's: neither `inv` nor
+            // an intermediate of safe_inv is held through the first traversal (they were spilled to scratch)
+            V3 dd = d;
+            asm volatile("" : "+v"(dd.x), "+v"(dd.y), "+v"(dd.z));
+            sl = make_slab(o, dd);
         } else {
-            sl = make_slab(o, d);
+            sl.ix = inv.x; sl.iy = inv.y; sl.iz = inv.z;      // make_slab with safe_inv already taken
+            sl.ox = o.x * sl.ix; sl.oy = o.y * sl.iy; sl.oz = o.z * sl.iz;
         }
         int sp = 0;
         int ref = 0;   // root
@@ -1059,15 +1156,26 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
     }
 
     // ---- fused write-back ----
-    if (GEN == 4) {
-        // formed below from the record and the ray's firing fraction, after the ray's index
-    } else if (GEN != 0) {
+    // prepared submit (GEN = 1 with a ray table): flag and float64 centre come from the pose record again (scalar loads) and the
+    // row's unit direction from the table, in the place of the per-lane fetch of the pose's translation.  Pointer and divisor
+    // are made opaque so that nothing of the prologue (the division's reciprocal) is held through the traversal.
+    const float4* tab = nullptr;
+    uint32_t tpp = 0u;
+    if (GEN == 1) {
+        tab = p.ray_tab; tpp = p.tiles_per_pose;
+        asm volatile("" : "+s"(tab));
+        asm volatile("" : "+s"(tpp));
+    }
+    const bool tabbed = GEN == 1 && tpp != 0u && tab != nullptr;      // a kernel argument: uniform over the launch
+    if (GEN != 0 && GEN != 4 && !tabbed) {
         // the range-filter centre (the pose's translation, float64) is fetched again here instead of being held in six
         // registers through the traversal; the pointer is made opaque so that the fetch is not merged with gen_ray's
         const double* M = p.poses16;
         asm volatile("" : "+s"(M));
         M += (size_t)pose32 * 16;
         cx = M[3]; cy = M[7]; cz = M[11];
+    } else if (GEN != 0) {
+        // formed below: GEN = 4 from the record and the firing fraction, a prepared submit from its pose record
     } else if (p.seg_centers3) {
         const double* c = p.seg_centers3 + (size_t)pose32 * 3;      // the centre of this ray's pose (segment)
         cx = c[0]; cy = c[1]; cz = c[2];
@@ -1081,9 +1189,31 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
     const uint32_t tile_w = p.tile_chunk_log2 ? xcd_tile_chunked(wg - p.pre.blocks, gridDim.x - p.pre.blocks, p.tile_chunk_log2)
                                               : xcd_tile(wg - p.pre.blocks, gridDim.x - p.pre.blocks);
     uint64_t gid_w = (uint64_t)tile_w * kTBlock + tid;
-    if (GEN == 1 && p.tiles_per_pose != 0u && p.line_tiles != 0u) {      // line-group tile: the same mapping as in front of the traversal
-        const uint32_t pu = tile_w / p.tiles_per_pose;
-        gid_w = (uint64_t)pu * p.rays_per_pose + tile_ray(tile_w - pu * p.tiles_per_pose, tid, p.line_tiles, p.tiles_per_pose, p.line_group);
+    uint32_t pu_w = 0u;
+    if (GEN == 1 && tpp != 0u && (p.line_tiles != 0u || tabbed)) pu_w = tile_w / tpp;
+    if (GEN == 1 && tpp != 0u && p.line_tiles != 0u)      // line-group tile: the same mapping as in front of the traversal
+        gid_w = (uint64_t)pu_w * p.rays_per_pose + tile_ray(tile_w - pu_w * tpp, tid, p.line_tiles, tpp, p.line_group);
+    bool have_h = false;
+    V3 h_tab{0.f, 0.f, 0.f};
+    if (tabbed) {
+        typedef __attribute__((address_space(4))) const RayPose cpose;
+        cpose* rp = (cpose*)(tab + (size_t)tpp * 192u) + pu_w;
+        // record and row are fetched side by side (one round trip); a wave that falls back drops the row
+        const uint32_t same = rp->same;
+        const double rx = rp->cx, ry = rp->cy, rz = rp->cz;
+        typedef __attribute__((address_space(1))) const nt_float4 gfloat4;      // a global load: the opaque pointer lost its address space
+        const nt_float4 th = ((gfloat4*)tab)[(size_t)tpp * 128u + ((uint32_t)gid_w - pu_w * (uint32_t)p.rays_per_pose)];
+        have_h = same != 0u;
+        if (have_h) {
+            h_tab.x = th.x; h_tab.y = th.y; h_tab.z = th.z;
+            cx = rx; cy = ry; cz = rz;
+        } else {
+            asm volatile("" :: "v"(th.x), "v"(th.y), "v"(th.z), "s"(rx), "s"(ry), "s"(rz));      // keeps the loads in front of the branch
+            const double* M = p.poses16;      // as above
+            asm volatile("" : "+s"(M));
+            M += (size_t)pose32 * 16;
+            cx = M[3]; cy = M[7]; cz = M[11];
+        }
     }
     if (GEN == 4) {
         // the range-filter centre c(s), float64, formed again from the record and fire[i] (as GEN = 1 fetches the pose's
@@ -1101,7 +1231,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         tbest = noisy_range(p.noise, p.noise.first_frame + pose32, (uint32_t)(gid_w - (uint64_t)pose32 * p.rays_per_pose), tbest);
         if (!(tbest > 0.0f)) best_slot = 0xFFFFFFFFu;
     }
-    write_back<GEN != 0, false, true>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot, best_label);
+    write_back<GEN != 0, false, true>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot, best_label, have_h, h_tab);
     if (STATS) {
         if (p.stats) {
             uint32_t* q = p.stats + gid_w * kStatsWords;
@@ -1635,6 +1765,17 @@ void lrc_internal_range_decide(double max_range, const double* s, uint64_t n, ui
         const bool band = !rb.fast || range_in_band(s[i], rb.lo, rb.hi);
         keep[i] = band ? (uint8_t)(std::sqrt(s[i]) < max_range) : (uint8_t)range_below(s[i], rb.lo);
         if (in_band) in_band[i] = (uint8_t)band;
+    }
+}
+
+// test hook (tests/test_ray_table_host.py): rows of the ray table of a prepared pipeline submit for the rotation block rot9 (row
+// major), made by the host compilation of the very function ray_table_kernel calls (lrc_device.h, ray_row): per row 9 floats
+// d, inv, h
+void lrc_internal_ray_table_rows(const double* rot9, const double* dirs3, uint64_t n, float* out9) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const RayRow r = ray_row(rot9, dirs3[3 * i], dirs3[3 * i + 1], dirs3[3 * i + 2]);
+        float* q = out9 + 9 * i;
+        q[0] = r.d.x; q[1] = r.d.y; q[2] = r.d.z; q[3] = r.inv.x; q[4] = r.inv.y; q[5] = r.inv.z; q[6] = r.h.x; q[7] = r.h.y; q[8] = r.h.z;
     }
 }
 
@@ -2694,6 +2835,12 @@ struct lrc_pipe {
     // line-group tiles (lrc_pipe_set_tile_lines): lines per tile asked for (0: automatic = 4 where the table has a group of
     // four), the split line detected with line_auto, and what the last launch ran with
     uint32_t lines_hint = 0, split_auto = 0, lines_last = 1, group_last = 0;
+    // prepared submits (lrc_pipe_set_ray_table; ray_table_kernel): one ray table per trace stream -- the kernel that fills it
+    // for submit k sits on that stream between the scan pass of submit k - 2 and the trace of submit k, so stream order alone
+    // keeps it from being rewritten while a trace reads it.  NULL: not a fused pipeline, or more rows than kRayTabMaxRows.
+    float4* ray_tab[2] = {};
+    bool use_ray_tab = true;
+    bool ray_tab_last = false;                               // the last submit's launch carried a table
 };
 
 int lrc_pipe_destroy(lrc_pipe* pp) {
@@ -2708,6 +2855,7 @@ int lrc_pipe_destroy(lrc_pipe* pp) {
     if (pp->ev_expand) (void)hipEventDestroy(pp->ev_expand);
     if (pp->d_line) (void)hipFree(pp->d_line);
     for (int k = 0; k < 2; ++k) {
+        if (pp->ray_tab[k]) (void)hipFree(pp->ray_tab[k]);
         if (pp->ev_flush[k]) (void)hipEventDestroy(pp->ev_flush[k]);
         for (lrc_ctx::TileScratch* scp : {&pp->scratch[k], &pp->gscratch[k]}) {
             lrc_ctx::TileScratch& sc = *scp;
@@ -2779,6 +2927,9 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
     }
     if (hipEventCreateWithFlags(&pp->ev_expand, hipEventDisableTiming) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
     if (pp->fused && hipMalloc((void**)&pp->d_line, 2 * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory")); }
+    if (pp->fused && kTBlock == 64 && rays_per_pose <= kRayTabMaxRows)
+        for (int k = 0; k < 2; ++k)
+            if (hipMalloc((void**)&pp->ray_tab[k], ray_tab_bytes(rays_per_pose, max_poses)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory for the ray tables")); }
     *out_pipe = pp;
     return LRC_OK;
 }
@@ -2824,6 +2975,20 @@ int lrc_pipe_set_tile_lines(lrc_pipe* pp, uint32_t lines) {
     if (lines != 0u && lines != 1u && lines != 2u && lines != 4u) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_set_tile_lines: lines must be 0, 1, 2 or 4");
     pp->lines_hint = lines;
     return LRC_OK;
+}
+
+int lrc_pipe_set_ray_table(lrc_pipe* pp, int enable) {
+    if (!pp) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_set_ray_table: pipe is NULL");
+    if (enable != 0 && enable != 1) return fail(LRC_ERR_INVALID_ARG, "lrc_pipe_set_ray_table: enable must be 0 or 1");
+    pp->use_ray_tab = enable != 0;
+    return LRC_OK;
+}
+
+// test hook (tests/test_pipe_ray_table_gpu.py): the ray table the trace launch of the last lrc_pipe_submit carried (device
+// pointer: 48 bytes per table row, then 64 per pose, see RayPose), or NULL -- the table changes no byte of the outputs, so only
+// its own content can tell whether it was there and which poses took it
+const void* lrc_internal_pipe_ray_table(const lrc_pipe* pp) {
+    return pp && pp->ray_tab_last ? (const void*)pp->ray_tab[(pp->ticket - 1) % 2] : nullptr;
 }
 
 int lrc_pipe_set_line_width(lrc_pipe* pp, uint64_t line_width) {
@@ -2881,6 +3046,18 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
         if (p.line_tiles != 0u)
             p.line_group = line_group_for(pp->line_hint == 0 ? pp->split_auto : 0u,
                                           pp->lines_hint == 0u ? (uint32_t)LRC_PIPE_TILE_LINES : pp->lines_hint);
+    }
+    // prepared submit: this stream's ray table is rebuilt from THIS submit's poses and table, behind the scan pass of submit
+    // k - 2 and in front of the trace (at most 64 one-wave workgroups: a few microseconds on an idle GPU, and beside the other
+    // stream's launch they trickle in during a step that has nothing else for this stream to do)
+    pp->ray_tab_last = false;
+    if (pp->fused && pp->use_ray_tab && pp->ray_tab[lane]) {
+        const uint64_t rows = N > P ? N : P, waves = (rows + 63) / 64;
+        hipLaunchKernelGGL(ray_table_kernel, dim3((uint32_t)(waves < 64 ? waves : 64)), dim3(64), 0, T, d_poses16, (uint32_t)P, d_dirs3,
+                           (uint32_t)N, pp->ray_tab[lane]);
+        LRC_HIP(hipGetLastError());
+        p.ray_tab = pp->ray_tab[lane];
+        pp->ray_tab_last = true;
     }
     // the rows of submit k - 2 (this stream's previous scan; its scan pass was enqueued behind its trace) ride in front
     const int prev = (int)((k + lrc_pipe::kSets - 2) % lrc_pipe::kSets);
@@ -3594,6 +3771,8 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
         if (q.poses16) q.poses16 = p.poses16 + p0 * 16;
         if (q.motion24) q.motion24 = p.motion24 + p0 * 24;
         q.noise.first_frame = p.noise.first_frame + p0;      // gen == 5: the chunk's first frame id
+        // (angles2 shares its slot with ray_tab: only lrc_pipe_submit sets a table and it never comes through this chunked
+        // path -- a launch with a table must not be given an offset here)
         if (q.angles2) q.angles2 = p.angles2 + r0 * 2;
         if (q.rays6) q.rays6 = p.rays6 + r0 * 6;
         if (q.seg_centers3) q.seg_centers3 = p.seg_centers3 + p0 * 3;

@@ -19,6 +19,7 @@
 namespace lrcdev {
 
 #define LRC_DI __device__ __forceinline__
+#define LRC_HDI __host__ __device__ __forceinline__     // also compiled for the host: the test hooks call these very functions
 
 constexpr float kTinyDir = 1e-30f;
 constexpr float kPadRelLo = 0.999755859375f;     // 1 - 2^-12
@@ -45,7 +46,7 @@ LRC_DI float max2(float a, float b) { return a > b ? a : b; }
 // Per-ray constants of the slab test.
 struct RaySlab { float ix, iy, iz, ox, oy, oz; };   // idir and o*idir
 
-LRC_DI float safe_inv(float d) {
+LRC_HDI float safe_inv(float d) {
     float a = __builtin_fabsf(d);
     float s = a < kTinyDir ? __builtin_copysignf(kTinyDir, d) : d;
     return 1.0f / s;
@@ -175,7 +176,7 @@ LRC_DI bool finite_ray(V3 o, V3 d) {
 // One output of np.dot(directions, R.T): the BLAS kernel accumulates over k from a +0.0 accumulator with fused
 // multiply-adds.  The accumulator matters for signed zeros only: (-0.0)*r or 0.0*(-r) alone would be -0.0, dgemm gives
 // +0.0 -- and the sign of a zero direction component decides which side of a box plane an in-plane ray is on.
-LRC_DI double dgemm_row(double a, double b, double c, double r0, double r1, double r2) {
+LRC_HDI double dgemm_row(double a, double b, double c, double r0, double r1, double r2) {
     return __builtin_fma(c, r2, __builtin_fma(b, r1, __builtin_fma(a, r0, 0.0)));
 }
 
@@ -289,12 +290,33 @@ LRC_DI float noisy_range(const lrcnoise::Params& np, uint64_t frame, uint32_t i,
     return t + np.range_std * lrcnoise::normal_of(w.w0, np.tab);
 }
 
+// d/|d| : numpy float32, one rounding per operation (reference: raycast_engine_cpu.py:57-60).  The one expression behind
+// hit_point and the ray table of a prepared pipeline submit (ray_row below).
+LRC_HDI V3 unit_dir(V3 d) {
+    const float nrm = __builtin_sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z);
+    return V3{d.x / nrm, d.y / nrm, d.z / nrm};
+}
 // p = o + (d/|d|)*t : numpy float32, one rounding per operation (reference: raycast_engine_cpu.py:57-62).
 // h receives the normalised direction.
 LRC_DI void hit_point(V3 o, V3 d, float t, V3& h, V3& pt) {
-    const float nrm = __builtin_sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z);
-    h.x = d.x / nrm; h.y = d.y / nrm; h.z = d.z / nrm;
+    h = unit_dir(d);
     pt.x = o.x + h.x * t; pt.y = o.y + h.y * t; pt.z = o.z + h.z * t;
+}
+
+// ---- ray table of a prepared pipeline submit -------------------------------------------------------
+// What a ray of a pose-batched scan owes to the table row and the pose's ROTATION alone, formed once per row for the rotation
+// block R (row major, 9 float64) by the functions the trace kernel itself calls per ray: d = float32(row . R^T) (gen_ray's
+// dgemm_row chain), inv = safe_inv(d) (the slab constants before the scene's scaling) and h = d / |d| (hit_point's unit
+// direction).  A pose whose rotation block has the same 72 bytes gets the same d, inv and h, bit for bit.
+struct RayRow { V3 d, inv, h; };
+LRC_HDI RayRow ray_row(const double* R, double a, double b, double c) {
+    RayRow r;
+    r.d.x = (float)dgemm_row(a, b, c, R[0], R[1], R[2]);
+    r.d.y = (float)dgemm_row(a, b, c, R[3], R[4], R[5]);
+    r.d.z = (float)dgemm_row(a, b, c, R[6], R[7], R[8]);
+    r.inv = V3{safe_inv(r.d.x), safe_inv(r.d.y), safe_inv(r.d.z)};
+    r.h = unit_dir(r.d);
+    return r;
 }
 
 // ---- two-line tiles of the scan pipeline ----------------------------------------------------------
@@ -307,9 +329,6 @@ LRC_DI void hit_point(V3 o, V3 d, float t, V3& h, V3& pt) {
 // covers exactly their own 64 rays.  So the mapping is a bijection of the pose's rays for ANY wt: a width that is not the
 // table's costs coherence, never a byte.  wt = 0: 1-D tiles.  Each half of a wave is half of a 1-D tile: rays
 // 64 t + 32 h ... + 31 of 1-D tile t, whose keep mask it fills as one 32-bit word.
-#ifndef LRC_HDI
-#define LRC_HDI __host__ __device__ __forceinline__
-#endif
 //
 // Line-group tiles generalise this to 64 / L columns of L adjacent lines, L in {1, 2, 4}.  `grp` packs the grouping: bit 31
 // set = groups of four lines where there are four, bits 0-30 = split, the first line whose elevation sign differs from line

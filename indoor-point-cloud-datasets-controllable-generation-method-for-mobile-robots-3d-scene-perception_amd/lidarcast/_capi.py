@@ -29,7 +29,7 @@ SYMBOLS = (
     "lrc_cast", "lrc_cast_dev", "lrc_cast_segments", "lrc_cast_segments_dev",
     "lrc_scan_poses", "lrc_scan_poses_dev", "lrc_scan_poses_compact", "lrc_host_alloc", "lrc_host_free",
     "lrc_pipe_create", "lrc_pipe_destroy", "lrc_pipe_submit", "lrc_pipe_wait", "lrc_pipe_records", "lrc_pipe_trace_ms",
-    "lrc_pipe_set_line_width", "lrc_pipe_set_tile_lines",
+    "lrc_pipe_set_line_width", "lrc_pipe_set_tile_lines", "lrc_pipe_set_ray_table",
     "lrc_pipe_submit_sharded", "lrc_pipe_trace_done", "lrc_pipe_scan_gathered", "lrc_pipe_assemble",
     "lrc_scan_angles_dev", "lrc_scan_angles_compact", "lrc_debug_scan_stats",
     "lrc_scan_grid_dev", "lrc_scan_grid_compact", "lrc_scan_rays_compact",
@@ -234,6 +234,7 @@ def load():
         "lrc_pipe_trace_ms": [vp, u64, C.POINTER(C.c_float)],
         "lrc_pipe_set_line_width": [vp, u64],
         "lrc_pipe_set_tile_lines": [vp, C.c_uint32],
+        "lrc_pipe_set_ray_table": [vp, C.c_int],
         "lrc_pipe_submit_sharded": [vp, vp, u64, vp, dbl, vp, vp, C.POINTER(LrcGathered), vp, C.POINTER(u64)],
         "lrc_pipe_trace_done": [vp, u64, vp],
         "lrc_pipe_scan_gathered": [vp, vp, C.POINTER(LrcGathered), vp],

@@ -922,6 +922,12 @@ class ScanPipe:
         only; results do not depend on it (lrc_pipe_set_tile_lines)."""
         check(self._lib.lrc_pipe_set_tile_lines(self._h, int(lines)), "lrc_pipe_set_tile_lines")
 
+    def set_ray_table(self, enable):
+        """1 (default): fused submits prepare a per-submit ray table (direction, reciprocal, unit vector per table row for
+        the rotation of pose 0) that the tracing waves of every pose with that rotation load; 0: every ray is formed from its
+        pose matrix.  Results do not depend on it (lrc_pipe_set_ray_table)."""
+        check(self._lib.lrc_pipe_set_ray_table(self._h, int(bool(enable))), "lrc_pipe_set_ray_table")
+
     # ---- N ranks: ids + keep counts into the caller's send slab, an earlier gathered scan assembled in the launch's front ----
     @staticmethod
     def gathered(all_poses_t, all_prims_t, all_tile_counts_t, poses_per_slab, slab_stride_bytes, own_slab, own_ticket,

@@ -39,6 +39,8 @@ io.t, io.point3, io.sem, io.ins = hits["t"].data_ptr(), hits["point3"].data_ptr(
 io.tile_count = hits["tile_count"].data_ptr()
 io.counts, io.out_xyzl = counts[3].data_ptr(), clouds[3].data_ptr()
 pipe = lidarcast.ScanPipe(scene, P, N)
+if "PIPE_RAY_TABLE" in os.environ:                                      # A/B: 0 = submits without the per-submit ray table
+    pipe.set_ray_table(int(os.environ["PIPE_RAY_TABLE"]))
 print("launch chaining (enabled, supported):", ctx.launch_chaining(), flush=True)
 
 
