@@ -24,6 +24,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "lrc_internal.h"
@@ -1846,14 +1847,8 @@ int lrc_ctx_destroy(lrc_ctx* ctx) {
     if (ctx->stat_scratch) (void)hipFree(ctx->stat_scratch);
     if (ctx->d_noise_tab) (void)hipFree(ctx->d_noise_tab);
     for (hipEvent_t e : ctx->compact_done) if (e) (void)hipEventDestroy(e);
-    for (lrc_ctx::TileScratch* sc : {&ctx->compact_scratch[0], &ctx->compact_scratch[1], &ctx->compact_scratch[2],
-                                     &ctx->compact_scratch[3], &ctx->cloud_scratch}) {
-        if (sc->d_tile_off) (void)hipFree(sc->d_tile_off);
-        if (sc->d_tile_cnt) (void)hipFree(sc->d_tile_cnt);
-        if (sc->d_super_total) (void)hipFree(sc->d_super_total);
-        if (sc->d_super_base) (void)hipFree(sc->d_super_base);
-        if (sc->d_dirs_soa) (void)hipFree(sc->d_dirs_soa);
-    }
+    for (lrc_ctx::TileScratch& sc : ctx->compact_scratch) sc.release();      // (the context's device is current: above)
+    ctx->cloud_scratch.release();
     delete ctx;
     return LRC_OK;
 }
@@ -2148,7 +2143,7 @@ static int ensure_prim_plane(lrc_scene* s, hipStream_t st) {
     LRC_HIP(hipMalloc((void**)&table, T * 32));
     hipError_t e = hipMemsetAsync(table, 0, T * 32, st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(prim_plane_kernel, dim3((uint32_t)((s->info.num_slots + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+        hipLaunchKernelGGL(prim_plane_kernel, dim3((uint32_t)blocks_of(s->info.num_slots, kBlock)), dim3(kBlock), 0, st,
                            (const float4*)s->d_tris, (const uint32_t*)s->d_slot_prim, (const uint32_t*)s->d_slot_label,
                            (uint32_t)s->info.num_slots, (uint32_t)T, table);
         e = hipGetLastError();
@@ -2225,7 +2220,7 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
         if (!s->d_slot_sphere && s->info.num_slots) {
             LRC_HIP(hipMalloc((void**)&s->d_slot_sphere, s->info.num_slots * 16));
             s->info.device_bytes += s->info.num_slots * 16;
-            hipLaunchKernelGGL(slot_sphere_kernel, dim3((uint32_t)((s->info.num_slots + kBlock - 1) / kBlock)), dim3(kBlock),
+            hipLaunchKernelGGL(slot_sphere_kernel, dim3((uint32_t)blocks_of(s->info.num_slots, kBlock)), dim3(kBlock),
                                0, st, (const float*)s->d_slot_box, (uint32_t)s->info.num_slots, s->d_slot_sphere);
         }
         q.slot_sphere = s->d_slot_sphere;
@@ -2290,6 +2285,10 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
 }
 #endif   // LRC_VARIANTS
 
+// stack entries a trace needs = deepest leaf depth (one pending sibling per inner level above it), and the LDS that holds them
+static uint32_t trace_stack_depth(const lrc_scene* s) { return s->info.max_depth < 1 ? 1 : s->info.max_depth; }
+static size_t trace_lds_bytes(uint32_t depth) { return (size_t)depth * kTBlock * sizeof(int); }
+
 // One launch of the trace kernel over p.total rays.  gen: 0 explicit rays, 1 pose x direction table, 2 pose x scan angles,
 // 3 a grid scan (lrc_scan_grid_*: the per-ray kernel here; the packet kernel in the laboratory build), 4 moving-sensor sweeps
 // (motion record x direction table x firing fractions), 5 pose x direction table with seeded sensor noise (p.noise).
@@ -2325,9 +2324,8 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     // the instrumented kernel, which has no tile_count
     if (p.tiles_per_pose == 0u || (p.lean.row == nullptr && !stats)) p.line_tiles = 0u;
     if (p.line_tiles == 0u) p.line_group = 0u;
-    // stack entries needed = deepest leaf depth (one pending sibling per inner level above it)
-    const uint32_t depth = s->info.max_depth < 1 ? 1 : s->info.max_depth;
-    const size_t lds = (size_t)depth * kTBlock * sizeof(int);
+    const uint32_t depth = trace_stack_depth(s);
+    const size_t lds = trace_lds_bytes(depth);
     p.stack_cap = depth;
     // Workgroup -> tile order.  A pose-batched scan deals every pose's tiles to the 8 XCDs in 16 chunks: each XCD works on
     // every pose (the poses of a trajectory cost differently: balance) but always on the same sixteenth-pairs of the scan
@@ -2380,18 +2378,20 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
         p.chain_word = nullptr;
         p.chain_seq = 0;
     }
-#define LRC_LAUNCH(G, S, Q) \
+#define LRC_LAUNCH_Q(G, S, Q) \
     hipLaunchKernelGGL((trace_kernel<G, kLeafW, true, false, S, Q>), dim3((uint32_t)(nblk + p.pre.blocks)), dim3(kTBlock), lds, st, p)
+#define LRC_LAUNCH(G, S) do { if (qn) LRC_LAUNCH_Q(G, S, 1); else LRC_LAUNCH_Q(G, S, 0); } while (0)      // quantised or float32 nodes
     if (stats) {   // per-ray traversal counters (lrc_debug_scan_stats)
-        if (gen == 1) { if (qn) LRC_LAUNCH(1, true, 1); else LRC_LAUNCH(1, true, 0); }
-        else if (gen == 0) { if (qn) LRC_LAUNCH(0, true, 1); else LRC_LAUNCH(0, true, 0); }
+        if (gen == 1) LRC_LAUNCH(1, true);
+        else if (gen == 0) LRC_LAUNCH(0, true);
         else return fail(LRC_ERR_INVALID_ARG, "traversal statistics are not available for the scan-angle generator");
-    } else if (gen == 1) { if (qn) LRC_LAUNCH(1, false, 1); else LRC_LAUNCH(1, false, 0); }
-    else if (gen == 4) { if (qn) LRC_LAUNCH(4, false, 1); else LRC_LAUNCH(4, false, 0); }
-    else if (gen == 5) { if (qn) LRC_LAUNCH(5, false, 1); else LRC_LAUNCH(5, false, 0); }
-    else if (gen == 2) { if (qn) LRC_LAUNCH(2, false, 1); else LRC_LAUNCH(2, false, 0); }
-    else { if (qn) LRC_LAUNCH(0, false, 1); else LRC_LAUNCH(0, false, 0); }
+    } else if (gen == 1) LRC_LAUNCH(1, false);
+    else if (gen == 4) LRC_LAUNCH(4, false);
+    else if (gen == 5) LRC_LAUNCH(5, false);
+    else if (gen == 2) LRC_LAUNCH(2, false);
+    else LRC_LAUNCH(0, false);
 #undef LRC_LAUNCH
+#undef LRC_LAUNCH_Q
     LRC_HIP(hipGetLastError());
     if (p.chain_word) { cx_->chain_seq = p.chain_seq; cx_->chain_stream = st; }
     s->launches += 1;
@@ -2402,21 +2402,29 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
 int lrc_scene_get_occupancy(const lrc_scene* s, int* waves_per_cu, int* vgprs, int* lds_bytes) {
     if (!s) return fail(LRC_ERR_INVALID_ARG, "lrc_scene_get_occupancy: scene is NULL");
     LRC_HIP(hipSetDevice(s->ctx->device));
-    const uint32_t depth = s->info.max_depth < 1 ? 1 : s->info.max_depth;
-    const size_t lds = (size_t)depth * kTBlock * sizeof(int);
+    const size_t lds = trace_lds_bytes(trace_stack_depth(s));
+    // the pose-batched product kernel this scene's scans run: over quantised nodes, or float32 ones
+    const void* const kernel = s->d_nodes_q ? reinterpret_cast<const void*>(&trace_kernel<1, kLeafW, true, false, false, 1>)
+                                            : reinterpret_cast<const void*>(&trace_kernel<1, kLeafW, true, false, false>);
     int blocks = 0;
     hipFuncAttributes attr;
-    if (s->d_nodes_q) {
-        LRC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trace_kernel<1, kLeafW, true, false, false, 1>, kTBlock, lds));
-        LRC_HIP(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&trace_kernel<1, kLeafW, true, false, false, 1>)));
-    } else {
-        LRC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trace_kernel<1, kLeafW, true, false, false>, kTBlock, lds));
-        LRC_HIP(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&trace_kernel<1, kLeafW, true, false, false>)));
-    }
+    LRC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, kTBlock, lds));
+    LRC_HIP(hipFuncGetAttributes(&attr, kernel));
     if (waves_per_cu) *waves_per_cu = blocks * (kTBlock / 64);
     if (vgprs) *vgprs = attr.numRegs;
     if (lds_bytes) *lds_bytes = (int)lds;
     return LRC_OK;
+}
+
+// The TraceParams fields every scan fills alike: `total` rays in poses of `rays_per_pose` (at least 1: the kernel divides by
+// it), the range filter about the pose centres and, where the caller has one, the record set to write.
+static void scan_fields(TraceParams& p, uint64_t rays_per_pose, uint64_t total, double max_range, const lrc_hits* out,
+                        bool has_center = true) {
+    p.rays_per_pose = rays_per_pose ? rays_per_pose : 1;
+    p.total = total;
+    p.has_center = has_center;
+    p.max_range = max_range;
+    if (out) p.out = *out;
 }
 
 int lrc_cast_dev(lrc_scene* s, const float* d_rays6, uint64_t n, const double* center3,
@@ -2426,12 +2434,8 @@ int lrc_cast_dev(lrc_scene* s, const float* d_rays6, uint64_t n, const double* c
     LRC_HIP(hipSetDevice(s->ctx->device));
     TraceParams p{};
     p.rays6 = d_rays6;
-    p.total = n;
-    p.rays_per_pose = n ? n : 1;
-    p.has_center = center3 != nullptr;
+    scan_fields(p, n, n, max_range, d_out, center3 != nullptr);
     if (center3) { p.cx = center3[0]; p.cy = center3[1]; p.cz = center3[2]; }
-    p.max_range = max_range;
-    p.out = *d_out;
     return launch_trace(s, p, 0, (hipStream_t)stream);
 }
 
@@ -2448,11 +2452,7 @@ int lrc_cast_segments_dev(lrc_scene* s, const float* d_rays6, uint64_t n, const 
     p.seg_offsets = d_seg_offsets;
     p.seg_centers3 = d_centers3;
     p.num_segments = (uint32_t)num_segments;
-    p.total = n;
-    p.rays_per_pose = n ? n : 1;
-    p.has_center = 1;
-    p.max_range = max_range;
-    p.out = *d_out;
+    scan_fields(p, n, n, max_range, d_out);
     return launch_trace(s, p, 0, (hipStream_t)stream);
 }
 
@@ -2465,11 +2465,7 @@ int lrc_scan_poses_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const 
     TraceParams p{};
     p.poses16 = d_poses16;
     p.dirs3 = d_dirs3;
-    p.rays_per_pose = N ? N : 1;
-    p.total = P * N;
-    p.has_center = 1;
-    p.max_range = max_range;
-    p.out = *d_out;
+    scan_fields(p, N, P * N, max_range, d_out);
     return launch_trace(s, p, 1, (hipStream_t)stream);
 }
 
@@ -2483,11 +2479,7 @@ int lrc_scan_sweeps_dev(lrc_scene* s, const double* d_motion24, uint64_t P, cons
     p.motion24 = d_motion24;
     p.dirs3 = d_dirs3;
     p.fire = d_fire;
-    p.rays_per_pose = N ? N : 1;
-    p.total = P * N;
-    p.has_center = 1;
-    p.max_range = max_range;
-    p.out = *d_out;
+    scan_fields(p, N, P * N, max_range, d_out);
     return launch_trace(s, p, 4, (hipStream_t)stream);
 }
 
@@ -2504,12 +2496,22 @@ int lrc_scan_noisy_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const 
     if (rc) return rc;
     p.poses16 = d_poses16;
     p.dirs3 = d_dirs3;
-    p.rays_per_pose = N ? N : 1;
-    p.total = P * N;
-    p.has_center = 1;
-    p.max_range = max_range;
-    p.out = *d_out;
+    scan_fields(p, N, P * N, max_range, d_out);
     return launch_trace(s, p, 5, (hipStream_t)stream);
+}
+
+int lrc_scan_angles_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_angles2,
+                        const uint8_t* d_keep, uint64_t N, double max_range, const lrc_hits* d_out, void* stream) {
+    if (!s || !d_out) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_angles_dev: NULL scene or output");
+    if (P && N && (!d_poses16 || !d_angles2))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_angles_dev: poses16 or angles2 is NULL");
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    TraceParams p{};
+    p.poses16 = d_poses16;
+    p.angles2 = d_angles2;
+    p.keep_mask = d_keep;
+    scan_fields(p, N, P * N, max_range, d_out);
+    return launch_trace(s, p, 2, (hipStream_t)stream);
 }
 
 static int check_grid(const char* who, const lrc_grid* g, uint64_t N) {
@@ -2534,11 +2536,7 @@ int lrc_scan_grid_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const d
     TraceParams p{};
     p.poses16 = d_poses16;
     p.dirs3 = d_dirs3;
-    p.rays_per_pose = N;
-    p.total = P * N;
-    p.has_center = 1;
-    p.max_range = max_range;
-    p.out = *d_out;
+    scan_fields(p, N, P * N, max_range, d_out);
     s->cur_grid = grid;
     rc = launch_trace(s, p, 3, (hipStream_t)stream);
     s->cur_grid = nullptr;
@@ -2549,33 +2547,62 @@ int lrc_scan_grid_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const d
 
 // ---- host-pointer convenience wrappers ---------------------------------------------------------
 namespace {
+// The per-ray columns of lrc_hits that the host-pointer entry points stage, listed ONCE: f(member, elements per ray, slot of
+// the context's staging pool).  The element size is the member's pointer type's.  (t_label and tile_count exist on the
+// device entry points only.)
+template <class F>
+int hits_columns(F&& f) {
+    int rc;
+    if ((rc = f(&lrc_hits::t, 1, kPoolT)) || (rc = f(&lrc_hits::prim, 1, kPoolPrim)) ||
+        (rc = f(&lrc_hits::normal3, 3, kPoolNormal)) || (rc = f(&lrc_hits::point3, 3, kPoolPoint)) ||
+        (rc = f(&lrc_hits::sem, 1, kPoolSem)) || (rc = f(&lrc_hits::ins, 1, kPoolIns)) ||
+        (rc = f(&lrc_hits::incident_deg, 1, kPoolInc)) || (rc = f(&lrc_hits::intensity, 1, kPoolInten)))
+        return rc;
+    return LRC_OK;
+}
+// The columns a compaction reads, listed ONCE: f(record array of lrc_hits, input array of lrc_compact_io, elements per ray).
+template <class F>
+int record_columns(F&& f) {
+    int rc;
+    if ((rc = f(&lrc_hits::t, &lrc_compact_io::t, 1)) || (rc = f(&lrc_hits::point3, &lrc_compact_io::point3, 3)) ||
+        (rc = f(&lrc_hits::sem, &lrc_compact_io::sem, 1)) || (rc = f(&lrc_hits::ins, &lrc_compact_io::ins, 1)) ||
+        (rc = f(&lrc_hits::incident_deg, &lrc_compact_io::incident_deg, 1)))
+        return rc;
+    return LRC_OK;
+}
+// The compacted columns of a frame, listed ONCE: f(array of lrc_frames, output array of lrc_compact_io, elements per row).
+// A new column is a line here, its allocation in FrameStage::alloc and its store in the scatter kernels.
+template <class F>
+int frame_columns(F&& f) {
+    int rc;
+    if ((rc = f(&lrc_frames::point3, &lrc_compact_io::out_point3, 3)) || (rc = f(&lrc_frames::sem, &lrc_compact_io::out_sem, 1)) ||
+        (rc = f(&lrc_frames::ins, &lrc_compact_io::out_ins, 1)) ||
+        (rc = f(&lrc_frames::incident_deg, &lrc_compact_io::out_incident_deg, 1)) ||
+        (rc = f(&lrc_frames::index, &lrc_compact_io::out_index, 1)) || (rc = f(&lrc_frames::xyzl, &lrc_compact_io::out_xyzl, 4)) ||
+        (rc = f(&lrc_frames::range_origin, &lrc_compact_io::out_range_origin, 1)))
+        return rc;
+    return LRC_OK;
+}
+// device arrays (context pool) for the columns of `h` the caller asked for, and their way home
 struct HitsStage {
-    DevBuf t, prim, normal3, point3, sem, ins, inc, inten;
     lrc_hits d{};
     int alloc(lrc_ctx* ctx, const lrc_hits& h, uint64_t n) {
         if (!n) return LRC_OK;
-        int rc;
-        if (h.t) { if ((rc = t.get(ctx, kPoolT, n * 4))) return rc; d.t = (float*)t.p; }
-        if (h.prim) { if ((rc = prim.get(ctx, kPoolPrim, n * 4))) return rc; d.prim = (uint32_t*)prim.p; }
-        if (h.normal3) { if ((rc = normal3.get(ctx, kPoolNormal, n * 12))) return rc; d.normal3 = (float*)normal3.p; }
-        if (h.point3) { if ((rc = point3.get(ctx, kPoolPoint, n * 12))) return rc; d.point3 = (float*)point3.p; }
-        if (h.sem) { if ((rc = sem.get(ctx, kPoolSem, n * 2))) return rc; d.sem = (uint16_t*)sem.p; }
-        if (h.ins) { if ((rc = ins.get(ctx, kPoolIns, n * 2))) return rc; d.ins = (uint16_t*)ins.p; }
-        if (h.incident_deg) { if ((rc = inc.get(ctx, kPoolInc, n * 8))) return rc; d.incident_deg = (double*)inc.p; }
-        if (h.intensity) { if ((rc = inten.get(ctx, kPoolInten, n * 4))) return rc; d.intensity = (float*)inten.p; }
-        return LRC_OK;
+        return hits_columns([&](auto col, size_t per_ray, int slot) -> int {
+            if (!(h.*col)) return LRC_OK;
+            DevBuf b;      // a pool slot: the context keeps it
+            int rc = b.get(ctx, slot, n * per_ray * sizeof(*(h.*col)));
+            if (rc) return rc;
+            d.*col = static_cast<std::remove_reference_t<decltype(d.*col)>>(b.p);
+            return LRC_OK;
+        });
     }
     int download(const lrc_hits& h, uint64_t n) {
         if (!n) return LRC_OK;
-        if (h.t) LRC_HIP(hipMemcpy(h.t, d.t, n * 4, hipMemcpyDeviceToHost));
-        if (h.prim) LRC_HIP(hipMemcpy(h.prim, d.prim, n * 4, hipMemcpyDeviceToHost));
-        if (h.normal3) LRC_HIP(hipMemcpy(h.normal3, d.normal3, n * 12, hipMemcpyDeviceToHost));
-        if (h.point3) LRC_HIP(hipMemcpy(h.point3, d.point3, n * 12, hipMemcpyDeviceToHost));
-        if (h.sem) LRC_HIP(hipMemcpy(h.sem, d.sem, n * 2, hipMemcpyDeviceToHost));
-        if (h.ins) LRC_HIP(hipMemcpy(h.ins, d.ins, n * 2, hipMemcpyDeviceToHost));
-        if (h.incident_deg) LRC_HIP(hipMemcpy(h.incident_deg, d.incident_deg, n * 8, hipMemcpyDeviceToHost));
-        if (h.intensity) LRC_HIP(hipMemcpy(h.intensity, d.intensity, n * 4, hipMemcpyDeviceToHost));
-        return LRC_OK;
+        return hits_columns([&](auto col, size_t per_ray, int) -> int {
+            if (h.*col) LRC_HIP(hipMemcpy(h.*col, d.*col, n * per_ray * sizeof(*(h.*col)), hipMemcpyDeviceToHost));
+            return LRC_OK;
+        });
     }
 };
 // host entry points: lrc_scan_options.range_noise is a HOST array; stage it in HBM for the call
@@ -2597,6 +2624,34 @@ struct NoiseStage {
     }
     ~NoiseStage() { if (s) s->opts.range_noise = host; }
 };
+// An input array of a host-pointer entry point: `count` elements into slot `slot` of the context's staging pool, copied
+// there before this returns or, with `async`, on that stream (the one that consumes them).
+template <class T>
+int stage_input(lrc_ctx* ctx, int slot, const T* host, size_t count, const T** dev, const hipStream_t* async = nullptr) {
+    DevBuf b;      // a pool slot: the context keeps it
+    int rc = b.get(ctx, slot, count * sizeof(T));
+    if (rc) return rc;
+    if (async) LRC_HIP(hipMemcpyAsync(b.p, host, count * sizeof(T), hipMemcpyHostToDevice, *async));
+    else LRC_HIP(hipMemcpy(b.p, host, count * sizeof(T), hipMemcpyHostToDevice));
+    *dev = static_cast<const T*>(b.p);
+    return LRC_OK;
+}
+// What lrc_cast, lrc_cast_segments and lrc_scan_poses share around their *_dev call: device arrays for the columns asked
+// for and the scene's host noise array staged for the call (restored on every exit), then -- when the call went through --
+// one synchronisation and the columns brought home.
+struct HostScan {
+    HitsStage st;
+    NoiseStage ns;
+    int begin(lrc_scene* s, const lrc_hits& out, uint64_t n) {
+        int rc = st.alloc(s->ctx, out, n);
+        return rc ? rc : ns.begin(s, n);
+    }
+    int finish(int rc, const lrc_hits& out, uint64_t n) {
+        if (rc) return rc;
+        LRC_HIP(hipDeviceSynchronize());
+        return st.download(out, n);
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -2607,18 +2662,12 @@ int lrc_cast(lrc_scene* s, const float* rays6, uint64_t n, const double* center3
     if (n && !rays6) return fail(LRC_ERR_INVALID_ARG, "lrc_cast: rays6 is NULL");
     if (!n) return LRC_OK;
     LRC_HIP(hipSetDevice(s->ctx->device));
-    DevBuf rays;
-    int rc = rays.get(s->ctx, kPoolRays, n * 24);
+    const float* d_rays = nullptr;
+    int rc = stage_input(s->ctx, kPoolRays, rays6, n * 6, &d_rays);
     if (rc) return rc;
-    LRC_HIP(hipMemcpy(rays.p, rays6, n * 24, hipMemcpyHostToDevice));
-    HitsStage st;
-    if ((rc = st.alloc(s->ctx, *out, n))) return rc;
-    NoiseStage ns;
-    if ((rc = ns.begin(s, n))) return rc;
-    rc = lrc_cast_dev(s, (const float*)rays.p, n, center3, max_range, &st.d, nullptr);
-    if (rc) return rc;
-    LRC_HIP(hipDeviceSynchronize());
-    return st.download(*out, n);
+    HostScan hs;
+    if ((rc = hs.begin(s, *out, n))) return rc;
+    return hs.finish(lrc_cast_dev(s, d_rays, n, center3, max_range, &hs.st.d, nullptr), *out, n);
 }
 
 int lrc_cast_segments(lrc_scene* s, const float* rays6, uint64_t n, const uint64_t* seg_offsets,
@@ -2633,23 +2682,17 @@ int lrc_cast_segments(lrc_scene* s, const float* rays6, uint64_t n, const uint64
         if (seg_offsets[k] > seg_offsets[k + 1])
             return fail(LRC_ERR_INVALID_ARG, "lrc_cast_segments: offsets must be non-decreasing");
     LRC_HIP(hipSetDevice(s->ctx->device));
-    DevBuf rays, offs, cen;
+    const float* d_rays = nullptr;
+    const uint64_t* d_offs = nullptr;
+    const double* d_cen = nullptr;
     int rc;
-    if ((rc = rays.get(s->ctx, kPoolRays, n * 24)) || (rc = offs.get(s->ctx, kPoolOffs, (num_segments + 1) * 8)) ||
-        (rc = cen.get(s->ctx, kPoolCen, num_segments * 24)))
+    if ((rc = stage_input(s->ctx, kPoolRays, rays6, n * 6, &d_rays)) ||
+        (rc = stage_input(s->ctx, kPoolOffs, seg_offsets, num_segments + 1, &d_offs)) ||
+        (rc = stage_input(s->ctx, kPoolCen, centers3, num_segments * 3, &d_cen)))
         return rc;
-    LRC_HIP(hipMemcpy(rays.p, rays6, n * 24, hipMemcpyHostToDevice));
-    LRC_HIP(hipMemcpy(offs.p, seg_offsets, (num_segments + 1) * 8, hipMemcpyHostToDevice));
-    LRC_HIP(hipMemcpy(cen.p, centers3, num_segments * 24, hipMemcpyHostToDevice));
-    HitsStage st;
-    if ((rc = st.alloc(s->ctx, *out, n))) return rc;
-    NoiseStage ns;
-    if ((rc = ns.begin(s, n))) return rc;
-    rc = lrc_cast_segments_dev(s, (const float*)rays.p, n, (const uint64_t*)offs.p, num_segments,
-                               (const double*)cen.p, max_range, &st.d, nullptr);
-    if (rc) return rc;
-    LRC_HIP(hipDeviceSynchronize());
-    return st.download(*out, n);
+    HostScan hs;
+    if ((rc = hs.begin(s, *out, n))) return rc;
+    return hs.finish(lrc_cast_segments_dev(s, d_rays, n, d_offs, num_segments, d_cen, max_range, &hs.st.d, nullptr), *out, n);
 }
 
 int lrc_scan_poses(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,
@@ -2660,79 +2703,31 @@ int lrc_scan_poses(lrc_scene* s, const double* poses16, uint64_t P, const double
     const uint64_t n = P * N;
     if (!n) return LRC_OK;
     LRC_HIP(hipSetDevice(s->ctx->device));
-    DevBuf dp, dd;
+    const double *d_poses = nullptr, *d_dirs = nullptr;
     int rc;
-    if ((rc = dp.get(s->ctx, kPoolPoses, P * 128)) || (rc = dd.get(s->ctx, kPoolDirs, N * 24))) return rc;
-    LRC_HIP(hipMemcpy(dp.p, poses16, P * 128, hipMemcpyHostToDevice));
-    LRC_HIP(hipMemcpy(dd.p, dirs3, N * 24, hipMemcpyHostToDevice));
-    HitsStage st;
-    if ((rc = st.alloc(s->ctx, *out, n))) return rc;
-    NoiseStage ns;
-    if ((rc = ns.begin(s, n))) return rc;
-    rc = lrc_scan_poses_dev(s, (const double*)dp.p, P, (const double*)dd.p, N, max_range, &st.d, nullptr);
-    if (rc) return rc;
-    LRC_HIP(hipDeviceSynchronize());
-    return st.download(*out, n);
+    if ((rc = stage_input(s->ctx, kPoolPoses, poses16, P * 16, &d_poses)) ||
+        (rc = stage_input(s->ctx, kPoolDirs, dirs3, N * 3, &d_dirs)))
+        return rc;
+    HostScan hs;
+    if ((rc = hs.begin(s, *out, n))) return rc;
+    return hs.finish(lrc_scan_poses_dev(s, d_poses, P, d_dirs, N, max_range, &hs.st.d, nullptr), *out, n);
 }
 
-static int ensure_tile_scratch(lrc_ctx* ctx, lrc_ctx::TileScratch& sc, uint64_t ntiles);
-static int compact_scratch_for(lrc_ctx* ctx, hipStream_t st, uint64_t ntiles, int* out_set);
+// ---- compaction: tile scratch, the scan chain, lrc_compact_dev ---------------------------------------------------------
+// the grid of a kBlock kernel that gives every tile of 64 entries one wave
+static uint64_t tile_blocks(uint64_t ntiles) { return blocks_of(ntiles, kBlock / 64); }
 
-// the launches of a compaction on stream `st` with scratch set `sc` (sized by the caller for nseg * ceil(seg_len / 64) tiles)
-static int enqueue_compaction(lrc_ctx::TileScratch& sc, uint64_t nseg, uint64_t seg_len, const lrc_compact_io* io, hipStream_t st) {
-    const uint64_t tps = (seg_len + 63) / 64;
-    const uint64_t ntiles = nseg * tps;
-    const uint64_t nblocks = (ntiles + kBlock / 64 - 1) / (kBlock / 64);
-    // the trace kernel can hand over its per-wave keep counts (lrc_hits.tile_count) when tiles line up
-    const uint32_t* cnt = (io->tile_count && seg_len % 64 == 0) ? io->tile_count : nullptr;
-    if (!cnt) {
-        hipLaunchKernelGGL(compact_count_kernel, dim3((uint32_t)nblocks), dim3(kBlock), 0, st, io->t, seg_len,
-                           tps, ntiles, sc.d_tile_cnt);
-        cnt = sc.d_tile_cnt;
-    }
-    const uint64_t nsuper = (ntiles + 1023) / 1024;
-    hipLaunchKernelGGL(compact_scan_kernel, dim3((uint32_t)nsuper), dim3(64), 0, st, cnt, ntiles, (uint64_t)0,
-                       sc.d_tile_off, ntiles, sc.d_super_total);
-    // few super tiles (a C3 scan has 64): every scatter wave sums the totals in front of it itself, one launch less
-    const bool inline_bases = nsuper <= 512;
-    if (!inline_bases)
-        hipLaunchKernelGGL(compact_base_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)sc.d_super_total,
-                           sc.d_super_base, nsuper);
-    // the scatter grid must also cover the threads that write the per-segment counts (one per segment)
-    const uint64_t need = io->counts ? (nseg + kBlock - 1) / kBlock : 0;
-    const uint64_t grid = nblocks > need ? nblocks : need;
-    hipLaunchKernelGGL(compact_scatter_kernel, dim3((uint32_t)grid), dim3(kBlock), 0, st, *io, seg_len, tps,
-                       ntiles, nseg, (const uint32_t*)sc.d_tile_off, (const uint64_t*)sc.d_super_base, (uint64_t)0,
-                       inline_bases ? (const uint32_t*)sc.d_super_total : (const uint32_t*)nullptr);
-    LRC_HIP(hipGetLastError());
-    return LRC_OK;
-}
-
-
-int lrc_compact_dev(lrc_ctx* ctx, uint64_t nseg, uint64_t seg_len, const lrc_compact_io* io,
-                    void* stream) {
-    if (!ctx || !io) return fail(LRC_ERR_INVALID_ARG, "lrc_compact_dev: NULL argument");
-    if (nseg == 0 || seg_len == 0) return LRC_OK;
-    if (!io->t) return fail(LRC_ERR_INVALID_ARG, "lrc_compact_dev: t is NULL");
-    if (((io->out_point3 || io->out_xyzl || io->out_range_origin) && !io->point3) || (io->out_sem && !io->sem) ||
-        (io->out_ins && !io->ins) || (io->out_incident_deg && !io->incident_deg))
-        return fail(LRC_ERR_INVALID_ARG, "lrc_compact_dev: an output is requested without its input");
-    LRC_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t tps = (seg_len + 63) / 64;
-    const uint64_t ntiles = nseg * tps;
-    const uint64_t nblocks = (ntiles + kBlock / 64 - 1) / (kBlock / 64);
-    if (nblocks > 0x7FFFFFFFull) return fail(LRC_ERR_INVALID_ARG, "lrc_compact_dev: too many entries");
-    int set = -1;
-    {
-        int rc_scratch = compact_scratch_for(ctx, st, ntiles, &set);
-        if (rc_scratch) return rc_scratch;
-    }
-    {
-        int rc_enq = enqueue_compaction(ctx->compact_scratch[set], nseg, seg_len, io, st);
-        if (rc_enq) return rc_enq;
-    }
-    LRC_HIP(hipEventRecord(ctx->compact_done[set], st));
+// Scratch for `ntiles` tiles.  Growing frees the old arrays -- the transposed direction table too: both its users make it
+// again behind this call -- so the caller has made the device current and nothing may still read them.
+static int ensure_tile_scratch(lrc_ctx::TileScratch& sc, uint64_t ntiles) {
+    if (sc.tile_cap >= ntiles + 1) return LRC_OK;
+    sc.release();
+    const uint64_t nsuper = blocks_of(ntiles, 1024);
+    LRC_HIP(hipMalloc((void**)&sc.d_tile_off, (ntiles + 1) * 4));
+    LRC_HIP(hipMalloc((void**)&sc.d_tile_cnt, (ntiles + 1) * 4));
+    LRC_HIP(hipMalloc((void**)&sc.d_super_total, (nsuper + 1) * 4));
+    LRC_HIP(hipMalloc((void**)&sc.d_super_base, (nsuper + 1) * 8));
+    sc.tile_cap = ntiles + 1;
     return LRC_OK;
 }
 
@@ -2756,22 +2751,80 @@ static int compact_scratch_for(lrc_ctx* ctx, hipStream_t st, uint64_t ntiles, in
         LRC_HIP(hipEventSynchronize(ctx->compact_done[set]));
     }
     *out_set = set;
-    return ensure_tile_scratch(ctx, sc, ntiles);
+    return ensure_tile_scratch(sc, ntiles);
 }
 
-static int ensure_tile_scratch(lrc_ctx* ctx, lrc_ctx::TileScratch& sc, uint64_t ntiles) {
-    (void)ctx;
-    if (sc.tile_cap >= ntiles + 1) return LRC_OK;
-    if (sc.d_tile_off) { (void)hipFree(sc.d_tile_off); sc.d_tile_off = nullptr; }
-    if (sc.d_tile_cnt) { (void)hipFree(sc.d_tile_cnt); sc.d_tile_cnt = nullptr; }
-    if (sc.d_super_total) { (void)hipFree(sc.d_super_total); sc.d_super_total = nullptr; }
-    if (sc.d_super_base) { (void)hipFree(sc.d_super_base); sc.d_super_base = nullptr; }
-    sc.tile_cap = 0;
-    LRC_HIP(hipMalloc((void**)&sc.d_tile_off, (ntiles + 1) * 4));
-    LRC_HIP(hipMalloc((void**)&sc.d_tile_cnt, (ntiles + 1) * 4));
-    LRC_HIP(hipMalloc((void**)&sc.d_super_total, ((ntiles + 1023) / 1024 + 1) * 4));
-    LRC_HIP(hipMalloc((void**)&sc.d_super_base, ((ntiles + 1023) / 1024 + 1) * 8));
-    sc.tile_cap = ntiles + 1;
+// The scan chain on `st`: per-tile keep counts `cnt` (tiles_per_slab of them every slab_stride words; stride 0: one run) ->
+// sc's offsets inside super tiles of 1024 tiles and the super tiles' totals, and, with `bases`, the totals' exclusive prefix
+// (a scatter over few super tiles sums the totals in front of it itself).
+static void launch_scan_chain(lrc_ctx::TileScratch& sc, const uint32_t* cnt, uint64_t tiles_per_slab, uint64_t slab_stride,
+                              uint64_t ntiles, bool bases, hipStream_t st) {
+    const uint64_t nsuper = blocks_of(ntiles, 1024);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3((uint32_t)nsuper), dim3(64), 0, st, cnt, tiles_per_slab, slab_stride,
+                       sc.d_tile_off, ntiles, sc.d_super_total);
+    if (bases)
+        hipLaunchKernelGGL(compact_base_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)sc.d_super_total,
+                           sc.d_super_base, nsuper);
+}
+
+// the launches of a compaction on stream `st` with scratch set `sc` (sized by the caller for nseg * ceil(seg_len / 64) tiles)
+static int enqueue_compaction(lrc_ctx::TileScratch& sc, uint64_t nseg, uint64_t seg_len, const lrc_compact_io* io, hipStream_t st) {
+    const uint64_t tps = blocks_of(seg_len, 64);
+    const uint64_t ntiles = nseg * tps;
+    const uint64_t nblocks = tile_blocks(ntiles);
+    // the trace kernel can hand over its per-wave keep counts (lrc_hits.tile_count) when tiles line up
+    const uint32_t* cnt = (io->tile_count && seg_len % 64 == 0) ? io->tile_count : nullptr;
+    if (!cnt) {
+        hipLaunchKernelGGL(compact_count_kernel, dim3((uint32_t)nblocks), dim3(kBlock), 0, st, io->t, seg_len,
+                           tps, ntiles, sc.d_tile_cnt);
+        cnt = sc.d_tile_cnt;
+    }
+    // few super tiles (a C3 scan has 64): every scatter wave sums the totals in front of it itself, one launch less
+    const bool inline_bases = blocks_of(ntiles, 1024) <= 512;
+    launch_scan_chain(sc, cnt, ntiles, 0, ntiles, !inline_bases, st);
+    // the scatter grid must also cover the threads that write the per-segment counts (one per segment)
+    const uint64_t need = io->counts ? blocks_of(nseg, kBlock) : 0;
+    const uint64_t grid = nblocks > need ? nblocks : need;
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3((uint32_t)grid), dim3(kBlock), 0, st, *io, seg_len, tps,
+                       ntiles, nseg, (const uint32_t*)sc.d_tile_off, (const uint64_t*)sc.d_super_base, (uint64_t)0,
+                       inline_bases ? (const uint32_t*)sc.d_super_total : (const uint32_t*)nullptr);
+    LRC_HIP(hipGetLastError());
+    return LRC_OK;
+}
+
+// The rebuild of a gathered scan's rows from its triangle ids: one wave per LRC_REBUILD_R tiles.
+static void launch_prim_scatter(const RebuildParams& q, hipStream_t st) {
+    constexpr int kR = LRC_REBUILD_R;
+    const uint64_t wblocks = tile_blocks(blocks_of(q.ntiles, kR));
+    hipLaunchKernelGGL(prim_scatter_kernel<kR>, dim3((uint32_t)(wblocks ? wblocks : 1)), dim3(kBlock), 0, st, q);
+}
+// ... and the rows of the rank's own poses (own_tiles tiles, tps per pose), straight from its local records `io` to the
+// offsets the rebuild's scan gave them; tile_base: the own slab's first tile in the assembled cloud.
+static void launch_own_rows(const lrc_compact_io& io, uint64_t N, uint64_t tps, uint64_t own_tiles, const RebuildParams& q,
+                            uint64_t tile_base, hipStream_t st) {
+    const uint64_t nblocks = tile_blocks(own_tiles);
+    if (nblocks)
+        hipLaunchKernelGGL(compact_scatter_kernel, dim3((uint32_t)nblocks), dim3(kBlock), 0, st, io, N, tps, own_tiles, own_tiles / tps,
+                           (const uint32_t*)q.tile_off, (const uint64_t*)q.super_base, tile_base, (const uint32_t*)nullptr);
+}
+
+int lrc_compact_dev(lrc_ctx* ctx, uint64_t nseg, uint64_t seg_len, const lrc_compact_io* io,
+                    void* stream) {
+    if (!ctx || !io) return fail(LRC_ERR_INVALID_ARG, "lrc_compact_dev: NULL argument");
+    if (nseg == 0 || seg_len == 0) return LRC_OK;
+    if (!io->t) return fail(LRC_ERR_INVALID_ARG, "lrc_compact_dev: t is NULL");
+    if (((io->out_point3 || io->out_xyzl || io->out_range_origin) && !io->point3) || (io->out_sem && !io->sem) ||
+        (io->out_ins && !io->ins) || (io->out_incident_deg && !io->incident_deg))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_compact_dev: an output is requested without its input");
+    LRC_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t ntiles = nseg * blocks_of(seg_len, 64);
+    if (tile_blocks(ntiles) > 0x7FFFFFFFull) return fail(LRC_ERR_INVALID_ARG, "lrc_compact_dev: too many entries");
+    int set = -1;
+    int rc = compact_scratch_for(ctx, st, ntiles, &set);
+    if (rc) return rc;
+    if ((rc = enqueue_compaction(ctx->compact_scratch[set], nseg, seg_len, io, st))) return rc;
+    LRC_HIP(hipEventRecord(ctx->compact_done[set], st));
     return LRC_OK;
 }
 
@@ -2798,6 +2851,9 @@ static int ensure_tile_scratch(lrc_ctx* ctx, lrc_ctx::TileScratch& sc, uint64_t 
 // write, and what lrc_pipe_records expands a lean set into on demand.
 #ifndef LRC_PIPE_TILE_LINES
 #define LRC_PIPE_TILE_LINES 4      // lines per tile of an automatic submit (profiles/trace_line_group_tiles.txt)
+#endif
+#ifndef LRC_PIPE_SCAN_WAVES
+#define LRC_PIPE_SCAN_WAVES 64     // waves of a submit's scan pass: one per super tile up to this (lrc_pipe_submit says why)
 #endif
 struct lrc_pipe {
     lrc_scene* scene = nullptr;
@@ -2857,14 +2913,8 @@ int lrc_pipe_destroy(lrc_pipe* pp) {
     for (int k = 0; k < 2; ++k) {
         if (pp->ray_tab[k]) (void)hipFree(pp->ray_tab[k]);
         if (pp->ev_flush[k]) (void)hipEventDestroy(pp->ev_flush[k]);
-        for (lrc_ctx::TileScratch* scp : {&pp->scratch[k], &pp->gscratch[k]}) {
-            lrc_ctx::TileScratch& sc = *scp;
-            if (sc.d_tile_off) (void)hipFree(sc.d_tile_off);
-            if (sc.d_tile_cnt) (void)hipFree(sc.d_tile_cnt);
-            if (sc.d_super_total) (void)hipFree(sc.d_super_total);
-            if (sc.d_super_base) (void)hipFree(sc.d_super_base);
-            if (sc.d_dirs_soa) (void)hipFree(sc.d_dirs_soa);
-        }
+        pp->scratch[k].release();        // (the pipeline's device is current: above)
+        pp->gscratch[k].release();
     }
     delete pp;
     return LRC_OK;
@@ -2885,8 +2935,8 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
     pp->max_poses = max_poses;
     pp->rays_per_pose = rays_per_pose;
     const uint64_t n = pp->cap = max_poses * rays_per_pose;
-    const uint64_t tiles = max_poses * ((rays_per_pose + 63) / 64);
-    pp->fused = rays_per_pose % 64 == 0 && (tiles + 1023) / 1024 <= 512;
+    const uint64_t tiles = max_poses * blocks_of(rays_per_pose, 64);
+    pp->fused = rays_per_pose % 64 == 0 && blocks_of(tiles, 1024) <= 512;
     auto bail = [&](int rc) { (void)lrc_pipe_destroy(pp); return rc; };
     auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
     // a record set: t | prim | normal3 | point3 | sem | ins | tile_count, 36 B per ray + 4 B per 64 rays, and for a fused
@@ -2917,7 +2967,7 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
     for (int k = 0; k < 2; ++k) {
         if (hipStreamCreateWithPriority(&pp->s_trace[k], hipStreamNonBlocking, prio_least) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: stream"));
         if (hipEventCreateWithFlags(&pp->ev_flush[k], hipEventDisableTiming) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
-        int rc = ensure_tile_scratch(s->ctx, pp->scratch[k], tiles);
+        int rc = ensure_tile_scratch(pp->scratch[k], tiles);
         if (rc) return bail(rc);
     }
     for (int k = 0; k < lrc_pipe::kSets; ++k) {
@@ -3019,11 +3069,7 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     TraceParams p{};
     p.poses16 = d_poses16;
     p.dirs3 = d_dirs3;
-    p.rays_per_pose = N;
-    p.total = P * N;
-    p.has_center = 1;
-    p.max_range = max_range;
-    p.out = pp->rec[set];
+    scan_fields(p, N, P * N, max_range, &pp->rec[set]);
     if (pp->fused) {           // the lean form: only what the scatter reads (the plain fallback below reads the full record)
         p.lean.row = pp->row[set]; p.lean.aux = pp->aux[set]; p.lean.keep_mask = pp->keep_mask[set];
         // line-group tiles: the hinted line width, or the table's own, detected once per table address -- on the caller's
@@ -3052,7 +3098,7 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     // stream's launch they trickle in during a step that has nothing else for this stream to do)
     pp->ray_tab_last = false;
     if (pp->fused && pp->use_ray_tab && pp->ray_tab[lane]) {
-        const uint64_t rows = N > P ? N : P, waves = (rows + 63) / 64;
+        const uint64_t rows = N > P ? N : P, waves = blocks_of(rows, 64);
         hipLaunchKernelGGL(ray_table_kernel, dim3((uint32_t)(waves < 64 ? waves : 64)), dim3(64), 0, T, d_poses16, (uint32_t)P, d_dirs3,
                            (uint32_t)N, pp->ray_tab[lane]);
         LRC_HIP(hipGetLastError());
@@ -3065,9 +3111,9 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     if (pp->fused && k >= 2 && pp->pending[prev]) {
         pio = pipe_io(pp, prev);
         const uint64_t tps = N / 64, ntiles = pp->poses[prev] * tps;
-        const uint64_t need = pio.counts ? (pp->poses[prev] + kTBlock - 1) / kTBlock : 0;
-        const uint64_t tile_blocks = (ntiles + kPreTiles - 1) / kPreTiles;
-        p.pre.blocks = (uint32_t)(tile_blocks > need ? tile_blocks : need);
+        const uint64_t need = pio.counts ? blocks_of(pp->poses[prev], kTBlock) : 0;
+        const uint64_t pre_blocks = blocks_of(ntiles, kPreTiles);
+        p.pre.blocks = (uint32_t)(pre_blocks > need ? pre_blocks : need);
         p.pre.rows_only = (pio.out_xyzl && !pio.out_point3 && !pio.out_sem && !pio.out_ins && !pio.out_index && !pio.out_range_origin) ? 1u : 0u;
         p.pre.seg_len = N; p.pre.tps = tps; p.pre.ntiles = ntiles; p.pre.nseg = pp->poses[prev];
         p.pre.tile_off = pp->scratch[lane].d_tile_off;
@@ -3090,15 +3136,12 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     if (pp->fused) {
         // the scan pass over this scan's per-wave keep counts: 32-64 one-wave workgroups behind the trace; the rows follow
         // with this stream's next launch (or with lrc_pipe_wait)
-        const uint64_t ntiles = P * (N / 64), nsuper = (ntiles + 1023) / 1024;
+        const uint64_t ntiles = P * (N / 64), nsuper = blocks_of(ntiles, 1024);
         // One wave per super tile.  Beside the other stream's running launch a kernel of this stream is handed a wave slot
         // every few microseconds at best, so in a long run four waves (in within 20 us, 80 us of work each) are 0.4 % ahead of
         // 64 (arriving over 300 us: the next launch of this stream waits behind them) -- but a run ENDS with this pass alone on
         // the GPU, where four waves take 80 us and 64 take 10: over blocks of 20 submits the wide pass is 2.4 % faster, over 300
         // submits 0.4 % slower (profiles/r04_pipe_scan_width.txt).  Callers synchronise more often than every 300 batches.
-#ifndef LRC_PIPE_SCAN_WAVES
-#define LRC_PIPE_SCAN_WAVES 64
-#endif
         // (a lean set's counts are the popcounts of its keep masks; rec's tile_count is filled on the way for lrc_pipe_records)
         hipLaunchKernelGGL(compact_scan_masks_kernel, dim3((uint32_t)(nsuper < LRC_PIPE_SCAN_WAVES ? nsuper : LRC_PIPE_SCAN_WAVES)), dim3(64), 0, T,
                            (const uint64_t*)pp->keep_mask[set], pp->rec[set].tile_count, pp->scratch[lane].d_tile_off, ntiles,
@@ -3147,7 +3190,7 @@ int scan_gathered(lrc_pipe* pp, const lrc_gathered* g, const double* d_dirs3, hi
     lrc_scene* s = pp->scene;
     lrc_ctx::TileScratch& sc = pp->gscratch[g->scan_slot & 1u];
     const uint64_t N = pp->rays_per_pose, tps = N / 64, ntiles = g->num_poses_all * tps;
-    int rc = ensure_tile_scratch(s->ctx, sc, ntiles);
+    int rc = ensure_tile_scratch(sc, ntiles);
     if (rc) return rc;
     if ((rc = ensure_prim_plane(s, st))) return rc;
     // every call: the table may have been edited in place, or be a new one at a recycled address
@@ -3155,9 +3198,9 @@ int scan_gathered(lrc_pipe* pp, const lrc_gathered* g, const double* d_dirs3, hi
         LRC_HIP(hipMalloc((void**)&sc.d_dirs_soa, N * 24));
         sc.dirs_cap = N;
     }
-    const uint64_t stride = g->slab_stride_bytes / 4, nsuper = (ntiles + 1023) / 1024;
+    const uint64_t stride = g->slab_stride_bytes / 4, nsuper = blocks_of(ntiles, 1024);
     // one wave per super tile, at least one per 1024 directions (16 rows of the table per lane), at most scan_waves
-    uint64_t grid = nsuper > (N + 1023) / 1024 ? nsuper : (N + 1023) / 1024;
+    uint64_t grid = nsuper > blocks_of(N, 1024) ? nsuper : blocks_of(N, 1024);
     if (scan_waves > 0 && grid > (uint64_t)scan_waves) grid = (uint64_t)scan_waves;
     hipLaunchKernelGGL(gathered_scan_kernel, dim3((uint32_t)grid), dim3(64), 0, st, g->d_all_tile_counts, g->poses_per_slab * tps, stride,
                        sc.d_tile_off, ntiles, sc.d_super_total, d_dirs3, (uint32_t)N, sc.d_dirs_soa);
@@ -3215,8 +3258,8 @@ int lrc_pipe_submit_sharded(lrc_pipe* pp, const double* d_poses16, uint64_t P, c
     if ((rc = wait_for_readers(pp, set, T))) return rc;
     const uint64_t N = pp->rays_per_pose;
     TraceParams p{};
-    p.poses16 = d_poses16; p.dirs3 = d_dirs3; p.rays_per_pose = N; p.total = P * N; p.has_center = 1; p.max_range = max_range;
-    p.out = pp->rec[set];
+    p.poses16 = d_poses16; p.dirs3 = d_dirs3;
+    scan_fields(p, N, P * N, max_range, &pp->rec[set]);
     p.out.prim = d_send_prim;                  // the 36-byte record stays complete: its id column IS the send slab
     p.out.tile_count = d_send_tile_count;
     lrc_compact_io own_io{};
@@ -3230,9 +3273,9 @@ int lrc_pipe_submit_sharded(lrc_pipe* pp, const double* d_poses16, uint64_t P, c
         p.pre.tile_off = pp->gscratch[assemble->scan_slot & 1u].d_tile_off;
         p.pre.super_base = pp->gscratch[assemble->scan_slot & 1u].d_super_base;
         p.pre.tile_base = tile_base;
-        p.pre.own_blocks = (uint32_t)((own_tiles + kPreTiles - 1) / kPreTiles);
-        const uint64_t rb = ((uint64_t)p.pre.rq.ntiles + LRC_REBUILD_R - 1) / LRC_REBUILD_R;
-        const uint64_t need = ((uint64_t)p.pre.rq.nseg + kTBlock - 1) / kTBlock;        // threads for the per-pose counts
+        p.pre.own_blocks = (uint32_t)blocks_of(own_tiles, kPreTiles);
+        const uint64_t rb = blocks_of(p.pre.rq.ntiles, LRC_REBUILD_R);
+        const uint64_t need = blocks_of(p.pre.rq.nseg, kTBlock);        // threads for the per-pose counts
         uint64_t blocks = p.pre.own_blocks + rb;
         if (blocks < need) blocks = need;
         p.pre.blocks = (uint32_t)blocks;
@@ -3285,14 +3328,8 @@ int lrc_pipe_assemble(lrc_pipe* pp, const double* d_dirs3, const lrc_gathered* g
     lrc_compact_io io{};
     uint64_t own_tiles = 0, tile_base = 0;
     if ((rc = prepare_gathered(pp, g, &q, &io, &own_tiles, &tile_base))) return rc;
-    constexpr int kR = LRC_REBUILD_R;
-    const uint64_t wblocks = (((uint64_t)q.ntiles + kR - 1) / kR + kBlock / 64 - 1) / (kBlock / 64);
-    hipLaunchKernelGGL(prim_scatter_kernel<kR>, dim3((uint32_t)(wblocks ? wblocks : 1)), dim3(kBlock), 0, st, q);
-    const uint64_t N = pp->rays_per_pose, tps = N / 64;
-    const uint64_t nblocks = (own_tiles + kBlock / 64 - 1) / (kBlock / 64);
-    if (nblocks)
-        hipLaunchKernelGGL(compact_scatter_kernel, dim3((uint32_t)nblocks), dim3(kBlock), 0, st, io, N, tps, own_tiles, own_tiles / tps,
-                           (const uint32_t*)q.tile_off, (const uint64_t*)q.super_base, tile_base, (const uint32_t*)nullptr);
+    launch_prim_scatter(q, st);
+    launch_own_rows(io, pp->rays_per_pose, pp->rays_per_pose / 64, own_tiles, q, tile_base, st);
     LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
@@ -3309,8 +3346,8 @@ int lrc_pipe_wait(lrc_pipe* pp, void* stream) {
         if (!pp->pending[set]) continue;
         lrc_compact_io io = pipe_io(pp, set);
         const uint64_t N = pp->rays_per_pose, tps = N / 64, ntiles = pp->poses[set] * tps;
-        const uint64_t nblocks = (ntiles + kBlock / 64 - 1) / (kBlock / 64);
-        const uint64_t need = io.counts ? (pp->poses[set] + kBlock - 1) / kBlock : 0;
+        const uint64_t nblocks = tile_blocks(ntiles);
+        const uint64_t need = io.counts ? blocks_of(pp->poses[set], kBlock) : 0;
         const dim3 grid((uint32_t)(nblocks > need ? nblocks : need));
         if (pp->lean[set])
             hipLaunchKernelGGL(compact_scatter_lean_kernel, grid, dim3(kBlock), 0, pp->s_trace[lane], io, pipe_lean(pp, set), N, tps,
@@ -3343,7 +3380,7 @@ int lrc_pipe_records(lrc_pipe* pp, uint64_t ticket, lrc_hits* out_records) {
         LRC_HIP(hipSetDevice(s->ctx->device));
         hipStream_t T = pp->s_trace[(ticket - 1) % 2];
         const uint64_t n = pp->poses[set] * pp->rays_per_pose;
-        hipLaunchKernelGGL(expand_lean_kernel, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, T,
+        hipLaunchKernelGGL(expand_lean_kernel, dim3((uint32_t)blocks_of(n, kBlock)), dim3(kBlock), 0, T,
                            (const float4*)pp->row[set], (const uint2*)pp->aux[set], (const uint32_t*)s->d_slot_prim,
                            (const float4*)s->d_tris, pp->rec[set], n);
         LRC_HIP(hipGetLastError());
@@ -3375,20 +3412,16 @@ int lrc_cloud_from_ranges_dev(lrc_ctx* ctx, const double* d_poses16, uint64_t P,
         return fail(LRC_ERR_INVALID_ARG, "lrc_cloud_from_ranges_dev: NULL argument");
     LRC_HIP(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t tps = (N + 63) / 64, ntiles = P * tps;
-    const uint64_t nblocks = (ntiles + kBlock / 64 - 1) / (kBlock / 64);
+    const uint64_t tps = blocks_of(N, 64), ntiles = P * tps;
+    const uint64_t nblocks = tile_blocks(ntiles);
     if (nblocks > 0x7FFFFFFFull) return fail(LRC_ERR_INVALID_ARG, "lrc_cloud_from_ranges_dev: too many entries");
     lrc_ctx::TileScratch& sc = ctx->cloud_scratch;
-    int rc = ensure_tile_scratch(ctx, sc, ntiles);
+    int rc = ensure_tile_scratch(sc, ntiles);
     if (rc) return rc;
-    const uint64_t nsuper = (ntiles + 1023) / 1024;
     hipLaunchKernelGGL(cloud_count_kernel, dim3((uint32_t)nblocks), dim3(kBlock), 0, st, (const uint2*)d_t_label, N,
                        tps, ntiles, sc.d_tile_cnt);
-    hipLaunchKernelGGL(compact_scan_kernel, dim3((uint32_t)nsuper), dim3(64), 0, st,
-                       (const uint32_t*)sc.d_tile_cnt, ntiles, (uint64_t)0, sc.d_tile_off, ntiles, sc.d_super_total);
-    hipLaunchKernelGGL(compact_base_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)sc.d_super_total,
-                       sc.d_super_base, nsuper);
-    const uint64_t need = d_counts ? (P + kBlock - 1) / kBlock : 0;
+    launch_scan_chain(sc, sc.d_tile_cnt, ntiles, 0, ntiles, true, st);
+    const uint64_t need = d_counts ? blocks_of(P, kBlock) : 0;
     const uint64_t grid = nblocks > need ? nblocks : need;
     hipLaunchKernelGGL(cloud_scatter_kernel, dim3((uint32_t)grid), dim3(kBlock), 0, st, d_poses16, d_dirs3,
                        (const uint2*)d_t_label, N, tps, ntiles, P, (const uint32_t*)sc.d_tile_off,
@@ -3408,7 +3441,7 @@ static int prepare_rebuild(lrc_scene* s, const char* who, const double* d_poses1
     if (s->opts.range_noise)
         return bad("a scan with range noise cannot be rebuilt from triangle ids; gather (t,label) pairs "
                    "(lrc_cloud_from_ranges_dev)");
-    const uint64_t tps = (N + 63) / 64, ntiles = P * tps;
+    const uint64_t tps = blocks_of(N, 64), ntiles = P * tps;
     if (poses_per_slab == 0 || poses_per_slab >= P) { poses_per_slab = P; slab_stride_bytes = 0; }
     else if (slab_stride_bytes % 4 || slab_stride_bytes < poses_per_slab * N * 4)
         return bad("slab stride smaller than a slab or not a multiple of 4");
@@ -3416,7 +3449,7 @@ static int prepare_rebuild(lrc_scene* s, const char* who, const double* d_poses1
     if (ntiles > 0x7FFFFFFFull || N > 0x7FFFFFFFull) return bad("too many entries");
     lrc_ctx* ctx = s->ctx;
     lrc_ctx::TileScratch& sc = ctx->cloud_scratch;
-    int rc = ensure_tile_scratch(ctx, sc, ntiles);
+    int rc = ensure_tile_scratch(sc, ntiles);
     if (rc) return rc;
     if ((rc = ensure_prim_plane(s, st))) return rc;
     if (sc.dirs_cap < N) {
@@ -3426,22 +3459,15 @@ static int prepare_rebuild(lrc_scene* s, const char* who, const double* d_poses1
         sc.dirs_cap = N;
     }
     const uint64_t stride = slab_stride_bytes / 4;
-    const uint64_t nsuper = (ntiles + 1023) / 1024;
     if (d_tile_count) {
         // the senders' trace kernels already counted (lrc_hits.tile_count travels in the slab): no counting pass
-        hipLaunchKernelGGL(compact_scan_kernel, dim3((uint32_t)nsuper), dim3(64), 0, st, d_tile_count,
-                           poses_per_slab * tps, stride, sc.d_tile_off, ntiles, sc.d_super_total);
+        launch_scan_chain(sc, d_tile_count, poses_per_slab * tps, stride, ntiles, true, st);
     } else {
-        const uint64_t nblocks = (ntiles + kBlock / 64 - 1) / (kBlock / 64);
-        hipLaunchKernelGGL(prim_count_kernel, dim3((uint32_t)nblocks), dim3(kBlock), 0, st, d_prim, poses_per_slab,
+        hipLaunchKernelGGL(prim_count_kernel, dim3((uint32_t)tile_blocks(ntiles)), dim3(kBlock), 0, st, d_prim, poses_per_slab,
                            stride, N, tps, ntiles, sc.d_tile_cnt);
-        hipLaunchKernelGGL(compact_scan_kernel, dim3((uint32_t)nsuper), dim3(64), 0, st,
-                           (const uint32_t*)sc.d_tile_cnt, ntiles, (uint64_t)0, sc.d_tile_off, ntiles,
-                           sc.d_super_total);
+        launch_scan_chain(sc, sc.d_tile_cnt, ntiles, 0, ntiles, true, st);
     }
-    hipLaunchKernelGGL(compact_base_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)sc.d_super_total,
-                       sc.d_super_base, nsuper);
-    hipLaunchKernelGGL(dirs_transpose_kernel, dim3((uint32_t)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL(dirs_transpose_kernel, dim3((uint32_t)blocks_of(N, kBlock)), dim3(kBlock), 0, st,
                        d_dirs3, (uint32_t)N, sc.d_dirs_soa);
     q->poses16 = d_poses16;
     q->dirs_soa = sc.d_dirs_soa;
@@ -3473,9 +3499,7 @@ int lrc_cloud_from_prims_dev(lrc_scene* s, const double* d_poses16, uint64_t P, 
     int rc = prepare_rebuild(s, "lrc_cloud_from_prims_dev", d_poses16, P, d_dirs3, N, d_prim, d_tile_count,
                              poses_per_slab, slab_stride_bytes, d_out_xyzl, d_counts, st, &q);
     if (rc) return rc;
-    constexpr int kR = LRC_REBUILD_R;
-    const uint64_t wblocks = (((uint64_t)q.ntiles + kR - 1) / kR + kBlock / 64 - 1) / (kBlock / 64);
-    hipLaunchKernelGGL(prim_scatter_kernel<kR>, dim3((uint32_t)(wblocks ? wblocks : 1)), dim3(kBlock), 0, st, q);
+    launch_prim_scatter(q, st);
     LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
@@ -3498,9 +3522,7 @@ int lrc_cloud_from_prims_own_dev(lrc_scene* s, const double* d_poses16, uint64_t
                              poses_per_slab, slab_stride_bytes, d_out_xyzl, d_counts, st, &q);
     if (rc) return rc;
     q.skip_slab = (uint32_t)own_slab;
-    constexpr int kR = LRC_REBUILD_R;
-    const uint64_t wblocks = (((uint64_t)q.ntiles + kR - 1) / kR + kBlock / 64 - 1) / (kBlock / 64);
-    hipLaunchKernelGGL(prim_scatter_kernel<kR>, dim3((uint32_t)(wblocks ? wblocks : 1)), dim3(kBlock), 0, st, q);
+    launch_prim_scatter(q, st);
     // the own poses: rows straight from the local record (what the trace wrote), at the offsets of the assembled cloud
     const uint64_t first_pose = own_slab * poses_per_slab;
     const uint64_t own_poses = first_pose + poses_per_slab <= P ? poses_per_slab : P - first_pose;
@@ -3510,9 +3532,7 @@ int lrc_cloud_from_prims_own_dev(lrc_scene* s, const double* d_poses16, uint64_t
     io.out_point3 = nullptr; io.out_sem = nullptr; io.out_ins = nullptr; io.out_incident_deg = nullptr;
     io.out_index = nullptr; io.out_range_origin = nullptr;
     io.out_xyzl = d_out_xyzl;
-    const uint64_t nblocks = (own_tiles + kBlock / 64 - 1) / (kBlock / 64);
-    hipLaunchKernelGGL(compact_scatter_kernel, dim3((uint32_t)nblocks), dim3(kBlock), 0, st, io, N, tps, own_tiles, own_poses,
-                       (const uint32_t*)q.tile_off, (const uint64_t*)q.super_base, first_pose * tps, (const uint32_t*)nullptr);
+    launch_own_rows(io, N, tps, own_tiles, q, first_pose * tps, st);
     LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
@@ -3526,7 +3546,7 @@ int lrc_cloud_range_stats_dev(lrc_ctx* ctx, const float* d_xyzl, const uint64_t*
     LRC_HIP(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     if (max_rows)
-        hipLaunchKernelGGL(rows_range_kernel, dim3((uint32_t)((max_rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+        hipLaunchKernelGGL(rows_range_kernel, dim3((uint32_t)blocks_of(max_rows, kBlock)), dim3(kBlock), 0, st,
                            (const float4*)d_xyzl, max_rows, d_range);
     const uint64_t need = segment_stats_scratch_values(num_poses, max_rows);
     if (ctx->stat_scratch_cap < need) {
@@ -3547,27 +3567,23 @@ int lrc_compact(lrc_ctx* ctx, uint64_t nseg, uint64_t seg_len, const lrc_compact
     if (!n) return LRC_OK;
     if (!io->t) return fail(LRC_ERR_INVALID_ARG, "lrc_compact: t is NULL");
     LRC_HIP(hipSetDevice(ctx->device));
-    DevBuf t, p3, sem, ins, inc, cnt, op3, osem, oins, oinc, oidx, oxyzl;
+    DevBuf bufs[13];          // allocations of this call: 5 inputs, the counts, 7 outputs
+    int used = 0;
     lrc_compact_io d{};
-    auto up = [&](DevBuf& b, const void* src, size_t bytes, const void** dst) -> int {
+    // `rows` rows of a column of io in HBM, for d's member `col`
+    auto device_column = [&](auto col, uint64_t rows, size_t per_row, bool upload) -> int {
+        DevBuf& b = bufs[used++];
+        const size_t bytes = rows * per_row * sizeof(*(d.*col));
         LRC_HIP(hipMalloc(&b.p, bytes));
-        LRC_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-        *dst = b.p;
+        if (upload) LRC_HIP(hipMemcpy(b.p, io->*col, bytes, hipMemcpyHostToDevice));
+        d.*col = static_cast<std::remove_reference_t<decltype(d.*col)>>(b.p);
         return LRC_OK;
     };
     int rc;
-    if ((rc = up(t, io->t, n * 4, (const void**)&d.t))) return rc;
-    if (io->point3 && (rc = up(p3, io->point3, n * 12, (const void**)&d.point3))) return rc;
-    if (io->sem && (rc = up(sem, io->sem, n * 2, (const void**)&d.sem))) return rc;
-    if (io->ins && (rc = up(ins, io->ins, n * 2, (const void**)&d.ins))) return rc;
-    if (io->incident_deg && (rc = up(inc, io->incident_deg, n * 8, (const void**)&d.incident_deg))) return rc;
-    LRC_HIP(hipMalloc(&cnt.p, nseg * 8)); d.counts = (uint64_t*)cnt.p;
-    if (io->out_point3) { LRC_HIP(hipMalloc(&op3.p, n * 12)); d.out_point3 = (float*)op3.p; }
-    if (io->out_sem) { LRC_HIP(hipMalloc(&osem.p, n * 2)); d.out_sem = (uint16_t*)osem.p; }
-    if (io->out_ins) { LRC_HIP(hipMalloc(&oins.p, n * 2)); d.out_ins = (uint16_t*)oins.p; }
-    if (io->out_incident_deg) { LRC_HIP(hipMalloc(&oinc.p, n * 8)); d.out_incident_deg = (double*)oinc.p; }
-    if (io->out_index) { LRC_HIP(hipMalloc(&oidx.p, n * 4)); d.out_index = (uint32_t*)oidx.p; }
-    if (io->out_xyzl) { LRC_HIP(hipMalloc(&oxyzl.p, n * 16)); d.out_xyzl = (float*)oxyzl.p; }
+    if ((rc = record_columns([&](auto, auto col, size_t per_ray) -> int { return io->*col ? device_column(col, n, per_ray, true) : LRC_OK; })) ||
+        (rc = device_column(&lrc_compact_io::counts, nseg, 1, false)) ||
+        (rc = frame_columns([&](auto, auto col, size_t per_row) -> int { return io->*col ? device_column(col, n, per_row, false) : LRC_OK; })))
+        return rc;
     if ((rc = lrc_compact_dev(ctx, nseg, seg_len, &d, nullptr))) return rc;
     LRC_HIP(hipDeviceSynchronize());
     std::vector<uint64_t> counts(nseg);
@@ -3576,16 +3592,11 @@ int lrc_compact(lrc_ctx* ctx, uint64_t nseg, uint64_t seg_len, const lrc_compact
     for (uint64_t c : counts) K += c;
     if (io->counts) std::memcpy(io->counts, counts.data(), nseg * 8);
     if (out_total) *out_total = K;
-    if (K) {
-        if (io->out_point3) LRC_HIP(hipMemcpy(io->out_point3, d.out_point3, K * 12, hipMemcpyDeviceToHost));
-        if (io->out_sem) LRC_HIP(hipMemcpy(io->out_sem, d.out_sem, K * 2, hipMemcpyDeviceToHost));
-        if (io->out_ins) LRC_HIP(hipMemcpy(io->out_ins, d.out_ins, K * 2, hipMemcpyDeviceToHost));
-        if (io->out_incident_deg)
-            LRC_HIP(hipMemcpy(io->out_incident_deg, d.out_incident_deg, K * 8, hipMemcpyDeviceToHost));
-        if (io->out_index) LRC_HIP(hipMemcpy(io->out_index, d.out_index, K * 4, hipMemcpyDeviceToHost));
-        if (io->out_xyzl) LRC_HIP(hipMemcpy(io->out_xyzl, d.out_xyzl, K * 16, hipMemcpyDeviceToHost));
-    }
-    return LRC_OK;
+    if (!K) return LRC_OK;
+    return frame_columns([&](auto, auto col, size_t per_row) -> int {
+        if (io->*col) LRC_HIP(hipMemcpy(io->*col, d.*col, K * per_row * sizeof(*(d.*col)), hipMemcpyDeviceToHost));
+        return LRC_OK;
+    });
 }
 
 
@@ -3627,7 +3638,7 @@ struct FrameStage {
             if ((rc = fstat.get(ctx, kPoolFrameStats, (P * 4 + 2 * stat_partial) * 8))) return rc;
             d_stats = (double*)fstat.p;
         }
-        if ((rc = tile.get(ctx, kPoolTile, ((n + 63) / 64 + 1) * 4))) return rc;
+        if ((rc = tile.get(ctx, kPoolTile, (blocks_of(n, 64) + 1) * 4))) return rc;
         rec.tile_count = (uint32_t*)tile.p;
         io.t = rec.t; io.point3 = rec.point3; io.sem = rec.sem; io.ins = rec.ins; io.incident_deg = rec.incident_deg;
         io.tile_count = rec.tile_count;
@@ -3653,6 +3664,61 @@ int ensure_streams(lrc_ctx* ctx) {
     for (hipEvent_t& e : ctx->ev_compact)
         if (!e) LRC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return LRC_OK;
+}
+
+// bytes of one row of the columns the caller asked for
+size_t frame_row_bytes(const lrc_frames& out) {
+    size_t bytes = 0;
+    (void)frame_columns([&](auto host, auto, size_t per_row) -> int {
+        if (out.*host) bytes += per_row * sizeof(*(out.*host));
+        return LRC_OK;
+    });
+    return bytes;
+}
+
+// `rows` rows of every column the caller asked for, from device row r0 of the compacted arrays to host row K, on stream `st`
+int copy_frame_rows(const lrc_frames& out, const lrc_compact_io& io, uint64_t r0, uint64_t K, uint64_t rows, hipStream_t st) {
+    return frame_columns([&](auto host, auto dev, size_t per_row) -> int {
+        if (out.*host)
+            LRC_HIP(hipMemcpyAsync(out.*host + K * per_row, io.*dev + r0 * per_row, rows * per_row * sizeof(*(out.*host)),
+                                   hipMemcpyDeviceToHost, st));
+        return LRC_OK;
+    });
+}
+
+// The statistics of poses [p0, p0 + np), whose compacted rows start at device row r0, enqueued on stream `ss` behind those
+// poses' compaction: numpy's arithmetic (lrc_stats.h) over the compacted columns, results into the page-locked area behind
+// the counts.  Floats in the first two blocks of P doubles' worth of space, doubles in the last two.
+int enqueue_frame_stats(lrc_ctx* ctx, const FrameStage& st, const lrc_frames* out, uint64_t P, uint64_t p0, uint64_t np_,
+                        uint64_t r0, hipStream_t ss) {
+    float* rm = (float*)st.d_stats;            float* rs = (float*)(st.d_stats + P);
+    double* im = st.d_stats + 2 * P;           double* is = st.d_stats + 3 * P;
+    double* hs = (double*)(ctx->h_counts + ctx->h_counts_cap);
+    if (out->range_origin_mean || out->range_origin_std) {
+        launch_segment_stats<float>(ss, (const float*)st.io.out_range_origin, (const uint64_t*)(st.io.counts + p0), r0, np_,
+                                    (float*)(st.d_stats + 4 * P) + r0 / 8192 + p0, rm + p0, rs + p0);
+        LRC_HIP(hipMemcpyAsync((float*)hs + p0, rm + p0, np_ * 4, hipMemcpyDeviceToHost, ss));
+        LRC_HIP(hipMemcpyAsync((float*)(hs + ctx->h_counts_cap) + p0, rs + p0, np_ * 4, hipMemcpyDeviceToHost, ss));
+    }
+    if (out->incident_mean || out->incident_std) {
+        launch_segment_stats<double>(ss, (const double*)st.io.out_incident_deg, (const uint64_t*)(st.io.counts + p0), r0, np_,
+                                     st.d_stats + 4 * P + st.stat_partial + r0 / 8192 + p0, im + p0, is + p0);
+        LRC_HIP(hipMemcpyAsync(hs + 2 * ctx->h_counts_cap + p0, im + p0, np_ * 8, hipMemcpyDeviceToHost, ss));
+        LRC_HIP(hipMemcpyAsync(hs + 3 * ctx->h_counts_cap + p0, is + p0, np_ * 8, hipMemcpyDeviceToHost, ss));
+    }
+    LRC_HIP(hipGetLastError());
+    return LRC_OK;
+}
+
+// ... and, once their stream is idle, the P statistics from that area to the caller's arrays
+void publish_frame_stats(const lrc_ctx* ctx, const lrc_frames* out, uint64_t P) {
+    const double* hs = (const double*)(ctx->h_counts + ctx->h_counts_cap);
+    for (uint64_t k = 0; k < P; ++k) {
+        if (out->range_origin_mean) out->range_origin_mean[k] = ((const float*)hs)[k];
+        if (out->range_origin_std) out->range_origin_std[k] = ((const float*)(hs + ctx->h_counts_cap))[k];
+        if (out->incident_mean) out->incident_mean[k] = hs[2 * ctx->h_counts_cap + k];
+        if (out->incident_std) out->incident_std[k] = hs[3 * ctx->h_counts_cap + k];
+    }
 }
 
 // Trace -> compaction -> kept rows to the host, pipelined over contiguous chunks of poses: while chunk c's rows cross
@@ -3709,9 +3775,7 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
     const float* noise = p.range_noise ? p.range_noise : s->opts.range_noise;   // staged in HBM by NoiseStage
     // (the callers enqueue their input copies on the compute stream: nothing to wait for here)
     const uint64_t n_all = P * N;
-    const size_t row_bytes = (out->point3 ? 12 : 0) + (out->sem ? 2 : 0) + (out->ins ? 2 : 0) + (out->incident_deg ? 8 : 0) +
-                             (out->index ? 4 : 0) + (out->xyzl ? 16 : 0) + (out->range_origin ? 4 : 0);
-    if (chunks == 1 && capacity >= n_all && n_all * row_bytes <= (4u << 20)) {
+    if (chunks == 1 && capacity >= n_all && n_all * frame_row_bytes(*out) <= (4u << 20)) {
         // A small call -- the reference's own loop asks for ONE pose per call (s3dis_simulator.py:254-264): everything on
         // one stream and ONE synchronisation.  The rows are copied at their worst-case length together with the counts
         // (a pose's rows are ~1 MB: cheaper than a second round trip to learn the exact length first).
@@ -3726,41 +3790,15 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
         if (rc) return rc;
         if ((rc = lrc_compact_dev(ctx, P, N, &st.io, cs))) return rc;
         LRC_HIP(hipMemcpyAsync(ctx->h_counts, st.io.counts, P * 8, hipMemcpyDeviceToHost, cs));
-        double* hs = (double*)(ctx->h_counts + ctx->h_counts_cap);
-        if (st.d_stats) {
-            float* rm = (float*)st.d_stats;            float* rs = (float*)(st.d_stats + P);
-            double* im = st.d_stats + 2 * P;           double* is = st.d_stats + 3 * P;
-            if (out->range_origin_mean || out->range_origin_std) {
-                launch_segment_stats<float>(cs, (const float*)st.io.out_range_origin, (const uint64_t*)st.io.counts, (uint64_t)0, P,
-                                            (float*)(st.d_stats + 4 * P), rm, rs);
-                LRC_HIP(hipMemcpyAsync((float*)hs, rm, P * 4, hipMemcpyDeviceToHost, cs));
-                LRC_HIP(hipMemcpyAsync((float*)(hs + ctx->h_counts_cap), rs, P * 4, hipMemcpyDeviceToHost, cs));
-            }
-            if (out->incident_mean || out->incident_std) {
-                launch_segment_stats<double>(cs, (const double*)st.io.out_incident_deg, (const uint64_t*)st.io.counts, (uint64_t)0, P,
-                                             st.d_stats + 4 * P + st.stat_partial, im, is);
-                LRC_HIP(hipMemcpyAsync(hs + 2 * ctx->h_counts_cap, im, P * 8, hipMemcpyDeviceToHost, cs));
-                LRC_HIP(hipMemcpyAsync(hs + 3 * ctx->h_counts_cap, is, P * 8, hipMemcpyDeviceToHost, cs));
-            }
-            LRC_HIP(hipGetLastError());
-        }
-        if (out->point3) LRC_HIP(hipMemcpyAsync(out->point3, st.io.out_point3, n_all * 12, hipMemcpyDeviceToHost, cs));
-        if (out->sem) LRC_HIP(hipMemcpyAsync(out->sem, st.io.out_sem, n_all * 2, hipMemcpyDeviceToHost, cs));
-        if (out->ins) LRC_HIP(hipMemcpyAsync(out->ins, st.io.out_ins, n_all * 2, hipMemcpyDeviceToHost, cs));
-        if (out->incident_deg) LRC_HIP(hipMemcpyAsync(out->incident_deg, st.io.out_incident_deg, n_all * 8, hipMemcpyDeviceToHost, cs));
-        if (out->index) LRC_HIP(hipMemcpyAsync(out->index, st.io.out_index, n_all * 4, hipMemcpyDeviceToHost, cs));
-        if (out->xyzl) LRC_HIP(hipMemcpyAsync(out->xyzl, st.io.out_xyzl, n_all * 16, hipMemcpyDeviceToHost, cs));
-        if (out->range_origin) LRC_HIP(hipMemcpyAsync(out->range_origin, st.io.out_range_origin, n_all * 4, hipMemcpyDeviceToHost, cs));
+        if (st.d_stats && (rc = enqueue_frame_stats(ctx, st, out, P, 0, P, 0, cs))) return rc;
+        if ((rc = copy_frame_rows(*out, st.io, 0, 0, n_all, cs))) return rc;
         LRC_HIP(hipStreamSynchronize(cs));
         uint64_t K1 = 0;
         for (uint64_t k = 0; k < P; ++k) {
             out->counts[k] = ctx->h_counts[k];
             K1 += ctx->h_counts[k];
-            if (out->range_origin_mean) out->range_origin_mean[k] = ((const float*)hs)[k];
-            if (out->range_origin_std) out->range_origin_std[k] = ((const float*)(hs + ctx->h_counts_cap))[k];
-            if (out->incident_mean) out->incident_mean[k] = hs[2 * ctx->h_counts_cap + k];
-            if (out->incident_std) out->incident_std[k] = hs[3 * ctx->h_counts_cap + k];
         }
+        publish_frame_stats(ctx, out, P);
         if (out_total) *out_total = K1;
         return LRC_OK;
     }
@@ -3781,52 +3819,32 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
         q.range_noise = nullptr;
         lrc_scan_options saved = s->opts;
         if (noise) { s->opts.range_noise = noise + r0; s->opts.range_noise_len = q.total; }
+        // the chunk's part of the record set, which is also what its compaction reads, and of the compacted arrays
         q.out = st.rec;
-        q.out.t = st.rec.t + r0;
-        if (q.out.point3) q.out.point3 = st.rec.point3 + r0 * 3;
-        if (q.out.sem) q.out.sem = st.rec.sem + r0;
-        if (q.out.ins) q.out.ins = st.rec.ins + r0;
-        if (q.out.incident_deg) q.out.incident_deg = st.rec.incident_deg + r0;
-        q.out.tile_count = st.rec.tile_count + (r0 + 63) / 64;
+        lrc_compact_io io = st.io;
+        (void)record_columns([&](auto hit, auto in, size_t per_ray) -> int {
+            if (st.rec.*hit) q.out.*hit = st.rec.*hit + r0 * per_ray;
+            io.*in = q.out.*hit;
+            return LRC_OK;
+        });
+        q.out.tile_count = st.rec.tile_count + blocks_of(r0, 64);
+        io.tile_count = q.out.tile_count;
+        io.counts = st.io.counts + p0;
+        (void)frame_columns([&](auto, auto dev, size_t per_row) -> int {
+            if (io.*dev) io.*dev = st.io.*dev + r0 * per_row;
+            return LRC_OK;
+        });
         rc = launch_trace(s, q, gen, ctx->s_compute);
         s->opts = saved;
         if (rc) return rc;
-        lrc_compact_io io = st.io;
-        io.t = q.out.t; io.point3 = q.out.point3; io.sem = q.out.sem; io.ins = q.out.ins;
-        io.incident_deg = q.out.incident_deg; io.tile_count = q.out.tile_count;
-        io.counts = st.io.counts + p0;
-        if (io.out_point3) io.out_point3 = st.io.out_point3 + r0 * 3;
-        if (io.out_sem) io.out_sem = st.io.out_sem + r0;
-        if (io.out_ins) io.out_ins = st.io.out_ins + r0;
-        if (io.out_incident_deg) io.out_incident_deg = st.io.out_incident_deg + r0;
-        if (io.out_index) io.out_index = st.io.out_index + r0;
-        if (io.out_xyzl) io.out_xyzl = st.io.out_xyzl + r0 * 4;
-        if (io.out_range_origin) io.out_range_origin = st.io.out_range_origin + r0;
         if ((rc = lrc_compact_dev(ctx, np_, N, &io, ctx->s_compute))) return rc;
         LRC_HIP(hipMemcpyAsync(ctx->h_counts + p0, st.io.counts + p0, np_ * 8, hipMemcpyDeviceToHost, ctx->s_compute));
         LRC_HIP(hipEventRecord(ctx->ev_chunk[c], ctx->s_compute));
         if (st.d_stats) {
-            // per-pose statistics of the compacted columns, numpy's arithmetic (lrc_stats.h), on a stream of their own:
-            // they need this chunk's compaction and nothing else, so they run beside the next chunk's trace and the
-            // row transfers.  Floats in the first two blocks of P doubles' worth of space, doubles in the last two.
-            hipStream_t ss = ctx->s_stats;
-            LRC_HIP(hipStreamWaitEvent(ss, ctx->ev_chunk[c], 0));
-            float* rm = (float*)st.d_stats;            float* rs = (float*)(st.d_stats + P);
-            double* im = st.d_stats + 2 * P;           double* is = st.d_stats + 3 * P;
-            double* hs = (double*)(ctx->h_counts + ctx->h_counts_cap);
-            if (out->range_origin_mean || out->range_origin_std) {
-                launch_segment_stats<float>(ss, (const float*)st.io.out_range_origin, (const uint64_t*)(st.io.counts + p0), r0, np_,
-                                            (float*)(st.d_stats + 4 * P) + r0 / 8192 + p0, rm + p0, rs + p0);
-                LRC_HIP(hipMemcpyAsync((float*)hs + p0, rm + p0, np_ * 4, hipMemcpyDeviceToHost, ss));
-                LRC_HIP(hipMemcpyAsync((float*)(hs + ctx->h_counts_cap) + p0, rs + p0, np_ * 4, hipMemcpyDeviceToHost, ss));
-            }
-            if (out->incident_mean || out->incident_std) {
-                launch_segment_stats<double>(ss, (const double*)st.io.out_incident_deg, (const uint64_t*)(st.io.counts + p0), r0, np_,
-                                             st.d_stats + 4 * P + st.stat_partial + r0 / 8192 + p0, im + p0, is + p0);
-                LRC_HIP(hipMemcpyAsync(hs + 2 * ctx->h_counts_cap + p0, im + p0, np_ * 8, hipMemcpyDeviceToHost, ss));
-                LRC_HIP(hipMemcpyAsync(hs + 3 * ctx->h_counts_cap + p0, is + p0, np_ * 8, hipMemcpyDeviceToHost, ss));
-            }
-            LRC_HIP(hipGetLastError());
+            // on a stream of their own: the statistics need this chunk's compaction and nothing else, so they run beside
+            // the next chunk's trace and the row transfers
+            LRC_HIP(hipStreamWaitEvent(ctx->s_stats, ctx->ev_chunk[c], 0));
+            if ((rc = enqueue_frame_stats(ctx, st, out, P, p0, np_, r0, ctx->s_stats))) return rc;
         }
         p0 = p1;
     }
@@ -3839,18 +3857,7 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
         uint64_t Kc = 0;
         for (uint64_t k = p0; k < p1; ++k) { out->counts[k] = ctx->h_counts[k]; Kc += ctx->h_counts[k]; }
         if (K + Kc > capacity) status = LRC_ERR_INVALID_ARG;        // keep counting: the caller learns the size needed
-        if (status == LRC_OK && Kc) {
-            hipStream_t cs = ctx->s_copy;
-            if (out->point3) LRC_HIP(hipMemcpyAsync(out->point3 + K * 3, st.io.out_point3 + r0 * 3, Kc * 12, hipMemcpyDeviceToHost, cs));
-            if (out->sem) LRC_HIP(hipMemcpyAsync(out->sem + K, st.io.out_sem + r0, Kc * 2, hipMemcpyDeviceToHost, cs));
-            if (out->ins) LRC_HIP(hipMemcpyAsync(out->ins + K, st.io.out_ins + r0, Kc * 2, hipMemcpyDeviceToHost, cs));
-            if (out->incident_deg)
-                LRC_HIP(hipMemcpyAsync(out->incident_deg + K, st.io.out_incident_deg + r0, Kc * 8, hipMemcpyDeviceToHost, cs));
-            if (out->index) LRC_HIP(hipMemcpyAsync(out->index + K, st.io.out_index + r0, Kc * 4, hipMemcpyDeviceToHost, cs));
-            if (out->xyzl) LRC_HIP(hipMemcpyAsync(out->xyzl + K * 4, st.io.out_xyzl + r0 * 4, Kc * 16, hipMemcpyDeviceToHost, cs));
-            if (out->range_origin)
-                LRC_HIP(hipMemcpyAsync(out->range_origin + K, st.io.out_range_origin + r0, Kc * 4, hipMemcpyDeviceToHost, cs));
-        }
+        if (status == LRC_OK && Kc && (rc = copy_frame_rows(*out, st.io, r0, K, Kc, ctx->s_copy))) return rc;
         K += Kc;
         p0 = p1;
     }
@@ -3858,19 +3865,59 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
     LRC_HIP(hipStreamSynchronize(ctx->s_compute));
     if (st.d_stats) {
         LRC_HIP(hipStreamSynchronize(ctx->s_stats));
-        const double* hs = (const double*)(ctx->h_counts + ctx->h_counts_cap);
-        for (uint64_t k = 0; k < P; ++k) {
-            if (out->range_origin_mean) out->range_origin_mean[k] = ((const float*)hs)[k];
-            if (out->range_origin_std) out->range_origin_std[k] = ((const float*)(hs + ctx->h_counts_cap))[k];
-            if (out->incident_mean) out->incident_mean[k] = hs[2 * ctx->h_counts_cap + k];
-            if (out->incident_std) out->incident_std[k] = hs[3 * ctx->h_counts_cap + k];
-        }
+        publish_frame_stats(ctx, out, P);
     }
     if (out_total) *out_total = K;
     if (status != LRC_OK)
         return fail(LRC_ERR_INVALID_ARG, "frame buffers too small: capacity " + std::to_string(capacity) +
                                              " rows, the scan kept " + std::to_string(K));
     return LRC_OK;
+}
+
+// What the *_compact entry points share from their SyncUnlessOk guard on.  The entry point has checked its arguments, made
+// the device current and filled what is its own in `p`; `inputs(up)` stages its input arrays with up(pool slot, host array,
+// elements, &device pointer in p), on the compute stream, which consumes them.  Here: the frame stage, the scene's host
+// noise array, the common TraceParams fields and frames_finish.  gen: the generator (launch_trace); `grid`: a grid scan.
+template <class Inputs>
+int scan_compact(lrc_scene* s, TraceParams& p, int gen, uint64_t P, uint64_t N, double max_range, const lrc_frames* out,
+                 uint64_t capacity, uint64_t* out_total, Inputs&& inputs, const lrc_grid* grid = nullptr) {
+    SyncUnlessOk guard;      // constructed before the first asynchronous upload, destroyed after everything below
+    lrc_ctx* const ctx = s->ctx;
+    const uint64_t n = P * N;
+    int rc;
+    if ((rc = ensure_streams(ctx))) return rc;
+    const hipStream_t in = ctx->s_compute;
+    if ((rc = inputs([&](int slot, auto* host, size_t count, auto** dev) { return stage_input(ctx, slot, host, count, dev, &in); })))
+        return rc;
+    FrameStage st;
+    if ((rc = st.alloc(ctx, *out, P, n))) return rc;
+    NoiseStage ns;           // restores the scene's host pointer on every exit
+    if (gen != 5 && (rc = ns.begin(s, n))) return rc;      // (gen 5 draws its own noise and has refused a range_noise option)
+    scan_fields(p, N, n, max_range, nullptr);
+    s->cur_grid = grid;
+    rc = frames_finish(s, p, gen, st, P, N, out, capacity, out_total);
+    s->cur_grid = nullptr;
+    return guard.done(rc);
+}
+
+// lrc_scan_poses_compact, and behind their own checks lrc_scan_table_compact (d_dirs3: the resident table, nothing to upload)
+// and lrc_scan_grid_compact.  The messages say lrc_scan_poses_compact for all three callers: callers match on them.
+int scan_compact_impl(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,
+                      const lrc_grid* grid, double max_range, const lrc_frames* out, uint64_t capacity,
+                      uint64_t* out_total, const double* d_dirs3 = nullptr) {
+    if (out_total) *out_total = 0;
+    if (!s || !out) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_poses_compact: NULL scene or output");
+    if (!(P * N)) return LRC_OK;
+    if (!poses16 || (!dirs3 && !d_dirs3) || !out->counts)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_poses_compact: poses16, dirs3 or counts is NULL");
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    TraceParams p{};
+    p.dirs3 = d_dirs3;
+    return scan_compact(s, p, grid ? 3 : 1, P, N, max_range, out, capacity, out_total, [&](auto up) {
+        int rc = up(kPoolPoses, poses16, P * 16, &p.poses16);
+        if (rc || d_dirs3) return rc;
+        return up(kPoolDirs, dirs3, N * 3, &p.dirs3);
+    }, grid);
 }
 }  // namespace
 
@@ -3891,10 +3938,6 @@ int lrc_host_free(lrc_ctx* ctx, void* ptr) {
     LRC_HIP(hipHostFree(ptr));
     return LRC_OK;
 }
-
-static int scan_compact_impl(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,
-                             const lrc_grid* grid, double max_range, const lrc_frames* out, uint64_t capacity,
-                             uint64_t* out_total, const double* d_dirs3 = nullptr);
 
 int lrc_table_create(lrc_ctx* ctx, const double* dirs3, uint64_t N, lrc_table** out_table) {
     if (!out_table) return fail(LRC_ERR_INVALID_ARG, "lrc_table_create: out_table is NULL");
@@ -3979,31 +4022,17 @@ int lrc_scan_sweeps_compact(lrc_scene* s, const double* motion24, uint64_t P, co
     if (!s || !out || !table) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_compact: NULL scene, table or output");
     if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_compact: table and scene belong to different contexts");
     if (!table->d_fire) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_compact: the table has no fire table (lrc_table_set_fire)");
-    const uint64_t N = table->n, n = P * N;
-    if (!n) return LRC_OK;
+    const uint64_t N = table->n;
+    if (!(P * N)) return LRC_OK;      // before motion24 is looked at
     if (!motion24 || !out->counts) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_sweeps_compact: motion24 or counts is NULL");
     int rc = check_motion("lrc_scan_sweeps_compact", motion24, P);
     if (rc) return rc;
     LRC_HIP(hipSetDevice(s->ctx->device));
-    SyncUnlessOk guard;
-    DevBuf dm;
-    if ((rc = ensure_streams(s->ctx))) return rc;
-    hipStream_t in = s->ctx->s_compute;       // inputs travel on the stream that consumes them
-    if ((rc = dm.get(s->ctx, kPoolPoses, P * 192))) return rc;
-    LRC_HIP(hipMemcpyAsync(dm.p, motion24, P * 192, hipMemcpyHostToDevice, in));
-    FrameStage st;
-    if ((rc = st.alloc(s->ctx, *out, P, n))) return rc;
-    NoiseStage ns;
-    if ((rc = ns.begin(s, n))) return rc;
     TraceParams p{};
-    p.motion24 = (const double*)dm.p;
     p.dirs3 = table->d_dirs3;
     p.fire = table->d_fire;
-    p.rays_per_pose = N;
-    p.total = n;
-    p.has_center = 1;
-    p.max_range = max_range;
-    return guard.done(frames_finish(s, p, 4, st, P, N, out, capacity, out_total));
+    return scan_compact(s, p, 4, P, N, max_range, out, capacity, out_total,
+                        [&](auto up) { return up(kPoolPoses, motion24, P * 24, &p.motion24); });
 }
 
 int lrc_scan_noisy_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, double max_range,
@@ -4013,28 +4042,16 @@ int lrc_scan_noisy_compact(lrc_scene* s, const double* poses16, uint64_t P, cons
     if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_compact: table and scene belong to different contexts");
     if (s->opts.range_noise)
         return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_compact: a range_noise option is set (one noise source per call)");
-    const uint64_t N = table->n, n = P * N;
+    const uint64_t N = table->n;
     LRC_HIP(hipSetDevice(s->ctx->device));
     TraceParams p{};
-    int rc = noise_params(s->ctx, "lrc_scan_noisy_compact", noise, N, &p.noise);
+    int rc = noise_params(s->ctx, "lrc_scan_noisy_compact", noise, N, &p.noise);      // checked for an empty call too
     if (rc) return rc;
-    if (!n) return LRC_OK;
+    if (!(P * N)) return LRC_OK;
     if (!poses16 || !out->counts) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_compact: poses16 or counts is NULL");
-    SyncUnlessOk guard;
-    DevBuf dp;
-    if ((rc = ensure_streams(s->ctx))) return rc;
-    hipStream_t in = s->ctx->s_compute;       // inputs travel on the stream that consumes them
-    if ((rc = dp.get(s->ctx, kPoolPoses, P * 128))) return rc;
-    LRC_HIP(hipMemcpyAsync(dp.p, poses16, P * 128, hipMemcpyHostToDevice, in));
-    FrameStage st;
-    if ((rc = st.alloc(s->ctx, *out, P, n))) return rc;
-    p.poses16 = (const double*)dp.p;
     p.dirs3 = table->d_dirs3;
-    p.rays_per_pose = N;
-    p.total = n;
-    p.has_center = 1;
-    p.max_range = max_range;
-    return guard.done(frames_finish(s, p, 5, st, P, N, out, capacity, out_total));
+    return scan_compact(s, p, 5, P, N, max_range, out, capacity, out_total,
+                        [&](auto up) { return up(kPoolPoses, poses16, P * 16, &p.poses16); });
 }
 
 int lrc_scan_poses_compact(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,
@@ -4052,64 +4069,6 @@ int lrc_scan_grid_compact(lrc_scene* s, const double* poses16, uint64_t P, const
     return scan_compact_impl(s, poses16, P, dirs3, N, grid, max_range, out, capacity, out_total);
 }
 
-static int scan_compact_impl(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,
-                             const lrc_grid* grid, double max_range, const lrc_frames* out, uint64_t capacity,
-                             uint64_t* out_total, const double* d_dirs3) {
-    if (out_total) *out_total = 0;
-    if (!s || !out) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_poses_compact: NULL scene or output");
-    const uint64_t n = P * N;
-    if (!n) return LRC_OK;
-    if (!poses16 || (!dirs3 && !d_dirs3) || !out->counts)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_poses_compact: poses16, dirs3 or counts is NULL");
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    SyncUnlessOk guard;
-    DevBuf dp, dd;
-    int rc;
-    if ((rc = ensure_streams(s->ctx))) return rc;
-    hipStream_t in = s->ctx->s_compute;       // inputs travel on the stream that consumes them
-    if ((rc = dp.get(s->ctx, kPoolPoses, P * 128))) return rc;
-    LRC_HIP(hipMemcpyAsync(dp.p, poses16, P * 128, hipMemcpyHostToDevice, in));
-    if (d_dirs3) {
-        dd.p = (void*)d_dirs3; dd.pooled = true;            // resident table (lrc_table): nothing to upload
-    } else {
-        if ((rc = dd.get(s->ctx, kPoolDirs, N * 24))) return rc;
-        LRC_HIP(hipMemcpyAsync(dd.p, dirs3, N * 24, hipMemcpyHostToDevice, in));
-    }
-    FrameStage st;
-    if ((rc = st.alloc(s->ctx, *out, P, n))) return rc;
-    NoiseStage ns;
-    if ((rc = ns.begin(s, n))) return rc;
-    TraceParams p{};
-    p.poses16 = (const double*)dp.p;
-    p.dirs3 = (const double*)dd.p;
-    p.rays_per_pose = N;
-    p.total = n;
-    p.has_center = 1;
-    p.max_range = max_range;
-    s->cur_grid = grid;
-    rc = frames_finish(s, p, grid ? 3 : 1, st, P, N, out, capacity, out_total);
-    s->cur_grid = nullptr;
-    return guard.done(rc);
-}
-
-int lrc_scan_angles_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_angles2,
-                        const uint8_t* d_keep, uint64_t N, double max_range, const lrc_hits* d_out, void* stream) {
-    if (!s || !d_out) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_angles_dev: NULL scene or output");
-    if (P && N && (!d_poses16 || !d_angles2))
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_angles_dev: poses16 or angles2 is NULL");
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    TraceParams p{};
-    p.poses16 = d_poses16;
-    p.angles2 = d_angles2;
-    p.keep_mask = d_keep;
-    p.rays_per_pose = N ? N : 1;
-    p.total = P * N;
-    p.has_center = 1;
-    p.max_range = max_range;
-    p.out = *d_out;
-    return launch_trace(s, p, 2, (hipStream_t)stream);
-}
-
 int lrc_scan_angles_compact(lrc_scene* s, const double* poses16, uint64_t P, const double* angles2,
                             const uint8_t* keep, uint64_t N, double max_range, const lrc_frames* out,
                             uint64_t capacity, uint64_t* out_total) {
@@ -4120,31 +4079,12 @@ int lrc_scan_angles_compact(lrc_scene* s, const double* poses16, uint64_t P, con
     if (!poses16 || !angles2 || !out->counts)
         return fail(LRC_ERR_INVALID_ARG, "lrc_scan_angles_compact: poses16, angles2 or counts is NULL");
     LRC_HIP(hipSetDevice(s->ctx->device));
-    SyncUnlessOk guard;
-    DevBuf dp, da, dk;
-    int rc;
-    if ((rc = ensure_streams(s->ctx))) return rc;
-    hipStream_t in = s->ctx->s_compute;
-    if ((rc = dp.get(s->ctx, kPoolPoses, P * 128)) || (rc = da.get(s->ctx, kPoolAngles, n * 16))) return rc;
-    LRC_HIP(hipMemcpyAsync(dp.p, poses16, P * 128, hipMemcpyHostToDevice, in));
-    LRC_HIP(hipMemcpyAsync(da.p, angles2, n * 16, hipMemcpyHostToDevice, in));
-    if (keep) {
-        if ((rc = dk.get(s->ctx, kPoolKeep, n))) return rc;
-        LRC_HIP(hipMemcpyAsync(dk.p, keep, n, hipMemcpyHostToDevice, in));
-    }
-    FrameStage st;
-    if ((rc = st.alloc(s->ctx, *out, P, n))) return rc;
-    NoiseStage ns;
-    if ((rc = ns.begin(s, n))) return rc;
     TraceParams p{};
-    p.poses16 = (const double*)dp.p;
-    p.angles2 = (const double*)da.p;
-    p.keep_mask = keep ? (const uint8_t*)dk.p : nullptr;
-    p.rays_per_pose = N;
-    p.total = n;
-    p.has_center = 1;
-    p.max_range = max_range;
-    return guard.done(frames_finish(s, p, 2, st, P, N, out, capacity, out_total));
+    return scan_compact(s, p, 2, P, N, max_range, out, capacity, out_total, [&](auto up) {
+        int rc;
+        if ((rc = up(kPoolPoses, poses16, P * 16, &p.poses16)) || (rc = up(kPoolAngles, angles2, n * 2, &p.angles2))) return rc;
+        return keep ? up(kPoolKeep, keep, n, &p.keep_mask) : LRC_OK;
+    });
 }
 
 int lrc_scan_rays_compact(lrc_scene* s, const float* rays6, const uint8_t* keep, const double* centers3, uint64_t P,
@@ -4156,31 +4096,12 @@ int lrc_scan_rays_compact(lrc_scene* s, const float* rays6, const uint8_t* keep,
     if (!rays6 || !centers3 || !out->counts)
         return fail(LRC_ERR_INVALID_ARG, "lrc_scan_rays_compact: rays6, centers3 or counts is NULL");
     LRC_HIP(hipSetDevice(s->ctx->device));
-    SyncUnlessOk guard;
-    DevBuf dr, dc, dk;
-    int rc;
-    if ((rc = ensure_streams(s->ctx))) return rc;
-    hipStream_t in = s->ctx->s_compute;
-    if ((rc = dr.get(s->ctx, kPoolRays, n * 24)) || (rc = dc.get(s->ctx, kPoolCen, P * 24))) return rc;
-    LRC_HIP(hipMemcpyAsync(dr.p, rays6, n * 24, hipMemcpyHostToDevice, in));
-    LRC_HIP(hipMemcpyAsync(dc.p, centers3, P * 24, hipMemcpyHostToDevice, in));
-    if (keep) {
-        if ((rc = dk.get(s->ctx, kPoolKeep, n))) return rc;
-        LRC_HIP(hipMemcpyAsync(dk.p, keep, n, hipMemcpyHostToDevice, in));
-    }
-    FrameStage st;
-    if ((rc = st.alloc(s->ctx, *out, P, n))) return rc;
-    NoiseStage ns;
-    if ((rc = ns.begin(s, n))) return rc;
     TraceParams p{};
-    p.rays6 = (const float*)dr.p;
-    p.seg_centers3 = (const double*)dc.p;
-    p.keep_mask = keep ? (const uint8_t*)dk.p : nullptr;
-    p.rays_per_pose = N;
-    p.total = n;
-    p.has_center = 1;
-    p.max_range = max_range;
-    return guard.done(frames_finish(s, p, 0, st, P, N, out, capacity, out_total));
+    return scan_compact(s, p, 0, P, N, max_range, out, capacity, out_total, [&](auto up) {
+        int rc;
+        if ((rc = up(kPoolRays, rays6, n * 6, &p.rays6)) || (rc = up(kPoolCen, centers3, P * 3, &p.seg_centers3))) return rc;
+        return keep ? up(kPoolKeep, keep, n, &p.keep_mask) : LRC_OK;
+    });
 }
 
 int lrc_debug_scan_stats(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,
@@ -4190,20 +4111,13 @@ int lrc_debug_scan_stats(lrc_scene* s, const double* poses16, uint64_t P, const 
     if (!n) return LRC_OK;
     if (!poses16 || !dirs3) return fail(LRC_ERR_INVALID_ARG, "lrc_debug_scan_stats: poses16 or dirs3 is NULL");
     LRC_HIP(hipSetDevice(s->ctx->device));
-    DevBuf dp, dd, ds;
-    int rc;
-    if ((rc = dp.get(s->ctx, kPoolPoses, P * 128)) || (rc = dd.get(s->ctx, kPoolDirs, N * 24)) ||
-        (rc = ds.get(s->ctx, kPoolStats, n * kStatsWords * 4)))
-        return rc;
-    LRC_HIP(hipMemcpy(dp.p, poses16, P * 128, hipMemcpyHostToDevice));
-    LRC_HIP(hipMemcpy(dd.p, dirs3, N * 24, hipMemcpyHostToDevice));
     TraceParams p{};
-    p.poses16 = (const double*)dp.p;
-    p.dirs3 = (const double*)dd.p;
-    p.rays_per_pose = N;
-    p.total = n;
-    p.has_center = 1;
-    p.max_range = max_range;
+    DevBuf ds;
+    int rc;
+    if ((rc = stage_input(s->ctx, kPoolPoses, poses16, P * 16, &p.poses16)) ||
+        (rc = stage_input(s->ctx, kPoolDirs, dirs3, N * 3, &p.dirs3)) || (rc = ds.get(s->ctx, kPoolStats, n * kStatsWords * 4)))
+        return rc;
+    scan_fields(p, N, n, max_range, nullptr);
     p.stats = (uint32_t*)ds.p;
     // LRC_STATS_LINE_WIDTH=W: the waves grouped as the scan pipeline groups them for lines of W rays (tools/trav_stats.py);
     // the counters stay indexed by ray

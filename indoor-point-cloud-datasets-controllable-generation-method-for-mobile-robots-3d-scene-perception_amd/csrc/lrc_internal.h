@@ -65,6 +65,13 @@ struct lrc_ctx {
         uint64_t tile_cap = 0;
         double* d_dirs_soa = nullptr;       // direction table transposed to x[N] y[N] z[N] (cloud rebuild only)
         uint64_t dirs_cap = 0;
+        // Frees every array and returns to the empty state.  A plain method, not a destructor: the owner makes the handle's
+        // device current first (hipSetDevice) and says so where it calls this.
+        void release() {
+            for (void* p : {(void*)d_tile_off, (void*)d_tile_cnt, (void*)d_super_total, (void*)d_super_base, (void*)d_dirs_soa})
+                if (p) (void)hipFree(p);
+            *this = TileScratch{};
+        }
     };
     TileScratch cloud_scratch;
     // lrc_compact_dev: one scratch set per caller stream (a caller that keeps two scans in flight on two streams compacts on
