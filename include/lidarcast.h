@@ -509,6 +509,59 @@ int lrc_noise_draws(const lrc_noise* noise, uint64_t num_poses, uint64_t rays_pe
                     float* z_el, uint8_t* keep);
 int lrc_noise_table(float* base1536, float* slope1536);
 
+/* ---- beam footprint and multi-echo returns (opt-in) ------------------------------------------
+ * Every other scan casts an infinitely thin ray.  A real beam diverges by a few milliradians; at a table edge or a door
+ * frame its footprint straddles two surfaces and the sensor reports two echoes, or one placed on the beam axis.  Here a
+ * BEAM is K sub-rays, 1 <= K <= 16, cast in neighbouring lanes of one wave and reduced to at most E echoes, 1 <= E <= 4,
+ * behind the traversal; no per-sub-ray record reaches memory.  The reference has nothing of the kind.
+ *   offsets   offsets2 is (K, 2) float64 (du_k, dv_k) in radians, supplied by the caller: the library builds no pattern.
+ *   sub-ray   k of table row (a, b, c), one float64 operation per step: h = sqrt(a*a + b*b), dp = du_k / h (du is an arc, so
+ *             the footprint stays round at high elevation), dt = dv_k, then the jitter step of the seeded noise above on
+ *             (a, b, c, dp, dt), then the dgemm chain and the float32 narrowing of lrc_scan_poses_dev.  A sub-ray with
+ *             du_k == 0 and dv_k == 0 passes the row through bit for bit; a row with h == 0 is left as it is for every k
+ *             (its K sub-rays coincide).
+ *   reduce    on the closest-hit distances t_k (float32, before any range filter) of the sub-rays that hit, ordered by
+ *             (t_k, k) ascending, s_0 <= s_1 <= ...: a new cluster starts at m = 0 and wherever (s_m - s_(m-1)) > separation
+ *             (one float32 subtraction, one compare), so a surface seen at a grazing angle chains into ONE cluster.  A
+ *             cluster has weight n_c (its member count), a representative (the member with the smallest k) and a range
+ *             (the representative's t).  Clusters with n_c < min_count are discarded; the first E of the rest, ascending,
+ *             are echoes 0..E-1; slots that stay empty are miss records.
+ *   record    echo e of beam (p, i) is record (p * N + i) * E + e: the record lrc_scan_poses_dev would write for the AXIS
+ *             ray (origin and direction of the unjittered row) had it hit the representative's triangle at the echo's
+ *             range.  point3 = o + unit(d_axis) * t; the range filter, min_range, incident_deg and intensity use that
+ *             point and direction; prim, normal3, sem and ins are the representative's.  d_weight, (P * N * E) uint8 or
+ *             NULL, receives n_c, 0 for an empty slot (also where the range filter then drops the record).
+ * Properties (tests/test_echo_gpu.py):
+ *   P1  K = 1 with offset (0, 0) and E = 1 gives the bytes of lrc_scan_poses_dev.
+ *   P2  with offsets2[0] == (0, 0), the echo whose representative is k = 0 equals the clean scan's record of that beam in
+ *       every column, incident_deg included.
+ *   P3  the result does not depend on pose order or chunking (P = 6 in one call = P = 2 and then P = 4).
+ * LRC_ERR_INVALID_ARG before any launch: K or E out of range, min_count outside [1, K], a non-finite offset, a separation
+ * that is not finite or <= 0, d_out->tile_count != NULL (a wave no longer writes 64 consecutive records) and a call while
+ * a range_noise option is set.  min_range and incident_mode apply unchanged.
+ *   lrc_scan_echoes_dev      device pointers; d_out holds P * N * E records.  The offsets are in device memory: the caller
+ *                            vouches that they are finite (lrc_scan_echoes_compact checks its host table)
+ *   lrc_scan_echoes_compact  host poses and offsets, a resident table: compacted like lrc_scan_table_compact as P poses
+ *                            of N * E records, so index = i * E + e; weight_rows, `capacity` bytes or NULL, receives
+ *                            the weights of the kept rows, aligned with them (gathered on the device)
+ *   lrc_echo_reduce          host, no GPU: the reduction alone.  t is (num_beams, K) float32 with +inf for a sub-ray
+ *                            without a hit; out_rep (num_beams, E) int32 receives the representative k of each echo
+ *                            (-1: empty slot), out_weight (num_beams, E) uint8 its weight.  Checks the beam as the scans
+ *                            do.  The restatement the tests and DESIGN.md point at (csrc/lrc_echo.h). */
+typedef struct lrc_beam {
+    uint32_t subrays;       /* K */
+    uint32_t max_echoes;    /* E */
+    uint32_t min_count;     /* clusters of fewer sub-rays are discarded; 1 keeps all */
+    float    separation;    /* metres */
+} lrc_beam;
+int lrc_scan_echoes_dev(lrc_scene* scene, const double* d_poses16, uint64_t num_poses, const double* d_dirs3,
+                        uint64_t rays_per_pose, const double* d_offsets2, const lrc_beam* beam, double max_range,
+                        const lrc_hits* d_out, uint8_t* d_weight /* nullable */, void* stream);
+int lrc_scan_echoes_compact(lrc_scene* scene, const double* poses16, uint64_t num_poses, const lrc_table* table,
+                            const double* offsets2, const lrc_beam* beam, double max_range, const lrc_frames* out,
+                            uint8_t* weight_rows /* nullable */, uint64_t capacity, uint64_t* out_total);
+int lrc_echo_reduce(const float* t, uint64_t num_beams, const lrc_beam* beam, int32_t* out_rep, uint8_t* out_weight);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

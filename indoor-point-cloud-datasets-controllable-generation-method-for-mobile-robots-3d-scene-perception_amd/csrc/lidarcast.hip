@@ -181,6 +181,9 @@ struct TraceParams {
     const double* fire;
     // GEN = 5 (seeded sensor noise, lrc_scan_noisy_*): generator parameters and the resident quantile table
     lrcnoise::Params noise;
+    // GEN = 6 (beam footprint and multi-echo returns, lrc_scan_echoes_*): the offset table and the reduction's parameters.  For
+    // this generator rays_per_pose and total count LANES (G per beam, lrc_echo.h) in the kernel; launch_trace converts them
+    lrcecho::Params echo;
 };
 
 // workgroup -> tile remap: consecutive tiles land on the same XCD (blocks b, b+8, ... share an L2),
@@ -678,11 +681,13 @@ __global__ __launch_bounds__(64) void ray_table_kernel(const double* __restrict_
 // GEN: 0 = explicit rays, 1 = pose x direction table, 2 = pose x per-ray scan angles (dual-axis sensor, opt-in),
 //      4 = motion record x direction table x firing fractions (moving-sensor sweeps, opt-in; same ray order as 1),
 //      5 = pose x direction table with seeded range noise, angle jitter and dropout drawn per ray (opt-in; same ray order as 1)
+//      6 = pose x direction table x offset table: K sub-rays per beam in the G neighbouring lanes of a group, reduced to at
+//          most E echoes per beam behind the traversal (opt-in; lrc_echo.h)
 // QN: 1 = walk the quantised node images (32-byte nodes for the per-lane fetches), 2 = walk their
 //     four-wide collapse (64-byte nodes, half the steps); a wave with a ray outside the bound the quantisation margin is
 //     proven for walks the float32 world-space nodes instead
 template <int GEN, int LEAFW, bool UNI, bool SPEC, bool STATS = false, int QN = 0>
-__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4 || GEN == 5)) ? 8 : 1) void trace_kernel(const TraceParams p) {
+__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4 || GEN == 5 || GEN == 6)) ? 8 : 1) void trace_kernel(const TraceParams p) {
     extern __shared__ int s_stack[];   // [stack depth][kTBlock]: one column per lane, conflict free
     const uint32_t tid = threadIdx.x;
     if (GEN == 1 && p.pre.blocks != 0u && p.pre.sharded != 0u) {
@@ -790,6 +795,16 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         const uint64_t pose = gid / p.rays_per_pose;
         const uint64_t i = gid - pose * p.rays_per_pose;
         gen_ray_noisy(p.poses16, p.dirs3, p.noise, pose, i, o, d, cx, cy, cz, live);
+        pose32 = (uint32_t)pose;
+    } else if (GEN == 6) {
+        // lane gid = beam * G + k.  64 % G == 0 and a pose is a whole number of groups, so k is the lane's place in its group of
+        // the wave, no group straddles a wave, and the `gid >= total` exit above removes whole groups only.  Lanes k >= K are
+        // not live: they cast nothing and take part in the reduction as sub-rays without a hit.
+        const uint64_t pose = gid / p.rays_per_pose;
+        const uint64_t r = gid - pose * p.rays_per_pose;
+        const uint32_t k = tid & ((1u << p.echo.group_log2) - 1u);
+        live = k < p.echo.subrays;
+        gen_ray_beam(p.poses16, p.dirs3, p.echo.offsets2, pose, r >> p.echo.group_log2, live ? k : 0u, o, d, cx, cy, cz);
         pose32 = (uint32_t)pose;
     } else {
         const float* r = p.rays6 + gid * 6;
@@ -1231,6 +1246,63 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         // non-positive range is no return
         tbest = noisy_range(p.noise, p.noise.first_frame + pose32, (uint32_t)(gid_w - (uint64_t)pose32 * p.rays_per_pose), tbest);
         if (!(tbest > 0.0f)) best_slot = 0xFFFFFFFFu;
+    }
+    if (GEN == 6) {
+        // ---- the beam's K closest hits -> at most E echoes, across the G lanes of the group (lrc_echo.h states the reduction) ----
+        // Every lane of the wave is here: no lane has left since the `gid >= total` exit, which takes whole groups.
+        const uint32_t glog = p.echo.group_log2, G = 1u << glog, k = tid & (G - 1u), base = tid - k;
+        const uint32_t gbits = (1u << G) - 1u;                // G <= 16
+        const float inf = __builtin_inff();
+        const bool hit = best_slot != 0xFFFFFFFFu;
+        const float tk = hit ? tbest : inf;
+        // who is in front of this sub-ray in the order by (t, k), and the range of the one directly in front
+        uint32_t less = 0u;
+        float pred = -inf;
+        for (uint32_t j = 0; j < G; ++j) {
+            const float tj = __shfl(tk, (int)(base + j), 64);
+            const bool front = (tj < inf) & ((tj < tk) | ((tj == tk) & (j < k)));
+            less |= front ? (1u << j) : 0u;
+            pred = front ? max2(pred, tj) : pred;
+        }
+        // a cluster starts at the first hit and wherever the gap to the one in front exceeds the separation
+        const bool start = hit & ((less == 0u) | ((tk - pred) > p.echo.separation));
+        const uint32_t smask = (uint32_t)(__ballot(start) >> base) & gbits;
+        const uint32_t cid = hit ? (uint32_t)__popc(smask & (less | (1u << k))) : 0u;      // 1, 2, ... in ascending order; 0: no hit
+        uint32_t same = 0u;                                                                 // the members of this lane's cluster
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t cj = (uint32_t)__shfl((int)cid, (int)(base + j), 64);
+            same |= ((cj == cid) & (cj != 0u)) ? (1u << j) : 0u;
+        }
+        const uint32_t count = (uint32_t)__popc(same);
+        // the representative (smallest k) of a cluster that is large enough speaks for it; clusters lie in the order one behind
+        // the other, so the echo's number is the number of such representatives in front of this one
+        const bool valid = hit & (same != 0u) & ((same & ((1u << k) - 1u)) == 0u) & (count >= (uint32_t)p.echo.min_count);
+        const uint32_t vmask = (uint32_t)(__ballot(valid) >> base) & gbits;
+        const uint32_t eidx = (uint32_t)__popc(vmask & less);
+        uint32_t src = 0xFFFFFFFFu;                           // lane e < E: the lane of echo e's representative
+        for (uint32_t e = 0; e < (uint32_t)p.echo.max_echoes; ++e) {
+            const uint32_t m = (uint32_t)(__ballot(valid & (eidx == e)) >> base) & gbits;
+            if (k == e && m != 0u) src = base + (uint32_t)__builtin_ctz(m);
+        }
+        const int from = (int)(src != 0xFFFFFFFFu ? src : tid);
+        float t_e = __shfl(tk, from, 64);
+        uint32_t slot_e = (uint32_t)__shfl((int)best_slot, from, 64);
+        const uint32_t label_e = (uint32_t)__shfl((int)best_label, from, 64);
+        uint32_t n_e = (uint32_t)__shfl((int)count, from, 64);
+        if (k >= (uint32_t)p.echo.max_echoes) return;         // the other lanes write nothing
+        if (src == 0xFFFFFFFFu) { t_e = inf; slot_e = 0xFFFFFFFFu; n_e = 0u; }
+        // the record is the AXIS ray's: gen_ray's bits of the unjittered row (the origin is every sub-ray's)
+        const uint64_t beam = gid_w >> glog;
+        {
+            const double* M = p.poses16;
+            asm volatile("" : "+s"(M));
+            double ux, uy, uz;
+            gen_ray(M, p.dirs3, pose32, beam - (uint64_t)pose32 * (p.rays_per_pose >> glog), o, d, ux, uy, uz);
+        }
+        const uint64_t rec = beam * (uint32_t)p.echo.max_echoes + k;
+        write_back<true, false, true>(p, rec, tid, o, d, cx, cy, cz, t_e, slot_e, label_e, false, h_tab);
+        if (p.echo.weight) p.echo.weight[rec] = (uint8_t)n_e;
+        return;
     }
     write_back<GEN != 0, false, true>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot, best_label, have_h, h_tab);
     if (STATS) {
@@ -2275,7 +2347,7 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
         return 1;
     }
     const bool plain = leafw == kLeafW && uni && !spec && !(qn && wide);
-    if (plain || gen == 2 || gen == 4 || gen == 5) return 1;
+    if (plain || gen == 2 || gen == 4 || gen == 5 || gen == 6) return 1;
     const bool wide_only = qn && wide && leafw == kLeafW && uni && !spec;
     if (gen == 1) { if (wide_only) LRC_LAB(1, kLeafW, true, false, 2); else LRC_LAB_PICK(1); }
     else { if (wide_only) LRC_LAB(0, kLeafW, true, false, 2); else LRC_LAB_PICK(0); }
@@ -2291,7 +2363,8 @@ static size_t trace_lds_bytes(uint32_t depth) { return (size_t)depth * kTBlock *
 
 // One launch of the trace kernel over p.total rays.  gen: 0 explicit rays, 1 pose x direction table, 2 pose x scan angles,
 // 3 a grid scan (lrc_scan_grid_*: the per-ray kernel here; the packet kernel in the laboratory build), 4 moving-sensor sweeps
-// (motion record x direction table x firing fractions), 5 pose x direction table with seeded sensor noise (p.noise).
+// (motion record x direction table x firing fractions), 5 pose x direction table with seeded sensor noise (p.noise), 6 pose x
+// direction table x beam offsets, reduced to echoes (p.echo; p.total and p.rays_per_pose count echo records on entry).
 static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, bool stats = false) {
     p.nodes = s->d_nodes;
     p.tris = s->d_tris;
@@ -2306,6 +2379,11 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     p.nodes_n4 = s->d_nodes_n4;
     for (int a = 0; a < 3; ++a) { p.qbase[a] = s->qbase[a]; p.qW[a] = s->qW[a]; p.qinvW[a] = s->qinvW[a]; }
     const bool qn = s->d_nodes_q != nullptr;
+    if (gen == 6) {      // the caller counts echo RECORDS (E per beam), the kernel LANES (G per beam, lrc_echo.h)
+        const uint64_t E = p.echo.max_echoes;
+        p.rays_per_pose = (p.rays_per_pose / E) << p.echo.group_log2;
+        p.total = (p.total / E) << p.echo.group_log2;
+    }
     p.min_range = s->opts.min_range;
     p.incident_mode = s->opts.incident_mode;
     if (!p.range_noise && s->opts.range_noise) {      // device entry points: the pointer is a device pointer
@@ -2337,7 +2415,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     // is worth more than the balance: measured +1...+16 % for the striped order there, -1...-10 % on the cache-resident
     // scenes (profiles/r03_xcd_striping_sweep.txt).
     constexpr uint64_t kStripeSceneBytes = 192ull << 20;
-    if ((gen == 1 || gen == 4 || gen == 5) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
+    if ((gen == 1 || gen == 4 || gen == 5 || gen == 6) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
         const uint64_t tpp = p.rays_per_pose / 64;
         if (tpp % 16 == 0) {
             const uint64_t chunk = tpp / 16;
@@ -2388,6 +2466,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     } else if (gen == 1) LRC_LAUNCH(1, false);
     else if (gen == 4) LRC_LAUNCH(4, false);
     else if (gen == 5) LRC_LAUNCH(5, false);
+    else if (gen == 6) LRC_LAUNCH(6, false);
     else if (gen == 2) LRC_LAUNCH(2, false);
     else LRC_LAUNCH(0, false);
 #undef LRC_LAUNCH
@@ -2395,7 +2474,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     LRC_HIP(hipGetLastError());
     if (p.chain_word) { cx_->chain_seq = p.chain_seq; cx_->chain_stream = st; }
     s->launches += 1;
-    s->rays += p.total;
+    s->rays += gen == 6 ? (p.total >> p.echo.group_log2) * p.echo.subrays : p.total;      // echoes: the sub-rays cast, not the lanes
     return LRC_OK;
 }
 
@@ -2544,6 +2623,18 @@ int lrc_scan_grid_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const d
 }
 
 }  // extern "C"
+
+// The trace launch of lrc_scan_echoes_dev, whose arguments lrc_echo.hip has checked (declared in lrc_internal.h): ep.offsets2 and
+// ep.weight are device pointers, d_out holds P * N * E records.
+int echo_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N, const lrcecho::Params& ep,
+                  double max_range, const lrc_hits* d_out, hipStream_t st) {
+    TraceParams p{};
+    p.poses16 = d_poses16;
+    p.dirs3 = d_dirs3;
+    p.echo = ep;
+    scan_fields(p, N * ep.max_echoes, P * N * ep.max_echoes, max_range, d_out);
+    return launch_trace(s, p, 6, st);
+}
 
 // ---- host-pointer convenience wrappers ---------------------------------------------------------
 namespace {
@@ -3752,6 +3843,7 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
     // stage (67 MB at 50-56 GB/s for C3): it starts as soon as a few poses are traced, and the later, larger chunks are ready
     // before the copy engine asks for them (C3: 1.48 ms against 1.53 for four equal chunks; tools/chunk_scheme_sweep.sh,
     // profiles/r03_chunk_schemes.txt).  Equal chunks for short trajectories.
+    if (gen == 6) chunks = 1;      // echoes: the weight rows are gathered from ONE packed run of compacted rows (echo_scan_compact)
     bool graded = chunks == 4 && P >= 8;
     uint32_t ends32[8] = {4, 16, 32, 32, 32, 32, 32, 32};       // chunk ends in 32nds of the trajectory
     if (graded) chunks = 3;
@@ -3920,6 +4012,48 @@ int scan_compact_impl(lrc_scene* s, const double* poses16, uint64_t P, const dou
     }, grid);
 }
 }  // namespace
+
+// lrc_scan_echoes_compact behind its checks (lrc_echo.hip; declared in lrc_internal.h).  The echo records are compacted by the
+// path every *_compact entry point takes, as P poses of N * E records: `index` comes out as i * E + e.  No wave of the echo
+// kernel writes 64 consecutive records, so the record set carries no per-tile keep counts and lrc_compact_dev counts itself.  The
+// weights of the kept rows are gathered on the device by the compacted index column (echo_gather_rows, lrc_echo.hip).
+int echo_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, const double* offsets2,
+                      lrcecho::Params ep, double max_range, const lrc_frames* out, uint8_t* weight_rows, uint64_t capacity,
+                      uint64_t* out_total) {
+    SyncUnlessOk guard;
+    lrc_ctx* const ctx = s->ctx;
+    const uint64_t NE = table->n * ep.max_echoes, n = P * NE;
+    int rc;
+    if ((rc = ensure_streams(ctx))) return rc;
+    const hipStream_t in = ctx->s_compute;
+    TraceParams p{};
+    p.dirs3 = table->d_dirs3;
+    if ((rc = stage_input(ctx, kPoolPoses, poses16, P * 16, &p.poses16, &in)) ||
+        (rc = stage_input(ctx, kPoolOffs, offsets2, (size_t)ep.subrays * 2, &ep.offsets2, &in)))
+        return rc;
+    FrameStage st;
+    if ((rc = st.alloc(ctx, *out, P, n))) return rc;
+    st.rec.tile_count = nullptr;
+    st.io.tile_count = nullptr;
+    DevBuf wbuf;
+    ep.weight = nullptr;
+    if (weight_rows) {
+        if (!st.io.out_index) {       // the gather reads the index column whether or not the caller asked for it
+            if ((rc = st.oidx.get(ctx, kPoolOutIdx, n * 4))) return rc;
+            st.io.out_index = (uint32_t*)st.oidx.p;
+        }
+        if ((rc = wbuf.get(ctx, kPoolKeep, n))) return rc;
+        ep.weight = (uint8_t*)wbuf.p;
+    }
+    p.echo = ep;
+    scan_fields(p, NE, n, max_range, nullptr);
+    uint64_t total = 0;
+    rc = frames_finish(s, p, 6, st, P, NE, out, capacity, &total);
+    if (out_total) *out_total = total;
+    if (rc == LRC_OK && weight_rows && total)
+        rc = echo_gather_rows(ctx, out->counts, P, st.io.out_index, ep.weight, NE, total, weight_rows);
+    return guard.done(rc);
+}
 
 extern "C" {
 

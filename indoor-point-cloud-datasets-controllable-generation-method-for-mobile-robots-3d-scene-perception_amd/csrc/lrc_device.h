@@ -290,6 +290,31 @@ LRC_DI float noisy_range(const lrcnoise::Params& np, uint64_t frame, uint32_t i,
     return t + np.range_std * lrcnoise::normal_of(w.w0, np.tab);
 }
 
+// ---- beam footprint (lrc_scan_echoes_*; include/lidarcast.h "beam footprint and multi-echo returns") ----
+// Sub-ray k of beam (pose, i): gen_ray with the table row moved by the offset (du, dv) = offsets2[k] in the sensor frame BEFORE
+// the dgemm chain.  One float64 operation per step: h = sqrt(a*a + b*b), dp = du / h (du is an arc: the footprint stays round
+// at high elevation), dt = dv, then lrc_noise.h jitter_row(a, b, c, dp, dt).  A zero offset passes the row through bit for bit
+// (the sub-ray is gen_ray's ray), and so does a row with h == 0 for every offset.
+LRC_DI void gen_ray_beam(const double* poses16, const double* dirs3, const double* offsets2, uint64_t pose, uint64_t i,
+                         uint32_t k, V3& o, V3& d, double& cx, double& cy, double& cz) {
+    const double* M = poses16 + pose * 16;
+    const double* dv = dirs3 + i * 3;
+    double a = dv[0], b = dv[1], c = dv[2];
+    const double du = offsets2[2 * k], dt = offsets2[2 * k + 1];
+    if (du != 0.0 || dt != 0.0) {
+        const double h = __builtin_sqrt(a * a + b * b);
+        if (h != 0.0) {
+            const double dp = du / h;
+            lrcnoise::jitter_row(a, b, c, dp, dt);
+        }
+    }
+    d.x = (float)dgemm_row(a, b, c, M[0], M[1], M[2]);
+    d.y = (float)dgemm_row(a, b, c, M[4], M[5], M[6]);
+    d.z = (float)dgemm_row(a, b, c, M[8], M[9], M[10]);
+    cx = M[3]; cy = M[7]; cz = M[11];
+    o.x = (float)cx; o.y = (float)cy; o.z = (float)cz;
+}
+
 // d/|d| : numpy float32, one rounding per operation (reference: raycast_engine_cpu.py:57-60).  The one expression behind
 // hit_point and the ray table of a prepared pipeline submit (ray_row below).
 LRC_HDI V3 unit_dir(V3 d) {

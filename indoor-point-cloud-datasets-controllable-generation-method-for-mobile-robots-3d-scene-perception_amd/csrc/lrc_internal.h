@@ -12,6 +12,7 @@
 #include "../../include/lidarcast.h"
 #include "lrc_bvh_device.h"
 #include "lrc_noise.h"
+#include "lrc_echo.h"
 
 // sets lrc_last_error() (lidarcast.hip).  Exported: lrc_nprandom.cpp, built without HIP headers, reports through it.
 extern "C" int lrc_internal_fail(int code, const char* msg);
@@ -171,5 +172,17 @@ int check_mesh(const char* who, const double* verts3, uint64_t V, const int32_t*
 // lrc_noise.hip: checks an lrc_noise for a table of N rays (LRC_ERR_INVALID_ARG, `who` prefixes the message), makes the
 // context's quantile table resident and fills the kernel's parameter block
 int noise_params(lrc_ctx* ctx, const char* who, const lrc_noise* nz, uint64_t N, lrcnoise::Params* out);
+
+// beam footprint and multi-echo returns.  lrc_echo.hip checks the arguments of lrc_scan_echoes_* and fills an lrcecho::Params;
+// lidarcast.hip, which owns the trace kernel and the frame path, launches (echo_scan_dev) and scans to frames
+// (echo_scan_compact: host poses and offsets, ep.offsets2 / ep.weight are filled there); lrc_echo.hip gathers the weights of the
+// `rows` kept rows from the fixed-stride weights by the compacted index column (counts: host, per pose).
+int echo_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N, const lrcecho::Params& ep,
+                  double max_range, const lrc_hits* d_out, hipStream_t st);
+int echo_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, const double* offsets2,
+                      lrcecho::Params ep, double max_range, const lrc_frames* out, uint8_t* weight_rows, uint64_t capacity,
+                      uint64_t* out_total);
+int echo_gather_rows(lrc_ctx* ctx, const uint64_t* counts, uint64_t P, const uint32_t* d_index, const uint8_t* d_weight,
+                     uint64_t records_per_pose, uint64_t rows, uint8_t* weight_rows);
 
 #pragma GCC visibility pop

@@ -36,6 +36,7 @@ SYMBOLS = (
     "lrc_table_create", "lrc_table_destroy", "lrc_scan_table_compact",
     "lrc_scan_sweeps_dev", "lrc_table_set_fire", "lrc_scan_sweeps_compact",
     "lrc_scan_noisy_dev", "lrc_scan_noisy_compact", "lrc_noise_draws", "lrc_noise_table",
+    "lrc_scan_echoes_dev", "lrc_scan_echoes_compact", "lrc_echo_reduce",
     "lrc_compact", "lrc_compact_dev", "lrc_cloud_from_ranges_dev", "lrc_cloud_from_prims_dev",
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
@@ -80,6 +81,10 @@ class LrcScanOptions(C.Structure):
 class LrcNoise(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_frame", C.c_uint64), ("range_std", C.c_double), ("angle_std", C.c_double),
                 ("dropout", C.c_double)]
+
+
+class LrcBeam(C.Structure):
+    _fields_ = [("subrays", C.c_uint32), ("max_echoes", C.c_uint32), ("min_count", C.c_uint32), ("separation", C.c_float)]
 
 
 class LrcCoverageInfo(C.Structure):
@@ -257,6 +262,9 @@ def load():
         "lrc_scan_noisy_compact": [vp, vp, u64, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcFrames), u64, C.POINTER(u64)],
         "lrc_noise_draws": [C.POINTER(LrcNoise), u64, u64, vp, vp, vp, vp],
         "lrc_noise_table": [vp, vp],
+        "lrc_scan_echoes_dev": [vp, vp, u64, vp, u64, vp, C.POINTER(LrcBeam), dbl, C.POINTER(LrcHits), vp, vp],
+        "lrc_scan_echoes_compact": [vp, vp, u64, vp, vp, C.POINTER(LrcBeam), dbl, C.POINTER(LrcFrames), vp, u64, C.POINTER(u64)],
+        "lrc_echo_reduce": [vp, u64, C.POINTER(LrcBeam), vp, vp],
         "lrc_occ_create": [vp, vp, u64, C.POINTER(vp)],
         "lrc_occ_destroy": [vp],
         "lrc_occ_query": [vp, vp, u64, dbl, vp],

@@ -694,6 +694,43 @@ class Scene:
             if own is not None:
                 own.close()
 
+    def scan_echoes_compact(self, poses, dirs, max_range, beam, want=("point3", "sem", "ins"), capacity=None):
+        """Pose-batched scan of diverging beams straight to frames (lrc_scan_echoes_compact): ``beam`` a
+        ``lidarcast.echo.BeamModel``, ``dirs`` a DirectionTable or an (N, 3) table.  The return value of ``scan_poses_compact``
+        over P poses of N * E echo records -- ``index`` is i * E + e -- plus ``beam_index`` (i), ``echo_index`` (e) and
+        ``echo_weight`` (the sub-rays behind the echo, uint8), one entry per kept row."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
+        own = None
+        if isinstance(dirs, DirectionTable):
+            if not dirs._h:
+                raise ValueError("direction table handle is closed")
+            if dirs.ctx is not self.ctx:
+                raise ValueError("direction table belongs to another context (device)")
+            table = dirs
+        else:
+            table = own = DirectionTable(self.ctx, dirs)
+        try:
+            P, N, E = poses.shape[0], table.n, beam.max_echoes
+            asked = tuple(want)
+            if "index" not in asked:
+                want = asked + ("index",)
+            fr, counts, bufs, cap = self._frames_begin(P, P * N * E, want, capacity)
+            weight = np.zeros(max(cap, 1), dtype=np.uint8)
+            total = C.c_uint64(0)
+            b = beam.struct()
+            check(self._lib.lrc_scan_echoes_compact(self._h, _ptr(poses), P, table._h, _ptr(beam.offsets), C.byref(b),
+                                                    float(max_range), C.byref(fr), _ptr(weight), cap, C.byref(total)),
+                  "lrc_scan_echoes_compact")
+            out = self._frames_end(counts, bufs, total.value)
+            idx = out["index"] if "index" in asked else out.pop("index")
+            out["beam_index"] = (idx // np.uint32(E)).astype(np.uint32)
+            out["echo_index"] = (idx % np.uint32(E)).astype(np.uint8)
+            out["echo_weight"] = weight[:total.value]
+            return out
+        finally:
+            if own is not None:
+                own.close()
+
     def scan_angles_compact(self, poses, angles, keep, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Dual-axis sensor, rays generated in the kernel from host-drawn (phi, theta) (lrc_scan_angles_compact).
         angles: (P, N, 2) float64; keep: (P, N) bool / uint8 or None."""
@@ -779,6 +816,28 @@ class Scene:
         check(self._lib.lrc_scan_noisy_dev(self._h, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
                                            float(max_range), C.byref(nz), C.byref(hits.struct), C.c_void_p(int(stream))),
               "lrc_scan_noisy_dev")
+
+    def scan_echoes_dev(self, poses_t, dirs_t, hits, max_range, beam, weight_t=None, offsets_t=None, stream=0):
+        """Pose-batched scan of diverging beams on device tensors (lrc_scan_echoes_dev): poses_t (P, 16) float64, dirs_t
+        (N, 3) float64, ``beam`` a ``lidarcast.echo.BeamModel``; ``hits`` holds P * N * E records, record (p * N + i) * E + e
+        echo e of beam (p, i); ``weight_t`` an optional (P * N * E) uint8 tensor for the echoes' weights.  ``offsets_t``: the
+        beam's (K, 2) float64 offsets already on the device (a caller that scans again and again uploads them once)."""
+        P, N = poses_t.shape[0], dirs_t.shape[0]
+        if hits.n != P * N * beam.max_echoes:
+            raise ValueError("hits must hold P * N * max_echoes records")
+        if weight_t is not None and weight_t.numel() != P * N * beam.max_echoes:
+            raise ValueError("weight_t must hold P * N * max_echoes entries")
+        if offsets_t is None:
+            import torch
+            offsets_t = torch.from_numpy(np.array(beam.offsets)).to(poses_t.device)
+        elif offsets_t.numel() != 2 * beam.subrays:
+            raise ValueError("offsets_t must be (K, 2)")
+        b = beam.struct()
+        check(self._lib.lrc_scan_echoes_dev(self._h, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
+                                            C.c_void_p(offsets_t.data_ptr()), C.byref(b), float(max_range),
+                                            C.byref(hits.struct), None if weight_t is None else C.c_void_p(weight_t.data_ptr()),
+                                            C.c_void_p(int(stream))), "lrc_scan_echoes_dev")
+        return offsets_t
 
     def scan_sweeps_dev(self, motion_t, dirs_t, fire_t, hits, max_range, stream=0):
         """Moving-sensor sweeps on device tensors (lrc_scan_sweeps_dev): motion_t (P, 24) float64, dirs_t (N, 3) float64,

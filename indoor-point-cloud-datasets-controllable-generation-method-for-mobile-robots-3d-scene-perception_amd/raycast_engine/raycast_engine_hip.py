@@ -373,6 +373,17 @@ class RaycastEngineHIP(RaycastEngineBase):
         return self.scene_for(mesh).scan_noisy_compact(poses, self._resident_table(intrinsics), intrinsics.max_range, noise,
                                                        want=want)
 
+    def scan_echo_frames(self, intrinsics, poses, mesh, beam, want=("point3", "sem", "ins")):
+        """``scan_frames`` with a diverging beam per table row (lrc_scan_echoes_compact): ``beam`` a
+        ``lidarcast.echo.BeamModel``.  A beam yields up to ``beam.max_echoes`` rows, so ``counts`` count echoes; the dict of
+        ``scan_frames`` plus, per kept row, ``beam_index`` (the table row), ``echo_index`` (0 = the nearest echo of its beam)
+        and ``echo_weight`` (the sub-rays behind the echo).  ``index``, when asked for, is beam_index * max_echoes + echo_index."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
+            raise ValueError("a beam footprint needs a sensor with a pose-independent direction table")
+        return self.scene_for(mesh).scan_echoes_compact(poses, self._resident_table(intrinsics), intrinsics.max_range, beam,
+                                                        want=want)
+
     def _firing_fractions(self, intrinsics):
         """(N,) firing fractions of the sensor's direction table (IndoorLidar.firing_fractions), cached with the table."""
         from lidar import IndoorLidar

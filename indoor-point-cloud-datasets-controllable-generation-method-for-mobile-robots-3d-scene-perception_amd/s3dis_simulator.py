@@ -200,6 +200,8 @@ class S3DISSimulator:
             raise NotImplementedError("surface coverage of moving-sensor sweeps is outside its scope")
         if self.config.get("noise") is not None:
             raise NotImplementedError("surface coverage under the noise key is outside its scope")
+        if self.config.get("beam") is not None:
+            raise NotImplementedError("surface coverage under the beam key is outside its scope")
         from lidarcast.synth import S3DIS_CLASSES
         s = self.raycast_engine.surface_coverage(self.lidar_config, poses_from_waypoints(waypoints),
                                                  self.scene.room_mesh)
@@ -221,6 +223,8 @@ class S3DISSimulator:
             raise NotImplementedError("occupancy grids of moving-sensor sweeps are outside their scope")
         if self.config.get("noise") is not None:
             raise NotImplementedError("occupancy grids under the noise key are outside their scope")
+        if self.config.get("beam") is not None:
+            raise NotImplementedError("occupancy grids under the beam key are outside their scope")
         from containers.s3dis_sim_scene import write_labeled_ply
         from lidarcast.synth import S3DIS_CLASSES
         r = self.raycast_engine.occupancy_grid(self.lidar_config, poses_from_waypoints(waypoints), self.scene.room_mesh,
@@ -255,6 +259,8 @@ class S3DISSimulator:
             raise NotImplementedError("frame annotations of moving-sensor sweeps are outside their scope")
         if self.config.get("noise") is not None:
             raise NotImplementedError("frame annotations under the noise key are outside their scope")
+        if self.config.get("beam") is not None:
+            raise NotImplementedError("frame annotations under the beam key are outside their scope")
         from lidar_net_bbox_visualizer import S3DIS_SEMANTIC_MAPPING
         from lidarcast.synth import S3DIS_CLASSES
         mapping = S3DIS_SEMANTIC_MAPPING if semantic_mapping is None else semantic_mapping
@@ -312,6 +318,22 @@ class S3DISSimulator:
                           range_std=float(cfg.get("range_std", getattr(k, "range_noise_std", 0.0))),
                           angle_std=float(np.deg2rad(float(cfg.get("angle_std_deg", getattr(k, "angle_noise_std", 0.0))))),
                           dropout=float(cfg.get("dropout", getattr(k, "dropout_probability", 0.0))))
+
+    def _beam_model(self):
+        """The BeamModel of the config key ``beam`` (None without the key): ``divergence_mrad`` (the beam's full angle) is
+        required; ``pattern`` (single, cross5, hex7), ``max_echoes``, ``separation`` (m) and ``min_fraction`` default to
+        BeamModel's."""
+        cfg = self.config.get("beam")
+        if cfg is None:
+            return None
+        if "divergence_mrad" not in cfg:
+            raise ValueError("the beam key needs divergence_mrad")
+        unknown = set(cfg) - {"divergence_mrad", "pattern", "max_echoes", "separation", "min_fraction"}
+        if unknown:
+            raise ValueError(f"unknown entries under the beam key: {sorted(unknown)}")
+        from lidarcast.echo import BeamModel
+        kw = {k: cfg[k] for k in ("pattern", "max_echoes", "separation", "min_fraction") if k in cfg}
+        return BeamModel(float(cfg["divergence_mrad"]) * 1e-3, **kw)
 
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
@@ -378,7 +400,23 @@ class S3DISSimulator:
                 raise ValueError("the noise key is not available on a multi-rank process group")
             if not batched:
                 raise ValueError("the noise key needs a multi-line sensor with a direction table (not the dual-axis sensor)")
-        if noise is not None:
+        # opt-in beam footprint (config key ``beam: {divergence_mrad, pattern?, max_echoes?, separation?, min_fraction?}``):
+        # every table row is a diverging beam of sub-rays reduced to echoes in the kernel; a frame then
+        # holds up to max_echoes points per beam and carries beam_index, echo_index and echo_weight per point.  Without the key
+        # nothing changes.
+        beam = self._beam_model() if len(waypoints) > 0 else None
+        if beam is not None:
+            if motion is not None:
+                raise ValueError("the beam key cannot be combined with moving-sensor sweeps (motion)")
+            if noise is not None:
+                raise ValueError("the beam key cannot be combined with the noise key")
+            if dist is not None:
+                raise ValueError("the beam key is not available on a multi-rank process group")
+            if not batched:
+                raise ValueError("the beam key needs a multi-line sensor with a direction table (not the dual-axis sensor)")
+        if beam is not None:
+            fr = engine.scan_echo_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, beam, want=want)
+        elif noise is not None:
             fr = engine.scan_noisy_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, noise, want=want)
         elif sweep is not None:
             fr = engine.scan_sweep_frames(self.lidar_config, None, None, mesh, want=want, inputs=sweep)
@@ -431,7 +469,7 @@ class S3DISSimulator:
             else:      # labels on demand: one labels-only scan of the trajectory (of the SAME sweeps), shared by its frames
                 sem_f = ins_f = itertools.repeat(None)
                 src_f = itertools.repeat(_LazyTrajectoryLabels(engine, self.lidar_config, poses_from_waypoints(waypoints),
-                                                               mesh, counts_l, sweep, noise))
+                                                               mesh, counts_l, sweep, noise, beam))
             if "range_origin_mean" in fr:      # statistics from the device
                 qual = self._quality_from_stats(fr, total, volume)
             else:
@@ -445,6 +483,9 @@ class S3DISSimulator:
             if "point_times" in fr:        # seconds since the start of the frame's sweep, per point
                 for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
                     f.point_times = fr["point_times"][e - c:e]
+            if "echo_weight" in fr:        # per point: its beam (table row), its place among the beam's echoes, the sub-rays behind it
+                for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
+                    f.beam_index, f.echo_index, f.echo_weight = (fr[a][e - c:e] for a in ("beam_index", "echo_index", "echo_weight"))
         for i, wp in enumerate(waypoints if fr is None else ()):
             a, b = off[i], off[i + 1]
             keep = seg["t"][a:b] != np.inf
@@ -464,12 +505,13 @@ class _LazyTrajectoryLabels:
     of the same poses over the same mesh (the scan is a pure function of both: same kept rays, same order), whose result
     all frames of the trajectory share."""
 
-    def __init__(self, engine, intrinsics, poses, mesh, counts, sweep=None, noise=None):
+    def __init__(self, engine, intrinsics, poses, mesh, counts, sweep=None, noise=None, beam=None):
         # sweep: the (motion records, fire table, period) of a moving-sensor scan -- rescanned exactly, never as static poses
         # noise: the NoiseModel of a noisy scan -- rescanned with the same seed and frame ids, never as the clean scan
         self._args = (engine, intrinsics, np.array(poses, dtype=np.float64, copy=True), mesh)
         self._sweep = sweep
         self._noise = noise
+        self._beam = beam      # the BeamModel of an echo scan -- rescanned as echoes, never as the clean labels-only scan
         self._counts = list(counts)
         self._sem = self._ins = None
         import threading
@@ -479,7 +521,9 @@ class _LazyTrajectoryLabels:
         with self._lock:
             if self._sem is None:
                 engine, intrinsics, poses, mesh = self._args
-                if self._noise is not None:
+                if self._beam is not None:
+                    fr = engine.scan_echo_frames(intrinsics, poses, mesh, self._beam, want=("sem", "ins"))
+                elif self._noise is not None:
                     fr = engine.scan_noisy_frames(intrinsics, poses, mesh, self._noise, want=("sem", "ins"))
                 elif self._sweep is not None:
                     fr = engine.scan_sweep_frames(intrinsics, None, None, mesh, want=("sem", "ins"), inputs=self._sweep)
@@ -488,7 +532,7 @@ class _LazyTrajectoryLabels:
                 if fr["counts"].tolist() != self._counts:
                     raise RuntimeError("the mesh or the scan options changed between the scan and the first look at its labels")
                 self._sem, self._ins, self._ends = fr["sem"], fr["ins"], list(itertools.accumulate(self._counts))
-                self._args = self._sweep = self._noise = None
+                self._args = self._sweep = self._noise = self._beam = None
         e, c = self._ends[i], self._counts[i]
         return self._sem[e - c:e], self._ins[e - c:e]
 
