@@ -562,6 +562,88 @@ int lrc_scan_echoes_compact(lrc_scene* scene, const double* poses16, uint64_t nu
                             uint8_t* weight_rows /* nullable */, uint64_t capacity, uint64_t* out_total);
 int lrc_echo_reduce(const float* t, uint64_t num_beams, const lrc_beam* beam, int32_t* out_rep, uint8_t* out_weight);
 
+/* ---- surface materials: glass, mirrors and return intensity (opt-in) ---------------------------
+ * Every other scan treats every surface as an opaque, matte sheet.  Here each semantic class has a MATERIAL, and a ray that
+ * meets glass or a mirror is continued from its hit point inside the trace kernel: a window is seen only near normal
+ * incidence and looked through otherwise, a mirror puts ghost points behind the wall, and the intensity column depends on
+ * the surface.  The reference has nothing of the kind.
+ *   record    lrc_material, 16 bytes, one per semantic class: kind (0 diffuse, 1 glass, 2 mirror), albedo (the strength of
+ *             the surface's own return), pass (the gain kept by a pulse that goes on: transmission of glass, specular
+ *             reflectance of a mirror, two-way), retro_cos (the surface answers itself when c >= retro_cos; a value above
+ *             1: never).  A semantic id >= num_classes is diffuse with albedo 1.
+ *   chain     a ray is a chain of SEGMENTS (o_k, d_k), k = 0, 1, ...; segment 0 is the ray of lrc_scan_poses_dev, bit for
+ *             bit.  State: T = +0 (path length), g = 1 (gain), b = 0 (bounces).  All arithmetic is float32 with one
+ *             rounding per operation except the fused expression named below.  Per segment:
+ *             1 hit       the closest hit of (o_k, d_k) under the library's hit definition: t_k and a triangle -- exactly
+ *                         what lrc_cast_dev returns for that ray without centre or filter.  A miss: no return.
+ *             2 geometry  h_k = d_k / |d_k| and pp_k = o_k + h_k * t_k as every record's point3 is formed; n the unit
+ *                         normal of the record (normal3); c = |fma(hz, nz, fma(hy, ny, hx * nx))| (the intensity
+ *                         expression of lrc_hits); T = T + t_k.
+ *             3 own       m = the record of the triangle's semantic id.  m.kind == 0 or c >= m.retro_cos: the surface
+ *                         returns, the chain ends, I = (g * m.albedo) * c.
+ *             4 go on     otherwise b == max_bounces: no return.  Otherwise b = b + 1, g = g * m.pass,
+ *                         glass: d_(k+1) = d_k; mirror: dn = (hx * nx + hy * ny) + hz * nz, s = dn + dn,
+ *                         d_(k+1) = h_k - s * n per component (not normalised); h_(k+1) = d_(k+1) / |d_(k+1)|,
+ *                         o_(k+1) = pp_k + h_(k+1) * skin with skin = 2^-10 m, T = T + skin.
+ *             5 record    a return with I < min_intensity is no return.  A return's record is the one lrc_scan_poses_dev
+ *                         would write for (o_0, d_0) had it hit the FINAL triangle at range T: point3 lies on the original
+ *                         beam at the total path length, where the sensor believes the surface to be; the range filter,
+ *                         min_range and incident_deg use that point; prim, normal3, sem and ins are the final surface's;
+ *                         intensity is I.  bounces (uint8) receives b and surface_point3 (float32 x 3) the last pp_k, where
+ *                         the return physically came from.  A ray without a return (also one the range filter drops) has
+ *                         the miss record, bounces = 0 and surface_point3 = 0.
+ *             The skin stands in the place of a "skip the triangle I stand on" rule: every segment is an ordinary ray, so
+ *             the explicit-ray cast and the CPU oracle trace the chain unchanged.
+ * Properties (tests/test_material_gpu.py): an all-diffuse table with albedo 1 gives the bytes of lrc_scan_poses_dev in
+ * every column, intensity included; the result does not depend on how the poses are split into calls.
+ * LRC_ERR_INVALID_ARG before any launch: num_classes outside [1, 256], max_bounces > 8, a min_intensity that is not finite
+ * or outside [0, 1], a kind > 2, an albedo or pass that is not finite or outside [0, 1], a retro_cos that is not finite or
+ * negative, a table of another context than the scene's, a call while a range_noise option is set, and a call while
+ * incident_mode is 1: the angle between the original beam and the final surface's normal means nothing behind a mirror.
+ * min_range applies unchanged; incident_deg (mode 0) is the angle of the reported point, on the original beam, as in every scan.
+ * Lifetime: a material table belongs to the context it was created on and must be destroyed BEFORE that context
+ * (lrc_material_table_destroy makes the context's device current); the library keeps no list of a context's tables.
+ *   lrc_material_table_create   validates `records` (model->num_classes of them, host) and makes them resident
+ *   lrc_scan_materials_dev      device pointers; d_out, d_bounces (nullable) and d_surface_point3 (nullable) hold P * N
+ *                               entries
+ *   lrc_scan_materials_compact  host poses, a resident direction table: compacted like lrc_scan_table_compact;
+ *                               intensity_rows (float32), bounces_rows (uint8) and surface_rows (float32 x 3), `capacity`
+ *                               rows each or NULL, receive those columns of the kept rows, aligned with them (gathered on
+ *                               the device)
+ *   lrc_material_step           host, no GPU: step 2 to 5 of ONE segment for n rays, by the inline functions the kernel calls
+ *                               (csrc/lrc_material.h).  In: this segment's closest hit per ray (t, +inf or any value that is
+ *                               not < +inf for a miss; sem; normal3).  In and out: origin3, dir3, path (T), gain (g), bounces
+ *                               (b) and status -- 0 pending, 1 returned, 2 no return; rays that are not pending are left
+ *                               alone.  Out for a ray that returns: intensity (I) and surface_point3; a ray that goes on has
+ *                               its next segment in origin3 / dir3.  min_intensity is applied to a return. */
+typedef struct lrc_material {
+    uint32_t kind;          /* 0 diffuse, 1 glass, 2 mirror */
+    float    albedo;
+    float    pass;
+    float    retro_cos;
+} lrc_material;
+typedef struct lrc_material_model {
+    uint32_t num_classes;   /* 1..256 */
+    uint32_t max_bounces;   /* 0..8 */
+    float    min_intensity;
+    uint32_t reserved_;
+} lrc_material_model;
+typedef struct lrc_material_table lrc_material_table;
+int lrc_material_table_create(lrc_ctx* ctx, const lrc_material_model* model, const lrc_material* records,
+                              lrc_material_table** out_table);
+int lrc_material_table_destroy(lrc_material_table* table);
+int lrc_scan_materials_dev(lrc_scene* scene, const double* d_poses16, uint64_t num_poses, const double* d_dirs3,
+                           uint64_t rays_per_pose, const lrc_material_table* materials, double max_range,
+                           const lrc_hits* d_out, uint8_t* d_bounces /* nullable */, float* d_surface_point3 /* nullable */,
+                           void* stream);
+int lrc_scan_materials_compact(lrc_scene* scene, const double* poses16, uint64_t num_poses, const lrc_table* table,
+                               const lrc_material_table* materials, double max_range, const lrc_frames* out,
+                               float* intensity_rows /* nullable */, uint8_t* bounces_rows /* nullable */,
+                               float* surface_rows /* nullable */, uint64_t capacity, uint64_t* out_total);
+int lrc_material_step(const lrc_material_model* model, const lrc_material* records, uint64_t n, const float* t,
+                      const uint16_t* sem, const float* normal3, float* origin3, float* dir3, float* path, float* gain,
+                      uint8_t* bounces, uint8_t* status, float* intensity, float* surface_point3);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

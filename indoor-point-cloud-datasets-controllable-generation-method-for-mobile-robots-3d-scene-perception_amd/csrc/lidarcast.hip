@@ -184,6 +184,9 @@ struct TraceParams {
     // GEN = 6 (beam footprint and multi-echo returns, lrc_scan_echoes_*): the offset table and the reduction's parameters.  For
     // this generator rays_per_pose and total count LANES (G per beam, lrc_echo.h) in the kernel; launch_trace converts them
     lrcecho::Params echo;
+    // GEN = 7 (surface materials, lrc_scan_materials_*): the resident table, the model's limits and the two per-ray outputs that
+    // travel beside the record set (lrc_material.h)
+    lrcmat::Params mat;
 };
 
 // workgroup -> tile remap: consecutive tiles land on the same XCD (blocks b, b+8, ... share an L2),
@@ -333,10 +336,12 @@ __device__ __forceinline__ double range_filter(const TraceParams& p, double s, b
 // BY_PRIM: `best_slot` is the caller's triangle ROW (sector_kernel keys rays by (t, row)); labels and the normal then
 // come from the per-row plane table instead of the per-slot arrays -- same values.
 // HAVE_LABEL: the caller has slot_label[best_slot] already (trace_kernel issues the load together with the box clause's).
-template <bool FILTER_ALWAYS, bool BY_PRIM = false, bool HAVE_LABEL = false>
-__device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, uint32_t tid, V3 o, V3 d, double cx,
+// MAT: the intensity column receives the caller's value (the material chain's I, trace_kernel GEN = 7) in the place of |h.n|.
+// Returns whether the ray is kept.
+template <bool FILTER_ALWAYS, bool BY_PRIM = false, bool HAVE_LABEL = false, bool MAT = false>
+__device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, uint32_t tid, V3 o, V3 d, double cx,
                                            double cy, double cz, float tbest, uint32_t best_slot, uint32_t slot_label_in = 0u,
-                                           bool have_h = false, V3 h_in = V3{0.f, 0.f, 0.f}) {
+                                           bool have_h = false, V3 h_in = V3{0.f, 0.f, 0.f}, float inten_in = 0.f) {
     constexpr int GEN = FILTER_ALWAYS ? 1 : 0;
     const bool lean = FILTER_ALWAYS && !BY_PRIM && p.lean.row != nullptr;    // a kernel argument: wave-uniform
     bool keep = best_slot != 0xFFFFFFFFu;
@@ -395,7 +400,7 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
                 }
             }
             if (p.out.intensity)      // opt-in: Lambertian return |h.n|, float32 (same FMA order as every dot product here)
-                inten = __builtin_fabsf(fma_(hz, nz, fma_(hy, ny, hx * nx)));
+                inten = MAT ? inten_in : __builtin_fabsf(fma_(hz, nz, fma_(hy, ny, hx * nx)));
             if (!p.out.normal3) { nx = ny = nz = 0.f; }
         } else {
             px = py = pz = 0.f;
@@ -410,7 +415,7 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
         if ((tid & 15u) == 0) ((uint16_t*)p.lean.keep_mask)[gid >> 4] = (uint16_t)(m >> (tid & 48u));
         p.lean.row[gid] = make_float4(px, py, pz, __uint_as_float(label));
         p.lean.aux[gid] = make_uint2(__float_as_uint(t_out), keep ? best_slot : 0xFFFFFFFFu);
-        return;
+        return keep;
     }
     if (p.out.tile_count) {   // kept rays of this wave's 64 consecutive outputs (feeds lrc_compact_dev)
         const unsigned long long m = __ballot(keep);
@@ -425,7 +430,7 @@ __device__ __forceinline__ void write_back(const TraceParams& p, uint64_t gid, u
     if (p.out.ins) p.out.ins[gid] = (uint16_t)(label >> 16);
     if (p.out.incident_deg) p.out.incident_deg[gid] = inc;
     if (p.out.intensity) p.out.intensity[gid] = inten;
-
+    return keep;
 }
 
 constexpr int kStatsWords = 5;   // node steps, triangle tests, wave-uniform node steps, dead node steps, pad-clause rejections
@@ -683,11 +688,13 @@ __global__ __launch_bounds__(64) void ray_table_kernel(const double* __restrict_
 //      5 = pose x direction table with seeded range noise, angle jitter and dropout drawn per ray (opt-in; same ray order as 1)
 //      6 = pose x direction table x offset table: K sub-rays per beam in the G neighbouring lanes of a group, reduced to at
 //          most E echoes per beam behind the traversal (opt-in; lrc_echo.h)
+//      7 = pose x direction table with surface materials: a ray that meets glass or a mirror is continued from its hit point,
+//          segment by segment, behind the first traversal (opt-in; same ray order as 1; lrc_material.h)
 // QN: 1 = walk the quantised node images (32-byte nodes for the per-lane fetches), 2 = walk their
 //     four-wide collapse (64-byte nodes, half the steps); a wave with a ray outside the bound the quantisation margin is
 //     proven for walks the float32 world-space nodes instead
 template <int GEN, int LEAFW, bool UNI, bool SPEC, bool STATS = false, int QN = 0>
-__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4 || GEN == 5 || GEN == 6)) ? 8 : 1) void trace_kernel(const TraceParams p) {
+__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4 || GEN == 5 || GEN == 6)) ? 8 : (!STATS && GEN == 7) ? 6 : 1) void trace_kernel(const TraceParams p) {
     extern __shared__ int s_stack[];   // [stack depth][kTBlock]: one column per lane, conflict free
     const uint32_t tid = threadIdx.x;
     if (GEN == 1 && p.pre.blocks != 0u && p.pre.sharded != 0u) {
@@ -795,6 +802,11 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         const uint64_t pose = gid / p.rays_per_pose;
         const uint64_t i = gid - pose * p.rays_per_pose;
         gen_ray_noisy(p.poses16, p.dirs3, p.noise, pose, i, o, d, cx, cy, cz, live);
+        pose32 = (uint32_t)pose;
+    } else if (GEN == 7) {
+        const uint64_t pose = gid / p.rays_per_pose;
+        double ux, uy, uz;          // the centre is fetched again behind the traversal
+        gen_ray(p.poses16, p.dirs3, pose, gid - pose * p.rays_per_pose, o, d, ux, uy, uz);
         pose32 = (uint32_t)pose;
     } else if (GEN == 6) {
         // lane gid = beam * G + k.  64 % G == 0 and a pose is a whole number of groups, so k is the lane's place in its group of
@@ -1302,6 +1314,69 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         const uint64_t rec = beam * (uint32_t)p.echo.max_echoes + k;
         write_back<true, false, true>(p, rec, tid, o, d, cx, cy, cz, t_e, slot_e, label_e, false, h_tab);
         if (p.echo.weight) p.echo.weight[rec] = (uint8_t)n_e;
+        return;
+    }
+    if (GEN == 7) {
+        // ---- the chain of segments (lrc_material.h states the step) ----
+        // Behind every traversal a pending lane looks at its closest hit: the surface returns, the chain is cut at the cap, or the
+        // ray goes on as a new segment.  While any lane of the wave goes on (ballot) those lanes traverse again, over the float32
+        // nodes with the clause tested per triangle as the redo route does -- continued rays of a wave share no octant -- and the
+        // finished lanes idle.  Carried: T, g, b and the current (o, d); a finished lane keeps its final slot in best_slot.
+        // A finished lane needs its segment no longer: its origin's registers keep the surface point and d.x the intensity.
+        // need_geom (kernel arguments: uniform over the launch): some output reads I or pp.  Where none does, a lane on a diffuse
+        // surface -- which ends the chain whatever c is -- adds t to T and is done: no normal, no unit direction.
+        const bool need_geom = p.out.intensity != nullptr || p.mat.surface3 != nullptr || p.mat.min_intensity > 0.0f;
+        float T = 0.0f, g = 1.0f;
+        uint32_t b = 0u;
+        bool pend = true;
+        bool touched = false;      // this lane's (o, d) no longer hold the original ray
+        while (true) {
+            bool cont = false;
+            if (pend && best_slot == 0xFFFFFFFFu) pend = false;      // a miss: no return
+            if (pend) {
+                const lrcmat::Record m = lrcmat::record_of(p.mat.table, p.mat.num_classes, best_label & 0xFFFFu);
+                if (m.kind == lrcmat::kDiffuse && !need_geom) {
+                    T = lrcmat::path_add(T, tbest);
+                    pend = false;
+                } else {
+                    float nx, ny, nz, I = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+                    touched = true;
+                    slot_normal(p.tris[(size_t)best_slot * 3 + 2], nx, ny, nz);
+                    lrcmat::Seg sg{o.x, o.y, o.z, d.x, d.y, d.z, T, g, b};
+                    const int r = lrcmat::step(sg, tbest, nx, ny, nz, m, p.mat.max_bounces, I, sx, sy, sz);
+                    T = sg.T; g = sg.g; b = sg.b;
+                    if (r == lrcmat::kContinue) {
+                        o = V3{sg.ox, sg.oy, sg.oz}; d = V3{sg.dx, sg.dy, sg.dz};
+                        tbest = __builtin_inff(); best_slot = 0xFFFFFFFFu; best_prim = 0xFFFFFFFFu;
+                        cont = finite_ray(o, d);      // a segment that is not finite is a miss, as for every cast
+                    } else {
+                        pend = false;
+                        o = V3{sx, sy, sz}; d.x = I;
+                        if (r == lrcmat::kNoReturn) best_slot = 0xFFFFFFFFu;
+                    }
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(cont) == 0ull) break;
+            if (cont) traverse(IntTag<0>{}, IntTag<1>{});
+            // every lane loads its label again, as behind the redo route: it is not held through the traversal
+            best_label = best_slot != 0xFFFFFFFFu ? p.slot_label[best_slot] : 0u;
+        }
+        const float I = d.x, sx = o.x, sy = o.y, sz = o.z;      // of a lane with a return; anything else is not kept
+        if (need_geom && best_slot != 0xFFFFFFFFu && I < p.mat.min_intensity) best_slot = 0xFFFFFFFFu;
+        // the record is the ORIGINAL ray's at the total path length: gen_ray's bits again, not held through the loop.  A wave none
+        // of whose lanes took the step still has it in (o, d), the registers of the current segment: nothing to form.
+        if (__builtin_amdgcn_ballot_w64(touched) != 0ull) {
+            const double* M = p.poses16;
+            asm volatile("" : "+s"(M));
+            double ux, uy, uz;
+            gen_ray(M, p.dirs3, pose32, gid_w - (uint64_t)pose32 * p.rays_per_pose, o, d, ux, uy, uz);
+        }
+        const bool kept = write_back<true, false, true, true>(p, gid_w, tid, o, d, cx, cy, cz, T, best_slot, best_label, false, h_tab, I);
+        if (p.mat.bounces) p.mat.bounces[gid_w] = kept ? (uint8_t)b : (uint8_t)0;
+        if (p.mat.surface3) {
+            float* q = p.mat.surface3 + gid_w * 3;
+            q[0] = kept ? sx : 0.0f; q[1] = kept ? sy : 0.0f; q[2] = kept ? sz : 0.0f;
+        }
         return;
     }
     write_back<GEN != 0, false, true>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot, best_label, have_h, h_tab);
@@ -2347,7 +2422,7 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
         return 1;
     }
     const bool plain = leafw == kLeafW && uni && !spec && !(qn && wide);
-    if (plain || gen == 2 || gen == 4 || gen == 5 || gen == 6) return 1;
+    if (plain || gen == 2 || gen == 4 || gen == 5 || gen == 6 || gen == 7) return 1;
     const bool wide_only = qn && wide && leafw == kLeafW && uni && !spec;
     if (gen == 1) { if (wide_only) LRC_LAB(1, kLeafW, true, false, 2); else LRC_LAB_PICK(1); }
     else { if (wide_only) LRC_LAB(0, kLeafW, true, false, 2); else LRC_LAB_PICK(0); }
@@ -2364,7 +2439,8 @@ static size_t trace_lds_bytes(uint32_t depth) { return (size_t)depth * kTBlock *
 // One launch of the trace kernel over p.total rays.  gen: 0 explicit rays, 1 pose x direction table, 2 pose x scan angles,
 // 3 a grid scan (lrc_scan_grid_*: the per-ray kernel here; the packet kernel in the laboratory build), 4 moving-sensor sweeps
 // (motion record x direction table x firing fractions), 5 pose x direction table with seeded sensor noise (p.noise), 6 pose x
-// direction table x beam offsets, reduced to echoes (p.echo; p.total and p.rays_per_pose count echo records on entry).
+// direction table x beam offsets, reduced to echoes (p.echo; p.total and p.rays_per_pose count echo records on entry), 7 pose x
+// direction table with surface materials (p.mat).
 static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, bool stats = false) {
     p.nodes = s->d_nodes;
     p.tris = s->d_tris;
@@ -2415,7 +2491,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     // is worth more than the balance: measured +1...+16 % for the striped order there, -1...-10 % on the cache-resident
     // scenes (profiles/r03_xcd_striping_sweep.txt).
     constexpr uint64_t kStripeSceneBytes = 192ull << 20;
-    if ((gen == 1 || gen == 4 || gen == 5 || gen == 6) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
+    if ((gen == 1 || gen == 4 || gen == 5 || gen == 6 || gen == 7) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
         const uint64_t tpp = p.rays_per_pose / 64;
         if (tpp % 16 == 0) {
             const uint64_t chunk = tpp / 16;
@@ -2467,6 +2543,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     else if (gen == 4) LRC_LAUNCH(4, false);
     else if (gen == 5) LRC_LAUNCH(5, false);
     else if (gen == 6) LRC_LAUNCH(6, false);
+    else if (gen == 7) LRC_LAUNCH(7, false);
     else if (gen == 2) LRC_LAUNCH(2, false);
     else LRC_LAUNCH(0, false);
 #undef LRC_LAUNCH
@@ -2634,6 +2711,18 @@ int echo_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const doubl
     p.echo = ep;
     scan_fields(p, N * ep.max_echoes, P * N * ep.max_echoes, max_range, d_out);
     return launch_trace(s, p, 6, st);
+}
+
+// The trace launch of lrc_scan_materials_dev, whose arguments lrc_material.hip has checked (declared in lrc_internal.h): mp.table,
+// mp.bounces and mp.surface3 are device pointers, d_out holds P * N records.
+int material_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N, const lrcmat::Params& mp,
+                      double max_range, const lrc_hits* d_out, hipStream_t st) {
+    TraceParams p{};
+    p.poses16 = d_poses16;
+    p.dirs3 = d_dirs3;
+    p.mat = mp;
+    scan_fields(p, N, P * N, max_range, d_out);
+    return launch_trace(s, p, 7, st);
 }
 
 // ---- host-pointer convenience wrappers ---------------------------------------------------------
@@ -3844,6 +3933,7 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
     // before the copy engine asks for them (C3: 1.48 ms against 1.53 for four equal chunks; tools/chunk_scheme_sweep.sh,
     // profiles/r03_chunk_schemes.txt).  Equal chunks for short trajectories.
     if (gen == 6) chunks = 1;      // echoes: the weight rows are gathered from ONE packed run of compacted rows (echo_scan_compact)
+    if (gen == 7) chunks = 1;      // materials: likewise for intensity, bounces and surface points (material_scan_compact)
     bool graded = chunks == 4 && P >= 8;
     uint32_t ends32[8] = {4, 16, 32, 32, 32, 32, 32, 32};       // chunk ends in 32nds of the trajectory
     if (graded) chunks = 3;
@@ -4013,10 +4103,74 @@ int scan_compact_impl(lrc_scene* s, const double* poses16, uint64_t P, const dou
 }
 }  // namespace
 
+// ---- per-ray columns beside the record set, for the kept rows ----------------------------------------------------------------
+// A scan family whose records carry a column a frame has no place for (the echo weight; intensity, bounces and surface points
+// of the material scan) keeps it at the fixed stride and gathers it for the kept rows by the compacted index column: row r of
+// the compacted arrays belongs to the pose whose run [prefix[p], prefix[p + 1]) holds it; its record is that pose's
+// index[r]-th.  One thread per row; the prefix is small (P + 1 values) and searched by bisection.  W: the column's word
+// (uint8_t or a 4-byte word), `words` of them per record.
+namespace {
+template <class W>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const uint64_t* __restrict__ prefix, uint32_t P,
+                                                          const uint32_t* __restrict__ index, const W* __restrict__ src,
+                                                          uint32_t words, uint64_t records_per_pose, uint64_t rows,
+                                                          W* __restrict__ out) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (r >= rows) return;
+    uint32_t lo = 0, hi = P;           // prefix[lo] <= r < prefix[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (prefix[mid] <= r) lo = mid; else hi = mid;
+    }
+    const uint32_t i = index[r];
+    const bool ok = i < records_per_pose;
+    const uint64_t from = ((uint64_t)lo * records_per_pose + (ok ? i : 0u)) * words;
+    for (uint32_t w = 0; w < words; ++w) out[r * words + w] = ok ? src[from + w] : (W)0;
+}
+
+struct GatherColumn {
+    const void* d_src;       // device: the column at the fixed stride; NULL: skipped
+    void* host_dst;          // host: `rows` records; NULL: skipped
+    uint32_t word_bytes;     // 1 or 4
+    uint32_t words;          // per record
+};
+
+// `who` prefixes the messages; counts: host, per pose, adding up to `rows`
+int gather_rows_by_index(const char* who, const uint64_t* counts, uint64_t P, const uint32_t* d_index, uint64_t records_per_pose,
+                         uint64_t rows, const GatherColumn* cols, int ncols) {
+    if (!rows) return LRC_OK;
+    if (P > 0x7FFFFFFFull || blocks_of(rows, 256) > 0x7FFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": too many poses or rows for the gather of the per-ray columns");
+    std::vector<uint64_t> prefix(P + 1, 0);
+    for (uint64_t p = 0; p < P; ++p) prefix[p + 1] = prefix[p] + counts[p];
+    if (prefix[P] != rows) return fail(LRC_ERR_INTERNAL, std::string(who) + ": counts do not add up to the kept rows");
+    Buf d_prefix;
+    LRC_HIP(hipMalloc(&d_prefix.p, (P + 1) * 8));
+    LRC_HIP(hipMemcpy(d_prefix.p, prefix.data(), (P + 1) * 8, hipMemcpyHostToDevice));
+    const dim3 grid((uint32_t)blocks_of(rows, 256));
+    for (int c = 0; c < ncols; ++c) {
+        const GatherColumn& g = cols[c];
+        if (!g.d_src || !g.host_dst) continue;
+        const size_t bytes = (size_t)rows * g.word_bytes * g.words;
+        Buf d_out;
+        LRC_HIP(hipMalloc(&d_out.p, bytes));
+        if (g.word_bytes == 1)
+            hipLaunchKernelGGL(gather_rows_kernel<uint8_t>, grid, dim3(256), 0, nullptr, (const uint64_t*)d_prefix.p, (uint32_t)P, d_index,
+                               (const uint8_t*)g.d_src, g.words, records_per_pose, rows, (uint8_t*)d_out.p);
+        else
+            hipLaunchKernelGGL(gather_rows_kernel<uint32_t>, grid, dim3(256), 0, nullptr, (const uint64_t*)d_prefix.p, (uint32_t)P, d_index,
+                               (const uint32_t*)g.d_src, g.words, records_per_pose, rows, (uint32_t*)d_out.p);
+        LRC_HIP(hipGetLastError());
+        LRC_HIP(hipMemcpy(g.host_dst, d_out.p, bytes, hipMemcpyDeviceToHost));
+    }
+    return LRC_OK;
+}
+}  // namespace
+
 // lrc_scan_echoes_compact behind its checks (lrc_echo.hip; declared in lrc_internal.h).  The echo records are compacted by the
 // path every *_compact entry point takes, as P poses of N * E records: `index` comes out as i * E + e.  No wave of the echo
 // kernel writes 64 consecutive records, so the record set carries no per-tile keep counts and lrc_compact_dev counts itself.  The
-// weights of the kept rows are gathered on the device by the compacted index column (echo_gather_rows, lrc_echo.hip).
+// weights of the kept rows are gathered on the device by the compacted index column (gather_rows_by_index above).
 int echo_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, const double* offsets2,
                       lrcecho::Params ep, double max_range, const lrc_frames* out, uint8_t* weight_rows, uint64_t capacity,
                       uint64_t* out_total) {
@@ -4050,8 +4204,60 @@ int echo_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc
     uint64_t total = 0;
     rc = frames_finish(s, p, 6, st, P, NE, out, capacity, &total);
     if (out_total) *out_total = total;
-    if (rc == LRC_OK && weight_rows && total)
-        rc = echo_gather_rows(ctx, out->counts, P, st.io.out_index, ep.weight, NE, total, weight_rows);
+    if (rc == LRC_OK && weight_rows && total) {
+        const GatherColumn col{ep.weight, weight_rows, 1, 1};
+        rc = gather_rows_by_index("lrc_scan_echoes_compact", out->counts, P, st.io.out_index, NE, total, &col, 1);
+    }
+    return guard.done(rc);
+}
+
+// lrc_scan_materials_compact behind its checks (lrc_material.hip; declared in lrc_internal.h): the path every *_compact entry
+// point takes, with three per-ray columns a frame has no place for -- the intensity of the record set, bounces and surface points
+// -- in buffers of their own (pool slots), gathered for the kept rows on the device by the compacted index column
+// (gather_rows_by_index above).
+int material_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, lrcmat::Params mp,
+                          double max_range, const lrc_frames* out, float* intensity_rows, uint8_t* bounces_rows, float* surface_rows,
+                          uint64_t capacity, uint64_t* out_total) {
+    SyncUnlessOk guard;
+    lrc_ctx* const ctx = s->ctx;
+    const uint64_t N = table->n, n = P * N;
+    int rc;
+    if ((rc = ensure_streams(ctx))) return rc;
+    const hipStream_t in = ctx->s_compute;
+    TraceParams p{};
+    p.dirs3 = table->d_dirs3;
+    if ((rc = stage_input(ctx, kPoolPoses, poses16, P * 16, &p.poses16, &in))) return rc;
+    FrameStage st;
+    if ((rc = st.alloc(ctx, *out, P, n))) return rc;
+    const bool gather = intensity_rows || bounces_rows || surface_rows;
+    if (gather && !st.io.out_index) {       // the gather reads the index column whether or not the caller asked for it
+        if ((rc = st.oidx.get(ctx, kPoolOutIdx, n * 4))) return rc;
+        st.io.out_index = (uint32_t*)st.oidx.p;
+    }
+    DevBuf ibuf, bbuf, sbuf;
+    mp.bounces = nullptr;
+    mp.surface3 = nullptr;
+    if (intensity_rows) {
+        if ((rc = ibuf.get(ctx, kPoolInten, n * 4))) return rc;
+        st.rec.intensity = (float*)ibuf.p;
+    }
+    if (bounces_rows) {
+        if ((rc = bbuf.get(ctx, kPoolKeep, n))) return rc;
+        mp.bounces = (uint8_t*)bbuf.p;
+    }
+    if (surface_rows) {
+        if ((rc = sbuf.get(ctx, kPoolNormal, n * 12))) return rc;      // no frame column lives in the normals' slot
+        mp.surface3 = (float*)sbuf.p;
+    }
+    p.mat = mp;
+    scan_fields(p, N, n, max_range, nullptr);
+    uint64_t total = 0;
+    rc = frames_finish(s, p, 7, st, P, N, out, capacity, &total);
+    if (out_total) *out_total = total;
+    if (rc == LRC_OK && gather && total) {
+        const GatherColumn cols[3] = {{st.rec.intensity, intensity_rows, 4, 1}, {mp.bounces, bounces_rows, 1, 1}, {mp.surface3, surface_rows, 4, 3}};
+        rc = gather_rows_by_index("lrc_scan_materials_compact", out->counts, P, st.io.out_index, N, total, cols, 3);
+    }
     return guard.done(rc);
 }
 

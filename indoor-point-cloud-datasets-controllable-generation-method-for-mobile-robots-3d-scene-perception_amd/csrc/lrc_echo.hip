@@ -1,8 +1,7 @@
 // lrc_echo.hip -- host side of the beam footprint and multi-echo returns (lrc_echo.h): the argument checks, the entry points
 // lrc_scan_echoes_dev / lrc_scan_echoes_compact (the trace launch and the frame path are lidarcast.hip's: echo_scan_dev,
-// echo_scan_compact), the gather of the kept rows' weights and the host reduction lrc_echo_reduce.
+// echo_scan_compact, which also gathers the kept rows' weights) and the host reduction lrc_echo_reduce.
 #include <cmath>
-#include <vector>
 
 #include "lrc_internal.h"
 #include "lrc_echo.h"
@@ -28,45 +27,7 @@ int check_beam(const char* who, const lrc_beam* b, lrcecho::Params* out) {
     return LRC_OK;
 }
 
-// row r of the compacted arrays belongs to the pose whose run [prefix[p], prefix[p + 1]) holds it; its record is that pose's
-// index[r]-th.  One thread per row; the prefix is small (P + 1 values) and searched by bisection.
-__global__ __launch_bounds__(256) void echo_gather_kernel(const uint64_t* __restrict__ prefix, uint32_t P,
-                                                          const uint32_t* __restrict__ index, const uint8_t* __restrict__ weight,
-                                                          uint64_t records_per_pose, uint64_t rows, uint8_t* __restrict__ out) {
-    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (r >= rows) return;
-    uint32_t lo = 0, hi = P;           // prefix[lo] <= r < prefix[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (prefix[mid] <= r) lo = mid; else hi = mid;
-    }
-    const uint32_t i = index[r];
-    out[r] = i < records_per_pose ? weight[(uint64_t)lo * records_per_pose + i] : (uint8_t)0;
-}
-
 }  // namespace
-
-#pragma GCC visibility push(hidden)
-int echo_gather_rows(lrc_ctx* ctx, const uint64_t* counts, uint64_t P, const uint32_t* d_index, const uint8_t* d_weight,
-                     uint64_t records_per_pose, uint64_t rows, uint8_t* weight_rows) {
-    (void)ctx;
-    if (!rows) return LRC_OK;
-    if (P > 0x7FFFFFFFull || blocks_of(rows, 256) > 0x7FFFFFFFull)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_echoes_compact: too many poses or rows for the weight gather");
-    std::vector<uint64_t> prefix(P + 1, 0);
-    for (uint64_t p = 0; p < P; ++p) prefix[p + 1] = prefix[p] + counts[p];
-    if (prefix[P] != rows) return fail(LRC_ERR_INTERNAL, "lrc_scan_echoes_compact: counts do not add up to the kept rows");
-    Buf d_prefix, d_out;
-    LRC_HIP(hipMalloc(&d_prefix.p, (P + 1) * 8));
-    LRC_HIP(hipMalloc(&d_out.p, rows));
-    LRC_HIP(hipMemcpy(d_prefix.p, prefix.data(), (P + 1) * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(echo_gather_kernel, dim3((uint32_t)blocks_of(rows, 256)), dim3(256), 0, nullptr,
-                       (const uint64_t*)d_prefix.p, (uint32_t)P, d_index, d_weight, records_per_pose, rows, (uint8_t*)d_out.p);
-    LRC_HIP(hipGetLastError());
-    LRC_HIP(hipMemcpy(weight_rows, d_out.p, rows, hipMemcpyDeviceToHost));
-    return LRC_OK;
-}
-#pragma GCC visibility pop
 
 extern "C" {
 

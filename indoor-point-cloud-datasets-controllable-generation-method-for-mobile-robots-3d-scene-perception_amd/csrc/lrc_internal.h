@@ -13,6 +13,7 @@
 #include "lrc_bvh_device.h"
 #include "lrc_noise.h"
 #include "lrc_echo.h"
+#include "lrc_material.h"
 
 // sets lrc_last_error() (lidarcast.hip).  Exported: lrc_nprandom.cpp, built without HIP headers, reports through it.
 extern "C" int lrc_internal_fail(int code, const char* msg);
@@ -110,6 +111,12 @@ struct lrc_table {            // a sensor's direction table resident in HBM (lrc
     double* d_fire = nullptr;   // optional (lrc_table_set_fire): per ray the fraction of the sweep at which it fires
 };
 
+struct lrc_material_table {   // a material table resident in HBM (lrc_material_table_create): num_classes records and the model
+    lrc_ctx* ctx = nullptr;
+    lrcmat::Record* d_records = nullptr;
+    lrc_material_model model{};
+};
+
 struct lrc_scene {
     lrc_ctx* ctx = nullptr;
     void* slab = nullptr;             // device-built scenes: ONE allocation holds every array below except d_slot_sphere / *4
@@ -175,14 +182,22 @@ int noise_params(lrc_ctx* ctx, const char* who, const lrc_noise* nz, uint64_t N,
 
 // beam footprint and multi-echo returns.  lrc_echo.hip checks the arguments of lrc_scan_echoes_* and fills an lrcecho::Params;
 // lidarcast.hip, which owns the trace kernel and the frame path, launches (echo_scan_dev) and scans to frames
-// (echo_scan_compact: host poses and offsets, ep.offsets2 / ep.weight are filled there); lrc_echo.hip gathers the weights of the
-// `rows` kept rows from the fixed-stride weights by the compacted index column (counts: host, per pose).
+// (echo_scan_compact: host poses and offsets, ep.offsets2 / ep.weight are filled there; the weights of the kept rows are gathered
+// there from the fixed-stride weights by the compacted index column).
 int echo_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N, const lrcecho::Params& ep,
                   double max_range, const lrc_hits* d_out, hipStream_t st);
 int echo_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, const double* offsets2,
                       lrcecho::Params ep, double max_range, const lrc_frames* out, uint8_t* weight_rows, uint64_t capacity,
                       uint64_t* out_total);
-int echo_gather_rows(lrc_ctx* ctx, const uint64_t* counts, uint64_t P, const uint32_t* d_index, const uint8_t* d_weight,
-                     uint64_t records_per_pose, uint64_t rows, uint8_t* weight_rows);
+
+// surface materials.  lrc_material.hip checks the arguments of lrc_scan_materials_* and fills an lrcmat::Params from the resident
+// table; lidarcast.hip, which owns the trace kernel and the frame path, launches (material_scan_dev) and scans to frames
+// (material_scan_compact: host poses; mp.bounces / mp.surface3 and the intensity column are its own device buffers, gathered
+// there for the kept rows by the compacted index column; a NULL destination is skipped).
+int material_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N, const lrcmat::Params& mp,
+                      double max_range, const lrc_hits* d_out, hipStream_t st);
+int material_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, lrcmat::Params mp,
+                          double max_range, const lrc_frames* out, float* intensity_rows, uint8_t* bounces_rows, float* surface_rows,
+                          uint64_t capacity, uint64_t* out_total);
 
 #pragma GCC visibility pop

@@ -37,6 +37,8 @@ SYMBOLS = (
     "lrc_scan_sweeps_dev", "lrc_table_set_fire", "lrc_scan_sweeps_compact",
     "lrc_scan_noisy_dev", "lrc_scan_noisy_compact", "lrc_noise_draws", "lrc_noise_table",
     "lrc_scan_echoes_dev", "lrc_scan_echoes_compact", "lrc_echo_reduce",
+    "lrc_material_table_create", "lrc_material_table_destroy", "lrc_scan_materials_dev", "lrc_scan_materials_compact",
+    "lrc_material_step",
     "lrc_compact", "lrc_compact_dev", "lrc_cloud_from_ranges_dev", "lrc_cloud_from_prims_dev",
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
@@ -85,6 +87,15 @@ class LrcNoise(C.Structure):
 
 class LrcBeam(C.Structure):
     _fields_ = [("subrays", C.c_uint32), ("max_echoes", C.c_uint32), ("min_count", C.c_uint32), ("separation", C.c_float)]
+
+
+class LrcMaterial(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("albedo", C.c_float), ("pass_", C.c_float), ("retro_cos", C.c_float)]
+
+
+class LrcMaterialModel(C.Structure):
+    _fields_ = [("num_classes", C.c_uint32), ("max_bounces", C.c_uint32), ("min_intensity", C.c_float),
+                ("reserved_", C.c_uint32)]
 
 
 class LrcCoverageInfo(C.Structure):
@@ -265,6 +276,11 @@ def load():
         "lrc_scan_echoes_dev": [vp, vp, u64, vp, u64, vp, C.POINTER(LrcBeam), dbl, C.POINTER(LrcHits), vp, vp],
         "lrc_scan_echoes_compact": [vp, vp, u64, vp, vp, C.POINTER(LrcBeam), dbl, C.POINTER(LrcFrames), vp, u64, C.POINTER(u64)],
         "lrc_echo_reduce": [vp, u64, C.POINTER(LrcBeam), vp, vp],
+        "lrc_material_table_create": [vp, C.POINTER(LrcMaterialModel), vp, C.POINTER(vp)],
+        "lrc_material_table_destroy": [vp],
+        "lrc_scan_materials_dev": [vp, vp, u64, vp, u64, vp, dbl, C.POINTER(LrcHits), vp, vp, vp],
+        "lrc_scan_materials_compact": [vp, vp, u64, vp, vp, dbl, C.POINTER(LrcFrames), vp, vp, vp, u64, C.POINTER(u64)],
+        "lrc_material_step": [C.POINTER(LrcMaterialModel), vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "lrc_occ_create": [vp, vp, u64, C.POINTER(vp)],
         "lrc_occ_destroy": [vp],
         "lrc_occ_query": [vp, vp, u64, dbl, vp],

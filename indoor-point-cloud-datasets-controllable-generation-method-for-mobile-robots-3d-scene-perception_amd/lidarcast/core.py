@@ -731,6 +731,41 @@ class Scene:
             if own is not None:
                 own.close()
 
+    def scan_materials_compact(self, poses, dirs, max_range, materials, want=("point3", "sem", "ins"), capacity=None):
+        """Pose-batched scan with surface materials straight to frames (lrc_scan_materials_compact): ``materials`` a
+        ``lidarcast.material.MaterialTable``, ``dirs`` a DirectionTable or an (N, 3) table.  The return value of
+        ``scan_poses_compact`` plus, one entry per kept row, ``intensity`` (float32: the return's strength), ``bounces`` (uint8:
+        the glass panes and mirrors on the way) and ``surface_point3`` (float32 x 3: where the return physically came from;
+        ``point3`` lies on the original beam at the total path length)."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
+        own = None
+        if isinstance(dirs, DirectionTable):
+            if not dirs._h:
+                raise ValueError("direction table handle is closed")
+            if dirs.ctx is not self.ctx:
+                raise ValueError("direction table belongs to another context (device)")
+            table = dirs
+        else:
+            table = own = DirectionTable(self.ctx, dirs)
+        try:
+            P, N = poses.shape[0], table.n
+            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
+            inten = np.zeros(max(cap, 1), dtype=np.float32)
+            bounces = np.zeros(max(cap, 1), dtype=np.uint8)
+            surface = np.zeros((max(cap, 1), 3), dtype=np.float32)
+            total = C.c_uint64(0)
+            check(self._lib.lrc_scan_materials_compact(self._h, _ptr(poses), P, table._h, materials.resident(self.ctx),
+                                                       float(max_range), C.byref(fr), _ptr(inten), _ptr(bounces), _ptr(surface),
+                                                       cap, C.byref(total)), "lrc_scan_materials_compact")
+            out = self._frames_end(counts, bufs, total.value)
+            out["intensity"] = inten[:total.value]
+            out["bounces"] = bounces[:total.value]
+            out["surface_point3"] = surface[:total.value]
+            return out
+        finally:
+            if own is not None:
+                own.close()
+
     def scan_angles_compact(self, poses, angles, keep, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Dual-axis sensor, rays generated in the kernel from host-drawn (phi, theta) (lrc_scan_angles_compact).
         angles: (P, N, 2) float64; keep: (P, N) bool / uint8 or None."""
@@ -838,6 +873,34 @@ class Scene:
                                             C.byref(hits.struct), None if weight_t is None else C.c_void_p(weight_t.data_ptr()),
                                             C.c_void_p(int(stream))), "lrc_scan_echoes_dev")
         return offsets_t
+
+    def scan_materials_dev(self, poses_t, dirs_t, hits, max_range, materials, bounces_t=None, surface_t=None, stream=0):
+        """Pose-batched scan with surface materials on device tensors (lrc_scan_materials_dev): poses_t (P, 16) float64, dirs_t
+        (N, 3) float64, ``materials`` a ``lidarcast.material.MaterialTable``; ``bounces_t`` an optional (P * N) uint8 tensor,
+        ``surface_t`` an optional (P * N, 3) float32 tensor.  ``hits`` holds P * N records; its intensity column receives the
+        return's strength."""
+        P, N = poses_t.shape[0], dirs_t.shape[0]
+        if hits.n != P * N:
+            raise ValueError("hits must hold P * N records")
+        if bounces_t is not None and bounces_t.numel() != P * N:
+            raise ValueError("bounces_t must hold P * N entries")
+        if surface_t is not None and surface_t.numel() != 3 * P * N:
+            raise ValueError("surface_t must be (P * N, 3)")
+        import torch
+        for name, t, dt in (("bounces_t", bounces_t, torch.uint8), ("surface_t", surface_t, torch.float32)):
+            if t is None:
+                continue
+            if t.dtype != dt:
+                raise ValueError(f"{name} must be {dt} (the kernel writes that many bytes per ray)")
+            if t.device != poses_t.device or not t.is_cuda:
+                raise ValueError(f"{name} must lie on the device of the poses")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        check(self._lib.lrc_scan_materials_dev(self._h, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
+                                               materials.resident(self.ctx), float(max_range), C.byref(hits.struct),
+                                               None if bounces_t is None else C.c_void_p(bounces_t.data_ptr()),
+                                               None if surface_t is None else C.c_void_p(surface_t.data_ptr()),
+                                               C.c_void_p(int(stream))), "lrc_scan_materials_dev")
 
     def scan_sweeps_dev(self, motion_t, dirs_t, fire_t, hits, max_range, stream=0):
         """Moving-sensor sweeps on device tensors (lrc_scan_sweeps_dev): motion_t (P, 24) float64, dirs_t (N, 3) float64,

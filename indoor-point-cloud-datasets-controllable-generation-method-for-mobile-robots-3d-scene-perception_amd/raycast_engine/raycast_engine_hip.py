@@ -384,6 +384,17 @@ class RaycastEngineHIP(RaycastEngineBase):
         return self.scene_for(mesh).scan_echoes_compact(poses, self._resident_table(intrinsics), intrinsics.max_range, beam,
                                                         want=want)
 
+    def scan_material_frames(self, intrinsics, poses, mesh, materials, want=("point3", "sem", "ins")):
+        """``scan_frames`` with surface materials (lrc_scan_materials_compact): ``materials`` a
+        ``lidarcast.material.MaterialTable``.  A ray that meets glass or a mirror goes on inside the kernel; the dict of
+        ``scan_frames`` plus, per kept row, ``intensity``, ``bounces`` and ``surface_point3`` (``point3`` lies on the original
+        beam at the total path length; sem / ins are the final surface's)."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
+            raise ValueError("surface materials need a sensor with a pose-independent direction table")
+        return self.scene_for(mesh).scan_materials_compact(poses, self._resident_table(intrinsics), intrinsics.max_range,
+                                                           materials, want=want)
+
     def _firing_fractions(self, intrinsics):
         """(N,) firing fractions of the sensor's direction table (IndoorLidar.firing_fractions), cached with the table."""
         from lidar import IndoorLidar

@@ -202,6 +202,8 @@ class S3DISSimulator:
             raise NotImplementedError("surface coverage under the noise key is outside its scope")
         if self.config.get("beam") is not None:
             raise NotImplementedError("surface coverage under the beam key is outside its scope")
+        if self.config.get("materials") is not None:
+            raise NotImplementedError("surface coverage under the materials key is outside its scope")
         from lidarcast.synth import S3DIS_CLASSES
         s = self.raycast_engine.surface_coverage(self.lidar_config, poses_from_waypoints(waypoints),
                                                  self.scene.room_mesh)
@@ -225,6 +227,8 @@ class S3DISSimulator:
             raise NotImplementedError("occupancy grids under the noise key are outside their scope")
         if self.config.get("beam") is not None:
             raise NotImplementedError("occupancy grids under the beam key are outside their scope")
+        if self.config.get("materials") is not None:
+            raise NotImplementedError("occupancy grids under the materials key are outside their scope")
         from containers.s3dis_sim_scene import write_labeled_ply
         from lidarcast.synth import S3DIS_CLASSES
         r = self.raycast_engine.occupancy_grid(self.lidar_config, poses_from_waypoints(waypoints), self.scene.room_mesh,
@@ -261,6 +265,8 @@ class S3DISSimulator:
             raise NotImplementedError("frame annotations under the noise key are outside their scope")
         if self.config.get("beam") is not None:
             raise NotImplementedError("frame annotations under the beam key are outside their scope")
+        if self.config.get("materials") is not None:
+            raise NotImplementedError("frame annotations under the materials key are outside their scope")
         from lidar_net_bbox_visualizer import S3DIS_SEMANTIC_MAPPING
         from lidarcast.synth import S3DIS_CLASSES
         mapping = S3DIS_SEMANTIC_MAPPING if semantic_mapping is None else semantic_mapping
@@ -335,6 +341,24 @@ class S3DISSimulator:
         kw = {k: cfg[k] for k in ("pattern", "max_echoes", "separation", "min_fraction") if k in cfg}
         return BeamModel(float(cfg["divergence_mrad"]) * 1e-3, **kw)
 
+    def _material_table(self):
+        """The MaterialTable of the config key ``materials`` (None without the key): ``classes`` maps a class name (S3DIS class
+        list) or a semantic id to ``{kind: diffuse | glass | mirror, albedo?, pass?, retro_deg? or retro_cos?}``;
+        ``max_bounces`` and ``min_intensity`` default to MaterialTable's.  ``retro_deg`` becomes retro_cos = cos(retro_deg) here,
+        on the host.  The key stands alone: motion, noise and beam are refused beside it."""
+        cfg = self.config.get("materials")
+        if cfg is None:
+            return None
+        for other in ("motion", "noise", "beam"):
+            if self.config.get(other) is not None:
+                raise ValueError(f"the materials key cannot be combined with the {other} key")
+        unknown = set(cfg) - {"classes", "max_bounces", "min_intensity"}
+        if unknown:
+            raise ValueError(f"unknown entries under the materials key: {sorted(unknown)}")
+        from lidarcast.material import MaterialTable
+        kw = {k: cfg[k] for k in ("max_bounces", "min_intensity") if k in cfg}
+        return MaterialTable.from_classes(cfg.get("classes", {}), **kw)
+
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
         rank (one process per GPU, backend "nccl" = RCCL), or with an explicit ``process_group``, the waypoints are
@@ -369,7 +393,12 @@ class S3DISSimulator:
         # the same poses fetches them the first time a frame's labels are looked at (or at export) -- so that a caller who
         # never does is not made to wait for four of every sixteen bytes to cross PCIe.  raycast_engine.eager_labels: true
         # brings them with the points as before.
-        lazy_labels = batched and not bool(self.config.get("raycast_engine", {}).get("eager_labels", False))
+        # opt-in surface materials (config key ``materials: {classes: {window: {kind: glass, ...}, ...}, max_bounces?,
+        # min_intensity?}``): a ray that meets glass or a mirror goes on inside the kernel; frames then
+        # carry intensities, bounces and surface_points per point, and their labels come with the points.  Without the key
+        # nothing changes.
+        materials = self._material_table() if len(waypoints) > 0 else None
+        lazy_labels = batched and materials is None and not bool(self.config.get("raycast_engine", {}).get("eager_labels", False))
         want = ("point3",) + (() if lazy_labels else ("sem", "ins")) + \
             ("range_origin_stats" if device_stats else "range_origin",) + \
             (() if self.bug_compatible else (("incident_deg", "incident_stats") if device_stats else ("incident_deg",)))
@@ -414,7 +443,13 @@ class S3DISSimulator:
                 raise ValueError("the beam key is not available on a multi-rank process group")
             if not batched:
                 raise ValueError("the beam key needs a multi-line sensor with a direction table (not the dual-axis sensor)")
-        if beam is not None:
+        if materials is not None:
+            if dist is not None:
+                raise ValueError("the materials key is not available on a multi-rank process group")
+            if not batched:
+                raise ValueError("the materials key needs a multi-line sensor with a direction table (not the dual-axis sensor)")
+            fr = engine.scan_material_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, materials, want=want)
+        elif beam is not None:
             fr = engine.scan_echo_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, beam, want=want)
         elif noise is not None:
             fr = engine.scan_noisy_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, noise, want=want)
@@ -486,6 +521,9 @@ class S3DISSimulator:
             if "echo_weight" in fr:        # per point: its beam (table row), its place among the beam's echoes, the sub-rays behind it
                 for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
                     f.beam_index, f.echo_index, f.echo_weight = (fr[a][e - c:e] for a in ("beam_index", "echo_index", "echo_weight"))
+            if "bounces" in fr:            # per point: the return's strength, the panes and mirrors on its way, where it came from
+                for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
+                    f.intensities, f.bounces, f.surface_points = (fr[a][e - c:e] for a in ("intensity", "bounces", "surface_point3"))
         for i, wp in enumerate(waypoints if fr is None else ()):
             a, b = off[i], off[i + 1]
             keep = seg["t"][a:b] != np.inf
