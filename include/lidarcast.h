@@ -866,7 +866,9 @@ int lrc_instance_boxes_dev(lrc_ctx* ctx, const float* d_xyzl, uint64_t num_rows,
  *              3 give (0, 0, 1).  Otherwise Open3D's nine cumulants are summed in neighbour order and divided by the
  *              count, cov = E[x x^T] - E[x] E[x]^T, and the normal is the unit eigenvector of the smallest eigenvalue
  *              from the closed-form robust symmetric 3x3 solver (Eberly; Open3D's fast_normal_computation path); a
- *              zero covariance gives (0, 0, 1).  The sign is the solver's: no orientation is applied.
+ *              zero covariance gives (0, 0, 1).  An exactly diagonal covariance gives the axis of its smallest entry,
+ *              and among equal smallest entries z before x before y (diag(s, s, L) with s < L gives (1, 0, 0)).  The
+ *              sign is the solver's: no orientation is applied.
  * 1 <= nb_neighbors <= 32 and 1 <= max_nn <= 32 (the lists live in registers; the reference uses 20 and 30), finite
  * std_ratio > 0 and radius > 0, n < 2^31; a non-finite coordinate fails with LRC_ERR_INVALID_ARG.  cell_size <= 0
  * picks the grid spacing (about max(nb_neighbors, max_nn) rows per cell); no result depends on it.

@@ -235,6 +235,7 @@ __device__ V3 smallest_eigvec(const double (&c)[6]) {
     if (!(norm > 0.0)) {
         if (a[0] < a[3] && a[0] < a[5]) return {1.0, 0.0, 0.0};
         if (a[3] < a[0] && a[3] < a[5]) return {0.0, 1.0, 0.0};
+        if (a[0] < a[5]) return {1.0, 0.0, 0.0};          // a[0] == a[3]: the smallest twice, x of its plane
         return {0.0, 0.0, 1.0};
     }
     const double q = (a[0] + a[3] + a[5]) / 3.0;

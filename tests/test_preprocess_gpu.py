@@ -7,6 +7,8 @@ import pickle
 import numpy as np
 import pytest
 
+import neighbour_restate as nr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -91,6 +93,9 @@ def check_normals(normals, nn, pk, radius, max_nn, rows):
     assert (got[few] == [0.0, 0.0, 1.0]).all()
     if few.all():                                       # max_nn < 3
         return
+    # every row, ill-separated eigenvalues included: the normal's Rayleigh quotient is the smallest eigenvalue
+    excess, lam = nr.rayleigh_excess(got[~few], cov[~few])
+    assert (excess[lam[:, 2] > 0] <= nr.RAYLEIGH_BOUND).all(), np.nanmax(excess)
     w, v = np.linalg.eigh(cov[~few])
     ok = (w[:, 1] - w[:, 0]) >= 1e-3 * np.abs(w[:, 2])
     ok &= w[:, 2] > 0
