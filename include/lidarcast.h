@@ -644,6 +644,72 @@ int lrc_material_step(const lrc_material_model* model, const lrc_material* recor
                       const uint16_t* sem, const float* normal3, float* origin3, float* dir3, float* path, float* gain,
                       uint8_t* bounces, uint8_t* status, float* intensity, float* surface_point3);
 
+/* ---- moving objects: rigid movers traced per frame (opt-in) -----------------------------------------
+ * Every other scan is of a frozen scene.  Here people, doors and carts stand at a different pose in every frame: a mover
+ * occludes the room behind it, the room occludes the mover, and every return says which mover it came from.  The static scene
+ * is built once; a frame costs one cast per mover, not a rebuild.  The reference has nothing of the kind.
+ *   mover     a rigid triangle mesh with per-triangle sem / ins, modelled around its own origin and held as an ordinary
+ *             lrc_scene of the same context.  A mover SET is 1 <= M <= 255 such scenes (lrc_movers_create; the set does not
+ *             own them: they must outlive it).
+ *   pose      per scan pose p and mover m a MOVER POSE: 12 float32, the row-major 3 x 4 [R | c] from object to world;
+ *             mover_poses12 is shaped (P, M, 12).  A mover stands still during a frame.
+ *   ray (p, i)   (o, d) is the ray of lrc_scan_poses_dev, bit for bit.  All arithmetic is float32 with one rounding per
+ *             operation, nothing fused.
+ *             1 static    t_s and a triangle: exactly what lrc_cast_dev returns for (o, d) without centre or filter.  A miss:
+ *                         +inf.
+ *             2 frame     per mover e = o - c (three subtractions), o'_j = (R[0][j] * e_x + R[1][j] * e_y) + R[2][j] * e_z,
+ *                         d'_j the same expression on d, not normalised.  t_m and a triangle: what lrc_cast_dev returns for
+ *                         (o', d') on mover m's scene without centre or filter; the finite-ray contract applies to (o', d').
+ *             3 merge     both kinds of range are taken before any range filter.  The winner is the smallest of t_s, t_0,
+ *                         ..., t_(M-1), compared as float32; on an exact tie the static scene wins over any mover and the
+ *                         smaller m wins among movers.
+ *             4 record    the record lrc_scan_poses_dev would write for (o, d) had it hit the winner at range t: point3 =
+ *                         o + unit(d) * t as every record forms it; the range filter, min_range, incident_deg (both modes)
+ *                         and intensity use that point, d and the normal3 that is written.  prim, sem and ins are the
+ *                         winner's; prim is the row in the winner's OWN mesh.  For a mover normal3_j = (R[j][0] * n_x +
+ *                         R[j][1] * n_y) + R[j][2] * n_z of the mover record's normal, not renormalised.  mover (uint8)
+ *                         receives 0 for the static scene and m + 1 for a mover, and 0 where there is no return or the
+ *                         filter drops it.  A static hit that the range filter or min_range removes does not uncover a
+ *                         mover behind it.
+ *   culling   a ray is left out of a mover's cast only when it cannot meet a sphere around the mover's box, enlarged by a
+ *             margin far above float32 rounding (csrc/lrc_movers.h): a test the traversal's own root-box test also fails.
+ *             It never changes a byte; a ray left out writes no ray record and is not cast (the keep mask of the
+ *             explicit-ray launch).
+ * Properties (tests/test_movers_gpu.py): a mover that is a copy of the room at the identity pose gives the clean scan's
+ * bytes and mover == 0; the result does not depend on how the poses are split into calls.
+ * LRC_ERR_INVALID_ARG before any launch: M = 0 or M > 255 in lrc_movers_create, a mover scene of another context, the static
+ * scene used as one of its movers, d_out->tile_count != NULL (the merge writes no per-tile keep counts), a call while a
+ * range_noise option is set and, in lrc_scan_movers_compact, a mover pose with an entry that is not finite or with
+ * max |R^T R - I| > 2^-16 evaluated in float64.  lrc_scan_movers_dev cannot read device poses: its caller vouches for them.
+ * A NULL set is allowed in both scan calls: the bytes of lrc_scan_poses_dev and a zero mover column.  min_range and
+ * incident_mode of the STATIC scene apply to the merged record; options of the mover scenes are ignored.
+ * Lifetime: a set belongs to the context it was created on and must be destroyed BEFORE that context and before its scenes'
+ * last use; it holds the scan's scratch (one ray set, one keep column, two record sets: 98 bytes per ray whatever M is), so
+ * calls on one set must not overlap on different streams.
+ *   lrc_movers_create        `scenes`: num_movers scene handles (host array)
+ *   lrc_scan_movers_dev      device pointers; d_out and d_mover (nullable) hold P * N entries; everything is enqueued on
+ *                            `stream`, nothing is waited for
+ *   lrc_scan_movers_compact  host poses and mover poses, a resident direction table: compacted like lrc_scan_table_compact;
+ *                            mover_rows (uint8, `capacity` rows, nullable) receives the mover column of the kept rows,
+ *                            aligned with them (gathered on the device)
+ *   lrc_mover_rays           host, no GPU: step 2 for n rays and ONE mover pose, by the inline functions the kernels call
+ *   lrc_mover_merge          host, no GPU: step 3 and the mover's world normal for n rays of ONE frame.  In: (t, normal3) of
+ *                            the static cast, (M, n) ranges and (M, n, 3) normals of the mover casts (+inf or any value that
+ *                            is not < the winner's for a miss), (M, 12) poses.  Out: the winner's t, normal3 and mover id. */
+typedef struct lrc_movers lrc_movers;
+int lrc_movers_create(lrc_ctx* ctx, lrc_scene* const* scenes, uint32_t num_movers, lrc_movers** out_set);
+int lrc_movers_destroy(lrc_movers* set);
+int lrc_scan_movers_dev(lrc_scene* scene, lrc_movers* set /* nullable */, const double* d_poses16, uint64_t num_poses,
+                        const double* d_dirs3, uint64_t rays_per_pose, const float* d_mover_poses12, double max_range,
+                        const lrc_hits* d_out, uint8_t* d_mover /* nullable */, void* stream);
+int lrc_scan_movers_compact(lrc_scene* scene, lrc_movers* set /* nullable */, const double* poses16, uint64_t num_poses,
+                            const lrc_table* table, const float* mover_poses12, double max_range, const lrc_frames* out,
+                            uint8_t* mover_rows /* nullable */, uint64_t capacity, uint64_t* out_total);
+int lrc_mover_rays(const float* rays6, uint64_t num_rays, const float* pose12, float* out_rays6);
+int lrc_mover_merge(uint64_t num_rays, uint32_t num_movers, const float* t_static, const float* normal3_static,
+                    const float* t_movers, const float* normal3_movers, const float* poses12, float* out_t,
+                    float* out_normal3, uint8_t* out_mover);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

@@ -164,6 +164,9 @@ class S3DISSimScene:
         self._s3dis_cache = None      # the reference's cache slot (dict of the four annotated arrays)
         self._annotated = None        # (points f64 (M,3), colors (M,3) in 0..1, sem (M,), ins (M,))
         self._nn = None
+        # the movers key of the simulator: {period, objects, times (P,), states (P, M, 4): x, y, z, yaw,
+        # poses12 (P, M, 12)} of the run, None without the key
+        self.mover_tracks = None
 
     def append_frame(self, frame: S3DISSimFrame):
         self.frames.append(frame)
@@ -381,6 +384,43 @@ class S3DISSimScene:
         Path(output_dir).mkdir(parents=True, exist_ok=True)
         vis.generate_detection_annotations(bboxes, Path(output_dir) / "combined_pointcloud_with_label_detection_annotations.json")
         return bboxes
+
+    def export_mover_tracks(self, output_dir) -> Dict[str, Any]:
+        """Ground truth of the moving objects of a run under the movers key, written to ``output_dir``/<scene>_mover_tracks.json:
+        the period, the object table (mesh, semantic, instance, the mesh's own box) and, per frame and mover, the time, the
+        pose (x, y, z, yaw_deg and the row-major 3 x 4 object-to-world matrix), the oriented box (``box7``: world centre,
+        extents of the mesh's own AABB, heading = yaw) and ``num_points``, the frame's returns from that mover.  Returns the
+        dict."""
+        tr = self.mover_tracks
+        if tr is None:
+            raise ValueError("this scene was not simulated under the movers key")
+        objs = tr["objects"]
+        frames = []
+        for f, frame in enumerate(self.frames):
+            ids = getattr(frame, "mover_ids", None)
+            if ids is None:
+                raise ValueError(f"frame {f} carries no mover_ids")
+            counts = np.bincount(np.asarray(ids, dtype=np.int64), minlength=len(objs) + 1)
+            movers = []
+            for m, obj in enumerate(objs):
+                x, y, z, yaw = (float(v) for v in tr["states"][f][m])
+                lo, hi = np.asarray(obj["box_min"], np.float64), np.asarray(obj["box_max"], np.float64)
+                c, s = np.cos(yaw), np.sin(yaw)
+                mid = 0.5 * (lo + hi)
+                centre = np.array([c * mid[0] - s * mid[1] + x, s * mid[0] + c * mid[1] + y, mid[2] + z])
+                movers.append({"mover": m + 1, "instance": obj["instance"], "semantic": obj["semantic"],
+                               "pose": {"x": x, "y": y, "z": z, "yaw_deg": float(np.degrees(yaw)),
+                                        "matrix12": [float(v) for v in tr["poses12"][f][m]]},
+                               "box7": [float(v) for v in centre] + [float(v) for v in (hi - lo)] + [yaw],
+                               "num_points": int(counts[m + 1])})
+            frames.append({"frame": f, "time": float(tr["times"][f]), "static_points": int(counts[0]), "movers": movers})
+        summary = {"scene_name": self.scene_name, "period": float(tr["period"]), "num_frames": len(frames), "objects": objs,
+                   "frames": frames}
+        out = Path(output_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        with open(out / f"{self.scene_name}_mover_tracks.json", "w") as fh:
+            json.dump(summary, fh, indent=2)
+        return summary
 
     def _save_labeled_ply(self, output_path: Path, points: np.ndarray, colors: np.ndarray,
                           semantic_labels: np.ndarray, instance_labels: np.ndarray):

@@ -337,11 +337,14 @@ __device__ __forceinline__ double range_filter(const TraceParams& p, double s, b
 // come from the per-row plane table instead of the per-slot arrays -- same values.
 // HAVE_LABEL: the caller has slot_label[best_slot] already (trace_kernel issues the load together with the box clause's).
 // MAT: the intensity column receives the caller's value (the material chain's I, trace_kernel GEN = 7) in the place of |h.n|.
+// GIVEN: the hit was found elsewhere (mover_merge_kernel: the winner among the static scene and the movers): `best_slot` is
+// the triangle ROW to report, slot_label_in its label and n_in the normal to write and to use; no scene array is read.
 // Returns whether the ray is kept.
-template <bool FILTER_ALWAYS, bool BY_PRIM = false, bool HAVE_LABEL = false, bool MAT = false>
+template <bool FILTER_ALWAYS, bool BY_PRIM = false, bool HAVE_LABEL = false, bool MAT = false, bool GIVEN = false>
 __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, uint32_t tid, V3 o, V3 d, double cx,
                                            double cy, double cz, float tbest, uint32_t best_slot, uint32_t slot_label_in = 0u,
-                                           bool have_h = false, V3 h_in = V3{0.f, 0.f, 0.f}, float inten_in = 0.f) {
+                                           bool have_h = false, V3 h_in = V3{0.f, 0.f, 0.f}, float inten_in = 0.f,
+                                           V3 n_in = V3{0.f, 0.f, 0.f}) {
     constexpr int GEN = FILTER_ALWAYS ? 1 : 0;
     const bool lean = FILTER_ALWAYS && !BY_PRIM && p.lean.row != nullptr;    // a kernel argument: wave-uniform
     bool keep = best_slot != 0xFFFFFFFFu;
@@ -377,7 +380,10 @@ __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, u
             label = HAVE_LABEL ? slot_label_in : p.slot_label[best_slot];
         } else if (keep) {
             t_out = tbest;
-            if (BY_PRIM) {
+            if (GIVEN) {
+                prim = best_slot;
+                label = slot_label_in;
+            } else if (BY_PRIM) {
                 prim = best_slot;
                 label = __float_as_uint(p.prim_plane[(size_t)best_slot * 2].w);
             } else {
@@ -385,10 +391,14 @@ __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, u
                 label = HAVE_LABEL ? slot_label_in : p.slot_label[best_slot];
             }
             if (p.out.normal3 || p.out.intensity || (p.out.incident_deg && p.incident_mode == 1)) {
-                float4 c;
-                if (BY_PRIM) { const float4 g = p.prim_plane[(size_t)best_slot * 2 + 1]; c = make_float4(0.f, g.x, g.y, g.z); }
-                else c = p.tris[(size_t)best_slot * 3 + 2];
-                slot_normal(c, nx, ny, nz);
+                if (GIVEN) {
+                    nx = n_in.x; ny = n_in.y; nz = n_in.z;
+                } else {
+                    float4 c;
+                    if (BY_PRIM) { const float4 g = p.prim_plane[(size_t)best_slot * 2 + 1]; c = make_float4(0.f, g.x, g.y, g.z); }
+                    else c = p.tris[(size_t)best_slot * 3 + 2];
+                    slot_normal(c, nx, ny, nz);
+                }
             }
             if (p.out.incident_deg) {
                 if (p.incident_mode == 1) {   // opt-in: angle between the ray and the surface normal
@@ -431,6 +441,104 @@ __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, u
     if (p.out.incident_deg) p.out.incident_deg[gid] = inc;
     if (p.out.intensity) p.out.intensity[gid] = inten;
     return keep;
+}
+
+// ---- moving objects (lrc_scan_movers_*; the arithmetic is lrc_movers.h's, the orchestration movers_scan_dev's) ---------------
+// Pose of ray gid and, with `uniform` (rays_per_pose % 64 == 0: a wave lies in one pose), the same value as a scalar, so that what
+// is read per pose comes through the scalar cache.
+__device__ __forceinline__ uint32_t mover_pose_of(uint64_t gid, uint64_t rays_per_pose, int uniform) {
+    uint32_t pose = (uint32_t)(gid / rays_per_pose);
+    if (uniform) pose = (uint32_t)__builtin_amdgcn_readfirstlane((int)pose);
+    return pose;
+}
+__device__ __forceinline__ void mover_pose_load(const float* poses12, uint32_t pose, uint32_t M, uint32_t m, int uniform, float* out12) {
+    const float* mp = poses12 + ((size_t)pose * M + m) * 12;
+    if (uniform) {
+        cfloat* c = (cfloat*)mp;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) out12[k] = c[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) out12[k] = mp[k];
+    }
+}
+
+// The ray kernel: one thread per (pose, i) forms gen_ray's bits; the static pass (q.poses12 == NULL) stores them, a mover's pass
+// stores the ray in the mover's frame and the keep byte of the explicit-ray launch (0: left out by lrcmov::culled, no ray stored).
+__global__ __launch_bounds__(kBlock) void mover_rays_kernel(const double* __restrict__ poses16, const double* __restrict__ dirs3,
+                                                            uint64_t rays_per_pose, uint64_t total, const lrcmov::RayPass q,
+                                                            int uniform, float* __restrict__ rays6, uint8_t* __restrict__ keep) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= total) return;
+    const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
+    V3 o, d;
+    double cx, cy, cz;
+    gen_ray(poses16, dirs3, pose, gid - (uint64_t)pose * rays_per_pose, o, d, cx, cy, cz);
+    lrcmov::Vec ro{o.x, o.y, o.z}, rd{d.x, d.y, d.z};
+    if (q.poses12 != nullptr) {
+        float m12[12];
+        mover_pose_load(q.poses12, pose, q.M, q.m, uniform, m12);
+        lrcmov::to_object(m12, lrcmov::Vec{o.x, o.y, o.z}, lrcmov::Vec{d.x, d.y, d.z}, ro, rd);
+        const bool out = lrcmov::culled(q.sphere, ro, rd);
+        keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
+        if (out) return;
+    }
+    float2* r = (float2*)(rays6 + gid * 6);      // 24-byte records: 8-byte aligned
+    r[0] = make_float2(ro.x, ro.y);
+    r[1] = make_float2(ro.z, rd.x);
+    r[2] = make_float2(rd.y, rd.z);
+}
+
+// The merge kernel's view of one mover's pass: the running winner (the static cast's record set to begin with), this mover's
+// cast, and -- in the last pass -- the caller's record set (p.out) and mover column.
+struct MoverMerge {
+    const float* poses12;      // (P, M, 12)
+    uint32_t M, m;
+    int uniform, last;
+    float* w_t; uint32_t* w_prim; float* w_n3; uint16_t* w_sem; uint16_t* w_ins; uint8_t* w_who;
+    const float* m_t; const uint32_t* m_prim; const float* m_n3; const uint16_t* m_sem; const uint16_t* m_ins;
+    uint8_t* d_mover;          // nullable
+};
+
+// One thread per (pose, i): the running winner against mover q.m (lrcmov::takes), the mover's normal turned into the world.  Every
+// pass but the last stores the winner; the last forms gen_ray's bits again and writes the record lrc_scan_poses_dev would write
+// had the ray hit the winner (write_back, GIVEN), filter included, and the mover column.
+__global__ __launch_bounds__(kBlock) void mover_merge_kernel(const TraceParams p, const MoverMerge q) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= p.total) return;
+    float t = q.w_t[gid];
+    uint32_t prim = q.w_prim[gid];
+    uint32_t label = (uint32_t)q.w_sem[gid] | ((uint32_t)q.w_ins[gid] << 16);
+    V3 n{q.w_n3[gid * 3], q.w_n3[gid * 3 + 1], q.w_n3[gid * 3 + 2]};
+    uint32_t who = q.w_who[gid];
+    const uint32_t pose = mover_pose_of(gid, p.rays_per_pose, q.uniform);
+    const float tm = q.m_t[gid];
+    if (lrcmov::takes(tm, t)) {
+        float m12[12];
+        mover_pose_load(q.poses12, pose, q.M, q.m, q.uniform, m12);
+        const lrcmov::Vec w = lrcmov::to_world(m12, lrcmov::Vec{q.m_n3[gid * 3], q.m_n3[gid * 3 + 1], q.m_n3[gid * 3 + 2]});
+        t = tm;
+        prim = q.m_prim[gid];
+        label = (uint32_t)q.m_sem[gid] | ((uint32_t)q.m_ins[gid] << 16);
+        n = V3{w.x, w.y, w.z};
+        who = q.m + 1u;
+    }
+    if (!q.last) {
+        q.w_t[gid] = t;
+        q.w_prim[gid] = prim;
+        q.w_n3[gid * 3] = n.x; q.w_n3[gid * 3 + 1] = n.y; q.w_n3[gid * 3 + 2] = n.z;
+        q.w_sem[gid] = (uint16_t)(label & 0xFFFFu);
+        q.w_ins[gid] = (uint16_t)(label >> 16);
+        q.w_who[gid] = (uint8_t)who;
+        return;
+    }
+    V3 o, d;
+    double cx, cy, cz;
+    gen_ray(p.poses16, p.dirs3, pose, gid - (uint64_t)pose * p.rays_per_pose, o, d, cx, cy, cz);
+    const bool hit = t < __builtin_inff();
+    const bool kept = write_back<true, false, true, false, true>(p, gid, threadIdx.x, o, d, cx, cy, cz, t, hit ? prim : 0xFFFFFFFFu,
+                                                                 label, false, V3{0.f, 0.f, 0.f}, 0.f, n);
+    if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
 }
 
 constexpr int kStatsWords = 5;   // node steps, triangle tests, wave-uniform node steps, dead node steps, pad-clause rejections
@@ -4257,6 +4365,156 @@ int material_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const
     if (rc == LRC_OK && gather && total) {
         const GatherColumn cols[3] = {{st.rec.intensity, intensity_rows, 4, 1}, {mp.bounces, bounces_rows, 1, 1}, {mp.surface3, surface_rows, 4, 3}};
         rc = gather_rows_by_index("lrc_scan_materials_compact", out->counts, P, st.io.out_index, N, total, cols, 3);
+    }
+    return guard.done(rc);
+}
+
+// ---- moving objects: lrc_scan_movers_* behind their checks (lrc_movers.hip; declared in lrc_internal.h) -----------------------
+namespace {
+// The explicit-ray launch as lrc_cast_dev makes it with no centre and no filter, whatever options the scene carries: the
+// ranges the merge compares are taken before any filter.  d_keep: nullable, 0 = the ray is not cast (a miss).
+int cast_plain(lrc_scene* sc, const float* d_rays6, const uint8_t* d_keep, uint64_t n, const lrc_hits& out, hipStream_t st) {
+    TraceParams p{};
+    p.rays6 = d_rays6;
+    p.keep_mask = d_keep;
+    scan_fields(p, n, n, (double)__builtin_inff(), &out, false);
+    const lrc_scan_options saved = sc->opts;
+    sc->opts = lrc_scan_options{};
+    const int rc = launch_trace(sc, p, 0, st);
+    sc->opts = saved;
+    return rc;
+}
+}  // namespace
+
+// All on `st`, nothing waited for.  A NULL set: the launch of lrc_scan_poses_dev and a zero mover column.  Otherwise
+//   the static pass    mover_rays_kernel (the world rays) and the explicit-ray launch on the scene, into the winner's columns
+//   per mover m        mover_rays_kernel (object-frame rays + keep bytes), the explicit-ray launch on the mover's scene, and
+//                      mover_merge_kernel, whose last pass writes the caller's records
+// in the set's scratch, which holds one ray set, one keep column and two record sets (winner, mover) whatever M is.
+int movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
+                    const float* d_mover_poses12, double max_range, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st) {
+    const uint64_t n = P * N;
+    if (!n) return LRC_OK;
+    if (!set) {
+        TraceParams p{};
+        p.poses16 = d_poses16;
+        p.dirs3 = d_dirs3;
+        scan_fields(p, N, n, max_range, d_out);
+        const int rc = launch_trace(s, p, 1, st);
+        if (rc) return rc;
+        if (d_mover) LRC_HIP(hipMemsetAsync(d_mover, 0, n, st));
+        return LRC_OK;
+    }
+    if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers: too many poses or rays for one call");
+    // scratch, 256-byte aligned columns: rays6 | keep | winner (t, prim, normal3, sem, ins, who) | mover (t, prim, normal3, sem, ins)
+    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
+    const uint64_t sizes[13] = {n * 24, n, n * 4, n * 4, n * 12, n * 2, n * 2, n, n * 4, n * 4, n * 12, n * 2, n * 2};
+    uint64_t off[14] = {0};
+    for (int k = 0; k < 13; ++k) off[k + 1] = off[k] + al(sizes[k]);
+    if (set->scratch_cap < off[13]) {
+        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
+        if (set->scratch) { (void)hipFree(set->scratch); set->scratch = nullptr; set->scratch_cap = 0; }
+        LRC_HIP(hipMalloc(&set->scratch, off[13] + off[13] / 8));
+        set->scratch_cap = off[13] + off[13] / 8;
+    }
+    uint8_t* const b = (uint8_t*)set->scratch;
+    float* const rays6 = (float*)(b + off[0]);
+    uint8_t* const keep = b + off[1];
+    lrc_hits w{}, mv{};
+    w.t = (float*)(b + off[2]); w.prim = (uint32_t*)(b + off[3]); w.normal3 = (float*)(b + off[4]);
+    w.sem = (uint16_t*)(b + off[5]); w.ins = (uint16_t*)(b + off[6]);
+    uint8_t* const who = b + off[7];
+    mv.t = (float*)(b + off[8]); mv.prim = (uint32_t*)(b + off[9]); mv.normal3 = (float*)(b + off[10]);
+    mv.sem = (uint16_t*)(b + off[11]); mv.ins = (uint16_t*)(b + off[12]);
+    const dim3 grid((uint32_t)blocks_of(n, kBlock));
+    const int uniform = N % 64 == 0;
+    const uint32_t M = (uint32_t)set->scenes.size();
+    int rc;
+    lrcmov::RayPass rp{};
+    hipLaunchKernelGGL(mover_rays_kernel, grid, dim3(kBlock), 0, st, d_poses16, d_dirs3, N, n, rp, uniform, rays6, keep);
+    LRC_HIP(hipGetLastError());
+    if ((rc = cast_plain(s, rays6, nullptr, n, w, st))) return rc;
+    LRC_HIP(hipMemsetAsync(who, 0, n, st));
+    TraceParams p{};       // what write_back reads: the scan's inputs, the filter, the scene's options, the caller's records
+    p.poses16 = d_poses16;
+    p.dirs3 = d_dirs3;
+    scan_fields(p, N, n, max_range, d_out);
+    p.min_range = s->opts.min_range;
+    p.incident_mode = s->opts.incident_mode;
+    for (uint32_t m = 0; m < M; ++m) {
+        lrc_scene* const ms = set->scenes[m];
+        rp.poses12 = d_mover_poses12;
+        rp.M = M;
+        rp.m = m;
+        rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
+        hipLaunchKernelGGL(mover_rays_kernel, grid, dim3(kBlock), 0, st, d_poses16, d_dirs3, N, n, rp, uniform, rays6, keep);
+        LRC_HIP(hipGetLastError());
+        if ((rc = cast_plain(ms, rays6, keep, n, mv, st))) return rc;
+        MoverMerge q{};
+        q.poses12 = d_mover_poses12; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
+        q.w_t = w.t; q.w_prim = w.prim; q.w_n3 = w.normal3; q.w_sem = w.sem; q.w_ins = w.ins; q.w_who = who;
+        q.m_t = mv.t; q.m_prim = mv.prim; q.m_n3 = mv.normal3; q.m_sem = mv.sem; q.m_ins = mv.ins;
+        q.d_mover = d_mover;
+        hipLaunchKernelGGL(mover_merge_kernel, grid, dim3(kBlock), 0, st, p, q);
+        LRC_HIP(hipGetLastError());
+    }
+    return LRC_OK;
+}
+
+// Host poses, a resident direction table: the records at the fixed stride by movers_scan_dev on the context's compute stream,
+// compacted by lrc_compact_dev (which counts itself: the merge kernel writes no per-tile keep counts); the counts come home
+// first, then exactly the kept rows.  The mover column stays at the fixed stride and is gathered for the kept rows by the
+// compacted index column (gather_rows_by_index above).
+int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                        const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
+                        uint64_t* out_total) {
+    SyncUnlessOk guard;
+    lrc_ctx* const ctx = s->ctx;
+    const uint64_t N = table->n, n = P * N;
+    int rc;
+    if ((rc = ensure_streams(ctx))) return rc;
+    const hipStream_t cs = ctx->s_compute;
+    struct Drain {
+        hipStream_t st;
+        ~Drain() { (void)hipStreamSynchronize(st); }
+    } drain{cs};
+    const double* d_poses = nullptr;
+    const float* d_mp = nullptr;
+    if ((rc = stage_input(ctx, kPoolPoses, poses16, P * 16, &d_poses, &cs))) return rc;
+    if (set && (rc = stage_input(ctx, kPoolNoise, mover_poses12, P * set->scenes.size() * 12, &d_mp, &cs))) return rc;
+    FrameStage st;
+    if ((rc = st.alloc(ctx, *out, P, n))) return rc;
+    st.rec.tile_count = nullptr;
+    st.io.tile_count = nullptr;
+    if (mover_rows && !st.io.out_index) {       // the gather reads the index column whether or not the caller asked for it
+        if ((rc = st.oidx.get(ctx, kPoolOutIdx, n * 4))) return rc;
+        st.io.out_index = (uint32_t*)st.oidx.p;
+    }
+    DevBuf mbuf;
+    if (mover_rows && (rc = mbuf.get(ctx, kPoolKeep, n))) return rc;
+    if (ctx->h_counts_cap < P) {
+        if (ctx->h_counts) { (void)hipHostFree(ctx->h_counts); ctx->h_counts = nullptr; ctx->h_counts_cap = 0; }
+        LRC_HIP(hipHostMalloc((void**)&ctx->h_counts, (P + P / 4 + 64) * 8 * 5, hipHostMallocDefault));
+        ctx->h_counts_cap = P + P / 4 + 64;
+    }
+    if ((rc = movers_scan_dev(s, set, d_poses, P, table->d_dirs3, N, d_mp, max_range, &st.rec, (uint8_t*)mbuf.p, cs))) return rc;
+    if ((rc = lrc_compact_dev(ctx, P, N, &st.io, cs))) return rc;
+    LRC_HIP(hipMemcpyAsync(ctx->h_counts, st.io.counts, P * 8, hipMemcpyDeviceToHost, cs));
+    if (st.d_stats && (rc = enqueue_frame_stats(ctx, st, out, P, 0, P, 0, cs))) return rc;
+    LRC_HIP(hipStreamSynchronize(cs));
+    uint64_t K = 0;
+    for (uint64_t k = 0; k < P; ++k) { out->counts[k] = ctx->h_counts[k]; K += ctx->h_counts[k]; }
+    if (out_total) *out_total = K;
+    if (K > capacity)
+        return guard.done(fail(LRC_ERR_INVALID_ARG, "frame buffers too small: capacity " + std::to_string(capacity) +
+                                                        " rows, the scan kept " + std::to_string(K)));
+    if (K && (rc = copy_frame_rows(*out, st.io, 0, 0, K, cs))) return rc;
+    LRC_HIP(hipStreamSynchronize(cs));
+    publish_frame_stats(ctx, out, P);
+    if (mover_rows && K) {
+        const GatherColumn col{mbuf.p, mover_rows, 1, 1};
+        rc = gather_rows_by_index("lrc_scan_movers_compact", out->counts, P, st.io.out_index, N, K, &col, 1);
     }
     return guard.done(rc);
 }

@@ -8,12 +8,14 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/lidarcast.h"
 #include "lrc_bvh_device.h"
 #include "lrc_noise.h"
 #include "lrc_echo.h"
 #include "lrc_material.h"
+#include "lrc_movers.h"
 
 // sets lrc_last_error() (lidarcast.hip).  Exported: lrc_nprandom.cpp, built without HIP headers, reports through it.
 extern "C" int lrc_internal_fail(int code, const char* msg);
@@ -145,6 +147,13 @@ struct lrc_scene {
     uint64_t launches = 0, rays = 0;
 };
 
+struct lrc_movers {           // a mover set (lrc_movers_create): the caller's scenes, not owned, and the scan's scratch
+    lrc_ctx* ctx = nullptr;
+    std::vector<lrc_scene*> scenes;
+    void* scratch = nullptr;      // movers_scan_dev: grown on demand, one ray set and two record sets whatever M is
+    uint64_t scratch_cap = 0;
+};
+
 // device buffer of a host-pointer entry point: its own allocation, or a slot of the context's staging pool
 struct DevBuf {
     void* p = nullptr;
@@ -199,5 +208,15 @@ int material_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const d
 int material_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc_table* table, lrcmat::Params mp,
                           double max_range, const lrc_frames* out, float* intensity_rows, uint8_t* bounces_rows, float* surface_rows,
                           uint64_t capacity, uint64_t* out_total);
+
+// moving objects.  lrc_movers.hip checks the arguments of lrc_scan_movers_* and owns the handle and the host functions;
+// lidarcast.hip, which owns the trace launch, write_back and the frame path, holds the kernels and enqueues the passes
+// (movers_scan_dev: everything on `st`, no host synchronisation; movers_scan_compact: host poses, the mover column gathered for
+// the kept rows by the compacted index column).  set == NULL: the scan of lrc_scan_poses_dev and a zero mover column.
+int movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
+                    const float* d_mover_poses12, double max_range, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st);
+int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                        const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
+                        uint64_t* out_total);
 
 #pragma GCC visibility pop

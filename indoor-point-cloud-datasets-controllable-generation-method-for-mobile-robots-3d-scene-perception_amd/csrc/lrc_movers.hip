@@ -1,0 +1,147 @@
+// lrc_movers.hip -- host side of the moving objects (lrc_movers.h): the mover set, the checks of lrc_scan_movers_dev /
+// lrc_scan_movers_compact (the kernels, the launches and the frame path are lidarcast.hip's: movers_scan_dev,
+// movers_scan_compact) and the two host functions lrc_mover_rays and lrc_mover_merge, which run the inline functions the
+// kernels call on arrays.
+#include <cmath>
+
+#include "lrc_internal.h"
+#include "lrc_movers.h"
+
+namespace {
+
+// the checks lrc_scan_movers_dev and lrc_scan_movers_compact share; `set` may be NULL
+int check_call(const char* who, const lrc_scene* s, const lrc_movers* set, const void* out) {
+    auto bad = [&](const char* t) { return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": " + t); };
+    if (!s || !out) return bad("NULL scene or output");
+    if (set) {
+        if (set->ctx != s->ctx) return bad("movers and scene belong to different contexts");
+        for (const lrc_scene* m : set->scenes)
+            if (m == s) return bad("the static scene is one of its own movers");
+    }
+    if (s->opts.range_noise) return bad("a range_noise option is set");
+    return LRC_OK;
+}
+
+// host-pose entry point: every entry finite, max |R^T R - I| <= 2^-16 in float64
+int check_poses12(const char* who, const float* m, uint64_t count) {
+    for (uint64_t k = 0; k < count; ++k) {
+        const float* q = m + k * 12;
+        for (int e = 0; e < 12; ++e)
+            if (!std::isfinite(q[e]))
+                return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover pose " + std::to_string(k) + " has an entry that is not finite");
+        double worst = 0.0;
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) {
+                double dot = 0.0;
+                for (int r = 0; r < 3; ++r) dot += (double)q[4 * r + a] * (double)q[4 * r + b];
+                worst = std::fmax(worst, std::fabs(dot - (a == b ? 1.0 : 0.0)));
+            }
+        if (worst > lrcmov::kOrthoTol)
+            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover pose " + std::to_string(k) + " is no rotation: max |R^T R - I| = " +
+                                                 std::to_string(worst) + " > 2^-16");
+    }
+    return LRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lrc_movers_create(lrc_ctx* ctx, lrc_scene* const* scenes, uint32_t num_movers, lrc_movers** out_set) {
+    if (out_set) *out_set = nullptr;
+    // what needs no context is checked first
+    if (num_movers < 1 || num_movers > lrcmov::kMaxMovers)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_movers_create: the number of movers must lie in [1, 255]");
+    if (!ctx || !out_set) return fail(LRC_ERR_INVALID_ARG, "lrc_movers_create: NULL context or output");
+    if (!scenes) return fail(LRC_ERR_INVALID_ARG, "lrc_movers_create: scenes is NULL");
+    for (uint32_t m = 0; m < num_movers; ++m) {
+        if (!scenes[m]) return fail(LRC_ERR_INVALID_ARG, "lrc_movers_create: mover " + std::to_string(m) + " is NULL");
+        if (scenes[m]->ctx != ctx)
+            return fail(LRC_ERR_INVALID_ARG, "lrc_movers_create: mover " + std::to_string(m) + " belongs to another context");
+    }
+    lrc_movers* set = new lrc_movers;
+    set->ctx = ctx;
+    set->scenes.assign(scenes, scenes + num_movers);
+    *out_set = set;
+    return LRC_OK;
+}
+
+int lrc_movers_destroy(lrc_movers* set) {
+    if (!set) return LRC_OK;
+    if (set->scratch) {
+        (void)hipSetDevice(set->ctx->device);
+        (void)hipFree(set->scratch);
+    }
+    delete set;
+    return LRC_OK;
+}
+
+int lrc_scan_movers_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
+                        const float* d_mover_poses12, double max_range, const lrc_hits* d_out, uint8_t* d_mover, void* stream) {
+    int rc = check_call("lrc_scan_movers_dev", s, set, d_out);
+    if (rc) return rc;
+    if (d_out->tile_count)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_dev: tile_count is not written by this scan (lrc_compact_dev counts itself)");
+    if (P && N && (!d_poses16 || !d_dirs3)) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_dev: poses16 or dirs3 is NULL");
+    if (P && N && set && !d_mover_poses12) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_dev: mover_poses12 is NULL");
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    return movers_scan_dev(s, set, d_poses16, P, d_dirs3, N, d_mover_poses12, max_range, d_out, d_mover, (hipStream_t)stream);
+}
+
+int lrc_scan_movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                            const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows,
+                            uint64_t capacity, uint64_t* out_total) {
+    if (out_total) *out_total = 0;
+    int rc = check_call("lrc_scan_movers_compact", s, set, out);
+    if (rc) return rc;
+    if (!table) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: table is NULL");
+    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: table and scene belong to different contexts");
+    if (!(P * table->n)) return LRC_OK;
+    if (!poses16 || !out->counts) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: poses16 or counts is NULL");
+    if (table->n > 0xFFFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: rays_per_pose must stay below 2^32 (the index column)");
+    if (set) {
+        if (!mover_poses12) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: mover_poses12 is NULL");
+        if ((rc = check_poses12("lrc_scan_movers_compact", mover_poses12, P * set->scenes.size()))) return rc;
+    }
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    return movers_scan_compact(s, set, poses16, P, table, mover_poses12, max_range, out, mover_rows, capacity, out_total);
+}
+
+int lrc_mover_rays(const float* rays6, uint64_t n, const float* pose12, float* out_rays6) {
+    if (!pose12 || (n && (!rays6 || !out_rays6))) return fail(LRC_ERR_INVALID_ARG, "lrc_mover_rays: NULL argument");
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* r = rays6 + i * 6;
+        lrcmov::Vec oo, od;
+        lrcmov::to_object(pose12, lrcmov::Vec{r[0], r[1], r[2]}, lrcmov::Vec{r[3], r[4], r[5]}, oo, od);
+        float* w = out_rays6 + i * 6;
+        w[0] = oo.x; w[1] = oo.y; w[2] = oo.z; w[3] = od.x; w[4] = od.y; w[5] = od.z;
+    }
+    return LRC_OK;
+}
+
+int lrc_mover_merge(uint64_t n, uint32_t M, const float* t_static, const float* normal3_static, const float* t_movers,
+                    const float* normal3_movers, const float* poses12, float* out_t, float* out_normal3, uint8_t* out_mover) {
+    if (M > lrcmov::kMaxMovers) return fail(LRC_ERR_INVALID_ARG, "lrc_mover_merge: the number of movers must not exceed 255");
+    if (n && (!t_static || !normal3_static || !out_t || !out_normal3 || !out_mover || (M && (!t_movers || !normal3_movers || !poses12))))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_mover_merge: NULL argument");
+    for (uint64_t i = 0; i < n; ++i) {
+        float t = t_static[i];
+        lrcmov::Vec nn{normal3_static[i * 3], normal3_static[i * 3 + 1], normal3_static[i * 3 + 2]};
+        uint8_t who = 0;
+        for (uint32_t m = 0; m < M; ++m) {
+            const float tm = t_movers[(uint64_t)m * n + i];
+            if (!lrcmov::takes(tm, t)) continue;
+            const float* q = normal3_movers + ((uint64_t)m * n + i) * 3;
+            nn = lrcmov::to_world(poses12 + (uint64_t)m * 12, lrcmov::Vec{q[0], q[1], q[2]});
+            t = tm;
+            who = (uint8_t)(m + 1u);
+        }
+        out_t[i] = t;
+        out_normal3[i * 3] = nn.x; out_normal3[i * 3 + 1] = nn.y; out_normal3[i * 3 + 2] = nn.z;
+        out_mover[i] = who;
+    }
+    return LRC_OK;
+}
+
+}  // extern "C"

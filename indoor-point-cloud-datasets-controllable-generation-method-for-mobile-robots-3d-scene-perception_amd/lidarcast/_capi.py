@@ -39,6 +39,8 @@ SYMBOLS = (
     "lrc_scan_echoes_dev", "lrc_scan_echoes_compact", "lrc_echo_reduce",
     "lrc_material_table_create", "lrc_material_table_destroy", "lrc_scan_materials_dev", "lrc_scan_materials_compact",
     "lrc_material_step",
+    "lrc_movers_create", "lrc_movers_destroy", "lrc_scan_movers_dev", "lrc_scan_movers_compact", "lrc_mover_rays",
+    "lrc_mover_merge",
     "lrc_compact", "lrc_compact_dev", "lrc_cloud_from_ranges_dev", "lrc_cloud_from_prims_dev",
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
@@ -281,6 +283,12 @@ def load():
         "lrc_scan_materials_dev": [vp, vp, u64, vp, u64, vp, dbl, C.POINTER(LrcHits), vp, vp, vp],
         "lrc_scan_materials_compact": [vp, vp, u64, vp, vp, dbl, C.POINTER(LrcFrames), vp, vp, vp, u64, C.POINTER(u64)],
         "lrc_material_step": [C.POINTER(LrcMaterialModel), vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrc_movers_create": [vp, vp, C.c_uint32, C.POINTER(vp)],
+        "lrc_movers_destroy": [vp],
+        "lrc_scan_movers_dev": [vp, vp, vp, u64, vp, u64, vp, dbl, C.POINTER(LrcHits), vp, vp],
+        "lrc_scan_movers_compact": [vp, vp, vp, u64, vp, vp, dbl, C.POINTER(LrcFrames), vp, u64, C.POINTER(u64)],
+        "lrc_mover_rays": [vp, u64, vp, vp],
+        "lrc_mover_merge": [u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
         "lrc_occ_create": [vp, vp, u64, C.POINTER(vp)],
         "lrc_occ_destroy": [vp],
         "lrc_occ_query": [vp, vp, u64, dbl, vp],

@@ -766,6 +766,41 @@ class Scene:
             if own is not None:
                 own.close()
 
+    def scan_movers_compact(self, poses, dirs, max_range, movers, mover_poses, want=("point3", "sem", "ins"), capacity=None):
+        """Pose-batched scan with moving objects straight to frames (lrc_scan_movers_compact): ``movers`` a
+        ``lidarcast.movers.MoverSet`` or None, ``mover_poses`` (P, M, 12) float32 object-to-world poses (``MoverTrack.poses12``),
+        ``dirs`` a DirectionTable or an (N, 3) table.  The return value of ``scan_poses_compact`` plus ``mover``, one uint8 per
+        kept row: 0 for the static scene, m + 1 for mover m."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
+        own = None
+        if isinstance(dirs, DirectionTable):
+            if not dirs._h:
+                raise ValueError("direction table handle is closed")
+            if dirs.ctx is not self.ctx:
+                raise ValueError("direction table belongs to another context (device)")
+            table = dirs
+        else:
+            table = own = DirectionTable(self.ctx, dirs)
+        try:
+            P, N = poses.shape[0], table.n
+            handle, mp = None, None
+            if movers is not None:
+                handle = movers.handle(self.ctx)
+                mp = np.ascontiguousarray(mover_poses, dtype=np.float32)
+                if mp.shape != (P, len(movers), 12):
+                    raise ValueError(f"mover_poses must be (P, M, 12) = ({P}, {len(movers)}, 12), got {mp.shape}")
+            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
+            rows = np.zeros(max(cap, 1), dtype=np.uint8)
+            total = C.c_uint64(0)
+            check(self._lib.lrc_scan_movers_compact(self._h, handle, _ptr(poses), P, table._h, _ptr(mp), float(max_range),
+                                                    C.byref(fr), _ptr(rows), cap, C.byref(total)), "lrc_scan_movers_compact")
+            out = self._frames_end(counts, bufs, total.value)
+            out["mover"] = rows[:total.value]
+            return out
+        finally:
+            if own is not None:
+                own.close()
+
     def scan_angles_compact(self, poses, angles, keep, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Dual-axis sensor, rays generated in the kernel from host-drawn (phi, theta) (lrc_scan_angles_compact).
         angles: (P, N, 2) float64; keep: (P, N) bool / uint8 or None."""
@@ -901,6 +936,37 @@ class Scene:
                                                None if bounces_t is None else C.c_void_p(bounces_t.data_ptr()),
                                                None if surface_t is None else C.c_void_p(surface_t.data_ptr()),
                                                C.c_void_p(int(stream))), "lrc_scan_materials_dev")
+
+    def scan_movers_dev(self, poses_t, dirs_t, hits, max_range, movers, mover_poses_t, mover_t=None, stream=0):
+        """Pose-batched scan with moving objects on device tensors (lrc_scan_movers_dev): poses_t (P, 16) float64, dirs_t
+        (N, 3) float64, ``movers`` a ``lidarcast.movers.MoverSet`` or None, ``mover_poses_t`` (P, M, 12) float32 (the caller
+        vouches for them), ``mover_t`` an optional (P * N) uint8 tensor: 0 for the static scene, m + 1 for mover m.  ``hits``
+        holds P * N records and no tile_count."""
+        P, N = poses_t.shape[0], dirs_t.shape[0]
+        if hits.n != P * N:
+            raise ValueError("hits must hold P * N records")
+        import torch
+        handle = None
+        if movers is not None:
+            handle = movers.handle(self.ctx)
+            if mover_poses_t is None or mover_poses_t.numel() != P * len(movers) * 12:
+                raise ValueError("mover_poses_t must be (P, M, 12)")
+        for name, t, dt in (("mover_poses_t", mover_poses_t, torch.float32), ("mover_t", mover_t, torch.uint8)):
+            if t is None:
+                continue
+            if t.dtype != dt:
+                raise ValueError(f"{name} must be {dt}")
+            if t.device != poses_t.device or not t.is_cuda:
+                raise ValueError(f"{name} must lie on the device of the poses")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        if mover_t is not None and mover_t.numel() != P * N:
+            raise ValueError("mover_t must hold P * N entries")
+        check(self._lib.lrc_scan_movers_dev(self._h, handle, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
+                                            None if mover_poses_t is None else C.c_void_p(mover_poses_t.data_ptr()),
+                                            float(max_range), C.byref(hits.struct),
+                                            None if mover_t is None else C.c_void_p(mover_t.data_ptr()),
+                                            C.c_void_p(int(stream))), "lrc_scan_movers_dev")
 
     def scan_sweeps_dev(self, motion_t, dirs_t, fire_t, hits, max_range, stream=0):
         """Moving-sensor sweeps on device tensors (lrc_scan_sweeps_dev): motion_t (P, 24) float64, dirs_t (N, 3) float64,

@@ -203,6 +203,34 @@ def unit_cube(lo=-1.0, hi=1.0):
     return TriangleMesh(vertices=v, triangles=np.array(f, dtype=np.int32))
 
 
+def make_pedestrian(height=1.7, radius=0.25, segments=16, rings=8, semantic=13, instance=1):
+    """A standing person as a closed prism: ``segments`` sides, ``rings`` bands over the height, a fan at each end --
+    2 * segments * rings + 2 * segments triangles (288 by default), wound outward.  Feet at z = 0, standing on its own origin:
+    a mover mesh (lidarcast.movers).  Every triangle carries ``semantic`` (default 13: one past the S3DIS class list) and ``instance``."""
+    segments, rings = int(segments), int(rings)
+    if segments < 3 or rings < 1:
+        raise ValueError("a pedestrian needs at least 3 segments and 1 ring")
+    ang = 2.0 * np.pi * np.arange(segments) / segments
+    z = np.linspace(0.0, float(height), rings + 1)
+    ring = np.stack([radius * np.cos(ang), radius * np.sin(ang)], 1)
+    v = np.concatenate([np.concatenate([ring, np.full((segments, 1), zk)], 1) for zk in z] +
+                       [np.array([[0.0, 0.0, 0.0], [0.0, 0.0, float(height)]])], 0)
+    bottom, top = segments * (rings + 1), segments * (rings + 1) + 1
+    t = []
+    for k in range(rings):
+        for j in range(segments):
+            a, b = k * segments + j, k * segments + (j + 1) % segments
+            c, d = a + segments, b + segments
+            t += [(a, b, d), (a, d, c)]
+    for j in range(segments):
+        a, b = j, (j + 1) % segments
+        t.append((bottom, b, a))
+        t.append((top, rings * segments + a, rings * segments + b))
+    t = np.array(t, dtype=np.int32)
+    return TriangleMesh(vertices=v.astype(np.float64), triangles=t, triangle_sem=np.full(len(t), semantic, np.uint16),
+                        triangle_ins=np.full(len(t), instance, np.uint16))
+
+
 def quad(z=2.0, half=1.0):
     """Two triangles forming the square |x|,|y| <= half in the plane z."""
     v = np.array([[-half, -half, z], [half, -half, z], [half, half, z], [-half, half, z]], dtype=np.float64)

@@ -395,6 +395,18 @@ class RaycastEngineHIP(RaycastEngineBase):
         return self.scene_for(mesh).scan_materials_compact(poses, self._resident_table(intrinsics), intrinsics.max_range,
                                                            materials, want=want)
 
+    def scan_mover_frames(self, intrinsics, poses, mesh, movers, mover_poses, want=("point3", "sem", "ins")):
+        """``scan_frames`` with moving objects (lrc_scan_movers_compact): ``movers`` a
+        ``lidarcast.movers.MoverSet`` of this engine's context (``MoverSet(engine.ctx, meshes)``) or None, ``mover_poses``
+        (P, M, 12) float32 object-to-world poses, one per scan pose and mover.  The static mesh is traced once and every mover in
+        its own frame; the nearest wins.  The dict of ``scan_frames`` plus ``mover``, one uint8 per kept row: 0 for the static
+        mesh, m + 1 for mover m (sem / ins / prim are then the mover's own)."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
+            raise ValueError("moving objects need a sensor with a pose-independent direction table")
+        return self.scene_for(mesh).scan_movers_compact(poses, self._resident_table(intrinsics), intrinsics.max_range, movers,
+                                                        mover_poses, want=want)
+
     def _firing_fractions(self, intrinsics):
         """(N,) firing fractions of the sensor's direction table (IndoorLidar.firing_fractions), cached with the table."""
         from lidar import IndoorLidar

@@ -204,6 +204,8 @@ class S3DISSimulator:
             raise NotImplementedError("surface coverage under the beam key is outside its scope")
         if self.config.get("materials") is not None:
             raise NotImplementedError("surface coverage under the materials key is outside its scope")
+        if self.config.get("movers") is not None:
+            raise NotImplementedError("surface coverage under the movers key is outside its scope")
         from lidarcast.synth import S3DIS_CLASSES
         s = self.raycast_engine.surface_coverage(self.lidar_config, poses_from_waypoints(waypoints),
                                                  self.scene.room_mesh)
@@ -229,6 +231,8 @@ class S3DISSimulator:
             raise NotImplementedError("occupancy grids under the beam key are outside their scope")
         if self.config.get("materials") is not None:
             raise NotImplementedError("occupancy grids under the materials key are outside their scope")
+        if self.config.get("movers") is not None:
+            raise NotImplementedError("occupancy grids under the movers key are outside their scope")
         from containers.s3dis_sim_scene import write_labeled_ply
         from lidarcast.synth import S3DIS_CLASSES
         r = self.raycast_engine.occupancy_grid(self.lidar_config, poses_from_waypoints(waypoints), self.scene.room_mesh,
@@ -267,6 +271,8 @@ class S3DISSimulator:
             raise NotImplementedError("frame annotations under the beam key are outside their scope")
         if self.config.get("materials") is not None:
             raise NotImplementedError("frame annotations under the materials key are outside their scope")
+        if self.config.get("movers") is not None:
+            raise NotImplementedError("frame annotations under the movers key are outside their scope")
         from lidar_net_bbox_visualizer import S3DIS_SEMANTIC_MAPPING
         from lidarcast.synth import S3DIS_CLASSES
         mapping = S3DIS_SEMANTIC_MAPPING if semantic_mapping is None else semantic_mapping
@@ -359,6 +365,61 @@ class S3DISSimulator:
         kw = {k: cfg[k] for k in ("max_bounces", "min_intensity") if k in cfg}
         return MaterialTable.from_classes(cfg.get("classes", {}), **kw)
 
+    def _mover_plan(self):
+        """The moving objects of the config key ``movers`` (None without the key): ``period`` (seconds between frames; frame k
+        is at k * period) and ``objects``, each ``{mesh: pedestrian | <path to a mesh>, semantic: id or S3DIS class name,
+        instance: id, path: [[t, x, y, z, yaw_deg], ...]}``.  Returns {period, meshes, tracks, objects (JSON-ready)}.  The key
+        stands alone: motion, noise, beam and materials are refused beside it."""
+        cfg = self.config.get("movers")
+        if cfg is None:
+            return None
+        for other in ("motion", "noise", "beam", "materials"):
+            if self.config.get(other) is not None:
+                raise ValueError(f"the movers key cannot be combined with the {other} key")
+        unknown = set(cfg) - {"period", "objects"}
+        if unknown:
+            raise ValueError(f"unknown entries under the movers key: {sorted(unknown)}")
+        period = float(cfg.get("period", 0.1))
+        if not (np.isfinite(period) and period > 0.0):
+            raise ValueError("movers.period must be a positive number of seconds")
+        objects = cfg.get("objects")
+        if not objects:
+            raise ValueError("the movers key needs at least one object")
+        if len(objects) > 255:
+            raise ValueError("the movers key takes at most 255 objects")
+        from lidarcast import synth
+        from lidarcast.movers import MoverTrack
+        meshes, tracks, listed = [], [], []
+        for k, obj in enumerate(objects):
+            unknown = set(obj) - {"mesh", "semantic", "instance", "path"}
+            if unknown:
+                raise ValueError(f"unknown entries of mover {k}: {sorted(unknown)}")
+            if "path" not in obj:
+                raise ValueError(f"mover {k} needs a path")
+            sem = obj.get("semantic", 13)
+            if isinstance(sem, str):
+                if sem not in synth.S3DIS_CLASSES:
+                    raise ValueError(f"mover {k}: unknown class {sem!r}")
+                sem = synth.S3DIS_CLASSES.index(sem)
+            sem, ins = int(sem), int(obj.get("instance", k + 1))
+            if not (0 <= sem < 65536 and 0 <= ins < 65536):
+                raise ValueError(f"mover {k}: semantic and instance ids must fit 16 bits")
+            name = obj.get("mesh", "pedestrian")
+            if name == "pedestrian":
+                mesh = synth.make_pedestrian(semantic=sem, instance=ins)
+            else:
+                from lidarcast.ply import read_triangle_mesh
+                src = read_triangle_mesh(str(name))
+                f = np.asarray(src.triangles, np.int32)
+                mesh = synth.TriangleMesh(vertices=np.asarray(src.vertices, np.float64), triangles=f,
+                                          triangle_sem=np.full(len(f), sem, np.uint16), triangle_ins=np.full(len(f), ins, np.uint16))
+            meshes.append(mesh)
+            tracks.append(MoverTrack(obj["path"]))
+            listed.append({"index": k, "mesh": str(name), "semantic": sem, "instance": ins, "num_triangles": len(mesh.triangles),
+                           "box_min": [float(x) for x in np.asarray(mesh.vertices).min(0)],
+                           "box_max": [float(x) for x in np.asarray(mesh.vertices).max(0)]})
+        return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed}
+
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
         rank (one process per GPU, backend "nccl" = RCCL), or with an explicit ``process_group``, the waypoints are
@@ -398,7 +459,11 @@ class S3DISSimulator:
         # carry intensities, bounces and surface_points per point, and their labels come with the points.  Without the key
         # nothing changes.
         materials = self._material_table() if len(waypoints) > 0 else None
-        lazy_labels = batched and materials is None and not bool(self.config.get("raycast_engine", {}).get("eager_labels", False))
+        # opt-in moving objects (config key ``movers: {period, objects: [{mesh, semantic, instance, path}, ...]}``): rigid meshes
+        # at a different pose in every frame, traced in their own frames beside the room; frames then
+        # carry mover_ids per point and their labels come with the points.  Without the key nothing changes.
+        movers = self._mover_plan() if len(waypoints) > 0 else None
+        lazy_labels = batched and materials is None and movers is None and not bool(self.config.get("raycast_engine", {}).get("eager_labels", False))
         want = ("point3",) + (() if lazy_labels else ("sem", "ins")) + \
             ("range_origin_stats" if device_stats else "range_origin",) + \
             (() if self.bug_compatible else (("incident_deg", "incident_stats") if device_stats else ("incident_deg",)))
@@ -443,7 +508,23 @@ class S3DISSimulator:
                 raise ValueError("the beam key is not available on a multi-rank process group")
             if not batched:
                 raise ValueError("the beam key needs a multi-line sensor with a direction table (not the dual-axis sensor)")
-        if materials is not None:
+        if movers is not None:
+            if dist is not None:
+                raise ValueError("the movers key is not available on a multi-rank process group")
+            if not batched:
+                raise ValueError("the movers key needs a multi-line sensor with a direction table (not the dual-axis sensor)")
+            from lidarcast.movers import MoverSet
+            times = np.arange(len(waypoints), dtype=np.float64) * movers["period"]
+            states = np.stack([t.state(times) for t in movers["tracks"]], axis=1)            # (P, M, 4): x, y, z, yaw
+            mover_poses = np.stack([t.poses12(times) for t in movers["tracks"]], axis=1)       # (P, M, 12) float32
+            mset = MoverSet(engine.ctx, movers["meshes"])
+            try:
+                fr = engine.scan_mover_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, want=want)
+            finally:
+                mset.close()
+            sim_scene.mover_tracks = {"period": movers["period"], "objects": movers["objects"], "times": times,
+                                      "states": states, "poses12": mover_poses}
+        elif materials is not None:
             if dist is not None:
                 raise ValueError("the materials key is not available on a multi-rank process group")
             if not batched:
@@ -521,6 +602,9 @@ class S3DISSimulator:
             if "echo_weight" in fr:        # per point: its beam (table row), its place among the beam's echoes, the sub-rays behind it
                 for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
                     f.beam_index, f.echo_index, f.echo_weight = (fr[a][e - c:e] for a in ("beam_index", "echo_index", "echo_weight"))
+            if "mover" in fr:              # per point: 0 for the room, m + 1 for mover m of the movers key
+                for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
+                    f.mover_ids = fr["mover"][e - c:e]
             if "bounces" in fr:            # per point: the return's strength, the panes and mirrors on its way, where it came from
                 for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
                     f.intensities, f.bounces, f.surface_points = (fr[a][e - c:e] for a in ("intensity", "bounces", "surface_point3"))
