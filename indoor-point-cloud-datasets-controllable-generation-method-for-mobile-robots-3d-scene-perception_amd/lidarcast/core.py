@@ -7,6 +7,7 @@ Device methods (torch CUDA tensors; torch is only the allocator and the stream) 
 Reference interface being served: raycast_engine/raycast_engine.py:16-61 (engine ABC) and the
 Open3D calls at raycast_engine/raycast_engine_cpu.py:46-53.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -25,6 +26,39 @@ _NP_SPEC = {
 
 def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _dptr(t):
+    """Device pointer of a torch tensor; None (an optional argument) stays None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream(stream):
+    return C.c_void_p(int(stream))
+
+
+def _keep_mask(keep, P, N):
+    """A (P, N) mask as the uint8 array the library reads: a view of a bool mask, a uint8 copy of anything else."""
+    if keep is None:
+        return None
+    if np.asarray(keep).dtype == np.bool_:
+        return np.ascontiguousarray(keep).reshape(P, N).view(np.uint8)
+    return np.ascontiguousarray(keep, dtype=np.uint8).reshape(P, N)
+
+
+def _check_side_tensor(name, t, dtype, numel, must, poses_t):
+    """An optional tensor the kernel reads or writes beside the records: its dtype (the kernel moves that many bytes per
+    entry), on the device of the poses, contiguous, ``numel`` entries (None: not checked; ``must`` words that message)."""
+    if t is None:
+        return
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}")
+    if t.device != poses_t.device or not t.is_cuda:
+        raise ValueError(f"{name} must lie on the device of the poses")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name} must {must}")
 
 
 FRAME_ATTRS = ("point3", "sem", "ins", "incident_deg", "index", "xyzl", "range_origin")
@@ -284,22 +318,20 @@ class Context:
     def cloud_from_ranges_dev(self, poses_t, dirs_t, t_label_t, out_rows_t, counts_t=None, stream=0):
         """Rebuild the compacted (x, y, z, label) rows of a pose-batched scan from its (t, label) pairs."""
         check(self._lib.lrc_cloud_from_ranges_dev(
-            self._h, C.c_void_p(poses_t.data_ptr()), poses_t.shape[0], C.c_void_p(dirs_t.data_ptr()),
-            dirs_t.shape[0], C.c_void_p(t_label_t.data_ptr()), C.c_void_p(out_rows_t.data_ptr()),
-            None if counts_t is None else C.c_void_p(counts_t.data_ptr()), C.c_void_p(int(stream))),
+            self._h, _dptr(poses_t), poses_t.shape[0], _dptr(dirs_t), dirs_t.shape[0], _dptr(t_label_t), _dptr(out_rows_t),
+            _dptr(counts_t), _stream(stream)),
             "lrc_cloud_from_ranges_dev")
 
     def cloud_range_stats_dev(self, rows_t, counts_t, range_t, mean_t, std_t, stream=0):
         """Per-pose mean / std of |row| (float32, numpy's arithmetic) over assembled (x, y, z, label) rows in HBM."""
         check(self._lib.lrc_cloud_range_stats_dev(
-            self._h, C.c_void_p(rows_t.data_ptr()), C.c_void_p(counts_t.data_ptr()), counts_t.shape[0], rows_t.shape[0],
-            C.c_void_p(range_t.data_ptr()), C.c_void_p(mean_t.data_ptr()), C.c_void_p(std_t.data_ptr()),
-            C.c_void_p(int(stream))), "lrc_cloud_range_stats_dev")
+            self._h, _dptr(rows_t), _dptr(counts_t), counts_t.shape[0], rows_t.shape[0],
+            _dptr(range_t), _dptr(mean_t), _dptr(std_t), _stream(stream)), "lrc_cloud_range_stats_dev")
 
     def compact_dev(self, nseg, seg_len, io, stream=0):
         """io: LrcCompactIO filled with device pointers."""
         check(self._lib.lrc_compact_dev(self._h, int(nseg), int(seg_len), C.byref(io),
-                                        C.c_void_p(int(stream))), "lrc_compact_dev")
+                                        _stream(stream)), "lrc_compact_dev")
 
 
 class DeviceHits:
@@ -377,6 +409,24 @@ class DirectionTable:
             self.close()
         except Exception:
             pass
+
+
+@contextlib.contextmanager
+def _table_for(ctx, dirs, fire=None):
+    """The direction table a scan on ``ctx`` runs with: the caller's DirectionTable, checked, or a table made of the (N, 3)
+    array ``dirs`` (and ``fire``) that lives as long as the ``with`` block."""
+    if isinstance(dirs, DirectionTable):
+        if not dirs._h:
+            raise ValueError("direction table handle is closed")
+        if dirs.ctx is not ctx:
+            raise ValueError("direction table belongs to another context (device)")
+        yield dirs
+        return
+    own = DirectionTable(ctx, dirs, fire)
+    try:
+        yield own
+    finally:
+        own.close()
 
 
 class Scene:
@@ -497,9 +547,8 @@ class Scene:
             if lab is not None and (lab.element_size() != 2 or lab.numel() != tris_t.shape[0] or not lab.is_contiguous()):
                 raise ValueError("per-triangle labels must be contiguous 16-bit arrays of shape (T,)")
         h = C.c_void_p()
-        dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        check(self._lib.lrc_scene_create_dev(ctx._h, dp(verts_t), verts_t.shape[0], dp(tris_t), tris_t.shape[0],
-                                             dp(sem_t), dp(ins_t), C.byref(h)), "lrc_scene_create_dev")
+        check(self._lib.lrc_scene_create_dev(ctx._h, _dptr(verts_t), verts_t.shape[0], _dptr(tris_t), tris_t.shape[0],
+                                             _dptr(sem_t), _dptr(ins_t), C.byref(h)), "lrc_scene_create_dev")
         self._h = h
         self.num_vertices, self.num_triangles = int(verts_t.shape[0]), int(tris_t.shape[0])
         return self
@@ -601,6 +650,19 @@ class Scene:
         g.lines, g.width, g.az0, g.az_step = int(grid[0]), int(grid[1]), float(grid[2]), float(grid[3])
         return g
 
+    def _scan_frames(self, name, P, rows, want, capacity, call, side=()):
+        """The scaffold of the *_compact methods: the frame buffers of P poses of ``rows`` rows each, one zeroed array per
+        per-row side column (key, dtype, tail) of ``side``, the C function ``name`` called through ``call(frames, capacity,
+        total, *side pointers)``, then the frame dict with the side columns behind it in list order, cut to the kept rows."""
+        fr, counts, bufs, cap = self._frames_begin(P, P * rows, want, capacity)
+        cols = [(key, np.zeros((max(cap, 1),) + tail, dtype=dt)) for key, dt, tail in side]
+        total = C.c_uint64(0)
+        check(call(C.byref(fr), cap, C.byref(total), *[_ptr(a) for _, a in cols]), name)
+        out = self._frames_end(counts, bufs, total.value)
+        for key, a in cols:
+            out[key] = a[:total.value]
+        return out
+
     def scan_poses_compact(self, poses, dirs, max_range, want=("point3", "sem", "ins"), capacity=None, grid=None):
         """Pose-batched scan straight to the kept rows of every pose (lrc_scan_poses_compact): dict of (K, ...)
         arrays over page-locked memory + ``counts`` (P,) int64 + ``total`` K.  Frame p = rows
@@ -608,33 +670,23 @@ class Scene:
         (scan line x azimuth) grid selects the packet kernel (lrc_scan_grid_compact): same bytes (a measured alternative,
         slower on the benchmark scenes).  ``dirs`` may be a DirectionTable handle (uploaded once, lrc_scan_table_compact)."""
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
+        lib, h, P, reach = self._lib, self._h, poses.shape[0], float(max_range)
         if isinstance(dirs, DirectionTable):          # resident table: nothing to upload
-            if not dirs._h:
-                raise ValueError("direction table handle is closed")
-            if dirs.ctx is not self.ctx:
-                raise ValueError("direction table belongs to another context (device)")
-            P, N = poses.shape[0], dirs.n
-            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
-            total = C.c_uint64(0)
-            g = None if grid is None else self._grid_struct(grid)
-            check(self._lib.lrc_scan_table_compact(self._h, _ptr(poses), P, dirs._h, None if g is None else C.byref(g),
-                                                   float(max_range), C.byref(fr), cap, C.byref(total)),
-                  "lrc_scan_table_compact")
-            return self._frames_end(counts, bufs, total.value)
+            with _table_for(self.ctx, dirs) as table:
+                g = None if grid is None else self._grid_struct(grid)
+                return self._scan_frames("lrc_scan_table_compact", P, table.n, want, capacity, lambda fr, cap, total:
+                                         lib.lrc_scan_table_compact(h, _ptr(poses), P, table._h, None if g is None else C.byref(g),
+                                                                    reach, fr, cap, total))
         dirs = np.ascontiguousarray(dirs, dtype=np.float64)
         if dirs.ndim != 2 or dirs.shape[1] != 3:
             raise ValueError("dirs must be (N, 3)")
-        P, N = poses.shape[0], dirs.shape[0]
-        fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
-        total = C.c_uint64(0)
+        N = dirs.shape[0]
         if grid is not None:
             g = self._grid_struct(grid)
-            check(self._lib.lrc_scan_grid_compact(self._h, _ptr(poses), P, _ptr(dirs), C.byref(g), float(max_range),
-                                                  C.byref(fr), cap, C.byref(total)), "lrc_scan_grid_compact")
-        else:
-            check(self._lib.lrc_scan_poses_compact(self._h, _ptr(poses), P, _ptr(dirs), N, float(max_range),
-                                                   C.byref(fr), cap, C.byref(total)), "lrc_scan_poses_compact")
-        return self._frames_end(counts, bufs, total.value)
+            return self._scan_frames("lrc_scan_grid_compact", P, N, want, capacity, lambda fr, cap, total:
+                                     lib.lrc_scan_grid_compact(h, _ptr(poses), P, _ptr(dirs), C.byref(g), reach, fr, cap, total))
+        return self._scan_frames("lrc_scan_poses_compact", P, N, want, capacity, lambda fr, cap, total:
+                                 lib.lrc_scan_poses_compact(h, _ptr(poses), P, _ptr(dirs), N, reach, fr, cap, total))
 
     def scan_sweeps_compact(self, motion, dirs, fire, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Moving-sensor sweeps straight to frames (lrc_scan_sweeps_compact): ``motion`` (P, 24) records
@@ -642,57 +694,28 @@ class Scene:
         None takes the DirectionTable's resident ones; a different table than the resident one is uploaded into it.
         Same return value as ``scan_poses_compact``."""
         motion = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 24)
-        own = None
-        if isinstance(dirs, DirectionTable):
-            if not dirs._h:
-                raise ValueError("direction table handle is closed")
-            if dirs.ctx is not self.ctx:
-                raise ValueError("direction table belongs to another context (device)")
-            if fire is not None and (dirs.fire is None or not np.array_equal(dirs.fire, np.asarray(fire, np.float64).reshape(-1))):
-                dirs.set_fire(fire)
-            table = dirs
-        else:
-            if fire is None:
-                raise ValueError("fire is required with a plain direction table")
-            table = own = DirectionTable(self.ctx, dirs, fire)
-        if table.fire is None:
-            raise ValueError("the direction table has no firing fractions")
-        try:
-            P, N = motion.shape[0], table.n
-            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
-            total = C.c_uint64(0)
-            check(self._lib.lrc_scan_sweeps_compact(self._h, _ptr(motion), P, table._h, float(max_range), C.byref(fr), cap,
-                                                    C.byref(total)), "lrc_scan_sweeps_compact")
-            return self._frames_end(counts, bufs, total.value)
-        finally:
-            if own is not None:
-                own.close()
+        lib, h, P, reach = self._lib, self._h, motion.shape[0], float(max_range)
+        if fire is None and not isinstance(dirs, DirectionTable):
+            raise ValueError("fire is required with a plain direction table")
+        with _table_for(self.ctx, dirs, fire) as table:
+            if table is dirs and fire is not None and \
+                    (table.fire is None or not np.array_equal(table.fire, np.asarray(fire, np.float64).reshape(-1))):
+                table.set_fire(fire)
+            if table.fire is None:
+                raise ValueError("the direction table has no firing fractions")
+            return self._scan_frames("lrc_scan_sweeps_compact", P, table.n, want, capacity, lambda fr, cap, total:
+                                     lib.lrc_scan_sweeps_compact(h, _ptr(motion), P, table._h, reach, fr, cap, total))
 
     def scan_noisy_compact(self, poses, dirs, max_range, noise, want=("point3", "sem", "ins"), capacity=None):
         """Pose-batched scan with seeded sensor noise straight to frames (lrc_scan_noisy_compact): ``noise`` a
         ``lidarcast.noise.NoiseModel`` (pose p of the call is frame ``noise.first_frame + p``), ``dirs`` a DirectionTable or
         an (N, 3) table.  Same return value as ``scan_poses_compact``."""
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
-        own = None
-        if isinstance(dirs, DirectionTable):
-            if not dirs._h:
-                raise ValueError("direction table handle is closed")
-            if dirs.ctx is not self.ctx:
-                raise ValueError("direction table belongs to another context (device)")
-            table = dirs
-        else:
-            table = own = DirectionTable(self.ctx, dirs)
-        try:
-            P, N = poses.shape[0], table.n
-            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
-            total = C.c_uint64(0)
+        lib, h, P, reach = self._lib, self._h, poses.shape[0], float(max_range)
+        with _table_for(self.ctx, dirs) as table:
             nz = noise.struct()
-            check(self._lib.lrc_scan_noisy_compact(self._h, _ptr(poses), P, table._h, float(max_range), C.byref(nz),
-                                                   C.byref(fr), cap, C.byref(total)), "lrc_scan_noisy_compact")
-            return self._frames_end(counts, bufs, total.value)
-        finally:
-            if own is not None:
-                own.close()
+            return self._scan_frames("lrc_scan_noisy_compact", P, table.n, want, capacity, lambda fr, cap, total:
+                                     lib.lrc_scan_noisy_compact(h, _ptr(poses), P, table._h, reach, C.byref(nz), fr, cap, total))
 
     def scan_echoes_compact(self, poses, dirs, max_range, beam, want=("point3", "sem", "ins"), capacity=None):
         """Pose-batched scan of diverging beams straight to frames (lrc_scan_echoes_compact): ``beam`` a
@@ -700,36 +723,21 @@ class Scene:
         over P poses of N * E echo records -- ``index`` is i * E + e -- plus ``beam_index`` (i), ``echo_index`` (e) and
         ``echo_weight`` (the sub-rays behind the echo, uint8), one entry per kept row."""
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
-        own = None
-        if isinstance(dirs, DirectionTable):
-            if not dirs._h:
-                raise ValueError("direction table handle is closed")
-            if dirs.ctx is not self.ctx:
-                raise ValueError("direction table belongs to another context (device)")
-            table = dirs
-        else:
-            table = own = DirectionTable(self.ctx, dirs)
-        try:
-            P, N, E = poses.shape[0], table.n, beam.max_echoes
+        lib, h, P, reach = self._lib, self._h, poses.shape[0], float(max_range)
+        with _table_for(self.ctx, dirs) as table:
+            E = beam.max_echoes
             asked = tuple(want)
-            if "index" not in asked:
-                want = asked + ("index",)
-            fr, counts, bufs, cap = self._frames_begin(P, P * N * E, want, capacity)
-            weight = np.zeros(max(cap, 1), dtype=np.uint8)
-            total = C.c_uint64(0)
             b = beam.struct()
-            check(self._lib.lrc_scan_echoes_compact(self._h, _ptr(poses), P, table._h, _ptr(beam.offsets), C.byref(b),
-                                                    float(max_range), C.byref(fr), _ptr(weight), cap, C.byref(total)),
-                  "lrc_scan_echoes_compact")
-            out = self._frames_end(counts, bufs, total.value)
-            idx = out["index"] if "index" in asked else out.pop("index")
-            out["beam_index"] = (idx // np.uint32(E)).astype(np.uint32)
-            out["echo_index"] = (idx % np.uint32(E)).astype(np.uint8)
-            out["echo_weight"] = weight[:total.value]
-            return out
-        finally:
-            if own is not None:
-                own.close()
+            out = self._scan_frames("lrc_scan_echoes_compact", P, table.n * E, asked if "index" in asked else asked + ("index",),
+                                    capacity, lambda fr, cap, total, weight:
+                                    lib.lrc_scan_echoes_compact(h, _ptr(poses), P, table._h, _ptr(beam.offsets), C.byref(b), reach,
+                                                                fr, weight, cap, total),
+                                    side=[("echo_weight", np.uint8, ())])
+        idx = out["index"] if "index" in asked else out.pop("index")
+        out["beam_index"] = (idx // np.uint32(E)).astype(np.uint32)
+        out["echo_index"] = (idx % np.uint32(E)).astype(np.uint8)
+        out["echo_weight"] = out.pop("echo_weight")         # behind the two columns derived from the index
+        return out
 
     def scan_materials_compact(self, poses, dirs, max_range, materials, want=("point3", "sem", "ins"), capacity=None):
         """Pose-batched scan with surface materials straight to frames (lrc_scan_materials_compact): ``materials`` a
@@ -738,33 +746,14 @@ class Scene:
         the glass panes and mirrors on the way) and ``surface_point3`` (float32 x 3: where the return physically came from;
         ``point3`` lies on the original beam at the total path length)."""
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
-        own = None
-        if isinstance(dirs, DirectionTable):
-            if not dirs._h:
-                raise ValueError("direction table handle is closed")
-            if dirs.ctx is not self.ctx:
-                raise ValueError("direction table belongs to another context (device)")
-            table = dirs
-        else:
-            table = own = DirectionTable(self.ctx, dirs)
-        try:
-            P, N = poses.shape[0], table.n
-            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
-            inten = np.zeros(max(cap, 1), dtype=np.float32)
-            bounces = np.zeros(max(cap, 1), dtype=np.uint8)
-            surface = np.zeros((max(cap, 1), 3), dtype=np.float32)
-            total = C.c_uint64(0)
-            check(self._lib.lrc_scan_materials_compact(self._h, _ptr(poses), P, table._h, materials.resident(self.ctx),
-                                                       float(max_range), C.byref(fr), _ptr(inten), _ptr(bounces), _ptr(surface),
-                                                       cap, C.byref(total)), "lrc_scan_materials_compact")
-            out = self._frames_end(counts, bufs, total.value)
-            out["intensity"] = inten[:total.value]
-            out["bounces"] = bounces[:total.value]
-            out["surface_point3"] = surface[:total.value]
-            return out
-        finally:
-            if own is not None:
-                own.close()
+        lib, h, P, reach = self._lib, self._h, poses.shape[0], float(max_range)
+        with _table_for(self.ctx, dirs) as table:
+            return self._scan_frames("lrc_scan_materials_compact", P, table.n, want, capacity,
+                                     lambda fr, cap, total, intensity, bounces, surface:
+                                     lib.lrc_scan_materials_compact(h, _ptr(poses), P, table._h, materials.resident(self.ctx), reach,
+                                                                    fr, intensity, bounces, surface, cap, total),
+                                     side=[("intensity", np.float32, ()), ("bounces", np.uint8, ()),
+                                           ("surface_point3", np.float32, (3,))])
 
     def scan_movers_compact(self, poses, dirs, max_range, movers, mover_poses, want=("point3", "sem", "ins"), capacity=None):
         """Pose-batched scan with moving objects straight to frames (lrc_scan_movers_compact): ``movers`` a
@@ -772,53 +761,31 @@ class Scene:
         ``dirs`` a DirectionTable or an (N, 3) table.  The return value of ``scan_poses_compact`` plus ``mover``, one uint8 per
         kept row: 0 for the static scene, m + 1 for mover m."""
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
-        own = None
-        if isinstance(dirs, DirectionTable):
-            if not dirs._h:
-                raise ValueError("direction table handle is closed")
-            if dirs.ctx is not self.ctx:
-                raise ValueError("direction table belongs to another context (device)")
-            table = dirs
-        else:
-            table = own = DirectionTable(self.ctx, dirs)
-        try:
-            P, N = poses.shape[0], table.n
+        lib, h, P, reach = self._lib, self._h, poses.shape[0], float(max_range)
+        with _table_for(self.ctx, dirs) as table:
             handle, mp = None, None
             if movers is not None:
                 handle = movers.handle(self.ctx)
                 mp = np.ascontiguousarray(mover_poses, dtype=np.float32)
                 if mp.shape != (P, len(movers), 12):
                     raise ValueError(f"mover_poses must be (P, M, 12) = ({P}, {len(movers)}, 12), got {mp.shape}")
-            fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
-            rows = np.zeros(max(cap, 1), dtype=np.uint8)
-            total = C.c_uint64(0)
-            check(self._lib.lrc_scan_movers_compact(self._h, handle, _ptr(poses), P, table._h, _ptr(mp), float(max_range),
-                                                    C.byref(fr), _ptr(rows), cap, C.byref(total)), "lrc_scan_movers_compact")
-            out = self._frames_end(counts, bufs, total.value)
-            out["mover"] = rows[:total.value]
-            return out
-        finally:
-            if own is not None:
-                own.close()
+            return self._scan_frames("lrc_scan_movers_compact", P, table.n, want, capacity, lambda fr, cap, total, rows:
+                                     lib.lrc_scan_movers_compact(h, handle, _ptr(poses), P, table._h, _ptr(mp), reach, fr, rows,
+                                                                 cap, total),
+                                     side=[("mover", np.uint8, ())])
 
     def scan_angles_compact(self, poses, angles, keep, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Dual-axis sensor, rays generated in the kernel from host-drawn (phi, theta) (lrc_scan_angles_compact).
         angles: (P, N, 2) float64; keep: (P, N) bool / uint8 or None."""
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
         angles = np.ascontiguousarray(angles, dtype=np.float64)
-        P = poses.shape[0]
+        lib, h, P, reach = self._lib, self._h, poses.shape[0], float(max_range)
         if angles.ndim != 3 or angles.shape[0] != P or angles.shape[2] != 2:
             raise ValueError("angles must be (P, N, 2)")
         N = angles.shape[1]
-        k8 = None
-        if keep is not None:
-            k8 = np.ascontiguousarray(keep).reshape(P, N).view(np.uint8) if np.asarray(keep).dtype == np.bool_ \
-                else np.ascontiguousarray(keep, dtype=np.uint8).reshape(P, N)
-        fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
-        total = C.c_uint64(0)
-        check(self._lib.lrc_scan_angles_compact(self._h, _ptr(poses), P, _ptr(angles), _ptr(k8), N, float(max_range),
-                                                C.byref(fr), cap, C.byref(total)), "lrc_scan_angles_compact")
-        return self._frames_end(counts, bufs, total.value)
+        k8 = _keep_mask(keep, P, N)
+        return self._scan_frames("lrc_scan_angles_compact", P, N, want, capacity, lambda fr, cap, total:
+                                 lib.lrc_scan_angles_compact(h, _ptr(poses), P, _ptr(angles), _ptr(k8), N, reach, fr, cap, total))
 
     def scan_rays_compact(self, rays, keep, centers, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Host-generated rays of several poses at a fixed stride straight to frames (lrc_scan_rays_compact).
@@ -826,17 +793,11 @@ class Scene:
         rays = np.ascontiguousarray(rays, dtype=np.float32)
         if rays.ndim != 3 or rays.shape[2] != 6:
             raise ValueError("rays must be (P, N, 6)")
-        P, N = rays.shape[0], rays.shape[1]
+        lib, h, P, N, reach = self._lib, self._h, rays.shape[0], rays.shape[1], float(max_range)
         cen = np.ascontiguousarray(centers, dtype=np.float64).reshape(P, 3)
-        k8 = None
-        if keep is not None:
-            k8 = np.ascontiguousarray(keep).reshape(P, N).view(np.uint8) if np.asarray(keep).dtype == np.bool_ \
-                else np.ascontiguousarray(keep, dtype=np.uint8).reshape(P, N)
-        fr, counts, bufs, cap = self._frames_begin(P, P * N, want, capacity)
-        total = C.c_uint64(0)
-        check(self._lib.lrc_scan_rays_compact(self._h, _ptr(rays), _ptr(k8), _ptr(cen), P, N, float(max_range),
-                                              C.byref(fr), cap, C.byref(total)), "lrc_scan_rays_compact")
-        return self._frames_end(counts, bufs, total.value)
+        k8 = _keep_mask(keep, P, N)
+        return self._scan_frames("lrc_scan_rays_compact", P, N, want, capacity, lambda fr, cap, total:
+                                 lib.lrc_scan_rays_compact(h, _ptr(rays), _ptr(k8), _ptr(cen), P, N, reach, fr, cap, total))
 
     def scan_stats(self, poses, dirs, max_range):
         """(P*N, 5) uint32 traversal counters per ray from the instrumented trace kernel (lrc_debug_scan_stats):
@@ -853,39 +814,31 @@ class Scene:
     def scan_angles_dev(self, poses_t, angles_t, keep_t, hits, max_range, stream=0):
         P = poses_t.shape[0]
         N = angles_t.shape[0] // max(P, 1) if angles_t.dim() == 2 else angles_t.shape[1]
-        check(self._lib.lrc_scan_angles_dev(self._h, C.c_void_p(poses_t.data_ptr()), P,
-                                            C.c_void_p(angles_t.data_ptr()),
-                                            None if keep_t is None else C.c_void_p(keep_t.data_ptr()), N,
-                                            float(max_range), C.byref(hits.struct), C.c_void_p(int(stream))),
-              "lrc_scan_angles_dev")
+        check(self._lib.lrc_scan_angles_dev(self._h, _dptr(poses_t), P, _dptr(angles_t), _dptr(keep_t), N, float(max_range),
+                                            C.byref(hits.struct), _stream(stream)), "lrc_scan_angles_dev")
 
     def cast_dev(self, rays_t, hits, center=None, max_range=np.inf, stream=0):
         c = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(3)
-        check(self._lib.lrc_cast_dev(self._h, C.c_void_p(rays_t.data_ptr()), rays_t.shape[0], _ptr(c),
-                                     float(max_range), C.byref(hits.struct), C.c_void_p(int(stream))),
-              "lrc_cast_dev")
+        check(self._lib.lrc_cast_dev(self._h, _dptr(rays_t), rays_t.shape[0], _ptr(c), float(max_range),
+                                     C.byref(hits.struct), _stream(stream)), "lrc_cast_dev")
 
     def scan_poses_dev(self, poses_t, dirs_t, hits, max_range, stream=0, grid=None):
         P, N = poses_t.shape[0], dirs_t.shape[0]
         if grid is not None:       # the table is a (scan line x azimuth) grid: packet kernel, same bytes
             g = self._grid_struct(grid)
-            check(self._lib.lrc_scan_grid_dev(self._h, C.c_void_p(poses_t.data_ptr()), P,
-                                              C.c_void_p(dirs_t.data_ptr()), C.byref(g), float(max_range),
-                                              C.byref(hits.struct), C.c_void_p(int(stream))), "lrc_scan_grid_dev")
+            check(self._lib.lrc_scan_grid_dev(self._h, _dptr(poses_t), P, _dptr(dirs_t), C.byref(g), float(max_range),
+                                              C.byref(hits.struct), _stream(stream)), "lrc_scan_grid_dev")
             return
-        check(self._lib.lrc_scan_poses_dev(self._h, C.c_void_p(poses_t.data_ptr()), P,
-                                           C.c_void_p(dirs_t.data_ptr()), N, float(max_range),
-                                           C.byref(hits.struct), C.c_void_p(int(stream))),
-              "lrc_scan_poses_dev")
+        check(self._lib.lrc_scan_poses_dev(self._h, _dptr(poses_t), P, _dptr(dirs_t), N, float(max_range),
+                                           C.byref(hits.struct), _stream(stream)), "lrc_scan_poses_dev")
 
     def scan_noisy_dev(self, poses_t, dirs_t, hits, max_range, noise, stream=0):
         """Pose-batched scan with seeded sensor noise on device tensors (lrc_scan_noisy_dev): poses_t (P, 16) float64,
         dirs_t (N, 3) float64, ``noise`` a ``lidarcast.noise.NoiseModel``; records as ``scan_poses_dev``."""
         P, N = poses_t.shape[0], dirs_t.shape[0]
         nz = noise.struct()
-        check(self._lib.lrc_scan_noisy_dev(self._h, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
-                                           float(max_range), C.byref(nz), C.byref(hits.struct), C.c_void_p(int(stream))),
-              "lrc_scan_noisy_dev")
+        check(self._lib.lrc_scan_noisy_dev(self._h, _dptr(poses_t), P, _dptr(dirs_t), N, float(max_range), C.byref(nz),
+                                           C.byref(hits.struct), _stream(stream)), "lrc_scan_noisy_dev")
 
     def scan_echoes_dev(self, poses_t, dirs_t, hits, max_range, beam, weight_t=None, offsets_t=None, stream=0):
         """Pose-batched scan of diverging beams on device tensors (lrc_scan_echoes_dev): poses_t (P, 16) float64, dirs_t
@@ -903,10 +856,9 @@ class Scene:
         elif offsets_t.numel() != 2 * beam.subrays:
             raise ValueError("offsets_t must be (K, 2)")
         b = beam.struct()
-        check(self._lib.lrc_scan_echoes_dev(self._h, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
-                                            C.c_void_p(offsets_t.data_ptr()), C.byref(b), float(max_range),
-                                            C.byref(hits.struct), None if weight_t is None else C.c_void_p(weight_t.data_ptr()),
-                                            C.c_void_p(int(stream))), "lrc_scan_echoes_dev")
+        check(self._lib.lrc_scan_echoes_dev(self._h, _dptr(poses_t), P, _dptr(dirs_t), N, _dptr(offsets_t), C.byref(b),
+                                            float(max_range), C.byref(hits.struct), _dptr(weight_t), _stream(stream)),
+              "lrc_scan_echoes_dev")
         return offsets_t
 
     def scan_materials_dev(self, poses_t, dirs_t, hits, max_range, materials, bounces_t=None, surface_t=None, stream=0):
@@ -914,59 +866,35 @@ class Scene:
         (N, 3) float64, ``materials`` a ``lidarcast.material.MaterialTable``; ``bounces_t`` an optional (P * N) uint8 tensor,
         ``surface_t`` an optional (P * N, 3) float32 tensor.  ``hits`` holds P * N records; its intensity column receives the
         return's strength."""
+        import torch
         P, N = poses_t.shape[0], dirs_t.shape[0]
         if hits.n != P * N:
             raise ValueError("hits must hold P * N records")
-        if bounces_t is not None and bounces_t.numel() != P * N:
-            raise ValueError("bounces_t must hold P * N entries")
-        if surface_t is not None and surface_t.numel() != 3 * P * N:
-            raise ValueError("surface_t must be (P * N, 3)")
-        import torch
-        for name, t, dt in (("bounces_t", bounces_t, torch.uint8), ("surface_t", surface_t, torch.float32)):
-            if t is None:
-                continue
-            if t.dtype != dt:
-                raise ValueError(f"{name} must be {dt} (the kernel writes that many bytes per ray)")
-            if t.device != poses_t.device or not t.is_cuda:
-                raise ValueError(f"{name} must lie on the device of the poses")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous")
-        check(self._lib.lrc_scan_materials_dev(self._h, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
-                                               materials.resident(self.ctx), float(max_range), C.byref(hits.struct),
-                                               None if bounces_t is None else C.c_void_p(bounces_t.data_ptr()),
-                                               None if surface_t is None else C.c_void_p(surface_t.data_ptr()),
-                                               C.c_void_p(int(stream))), "lrc_scan_materials_dev")
+        _check_side_tensor("bounces_t", bounces_t, torch.uint8, P * N, "hold P * N entries", poses_t)
+        _check_side_tensor("surface_t", surface_t, torch.float32, 3 * P * N, "be (P * N, 3)", poses_t)
+        check(self._lib.lrc_scan_materials_dev(self._h, _dptr(poses_t), P, _dptr(dirs_t), N, materials.resident(self.ctx),
+                                               float(max_range), C.byref(hits.struct), _dptr(bounces_t), _dptr(surface_t),
+                                               _stream(stream)), "lrc_scan_materials_dev")
 
     def scan_movers_dev(self, poses_t, dirs_t, hits, max_range, movers, mover_poses_t, mover_t=None, stream=0):
         """Pose-batched scan with moving objects on device tensors (lrc_scan_movers_dev): poses_t (P, 16) float64, dirs_t
         (N, 3) float64, ``movers`` a ``lidarcast.movers.MoverSet`` or None, ``mover_poses_t`` (P, M, 12) float32 (the caller
         vouches for them), ``mover_t`` an optional (P * N) uint8 tensor: 0 for the static scene, m + 1 for mover m.  ``hits``
         holds P * N records and no tile_count."""
+        import torch
         P, N = poses_t.shape[0], dirs_t.shape[0]
         if hits.n != P * N:
             raise ValueError("hits must hold P * N records")
-        import torch
-        handle = None
+        handle, entries = None, None
         if movers is not None:
-            handle = movers.handle(self.ctx)
-            if mover_poses_t is None or mover_poses_t.numel() != P * len(movers) * 12:
+            handle, entries = movers.handle(self.ctx), P * len(movers) * 12
+            if mover_poses_t is None:
                 raise ValueError("mover_poses_t must be (P, M, 12)")
-        for name, t, dt in (("mover_poses_t", mover_poses_t, torch.float32), ("mover_t", mover_t, torch.uint8)):
-            if t is None:
-                continue
-            if t.dtype != dt:
-                raise ValueError(f"{name} must be {dt}")
-            if t.device != poses_t.device or not t.is_cuda:
-                raise ValueError(f"{name} must lie on the device of the poses")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous")
-        if mover_t is not None and mover_t.numel() != P * N:
-            raise ValueError("mover_t must hold P * N entries")
-        check(self._lib.lrc_scan_movers_dev(self._h, handle, C.c_void_p(poses_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()), N,
-                                            None if mover_poses_t is None else C.c_void_p(mover_poses_t.data_ptr()),
-                                            float(max_range), C.byref(hits.struct),
-                                            None if mover_t is None else C.c_void_p(mover_t.data_ptr()),
-                                            C.c_void_p(int(stream))), "lrc_scan_movers_dev")
+        _check_side_tensor("mover_poses_t", mover_poses_t, torch.float32, entries, "be (P, M, 12)", poses_t)
+        _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", poses_t)
+        check(self._lib.lrc_scan_movers_dev(self._h, handle, _dptr(poses_t), P, _dptr(dirs_t), N, _dptr(mover_poses_t),
+                                            float(max_range), C.byref(hits.struct), _dptr(mover_t), _stream(stream)),
+              "lrc_scan_movers_dev")
 
     def scan_sweeps_dev(self, motion_t, dirs_t, fire_t, hits, max_range, stream=0):
         """Moving-sensor sweeps on device tensors (lrc_scan_sweeps_dev): motion_t (P, 24) float64, dirs_t (N, 3) float64,
@@ -974,9 +902,8 @@ class Scene:
         P, N = motion_t.shape[0], dirs_t.shape[0]
         if motion_t.numel() != P * 24 or fire_t.numel() != N:
             raise ValueError("motion_t must be (P, 24) and fire_t (N,)")
-        check(self._lib.lrc_scan_sweeps_dev(self._h, C.c_void_p(motion_t.data_ptr()), P, C.c_void_p(dirs_t.data_ptr()),
-                                            C.c_void_p(fire_t.data_ptr()), N, float(max_range), C.byref(hits.struct),
-                                            C.c_void_p(int(stream))), "lrc_scan_sweeps_dev")
+        check(self._lib.lrc_scan_sweeps_dev(self._h, _dptr(motion_t), P, _dptr(dirs_t), _dptr(fire_t), N, float(max_range),
+                                            C.byref(hits.struct), _stream(stream)), "lrc_scan_sweeps_dev")
 
     def cloud_from_prims_dev(self, poses_t, dirs_t, prim_t, out_rows_t, counts_t=None, tile_count_t=None,
                              poses_per_slab=0, slab_stride_bytes=0, stream=0, own_slab=None, own_io=None):
@@ -986,18 +913,13 @@ class Scene:
         come from its local records instead of being rebuilt (lrc_cloud_from_prims_own_dev)."""
         if own_slab is not None:
             check(self._lib.lrc_cloud_from_prims_own_dev(
-                self._h, C.c_void_p(poses_t.data_ptr()), poses_t.shape[0], C.c_void_p(dirs_t.data_ptr()),
-                dirs_t.shape[0], C.c_void_p(prim_t.data_ptr()), C.c_void_p(tile_count_t.data_ptr()),
-                int(poses_per_slab), int(slab_stride_bytes), int(own_slab), C.byref(own_io),
-                C.c_void_p(out_rows_t.data_ptr()), None if counts_t is None else C.c_void_p(counts_t.data_ptr()),
-                C.c_void_p(int(stream))), "lrc_cloud_from_prims_own_dev")
+                self._h, _dptr(poses_t), poses_t.shape[0], _dptr(dirs_t), dirs_t.shape[0], _dptr(prim_t), _dptr(tile_count_t),
+                int(poses_per_slab), int(slab_stride_bytes), int(own_slab), C.byref(own_io), _dptr(out_rows_t), _dptr(counts_t),
+                _stream(stream)), "lrc_cloud_from_prims_own_dev")
             return
         check(self._lib.lrc_cloud_from_prims_dev(
-            self._h, C.c_void_p(poses_t.data_ptr()), poses_t.shape[0], C.c_void_p(dirs_t.data_ptr()),
-            dirs_t.shape[0], C.c_void_p(prim_t.data_ptr()),
-            None if tile_count_t is None else C.c_void_p(tile_count_t.data_ptr()),
-            int(poses_per_slab), int(slab_stride_bytes), C.c_void_p(out_rows_t.data_ptr()),
-            None if counts_t is None else C.c_void_p(counts_t.data_ptr()), C.c_void_p(int(stream))),
+            self._h, _dptr(poses_t), poses_t.shape[0], _dptr(dirs_t), dirs_t.shape[0], _dptr(prim_t), _dptr(tile_count_t),
+            int(poses_per_slab), int(slab_stride_bytes), _dptr(out_rows_t), _dptr(counts_t), _stream(stream)),
             "lrc_cloud_from_prims_dev")
 
 
@@ -1092,13 +1014,12 @@ class ScanPipe:
             if counts_t is not None:
                 io.counts = counts_t.data_ptr()
         ticket = C.c_uint64(0)
-        check(self._lib.lrc_pipe_submit(self._h, C.c_void_p(poses_t.data_ptr()), poses_t.shape[0],
-                                        C.c_void_p(dirs_t.data_ptr()), float(max_range), C.byref(io),
-                                        C.c_void_p(int(stream)), C.byref(ticket)), "lrc_pipe_submit")
+        check(self._lib.lrc_pipe_submit(self._h, _dptr(poses_t), poses_t.shape[0], _dptr(dirs_t), float(max_range),
+                                        C.byref(io), _stream(stream), C.byref(ticket)), "lrc_pipe_submit")
         return ticket.value
 
     def wait(self, stream=0):
-        check(self._lib.lrc_pipe_wait(self._h, C.c_void_p(int(stream))), "lrc_pipe_wait")
+        check(self._lib.lrc_pipe_wait(self._h, _stream(stream)), "lrc_pipe_wait")
 
     def set_line_width(self, line_width):
         """Hint: the table's rays come in scan lines of `line_width` rows (0: detect it from the table).  Regroups rays into
@@ -1133,23 +1054,23 @@ class ScanPipe:
     def submit_sharded(self, poses_t, dirs_t, max_range, send_prim_t, send_tile_count_t, assemble=None, stream=0):
         ticket = C.c_uint64(0)
         check(self._lib.lrc_pipe_submit_sharded(
-            self._h, C.c_void_p(poses_t.data_ptr()), poses_t.shape[0], C.c_void_p(dirs_t.data_ptr()), float(max_range),
-            C.c_void_p(send_prim_t.data_ptr()), C.c_void_p(send_tile_count_t.data_ptr()),
-            C.byref(assemble) if assemble is not None else None, C.c_void_p(int(stream)), C.byref(ticket)),
+            self._h, _dptr(poses_t), poses_t.shape[0], _dptr(dirs_t), float(max_range),
+            _dptr(send_prim_t), _dptr(send_tile_count_t),
+            C.byref(assemble) if assemble is not None else None, _stream(stream), C.byref(ticket)),
             "lrc_pipe_submit_sharded")
         return ticket.value
 
     def trace_done(self, ticket, stream=0):
         """``stream`` waits for the trace of that submit: its send slab is complete, the collective may start."""
-        check(self._lib.lrc_pipe_trace_done(self._h, int(ticket), C.c_void_p(int(stream))), "lrc_pipe_trace_done")
+        check(self._lib.lrc_pipe_trace_done(self._h, int(ticket), _stream(stream)), "lrc_pipe_trace_done")
 
     def scan_gathered(self, dirs_t, gathered, stream=0):
         """The scan over the gathered keep counts: enqueue on the communication stream right behind the collective."""
-        check(self._lib.lrc_pipe_scan_gathered(self._h, C.c_void_p(dirs_t.data_ptr()), C.byref(gathered), C.c_void_p(int(stream))),
+        check(self._lib.lrc_pipe_scan_gathered(self._h, _dptr(dirs_t), C.byref(gathered), _stream(stream)),
               "lrc_pipe_scan_gathered")
 
     def assemble(self, dirs_t, gathered, stream=0):
-        check(self._lib.lrc_pipe_assemble(self._h, C.c_void_p(dirs_t.data_ptr()), C.byref(gathered), C.c_void_p(int(stream))),
+        check(self._lib.lrc_pipe_assemble(self._h, _dptr(dirs_t), C.byref(gathered), _stream(stream)),
               "lrc_pipe_assemble")
 
     def records(self, ticket):
@@ -1201,10 +1122,8 @@ class NearestIndex:
         return (idx, dist) if return_distance else idx
 
     def query_dev(self, q_t, idx_t, dist_t=None, stream=0):
-        check(self._lib.lrc_nn_query_dev(self._h, C.c_void_p(q_t.data_ptr()), q_t.shape[0],
-                                         C.c_void_p(idx_t.data_ptr()),
-                                         None if dist_t is None else C.c_void_p(dist_t.data_ptr()),
-                                         C.c_void_p(int(stream))), "lrc_nn_query_dev")
+        check(self._lib.lrc_nn_query_dev(self._h, _dptr(q_t), q_t.shape[0], _dptr(idx_t), _dptr(dist_t), _stream(stream)),
+              "lrc_nn_query_dev")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -333,22 +333,35 @@ class RaycastEngineHIP(RaycastEngineBase):
         return points, np.empty(0)
 
     # ---- pose-batched fast path (what the per-waypoint loop becomes) ---------------------------------
+    @staticmethod
+    def _need_table(intrinsics, message, exc=ValueError):
+        """Table-driven scans are for sensors with a pose-independent direction table (IndoorLidar's records, not the
+        dual-axis sensor's): anything else is refused with the caller's ``message``, raised as the caller's ``exc``."""
+        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
+            raise exc(message)
+
+    def _table_frames(self, method, message, intrinsics, poses, mesh, *args, packet_grid=False, **kw):
+        """``Scene.<method>(poses, the sensor's resident table, max_range, *args, **kw)`` on the mesh's cached scene;
+        ``packet_grid`` adds the table's ``grid`` when the packet kernel is switched on."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        self._need_table(intrinsics, message)
+        if packet_grid:
+            kw["grid"] = self._grid_of(intrinsics, len(poses))
+        return getattr(self.scene_for(mesh), method)(poses, self._resident_table(intrinsics), intrinsics.max_range, *args, **kw)
+
     def scan_poses(self, intrinsics, poses, mesh, want=("t", "point3", "incident_deg")):
         """All poses of a trajectory in one launch, rays generated in the kernel.
 
         Returns (records dict of (P, N, ...) arrays, N).  Only for sensors with a pose-independent
         direction table (IndoorLidar with vertical_degrees); other sensors go pose by pose.
         """
-        from lidar import IndoorLidar
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
-        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
-            raise ValueError("sensor has no pose-independent direction table")
+        self._need_table(intrinsics, "sensor has no pose-independent direction table")
         dirs = self._direction_table(intrinsics)
         scene = self.scene_for(mesh)
         out = scene.scan_poses(poses, dirs, intrinsics.max_range, want=want)
         P, N = poses.shape[0], dirs.shape[0]
         return {k: a.reshape((P, N) + a.shape[1:]) for k, a in out.items()}, N
-
 
     def scan_frames(self, intrinsics, poses, mesh, want=("point3", "sem", "ins")):
         """The whole trajectory straight to the reference's per-pose frames: scan + compaction stay in HBM, only the
@@ -356,44 +369,31 @@ class RaycastEngineHIP(RaycastEngineBase):
         lidarcast.Scene.scan_poses_compact: (K, ...) arrays in np.vstack order + ``counts`` (P,) + ``total``;
         ``split_frames`` turns it into per-pose views.  What the per-waypoint loop of
         s3dis_simulator.py:254-288 produces, for multi-line sensors."""
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
-        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
-            raise ValueError("sensor has no pose-independent direction table")
-        return self.scene_for(mesh).scan_poses_compact(poses, self._resident_table(intrinsics),
-                                                       intrinsics.max_range, want=want,
-                                                       grid=self._grid_of(intrinsics, len(poses)))
+        return self._table_frames("scan_poses_compact", "sensor has no pose-independent direction table",
+                                  intrinsics, poses, mesh, want=want, packet_grid=True)
 
     def scan_noisy_frames(self, intrinsics, poses, mesh, noise, want=("point3", "sem", "ins")):
         """``scan_frames`` with seeded sensor noise drawn in the kernel (lrc_scan_noisy_compact):
         ``noise`` a ``lidarcast.noise.NoiseModel``; pose p is frame ``noise.first_frame + p``, so any subset of a trajectory
         can be scanned again with its exact noise.  Same dict as ``scan_frames``."""
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
-        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
-            raise ValueError("seeded sensor noise needs a sensor with a pose-independent direction table")
-        return self.scene_for(mesh).scan_noisy_compact(poses, self._resident_table(intrinsics), intrinsics.max_range, noise,
-                                                       want=want)
+        return self._table_frames("scan_noisy_compact", "seeded sensor noise needs a sensor with a pose-independent direction table",
+                                  intrinsics, poses, mesh, noise, want=want)
 
     def scan_echo_frames(self, intrinsics, poses, mesh, beam, want=("point3", "sem", "ins")):
         """``scan_frames`` with a diverging beam per table row (lrc_scan_echoes_compact): ``beam`` a
         ``lidarcast.echo.BeamModel``.  A beam yields up to ``beam.max_echoes`` rows, so ``counts`` count echoes; the dict of
         ``scan_frames`` plus, per kept row, ``beam_index`` (the table row), ``echo_index`` (0 = the nearest echo of its beam)
         and ``echo_weight`` (the sub-rays behind the echo).  ``index``, when asked for, is beam_index * max_echoes + echo_index."""
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
-        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
-            raise ValueError("a beam footprint needs a sensor with a pose-independent direction table")
-        return self.scene_for(mesh).scan_echoes_compact(poses, self._resident_table(intrinsics), intrinsics.max_range, beam,
-                                                        want=want)
+        return self._table_frames("scan_echoes_compact", "a beam footprint needs a sensor with a pose-independent direction table",
+                                  intrinsics, poses, mesh, beam, want=want)
 
     def scan_material_frames(self, intrinsics, poses, mesh, materials, want=("point3", "sem", "ins")):
         """``scan_frames`` with surface materials (lrc_scan_materials_compact): ``materials`` a
         ``lidarcast.material.MaterialTable``.  A ray that meets glass or a mirror goes on inside the kernel; the dict of
         ``scan_frames`` plus, per kept row, ``intensity``, ``bounces`` and ``surface_point3`` (``point3`` lies on the original
         beam at the total path length; sem / ins are the final surface's)."""
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
-        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
-            raise ValueError("surface materials need a sensor with a pose-independent direction table")
-        return self.scene_for(mesh).scan_materials_compact(poses, self._resident_table(intrinsics), intrinsics.max_range,
-                                                           materials, want=want)
+        return self._table_frames("scan_materials_compact", "surface materials need a sensor with a pose-independent direction table",
+                                  intrinsics, poses, mesh, materials, want=want)
 
     def scan_mover_frames(self, intrinsics, poses, mesh, movers, mover_poses, want=("point3", "sem", "ins")):
         """``scan_frames`` with moving objects (lrc_scan_movers_compact): ``movers`` a
@@ -401,11 +401,8 @@ class RaycastEngineHIP(RaycastEngineBase):
         (P, M, 12) float32 object-to-world poses, one per scan pose and mover.  The static mesh is traced once and every mover in
         its own frame; the nearest wins.  The dict of ``scan_frames`` plus ``mover``, one uint8 per kept row: 0 for the static
         mesh, m + 1 for mover m (sem / ins / prim are then the mover's own)."""
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
-        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
-            raise ValueError("moving objects need a sensor with a pose-independent direction table")
-        return self.scene_for(mesh).scan_movers_compact(poses, self._resident_table(intrinsics), intrinsics.max_range, movers,
-                                                        mover_poses, want=want)
+        return self._table_frames("scan_movers_compact", "moving objects need a sensor with a pose-independent direction table",
+                                  intrinsics, poses, mesh, movers, mover_poses, want=want)
 
     def _firing_fractions(self, intrinsics):
         """(N,) firing fractions of the sensor's direction table (IndoorLidar.firing_fractions), cached with the table."""
@@ -423,8 +420,8 @@ class RaycastEngineHIP(RaycastEngineBase):
         """(motion records (P, 24), firing fractions (N,), sweep period T) of the moving-sensor sweeps from start_poses[k]
         to end_poses[k]: what ``scan_sweep_frames`` scans, for callers that rescan the same sweeps."""
         from lidarcast import motion_records
-        if not hasattr(intrinsics, "horizontal_res") or hasattr(intrinsics, "swing_amplitude"):
-            raise NotImplementedError("moving-sensor sweeps need a sensor with a pose-independent direction table")
+        self._need_table(intrinsics, "moving-sensor sweeps need a sensor with a pose-independent direction table",
+                         NotImplementedError)
         motion = motion_records(start_poses, end_poses)
         return motion, self._firing_fractions(intrinsics), 1.0 / float(intrinsics.scan_frequency)
 

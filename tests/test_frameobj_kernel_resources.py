@@ -1,36 +1,16 @@
 """CPU: the per-frame object kernels (csrc/lrc_frameobj.hip) as compiled for gfx950 -- no scratch, at least seven waves per SIMD,
 and the sensor-frame coordinate without any fused multiply-add (the bit-exactness of DESIGN.md section 5g rests on it):
 read from the compiler's kernel-resource-usage remarks and from the accumulate kernel's ISA."""
-import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import PKG
+from kernel_resources import usage_of
 
 
 @pytest.fixture(scope="module")
-def compiled(tmp_path_factory):
-    import __graft_entry__ as entry
-    hipcc = entry.HIPCC if os.path.exists(entry.HIPCC) else "hipcc"
-    flags = [f for f in entry.HIP_FLAGS if f not in ("-shared", "-fPIC")]
-    out = tmp_path_factory.mktemp("frameobj_res") / "t.s"
-    r = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-                        os.path.join(PKG, "csrc", "lrc_frameobj.hip"), "-o", str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)",
-                      line)
-        if m and name:
-            res[name][m.group(1).split()[0]] = int(m.group(2))
-    return res, out.read_text()
+def compiled():
+    return usage_of("lrc_frameobj.hip", ("-shared", "-fPIC"), asm=True)
 
 
 def _kernel(res, part):

@@ -1,39 +1,17 @@
 """CPU: register and scratch budgets of the product trace kernels in csrc/lidarcast.hip, read from the compiler's
 kernel-resource-usage remarks.  The quantised pose-batched kernel is sized for 8 waves per SIMD (its launch bound asks
 for them): 64 VGPRs and at most 80 SGPRs -- 82..96 SGPRs admit only 7 waves although the remark still says 8."""
-import os
-import re
-import subprocess
-
 import pytest
 
-from conftest import PKG
+from kernel_resources import usage_of
 
 QUANTISED = "_ZN12_GLOBAL__N_112trace_kernelILi1ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <1, 2, true, false, false, 1>
 FLOAT32 = "_ZN12_GLOBAL__N_112trace_kernelILi1ELi2ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE"     # <1, 2, true, false, false, 0>
 
 
 @pytest.fixture(scope="module")
-def usage(tmp_path_factory):
-    import __graft_entry__ as entry
-    hipcc = entry.HIPCC if os.path.exists(entry.HIPCC) else "hipcc"
-    flags = [f for f in entry.HIP_FLAGS if f != "-shared"]
-    out = tmp_path_factory.mktemp("trace_res") / "t.o"
-    r = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                        os.path.join(PKG, "csrc", "lidarcast.hip"), "-o", str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    res = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split()[0]] = int(m.group(2))
-    return res
+def usage():
+    return usage_of("lidarcast.hip")
 
 
 def test_quantised_trace_kernel_keeps_eight_waves(usage):
