@@ -509,6 +509,47 @@ int lrc_noise_draws(const lrc_noise* noise, uint64_t num_poses, uint64_t rays_pe
                     float* z_el, uint8_t* keep);
 int lrc_noise_table(float* base1536, float* slope1536);
 
+/* ---- noisy moving-sensor sweeps (opt-in) -----------------------------------------------------
+ * The two sensor-side effects above in one scan: every ray is cast from the pose of the sensor at the moment it fires AND
+ * carries the seeded noise of (seed, first_frame + k, i).  Motion records, firing fractions and lrc_noise are those of the
+ * two sections above.  For ray i of sweep k, frame = first_frame + k in 64 bits, every step a separate float64 operation
+ * in this order (csrc/lrc_device.h gen_ray_noisy_sweep; tests/test_noisy_sweep_host.py restates it in numpy):
+ *   1 words    w = the Philox block of (seed, frame, i), formed only if angle_std != 0 or dropout != 0.  The ray is dropped
+ *              iff dropout != 0 and w3 < threshold: never cast, reported as a miss            (the seeded noise's rule)
+ *   2 jitter   angle_std != 0: the jitter step on the float64 table row (a, b, c) with dp = angle_std*z(w1),
+ *              dt = angle_std*z(w2); a row with h == 0 is left as it is                        (the seeded noise's step)
+ *   3 static   v = the dgemm FMA chain of the (jittered) row under the START rotation of motion record k
+ *   4 sweep    s = fire[i]: v' = v rotated by q(s)/|q(s)|, c = c(s) with the -0.0-keeping select; direction =
+ *              float32(v'), origin = float32(c)                                                (the sweep's steps from v on)
+ *   5 range    behind the traversal: the range-filter centre is c(s) in float64, and where range_std != 0 and the ray hit,
+ *              t' = t + float32(range_std) * z(w0); t' <= 0 is no return; point, range filter, min_range and incident
+ *              angle use t' and c(s)
+ *   6 a zero range_std, angle_std or dropout skips its step.
+ * Properties, bit for bit: the all-zero model returns the bytes of lrc_scan_sweeps_*; records whose end is their start, and a
+ * zero fire table, return the bytes of lrc_scan_noisy_* under the start poses (the sweep then adds signed zeros only to a
+ * direction that is never -0.0); P = 6 in one call = P = 2 and then P = 4 with first_frame + 2.
+ *   lrc_scan_noisy_sweeps_dev      device pointers.  The caller vouches for the records and the fire table, as in
+ *                                  lrc_scan_sweeps_dev; the lrc_noise is checked as in lrc_scan_noisy_dev; a call while a
+ *                                  range_noise option is set fails with LRC_ERR_INVALID_ARG.
+ *   lrc_scan_noisy_sweeps_compact  host records and the resident table with its fire table: compacted in HBM exactly like
+ *                                  lrc_scan_table_compact.  Checks the records as lrc_scan_sweeps_compact and the lrc_noise
+ *                                  (for an empty call too); a table without a fire table is refused.
+ *   lrc_noisy_sweep_rays           host, no GPU, compiled from the kernel's own generator: per ray the float32 origin and
+ *                                  direction (rays6; a dropped ray's direction is NaN), the float64 centre c(s) (centres3),
+ *                                  float32(range_std) * z(w0) (range_term; 0 when range_std == 0) and the keep flag (1 = not
+ *                                  dropped).  Any output may be NULL.  Checks the lrc_noise, the records and the fire table
+ *                                  (values in [0, 1)).
+ * min_range and incident_mode apply unchanged. */
+int lrc_scan_noisy_sweeps_dev(lrc_scene* scene, const double* d_motion24, uint64_t num_poses, const double* d_dirs3,
+                              uint64_t rays_per_pose, const double* d_fire, double max_range, const lrc_noise* noise,
+                              const lrc_hits* d_out, void* stream);
+int lrc_scan_noisy_sweeps_compact(lrc_scene* scene, const double* motion24, uint64_t num_poses, const lrc_table* table,
+                                  double max_range, const lrc_noise* noise, const lrc_frames* out, uint64_t capacity,
+                                  uint64_t* out_total);
+int lrc_noisy_sweep_rays(const lrc_noise* noise, const double* motion24, uint64_t num_poses, const double* dirs3,
+                         const double* fire, uint64_t rays_per_pose, float* rays6, double* centres3, float* range_term,
+                         uint8_t* keep);
+
 /* ---- beam footprint and multi-echo returns (opt-in) ------------------------------------------
  * Every other scan casts an infinitely thin ray.  A real beam diverges by a few milliradians; at a table edge or a door
  * frame its footprint straddles two surfaces and the sensor reports two echoes, or one placed on the beam axis.  Here a

@@ -798,11 +798,13 @@ __global__ __launch_bounds__(64) void ray_table_kernel(const double* __restrict_
 //          most E echoes per beam behind the traversal (opt-in; lrc_echo.h)
 //      7 = pose x direction table with surface materials: a ray that meets glass or a mirror is continued from its hit point,
 //          segment by segment, behind the first traversal (opt-in; same ray order as 1; lrc_material.h)
+//      8 = motion record x direction table x firing fractions with the seeded noise of 5: the row is jittered in front of the
+//          dgemm chain, the direction swept behind it (opt-in; same ray order as 1)
 // QN: 1 = walk the quantised node images (32-byte nodes for the per-lane fetches), 2 = walk their
 //     four-wide collapse (64-byte nodes, half the steps); a wave with a ray outside the bound the quantisation margin is
 //     proven for walks the float32 world-space nodes instead
 template <int GEN, int LEAFW, bool UNI, bool SPEC, bool STATS = false, int QN = 0>
-__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4 || GEN == 5 || GEN == 6)) ? 8 : (!STATS && GEN == 7) ? 6 : 1) void trace_kernel(const TraceParams p) {
+__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4 || GEN == 5 || GEN == 6 || GEN == 8)) ? 8 : (!STATS && GEN == 7) ? 6 : 1) void trace_kernel(const TraceParams p) {
     extern __shared__ int s_stack[];   // [stack depth][kTBlock]: one column per lane, conflict free
     const uint32_t tid = threadIdx.x;
     if (GEN == 1 && p.pre.blocks != 0u && p.pre.sharded != 0u) {
@@ -910,6 +912,11 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         const uint64_t pose = gid / p.rays_per_pose;
         const uint64_t i = gid - pose * p.rays_per_pose;
         gen_ray_noisy(p.poses16, p.dirs3, p.noise, pose, i, o, d, cx, cy, cz, live);
+        pose32 = (uint32_t)pose;
+    } else if (GEN == 8) {
+        const uint64_t pose = gid / p.rays_per_pose;
+        const uint64_t i = gid - pose * p.rays_per_pose;
+        gen_ray_noisy_sweep(p.motion24, p.dirs3, p.fire, p.noise, pose, i, o, d, live);
         pose32 = (uint32_t)pose;
     } else if (GEN == 7) {
         const uint64_t pose = gid / p.rays_per_pose;
@@ -1303,7 +1310,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         asm volatile("" : "+s"(tpp));
     }
     const bool tabbed = GEN == 1 && tpp != 0u && tab != nullptr;      // a kernel argument: uniform over the launch
-    if (GEN != 0 && GEN != 4 && !tabbed) {
+    if (GEN != 0 && GEN != 4 && GEN != 8 && !tabbed) {
         // the range-filter centre (the pose's translation, float64) is fetched again here instead of being held in six
         // registers through the traversal; the pointer is made opaque so that the fetch is not merged with gen_ray's
         const double* M = p.poses16;
@@ -1311,7 +1318,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         M += (size_t)pose32 * 16;
         cx = M[3]; cy = M[7]; cz = M[11];
     } else if (GEN != 0) {
-        // formed below: GEN = 4 from the record and the firing fraction, a prepared submit from its pose record
+        // formed below: GEN = 4 and 8 from the record and the firing fraction, a prepared submit from its pose record
     } else if (p.seg_centers3) {
         const double* c = p.seg_centers3 + (size_t)pose32 * 3;      // the centre of this ray's pose (segment)
         cx = c[0]; cy = c[1]; cz = c[2];
@@ -1351,7 +1358,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
             cx = M[3]; cy = M[7]; cz = M[11];
         }
     }
-    if (GEN == 4) {
+    if (GEN == 4 || GEN == 8) {
         // the range-filter centre c(s), float64, formed again from the record and fire[i] (as GEN = 1 fetches the pose's
         // translation again) instead of being held through the traversal; opaque pointers keep the loads from merging
         const double* M = p.motion24;
@@ -1361,7 +1368,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         M += (size_t)pose32 * 24;
         sweep_centre(M, F[gid_w - (uint64_t)pose32 * p.rays_per_pose], cx, cy, cz);
     }
-    if (GEN == 5 && p.noise.range_std != 0.0f && best_slot != 0xFFFFFFFFu) {
+    if ((GEN == 5 || GEN == 8) && p.noise.range_std != 0.0f && best_slot != 0xFFFFFFFFu) {
         // the range draw: the ray's Philox block is formed again here instead of z0 being held through the traversal; a
         // non-positive range is no return
         tbest = noisy_range(p.noise, p.noise.first_frame + pose32, (uint32_t)(gid_w - (uint64_t)pose32 * p.rays_per_pose), tbest);
@@ -2530,7 +2537,7 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
         return 1;
     }
     const bool plain = leafw == kLeafW && uni && !spec && !(qn && wide);
-    if (plain || gen == 2 || gen == 4 || gen == 5 || gen == 6 || gen == 7) return 1;
+    if (plain || gen == 2 || gen == 4 || gen == 5 || gen == 6 || gen == 7 || gen == 8) return 1;
     const bool wide_only = qn && wide && leafw == kLeafW && uni && !spec;
     if (gen == 1) { if (wide_only) LRC_LAB(1, kLeafW, true, false, 2); else LRC_LAB_PICK(1); }
     else { if (wide_only) LRC_LAB(0, kLeafW, true, false, 2); else LRC_LAB_PICK(0); }
@@ -2548,7 +2555,8 @@ static size_t trace_lds_bytes(uint32_t depth) { return (size_t)depth * kTBlock *
 // 3 a grid scan (lrc_scan_grid_*: the per-ray kernel here; the packet kernel in the laboratory build), 4 moving-sensor sweeps
 // (motion record x direction table x firing fractions), 5 pose x direction table with seeded sensor noise (p.noise), 6 pose x
 // direction table x beam offsets, reduced to echoes (p.echo; p.total and p.rays_per_pose count echo records on entry), 7 pose x
-// direction table with surface materials (p.mat).
+// direction table with surface materials (p.mat), 8 noisy moving-sensor sweeps (motion record x direction table x firing
+// fractions with p.noise).
 static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, bool stats = false) {
     p.nodes = s->d_nodes;
     p.tris = s->d_tris;
@@ -2599,7 +2607,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     // is worth more than the balance: measured +1...+16 % for the striped order there, -1...-10 % on the cache-resident
     // scenes (profiles/r03_xcd_striping_sweep.txt).
     constexpr uint64_t kStripeSceneBytes = 192ull << 20;
-    if ((gen == 1 || gen == 4 || gen == 5 || gen == 6 || gen == 7) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
+    if ((gen == 1 || gen == 4 || gen == 5 || gen == 6 || gen == 7 || gen == 8) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
         const uint64_t tpp = p.rays_per_pose / 64;
         if (tpp % 16 == 0) {
             const uint64_t chunk = tpp / 16;
@@ -2652,6 +2660,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     else if (gen == 5) LRC_LAUNCH(5, false);
     else if (gen == 6) LRC_LAUNCH(6, false);
     else if (gen == 7) LRC_LAUNCH(7, false);
+    else if (gen == 8) LRC_LAUNCH(8, false);
     else if (gen == 2) LRC_LAUNCH(2, false);
     else LRC_LAUNCH(0, false);
 #undef LRC_LAUNCH
@@ -2762,6 +2771,24 @@ int lrc_scan_noisy_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const 
     p.dirs3 = d_dirs3;
     scan_fields(p, N, P * N, max_range, d_out);
     return launch_trace(s, p, 5, (hipStream_t)stream);
+}
+
+int lrc_scan_noisy_sweeps_dev(lrc_scene* s, const double* d_motion24, uint64_t P, const double* d_dirs3, uint64_t N,
+                              const double* d_fire, double max_range, const lrc_noise* noise, const lrc_hits* d_out, void* stream) {
+    if (!s || !d_out) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_sweeps_dev: NULL scene or output");
+    if (P && N && (!d_motion24 || !d_dirs3 || !d_fire))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_sweeps_dev: motion24, dirs3 or fire is NULL");
+    if (s->opts.range_noise)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_sweeps_dev: a range_noise option is set (one noise source per call)");
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    TraceParams p{};
+    int rc = noise_params(s->ctx, "lrc_scan_noisy_sweeps_dev", noise, N, &p.noise);
+    if (rc) return rc;
+    p.motion24 = d_motion24;
+    p.dirs3 = d_dirs3;
+    p.fire = d_fire;
+    scan_fields(p, N, P * N, max_range, d_out);
+    return launch_trace(s, p, 8, (hipStream_t)stream);
 }
 
 int lrc_scan_angles_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_angles2,
@@ -4098,7 +4125,7 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
         TraceParams q = p;
         if (q.poses16) q.poses16 = p.poses16 + p0 * 16;
         if (q.motion24) q.motion24 = p.motion24 + p0 * 24;
-        q.noise.first_frame = p.noise.first_frame + p0;      // gen == 5: the chunk's first frame id
+        q.noise.first_frame = p.noise.first_frame + p0;      // gen == 5, 8: the chunk's first frame id
         // (angles2 shares its slot with ray_tab: only lrc_pipe_submit sets a table and it never comes through this chunked
         // path -- a launch with a table must not be given an offset here)
         if (q.angles2) q.angles2 = p.angles2 + r0 * 2;
@@ -4182,7 +4209,7 @@ int scan_compact(lrc_scene* s, TraceParams& p, int gen, uint64_t P, uint64_t N, 
     FrameStage st;
     if ((rc = st.alloc(ctx, *out, P, n))) return rc;
     NoiseStage ns;           // restores the scene's host pointer on every exit
-    if (gen != 5 && (rc = ns.begin(s, n))) return rc;      // (gen 5 draws its own noise and has refused a range_noise option)
+    if (gen != 5 && gen != 8 && (rc = ns.begin(s, n))) return rc;      // (gen 5 and 8 draw their own noise and have refused a range_noise option)
     scan_fields(p, N, n, max_range, nullptr);
     s->cur_grid = grid;
     rc = frames_finish(s, p, gen, st, P, N, out, capacity, out_total);
@@ -4650,6 +4677,62 @@ int lrc_scan_noisy_compact(lrc_scene* s, const double* poses16, uint64_t P, cons
     p.dirs3 = table->d_dirs3;
     return scan_compact(s, p, 5, P, N, max_range, out, capacity, out_total,
                         [&](auto up) { return up(kPoolPoses, poses16, P * 16, &p.poses16); });
+}
+
+int lrc_scan_noisy_sweeps_compact(lrc_scene* s, const double* motion24, uint64_t P, const lrc_table* table, double max_range,
+                                  const lrc_noise* noise, const lrc_frames* out, uint64_t capacity, uint64_t* out_total) {
+    if (out_total) *out_total = 0;
+    if (!s || !out || !table) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_sweeps_compact: NULL scene, table or output");
+    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_sweeps_compact: table and scene belong to different contexts");
+    if (!table->d_fire) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_sweeps_compact: the table has no fire table (lrc_table_set_fire)");
+    if (s->opts.range_noise)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_sweeps_compact: a range_noise option is set (one noise source per call)");
+    const uint64_t N = table->n;
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    TraceParams p{};
+    int rc = noise_params(s->ctx, "lrc_scan_noisy_sweeps_compact", noise, N, &p.noise);      // checked for an empty call too
+    if (rc) return rc;
+    if (!(P * N)) return LRC_OK;      // before motion24 is looked at
+    if (!motion24 || !out->counts) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_sweeps_compact: motion24 or counts is NULL");
+    if ((rc = check_motion("lrc_scan_noisy_sweeps_compact", motion24, P))) return rc;
+    p.dirs3 = table->d_dirs3;
+    p.fire = table->d_fire;
+    return scan_compact(s, p, 8, P, N, max_range, out, capacity, out_total,
+                        [&](auto up) { return up(kPoolPoses, motion24, P * 24, &p.motion24); });
+}
+
+// Host, no GPU: what trace_kernel<8> casts and uses, from the very gen_ray_noisy_sweep, sweep_centre and normal_of it runs.
+int lrc_noisy_sweep_rays(const lrc_noise* noise, const double* motion24, uint64_t P, const double* dirs3, const double* fire,
+                         uint64_t N, float* rays6, double* centres3, float* range_term, uint8_t* keep) {
+    lrcnoise::Params np{};
+    int rc = noise_params_host("lrc_noisy_sweep_rays", noise, N, &np);
+    if (rc) return rc;
+    if (!(P * N)) return LRC_OK;
+    if (!motion24 || !dirs3 || !fire) return fail(LRC_ERR_INVALID_ARG, "lrc_noisy_sweep_rays: motion24, dirs3 or fire is NULL");
+    if ((rc = check_motion("lrc_noisy_sweep_rays", motion24, P))) return rc;
+    for (uint64_t i = 0; i < N; ++i)
+        if (!(fire[i] >= 0.0 && fire[i] < 1.0))     // NaN fails both
+            return fail(LRC_ERR_INVALID_ARG, "lrc_noisy_sweep_rays: fire[" + std::to_string(i) + "] is outside [0, 1)");
+    const float nan32 = lrcnoise::bits_float(0x7FC00000u);
+    for (uint64_t k = 0; k < P; ++k)
+        for (uint64_t i = 0; i < N; ++i) {
+            const uint64_t r = k * N + i;
+            V3 o, d;
+            bool live = true;
+            gen_ray_noisy_sweep(motion24, dirs3, fire, np, k, i, o, d, live);
+            if (rays6) {
+                float* q = rays6 + r * 6;
+                q[0] = o.x; q[1] = o.y; q[2] = o.z;
+                q[3] = live ? d.x : nan32; q[4] = live ? d.y : nan32; q[5] = live ? d.z : nan32;      // a dropped ray has no direction
+            }
+            if (centres3) sweep_centre(motion24 + k * 24, fire[i], centres3[r * 3], centres3[r * 3 + 1], centres3[r * 3 + 2]);
+            if (range_term)      // noisy_range's term: t' = t + range_term
+                range_term[r] = np.range_std != 0.0f
+                                    ? np.range_std * lrcnoise::normal_of(lrcnoise::ray_words(np.seed, np.first_frame + k, (uint32_t)i).w0, np.tab)
+                                    : 0.0f;
+            if (keep) keep[r] = (uint8_t)live;
+        }
+    return LRC_OK;
 }
 
 int lrc_scan_poses_compact(lrc_scene* s, const double* poses16, uint64_t P, const double* dirs3, uint64_t N,

@@ -227,7 +227,7 @@ LRC_DI void gen_ray_angles(const double* poses16, uint64_t pose, double phi, dou
 //            v'_j = v_j + k * (qw * t_j + w_j)
 // v is gen_ray's float64 world direction (dgemm_row): s = 0 adds only signed zeros to it (dgemm_row never yields -0.0), so the
 // static ray comes out bit for bit.
-LRC_DI void sweep_centre(const double* M, double s, double& cx, double& cy, double& cz) {
+LRC_HDI void sweep_centre(const double* M, double s, double& cx, double& cy, double& cz) {
     const double sx = s * M[16], sy = s * M[17], sz = s * M[18];
     cx = sx == 0.0 ? M[3] : M[3] + sx;
     cy = sy == 0.0 ? M[7] : M[7] + sy;
@@ -288,6 +288,49 @@ LRC_DI void gen_ray_noisy(const double* poses16, const double* dirs3, const lrcn
 LRC_DI float noisy_range(const lrcnoise::Params& np, uint64_t frame, uint32_t i, float t) {
     const lrcnoise::Words w = lrcnoise::ray_words(np.seed, frame, i);
     return t + np.range_std * lrcnoise::normal_of(w.w0, np.tab);
+}
+
+// ---- noisy moving-sensor sweeps (lrc_scan_noisy_sweeps_*; include/lidarcast.h "noisy moving-sensor sweeps") ----
+// Ray (k, i) of a noisy sweep: the two generators above, one behind the other.  The jitter acts on the float64 table row in FRONT
+// of the dgemm chain, the sweep on the float64 world direction BEHIND it; every step a separate float64 operation in this order:
+//   words     w = ray_words(seed, first_frame + k, i), formed only if angle_std != 0 or drop_thr != 0; drop_thr != 0 and
+//             w3 < drop_thr: live = false (never cast, reported as a miss)                                    [gen_ray_noisy]
+//   jitter    angle_std != 0: jitter_row(a, b, c, angle_std * z(w1), angle_std * z(w2)); an h == 0 row passes through  [gen_ray_noisy]
+//   static    v = dgemm_row(row, R_start) from motion24[k]
+//   sweep     s = fire[i]: v' = rotate(v, q(s)), origin = float32(c(s)) with the -0.0-keeping select            [gen_ray_sweep]
+// The range draw (noisy_range) and the filter centre (sweep_centre) are formed again behind the traversal.  Zero parameters skip
+// their step (kernel arguments: wave-uniform): the all-zero model is gen_ray_sweep bit for bit; s = 0, or a record whose end is
+// its start, adds signed zeros only to gen_ray_noisy's direction.  Also compiled for the host: lrc_noisy_sweep_rays is this text.
+LRC_HDI void gen_ray_noisy_sweep(const double* motion24, const double* dirs3, const double* fire, const lrcnoise::Params& np,
+                                 uint64_t k, uint64_t i, V3& o, V3& d, bool& live) {
+    const double* M = motion24 + k * 24;
+    const double* dv = dirs3 + i * 3;
+    double a = dv[0], b = dv[1], c = dv[2];
+    if (np.angle_std != 0.0 || np.drop_thr != 0u) {
+        const lrcnoise::Words w = lrcnoise::ray_words(np.seed, np.first_frame + k, (uint32_t)i);
+        if (np.drop_thr != 0u) live = w.w3 >= np.drop_thr;
+        if (np.angle_std != 0.0) {
+            const double dp = np.angle_std * (double)lrcnoise::normal_of(w.w1, np.tab);
+            const double dt = np.angle_std * (double)lrcnoise::normal_of(w.w2, np.tab);
+            lrcnoise::jitter_row(a, b, c, dp, dt);
+        }
+    }
+    const double vx = dgemm_row(a, b, c, M[0], M[1], M[2]);
+    const double vy = dgemm_row(a, b, c, M[4], M[5], M[6]);
+    const double vz = dgemm_row(a, b, c, M[8], M[9], M[10]);
+    const double s = fire[i];
+    const double qw = (1.0 - s) + s * M[12];
+    const double ux = s * M[13], uy = s * M[14], uz = s * M[15];
+    const double n = ((qw * qw + ux * ux) + uy * uy) + uz * uz;
+    const double kk = 2.0 / n;
+    const double tx = uy * vz - uz * vy, ty = uz * vx - ux * vz, tz = ux * vy - uy * vx;
+    const double wx = uy * tz - uz * ty, wy = uz * tx - ux * tz, wz = ux * ty - uy * tx;
+    d.x = (float)(vx + kk * (qw * tx + wx));
+    d.y = (float)(vy + kk * (qw * ty + wy));
+    d.z = (float)(vz + kk * (qw * tz + wz));
+    double cx, cy, cz;
+    sweep_centre(M, s, cx, cy, cz);
+    o.x = (float)cx; o.y = (float)cy; o.z = (float)cz;
 }
 
 // ---- beam footprint (lrc_scan_echoes_*; include/lidarcast.h "beam footprint and multi-echo returns") ----

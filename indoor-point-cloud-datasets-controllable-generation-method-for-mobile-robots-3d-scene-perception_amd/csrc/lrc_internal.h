@@ -188,6 +188,8 @@ int check_mesh(const char* who, const double* verts3, uint64_t V, const int32_t*
 // lrc_noise.hip: checks an lrc_noise for a table of N rays (LRC_ERR_INVALID_ARG, `who` prefixes the message), makes the
 // context's quantile table resident and fills the kernel's parameter block
 int noise_params(lrc_ctx* ctx, const char* who, const lrc_noise* nz, uint64_t N, lrcnoise::Params* out);
+// the same checks and the same block with the HOST copy of the table, for the host twins of the generators (no context, no GPU)
+int noise_params_host(const char* who, const lrc_noise* nz, uint64_t N, lrcnoise::Params* out);
 
 // beam footprint and multi-echo returns.  lrc_echo.hip checks the arguments of lrc_scan_echoes_* and fills an lrcecho::Params;
 // lidarcast.hip, which owns the trace kernel and the frame path, launches (echo_scan_dev) and scans to frames

@@ -72,6 +72,18 @@ int noise_params(lrc_ctx* ctx, const char* who, const lrc_noise* nz, uint64_t N,
     out->drop_thr = lrcnoise::drop_threshold(nz->dropout);
     return LRC_OK;
 }
+
+int noise_params_host(const char* who, const lrc_noise* nz, uint64_t N, lrcnoise::Params* out) {
+    int rc = check_noise(who, nz, N);
+    if (rc) return rc;
+    out->seed = nz->seed;
+    out->first_frame = nz->first_frame;
+    out->angle_std = nz->angle_std;
+    out->tab = host_table();
+    out->range_std = (float)nz->range_std;
+    out->drop_thr = lrcnoise::drop_threshold(nz->dropout);
+    return LRC_OK;
+}
 #pragma GCC visibility pop
 
 extern "C" {

@@ -36,6 +36,7 @@ SYMBOLS = (
     "lrc_table_create", "lrc_table_destroy", "lrc_scan_table_compact",
     "lrc_scan_sweeps_dev", "lrc_table_set_fire", "lrc_scan_sweeps_compact",
     "lrc_scan_noisy_dev", "lrc_scan_noisy_compact", "lrc_noise_draws", "lrc_noise_table",
+    "lrc_scan_noisy_sweeps_dev", "lrc_scan_noisy_sweeps_compact", "lrc_noisy_sweep_rays",
     "lrc_scan_echoes_dev", "lrc_scan_echoes_compact", "lrc_echo_reduce",
     "lrc_material_table_create", "lrc_material_table_destroy", "lrc_scan_materials_dev", "lrc_scan_materials_compact",
     "lrc_material_step",
@@ -275,6 +276,9 @@ def load():
         "lrc_scan_noisy_compact": [vp, vp, u64, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcFrames), u64, C.POINTER(u64)],
         "lrc_noise_draws": [C.POINTER(LrcNoise), u64, u64, vp, vp, vp, vp],
         "lrc_noise_table": [vp, vp],
+        "lrc_scan_noisy_sweeps_dev": [vp, vp, u64, vp, u64, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcHits), vp],
+        "lrc_scan_noisy_sweeps_compact": [vp, vp, u64, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcFrames), u64, C.POINTER(u64)],
+        "lrc_noisy_sweep_rays": [C.POINTER(LrcNoise), vp, u64, vp, vp, u64, vp, vp, vp, vp],
         "lrc_scan_echoes_dev": [vp, vp, u64, vp, u64, vp, C.POINTER(LrcBeam), dbl, C.POINTER(LrcHits), vp, vp],
         "lrc_scan_echoes_compact": [vp, vp, u64, vp, vp, C.POINTER(LrcBeam), dbl, C.POINTER(LrcFrames), vp, u64, C.POINTER(u64)],
         "lrc_echo_reduce": [vp, u64, C.POINTER(LrcBeam), vp, vp],

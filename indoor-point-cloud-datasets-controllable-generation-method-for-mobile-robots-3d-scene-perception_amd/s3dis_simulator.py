@@ -312,18 +312,20 @@ class S3DISSimulator:
             json.dump(summary, fh, indent=2)
         return summary
 
-    def _noise_model(self):
+    def _noise_model(self, nested=False):
         """The NoiseModel of the config key ``noise`` (None without the key): ``seed`` is required; ``range_std`` (m),
         ``angle_std_deg`` and ``dropout`` default to the sensor record's range_noise_std, angle_noise_std (degrees) and
-        dropout_probability.  first_frame = 0: frame p of a run has frame id p."""
-        cfg = self.config.get("noise")
+        dropout_probability.  first_frame = 0: frame p of a run has frame id p.  ``nested``: the same entries under
+        ``motion: {noise: ...}``, the seeded noise of moving-sensor sweeps."""
+        cfg = (self.config.get("motion") or {}).get("noise") if nested else self.config.get("noise")
+        key = "motion.noise" if nested else "noise"
         if cfg is None:
             return None
         if "seed" not in cfg:
-            raise ValueError("the noise key needs a seed")
+            raise ValueError(f"the {key} key needs a seed")
         unknown = set(cfg) - {"seed", "range_std", "angle_std_deg", "dropout"}
         if unknown:
-            raise ValueError(f"unknown entries under the noise key: {sorted(unknown)}")
+            raise ValueError(f"unknown entries under the {key} key: {sorted(unknown)}")
         from lidarcast.noise import NoiseModel
         k = self.lidar_config
         return NoiseModel(seed=int(cfg["seed"]),
@@ -474,7 +476,7 @@ class S3DISSimulator:
         # opt-in moving-sensor sweeps (config key ``motion: {speed: m/s}``): every ray is cast from the pose of the sensor at
         # the moment it fires; frames then carry per-point times.  Without the key nothing changes.
         motion = self.config.get("motion")
-        sweep = None
+        sweep = sweep_noise = None
         if motion is not None and len(waypoints) > 0:
             if dist is not None:
                 raise NotImplementedError("moving-sensor sweeps are not available on a multi-rank process group")
@@ -483,13 +485,18 @@ class S3DISSimulator:
             start_poses = poses_from_waypoints(waypoints)
             end_poses = sweep_end_poses(waypoints, self.lidar_config.scan_frequency, float(motion.get("speed", 0.0)))
             sweep = engine.sweep_inputs(self.lidar_config, start_poses, end_poses)
+            # ... with seeded sensor noise under them (nested key ``motion: {speed, noise: {seed, range_std?, angle_std_deg?,
+            # dropout?}}``, the entries of the noise key below): the row is jittered and the range drawn in the sweep's own
+            # kernel; frame p has frame id p.  Without the nested entry nothing changes.
+            sweep_noise = self._noise_model(nested=True)
         # opt-in seeded sensor noise (config key ``noise: {seed, range_std?, angle_std_deg?, dropout?}``): range noise, angle
         # jitter and dropout drawn in the kernel; frame p of the run has frame id p, so scanning any
         # subset again reproduces it.  Without the key nothing changes.
         noise = self._noise_model() if len(waypoints) > 0 else None
         if noise is not None:
             if motion is not None:
-                raise ValueError("the noise key cannot be combined with moving-sensor sweeps (motion)")
+                raise ValueError("the noise key cannot be combined with moving-sensor sweeps (motion): noise under sweeps is "
+                                 "asked for with the nested key motion: {speed, noise: {seed, ...}}")
             if dist is not None:
                 raise ValueError("the noise key is not available on a multi-rank process group")
             if not batched:
@@ -534,6 +541,9 @@ class S3DISSimulator:
             fr = engine.scan_echo_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, beam, want=want)
         elif noise is not None:
             fr = engine.scan_noisy_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, noise, want=want)
+        elif sweep is not None and sweep_noise is not None:
+            from lidarcast.noise import scan_noisy_sweep_frames
+            fr = scan_noisy_sweep_frames(engine, self.lidar_config, None, None, mesh, sweep_noise, want=want, inputs=sweep)
         elif sweep is not None:
             fr = engine.scan_sweep_frames(self.lidar_config, None, None, mesh, want=want, inputs=sweep)
         elif dist is not None and len(waypoints) > 0:
@@ -585,7 +595,8 @@ class S3DISSimulator:
             else:      # labels on demand: one labels-only scan of the trajectory (of the SAME sweeps), shared by its frames
                 sem_f = ins_f = itertools.repeat(None)
                 src_f = itertools.repeat(_LazyTrajectoryLabels(engine, self.lidar_config, poses_from_waypoints(waypoints),
-                                                               mesh, counts_l, sweep, noise, beam))
+                                                               mesh, counts_l, sweep, noise if sweep is None else sweep_noise,
+                                                               beam))
             if "range_origin_mean" in fr:      # statistics from the device
                 qual = self._quality_from_stats(fr, total, volume)
             else:
@@ -630,6 +641,7 @@ class _LazyTrajectoryLabels:
     def __init__(self, engine, intrinsics, poses, mesh, counts, sweep=None, noise=None, beam=None):
         # sweep: the (motion records, fire table, period) of a moving-sensor scan -- rescanned exactly, never as static poses
         # noise: the NoiseModel of a noisy scan -- rescanned with the same seed and frame ids, never as the clean scan
+        # both: noisy moving-sensor sweeps -- rescanned as such from the same records and model, never as either alone
         self._args = (engine, intrinsics, np.array(poses, dtype=np.float64, copy=True), mesh)
         self._sweep = sweep
         self._noise = noise
@@ -645,6 +657,10 @@ class _LazyTrajectoryLabels:
                 engine, intrinsics, poses, mesh = self._args
                 if self._beam is not None:
                     fr = engine.scan_echo_frames(intrinsics, poses, mesh, self._beam, want=("sem", "ins"))
+                elif self._sweep is not None and self._noise is not None:
+                    from lidarcast.noise import scan_noisy_sweep_frames
+                    fr = scan_noisy_sweep_frames(engine, intrinsics, None, None, mesh, self._noise, want=("sem", "ins"),
+                                                 inputs=self._sweep)
                 elif self._noise is not None:
                     fr = engine.scan_noisy_frames(intrinsics, poses, mesh, self._noise, want=("sem", "ins"))
                 elif self._sweep is not None:
