@@ -10,7 +10,7 @@
 //                        stack in LDS ([depth][lane], conflict free); wave-uniform nodes fetched through the
 //                        scalar cache (s_load); fused hit write-back (t, prim, normal, point, labels, range
 //                        filter, incident angle, packed (t,label) pair, per-wave keep count).
-//                        GEN = rays generated from (pose, direction table) inside the kernel.
+//                        GEN = the ray generator (lrc_gen.h): explicit rays, or rays formed inside the kernel.
 //                        QN = per-lane node fetches from the 32-byte quantised node images (15-bit grid per axis,
 //                        one v_perm_b32 per plane); float32 world-space nodes for the rays the grid is not proven for.
 //   compact_*            stable stream compaction of the fixed-stride records into frame order.
@@ -31,6 +31,7 @@
 #include "lrc_bvh.h"
 #include "lrc_qnodes.h"
 #include "lrc_device.h"
+#include "lrc_gen.h"
 
 using namespace lrcdev;
 
@@ -101,9 +102,9 @@ struct TraceParams {
     const float* slot_box;     // per slot lo xyz, hi xyz of the triangle's vertices
     const float4* prim_plane;  // per caller's triangle row: (v0, label bits), (Ng, 0)
     uint32_t num_nodes;
-    // GEN = 1 with rays_per_pose % 64 == 0: tiles (workgroups) per pose -- a tile then lies in one pose, and the pose and the
+    // kGenPoses with rays_per_pose % 64 == 0: tiles (workgroups) per pose -- a tile then lies in one pose, and the pose and the
     // tile's first in-pose index are scalar arithmetic on the 32-bit tile number.  0: per-lane 64-bit division, as for every other
-    // GEN.  (Placed in the padding behind num_nodes: the argument block keeps its size.)
+    // generator.  (Placed in the padding behind num_nodes: the argument block keeps its size.)
     uint32_t tiles_per_pose;
     const uint4* nodes_q;      // QN kernels: 32-byte quantised nodes (per-lane fetches) ...
     const float4* nodes_n;     // ... and the same boxes as normalised float32 (scalar fetches)
@@ -148,23 +149,23 @@ struct TraceParams {
     } lean;
     float qbase[3], qW[3], qinvW[3];   // normalised coordinate n = (x - qbase) * qinvW in [2, 4); qW = 1 / qinvW = 2^k
     // inputs
-    const float* rays6;        // explicit rays (GEN = false)
+    const float* rays6;        // explicit rays (kGenRays)
     const uint64_t* seg_offsets;   // explicit rays in S segments (poses): (S+1) ray offsets, or NULL
     const double* seg_centers3;    // (S,3) range-filter centres of the segments
     uint32_t num_segments;
     // with line_tiles != 0: the line grouping of the tiles (lrc_device.h, tile_ray: bit 31 = groups of four lines, bits 0-30 =
     // the first line of the other elevation sign).  0: groups of two from line 0.  (In the padding behind num_segments.)
     uint32_t line_group;
-    const double* poses16;     // GEN = 1, 2
-    const double* dirs3;       // GEN = 1: (N,3) sensor-frame direction table
-    // GEN = 2: (P*N,2) noisy (phi, theta) of the dual-axis sensor.  GEN = 1 never reads them, and only GEN = 1 reads the ray
+    const double* poses16;     // kGenPoses, kGenAngles and every generator that scans from poses
+    const double* dirs3;       // kGenPoses: (N,3) sensor-frame direction table
+    // kGenAngles: (P*N,2) noisy (phi, theta) of the dual-axis sensor.  kGenPoses never reads them, and only kGenPoses reads the ray
     // table of a prepared pipeline submit (RayPose below; NULL: none), so the two share one slot: the argument block keeps its
     // size, on which the register allocation of the product kernel has depended before.
     union {
         const double* angles2;
         const float4* ray_tab;
     };
-    const uint8_t* keep_mask;  // GEN = 2, nullable: 0 = ray dropped by the sensor (never cast, reported as a miss)
+    const uint8_t* keep_mask;  // kGenAngles, nullable: 0 = ray dropped by the sensor (never cast, reported as a miss)
     uint32_t* stats;           // STATS build only: kStatsWords counters per ray
     uint64_t rays_per_pose;
     uint64_t total;
@@ -176,15 +177,15 @@ struct TraceParams {
     const float* range_noise;
     int incident_mode;
     lrc_hits out;
-    // GEN = 4 (moving-sensor sweeps, lrc_scan_sweeps_*): (P,24) motion records and the (N) firing fractions of the table
+    // kGenSweeps (moving-sensor sweeps, lrc_scan_sweeps_*): (P,24) motion records and the (N) firing fractions of the table
     const double* motion24;
     const double* fire;
-    // GEN = 5 (seeded sensor noise, lrc_scan_noisy_*): generator parameters and the resident quantile table
+    // kGenNoisy (seeded sensor noise, lrc_scan_noisy_*): generator parameters and the resident quantile table
     lrcnoise::Params noise;
-    // GEN = 6 (beam footprint and multi-echo returns, lrc_scan_echoes_*): the offset table and the reduction's parameters.  For
+    // kGenEchoes (beam footprint and multi-echo returns, lrc_scan_echoes_*): the offset table and the reduction's parameters.  For
     // this generator rays_per_pose and total count LANES (G per beam, lrc_echo.h) in the kernel; launch_trace converts them
     lrcecho::Params echo;
-    // GEN = 7 (surface materials, lrc_scan_materials_*): the resident table, the model's limits and the two per-ray outputs that
+    // kGenMaterials (surface materials, lrc_scan_materials_*): the resident table, the model's limits and the two per-ray outputs that
     // travel beside the record set (lrc_material.h)
     lrcmat::Params mat;
 };
@@ -336,7 +337,7 @@ __device__ __forceinline__ double range_filter(const TraceParams& p, double s, b
 // BY_PRIM: `best_slot` is the caller's triangle ROW (sector_kernel keys rays by (t, row)); labels and the normal then
 // come from the per-row plane table instead of the per-slot arrays -- same values.
 // HAVE_LABEL: the caller has slot_label[best_slot] already (trace_kernel issues the load together with the box clause's).
-// MAT: the intensity column receives the caller's value (the material chain's I, trace_kernel GEN = 7) in the place of |h.n|.
+// MAT: the intensity column receives the caller's value (the material chain's I, trace_kernel kGenMaterials) in the place of |h.n|.
 // GIVEN: the hit was found elsewhere (mover_merge_kernel: the winner among the static scene and the movers): `best_slot` is
 // the triangle ROW to report, slot_label_in its label and n_in the normal to write and to use; no scene array is read.
 // Returns whether the ray is kept.
@@ -345,7 +346,6 @@ __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, u
                                            double cy, double cz, float tbest, uint32_t best_slot, uint32_t slot_label_in = 0u,
                                            bool have_h = false, V3 h_in = V3{0.f, 0.f, 0.f}, float inten_in = 0.f,
                                            V3 n_in = V3{0.f, 0.f, 0.f}) {
-    constexpr int GEN = FILTER_ALWAYS ? 1 : 0;
     const bool lean = FILTER_ALWAYS && !BY_PRIM && p.lean.row != nullptr;    // a kernel argument: wave-uniform
     bool keep = best_slot != 0xFFFFFFFFu;
     float t_out = __builtin_inff();
@@ -374,7 +374,7 @@ __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, u
         px = pp.x; py = pp.y; pz = pp.z;
         // range filter + incident angle in float64 (raycast_engine_cpu.py:95-107)
         const double ex = (double)px - cx, ey = (double)py - cy, ez = (double)pz - cz;
-        const double dist = range_filter<GEN != 0>(p, (ex * ex + ey * ey) + ez * ez, keep);
+        const double dist = range_filter<FILTER_ALWAYS>(p, (ex * ex + ey * ey) + ez * ez, keep);
         if (keep && lean) {           // the lean record: no triangle id, no normal
             t_out = tbest;
             label = HAVE_LABEL ? slot_label_in : p.slot_label[best_slot];
@@ -791,23 +791,16 @@ __global__ __launch_bounds__(64) void ray_table_kernel(const double* __restrict_
     }
 }
 
-// GEN: 0 = explicit rays, 1 = pose x direction table, 2 = pose x per-ray scan angles (dual-axis sensor, opt-in),
-//      4 = motion record x direction table x firing fractions (moving-sensor sweeps, opt-in; same ray order as 1),
-//      5 = pose x direction table with seeded range noise, angle jitter and dropout drawn per ray (opt-in; same ray order as 1)
-//      6 = pose x direction table x offset table: K sub-rays per beam in the G neighbouring lanes of a group, reduced to at
-//          most E echoes per beam behind the traversal (opt-in; lrc_echo.h)
-//      7 = pose x direction table with surface materials: a ray that meets glass or a mirror is continued from its hit point,
-//          segment by segment, behind the first traversal (opt-in; same ray order as 1; lrc_material.h)
-//      8 = motion record x direction table x firing fractions with the seeded noise of 5: the row is jittered in front of the
-//          dgemm chain, the direction swept behind it (opt-in; same ray order as 1)
+// GEN: the ray generator, one of the names of lrc_gen.h (which also states what each implies for the launch and the tail).
 // QN: 1 = walk the quantised node images (32-byte nodes for the per-lane fetches), 2 = walk their
 //     four-wide collapse (64-byte nodes, half the steps); a wave with a ray outside the bound the quantisation margin is
 //     proven for walks the float32 world-space nodes instead
 template <int GEN, int LEAFW, bool UNI, bool SPEC, bool STATS = false, int QN = 0>
-__global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 4 || GEN == 5 || GEN == 6 || GEN == 8)) ? 8 : (!STATS && GEN == 7) ? 6 : 1) void trace_kernel(const TraceParams p) {
+__global__ __launch_bounds__(kTBlock, gen_min_waves(GEN, QN, STATS)) void trace_kernel(const TraceParams p) {
     extern __shared__ int s_stack[];   // [stack depth][kTBlock]: one column per lane, conflict free
+    constexpr bool kCentreFromMotion = gen_centre_from_motion(GEN), kDrawsNoise = gen_draws_noise(GEN);
     const uint32_t tid = threadIdx.x;
-    if (GEN == 1 && p.pre.blocks != 0u && p.pre.sharded != 0u) {
+    if (GEN == kGenPoses && p.pre.blocks != 0u && p.pre.sharded != 0u) {
         if (blockIdx.x < p.pre.blocks) {
             // per-pose counts of the assembled cloud (one thread per pose of ALL ranks), then this workgroup's share
             rebuild_counts(p.pre.rq, blockIdx.x * kTBlock + tid, p.pre.blocks * kTBlock);
@@ -823,7 +816,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
             return;
         }
     } else
-    if (GEN == 1 && p.pre.blocks != 0u) {          // wave-uniform; only the pose-batched scan is ever pipelined
+    if (GEN == kGenPoses && p.pre.blocks != 0u) {          // wave-uniform; only the pose-batched scan is ever pipelined
         if (blockIdx.x < p.pre.blocks) {
             if (p.pre.io.counts) segment_count(p.pre.io, p.pre.tps, p.pre.ntiles, p.pre.nseg, (uint64_t)blockIdx.x * kTBlock + tid,
                                                p.pre.tile_off, nullptr, p.pre.super_total);
@@ -853,11 +846,11 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
 
     // ---- the ray ----
     V3 o, d;
-    V3 inv;                    // safe_inv of d per axis: formed with the ray (GEN = 1 may take it from a prepared table)
+    V3 inv;                    // safe_inv of d per axis: formed with the ray (kGenPoses may take it from a prepared table)
     double cx, cy, cz;
     bool live = true;          // false: not cast at all (dropped by the sensor, or a non-finite ray)
     uint32_t pose32 = 0;
-    if (GEN == 1) {
+    if (GEN == kGenPoses) {
         uint64_t pose, i;
         if (p.tiles_per_pose != 0u) {
             // a tile lies in one pose: pose and in-pose index from the 32-bit tile number, one 32-bit division of
@@ -897,33 +890,33 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
             inv = V3{safe_inv(d.x), safe_inv(d.y), safe_inv(d.z)};
         }
         pose32 = (uint32_t)pose;
-    } else if (GEN == 2) {
+    } else if (GEN == kGenAngles) {
         const uint64_t pose = gid / p.rays_per_pose;
         const double2 a = ((const double2*)p.angles2)[gid];
         gen_ray_angles(p.poses16, pose, a.x, a.y, o, d, cx, cy, cz);
         if (p.keep_mask) live = p.keep_mask[gid] != 0;
         pose32 = (uint32_t)pose;
-    } else if (GEN == 4) {
+    } else if (GEN == kGenSweeps) {
         const uint64_t pose = gid / p.rays_per_pose;
         const uint64_t i = gid - pose * p.rays_per_pose;
         gen_ray_sweep(p.motion24, p.dirs3, p.fire, pose, i, o, d);
         pose32 = (uint32_t)pose;
-    } else if (GEN == 5) {
+    } else if (GEN == kGenNoisy) {
         const uint64_t pose = gid / p.rays_per_pose;
         const uint64_t i = gid - pose * p.rays_per_pose;
         gen_ray_noisy(p.poses16, p.dirs3, p.noise, pose, i, o, d, cx, cy, cz, live);
         pose32 = (uint32_t)pose;
-    } else if (GEN == 8) {
+    } else if (GEN == kGenNoisySweeps) {
         const uint64_t pose = gid / p.rays_per_pose;
         const uint64_t i = gid - pose * p.rays_per_pose;
         gen_ray_noisy_sweep(p.motion24, p.dirs3, p.fire, p.noise, pose, i, o, d, live);
         pose32 = (uint32_t)pose;
-    } else if (GEN == 7) {
+    } else if (GEN == kGenMaterials) {
         const uint64_t pose = gid / p.rays_per_pose;
         double ux, uy, uz;          // the centre is fetched again behind the traversal
         gen_ray(p.poses16, p.dirs3, pose, gid - pose * p.rays_per_pose, o, d, ux, uy, uz);
         pose32 = (uint32_t)pose;
-    } else if (GEN == 6) {
+    } else if (GEN == kGenEchoes) {
         // lane gid = beam * G + k.  64 % G == 0 and a pose is a whole number of groups, so k is the lane's place in its group of
         // the wave, no group straddles a wave, and the `gid >= total` exit above removes whole groups only.  Lanes k >= K are
         // not live: they cast nothing and take part in the reduction as sub-rays without a hit.
@@ -960,7 +953,7 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
 
     uint32_t st_nodes = 0, st_tris = 0, st_uni = 0, st_dead = 0, st_pad = 0;   // STATS build only (lrc_debug_scan_stats)
     live = live & finite_ray(o, d);
-    if (GEN != 1) inv = V3{safe_inv(d.x), safe_inv(d.y), safe_inv(d.z)};
+    if (GEN != kGenPoses) inv = V3{safe_inv(d.x), safe_inv(d.y), safe_inv(d.z)};
 
     // The traversal, once per node image: Q = false walks the float32 world-space nodes with the ray's world-space slab
     // constants; Q = true walks the quantised images with the slab constants in normalised coordinates.  Which boxes
@@ -1299,26 +1292,26 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
     }
 
     // ---- fused write-back ----
-    // prepared submit (GEN = 1 with a ray table): flag and float64 centre come from the pose record again (scalar loads) and the
+    // prepared submit (kGenPoses with a ray table): flag and float64 centre come from the pose record again (scalar loads) and the
     // row's unit direction from the table, in the place of the per-lane fetch of the pose's translation.  Pointer and divisor
     // are made opaque so that nothing of the prologue (the division's reciprocal) is held through the traversal.
     const float4* tab = nullptr;
     uint32_t tpp = 0u;
-    if (GEN == 1) {
+    if (GEN == kGenPoses) {
         tab = p.ray_tab; tpp = p.tiles_per_pose;
         asm volatile("" : "+s"(tab));
         asm volatile("" : "+s"(tpp));
     }
-    const bool tabbed = GEN == 1 && tpp != 0u && tab != nullptr;      // a kernel argument: uniform over the launch
-    if (GEN != 0 && GEN != 4 && GEN != 8 && !tabbed) {
+    const bool tabbed = GEN == kGenPoses && tpp != 0u && tab != nullptr;      // a kernel argument: uniform over the launch
+    if (GEN != kGenRays && !kCentreFromMotion && !tabbed) {
         // the range-filter centre (the pose's translation, float64) is fetched again here instead of being held in six
         // registers through the traversal; the pointer is made opaque so that the fetch is not merged with gen_ray's
         const double* M = p.poses16;
         asm volatile("" : "+s"(M));
         M += (size_t)pose32 * 16;
         cx = M[3]; cy = M[7]; cz = M[11];
-    } else if (GEN != 0) {
-        // formed below: GEN = 4 and 8 from the record and the firing fraction, a prepared submit from its pose record
+    } else if (GEN != kGenRays) {
+        // formed below: kGenSweeps and kGenNoisySweeps from the record and the firing fraction, a prepared submit from its pose record
     } else if (p.seg_centers3) {
         const double* c = p.seg_centers3 + (size_t)pose32 * 3;      // the centre of this ray's pose (segment)
         cx = c[0]; cy = c[1]; cz = c[2];
@@ -1333,8 +1326,8 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
                                               : xcd_tile(wg - p.pre.blocks, gridDim.x - p.pre.blocks);
     uint64_t gid_w = (uint64_t)tile_w * kTBlock + tid;
     uint32_t pu_w = 0u;
-    if (GEN == 1 && tpp != 0u && (p.line_tiles != 0u || tabbed)) pu_w = tile_w / tpp;
-    if (GEN == 1 && tpp != 0u && p.line_tiles != 0u)      // line-group tile: the same mapping as in front of the traversal
+    if (GEN == kGenPoses && tpp != 0u && (p.line_tiles != 0u || tabbed)) pu_w = tile_w / tpp;
+    if (GEN == kGenPoses && tpp != 0u && p.line_tiles != 0u)      // line-group tile: the same mapping as in front of the traversal
         gid_w = (uint64_t)pu_w * p.rays_per_pose + tile_ray(tile_w - pu_w * tpp, tid, p.line_tiles, tpp, p.line_group);
     bool have_h = false;
     V3 h_tab{0.f, 0.f, 0.f};
@@ -1358,8 +1351,8 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
             cx = M[3]; cy = M[7]; cz = M[11];
         }
     }
-    if (GEN == 4 || GEN == 8) {
-        // the range-filter centre c(s), float64, formed again from the record and fire[i] (as GEN = 1 fetches the pose's
+    if (kCentreFromMotion) {
+        // the range-filter centre c(s), float64, formed again from the record and fire[i] (as kGenPoses fetches the pose's
         // translation again) instead of being held through the traversal; opaque pointers keep the loads from merging
         const double* M = p.motion24;
         const double* F = p.fire;
@@ -1368,133 +1361,45 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
         M += (size_t)pose32 * 24;
         sweep_centre(M, F[gid_w - (uint64_t)pose32 * p.rays_per_pose], cx, cy, cz);
     }
-    if ((GEN == 5 || GEN == 8) && p.noise.range_std != 0.0f && best_slot != 0xFFFFFFFFu) {
+    if (kDrawsNoise && p.noise.range_std != 0.0f && best_slot != 0xFFFFFFFFu) {
         // the range draw: the ray's Philox block is formed again here instead of z0 being held through the traversal; a
         // non-positive range is no return
         tbest = noisy_range(p.noise, p.noise.first_frame + pose32, (uint32_t)(gid_w - (uint64_t)pose32 * p.rays_per_pose), tbest);
         if (!(tbest > 0.0f)) best_slot = 0xFFFFFFFFu;
     }
-    if (GEN == 6) {
-        // ---- the beam's K closest hits -> at most E echoes, across the G lanes of the group (lrc_echo.h states the reduction) ----
-        // Every lane of the wave is here: no lane has left since the `gid >= total` exit, which takes whole groups.
-        const uint32_t glog = p.echo.group_log2, G = 1u << glog, k = tid & (G - 1u), base = tid - k;
-        const uint32_t gbits = (1u << G) - 1u;                // G <= 16
-        const float inf = __builtin_inff();
-        const bool hit = best_slot != 0xFFFFFFFFu;
-        const float tk = hit ? tbest : inf;
-        // who is in front of this sub-ray in the order by (t, k), and the range of the one directly in front
-        uint32_t less = 0u;
-        float pred = -inf;
-        for (uint32_t j = 0; j < G; ++j) {
-            const float tj = __shfl(tk, (int)(base + j), 64);
-            const bool front = (tj < inf) & ((tj < tk) | ((tj == tk) & (j < k)));
-            less |= front ? (1u << j) : 0u;
-            pred = front ? max2(pred, tj) : pred;
-        }
-        // a cluster starts at the first hit and wherever the gap to the one in front exceeds the separation
-        const bool start = hit & ((less == 0u) | ((tk - pred) > p.echo.separation));
-        const uint32_t smask = (uint32_t)(__ballot(start) >> base) & gbits;
-        const uint32_t cid = hit ? (uint32_t)__popc(smask & (less | (1u << k))) : 0u;      // 1, 2, ... in ascending order; 0: no hit
-        uint32_t same = 0u;                                                                 // the members of this lane's cluster
-        for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t cj = (uint32_t)__shfl((int)cid, (int)(base + j), 64);
-            same |= ((cj == cid) & (cj != 0u)) ? (1u << j) : 0u;
-        }
-        const uint32_t count = (uint32_t)__popc(same);
-        // the representative (smallest k) of a cluster that is large enough speaks for it; clusters lie in the order one behind
-        // the other, so the echo's number is the number of such representatives in front of this one
-        const bool valid = hit & (same != 0u) & ((same & ((1u << k) - 1u)) == 0u) & (count >= (uint32_t)p.echo.min_count);
-        const uint32_t vmask = (uint32_t)(__ballot(valid) >> base) & gbits;
-        const uint32_t eidx = (uint32_t)__popc(vmask & less);
-        uint32_t src = 0xFFFFFFFFu;                           // lane e < E: the lane of echo e's representative
-        for (uint32_t e = 0; e < (uint32_t)p.echo.max_echoes; ++e) {
-            const uint32_t m = (uint32_t)(__ballot(valid & (eidx == e)) >> base) & gbits;
-            if (k == e && m != 0u) src = base + (uint32_t)__builtin_ctz(m);
-        }
-        const int from = (int)(src != 0xFFFFFFFFu ? src : tid);
-        float t_e = __shfl(tk, from, 64);
-        uint32_t slot_e = (uint32_t)__shfl((int)best_slot, from, 64);
-        const uint32_t label_e = (uint32_t)__shfl((int)best_label, from, 64);
-        uint32_t n_e = (uint32_t)__shfl((int)count, from, 64);
-        if (k >= (uint32_t)p.echo.max_echoes) return;         // the other lanes write nothing
-        if (src == 0xFFFFFFFFu) { t_e = inf; slot_e = 0xFFFFFFFFu; n_e = 0u; }
-        // the record is the AXIS ray's: gen_ray's bits of the unjittered row (the origin is every sub-ray's)
-        const uint64_t beam = gid_w >> glog;
-        {
+    if (GEN == kGenEchoes) {
+        // the beam's K closest hits -> at most E echoes, across the G lanes of the group.  Every lane of the wave is here: no
+        // lane has left since the `gid >= total` exit, which takes whole groups.  The record is the AXIS ray's: gen_ray's bits
+        // of the unjittered row (the origin is every sub-ray's)
+        lrcecho::reduce_lanes(p.echo, tid, gid_w, tbest, best_slot, best_label,
+                              [&](uint64_t beam, uint64_t rec, float t_e, uint32_t slot_e, uint32_t label_e) {
             const double* M = p.poses16;
             asm volatile("" : "+s"(M));
             double ux, uy, uz;
-            gen_ray(M, p.dirs3, pose32, beam - (uint64_t)pose32 * (p.rays_per_pose >> glog), o, d, ux, uy, uz);
-        }
-        const uint64_t rec = beam * (uint32_t)p.echo.max_echoes + k;
-        write_back<true, false, true>(p, rec, tid, o, d, cx, cy, cz, t_e, slot_e, label_e, false, h_tab);
-        if (p.echo.weight) p.echo.weight[rec] = (uint8_t)n_e;
+            gen_ray(M, p.dirs3, pose32, beam - (uint64_t)pose32 * (p.rays_per_pose >> p.echo.group_log2), o, d, ux, uy, uz);
+            write_back<true, false, true>(p, rec, tid, o, d, cx, cy, cz, t_e, slot_e, label_e, false, h_tab);
+        });
         return;
     }
-    if (GEN == 7) {
-        // ---- the chain of segments (lrc_material.h states the step) ----
-        // Behind every traversal a pending lane looks at its closest hit: the surface returns, the chain is cut at the cap, or the
-        // ray goes on as a new segment.  While any lane of the wave goes on (ballot) those lanes traverse again, over the float32
-        // nodes with the clause tested per triangle as the redo route does -- continued rays of a wave share no octant -- and the
-        // finished lanes idle.  Carried: T, g, b and the current (o, d); a finished lane keeps its final slot in best_slot.
-        // A finished lane needs its segment no longer: its origin's registers keep the surface point and d.x the intensity.
-        // need_geom (kernel arguments: uniform over the launch): some output reads I or pp.  Where none does, a lane on a diffuse
-        // surface -- which ends the chain whatever c is -- adds t to T and is done: no normal, no unit direction.
-        const bool need_geom = p.out.intensity != nullptr || p.mat.surface3 != nullptr || p.mat.min_intensity > 0.0f;
-        float T = 0.0f, g = 1.0f;
-        uint32_t b = 0u;
-        bool pend = true;
-        bool touched = false;      // this lane's (o, d) no longer hold the original ray
-        while (true) {
-            bool cont = false;
-            if (pend && best_slot == 0xFFFFFFFFu) pend = false;      // a miss: no return
-            if (pend) {
-                const lrcmat::Record m = lrcmat::record_of(p.mat.table, p.mat.num_classes, best_label & 0xFFFFu);
-                if (m.kind == lrcmat::kDiffuse && !need_geom) {
-                    T = lrcmat::path_add(T, tbest);
-                    pend = false;
-                } else {
-                    float nx, ny, nz, I = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
-                    touched = true;
-                    slot_normal(p.tris[(size_t)best_slot * 3 + 2], nx, ny, nz);
-                    lrcmat::Seg sg{o.x, o.y, o.z, d.x, d.y, d.z, T, g, b};
-                    const int r = lrcmat::step(sg, tbest, nx, ny, nz, m, p.mat.max_bounces, I, sx, sy, sz);
-                    T = sg.T; g = sg.g; b = sg.b;
-                    if (r == lrcmat::kContinue) {
-                        o = V3{sg.ox, sg.oy, sg.oz}; d = V3{sg.dx, sg.dy, sg.dz};
-                        tbest = __builtin_inff(); best_slot = 0xFFFFFFFFu; best_prim = 0xFFFFFFFFu;
-                        cont = finite_ray(o, d);      // a segment that is not finite is a miss, as for every cast
-                    } else {
-                        pend = false;
-                        o = V3{sx, sy, sz}; d.x = I;
-                        if (r == lrcmat::kNoReturn) best_slot = 0xFFFFFFFFu;
-                    }
-                }
+    if (GEN == kGenMaterials) {
+        // the chain of segments behind the first traversal.  The record is the ORIGINAL ray's at the total path length:
+        // gen_ray's bits again, not held through the loop.  A wave none of whose lanes took the step still has it in (o, d), the
+        // registers of the current segment: nothing to form.
+        lrcmat::chain_lanes(p, gid_w, o, d, tbest, best_slot, best_label,
+                            [&](uint32_t slot, float& nx, float& ny, float& nz) { slot_normal(p.tris[(size_t)slot * 3 + 2], nx, ny, nz); },
+                            [&] { best_prim = 0xFFFFFFFFu; traverse(IntTag<0>{}, IntTag<1>{}); },
+                            [&](bool touched, float T, uint32_t slot, uint32_t label, float I) {
+            if (__builtin_amdgcn_ballot_w64(touched) != 0ull) {
+                const double* M = p.poses16;
+                asm volatile("" : "+s"(M));
+                double ux, uy, uz;
+                gen_ray(M, p.dirs3, pose32, gid_w - (uint64_t)pose32 * p.rays_per_pose, o, d, ux, uy, uz);
             }
-            if (__builtin_amdgcn_ballot_w64(cont) == 0ull) break;
-            if (cont) traverse(IntTag<0>{}, IntTag<1>{});
-            // every lane loads its label again, as behind the redo route: it is not held through the traversal
-            best_label = best_slot != 0xFFFFFFFFu ? p.slot_label[best_slot] : 0u;
-        }
-        const float I = d.x, sx = o.x, sy = o.y, sz = o.z;      // of a lane with a return; anything else is not kept
-        if (need_geom && best_slot != 0xFFFFFFFFu && I < p.mat.min_intensity) best_slot = 0xFFFFFFFFu;
-        // the record is the ORIGINAL ray's at the total path length: gen_ray's bits again, not held through the loop.  A wave none
-        // of whose lanes took the step still has it in (o, d), the registers of the current segment: nothing to form.
-        if (__builtin_amdgcn_ballot_w64(touched) != 0ull) {
-            const double* M = p.poses16;
-            asm volatile("" : "+s"(M));
-            double ux, uy, uz;
-            gen_ray(M, p.dirs3, pose32, gid_w - (uint64_t)pose32 * p.rays_per_pose, o, d, ux, uy, uz);
-        }
-        const bool kept = write_back<true, false, true, true>(p, gid_w, tid, o, d, cx, cy, cz, T, best_slot, best_label, false, h_tab, I);
-        if (p.mat.bounces) p.mat.bounces[gid_w] = kept ? (uint8_t)b : (uint8_t)0;
-        if (p.mat.surface3) {
-            float* q = p.mat.surface3 + gid_w * 3;
-            q[0] = kept ? sx : 0.0f; q[1] = kept ? sy : 0.0f; q[2] = kept ? sz : 0.0f;
-        }
+            return write_back<true, false, true, true>(p, gid_w, tid, o, d, cx, cy, cz, T, slot, label, false, h_tab, I);
+        });
         return;
     }
-    write_back<GEN != 0, false, true>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot, best_label, have_h, h_tab);
+    write_back<GEN != kGenRays, false, true>(p, gid_w, tid, o, d, cx, cy, cz, tbest, best_slot, best_label, have_h, h_tab);
     if (STATS) {
         if (p.stats) {
             uint32_t* q = p.stats + gid_w * kStatsWords;
@@ -1504,148 +1409,6 @@ __global__ __launch_bounds__(kTBlock, (QN != 0 && !STATS && (GEN == 1 || GEN == 
 
 }
 
-#ifdef LRC_VARIANTS
-// ---- measured alternative: K rays per lane with private refill (LRC_REFILL=K) -------------
-// One wave owns K consecutive 64-ray tiles of a pose-batched scan; lane l traces rays l, 64+l, 128+l, ... one after the
-// other, starting its next ray the moment the current one is done instead of idling until the slowest lane of the wave
-// has finished ("private refill").  The closest hit (t, slot) of each ray is parked in LDS and the whole write-back
-// runs afterwards, coherently, K passes of 64 lanes.  The next ray's direction is fetched while the current one is
-// traced.  Same arithmetic, same result bytes as trace_kernel (tests/test_parity_gpu.py::
-// test_kernel_variants_are_bit_identical); what changes is the balance of work inside a wave (tools/trav_stats.py:
-// 0.68 -> 0.77 / 0.84 for K = 2 / 4) at the price of (a) refilled lanes restarting at the root while their
-// neighbours are deep in the tree, which takes the wave off the scalar-fetch path, (b) K x 512 B more LDS per wave and
-// 6 more VGPRs, i.e. fewer resident waves.
-// W = resident waves per SIMD the register allocator must leave room for (its natural footprint is 78 / 93 VGPRs for
-// K = 2 / 4, i.e. 6 / 5 waves; 7 waves cost a few spilled registers)
-template <int K, int W>
-__global__ __launch_bounds__(kTBlock, W) void trace_refill_kernel(const TraceParams p, uint32_t depth) {
-    extern __shared__ int s_mem[];                 // [depth][64] stacks | [K][64] {t bits, slot}
-    int* s_stack = s_mem;
-    uint2* s_res = (uint2*)(s_mem + (size_t)depth * 64);
-    const uint32_t tid = threadIdx.x;
-    // the host launches this kernel only when rays_per_pose % (64 K) == 0: a wave's K tiles lie in ONE pose, so the pose
-    // and everything derived from it is wave-uniform (scalar loads, SGPR operands)
-    const uint64_t N = p.rays_per_pose;
-    const uint64_t tile0 = (uint64_t)xcd_tile(blockIdx.x, gridDim.x) * (64u * K);
-    if (tile0 >= p.total) return;
-    const uint64_t pose = tile0 / N;
-    const uint32_t i0 = (uint32_t)(tile0 - pose * N);
-    const double* M = p.poses16 + pose * 16;
-    const uint64_t base = tile0 + tid;
-
-    V3 o, d;
-    RaySlab sl;
-    float tbest;
-    uint32_t best_slot, best_prim;
-    int sp = 0, ref = ~0;
-    int k = 0;
-    double nd0 = 0.0, nd1 = 0.0, nd2 = 0.0;        // next ray's sensor-frame direction, in flight
-
-    auto fetch_next = [&](int kk) {
-        if (kk < K) {
-            const double* dv = p.dirs3 + (size_t)(i0 + (uint32_t)kk * 64u + tid) * 3;
-            nd0 = dv[0]; nd1 = dv[1]; nd2 = dv[2];
-        }
-    };
-    // ray kk from the prefetched direction; false when the lane has no ray kk
-    auto begin = [&](int kk) -> bool {
-        if (kk >= K) return false;
-        d.x = (float)dgemm_row(nd0, nd1, nd2, M[0], M[1], M[2]);
-        d.y = (float)dgemm_row(nd0, nd1, nd2, M[4], M[5], M[6]);
-        d.z = (float)dgemm_row(nd0, nd1, nd2, M[8], M[9], M[10]);
-        o.x = (float)M[3]; o.y = (float)M[7]; o.z = (float)M[11];
-        sl = make_slab(o, d);
-        tbest = __builtin_inff();
-        best_slot = 0xFFFFFFFFu; best_prim = 0xFFFFFFFFu;
-        sp = 0;
-        ref = (p.num_nodes && finite_ray(o, d)) ? 0 : ~0;
-        return true;
-    };
-    fetch_next(0);
-    begin(0);
-    fetch_next(1);
-
-    auto step = [&](const F4 q0, const F4 q1, const F4 q2, const F4 q3) {
-        float n0, f0, n1, f1;
-        slab_interval(sl, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, n0, f0);
-        slab_interval(sl, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, n1, f1);
-        const bool h0 = (n0 <= f0) & (n0 <= tbest);
-        const bool h1 = (n1 <= f1) & (n1 <= tbest);
-        const int r0 = __float_as_int(q3.x), r1 = __float_as_int(q3.y);
-        if (h0 & h1) {
-            const bool first0 = n0 <= n1;
-            s_stack[sp * 64 + tid] = first0 ? r1 : r0;
-            ++sp;
-            ref = first0 ? r0 : r1;
-        } else if (h0) {
-            ref = r0;
-        } else if (h1) {
-            ref = r1;
-        } else if (sp == 0) {
-            ref = ~0;
-        } else {
-            --sp;
-            ref = s_stack[sp * 64 + tid];
-        }
-    };
-    auto leaf = [&](const int lref) {
-        const uint32_t enc = (uint32_t)(~lref);
-        const uint32_t first = enc >> 3, cnt = enc & 7u;
-        for (uint32_t j = 0; j < cnt; ++j) {
-            const uint32_t slot = first + j;
-            const float4* tr = p.tris + (size_t)slot * 3;
-            const float4 a = tr[0], b = tr[1], c = tr[2];
-            const V3 v0{a.x, a.y, a.z}, e1{a.w, b.x, b.y}, e2{b.z, b.w, c.x}, ng{c.y, c.z, c.w};
-            float t;
-            if (tri_hit(o, d, sl, v0, e1, e2, ng, p.slot_box + (size_t)slot * 6, t)) {
-                if (t < tbest) {
-                    tbest = t; best_slot = slot; best_prim = 0xFFFFFFFFu;
-                } else if (t == tbest) {
-                    if (best_prim == 0xFFFFFFFFu) best_prim = p.slot_prim[best_slot];
-                    const uint32_t pr = p.slot_prim[slot];
-                    if (pr < best_prim) { best_slot = slot; best_prim = pr; }
-                }
-            }
-        }
-    };
-
-    while (true) {
-        while (ref >= 0) {
-            const int uref = __builtin_amdgcn_readfirstlane(ref);
-            if (__builtin_amdgcn_ballot_w64(ref != uref) == 0ull) {
-                const float4* n = p.nodes + (size_t)uref * 4;
-                step(ld_uniform(n), ld_uniform(n + 1), ld_uniform(n + 2), ld_uniform(n + 3));
-            } else {
-                const F4* n = (const F4*)(p.nodes + (size_t)ref * 4);
-                step(n[0], n[1], n[2], n[3]);
-            }
-        }
-        leaf(ref);
-        if (sp != 0) {
-            --sp;
-            ref = s_stack[sp * 64 + tid];
-            continue;
-        }
-        // this lane's ray is done: park its hit, start the next one
-        s_res[k * 64 + tid] = make_uint2(__float_as_uint(tbest), best_slot);
-        ++k;
-        if (!begin(k)) break;
-        fetch_next(k + 1);
-    }
-
-    // ---- coherent write-back, one pass per tile ----
-#pragma unroll 1
-    for (int kk = 0; kk < K; ++kk) {
-        const uint64_t gid = base + (uint64_t)kk * 64u;
-        double cx, cy, cz;
-        gen_ray(p.poses16, p.dirs3, pose, i0 + (uint32_t)kk * 64u + tid, o, d, cx, cy, cz);
-        const uint2 r = s_res[kk * 64 + tid];
-        write_back<true>(p, gid, tid, o, d, cx, cy, cz, __uint_as_float(r.x), r.y);
-    }
-}
-
-#include "lrc_sector.h"
-#endif   // LRC_VARIANTS
 #include "lrc_stats.h"
 
 // ---- compaction -------------------------------------------------------------------------------
@@ -1951,30 +1714,6 @@ __global__ __launch_bounds__(kBlock) void prim_scatter_kernel(const RebuildParam
     if (tile0 >= q.ntiles) return;
     rebuild_tiles<R>(q, tile0, q.ntiles, threadIdx.x & 63u);
 }
-
-#ifdef LRC_VARIANTS
-// Bounding sphere of every triangle's axis-aligned box (centre and half diagonal, rounded up): what sector_kernel
-// tests against a packet of rays before it runs the exact ray/triangle test.  Built on first use of the packet kernel.
-__global__ __launch_bounds__(kBlock) void slot_sphere_kernel(const float* __restrict__ slot_box, uint32_t num_slots,
-                                                             float4* __restrict__ sphere) {
-    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
-    if (k >= num_slots) return;
-    const float* bx = slot_box + (size_t)k * 6;
-    float ctr[3];
-    double hd2 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {       // distance from the ROUNDED centre to the farthest corner
-        const double lo = (double)bx[q], hi = (double)bx[3 + q];
-        ctr[q] = (float)(0.5 * (lo + hi));
-        const double cc = (double)ctr[q];
-        const double e = fmax(hi - cc, cc - lo);
-        hd2 += e * e;
-    }
-    const float r = (float)__builtin_sqrt(hd2);
-    sphere[k] = make_float4(ctr[0], ctr[1], ctr[2], __uint_as_float(__float_as_uint(r) + 1u));    // nextafter(r, +inf), r >= 0
-}
-
-#endif   // LRC_VARIANTS
 
 // Per caller's triangle ROW: (v0, label bits), (Ng, 0) -- all a known hit needs to give t again.  Read by the multi-GPU
 // cloud rebuild only (lrc_cloud_from_prims_dev), so it is built from the slot arrays the first time that is called.
@@ -2315,6 +2054,10 @@ bool want_device_build() {
 
 }  // namespace
 
+#ifdef LRC_VARIANTS
+#include "lrc_lab.h"
+#endif
+
 extern "C" {
 
 int lrc_scene_create(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T,
@@ -2451,112 +2194,13 @@ int lrc_scene_export_array(const lrc_scene* cs, int which, void* dst, uint64_t d
     return LRC_OK;
 }
 
-#ifdef LRC_VARIANTS
-// Laboratory build (-DLRC_VARIANTS; tests/test_parity_gpu.py::test_kernel_variants_are_bit_identical, tools/): the measured
-// alternatives of DESIGN.md section 4.1, selected by environment variables.  Every one returns the product kernel's bytes.
-// Returns 1 when no variant is selected (the caller goes on with the product dispatch).
-static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, bool stats, uint64_t nblk, size_t lds,
-                            uint32_t depth) {
-    static const int force_redo = env_int("LRC_DEBUG_FORCE_REDO", 0);
-    static const int leafw = env_int("LRC_LEAFW", kLeafW) == 1 ? 1 : 2, uni = env_int("LRC_UNIFORM", 1), spec = env_int("LRC_SPEC", 0);
-    static const int sector = env_int("LRC_SECTOR", 1), refill = env_int("LRC_REFILL", 0);
-    p.force_redo = (uint32_t)force_redo;
-    // a pipelined launch (lrc_pipe_*) carries leading workgroups that scatter or assemble an earlier scan: only the product
-    // dispatch sizes its grid for them (nblk + p.pre.blocks); the variants below ignore p.pre
-    if (p.pre.blocks != 0u) return 1;
-    const bool qn = s->d_nodes_q != nullptr, wide = s->d_nodes_q4 != nullptr;
-#define LRC_LAB(G, W, U, S, Q) \
-    hipLaunchKernelGGL((trace_kernel<G, W, U, S, false, Q>), dim3((uint32_t)nblk), dim3(kTBlock), lds, st, p)
-#define LRC_LAB_PICK(G)                                                                              \
-    do {                                                                                             \
-        if (spec) { if (leafw == 2) LRC_LAB(G, 2, true, true, 0); else LRC_LAB(G, 1, true, true, 0); } \
-        else if (!uni) { if (leafw == 2) LRC_LAB(G, 2, false, false, 0); else LRC_LAB(G, 1, false, false, 0); } \
-        else { if (qn) LRC_LAB(G, 1, true, false, 1); else LRC_LAB(G, 1, true, false, 0); }     /* leafw == 1 */ \
-    } while (0)
-    if (gen == 3 && sector && !stats) {
-        const lrc_grid& g = *s->cur_grid;
-        SectorParams q{};
-        { int rc = ensure_prim_plane(s, st); if (rc) return rc; }      // the packet kernel keys rays by triangle row
-        p.prim_plane = s->d_prim_plane;
-        q.tp = p;
-        if (!s->d_slot_sphere && s->info.num_slots) {
-            LRC_HIP(hipMalloc((void**)&s->d_slot_sphere, s->info.num_slots * 16));
-            s->info.device_bytes += s->info.num_slots * 16;
-            hipLaunchKernelGGL(slot_sphere_kernel, dim3((uint32_t)blocks_of(s->info.num_slots, kBlock)), dim3(kBlock),
-                               0, st, (const float*)s->d_slot_box, (uint32_t)s->info.num_slots, s->d_slot_sphere);
-        }
-        q.slot_sphere = s->d_slot_sphere;
-        q.H = g.lines; q.W = g.width;
-        static const int nl_env = env_int("LRC_SECTOR_LINES", 0);
-        uint32_t nl = nl_env > 0 ? (uint32_t)nl_env : 8u;
-        if (nl > 8u) nl = 8u;
-        if (nl > g.lines) nl = g.lines;
-        q.nl = nl;
-        q.groups = (g.lines + nl - 1) / nl;
-        q.az0 = (float)g.az0; q.az_step = (float)g.az_step;
-        q.levels = s->info.max_depth + 1u;
-        q.stack_cap = 128u * q.levels;
-        const uint64_t P = p.total / p.rays_per_pose;
-        q.num_packets = P * q.groups * (g.width / 64u);
-        if (q.num_packets > 0x7FFFFFFFull) return fail(LRC_ERR_INVALID_ARG, "too many rays for one launch");
-        const size_t R = (size_t)nl * 64;
-        const size_t lds_s = R * 8 + R * 12 + (size_t)q.levels * 4 + (size_t)q.stack_cap * 4 + kLeafQ * 4 + kPairQ * 8;
-        static const int sdiag = env_int("LRC_SECTOR_DIAG", 0);
-        if (sdiag) {      // work totals of this launch, printed to stderr (tools only)
-            unsigned long long* d = nullptr;
-            LRC_HIP(hipMalloc((void**)&d, kSectorDiagWords * 8));
-            LRC_HIP(hipMemsetAsync(d, 0, kSectorDiagWords * 8, st));
-            q.diag = d;
-            hipLaunchKernelGGL(sector_kernel<true>, dim3((uint32_t)q.num_packets), dim3(64), lds_s, st, q);
-            unsigned long long h[kSectorDiagWords];
-            LRC_HIP(hipStreamSynchronize(st));
-            LRC_HIP(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-            (void)hipFree(d);
-            std::fprintf(stderr, "[sector diag] packets %llu lines/packet %u: node rounds %llu, nodes %llu, leaves %llu, "
-                                 "triangles %llu, pairs %llu, pair rounds %llu, candidate rays %llu, accepted %llu\n",
-                         (unsigned long long)q.num_packets, nl, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-        } else {
-            hipLaunchKernelGGL(sector_kernel<false>, dim3((uint32_t)q.num_packets), dim3(64), lds_s, st, q);
-        }
-        return LRC_OK;
-    }
-    if (gen == 3) gen = 1;
-    if (refill > 1 && gen == 1 && !stats && p.rays_per_pose % (64u * (refill >= 4 ? 4 : 2)) == 0) {
-        const int K = refill >= 4 ? 4 : 2;        // K rays per lane with private refill
-        const uint64_t nb = (p.total + 64ull * K - 1) / (64ull * K);
-        const size_t ldsK = ((size_t)depth * 64 + (size_t)K * 64 * 2) * sizeof(int);
-        static const int rw = env_int("LRC_REFILL_W", 0);
-#define LRC_RF(KK, WW) hipLaunchKernelGGL((trace_refill_kernel<KK, WW>), dim3((uint32_t)nb), dim3(kTBlock), ldsK, st, p, depth)
-        if (K == 4) { if (rw >= 7) LRC_RF(4, 7); else LRC_RF(4, 5); }
-        else { if (rw >= 7) LRC_RF(2, 7); else LRC_RF(2, 6); }
-#undef LRC_RF
-        return LRC_OK;
-    }
-    if (stats) {
-        if (gen == 1 && qn && wide) { hipLaunchKernelGGL((trace_kernel<1, kLeafW, true, false, true, 2>), dim3((uint32_t)nblk), dim3(kTBlock), lds, st, p); return LRC_OK; }
-        return 1;
-    }
-    const bool plain = leafw == kLeafW && uni && !spec && !(qn && wide);
-    if (plain || gen == 2 || gen == 4 || gen == 5 || gen == 6 || gen == 7 || gen == 8) return 1;
-    const bool wide_only = qn && wide && leafw == kLeafW && uni && !spec;
-    if (gen == 1) { if (wide_only) LRC_LAB(1, kLeafW, true, false, 2); else LRC_LAB_PICK(1); }
-    else { if (wide_only) LRC_LAB(0, kLeafW, true, false, 2); else LRC_LAB_PICK(0); }
-#undef LRC_LAB_PICK
-#undef LRC_LAB
-    return LRC_OK;
-}
-#endif   // LRC_VARIANTS
-
 // stack entries a trace needs = deepest leaf depth (one pending sibling per inner level above it), and the LDS that holds them
 static uint32_t trace_stack_depth(const lrc_scene* s) { return s->info.max_depth < 1 ? 1 : s->info.max_depth; }
 static size_t trace_lds_bytes(uint32_t depth) { return (size_t)depth * kTBlock * sizeof(int); }
 
-// One launch of the trace kernel over p.total rays.  gen: 0 explicit rays, 1 pose x direction table, 2 pose x scan angles,
-// 3 a grid scan (lrc_scan_grid_*: the per-ray kernel here; the packet kernel in the laboratory build), 4 moving-sensor sweeps
-// (motion record x direction table x firing fractions), 5 pose x direction table with seeded sensor noise (p.noise), 6 pose x
-// direction table x beam offsets, reduced to echoes (p.echo; p.total and p.rays_per_pose count echo records on entry), 7 pose x
-// direction table with surface materials (p.mat), 8 noisy moving-sensor sweeps (motion record x direction table x firing
-// fractions with p.noise).
+// One launch of the trace kernel over p.total rays.  gen: the generator by its name in lrc_gen.h.  kGenGrid is a grid scan
+// (lrc_scan_grid_*): the per-ray kernel of kGenPoses here, the packet kernel in the laboratory build.  kGenEchoes: p.total and
+// p.rays_per_pose count echo records on entry.
 static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, bool stats = false) {
     p.nodes = s->d_nodes;
     p.tris = s->d_tris;
@@ -2571,7 +2215,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     p.nodes_n4 = s->d_nodes_n4;
     for (int a = 0; a < 3; ++a) { p.qbase[a] = s->qbase[a]; p.qW[a] = s->qW[a]; p.qinvW[a] = s->qinvW[a]; }
     const bool qn = s->d_nodes_q != nullptr;
-    if (gen == 6) {      // the caller counts echo RECORDS (E per beam), the kernel LANES (G per beam, lrc_echo.h)
+    if (gen == kGenEchoes) {      // the caller counts echo RECORDS (E per beam), the kernel LANES (G per beam, lrc_echo.h)
         const uint64_t E = p.echo.max_echoes;
         p.rays_per_pose = (p.rays_per_pose / E) << p.echo.group_log2;
         p.total = (p.total / E) << p.echo.group_log2;
@@ -2588,7 +2232,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     if (nblk + p.pre.blocks > 0x7FFFFFFFull) return fail(LRC_ERR_INVALID_ARG, "too many rays for one launch");
     // pose-batched scans whose poses are whole tiles: the kernel forms pose and in-pose index from the tile number (in 32 bits:
     // poses of less than 2^32 rays)
-    p.tiles_per_pose = ((gen == 1 || gen == 3) && p.rays_per_pose % kTBlock == 0 && p.rays_per_pose <= 0xFFFFFFFFull)
+    p.tiles_per_pose = (gen_pose_is_tiles(gen) && p.rays_per_pose % kTBlock == 0 && p.rays_per_pose <= 0xFFFFFFFFull)
                            ? (uint32_t)(p.rays_per_pose / kTBlock) : 0u;
     // two-line tiles: lean record sets only (the serial calls' tile_count is per 64 consecutive outputs), and the counters of
     // the instrumented kernel, which has no tile_count
@@ -2607,20 +2251,13 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     // is worth more than the balance: measured +1...+16 % for the striped order there, -1...-10 % on the cache-resident
     // scenes (profiles/r03_xcd_striping_sweep.txt).
     constexpr uint64_t kStripeSceneBytes = 192ull << 20;
-    if ((gen == 1 || gen == 4 || gen == 5 || gen == 6 || gen == 7 || gen == 8) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
+    if (gen_table_order(gen) && p.rays_per_pose % 64 == 0 && s->info.device_bytes <= kStripeSceneBytes) {
         const uint64_t tpp = p.rays_per_pose / 64;
         if (tpp % 16 == 0) {
             const uint64_t chunk = tpp / 16;
             if (chunk >= 16 && (chunk & (chunk - 1)) == 0) { uint32_t k = 0; while ((1ull << k) < chunk) ++k; p.tile_chunk_log2 = k + 1; }
         }
     }
-#ifdef LRC_VARIANTS
-    {   // A/B knob (tools/chunk_sweep*.sh): LRC_TILE_CHUNK = n (power of two) tiles per chunk, -1 = contiguous ranges
-        static const int tc = env_int("LRC_TILE_CHUNK", 0);
-        if (tc < 0) p.tile_chunk_log2 = 0;
-        if (tc > 0 && (tc & (tc - 1)) == 0) { uint32_t k = 0; while ((1 << k) < tc) ++k; p.tile_chunk_log2 = k + 1; }
-    }
-#endif
 #ifdef LRC_VARIANTS
     {
         const int rc = launch_trace_lab(s, p, gen, st, stats, nblk, lds, depth);
@@ -2630,7 +2267,7 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
         }
     }
 #endif
-    if (gen == 3) gen = 1;
+    if (gen == kGenGrid) gen = kGenPoses;
     // Launch chain.  Every product trace launch signs the context's signal word when its last workgroup starts.  A launch
     // that goes to ANOTHER stream than the previous one is held until that signature is there: the caller keeps two scans
     // in flight (two streams, two record sets), so instead of both launches dispatching side by side and ending together --
@@ -2650,25 +2287,32 @@ static int launch_trace(lrc_scene* s, TraceParams& p, int gen, hipStream_t st, b
     }
 #define LRC_LAUNCH_Q(G, S, Q) \
     hipLaunchKernelGGL((trace_kernel<G, kLeafW, true, false, S, Q>), dim3((uint32_t)(nblk + p.pre.blocks)), dim3(kTBlock), lds, st, p)
-#define LRC_LAUNCH(G, S) do { if (qn) LRC_LAUNCH_Q(G, S, 1); else LRC_LAUNCH_Q(G, S, 0); } while (0)      // quantised or float32 nodes
+#define LRC_LAUNCH(G, S) case G: if (qn) LRC_LAUNCH_Q(G, S, 1); else LRC_LAUNCH_Q(G, S, 0); break      // quantised or float32 nodes
     if (stats) {   // per-ray traversal counters (lrc_debug_scan_stats)
-        if (gen == 1) LRC_LAUNCH(1, true);
-        else if (gen == 0) LRC_LAUNCH(0, true);
-        else return fail(LRC_ERR_INVALID_ARG, "traversal statistics are not available for the scan-angle generator");
-    } else if (gen == 1) LRC_LAUNCH(1, false);
-    else if (gen == 4) LRC_LAUNCH(4, false);
-    else if (gen == 5) LRC_LAUNCH(5, false);
-    else if (gen == 6) LRC_LAUNCH(6, false);
-    else if (gen == 7) LRC_LAUNCH(7, false);
-    else if (gen == 8) LRC_LAUNCH(8, false);
-    else if (gen == 2) LRC_LAUNCH(2, false);
-    else LRC_LAUNCH(0, false);
+        switch (gen) {
+            LRC_LAUNCH(kGenPoses, true);
+            LRC_LAUNCH(kGenRays, true);
+            default: return fail(LRC_ERR_INVALID_ARG, "traversal statistics are not available for the scan-angle generator");
+        }
+    } else {
+        switch (gen) {
+            LRC_LAUNCH(kGenRays, false);
+            LRC_LAUNCH(kGenPoses, false);
+            LRC_LAUNCH(kGenAngles, false);
+            LRC_LAUNCH(kGenSweeps, false);
+            LRC_LAUNCH(kGenNoisy, false);
+            LRC_LAUNCH(kGenEchoes, false);
+            LRC_LAUNCH(kGenMaterials, false);
+            LRC_LAUNCH(kGenNoisySweeps, false);
+            default: return fail(LRC_ERR_INTERNAL, "launch_trace: unknown ray generator");
+        }
+    }
 #undef LRC_LAUNCH
 #undef LRC_LAUNCH_Q
     LRC_HIP(hipGetLastError());
     if (p.chain_word) { cx_->chain_seq = p.chain_seq; cx_->chain_stream = st; }
     s->launches += 1;
-    s->rays += gen == 6 ? (p.total >> p.echo.group_log2) * p.echo.subrays : p.total;      // echoes: the sub-rays cast, not the lanes
+    s->rays += gen == kGenEchoes ? (p.total >> p.echo.group_log2) * p.echo.subrays : p.total;      // echoes: the sub-rays cast, not the lanes
     return LRC_OK;
 }
 
@@ -2677,8 +2321,8 @@ int lrc_scene_get_occupancy(const lrc_scene* s, int* waves_per_cu, int* vgprs, i
     LRC_HIP(hipSetDevice(s->ctx->device));
     const size_t lds = trace_lds_bytes(trace_stack_depth(s));
     // the pose-batched product kernel this scene's scans run: over quantised nodes, or float32 ones
-    const void* const kernel = s->d_nodes_q ? reinterpret_cast<const void*>(&trace_kernel<1, kLeafW, true, false, false, 1>)
-                                            : reinterpret_cast<const void*>(&trace_kernel<1, kLeafW, true, false, false>);
+    const void* const kernel = s->d_nodes_q ? reinterpret_cast<const void*>(&trace_kernel<kGenPoses, kLeafW, true, false, false, 1>)
+                                            : reinterpret_cast<const void*>(&trace_kernel<kGenPoses, kLeafW, true, false, false>);
     int blocks = 0;
     hipFuncAttributes attr;
     LRC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, kTBlock, lds));
@@ -2709,7 +2353,7 @@ int lrc_cast_dev(lrc_scene* s, const float* d_rays6, uint64_t n, const double* c
     p.rays6 = d_rays6;
     scan_fields(p, n, n, max_range, d_out, center3 != nullptr);
     if (center3) { p.cx = center3[0]; p.cy = center3[1]; p.cz = center3[2]; }
-    return launch_trace(s, p, 0, (hipStream_t)stream);
+    return launch_trace(s, p, kGenRays, (hipStream_t)stream);
 }
 
 int lrc_cast_segments_dev(lrc_scene* s, const float* d_rays6, uint64_t n, const uint64_t* d_seg_offsets,
@@ -2726,7 +2370,7 @@ int lrc_cast_segments_dev(lrc_scene* s, const float* d_rays6, uint64_t n, const 
     p.seg_centers3 = d_centers3;
     p.num_segments = (uint32_t)num_segments;
     scan_fields(p, n, n, max_range, d_out);
-    return launch_trace(s, p, 0, (hipStream_t)stream);
+    return launch_trace(s, p, kGenRays, (hipStream_t)stream);
 }
 
 int lrc_scan_poses_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_dirs3,
@@ -2739,7 +2383,7 @@ int lrc_scan_poses_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const 
     p.poses16 = d_poses16;
     p.dirs3 = d_dirs3;
     scan_fields(p, N, P * N, max_range, d_out);
-    return launch_trace(s, p, 1, (hipStream_t)stream);
+    return launch_trace(s, p, kGenPoses, (hipStream_t)stream);
 }
 
 int lrc_scan_sweeps_dev(lrc_scene* s, const double* d_motion24, uint64_t P, const double* d_dirs3, const double* d_fire,
@@ -2753,7 +2397,7 @@ int lrc_scan_sweeps_dev(lrc_scene* s, const double* d_motion24, uint64_t P, cons
     p.dirs3 = d_dirs3;
     p.fire = d_fire;
     scan_fields(p, N, P * N, max_range, d_out);
-    return launch_trace(s, p, 4, (hipStream_t)stream);
+    return launch_trace(s, p, kGenSweeps, (hipStream_t)stream);
 }
 
 int lrc_scan_noisy_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N, double max_range,
@@ -2770,7 +2414,7 @@ int lrc_scan_noisy_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const 
     p.poses16 = d_poses16;
     p.dirs3 = d_dirs3;
     scan_fields(p, N, P * N, max_range, d_out);
-    return launch_trace(s, p, 5, (hipStream_t)stream);
+    return launch_trace(s, p, kGenNoisy, (hipStream_t)stream);
 }
 
 int lrc_scan_noisy_sweeps_dev(lrc_scene* s, const double* d_motion24, uint64_t P, const double* d_dirs3, uint64_t N,
@@ -2788,7 +2432,7 @@ int lrc_scan_noisy_sweeps_dev(lrc_scene* s, const double* d_motion24, uint64_t P
     p.dirs3 = d_dirs3;
     p.fire = d_fire;
     scan_fields(p, N, P * N, max_range, d_out);
-    return launch_trace(s, p, 8, (hipStream_t)stream);
+    return launch_trace(s, p, kGenNoisySweeps, (hipStream_t)stream);
 }
 
 int lrc_scan_angles_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const double* d_angles2,
@@ -2802,7 +2446,7 @@ int lrc_scan_angles_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const
     p.angles2 = d_angles2;
     p.keep_mask = d_keep;
     scan_fields(p, N, P * N, max_range, d_out);
-    return launch_trace(s, p, 2, (hipStream_t)stream);
+    return launch_trace(s, p, kGenAngles, (hipStream_t)stream);
 }
 
 static int check_grid(const char* who, const lrc_grid* g, uint64_t N) {
@@ -2829,7 +2473,7 @@ int lrc_scan_grid_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const d
     p.dirs3 = d_dirs3;
     scan_fields(p, N, P * N, max_range, d_out);
     s->cur_grid = grid;
-    rc = launch_trace(s, p, 3, (hipStream_t)stream);
+    rc = launch_trace(s, p, kGenGrid, (hipStream_t)stream);
     s->cur_grid = nullptr;
     return rc;
 }
@@ -2845,7 +2489,7 @@ int echo_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const doubl
     p.dirs3 = d_dirs3;
     p.echo = ep;
     scan_fields(p, N * ep.max_echoes, P * N * ep.max_echoes, max_range, d_out);
-    return launch_trace(s, p, 6, st);
+    return launch_trace(s, p, kGenEchoes, st);
 }
 
 // The trace launch of lrc_scan_materials_dev, whose arguments lrc_material.hip has checked (declared in lrc_internal.h): mp.table,
@@ -2857,7 +2501,7 @@ int material_scan_dev(lrc_scene* s, const double* d_poses16, uint64_t P, const d
     p.dirs3 = d_dirs3;
     p.mat = mp;
     scan_fields(p, N, P * N, max_range, d_out);
-    return launch_trace(s, p, 7, st);
+    return launch_trace(s, p, kGenMaterials, st);
 }
 
 // ---- host-pointer convenience wrappers ---------------------------------------------------------
@@ -3437,7 +3081,7 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
         p.pre.lean = pipe_lean(pp, prev);
     }
     LRC_HIP(hipEventRecord(pp->ev_t0[set], T));
-    rc = launch_trace(s, p, 1, T);
+    rc = launch_trace(s, p, kGenPoses, T);
     if (rc) return rc;
     LRC_HIP(hipEventRecord(pp->ev_trace[set], T));
     pp->line_last = p.line_tiles;
@@ -3596,7 +3240,7 @@ int lrc_pipe_submit_sharded(lrc_pipe* pp, const double* d_poses16, uint64_t P, c
         p.pre.blocks = (uint32_t)blocks;
     }
     LRC_HIP(hipEventRecord(pp->ev_t0[set], T));
-    rc = launch_trace(s, p, 1, T);
+    rc = launch_trace(s, p, kGenPoses, T);
     if (rc) return rc;
     LRC_HIP(hipEventRecord(pp->ev_trace[set], T));
     if (assemble) pp->read_by[(assemble->own_ticket - 1) % lrc_pipe::kSets] = k + 1;
@@ -4067,8 +3711,9 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
     // stage (67 MB at 50-56 GB/s for C3): it starts as soon as a few poses are traced, and the later, larger chunks are ready
     // before the copy engine asks for them (C3: 1.48 ms against 1.53 for four equal chunks; tools/chunk_scheme_sweep.sh,
     // profiles/r03_chunk_schemes.txt).  Equal chunks for short trajectories.
-    if (gen == 6) chunks = 1;      // echoes: the weight rows are gathered from ONE packed run of compacted rows (echo_scan_compact)
-    if (gen == 7) chunks = 1;      // materials: likewise for intensity, bounces and surface points (material_scan_compact)
+    // echoes: the weight rows are gathered from ONE packed run of compacted rows (echo_scan_compact); materials: likewise for
+    // intensity, bounces and surface points (material_scan_compact)
+    if (gen_frames_one_chunk(gen)) chunks = 1;
     bool graded = chunks == 4 && P >= 8;
     uint32_t ends32[8] = {4, 16, 32, 32, 32, 32, 32, 32};       // chunk ends in 32nds of the trajectory
     if (graded) chunks = 3;
@@ -4125,7 +3770,7 @@ int frames_finish(lrc_scene* s, TraceParams& p, int gen, FrameStage& st, uint64_
         TraceParams q = p;
         if (q.poses16) q.poses16 = p.poses16 + p0 * 16;
         if (q.motion24) q.motion24 = p.motion24 + p0 * 24;
-        q.noise.first_frame = p.noise.first_frame + p0;      // gen == 5, 8: the chunk's first frame id
+        q.noise.first_frame = p.noise.first_frame + p0;      // the generators that draw noise: the chunk's first frame id
         // (angles2 shares its slot with ray_tab: only lrc_pipe_submit sets a table and it never comes through this chunked
         // path -- a launch with a table must not be given an offset here)
         if (q.angles2) q.angles2 = p.angles2 + r0 * 2;
@@ -4209,7 +3854,7 @@ int scan_compact(lrc_scene* s, TraceParams& p, int gen, uint64_t P, uint64_t N, 
     FrameStage st;
     if ((rc = st.alloc(ctx, *out, P, n))) return rc;
     NoiseStage ns;           // restores the scene's host pointer on every exit
-    if (gen != 5 && gen != 8 && (rc = ns.begin(s, n))) return rc;      // (gen 5 and 8 draw their own noise and have refused a range_noise option)
+    if (!gen_draws_noise(gen) && (rc = ns.begin(s, n))) return rc;      // (those draw their own noise and have refused a range_noise option)
     scan_fields(p, N, n, max_range, nullptr);
     s->cur_grid = grid;
     rc = frames_finish(s, p, gen, st, P, N, out, capacity, out_total);
@@ -4230,7 +3875,7 @@ int scan_compact_impl(lrc_scene* s, const double* poses16, uint64_t P, const dou
     LRC_HIP(hipSetDevice(s->ctx->device));
     TraceParams p{};
     p.dirs3 = d_dirs3;
-    return scan_compact(s, p, grid ? 3 : 1, P, N, max_range, out, capacity, out_total, [&](auto up) {
+    return scan_compact(s, p, grid ? kGenGrid : kGenPoses, P, N, max_range, out, capacity, out_total, [&](auto up) {
         int rc = up(kPoolPoses, poses16, P * 16, &p.poses16);
         if (rc || d_dirs3) return rc;
         return up(kPoolDirs, dirs3, N * 3, &p.dirs3);
@@ -4337,7 +3982,7 @@ int echo_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const lrc
     p.echo = ep;
     scan_fields(p, NE, n, max_range, nullptr);
     uint64_t total = 0;
-    rc = frames_finish(s, p, 6, st, P, NE, out, capacity, &total);
+    rc = frames_finish(s, p, kGenEchoes, st, P, NE, out, capacity, &total);
     if (out_total) *out_total = total;
     if (rc == LRC_OK && weight_rows && total) {
         const GatherColumn col{ep.weight, weight_rows, 1, 1};
@@ -4387,7 +4032,7 @@ int material_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const
     p.mat = mp;
     scan_fields(p, N, n, max_range, nullptr);
     uint64_t total = 0;
-    rc = frames_finish(s, p, 7, st, P, N, out, capacity, &total);
+    rc = frames_finish(s, p, kGenMaterials, st, P, N, out, capacity, &total);
     if (out_total) *out_total = total;
     if (rc == LRC_OK && gather && total) {
         const GatherColumn cols[3] = {{st.rec.intensity, intensity_rows, 4, 1}, {mp.bounces, bounces_rows, 1, 1}, {mp.surface3, surface_rows, 4, 3}};
@@ -4407,7 +4052,7 @@ int cast_plain(lrc_scene* sc, const float* d_rays6, const uint8_t* d_keep, uint6
     scan_fields(p, n, n, (double)__builtin_inff(), &out, false);
     const lrc_scan_options saved = sc->opts;
     sc->opts = lrc_scan_options{};
-    const int rc = launch_trace(sc, p, 0, st);
+    const int rc = launch_trace(sc, p, kGenRays, st);
     sc->opts = saved;
     return rc;
 }
@@ -4427,7 +4072,7 @@ int movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint
         p.poses16 = d_poses16;
         p.dirs3 = d_dirs3;
         scan_fields(p, N, n, max_range, d_out);
-        const int rc = launch_trace(s, p, 1, st);
+        const int rc = launch_trace(s, p, kGenPoses, st);
         if (rc) return rc;
         if (d_mover) LRC_HIP(hipMemsetAsync(d_mover, 0, n, st));
         return LRC_OK;
@@ -4656,7 +4301,7 @@ int lrc_scan_sweeps_compact(lrc_scene* s, const double* motion24, uint64_t P, co
     TraceParams p{};
     p.dirs3 = table->d_dirs3;
     p.fire = table->d_fire;
-    return scan_compact(s, p, 4, P, N, max_range, out, capacity, out_total,
+    return scan_compact(s, p, kGenSweeps, P, N, max_range, out, capacity, out_total,
                         [&](auto up) { return up(kPoolPoses, motion24, P * 24, &p.motion24); });
 }
 
@@ -4675,7 +4320,7 @@ int lrc_scan_noisy_compact(lrc_scene* s, const double* poses16, uint64_t P, cons
     if (!(P * N)) return LRC_OK;
     if (!poses16 || !out->counts) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_compact: poses16 or counts is NULL");
     p.dirs3 = table->d_dirs3;
-    return scan_compact(s, p, 5, P, N, max_range, out, capacity, out_total,
+    return scan_compact(s, p, kGenNoisy, P, N, max_range, out, capacity, out_total,
                         [&](auto up) { return up(kPoolPoses, poses16, P * 16, &p.poses16); });
 }
 
@@ -4697,11 +4342,11 @@ int lrc_scan_noisy_sweeps_compact(lrc_scene* s, const double* motion24, uint64_t
     if ((rc = check_motion("lrc_scan_noisy_sweeps_compact", motion24, P))) return rc;
     p.dirs3 = table->d_dirs3;
     p.fire = table->d_fire;
-    return scan_compact(s, p, 8, P, N, max_range, out, capacity, out_total,
+    return scan_compact(s, p, kGenNoisySweeps, P, N, max_range, out, capacity, out_total,
                         [&](auto up) { return up(kPoolPoses, motion24, P * 24, &p.motion24); });
 }
 
-// Host, no GPU: what trace_kernel<8> casts and uses, from the very gen_ray_noisy_sweep, sweep_centre and normal_of it runs.
+// Host, no GPU: what trace_kernel<kGenNoisySweeps> casts and uses, from the very gen_ray_noisy_sweep, sweep_centre and normal_of it runs.
 int lrc_noisy_sweep_rays(const lrc_noise* noise, const double* motion24, uint64_t P, const double* dirs3, const double* fire,
                          uint64_t N, float* rays6, double* centres3, float* range_term, uint8_t* keep) {
     lrcnoise::Params np{};
@@ -4761,7 +4406,7 @@ int lrc_scan_angles_compact(lrc_scene* s, const double* poses16, uint64_t P, con
         return fail(LRC_ERR_INVALID_ARG, "lrc_scan_angles_compact: poses16, angles2 or counts is NULL");
     LRC_HIP(hipSetDevice(s->ctx->device));
     TraceParams p{};
-    return scan_compact(s, p, 2, P, N, max_range, out, capacity, out_total, [&](auto up) {
+    return scan_compact(s, p, kGenAngles, P, N, max_range, out, capacity, out_total, [&](auto up) {
         int rc;
         if ((rc = up(kPoolPoses, poses16, P * 16, &p.poses16)) || (rc = up(kPoolAngles, angles2, n * 2, &p.angles2))) return rc;
         return keep ? up(kPoolKeep, keep, n, &p.keep_mask) : LRC_OK;
@@ -4778,7 +4423,7 @@ int lrc_scan_rays_compact(lrc_scene* s, const float* rays6, const uint8_t* keep,
         return fail(LRC_ERR_INVALID_ARG, "lrc_scan_rays_compact: rays6, centers3 or counts is NULL");
     LRC_HIP(hipSetDevice(s->ctx->device));
     TraceParams p{};
-    return scan_compact(s, p, 0, P, N, max_range, out, capacity, out_total, [&](auto up) {
+    return scan_compact(s, p, kGenRays, P, N, max_range, out, capacity, out_total, [&](auto up) {
         int rc;
         if ((rc = up(kPoolRays, rays6, n * 6, &p.rays6)) || (rc = up(kPoolCen, centers3, P * 3, &p.seg_centers3))) return rc;
         return keep ? up(kPoolKeep, keep, n, &p.keep_mask) : LRC_OK;
@@ -4805,7 +4450,7 @@ int lrc_debug_scan_stats(lrc_scene* s, const double* poses16, uint64_t P, const 
     // LRC_STATS_TILE_LINES=4 with LRC_STATS_LINE_SPLIT=s: groups of four lines on either side of line s
     p.line_tiles = kTBlock == 64 ? line_tiles_for((uint64_t)env_int("LRC_STATS_LINE_WIDTH", 0), N) : 0u;
     p.line_group = line_group_for((uint32_t)env_int("LRC_STATS_LINE_SPLIT", 0), (uint32_t)env_int("LRC_STATS_TILE_LINES", 2));
-    if ((rc = launch_trace(s, p, 1, nullptr, true))) return rc;
+    if ((rc = launch_trace(s, p, kGenPoses, nullptr, true))) return rc;
     LRC_HIP(hipDeviceSynchronize());
     LRC_HIP(hipMemcpy(stats, ds.p, n * kStatsWords * 4, hipMemcpyDeviceToHost));
     return LRC_OK;

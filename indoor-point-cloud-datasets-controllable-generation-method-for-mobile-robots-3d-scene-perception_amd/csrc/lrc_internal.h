@@ -141,7 +141,7 @@ struct lrc_scene {
     float4* d_nodes_n4 = nullptr;
     uint64_t num_nodes4 = 0;
     float qbase[3] = {0, 0, 0}, qW[3] = {1, 1, 1}, qinvW[3] = {1, 1, 1};
-    const lrc_grid* cur_grid = nullptr;   // set around a grid scan (launch_trace gen == 3)
+    const lrc_grid* cur_grid = nullptr;   // set around a grid scan (launch_trace, kGenGrid)
     lrc_scene_info info{};
     lrc_scan_options opts{};          // sticky opt-in options (lrc_scene_set_options)
     uint64_t launches = 0, rays = 0;

@@ -30,7 +30,7 @@ constexpr int kOctaves = 24, kCells = 64, kTable = kOctaves * kCells;   // 1536 
 
 struct Words { uint32_t w0, w1, w2, w3; };
 
-// what the trace kernel needs of an lrc_noise (GEN = 5): a zero range_std, angle_std or drop_thr skips its step
+// what the trace kernel needs of an lrc_noise (kGenNoisy, kGenNoisySweeps): a zero range_std, angle_std or drop_thr skips its step
 struct Params {
     uint64_t seed, first_frame;
     double angle_std;        // radians

@@ -13,6 +13,22 @@ FIELDS = r"(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]
 
 
 @functools.lru_cache(maxsize=None)
+def _generators():
+    """{name: value} of the ray generators, from their one table (csrc/lrc_gen.h)."""
+    with open(os.path.join(PKG, "csrc", "lrc_gen.h")) as fh:
+        found = {m.group(1): int(m.group(2)) for m in re.finditer(r"constexpr int (kGen\w+) = (\d+);", fh.read())}
+    assert found, "csrc/lrc_gen.h: no `constexpr int kGen... = n;` line found"
+    return found
+
+
+def trace_kernel_name(gen, qn, stats=False):
+    """The mangled name of lidarcast.hip's trace_kernel<gen, 2, true, false, stats, qn>: ``gen`` is a generator's name in
+    csrc/lrc_gen.h ("kGenPoses", ...); ``qn`` 1 = quantised nodes, 0 = float32 nodes."""
+    assert gen in _generators(), f"{gen!r} is not a generator of csrc/lrc_gen.h: {sorted(_generators())}"
+    return f"_ZN12_GLOBAL__N_112trace_kernelILi{_generators()[gen]}ELi2ELb1ELb0ELb{int(stats)}ELi{int(qn)}EEEvNS_11TraceParamsE"
+
+
+@functools.lru_cache(maxsize=None)
 def usage_of(source, drop_flags=("-shared",), asm=False):
     """{mangled kernel name: {"TotalSGPRs", "VGPRs", "ScratchSize", "Occupancy", "LDS": int}} of csrc/<source>, compiled with
     the build's flags less ``drop_flags``.  ``asm=True`` compiles to assembly text (-S) and returns (that dict, the text)."""

@@ -4,10 +4,10 @@ budget of the pose-batched scan it extends -- 64 VGPRs, 8 waves per SIMD -- read
 remarks as tests/test_noise_kernel_resources.py reads them.  The figures are printed (DESIGN.md section 5i records them)."""
 import pytest
 
-from kernel_resources import usage_of
+from kernel_resources import trace_kernel_name, usage_of
 
-ECHO_QUANTISED = "_ZN12_GLOBAL__N_112trace_kernelILi6ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <6, 2, true, false, false, 1>
-ECHO_FLOAT32 = "_ZN12_GLOBAL__N_112trace_kernelILi6ELi2ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE"     # <6, 2, true, false, false, 0>
+ECHO_QUANTISED = trace_kernel_name("kGenEchoes", qn=1)
+ECHO_FLOAT32 = trace_kernel_name("kGenEchoes", qn=0)
 
 
 @pytest.fixture(scope="module")

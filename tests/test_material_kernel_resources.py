@@ -4,10 +4,10 @@ the compiler's kernel-resource-usage remarks as tests/test_echo_kernel_resources
 printed, not fixed (DESIGN.md section 5j records them)."""
 import pytest
 
-from kernel_resources import usage_of
+from kernel_resources import trace_kernel_name, usage_of
 
-MATERIAL_QUANTISED = "_ZN12_GLOBAL__N_112trace_kernelILi7ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <7, 2, true, false, false, 1>
-MATERIAL_FLOAT32 = "_ZN12_GLOBAL__N_112trace_kernelILi7ELi2ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE"     # <7, 2, true, false, false, 0>
+MATERIAL_QUANTISED = trace_kernel_name("kGenMaterials", qn=1)
+MATERIAL_FLOAT32 = trace_kernel_name("kGenMaterials", qn=0)
 
 
 @pytest.fixture(scope="module")

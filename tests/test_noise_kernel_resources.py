@@ -4,10 +4,10 @@ extends -- 64 VGPRs, at most 80 SGPRs, no scratch, 8 waves per SIMD -- read from
 as tests/test_sweep_kernel_resources.py reads them."""
 import pytest
 
-from kernel_resources import usage_of
+from kernel_resources import trace_kernel_name, usage_of
 
-NOISY_QUANTISED = "_ZN12_GLOBAL__N_112trace_kernelILi5ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <5, 2, true, false, false, 1>
-NOISY_FLOAT32 = "_ZN12_GLOBAL__N_112trace_kernelILi5ELi2ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE"     # <5, 2, true, false, false, 0>
+NOISY_QUANTISED = trace_kernel_name("kGenNoisy", qn=1)
+NOISY_FLOAT32 = trace_kernel_name("kGenNoisy", qn=0)
 
 
 @pytest.fixture(scope="module")

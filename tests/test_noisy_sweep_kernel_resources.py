@@ -5,10 +5,10 @@ quantised nodes; at most 64 VGPRs and no scratch over float32 nodes -- read from
 tests/test_sweep_kernel_resources.py reads them."""
 import pytest
 
-from kernel_resources import usage_of
+from kernel_resources import trace_kernel_name, usage_of
 
-NOISY_SWEEP_QUANTISED = "_ZN12_GLOBAL__N_112trace_kernelILi8ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <8, 2, true, false, false, 1>
-NOISY_SWEEP_FLOAT32 = "_ZN12_GLOBAL__N_112trace_kernelILi8ELi2ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE"     # <8, 2, true, false, false, 0>
+NOISY_SWEEP_QUANTISED = trace_kernel_name("kGenNoisySweeps", qn=1)
+NOISY_SWEEP_FLOAT32 = trace_kernel_name("kGenNoisySweeps", qn=0)
 
 
 @pytest.fixture(scope="module")

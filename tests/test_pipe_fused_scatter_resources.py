@@ -4,9 +4,9 @@ test_pipe_lean_resources.py does.  It repeats that budget on purpose: the kernel
 give the tracing waves part of that work (profiles/pipe_fused_scatter.txt) moved this figure first."""
 import pytest
 
-from kernel_resources import usage_of
+from kernel_resources import trace_kernel_name, usage_of
 
-PRODUCT = "_ZN12_GLOBAL__N_112trace_kernelILi1ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <1, 2, true, false, false, 1>
+PRODUCT = trace_kernel_name("kGenPoses", qn=1)
 
 
 @pytest.fixture(scope="module")

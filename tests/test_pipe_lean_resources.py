@@ -4,9 +4,9 @@ scratch, and the product trace kernel, which now carries the lean write-back and
 workgroups, still fits 64 VGPRs, 80 SGPRs and 8 waves per SIMD with no scratch."""
 import pytest
 
-from kernel_resources import usage_of
+from kernel_resources import trace_kernel_name, usage_of
 
-QUANTISED = "_ZN12_GLOBAL__N_112trace_kernelILi1ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <1, 2, true, false, false, 1>
+QUANTISED = trace_kernel_name("kGenPoses", qn=1)
 
 
 @pytest.fixture(scope="module")

@@ -3,10 +3,10 @@ pose-batched scan it extends -- 64 VGPRs, at most 80 SGPRs, no scratch, 8 waves 
 kernel-resource-usage remarks as tests/test_trace_kernel_resources.py reads them."""
 import pytest
 
-from kernel_resources import usage_of
+from kernel_resources import trace_kernel_name, usage_of
 
-SWEEP_QUANTISED = "_ZN12_GLOBAL__N_112trace_kernelILi4ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <4, 2, true, false, false, 1>
-SWEEP_FLOAT32 = "_ZN12_GLOBAL__N_112trace_kernelILi4ELi2ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE"     # <4, 2, true, false, false, 0>
+SWEEP_QUANTISED = trace_kernel_name("kGenSweeps", qn=1)
+SWEEP_FLOAT32 = trace_kernel_name("kGenSweeps", qn=0)
 
 
 @pytest.fixture(scope="module")

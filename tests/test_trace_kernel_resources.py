@@ -3,10 +3,10 @@ kernel-resource-usage remarks.  The quantised pose-batched kernel is sized for 8
 for them): 64 VGPRs and at most 80 SGPRs -- 82..96 SGPRs admit only 7 waves although the remark still says 8."""
 import pytest
 
-from kernel_resources import usage_of
+from kernel_resources import trace_kernel_name, usage_of
 
-QUANTISED = "_ZN12_GLOBAL__N_112trace_kernelILi1ELi2ELb1ELb0ELb0ELi1EEEvNS_11TraceParamsE"   # <1, 2, true, false, false, 1>
-FLOAT32 = "_ZN12_GLOBAL__N_112trace_kernelILi1ELi2ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE"     # <1, 2, true, false, false, 0>
+QUANTISED = trace_kernel_name("kGenPoses", qn=1)
+FLOAT32 = trace_kernel_name("kGenPoses", qn=0)
 
 
 @pytest.fixture(scope="module")
