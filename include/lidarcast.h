@@ -913,7 +913,9 @@ int lrc_nn_query_dev(lrc_nn* nn, const float* d_query3, uint64_t num_queries, ui
  *   lrc_min_distances : out_min[i] = min_j |a_i - b_j| in float32 (sum of squares, one sqrt): the directed
  *                       term of compute_chamfer_distance (:81-96) and compute_hausdorff_distance (:98-111)
  *   lrc_rbf_kernel_sum: sum_ij exp(-gamma * max(|a_i|^2 + |b_j|^2 - 2 a_i.b_j, 0)), float64: one of the
- *                       three kernel sums of compute_mmd_sampled (:55-79) */
+ *                       three kernel sums of compute_mmd_sampled (:55-79)
+ * Non-finite coordinates answer as numpy's min, maximum and exp do: a distance or a kernel term that is NaN there
+ * (a NaN coordinate, inf - inf, 0 * inf) makes the row's minimum, or the sum, NaN. */
 int lrc_min_distances(lrc_ctx* ctx, const float* a3, uint64_t n, const float* b3, uint64_t m, float* out_min);
 int lrc_rbf_kernel_sum(lrc_ctx* ctx, const float* a3, uint64_t n, const float* b3, uint64_t m, double gamma,
                        double* out_sum);
@@ -1042,7 +1044,8 @@ int lrc_object_boxes_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, cons
 
 /* ---- robot-cube occupancy for the trajectory planner ----------------
  * out_flags[q] = 1 iff some mesh vertex lies inside the axis-aligned cube [p_q - half, p_q + half] (float64,
- * inclusive), for all Q positions at once.  Replaces AutoTrajectoryGenerator._is_point_inside_mesh
+ * inclusive; a NaN coordinate is inside nothing), for all Q positions at once, any number of them.  Replaces
+ * AutoTrajectoryGenerator._is_point_inside_mesh
  * (trajectory/auto_trajectory_generator.py:219-238), which the reference evaluates position by position over
  * every vertex for the free-space grid (:129-139) and for every waypoint of every candidate (:345-356). */
 typedef struct lrc_occ lrc_occ;

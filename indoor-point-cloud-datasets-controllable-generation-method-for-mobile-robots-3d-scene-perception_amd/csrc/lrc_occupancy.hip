@@ -98,11 +98,18 @@ int lrc_occ_query(lrc_occ* occ, const double* points3, uint64_t Q, double half, 
     LRC_HIP(hipMalloc(&df.p, Q * 4));
     LRC_HIP(hipMemcpy(dp.p, points3, Q * 24, hipMemcpyHostToDevice));
     LRC_HIP(hipMemset(df.p, 0, Q * 4));
-    const uint64_t gx = (occ->V + 256ull * kVPT - 1) / (256ull * kVPT), gy = (Q + kQ - 1) / kQ;
-    if (gx > 0x7FFFFFFFull || gy > 65535ull) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_occ_query: too large");
-    hipLaunchKernelGGL(occupancy_kernel, dim3((uint32_t)gx, (uint32_t)gy), dim3(256), 0, nullptr,
-                       (const double*)occ->d_verts, occ->V, (const double*)dp.p, Q, half, (uint32_t*)df.p);
-    LRC_HIP(hipGetLastError());
+    const uint64_t gx = (occ->V + 256ull * kVPT - 1) / (256ull * kVPT);
+    if (gx > 0x7FFFFFFFull) return lrc_internal_fail(LRC_ERR_INVALID_ARG, "lrc_occ_query: too many vertices");
+    // gridDim.y holds at most 65 535 blocks of kQ positions: longer queries go out as several launches, each on its
+    // own slice of the positions and of the flags.
+    constexpr uint64_t kChunk = 65535ull * kQ;
+    for (uint64_t q0 = 0; q0 < Q; q0 += kChunk) {
+        const uint64_t nq = (Q - q0) < kChunk ? (Q - q0) : kChunk;
+        hipLaunchKernelGGL(occupancy_kernel, dim3((uint32_t)gx, (uint32_t)((nq + kQ - 1) / kQ)), dim3(256), 0, nullptr,
+                           (const double*)occ->d_verts, occ->V, (const double*)dp.p + 3 * q0, nq, half,
+                           (uint32_t*)df.p + q0);
+        LRC_HIP(hipGetLastError());
+    }
     LRC_HIP(hipDeviceSynchronize());
     uint32_t* tmp = new (std::nothrow) uint32_t[Q];
     if (!tmp) return lrc_internal_fail(LRC_ERR_OOM, "lrc_occ_query: out of host memory");
