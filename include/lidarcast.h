@@ -751,6 +751,68 @@ int lrc_mover_merge(uint64_t num_rays, uint32_t num_movers, const float* t_stati
                     const float* t_movers, const float* normal3_movers, const float* poses12, float* out_t,
                     float* out_normal3, uint8_t* out_mover);
 
+/* ---- scene flow under movers: per-point flow and visibility at the next frame (opt-in) ----------------
+ * For every return of a frame scanned with movers: where the surface the point lies on will be at a NEXT frame, and whether
+ * that place can be seen from the next sensor pose (the occlusion mask of scene-flow benchmarks).  "Next" is given per frame,
+ * so a caller pairs frames as it likes (k -> k + 1, backward flow, k -> k + 2) and the result does not depend on how frames are
+ * split into calls.  The reference has nothing of the kind.
+ * Row (p, i) is a record of lrc_scan_movers_dev: x = point3 (float32), w = mover (0: the room, m + 1: mover m; a w above M is
+ * read as 0).  Per frame p: A = mover_poses12[p] (the poses the row was scanned with), B = next_mover_poses12[p], the sensor
+ * pose next_poses16[p] to be seen from, has_next[p] (uint8; a NULL pointer means all ones).
+ *   1 target  w == 0, or the 48 bytes of A[w-1] and B[w-1] are equal: y = x.  Otherwise in float64, one rounding per operation,
+ *             nothing fused: e = x - c_A; q_j = (R_A[0][j] e_x + R_A[1][j] e_y) + R_A[2][j] e_z;
+ *             y_j = ((R_B[j][0] q_x + R_B[j][1] q_y) + R_B[j][2] q_z) + c_B,j
+ *   2 flow    flow3_j = float32(y_j - x_j); a room point or a mover that stands still gives +0 in all three components
+ *   3 sight   y32 = float32(y); o = float32(next_pose[:3,3]); d = y32 - o, L = sqrt((d_x^2 + d_y^2) + d_z^2), h = d / L, all
+ *             float32.  dist = the float64 distance of y32 from the float64 translation of the next pose, as the scan's range
+ *             filter forms it: sqrt((e_x^2 + e_y^2) + e_z^2), e = float64(y32) - c.  Unless dist < max_range (and, with the
+ *             static scene's min_range > 0, dist >= min_range) the row is OUT OF RANGE (3) and not cast.
+ *   4 ranges  t_s = what lrc_cast_dev returns for (o, h) on the room without centre or filter; per mover t_m = what it returns
+ *             on mover m's scene for the ray taken into its frame with B[m] (step 2 of the moving objects).  Culling as there:
+ *             it never changes a byte.  A ray that is not finite is not cast (the finite-ray contract): a miss.
+ *   5 status  thr = L - 2^-12 * max(L, 1) in float32 (the product is exact: one rounding).  OCCLUDED (2) iff
+ *             min(t_s, t_0, ..., t_(M-1)) < thr compared as float32, else VISIBLE (1).  The surface the point lies on is itself
+ *             met at about L; the margin keeps it from counting (measured: DESIGN.md section 5m).
+ *   6 a row without a return (t = +inf), or of a frame with has_next[p] == 0: +0 flow and status NONE (0).
+ * Status 1 means line of sight and range, not that a scan line of the next frame lands there (no field-of-view test).
+ * LRC_ERR_INVALID_ARG before any launch: what lrc_scan_movers_* refuse (a set of another context, the static scene among its
+ * movers, a range_noise option, NULL scene or records), a NULL flow3 / flow_rows, records without t or point3, a NULL mover
+ * column with a set, NULL next sensor poses, NULL mover poses (either table) with a set and, in lrc_scan_flow_compact, what
+ * lrc_scan_movers_compact refuses, applied to both mover pose tables.
+ *   lrc_scan_flow_dev      device pointers; everything is enqueued on `stream`, nothing is waited for.  d_records: t and point3
+ *                          of P * N records; d_flow3 (P * N, 3) float32; d_status (P * N) uint8, NULL: the flow alone, nothing
+ *                          is cast.  A NULL set: zero flow and line of sight against the room alone.  Scratch lives in the set
+ *                          (in the scene without one) and does not grow with M; calls that share it must share a stream.
+ *   lrc_scan_flow_compact  what lrc_scan_movers_compact takes plus the next sensor poses (P, 16), the next mover poses
+ *                          (P, M, 12) and has_next (P, nullable), all on the host: the mover scan and the flow at the fixed
+ *                          stride, compacted; flow_rows (capacity, 3) float32 and status_rows (capacity) uint8 (nullable: the
+ *                          flow alone) receive the two columns of the kept rows, gathered like mover_rows.
+ *   lrc_flow_rays          host, no GPU: steps 1 to 3 for P frames of N rows by the inline functions the kernels call.  Out per
+ *                          row: flow3, the ray (o, h) as rays6, keep (1: to be cast), thr and the status so far (0, 3, or 1 for
+ *                          a row that is cast); the ray and thr of a row that is not cast are zero.
+ *   lrc_flow_status        host, no GPU: step 5 for n rows.  In: the static cast's ranges (n), the mover casts' (M, n) (+inf for
+ *                          a miss or a ray not cast), thr and the status of lrc_flow_rays.  Out: rows of status 1 judged, every
+ *                          other row's status unchanged. */
+#define LRC_FLOW_NONE 0
+#define LRC_FLOW_VISIBLE 1
+#define LRC_FLOW_OCCLUDED 2
+#define LRC_FLOW_OUT_OF_RANGE 3
+int lrc_scan_flow_dev(lrc_scene* scene, lrc_movers* set /* nullable */, const lrc_hits* d_records, const uint8_t* d_mover,
+                      uint64_t num_poses, uint64_t rays_per_pose, const float* d_mover_poses12, const float* d_next_mover_poses12,
+                      const double* d_next_poses16, const uint8_t* d_has_next /* nullable */, double max_range, float* d_flow3,
+                      uint8_t* d_status /* nullable */, void* stream);
+int lrc_scan_flow_compact(lrc_scene* scene, lrc_movers* set /* nullable */, const double* poses16, uint64_t num_poses,
+                          const lrc_table* table, const float* mover_poses12, const double* next_poses16,
+                          const float* next_mover_poses12, const uint8_t* has_next /* nullable */, double max_range,
+                          const lrc_frames* out, uint8_t* mover_rows /* nullable */, float* flow_rows,
+                          uint8_t* status_rows /* nullable */, uint64_t capacity, uint64_t* out_total);
+int lrc_flow_rays(const float* t, const float* point3, const uint8_t* mover, uint64_t num_poses, uint64_t rays_per_pose,
+                  uint32_t num_movers, const float* mover_poses12, const float* next_mover_poses12, const double* next_poses16,
+                  const uint8_t* has_next /* nullable */, double max_range, double min_range, float* out_flow3, float* out_rays6,
+                  uint8_t* out_keep, float* out_thr, uint8_t* out_status);
+int lrc_flow_status(uint64_t num_rows, uint32_t num_movers, const float* t_static, const float* t_movers, const float* thr,
+                    const uint8_t* status, uint8_t* out_status);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

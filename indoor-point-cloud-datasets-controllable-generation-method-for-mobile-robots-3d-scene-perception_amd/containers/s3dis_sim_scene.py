@@ -165,7 +165,7 @@ class S3DISSimScene:
         self._annotated = None        # (points f64 (M,3), colors (M,3) in 0..1, sem (M,), ins (M,))
         self._nn = None
         # the movers key of the simulator: {period, objects, times (P,), states (P, M, 4): x, y, z, yaw,
-        # poses12 (P, M, 12)} of the run, None without the key
+        # poses12 (P, M, 12), sensor_poses (P, 4, 4)} of the run, None without the key
         self.mover_tracks = None
 
     def append_frame(self, frame: S3DISSimFrame):
@@ -421,6 +421,39 @@ class S3DISSimScene:
         with open(out / f"{self.scene_name}_mover_tracks.json", "w") as fh:
             json.dump(summary, fh, indent=2)
         return summary
+
+    def export_scene_flow(self, output_dir) -> Dict[str, Any]:
+        """Scene-flow ground truth of a run under ``movers: {..., flow: true}``, written to ``output_dir``/<scene>_scene_flow.npz:
+        ``points`` (K, 3) float32 of all frames stacked, ``flow`` (K, 3) float32 (world displacement of the surface under the
+        point up to the next frame), ``status`` (K,) uint8 (0 no next frame, 1 visible from the next pose, 2 occluded, 3 out of
+        range), ``mover_ids`` (K,) uint8, ``frame_offsets`` (F + 1,) int64 (frame f = rows [offsets[f], offsets[f + 1])),
+        ``sensor_poses`` (F, 4, 4) float64, ``mover_poses12`` (F, M, 12) float32 and ``times`` (F,).  Returns the arrays."""
+        tr = self.mover_tracks
+        if tr is None:
+            raise ValueError("this scene was not simulated under the movers key")
+        cols = {"points": [], "flow": [], "status": [], "mover_ids": []}
+        for f, frame in enumerate(self.frames):
+            if getattr(frame, "flow", None) is None or getattr(frame, "flow_status", None) is None:
+                raise ValueError(f"frame {f} carries no flow: the movers key needs flow: true")
+            pts = np.asarray(frame.points, np.float32).reshape(-1, 3)
+            rows = {"points": pts, "flow": np.asarray(frame.flow, np.float32).reshape(-1, 3),
+                    "status": np.asarray(frame.flow_status, np.uint8).reshape(-1),
+                    "mover_ids": np.asarray(frame.mover_ids, np.uint8).reshape(-1)}
+            if any(len(a) != len(pts) for a in rows.values()):
+                raise ValueError(f"frame {f}: points, flow, flow_status and mover_ids differ in length")
+            for k, a in rows.items():
+                cols[k].append(a)
+        empty = {"points": (0, 3), "flow": (0, 3), "status": (0,), "mover_ids": (0,)}
+        out = {k: np.concatenate(v) if v else np.zeros(empty[k], np.float32 if len(empty[k]) == 2 else np.uint8)
+               for k, v in cols.items()}
+        out["frame_offsets"] = np.concatenate([[0], np.cumsum([len(a) for a in cols["points"]])]).astype(np.int64)
+        out["sensor_poses"] = np.asarray(tr["sensor_poses"], np.float64).reshape(-1, 4, 4)
+        out["mover_poses12"] = np.asarray(tr["poses12"], np.float32)
+        out["times"] = np.asarray(tr["times"], np.float64)
+        path = Path(output_dir)
+        path.mkdir(parents=True, exist_ok=True)
+        np.savez(path / f"{self.scene_name}_scene_flow.npz", **out)
+        return out
 
     def _save_labeled_ply(self, output_path: Path, points: np.ndarray, colors: np.ndarray,
                           semantic_labels: np.ndarray, instance_labels: np.ndarray):

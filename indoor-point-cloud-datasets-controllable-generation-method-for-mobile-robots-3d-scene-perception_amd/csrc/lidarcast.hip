@@ -541,6 +541,94 @@ __global__ __launch_bounds__(kBlock) void mover_merge_kernel(const TraceParams p
     if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
 }
 
+// ---- scene flow under movers (lrc_scan_flow_*; the arithmetic is lrc_flow.h's, the orchestration flow_scan_dev's) -------------
+// What the flow's ray kernel reads and writes.  The four line-of-sight columns are NULL together (flow only).
+struct FlowRays {
+    const float* t; const float* point3; const uint8_t* mover;       // the records of lrc_scan_movers_dev; mover nullable (all room)
+    const float* A; const float* B;                                  // (P, M, 12) each; unread with M == 0
+    const double* next16; const uint8_t* has_next;                   // (P, 16); (P) nullable: all ones
+    uint32_t M;
+    uint64_t rays_per_pose, total;
+    double max_range, min_range;
+    float* flow3;
+    float* rays6; uint8_t* keep; float* thr; uint8_t* status;
+};
+
+// One thread per record: steps 1 to 3 of the header.  The row's own pose pair is a per-lane fetch by w; most lanes have w == 0
+// and fetch nothing.
+__global__ __launch_bounds__(kBlock) void flow_rays_kernel(const FlowRays q) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= q.total) return;
+    const uint32_t pose = (uint32_t)(gid / q.rays_per_pose);
+    const bool live = (q.t[gid] < __builtin_inff()) & (q.has_next == nullptr || q.has_next[pose] != 0);
+    const uint32_t w = (live && q.mover) ? q.mover[gid] : 0u;
+    float x[3] = {0.f, 0.f, 0.f}, A[12], B[12];
+    bool moved = false;
+    if (live) {
+        x[0] = q.point3[gid * 3]; x[1] = q.point3[gid * 3 + 1]; x[2] = q.point3[gid * 3 + 2];
+    }
+    if (w != 0u && w <= q.M) {
+        const size_t row = ((size_t)pose * q.M + (w - 1u)) * 12;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { A[k] = q.A[row + k]; B[k] = q.B[row + k]; }
+        moved = !lrcflow::same_pose(A, B);
+    }
+    const lrcflow::Ray r = lrcflow::ray(live, moved, x, A, B, q.next16 + (size_t)pose * 16, q.max_range, q.min_range);
+    q.flow3[gid * 3] = r.flow[0]; q.flow3[gid * 3 + 1] = r.flow[1]; q.flow3[gid * 3 + 2] = r.flow[2];
+    if (!q.status) return;
+    const bool cast = r.status == lrcflow::kVisible;
+    q.status[gid] = r.status;
+    q.keep[gid] = cast ? (uint8_t)1 : (uint8_t)0;
+    if (!cast) return;
+    q.thr[gid] = r.thr;
+    float2* o = (float2*)(q.rays6 + gid * 6);      // 24-byte records: 8-byte aligned
+    o[0] = make_float2(r.o.x, r.o.y);
+    o[1] = make_float2(r.o.z, r.h.x);
+    o[2] = make_float2(r.h.y, r.h.z);
+}
+
+// A mover's pass: the world ray of every row that is cast, taken into mover q.m's frame with its NEXT pose, and the keep byte of
+// the explicit-ray launch (0: not cast at all, or left out by lrcmov::culled).
+__global__ __launch_bounds__(kBlock) void flow_object_rays_kernel(const float* __restrict__ world6, const uint8_t* __restrict__ cast,
+                                                                 uint64_t rays_per_pose, uint64_t total, const lrcmov::RayPass q,
+                                                                 int uniform, float* __restrict__ rays6, uint8_t* __restrict__ keep) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= total) return;
+    const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
+    float m12[12];
+    mover_pose_load(q.poses12, pose, q.M, q.m, uniform, m12);
+    bool out = cast[gid] == 0;
+    lrcmov::Vec ro{0.f, 0.f, 0.f}, rd{0.f, 0.f, 0.f};
+    if (!out) {
+        const float2* r = (const float2*)(world6 + gid * 6);
+        const float2 a = r[0], b = r[1], c = r[2];
+        lrcmov::to_object(m12, lrcmov::Vec{a.x, a.y, b.x}, lrcmov::Vec{b.y, c.x, c.y}, ro, rd);
+        out = lrcmov::culled(q.sphere, ro, rd);
+    }
+    keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
+    if (out) return;
+    float2* w = (float2*)(rays6 + gid * 6);
+    w[0] = make_float2(ro.x, ro.y);
+    w[1] = make_float2(ro.z, rd.x);
+    w[2] = make_float2(rd.y, rd.z);
+}
+
+// The running float32 minimum of the ranges met along the line of sight (t_min holds the static cast's to begin with) against
+// one mover's cast (t_mover; NULL: no mover, only the verdict).  The last pass writes the status of the rows that were cast.
+__global__ __launch_bounds__(kBlock) void flow_merge_kernel(float* __restrict__ t_min, const float* __restrict__ t_mover,
+                                                            const float* __restrict__ thr, const uint8_t* __restrict__ cast,
+                                                            uint64_t total, int last, uint8_t* __restrict__ status) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= total) return;
+    float t = t_min[gid];
+    if (t_mover) t = lrcflow::nearer(t_mover[gid], t);
+    if (!last) {
+        t_min[gid] = t;
+        return;
+    }
+    if (cast[gid]) status[gid] = lrcflow::judge(t, thr[gid]);
+}
+
 constexpr int kStatsWords = 5;   // node steps, triangle tests, wave-uniform node steps, dead node steps, pad-clause rejections
 
 // ---- stable compaction, one tile (64 consecutive entries of one segment) per wave ---------------------------------------
@@ -1879,6 +1967,7 @@ int lrc_scene_destroy(lrc_scene* s) {
     if (s->d_slot_sphere) (void)hipFree(s->d_slot_sphere);
     if (s->d_nodes_q4) (void)hipFree(s->d_nodes_q4);
     if (s->d_nodes_n4) (void)hipFree(s->d_nodes_n4);
+    if (s->flow_scratch) (void)hipFree(s->flow_scratch);
     delete s;
     return LRC_OK;
 }
@@ -4134,13 +4223,96 @@ int movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint
     return LRC_OK;
 }
 
+// lrc_scan_flow_dev behind its checks (lrc_flow.hip).  All on `st`, nothing waited for:
+//   the ray kernel     flow_rays_kernel: the flow and, with d_status, the world line of sight, its cast byte, thr, the first status
+//   the static pass    the explicit-ray launch on the scene, straight into the running minimum
+//   per mover m        flow_object_rays_kernel (object-frame rays by the NEXT pose + keep bytes), the explicit-ray launch on the
+//                      mover's scene, flow_merge_kernel; the last merge writes the status
+// in the set's scratch (the scene's own without a set): two ray sets, two byte columns and three float columns whatever M is.
+int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const uint8_t* d_mover, uint64_t P, uint64_t N,
+                  const float* d_mover_poses12, const FlowNext& next, double max_range, float* d_flow3, uint8_t* d_status,
+                  hipStream_t st) {
+    const uint64_t n = P * N;
+    if (!n) return LRC_OK;
+    if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_flow: too many poses or rays for one call");
+    const dim3 grid((uint32_t)blocks_of(n, kBlock));
+    const uint32_t M = set ? (uint32_t)set->scenes.size() : 0u;
+    FlowRays fr{};
+    fr.t = d_rec->t; fr.point3 = d_rec->point3; fr.mover = set ? d_mover : nullptr;
+    fr.A = d_mover_poses12; fr.B = next.next_mover_poses12;
+    fr.next16 = next.next_poses16; fr.has_next = next.has_next;
+    fr.M = M; fr.rays_per_pose = N; fr.total = n;
+    fr.max_range = max_range; fr.min_range = s->opts.min_range;
+    fr.flow3 = d_flow3;
+    if (!d_status) {
+        hipLaunchKernelGGL(flow_rays_kernel, grid, dim3(kBlock), 0, st, fr);
+        LRC_HIP(hipGetLastError());
+        return LRC_OK;
+    }
+    // scratch, 256-byte aligned columns: world rays6 | object rays6 | cast | keep | thr | t_min | t_mover
+    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
+    const uint64_t sizes[7] = {n * 24, n * 24, n, n, n * 4, n * 4, n * 4};
+    uint64_t off[8] = {0};
+    for (int k = 0; k < 7; ++k) off[k + 1] = off[k] + al(sizes[k]);
+    void*& block = set ? set->scratch : s->flow_scratch;
+    uint64_t& cap = set ? set->scratch_cap : s->flow_scratch_cap;
+    if (cap < off[7]) {
+        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
+        if (block) { (void)hipFree(block); block = nullptr; cap = 0; }
+        LRC_HIP(hipMalloc(&block, off[7] + off[7] / 8));
+        cap = off[7] + off[7] / 8;
+    }
+    uint8_t* const b = (uint8_t*)block;
+    float* const world6 = (float*)(b + off[0]);
+    float* const obj6 = (float*)(b + off[1]);
+    uint8_t* const cast = b + off[2];
+    uint8_t* const keep = b + off[3];
+    float* const thr = (float*)(b + off[4]);
+    lrc_hits w{}, mv{};
+    w.t = (float*)(b + off[5]);
+    mv.t = (float*)(b + off[6]);
+    fr.rays6 = world6; fr.keep = cast; fr.thr = thr; fr.status = d_status;
+    hipLaunchKernelGGL(flow_rays_kernel, grid, dim3(kBlock), 0, st, fr);
+    LRC_HIP(hipGetLastError());
+    int rc;
+    if ((rc = cast_plain(s, world6, cast, n, w, st))) return rc;
+    const int uniform = N % 64 == 0;
+    for (uint32_t m = 0; m < M; ++m) {
+        lrc_scene* const ms = set->scenes[m];
+        lrcmov::RayPass rp{};
+        rp.poses12 = next.next_mover_poses12;
+        rp.M = M;
+        rp.m = m;
+        rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
+        hipLaunchKernelGGL(flow_object_rays_kernel, grid, dim3(kBlock), 0, st, world6, cast, N, n, rp, uniform, obj6, keep);
+        LRC_HIP(hipGetLastError());
+        if ((rc = cast_plain(ms, obj6, keep, n, mv, st))) return rc;
+        hipLaunchKernelGGL(flow_merge_kernel, grid, dim3(kBlock), 0, st, w.t, mv.t, thr, cast, n, (int)(m + 1 == M), d_status);
+        LRC_HIP(hipGetLastError());
+    }
+    if (!M) {
+        hipLaunchKernelGGL(flow_merge_kernel, grid, dim3(kBlock), 0, st, w.t, (const float*)nullptr, thr, cast, n, 1, d_status);
+        LRC_HIP(hipGetLastError());
+    }
+    return LRC_OK;
+}
+
 // Host poses, a resident direction table: the records at the fixed stride by movers_scan_dev on the context's compute stream,
 // compacted by lrc_compact_dev (which counts itself: the merge kernel writes no per-tile keep counts); the counts come home
 // first, then exactly the kept rows.  The mover column stays at the fixed stride and is gathered for the kept rows by the
 // compacted index column (gather_rows_by_index above).
-int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
-                        const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
-                        uint64_t* out_total) {
+// With `flow` (flow_scan_compact): the flow and its status at the fixed stride behind the mover scan, gathered like the mover column.
+namespace {
+struct FlowCompact {
+    FlowNext next;             // host pointers
+    float* flow_rows;          // nullable
+    uint8_t* status_rows;      // nullable: flow only, nothing cast
+};
+int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                   const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
+                   uint64_t* out_total, const FlowCompact* flow) {
+    const char* const who = flow ? "lrc_scan_flow_compact" : "lrc_scan_movers_compact";
     SyncUnlessOk guard;
     lrc_ctx* const ctx = s->ctx;
     const uint64_t N = table->n, n = P * N;
@@ -4159,18 +4331,37 @@ int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, ui
     if ((rc = st.alloc(ctx, *out, P, n))) return rc;
     st.rec.tile_count = nullptr;
     st.io.tile_count = nullptr;
-    if (mover_rows && !st.io.out_index) {       // the gather reads the index column whether or not the caller asked for it
+    const bool want_flow = flow && (flow->flow_rows || flow->status_rows);
+    if ((mover_rows || want_flow) && !st.io.out_index) {       // the gather reads the index column whether or not the caller asked for it
         if ((rc = st.oidx.get(ctx, kPoolOutIdx, n * 4))) return rc;
         st.io.out_index = (uint32_t*)st.oidx.p;
     }
-    DevBuf mbuf;
-    if (mover_rows && (rc = mbuf.get(ctx, kPoolKeep, n))) return rc;
+    DevBuf mbuf, p3buf, fbuf, sbuf;
+    if ((mover_rows || (want_flow && set)) && (rc = mbuf.get(ctx, kPoolKeep, n))) return rc;
+    FlowNext d_next{};
+    if (want_flow) {
+        // the flow reads point3 whether or not a frame column needs it; no frame column lives in the slots of the two flow columns
+        if (!st.rec.point3) {
+            if ((rc = p3buf.get(ctx, kPoolPoint, n * 12))) return rc;
+            st.rec.point3 = (float*)p3buf.p;
+        }
+        if ((rc = fbuf.get(ctx, kPoolNormal, n * 12))) return rc;
+        if (flow->status_rows && (rc = sbuf.get(ctx, kPoolAngles, n))) return rc;
+        if ((rc = stage_input(ctx, kPoolCen, flow->next.next_poses16, P * 16, &d_next.next_poses16, &cs))) return rc;
+        if (set && (rc = stage_input(ctx, kPoolOffs, flow->next.next_mover_poses12, P * set->scenes.size() * 12,
+                                     &d_next.next_mover_poses12, &cs)))
+            return rc;
+        if (flow->next.has_next && (rc = stage_input(ctx, kPoolRays, flow->next.has_next, P, &d_next.has_next, &cs))) return rc;
+    }
     if (ctx->h_counts_cap < P) {
         if (ctx->h_counts) { (void)hipHostFree(ctx->h_counts); ctx->h_counts = nullptr; ctx->h_counts_cap = 0; }
         LRC_HIP(hipHostMalloc((void**)&ctx->h_counts, (P + P / 4 + 64) * 8 * 5, hipHostMallocDefault));
         ctx->h_counts_cap = P + P / 4 + 64;
     }
     if ((rc = movers_scan_dev(s, set, d_poses, P, table->d_dirs3, N, d_mp, max_range, &st.rec, (uint8_t*)mbuf.p, cs))) return rc;
+    if (want_flow && (rc = flow_scan_dev(s, set, &st.rec, (const uint8_t*)mbuf.p, P, N, d_mp, d_next, max_range, (float*)fbuf.p,
+                                         (uint8_t*)sbuf.p, cs)))
+        return rc;
     if ((rc = lrc_compact_dev(ctx, P, N, &st.io, cs))) return rc;
     LRC_HIP(hipMemcpyAsync(ctx->h_counts, st.io.counts, P * 8, hipMemcpyDeviceToHost, cs));
     if (st.d_stats && (rc = enqueue_frame_stats(ctx, st, out, P, 0, P, 0, cs))) return rc;
@@ -4184,11 +4375,27 @@ int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, ui
     if (K && (rc = copy_frame_rows(*out, st.io, 0, 0, K, cs))) return rc;
     LRC_HIP(hipStreamSynchronize(cs));
     publish_frame_stats(ctx, out, P);
-    if (mover_rows && K) {
-        const GatherColumn col{mbuf.p, mover_rows, 1, 1};
-        rc = gather_rows_by_index("lrc_scan_movers_compact", out->counts, P, st.io.out_index, N, K, &col, 1);
+    if ((mover_rows || want_flow) && K) {
+        const GatherColumn cols[3] = {{mbuf.p, mover_rows, 1, 1},
+                                      {fbuf.p, flow ? flow->flow_rows : nullptr, 4, 3},
+                                      {sbuf.p, flow ? flow->status_rows : nullptr, 1, 1}};
+        rc = gather_rows_by_index(who, out->counts, P, st.io.out_index, N, K, cols, 3);
     }
     return guard.done(rc);
+}
+}  // namespace
+
+int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                        const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
+                        uint64_t* out_total) {
+    return movers_compact(s, set, poses16, P, table, mover_poses12, max_range, out, mover_rows, capacity, out_total, nullptr);
+}
+
+int flow_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                      const float* mover_poses12, const FlowNext& next, double max_range, const lrc_frames* out, uint8_t* mover_rows,
+                      float* flow_rows, uint8_t* status_rows, uint64_t capacity, uint64_t* out_total) {
+    const FlowCompact flow{next, flow_rows, status_rows};
+    return movers_compact(s, set, poses16, P, table, mover_poses12, max_range, out, mover_rows, capacity, out_total, &flow);
 }
 
 extern "C" {

@@ -1,0 +1,101 @@
+// lrc_flow.hip -- host side of the scene flow under movers (lrc_flow.h): the checks of lrc_scan_flow_dev / lrc_scan_flow_compact
+// (the kernels, the launches and the frame path are lidarcast.hip's: flow_scan_dev, flow_scan_compact) and the two host functions
+// lrc_flow_rays and lrc_flow_status, which run the inline functions the kernels call on arrays.
+#include <cmath>
+
+#include "lrc_internal.h"
+#include "lrc_flow.h"
+
+extern "C" {
+
+int lrc_scan_flow_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_records, const uint8_t* d_mover, uint64_t P, uint64_t N,
+                      const float* d_mover_poses12, const float* d_next_mover_poses12, const double* d_next_poses16,
+                      const uint8_t* d_has_next, double max_range, float* d_flow3, uint8_t* d_status, void* stream) {
+    auto bad = [&](const char* t) { return fail(LRC_ERR_INVALID_ARG, std::string("lrc_scan_flow_dev: ") + t); };
+    int rc = check_call("lrc_scan_flow_dev", s, set, d_records);
+    if (rc) return rc;
+    if (!d_flow3) return bad("flow3 is NULL");
+    if (!d_records->t || !d_records->point3) return bad("the records need t and point3");
+    if (set && !d_mover) return bad("the mover column is NULL");
+    if (!d_next_poses16) return bad("next_poses16 is NULL");
+    if (set && (!d_mover_poses12 || !d_next_mover_poses12)) return bad("mover_poses12 or next_mover_poses12 is NULL");
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    const FlowNext next{d_next_mover_poses12, d_next_poses16, d_has_next};
+    return flow_scan_dev(s, set, d_records, d_mover, P, N, d_mover_poses12, next, max_range, d_flow3, d_status, (hipStream_t)stream);
+}
+
+int lrc_scan_flow_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                          const float* mover_poses12, const double* next_poses16, const float* next_mover_poses12,
+                          const uint8_t* has_next, double max_range, const lrc_frames* out, uint8_t* mover_rows, float* flow_rows,
+                          uint8_t* status_rows, uint64_t capacity, uint64_t* out_total) {
+    auto bad = [&](const char* t) { return fail(LRC_ERR_INVALID_ARG, std::string("lrc_scan_flow_compact: ") + t); };
+    if (out_total) *out_total = 0;
+    int rc = check_call("lrc_scan_flow_compact", s, set, out);
+    if (rc) return rc;
+    if (!table) return bad("table is NULL");
+    if (table->ctx != s->ctx) return bad("table and scene belong to different contexts");
+    if (!flow_rows) return bad("flow_rows is NULL");
+    if (!next_poses16) return bad("next_poses16 is NULL");
+    if (set && (!mover_poses12 || !next_mover_poses12)) return bad("mover_poses12 or next_mover_poses12 is NULL");
+    if (!(P * table->n)) return LRC_OK;
+    if (!poses16 || !out->counts) return bad("poses16 or counts is NULL");
+    if (table->n > 0xFFFFFFFFull) return bad("rays_per_pose must stay below 2^32 (the index column)");
+    if (set) {
+        if ((rc = check_poses12("lrc_scan_flow_compact", mover_poses12, P * set->scenes.size()))) return rc;
+        if ((rc = check_poses12("lrc_scan_flow_compact (next)", next_mover_poses12, P * set->scenes.size()))) return rc;
+    }
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    const FlowNext next{next_mover_poses12, next_poses16, has_next};
+    return flow_scan_compact(s, set, poses16, P, table, mover_poses12, next, max_range, out, mover_rows, flow_rows, status_rows,
+                             capacity, out_total);
+}
+
+int lrc_flow_rays(const float* t, const float* point3, const uint8_t* mover, uint64_t P, uint64_t N, uint32_t M,
+                  const float* mover_poses12, const float* next_mover_poses12, const double* next_poses16, const uint8_t* has_next,
+                  double max_range, double min_range, float* out_flow3, float* out_rays6, uint8_t* out_keep, float* out_thr,
+                  uint8_t* out_status) {
+    if (M > lrcmov::kMaxMovers) return fail(LRC_ERR_INVALID_ARG, "lrc_flow_rays: the number of movers must not exceed 255");
+    const uint64_t n = P * N;
+    if (n && (!t || !point3 || !next_poses16 || !out_flow3 || !out_rays6 || !out_keep || !out_thr || !out_status ||
+              (M && (!mover || !mover_poses12 || !next_mover_poses12))))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_flow_rays: NULL argument");
+    for (uint64_t p = 0; p < P; ++p)
+        for (uint64_t i = 0; i < N; ++i) {
+            const uint64_t g = p * N + i;
+            const bool live = (t[g] < INFINITY) & (has_next == nullptr || has_next[p] != 0);
+            const uint32_t w = (live && M) ? mover[g] : 0u;
+            const float* A = nullptr;
+            const float* B = nullptr;
+            bool moved = false;
+            if (w != 0u && w <= M) {
+                A = mover_poses12 + (p * M + (w - 1u)) * 12;
+                B = next_mover_poses12 + (p * M + (w - 1u)) * 12;
+                moved = !lrcflow::same_pose(A, B);
+            }
+            const lrcflow::Ray r = lrcflow::ray(live, moved, point3 + g * 3, A, B, next_poses16 + p * 16, max_range, min_range);
+            const bool cast = r.status == lrcflow::kVisible;
+            for (int j = 0; j < 3; ++j) out_flow3[g * 3 + j] = r.flow[j];
+            float* w6 = out_rays6 + g * 6;
+            w6[0] = cast ? r.o.x : 0.f; w6[1] = cast ? r.o.y : 0.f; w6[2] = cast ? r.o.z : 0.f;
+            w6[3] = cast ? r.h.x : 0.f; w6[4] = cast ? r.h.y : 0.f; w6[5] = cast ? r.h.z : 0.f;
+            out_keep[g] = cast ? 1 : 0;
+            out_thr[g] = cast ? r.thr : 0.f;
+            out_status[g] = r.status;
+        }
+    return LRC_OK;
+}
+
+int lrc_flow_status(uint64_t n, uint32_t M, const float* t_static, const float* t_movers, const float* thr, const uint8_t* status,
+                    uint8_t* out_status) {
+    if (M > lrcmov::kMaxMovers) return fail(LRC_ERR_INVALID_ARG, "lrc_flow_status: the number of movers must not exceed 255");
+    if (n && (!t_static || !thr || !status || !out_status || (M && !t_movers)))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_flow_status: NULL argument");
+    for (uint64_t i = 0; i < n; ++i) {
+        float t = t_static[i];
+        for (uint32_t m = 0; m < M; ++m) t = lrcflow::nearer(t_movers[(uint64_t)m * n + i], t);
+        out_status[i] = status[i] == lrcflow::kVisible ? lrcflow::judge(t, thr[i]) : status[i];
+    }
+    return LRC_OK;
+}
+
+}  // extern "C"

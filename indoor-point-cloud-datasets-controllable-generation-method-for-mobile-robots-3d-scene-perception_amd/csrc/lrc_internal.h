@@ -16,6 +16,7 @@
 #include "lrc_echo.h"
 #include "lrc_material.h"
 #include "lrc_movers.h"
+#include "lrc_flow.h"
 
 // sets lrc_last_error() (lidarcast.hip).  Exported: lrc_nprandom.cpp, built without HIP headers, reports through it.
 extern "C" int lrc_internal_fail(int code, const char* msg);
@@ -145,12 +146,14 @@ struct lrc_scene {
     lrc_scene_info info{};
     lrc_scan_options opts{};          // sticky opt-in options (lrc_scene_set_options)
     uint64_t launches = 0, rays = 0;
+    void* flow_scratch = nullptr;     // flow_scan_dev without a mover set: grown on demand (a set brings its own scratch)
+    uint64_t flow_scratch_cap = 0;
 };
 
 struct lrc_movers {           // a mover set (lrc_movers_create): the caller's scenes, not owned, and the scan's scratch
     lrc_ctx* ctx = nullptr;
     std::vector<lrc_scene*> scenes;
-    void* scratch = nullptr;      // movers_scan_dev: grown on demand, one ray set and two record sets whatever M is
+    void* scratch = nullptr;      // movers_scan_dev and flow_scan_dev: grown on demand, the same size whatever M is
     uint64_t scratch_cap = 0;
 };
 
@@ -220,5 +223,27 @@ int movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint
 int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
                         const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
                         uint64_t* out_total);
+
+// the checks lrc_scan_movers_* and lrc_scan_flow_* share (lrc_movers.hip).  check_call: NULL scene or output, a set of another
+// context or one that holds the static scene, a range_noise option; `set` may be NULL.  check_poses12: `count` host mover poses,
+// every entry finite and max |R^T R - I| <= 2^-16 in float64.
+int check_call(const char* who, const lrc_scene* s, const lrc_movers* set, const void* out);
+int check_poses12(const char* who, const float* m, uint64_t count);
+
+// scene flow under movers.  lrc_flow.hip checks the arguments of lrc_scan_flow_* and owns the host functions; lidarcast.hip holds
+// the kernels and enqueues the passes (flow_scan_dev: everything on `st`, no host synchronisation; d_status == NULL: the flow
+// alone, nothing cast) and scans to frames (flow_scan_compact: the mover scan and the flow at the fixed stride, then the frame
+// path of movers_scan_compact with the flow and status columns gathered beside the mover column).
+struct FlowNext {             // what pairs every frame of a call with its next one: device pointers for flow_scan_dev, host
+    const float* next_mover_poses12;      // pointers for flow_scan_compact
+    const double* next_poses16;
+    const uint8_t* has_next;              // nullable: all ones
+};
+int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const uint8_t* d_mover, uint64_t P, uint64_t N,
+                  const float* d_mover_poses12, const FlowNext& next, double max_range, float* d_flow3, uint8_t* d_status,
+                  hipStream_t st);
+int flow_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                      const float* mover_poses12, const FlowNext& next, double max_range, const lrc_frames* out, uint8_t* mover_rows,
+                      float* flow_rows, uint8_t* status_rows, uint64_t capacity, uint64_t* out_total);
 
 #pragma GCC visibility pop

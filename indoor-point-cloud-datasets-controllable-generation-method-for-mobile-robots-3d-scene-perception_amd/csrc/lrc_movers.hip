@@ -7,9 +7,7 @@
 #include "lrc_internal.h"
 #include "lrc_movers.h"
 
-namespace {
-
-// the checks lrc_scan_movers_dev and lrc_scan_movers_compact share; `set` may be NULL
+// the checks lrc_scan_movers_* and lrc_scan_flow_* share (declared in lrc_internal.h); `set` may be NULL
 int check_call(const char* who, const lrc_scene* s, const lrc_movers* set, const void* out) {
     auto bad = [&](const char* t) { return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": " + t); };
     if (!s || !out) return bad("NULL scene or output");
@@ -42,8 +40,6 @@ int check_poses12(const char* who, const float* m, uint64_t count) {
     }
     return LRC_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

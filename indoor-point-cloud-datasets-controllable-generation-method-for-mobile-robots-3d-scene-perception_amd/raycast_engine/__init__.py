@@ -6,5 +6,8 @@ from . import raycast_engine_hip as _hip
 RaycastEngineBase = _base.RaycastEngineBase
 RaycastEngineHIP, RaycastEngineGPU, RaycastEngineCPU = _hip.RaycastEngineHIP, _hip.RaycastEngineGPU, _hip.RaycastEngineCPU
 mesh_arrays = _hip.mesh_arrays
+# scene flow under movers lives in lidarcast.flow, the engine as its first argument; bound here as the engines' method
+from lidarcast.flow import scan_flow_frames as _scan_flow_frames  # noqa: E402
+RaycastEngineHIP.scan_flow_frames = _scan_flow_frames
 
 __all__ = ["RaycastEngineBase", "RaycastEngineCPU", "RaycastEngineGPU", "RaycastEngineHIP", "mesh_arrays"]

@@ -370,17 +370,20 @@ class S3DISSimulator:
     def _mover_plan(self):
         """The moving objects of the config key ``movers`` (None without the key): ``period`` (seconds between frames; frame k
         is at k * period) and ``objects``, each ``{mesh: pedestrian | <path to a mesh>, semantic: id or S3DIS class name,
-        instance: id, path: [[t, x, y, z, yaw_deg], ...]}``.  Returns {period, meshes, tracks, objects (JSON-ready)}.  The key
-        stands alone: motion, noise, beam and materials are refused beside it."""
+        instance: id, path: [[t, x, y, z, yaw_deg], ...]}``, and optionally ``flow: true`` (scene flow: frames then carry the flow
+        to the next frame and its status).  Returns {period, meshes, tracks, objects (JSON-ready), flow}.
+        The key stands alone: motion, noise, beam and materials are refused beside it."""
         cfg = self.config.get("movers")
         if cfg is None:
             return None
         for other in ("motion", "noise", "beam", "materials"):
             if self.config.get(other) is not None:
                 raise ValueError(f"the movers key cannot be combined with the {other} key")
-        unknown = set(cfg) - {"period", "objects"}
+        unknown = set(cfg) - {"period", "objects", "flow"}
         if unknown:
             raise ValueError(f"unknown entries under the movers key: {sorted(unknown)}")
+        if not isinstance(cfg.get("flow", False), bool):
+            raise ValueError("movers.flow must be true or false")
         period = float(cfg.get("period", 0.1))
         if not (np.isfinite(period) and period > 0.0):
             raise ValueError("movers.period must be a positive number of seconds")
@@ -420,7 +423,7 @@ class S3DISSimulator:
             listed.append({"index": k, "mesh": str(name), "semantic": sem, "instance": ins, "num_triangles": len(mesh.triangles),
                            "box_min": [float(x) for x in np.asarray(mesh.vertices).min(0)],
                            "box_max": [float(x) for x in np.asarray(mesh.vertices).max(0)]})
-        return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed}
+        return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed, "flow": bool(cfg.get("flow", False))}
 
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
@@ -526,11 +529,13 @@ class S3DISSimulator:
             mover_poses = np.stack([t.poses12(times) for t in movers["tracks"]], axis=1)       # (P, M, 12) float32
             mset = MoverSet(engine.ctx, movers["meshes"])
             try:
-                fr = engine.scan_mover_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, want=want)
+                scan = engine.scan_flow_frames if movers["flow"] else engine.scan_mover_frames
+                fr = scan(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, want=want)
             finally:
                 mset.close()
             sim_scene.mover_tracks = {"period": movers["period"], "objects": movers["objects"], "times": times,
-                                      "states": states, "poses12": mover_poses}
+                                      "states": states, "poses12": mover_poses,
+                                      "sensor_poses": poses_from_waypoints(waypoints)}
         elif materials is not None:
             if dist is not None:
                 raise ValueError("the materials key is not available on a multi-rank process group")
@@ -616,6 +621,9 @@ class S3DISSimulator:
             if "mover" in fr:              # per point: 0 for the room, m + 1 for mover m of the movers key
                 for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
                     f.mover_ids = fr["mover"][e - c:e]
+            if "flow_status" in fr:        # per point: where its surface goes up to the next frame, and whether it is seen there
+                for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
+                    f.flow, f.flow_status = fr["flow"][e - c:e], fr["flow_status"][e - c:e]
             if "bounces" in fr:            # per point: the return's strength, the panes and mirrors on its way, where it came from
                 for f, e, c in zip(sim_scene.frames[first:], ends_l, counts_l):
                     f.intensities, f.bounces, f.surface_points = (fr[a][e - c:e] for a in ("intensity", "bounces", "surface_point3"))
