@@ -751,6 +751,52 @@ int lrc_mover_merge(uint64_t num_rays, uint32_t num_movers, const float* t_stati
                     const float* t_movers, const float* normal3_movers, const float* poses12, float* out_t,
                     float* out_normal3, uint8_t* out_mover);
 
+/* ---- movers under moving-sensor sweeps: per-ray mover pose (opt-in) ----------------------------------
+ * The two features above, composed: ray i of sweep k fires at s = fire[i], is cast from the sensor pose at s (exactly the ray of
+ * lrc_scan_sweeps_dev, bit for bit) and meets every mover at THAT MOVER'S pose at s.  A person who walks through a 0.1 s sweep is
+ * sheared and stretched as in real data; a mover that stands still gives the bytes of lrc_scan_movers_*.
+ *   record    per sweep k and mover m a MOVER SWEEP RECORD: 24 float32, shaped (P, M, 24)
+ *               [0..11]  the mover's pose12 at the START of the sweep
+ *               [12..15] dq = (w, x, y, z), w >= cos(pi/4): R_end = R(dq) R_start
+ *               [16..18] dc = c_end - c_start
+ *               [19..23] zero
+ *             The mover moves between the two poses as the sensor does between its own: the centre straight, the rotation by
+ *             nlerp (the error table of the moving-sensor sweeps applies).
+ *   ray (k, i)  s = (float)fire[i].  All mover arithmetic is float32, one rounding per operation, nothing fused, in this order:
+ *               c_j = c0_j + s*dc_j;   qw = (1 - s) + s*dq.w;   u = (s*dq.x, s*dq.y, s*dq.z)
+ *               n = ((qw*qw + ux*ux) + uy*uy) + uz*uz;   k = 2/n
+ *               for a vector v:  t = u x v, w = u x t  (tx = uy*vz - uz*vy, ty = uz*vx - ux*vz, tz = ux*vy - uy*vx; w alike)
+ *                                forward R(q) v:   v'_j = v_j + k*(qw*t_j + w_j)
+ *                                inverse R(q)^T v: v'_j = v_j + k*(w_j - qw*t_j)
+ *             2 frame   e = o - c;  o' = R_start^T inverse(e),  d' = R_start^T inverse(d)  (R_start^T as step 2 of the moving
+ *                       objects forms it)
+ *             4 record  normal3 = forward(R_start n) of the mover record's normal n (R_start n as step 4 there), not renormalised;
+ *                       the record is the one lrc_scan_sweeps_dev would write for (o, d) had it hit the winner: point3 on the world
+ *                       ray, the range filter about the sensor's centre c(s) in float64
+ *             Steps 1 and 3, the tie rule, the culling and the options are those of the moving objects, unchanged.
+ *   still     a record whose word 12 has the bits of 1.0f and whose words 13..18 are all +0.0f takes steps 2 and 4 of the moving
+ *             objects with its pose12: the same bytes as lrc_scan_movers_dev when the sensor stands still too.
+ * The record interpolates between the poses at the two ends of the sweep and nothing else: a path that turns a corner inside a
+ * sweep is cut straight.
+ * LRC_ERR_INVALID_ARG before any launch: what lrc_scan_movers_* refuse (a range_noise option among it), d_out->tile_count != NULL
+ * and, in lrc_scan_mover_sweeps_compact, what lrc_scan_sweeps_compact refuses (no fire table, a bad sensor record) and a mover
+ * sweep record with an entry that is not finite, a start pose with max |R^T R - I| > 2^-16 or dq.w < cos(pi/4) (as float32).
+ * A NULL set: the bytes of lrc_scan_sweeps_dev and a zero mover column.  Scratch: the set's, 122 bytes per ray whatever M is.
+ *   lrc_scan_mover_sweeps_dev      device pointers, as lrc_scan_sweeps_dev and lrc_scan_movers_dev take them; enqueued on `stream`
+ *   lrc_scan_mover_sweeps_compact  host records, the resident table with its fire table; frames and mover_rows as
+ *                                  lrc_scan_movers_compact (the index column gives each point's firing fraction)
+ *   lrc_mover_sweep_rays           host, no GPU: step 2 for n world rays with their own fire[i] and ONE record
+ *   lrc_mover_sweep_normals        host, no GPU: step 4's normal for n normals with their own fire[i] and ONE record */
+int lrc_scan_mover_sweeps_dev(lrc_scene* scene, lrc_movers* set /* nullable */, const double* d_motion24, uint64_t num_poses,
+                              const double* d_dirs3, const double* d_fire, uint64_t rays_per_pose, const float* d_mover_motion24,
+                              double max_range, const lrc_hits* d_out, uint8_t* d_mover /* nullable */, void* stream);
+int lrc_scan_mover_sweeps_compact(lrc_scene* scene, lrc_movers* set /* nullable */, const double* motion24, uint64_t num_poses,
+                                  const lrc_table* table, const float* mover_motion24, double max_range, const lrc_frames* out,
+                                  uint8_t* mover_rows /* nullable */, uint64_t capacity, uint64_t* out_total);
+int lrc_mover_sweep_rays(const float* rays6, const double* fire, uint64_t num_rays, const float* motion24, float* out_rays6);
+int lrc_mover_sweep_normals(const float* normal3, const double* fire, uint64_t num_rays, const float* motion24,
+                            float* out_normal3);
+
 /* ---- scene flow under movers: per-point flow and visibility at the next frame (opt-in) ----------------
  * For every return of a frame scanned with movers: where the surface the point lies on will be at a NEXT frame, and whether
  * that place can be seen from the next sensor pose (the occlusion mask of scene-flow benchmarks).  "Next" is given per frame,

@@ -389,8 +389,10 @@ class S3DISSimScene:
         """Ground truth of the moving objects of a run under the movers key, written to ``output_dir``/<scene>_mover_tracks.json:
         the period, the object table (mesh, semantic, instance, the mesh's own box) and, per frame and mover, the time, the
         pose (x, y, z, yaw_deg and the row-major 3 x 4 object-to-world matrix), the oriented box (``box7``: world centre,
-        extents of the mesh's own AABB, heading = yaw) and ``num_points``, the frame's returns from that mover.  Returns the
-        dict."""
+        extents of the mesh's own AABB, heading = yaw) and ``num_points``, the frame's returns from that mover.  Under the
+        nested key ``motion: {movers: ...}`` (movers that move while a sweep is scanned) ``pose`` is the pose at the START of the
+        frame's sweep, every mover additionally carries ``end_pose`` (x, y, z, yaw_deg at the END of the sweep) and ``record24``
+        (the mover sweep record the scan used), and every frame ``sweep_duration`` in seconds.  Returns the dict."""
         tr = self.mover_tracks
         if tr is None:
             raise ValueError("this scene was not simulated under the movers key")
@@ -413,7 +415,13 @@ class S3DISSimScene:
                                         "matrix12": [float(v) for v in tr["poses12"][f][m]]},
                                "box7": [float(v) for v in centre] + [float(v) for v in (hi - lo)] + [yaw],
                                "num_points": int(counts[m + 1])})
+                if "end_states" in tr:
+                    ex, ey, ez, eyaw = (float(v) for v in tr["end_states"][f][m])
+                    movers[-1]["end_pose"] = {"x": ex, "y": ey, "z": ez, "yaw_deg": float(np.degrees(eyaw))}
+                    movers[-1]["record24"] = [float(v) for v in tr["records24"][f][m]]
             frames.append({"frame": f, "time": float(tr["times"][f]), "static_points": int(counts[0]), "movers": movers})
+            if "end_states" in tr:
+                frames[-1]["sweep_duration"] = float(tr["sweep_duration"])
         summary = {"scene_name": self.scene_name, "period": float(tr["period"]), "num_frames": len(frames), "objects": objs,
                    "frames": frames}
         out = Path(output_dir)

@@ -541,6 +541,115 @@ __global__ __launch_bounds__(kBlock) void mover_merge_kernel(const TraceParams p
     if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
 }
 
+// ---- movers under moving-sensor sweeps (lrc_scan_mover_sweeps_*; the arithmetic is lrc_movers.h's and gen_ray_sweep's, the
+// orchestration mover_sweeps_scan_dev's) ----------------------------------------------------------------------------------
+// The 19 words of mover sweep record (pose, m) that are read: through the scalar cache where a wave lies in one sweep.
+__device__ __forceinline__ void mover_record_load(const float* motion24, uint32_t pose, uint32_t M, uint32_t m, int uniform, float* out19) {
+    const float* mp = motion24 + ((size_t)pose * M + m) * 24;
+    if (uniform) {
+        cfloat* c = (cfloat*)mp;
+#pragma unroll
+        for (int k = 0; k < 19; ++k) out19[k] = c[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 19; ++k) out19[k] = mp[k];
+    }
+}
+
+// The sweep ray kernel: one thread per (sweep, i).  The static pass (q.motion24 == NULL) forms gen_ray_sweep's bits once and
+// stores them as the world ray; a mover's pass reads that world ray back (no float64 chain, no division per mover), takes it into
+// the frame the mover has at s = (float)fire[i] (lrcmov::to_object_at) and stores it with the keep byte of the explicit-ray launch
+// (0: left out by lrcmov::culled, no ray stored).  The still test of a record is wave-uniform with `uniform`.
+__global__ __launch_bounds__(kBlock) void mover_sweep_rays_kernel(const double* __restrict__ motion24, const double* __restrict__ dirs3,
+                                                                  const double* __restrict__ fire, uint64_t rays_per_pose,
+                                                                  uint64_t total, const lrcmov::SweepRayPass q, int uniform,
+                                                                  float* __restrict__ world6, float* __restrict__ rays6,
+                                                                  uint8_t* __restrict__ keep) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= total) return;
+    const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
+    const uint64_t i = gid - (uint64_t)pose * rays_per_pose;
+    if (q.motion24 == nullptr) {
+        V3 o, d;
+        gen_ray_sweep(motion24, dirs3, fire, pose, i, o, d);
+        float2* w = (float2*)(world6 + gid * 6);      // 24-byte records: 8-byte aligned
+        w[0] = make_float2(o.x, o.y);
+        w[1] = make_float2(o.z, d.x);
+        w[2] = make_float2(d.y, d.z);
+        return;
+    }
+    float r19[19];
+    mover_record_load(q.motion24, pose, q.M, q.m, uniform, r19);
+    const float2* w = (const float2*)(world6 + gid * 6);
+    const float2 a = w[0], b = w[1], c = w[2];
+    lrcmov::Vec ro, rd;
+    lrcmov::to_object_at(r19, (float)fire[i], lrcmov::Vec{a.x, a.y, b.x}, lrcmov::Vec{b.y, c.x, c.y}, ro, rd);
+    const bool out = lrcmov::culled(q.sphere, ro, rd);
+    keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
+    if (out) return;
+    float2* r = (float2*)(rays6 + gid * 6);
+    r[0] = make_float2(ro.x, ro.y);
+    r[1] = make_float2(ro.z, rd.x);
+    r[2] = make_float2(rd.y, rd.z);
+}
+
+// The sweep merge kernel's view of one mover's pass: MoverMerge with the mover sweep records in the place of the poses, and the
+// stored world rays.  p.motion24 / p.fire are the SENSOR's records and the firing fractions.
+struct MoverSweepMerge {
+    const float* motion24;     // (P, M, 24)
+    const float* world6;       // the static pass's world rays
+    uint32_t M, m;
+    int uniform, last;
+    float* w_t; uint32_t* w_prim; float* w_n3; uint16_t* w_sem; uint16_t* w_ins; uint8_t* w_who;
+    const float* m_t; const uint32_t* m_prim; const float* m_n3; const uint16_t* m_sem; const uint16_t* m_ins;
+    uint8_t* d_mover;          // nullable
+};
+
+// One thread per (sweep, i): the running winner against mover q.m (lrcmov::takes), the mover's normal turned into the world by the
+// pose the mover has at s (lrcmov::to_world_at).  Every pass but the last stores the winner; the last writes the record
+// lrc_scan_sweeps_dev would write had the ray hit the winner (write_back, GIVEN: the stored world ray, the filter centre
+// sweep_centre forms from the sensor's record), filter included, and the mover column.
+__global__ __launch_bounds__(kBlock) void mover_sweep_merge_kernel(const TraceParams p, const MoverSweepMerge q) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= p.total) return;
+    float t = q.w_t[gid];
+    uint32_t prim = q.w_prim[gid];
+    uint32_t label = (uint32_t)q.w_sem[gid] | ((uint32_t)q.w_ins[gid] << 16);
+    V3 n{q.w_n3[gid * 3], q.w_n3[gid * 3 + 1], q.w_n3[gid * 3 + 2]};
+    uint32_t who = q.w_who[gid];
+    const uint32_t pose = mover_pose_of(gid, p.rays_per_pose, q.uniform);
+    const uint64_t i = gid - (uint64_t)pose * p.rays_per_pose;
+    const float tm = q.m_t[gid];
+    if (lrcmov::takes(tm, t)) {
+        float r19[19];
+        mover_record_load(q.motion24, pose, q.M, q.m, q.uniform, r19);
+        const lrcmov::Vec w = lrcmov::to_world_at(r19, (float)p.fire[i], lrcmov::Vec{q.m_n3[gid * 3], q.m_n3[gid * 3 + 1], q.m_n3[gid * 3 + 2]});
+        t = tm;
+        prim = q.m_prim[gid];
+        label = (uint32_t)q.m_sem[gid] | ((uint32_t)q.m_ins[gid] << 16);
+        n = V3{w.x, w.y, w.z};
+        who = q.m + 1u;
+    }
+    if (!q.last) {
+        q.w_t[gid] = t;
+        q.w_prim[gid] = prim;
+        q.w_n3[gid * 3] = n.x; q.w_n3[gid * 3 + 1] = n.y; q.w_n3[gid * 3 + 2] = n.z;
+        q.w_sem[gid] = (uint16_t)(label & 0xFFFFu);
+        q.w_ins[gid] = (uint16_t)(label >> 16);
+        q.w_who[gid] = (uint8_t)who;
+        return;
+    }
+    const float2* wr = (const float2*)(q.world6 + gid * 6);
+    const float2 a = wr[0], b = wr[1], c = wr[2];
+    const V3 o{a.x, a.y, b.x}, d{b.y, c.x, c.y};
+    double cx, cy, cz;
+    sweep_centre(p.motion24 + (size_t)pose * 24, p.fire[i], cx, cy, cz);
+    const bool hit = t < __builtin_inff();
+    const bool kept = write_back<true, false, true, false, true>(p, gid, threadIdx.x, o, d, cx, cy, cz, t, hit ? prim : 0xFFFFFFFFu,
+                                                                 label, false, V3{0.f, 0.f, 0.f}, 0.f, n);
+    if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
+}
+
 // ---- scene flow under movers (lrc_scan_flow_*; the arithmetic is lrc_flow.h's, the orchestration flow_scan_dev's) -------------
 // What the flow's ray kernel reads and writes.  The four line-of-sight columns are NULL together (flow only).
 struct FlowRays {
@@ -4223,6 +4332,88 @@ int movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint
     return LRC_OK;
 }
 
+// movers_scan_dev under moving-sensor sweeps.  A NULL set: the launch of lrc_scan_sweeps_dev and a zero mover column.  Otherwise
+//   the static pass    mover_sweep_rays_kernel (gen_ray_sweep's world rays, stored) and the explicit-ray launch on the scene
+//   per mover m        mover_sweep_rays_kernel (the stored world ray in the frame the mover has at the ray's s + keep bytes), the
+//                      explicit-ray launch on the mover's scene, and mover_sweep_merge_kernel, whose last pass writes the records
+// in the set's scratch: what movers_scan_dev holds there plus the world ray set (24 bytes per ray), grown under the same rule.
+int mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
+                          const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range, const lrc_hits* d_out,
+                          uint8_t* d_mover, hipStream_t st) {
+    const uint64_t n = P * N;
+    if (!n) return LRC_OK;
+    if (!set) {
+        TraceParams p{};
+        p.motion24 = d_motion24;
+        p.dirs3 = d_dirs3;
+        p.fire = d_fire;
+        scan_fields(p, N, n, max_range, d_out);
+        const int rc = launch_trace(s, p, kGenSweeps, st);
+        if (rc) return rc;
+        if (d_mover) LRC_HIP(hipMemsetAsync(d_mover, 0, n, st));
+        return LRC_OK;
+    }
+    if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_mover_sweeps: too many sweeps or rays for one call");
+    // scratch, 256-byte aligned columns: world6 | rays6 | keep | winner (t, prim, normal3, sem, ins, who) | mover (t, prim, normal3, sem, ins)
+    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
+    const uint64_t sizes[14] = {n * 24, n * 24, n, n * 4, n * 4, n * 12, n * 2, n * 2, n, n * 4, n * 4, n * 12, n * 2, n * 2};
+    uint64_t off[15] = {0};
+    for (int k = 0; k < 14; ++k) off[k + 1] = off[k] + al(sizes[k]);
+    if (set->scratch_cap < off[14]) {
+        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
+        if (set->scratch) { (void)hipFree(set->scratch); set->scratch = nullptr; set->scratch_cap = 0; }
+        LRC_HIP(hipMalloc(&set->scratch, off[14] + off[14] / 8));
+        set->scratch_cap = off[14] + off[14] / 8;
+    }
+    uint8_t* const b = (uint8_t*)set->scratch;
+    float* const world6 = (float*)(b + off[0]);
+    float* const rays6 = (float*)(b + off[1]);
+    uint8_t* const keep = b + off[2];
+    lrc_hits w{}, mv{};
+    w.t = (float*)(b + off[3]); w.prim = (uint32_t*)(b + off[4]); w.normal3 = (float*)(b + off[5]);
+    w.sem = (uint16_t*)(b + off[6]); w.ins = (uint16_t*)(b + off[7]);
+    uint8_t* const who = b + off[8];
+    mv.t = (float*)(b + off[9]); mv.prim = (uint32_t*)(b + off[10]); mv.normal3 = (float*)(b + off[11]);
+    mv.sem = (uint16_t*)(b + off[12]); mv.ins = (uint16_t*)(b + off[13]);
+    const dim3 grid((uint32_t)blocks_of(n, kBlock));
+    const int uniform = N % 64 == 0;
+    const uint32_t M = (uint32_t)set->scenes.size();
+    int rc;
+    lrcmov::SweepRayPass rp{};
+    hipLaunchKernelGGL(mover_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, N, n, rp, uniform, world6,
+                       rays6, keep);
+    LRC_HIP(hipGetLastError());
+    if ((rc = cast_plain(s, world6, nullptr, n, w, st))) return rc;
+    LRC_HIP(hipMemsetAsync(who, 0, n, st));
+    TraceParams p{};       // what write_back reads: the sweep's inputs, the filter, the scene's options, the caller's records
+    p.motion24 = d_motion24;
+    p.dirs3 = d_dirs3;
+    p.fire = d_fire;
+    scan_fields(p, N, n, max_range, d_out);
+    p.min_range = s->opts.min_range;
+    p.incident_mode = s->opts.incident_mode;
+    for (uint32_t m = 0; m < M; ++m) {
+        lrc_scene* const ms = set->scenes[m];
+        rp.motion24 = d_mover_motion24;
+        rp.M = M;
+        rp.m = m;
+        rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
+        hipLaunchKernelGGL(mover_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, N, n, rp, uniform, world6,
+                           rays6, keep);
+        LRC_HIP(hipGetLastError());
+        if ((rc = cast_plain(ms, rays6, keep, n, mv, st))) return rc;
+        MoverSweepMerge q{};
+        q.motion24 = d_mover_motion24; q.world6 = world6; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
+        q.w_t = w.t; q.w_prim = w.prim; q.w_n3 = w.normal3; q.w_sem = w.sem; q.w_ins = w.ins; q.w_who = who;
+        q.m_t = mv.t; q.m_prim = mv.prim; q.m_n3 = mv.normal3; q.m_sem = mv.sem; q.m_ins = mv.ins;
+        q.d_mover = d_mover;
+        hipLaunchKernelGGL(mover_sweep_merge_kernel, grid, dim3(kBlock), 0, st, p, q);
+        LRC_HIP(hipGetLastError());
+    }
+    return LRC_OK;
+}
+
 // lrc_scan_flow_dev behind its checks (lrc_flow.hip).  All on `st`, nothing waited for:
 //   the ray kernel     flow_rays_kernel: the flow and, with d_status, the world line of sight, its cast byte, thr, the first status
 //   the static pass    the explicit-ray launch on the scene, straight into the running minimum
@@ -4303,6 +4494,8 @@ int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const ui
 // first, then exactly the kept rows.  The mover column stays at the fixed stride and is gathered for the kept rows by the
 // compacted index column (gather_rows_by_index above).
 // With `flow` (flow_scan_compact): the flow and its status at the fixed stride behind the mover scan, gathered like the mover column.
+// With `motion24` (mover_sweeps_scan_compact): poses16 is unread, the P sensor records are staged in its place, `mover_poses12`
+// holds the (P, M, 24) mover sweep records, the table brings its fire table and mover_sweeps_scan_dev scans.
 namespace {
 struct FlowCompact {
     FlowNext next;             // host pointers
@@ -4311,8 +4504,8 @@ struct FlowCompact {
 };
 int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
                    const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
-                   uint64_t* out_total, const FlowCompact* flow) {
-    const char* const who = flow ? "lrc_scan_flow_compact" : "lrc_scan_movers_compact";
+                   uint64_t* out_total, const FlowCompact* flow, const double* motion24 = nullptr) {
+    const char* const who = motion24 ? "lrc_scan_mover_sweeps_compact" : flow ? "lrc_scan_flow_compact" : "lrc_scan_movers_compact";
     SyncUnlessOk guard;
     lrc_ctx* const ctx = s->ctx;
     const uint64_t N = table->n, n = P * N;
@@ -4325,8 +4518,10 @@ int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_
     } drain{cs};
     const double* d_poses = nullptr;
     const float* d_mp = nullptr;
-    if ((rc = stage_input(ctx, kPoolPoses, poses16, P * 16, &d_poses, &cs))) return rc;
-    if (set && (rc = stage_input(ctx, kPoolNoise, mover_poses12, P * set->scenes.size() * 12, &d_mp, &cs))) return rc;
+    if ((rc = motion24 ? stage_input(ctx, kPoolPoses, motion24, P * 24, &d_poses, &cs)
+                       : stage_input(ctx, kPoolPoses, poses16, P * 16, &d_poses, &cs)))
+        return rc;
+    if (set && (rc = stage_input(ctx, kPoolNoise, mover_poses12, P * set->scenes.size() * (motion24 ? 24 : 12), &d_mp, &cs))) return rc;
     FrameStage st;
     if ((rc = st.alloc(ctx, *out, P, n))) return rc;
     st.rec.tile_count = nullptr;
@@ -4358,7 +4553,10 @@ int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_
         LRC_HIP(hipHostMalloc((void**)&ctx->h_counts, (P + P / 4 + 64) * 8 * 5, hipHostMallocDefault));
         ctx->h_counts_cap = P + P / 4 + 64;
     }
-    if ((rc = movers_scan_dev(s, set, d_poses, P, table->d_dirs3, N, d_mp, max_range, &st.rec, (uint8_t*)mbuf.p, cs))) return rc;
+    if ((rc = motion24 ? mover_sweeps_scan_dev(s, set, d_poses, P, table->d_dirs3, table->d_fire, N, d_mp, max_range, &st.rec,
+                                               (uint8_t*)mbuf.p, cs)
+                       : movers_scan_dev(s, set, d_poses, P, table->d_dirs3, N, d_mp, max_range, &st.rec, (uint8_t*)mbuf.p, cs)))
+        return rc;
     if (want_flow && (rc = flow_scan_dev(s, set, &st.rec, (const uint8_t*)mbuf.p, P, N, d_mp, d_next, max_range, (float*)fbuf.p,
                                          (uint8_t*)sbuf.p, cs)))
         return rc;
@@ -4389,6 +4587,32 @@ int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, ui
                         const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
                         uint64_t* out_total) {
     return movers_compact(s, set, poses16, P, table, mover_poses12, max_range, out, mover_rows, capacity, out_total, nullptr);
+}
+
+// Host check of (P,24) motion records (lrc_scan_sweeps_compact): finite, dq.w >= cos(pi/4) (a rotation of at most pi/2 per
+// sweep, where the nlerp error table of include/lidarcast.h holds), |dq| = 1 to 1e-6.  Declared in lrc_internal.h: the checks of
+// lrc_scan_mover_sweeps_compact (lrc_movers.hip) make it too.
+int check_motion(const char* who, const double* m, uint64_t P) {
+    constexpr double kCosQuarterPi = 0.70710678118654752440;
+    for (uint64_t k = 0; k < P; ++k) {
+        const double* r = m + k * 24;
+        for (int j = 0; j < 24; ++j)
+            if (!std::isfinite(r[j]))
+                return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) + " is not finite");
+        if (r[12] < kCosQuarterPi)
+            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) +
+                                                 " rotates by more than pi/2 per sweep (dq.w < cos(pi/4))");
+        const double n = ((r[12] * r[12] + r[13] * r[13]) + r[14] * r[14]) + r[15] * r[15];
+        if (!(std::fabs(n - 1.0) <= 1e-6))
+            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) + " has a non-unit dq");
+    }
+    return LRC_OK;
+}
+
+int mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
+                              const float* mover_motion24, double max_range, const lrc_frames* out, uint8_t* mover_rows,
+                              uint64_t capacity, uint64_t* out_total) {
+    return movers_compact(s, set, nullptr, P, table, mover_motion24, max_range, out, mover_rows, capacity, out_total, nullptr, motion24);
 }
 
 int flow_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
@@ -4471,25 +4695,6 @@ int lrc_table_set_fire(lrc_table* t, const double* fire, uint64_t N) {
     LRC_HIP(hipSetDevice(t->ctx->device));
     if (!t->d_fire) LRC_HIP(hipMalloc((void**)&t->d_fire, N * 8));
     LRC_HIP(hipMemcpy(t->d_fire, fire, N * 8, hipMemcpyHostToDevice));
-    return LRC_OK;
-}
-
-// Host check of (P,24) motion records (lrc_scan_sweeps_compact): finite, dq.w >= cos(pi/4) (a rotation of at most pi/2 per
-// sweep, where the nlerp error table of include/lidarcast.h holds), |dq| = 1 to 1e-6.
-static int check_motion(const char* who, const double* m, uint64_t P) {
-    constexpr double kCosQuarterPi = 0.70710678118654752440;
-    for (uint64_t k = 0; k < P; ++k) {
-        const double* r = m + k * 24;
-        for (int j = 0; j < 24; ++j)
-            if (!std::isfinite(r[j]))
-                return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) + " is not finite");
-        if (r[12] < kCosQuarterPi)
-            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) +
-                                                 " rotates by more than pi/2 per sweep (dq.w < cos(pi/4))");
-        const double n = ((r[12] * r[12] + r[13] * r[13]) + r[14] * r[14]) + r[15] * r[15];
-        if (!(std::fabs(n - 1.0) <= 1e-6))
-            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": record " + std::to_string(k) + " has a non-unit dq");
-    }
     return LRC_OK;
 }
 

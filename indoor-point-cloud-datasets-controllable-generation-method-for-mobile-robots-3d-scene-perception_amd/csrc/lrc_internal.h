@@ -230,6 +230,18 @@ int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, ui
 int check_call(const char* who, const lrc_scene* s, const lrc_movers* set, const void* out);
 int check_poses12(const char* who, const float* m, uint64_t count);
 
+// movers under moving-sensor sweeps: the same split.  lidarcast.hip: mover_sweeps_scan_dev (movers_scan_dev with the sensor's
+// (P,24) float64 records, the firing fractions and the (P, M, 24) float32 mover sweep records; set == NULL: the scan of
+// lrc_scan_sweeps_dev and a zero mover column), mover_sweeps_scan_compact (host records, the table with its fire table) and
+// check_motion, the host check of (P,24) sensor records every *_sweeps_compact call makes.
+int mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
+                          const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range, const lrc_hits* d_out,
+                          uint8_t* d_mover, hipStream_t st);
+int mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
+                              const float* mover_motion24, double max_range, const lrc_frames* out, uint8_t* mover_rows,
+                              uint64_t capacity, uint64_t* out_total);
+int check_motion(const char* who, const double* m, uint64_t P);
+
 // scene flow under movers.  lrc_flow.hip checks the arguments of lrc_scan_flow_* and owns the host functions; lidarcast.hip holds
 // the kernels and enqueues the passes (flow_scan_dev: everything on `st`, no host synchronisation; d_status == NULL: the flow
 // alone, nothing cast) and scans to frames (flow_scan_compact: the mover scan and the flow at the fixed stride, then the frame

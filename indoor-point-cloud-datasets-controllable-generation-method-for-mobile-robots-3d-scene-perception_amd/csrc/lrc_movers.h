@@ -1,6 +1,6 @@
 // lrc_movers.h -- rigid movers of lrc_scan_movers_* (include/lidarcast.h "moving objects"): the three
 // pieces of arithmetic the mover kernels of lidarcast.hip and the host functions lrc_mover_rays / lrc_mover_merge share,
-// written once for both.
+// written once for both.  Below them: the per-ray mover pose of lrc_scan_mover_sweeps_* (DESIGN.md section 5n).
 //
 //   pose12    the row-major 3 x 4 [R | c] from object to world: R[i][j] = m[4 i + j], c_i = m[4 i + 3]
 //   to_object e = o - c; o'_j = (R[0][j] * e_x + R[1][j] * e_y) + R[2][j] * e_z; d'_j the same expression on d
@@ -90,6 +90,74 @@ LRC_VHD bool culled(const Sphere s, Vec o, Vec d) {
 // What the ray kernel needs of one mover of a call (lidarcast.hip, mover_rays_kernel).
 struct RayPass {
     const float* poses12;      // device: (P, M, 12); NULL: the static pass, the world ray itself, nothing culled
+    uint32_t M, m;
+    Sphere sphere;
+};
+
+// ---- movers under moving-sensor sweeps (lrc_scan_mover_sweeps_*; include/lidarcast.h "movers under moving-sensor sweeps",
+// DESIGN.md section 5n) -----------------------------------------------------------------------------------------------------
+// Mover sweep record of (sweep, mover), 24 float32: r[0..11] the START pose12, r[12..15] dq = (w, x, y, z) with
+// R_end = R(dq) R_start and w >= cos(pi/4), r[16..18] dc = c_end - c_start, the rest zero.  Ray i fires at s = (float)fire[i] and
+// meets the mover at its pose at s.  Every operation is a separate IEEE float32 operation in exactly this order (nothing fused;
+// tests/mover_sweep_restate.py restates it op for op in numpy):
+//   pose at s   c_j = c0_j + s * dc_j                                                 (a product, then a sum)
+//               qw = (1 - s) + s * dq.w;  u = (s * dq.x, s * dq.y, s * dq.z)          (nlerp, never normalised)
+//               n = ((qw*qw + ux*ux) + uy*uy) + uz*uz;  k = 2 / n
+//   cross       t = u x v:  tx = uy*vz - uz*vy,  ty = uz*vx - ux*vz,  tz = ux*vy - uy*vx
+//               w = u x t:  wx = uy*tz - uz*ty,  wy = uz*tx - ux*tz,  wz = ux*ty - uy*tx
+//   forward     R(q) v:    v'_j = v_j + k * (qw * t_j + w_j)                          (gen_ray_sweep's form, in float32)
+//   inverse     R(q)^T v:  v'_j = v_j + k * (w_j - qw * t_j)                          (the conjugate: u -> -u flips t, keeps w)
+//   to_object_at  e = o - c (three subtractions);  o' = rot_to_object(R_start, inverse(e));  d' = rot_to_object(R_start, inverse(d))
+//   to_world_at   n' = forward(to_world(R_start, n)), not renormalised
+// A STILL record -- r[12] has the bits of 1.0f and r[13..18] are all +0.0f, tested on the seven words -- takes to_object /
+// to_world with r[0..11] instead, so a mover that stands still through a sweep gives the bits of lrc_scan_movers_*.  (A -0.0 among
+// the six words is no still record: it takes the general path, whose result then differs from the still one in signed zeros only.)
+struct At { float cx, cy, cz, qw, ux, uy, uz, k; };
+
+LRC_VHD bool still(const float* r) {
+    uint32_t w[7];
+    __builtin_memcpy(w, r + 12, 28);
+    return (w[0] == 0x3F800000u) & ((w[1] | w[2] | w[3] | w[4] | w[5] | w[6]) == 0u);
+}
+
+LRC_VHD At pose_at(const float* r, float s) {
+    At a;
+    a.cx = r[3] + s * r[16];
+    a.cy = r[7] + s * r[17];
+    a.cz = r[11] + s * r[18];
+    a.qw = (1.0f - s) + s * r[12];
+    a.ux = s * r[13]; a.uy = s * r[14]; a.uz = s * r[15];
+    const float n = ((a.qw * a.qw + a.ux * a.ux) + a.uy * a.uy) + a.uz * a.uz;
+    a.k = 2.0f / n;
+    return a;
+}
+
+// R(q) v (inverse == false) or R(q)^T v (inverse == true)
+LRC_VHD Vec rot_at(const At& a, Vec v, bool inverse) {
+    const float tx = a.uy * v.z - a.uz * v.y, ty = a.uz * v.x - a.ux * v.z, tz = a.ux * v.y - a.uy * v.x;
+    const float wx = a.uy * tz - a.uz * ty, wy = a.uz * tx - a.ux * tz, wz = a.ux * ty - a.uy * tx;
+    if (inverse) return Vec{v.x + a.k * (wx - a.qw * tx), v.y + a.k * (wy - a.qw * ty), v.z + a.k * (wz - a.qw * tz)};
+    return Vec{v.x + a.k * (a.qw * tx + wx), v.y + a.k * (a.qw * ty + wy), v.z + a.k * (a.qw * tz + wz)};
+}
+
+// the world ray (o, d) in the frame the mover of record r has at s
+LRC_VHD void to_object_at(const float* r, float s, Vec o, Vec d, Vec& oo, Vec& od) {
+    if (still(r)) { to_object(r, o, d, oo, od); return; }
+    const At a = pose_at(r, s);
+    const Vec e{o.x - a.cx, o.y - a.cy, o.z - a.cz};
+    oo = rot_to_object(r, rot_at(a, e, true));
+    od = rot_to_object(r, rot_at(a, d, true));
+}
+
+// the mover record's normal in the world, by the pose the mover of record r has at s
+LRC_VHD Vec to_world_at(const float* r, float s, Vec n) {
+    if (still(r)) return to_world(r, n);
+    return rot_at(pose_at(r, s), to_world(r, n), false);
+}
+
+// What the sweep ray kernel needs of one mover of a call (lidarcast.hip, mover_sweep_rays_kernel).
+struct SweepRayPass {
+    const float* motion24;     // device: the mover sweep records (P, M, 24); NULL: the static pass, the world ray is formed and stored
     uint32_t M, m;
     Sphere sphere;
 };

@@ -1,7 +1,9 @@
 // lrc_movers.hip -- host side of the moving objects (lrc_movers.h): the mover set, the checks of lrc_scan_movers_dev /
 // lrc_scan_movers_compact (the kernels, the launches and the frame path are lidarcast.hip's: movers_scan_dev,
 // movers_scan_compact) and the two host functions lrc_mover_rays and lrc_mover_merge, which run the inline functions the
-// kernels call on arrays.
+// kernels call on arrays.  The same for the movers under moving-sensor sweeps: the checks of lrc_scan_mover_sweeps_dev /
+// lrc_scan_mover_sweeps_compact (mover_sweeps_scan_dev, mover_sweeps_scan_compact) and the host functions lrc_mover_sweep_rays and
+// lrc_mover_sweep_normals.
 #include <cmath>
 
 #include "lrc_internal.h"
@@ -20,23 +22,47 @@ int check_call(const char* who, const lrc_scene* s, const lrc_movers* set, const
     return LRC_OK;
 }
 
+// one host pose12 `q`, named `what` k in the message: every entry finite, max |R^T R - I| <= 2^-16 in float64
+static int check_pose12(const char* who, const char* what, uint64_t k, const float* q) {
+    for (int e = 0; e < 12; ++e)
+        if (!std::isfinite(q[e]))
+            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": " + what + " " + std::to_string(k) + " has an entry that is not finite");
+    double worst = 0.0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            double dot = 0.0;
+            for (int r = 0; r < 3; ++r) dot += (double)q[4 * r + a] * (double)q[4 * r + b];
+            worst = std::fmax(worst, std::fabs(dot - (a == b ? 1.0 : 0.0)));
+        }
+    if (worst > lrcmov::kOrthoTol)
+        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": " + what + " " + std::to_string(k) + " is no rotation: max |R^T R - I| = " +
+                                             std::to_string(worst) + " > 2^-16");
+    return LRC_OK;
+}
+
 // host-pose entry point: every entry finite, max |R^T R - I| <= 2^-16 in float64
 int check_poses12(const char* who, const float* m, uint64_t count) {
     for (uint64_t k = 0; k < count; ++k) {
-        const float* q = m + k * 12;
-        for (int e = 0; e < 12; ++e)
-            if (!std::isfinite(q[e]))
-                return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover pose " + std::to_string(k) + " has an entry that is not finite");
-        double worst = 0.0;
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) {
-                double dot = 0.0;
-                for (int r = 0; r < 3; ++r) dot += (double)q[4 * r + a] * (double)q[4 * r + b];
-                worst = std::fmax(worst, std::fabs(dot - (a == b ? 1.0 : 0.0)));
-            }
-        if (worst > lrcmov::kOrthoTol)
-            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover pose " + std::to_string(k) + " is no rotation: max |R^T R - I| = " +
-                                                 std::to_string(worst) + " > 2^-16");
+        const int rc = check_pose12(who, "mover pose", k, m + k * 12);
+        if (rc) return rc;
+    }
+    return LRC_OK;
+}
+
+// host mover sweep records (count x 24 float32): every entry finite, the start pose a rotation as check_poses12 asks, dq.w >=
+// cos(pi/4) (at most pi/2 per sweep, where the nlerp error table of include/lidarcast.h holds)
+static int check_motion24(const char* who, const float* m, uint64_t count) {
+    constexpr double kCosQuarterPi = 0.70710678118654752440;
+    for (uint64_t k = 0; k < count; ++k) {
+        const float* r = m + k * 24;
+        for (int e = 12; e < 24; ++e)
+            if (!std::isfinite(r[e]))
+                return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover sweep record " + std::to_string(k) + " has an entry that is not finite");
+        const int rc = check_pose12(who, "mover sweep record", k, r);
+        if (rc) return rc;
+        if (r[12] < (float)kCosQuarterPi)      // the float32 nearest cos(pi/4): a quarter turn narrowed from float64 passes
+            return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover sweep record " + std::to_string(k) +
+                                                 " rotates by more than pi/2 per sweep (dq.w < cos(pi/4))");
     }
     return LRC_OK;
 }
@@ -136,6 +162,68 @@ int lrc_mover_merge(uint64_t n, uint32_t M, const float* t_static, const float* 
         out_t[i] = t;
         out_normal3[i * 3] = nn.x; out_normal3[i * 3 + 1] = nn.y; out_normal3[i * 3 + 2] = nn.z;
         out_mover[i] = who;
+    }
+    return LRC_OK;
+}
+
+// ---- movers under moving-sensor sweeps ---------------------------------------------------------------------------------------
+
+int lrc_scan_mover_sweeps_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
+                              const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range,
+                              const lrc_hits* d_out, uint8_t* d_mover, void* stream) {
+    int rc = check_call("lrc_scan_mover_sweeps_dev", s, set, d_out);
+    if (rc) return rc;
+    if (d_out->tile_count)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_mover_sweeps_dev: tile_count is not written by this scan (lrc_compact_dev counts itself)");
+    if (P && N && (!d_motion24 || !d_dirs3 || !d_fire))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_mover_sweeps_dev: motion24, dirs3 or fire is NULL");
+    if (P && N && set && !d_mover_motion24) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_mover_sweeps_dev: mover_motion24 is NULL");
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    return mover_sweeps_scan_dev(s, set, d_motion24, P, d_dirs3, d_fire, N, d_mover_motion24, max_range, d_out, d_mover,
+                                 (hipStream_t)stream);
+}
+
+int lrc_scan_mover_sweeps_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
+                                  const float* mover_motion24, double max_range, const lrc_frames* out, uint8_t* mover_rows,
+                                  uint64_t capacity, uint64_t* out_total) {
+    const char* const who = "lrc_scan_mover_sweeps_compact";
+    if (out_total) *out_total = 0;
+    int rc = check_call(who, s, set, out);
+    if (rc) return rc;
+    if (!table) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table is NULL");
+    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table and scene belong to different contexts");
+    if (!table->d_fire) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": the table has no fire table (lrc_table_set_fire)");
+    if (!(P * table->n)) return LRC_OK;
+    if (!motion24 || !out->counts) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": motion24 or counts is NULL");
+    if (table->n > 0xFFFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": rays_per_pose must stay below 2^32 (the index column)");
+    if ((rc = check_motion(who, motion24, P))) return rc;
+    if (set) {
+        if (!mover_motion24) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_motion24 is NULL");
+        if ((rc = check_motion24(who, mover_motion24, P * set->scenes.size()))) return rc;
+    }
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    return mover_sweeps_scan_compact(s, set, motion24, P, table, mover_motion24, max_range, out, mover_rows, capacity, out_total);
+}
+
+int lrc_mover_sweep_rays(const float* rays6, const double* fire, uint64_t n, const float* motion24, float* out_rays6) {
+    if (!motion24 || (n && (!rays6 || !fire || !out_rays6))) return fail(LRC_ERR_INVALID_ARG, "lrc_mover_sweep_rays: NULL argument");
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* r = rays6 + i * 6;
+        lrcmov::Vec oo, od;
+        lrcmov::to_object_at(motion24, (float)fire[i], lrcmov::Vec{r[0], r[1], r[2]}, lrcmov::Vec{r[3], r[4], r[5]}, oo, od);
+        float* w = out_rays6 + i * 6;
+        w[0] = oo.x; w[1] = oo.y; w[2] = oo.z; w[3] = od.x; w[4] = od.y; w[5] = od.z;
+    }
+    return LRC_OK;
+}
+
+int lrc_mover_sweep_normals(const float* normal3, const double* fire, uint64_t n, const float* motion24, float* out_normal3) {
+    if (!motion24 || (n && (!normal3 || !fire || !out_normal3))) return fail(LRC_ERR_INVALID_ARG, "lrc_mover_sweep_normals: NULL argument");
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* q = normal3 + i * 3;
+        const lrcmov::Vec w = lrcmov::to_world_at(motion24, (float)fire[i], lrcmov::Vec{q[0], q[1], q[2]});
+        out_normal3[i * 3] = w.x; out_normal3[i * 3 + 1] = w.y; out_normal3[i * 3 + 2] = w.z;
     }
     return LRC_OK;
 }

@@ -42,6 +42,7 @@ SYMBOLS = (
     "lrc_material_step",
     "lrc_movers_create", "lrc_movers_destroy", "lrc_scan_movers_dev", "lrc_scan_movers_compact", "lrc_mover_rays",
     "lrc_mover_merge",
+    "lrc_scan_mover_sweeps_dev", "lrc_scan_mover_sweeps_compact", "lrc_mover_sweep_rays", "lrc_mover_sweep_normals",
     "lrc_scan_flow_dev", "lrc_scan_flow_compact", "lrc_flow_rays", "lrc_flow_status",
     "lrc_compact", "lrc_compact_dev", "lrc_cloud_from_ranges_dev", "lrc_cloud_from_prims_dev",
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
@@ -294,6 +295,10 @@ def load():
         "lrc_scan_movers_compact": [vp, vp, vp, u64, vp, vp, dbl, C.POINTER(LrcFrames), vp, u64, C.POINTER(u64)],
         "lrc_mover_rays": [vp, u64, vp, vp],
         "lrc_mover_merge": [u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrc_scan_mover_sweeps_dev": [vp, vp, vp, u64, vp, vp, u64, vp, dbl, C.POINTER(LrcHits), vp, vp],
+        "lrc_scan_mover_sweeps_compact": [vp, vp, vp, u64, vp, vp, dbl, C.POINTER(LrcFrames), vp, u64, C.POINTER(u64)],
+        "lrc_mover_sweep_rays": [vp, vp, u64, vp, vp],
+        "lrc_mover_sweep_normals": [vp, vp, u64, vp, vp],
         "lrc_scan_flow_dev": [vp, vp, C.POINTER(LrcHits), vp, u64, u64, vp, vp, vp, vp, dbl, vp, vp, vp],
         "lrc_scan_flow_compact": [vp, vp, vp, u64, vp, vp, vp, vp, vp, dbl, C.POINTER(LrcFrames), vp, vp, vp, u64, C.POINTER(u64)],
         "lrc_flow_rays": [vp, vp, vp, u64, u64, C.c_uint32, vp, vp, vp, vp, dbl, dbl, vp, vp, vp, vp, vp],

@@ -4,6 +4,11 @@
 a timed path into the (12,) float32 object-to-world poses the scan takes.  ``Scene.scan_movers_dev`` /
 ``Scene.scan_movers_compact`` trace the static scene once and every mover in its own frame, and keep the nearest;
 ``rays`` and ``merge`` are the two host steps of that, without a GPU (lrc_mover_rays, lrc_mover_merge).
+
+Movers under moving-sensor sweeps are this module's own, as the noisy sweeps are ``lidarcast.noise``'s:
+``sweep_records`` makes the (P, M, 24) mover sweep records from tracks, ``sweep_rays`` / ``sweep_normals`` are the host steps,
+``scan_mover_sweeps_dev``, ``scan_mover_sweeps_compact`` and ``scan_mover_sweep_frames`` the scans -- module functions that take
+the scene or the engine as their first argument.
 """
 import ctypes as C
 
@@ -150,3 +155,133 @@ def merge(t_static, normal3_static, t_movers, normal3_movers, poses12):
     check(lib.lrc_mover_merge(n, M, ts.ctypes.data, ns.ctypes.data, tm.ctypes.data, nm.ctypes.data, p.ctypes.data,
                               out_t.ctypes.data, out_n.ctypes.data, out_m.ctypes.data), "lrc_mover_merge")
     return out_t, out_n, out_m
+
+
+# ---- movers under moving-sensor sweeps (include/lidarcast.h "movers under moving-sensor sweeps") -----
+# Every ray of a sweep meets each mover at the pose the mover has when the ray fires.  Module functions, as
+# lidarcast.noise.sweep_rays / scan_noisy_sweeps_* are: the scene and the engine are arguments.
+
+def sweep_records(tracks, t_start, t_end):
+    """(P, M, 24) float32 mover sweep records of M ``MoverTrack``s over P sweeps that start at ``t_start`` (P,) and end at
+    ``t_end`` (P,) seconds: the start pose12, dq = (cos(a/2), 0, 0, sin(a/2)) of the yaw step a from start to end along the
+    shorter arc, dc = c_end - c_start; float64 arithmetic, narrowed last.  Each track is evaluated at the two times and nothing
+    else: the record moves straight between the two poses, so a path knot inside a sweep is cut straight.  A mover that does not
+    move during a sweep gets the still record (dq = (1, 0, 0, 0), dc = 0) exactly.  Raises ValueError for a yaw step above
+    pi/2 within one sweep."""
+    t0 = np.atleast_1d(np.asarray(t_start, dtype=np.float64))
+    t1 = np.atleast_1d(np.asarray(t_end, dtype=np.float64))
+    if t0.shape != t1.shape or t0.ndim != 1:
+        raise ValueError("t_start and t_end must be (P,)")
+    tracks = list(tracks)
+    out = np.zeros((len(t0), len(tracks), 24), np.float32)
+    for m, tr in enumerate(tracks):
+        a, b = tr.state(t0), tr.state(t1)
+        dyaw = (b[:, 3] - a[:, 3] + np.pi) % (2.0 * np.pi) - np.pi          # the shorter arc, in [-pi, pi)
+        if (np.abs(dyaw) > np.pi / 2).any():
+            k = int(np.argmax(np.abs(dyaw)))
+            raise ValueError(f"mover {m} turns by {abs(dyaw[k]):.3f} rad in sweep {k}: at most pi/2 per sweep")
+        out[:, m, :12] = pose12(a)
+        out[:, m, 12] = np.cos(0.5 * dyaw)
+        out[:, m, 15] = np.sin(0.5 * dyaw)
+        out[:, m, 16:19] = b[:, :3] - a[:, :3]
+    return out
+
+
+def _per_ray(rays, width, fire_of_ray, record24):
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, width)
+    f = np.ascontiguousarray(fire_of_ray, dtype=np.float64).reshape(-1)
+    if len(f) != len(r):
+        raise ValueError("fire_of_ray must hold one firing fraction per row")
+    return r, f, np.ascontiguousarray(record24, dtype=np.float32).reshape(24)
+
+
+def sweep_rays(rays6, fire_of_ray, record24):
+    """lrc_mover_sweep_rays: the (n, 6) float32 world rays, ray i in the frame the mover of ONE sweep record (24,) float32 has at
+    ``fire_of_ray[i]`` (float64, narrowed to float32 as the kernel narrows it); no GPU."""
+    lib = _capi.load()
+    r, f, rec = _per_ray(rays6, 6, fire_of_ray, record24)
+    out = np.empty_like(r)
+    check(lib.lrc_mover_sweep_rays(r.ctypes.data, f.ctypes.data, len(r), rec.ctypes.data, out.ctypes.data), "lrc_mover_sweep_rays")
+    return out
+
+
+def sweep_normals(normal3, fire_of_ray, record24):
+    """lrc_mover_sweep_normals: the (n, 3) float32 normals of ONE mover's cast turned into the world, normal i by the pose the
+    mover of the record has at ``fire_of_ray[i]``; no GPU.  ``merge`` then serves unchanged: it picks the winner, and the
+    winner's normal is the row of this array."""
+    lib = _capi.load()
+    q, f, rec = _per_ray(normal3, 3, fire_of_ray, record24)
+    out = np.empty_like(q)
+    check(lib.lrc_mover_sweep_normals(q.ctypes.data, f.ctypes.data, len(q), rec.ctypes.data, out.ctypes.data),
+          "lrc_mover_sweep_normals")
+    return out
+
+
+def scan_mover_sweeps_dev(scene, motion_t, dirs_t, fire_t, hits, max_range, movers, mover_records_t, mover_t=None, stream=0):
+    """Moving-sensor sweeps with moving objects on device tensors (lrc_scan_mover_sweeps_dev): motion_t (P, 24) float64, dirs_t
+    (N, 3) float64, fire_t (N,) float64 as ``Scene.scan_sweeps_dev`` takes them; ``movers`` a MoverSet or None,
+    ``mover_records_t`` (P, M, 24) float32 (``sweep_records``; the caller vouches for them), ``mover_t`` an optional (P * N)
+    uint8 tensor: 0 for the static scene, m + 1 for mover m.  Records as ``Scene.scan_poses_dev``."""
+    import torch
+    from .core import _check_side_tensor, _dptr, _stream
+    P, N = motion_t.shape[0], dirs_t.shape[0]
+    if motion_t.numel() != P * 24 or fire_t.numel() != N:
+        raise ValueError("motion_t must be (P, 24) and fire_t (N,)")
+    if hits.n != P * N:
+        raise ValueError("hits must hold P * N records")
+    handle, entries = None, None
+    if movers is not None:
+        handle, entries = movers.handle(scene.ctx), P * len(movers) * 24
+        if mover_records_t is None:
+            raise ValueError("mover_records_t must be (P, M, 24)")
+    _check_side_tensor("mover_records_t", mover_records_t, torch.float32, entries, "be (P, M, 24)", motion_t)
+    _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", motion_t)
+    check(scene._lib.lrc_scan_mover_sweeps_dev(scene._h, handle, _dptr(motion_t), P, _dptr(dirs_t), _dptr(fire_t), N,
+                                               _dptr(mover_records_t), float(max_range), C.byref(hits.struct), _dptr(mover_t),
+                                               _stream(stream)), "lrc_scan_mover_sweeps_dev")
+
+
+def scan_mover_sweeps_compact(scene, motion, dirs, fire, max_range, movers, mover_records, want=("point3", "sem", "ins"),
+                              capacity=None):
+    """Moving-sensor sweeps with moving objects straight to frames (lrc_scan_mover_sweeps_compact): ``motion``, ``dirs`` and
+    ``fire`` as ``Scene.scan_sweeps_compact`` takes them, ``movers`` a MoverSet or None, ``mover_records`` (P, M, 24) float32.
+    The return value of ``Scene.scan_movers_compact``: the frames plus ``mover``, one uint8 per kept row."""
+    from .core import DirectionTable, _ptr, _table_for
+    motion = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 24)
+    lib, h, P, reach = scene._lib, scene._h, motion.shape[0], float(max_range)
+    if fire is None and not isinstance(dirs, DirectionTable):
+        raise ValueError("fire is required with a plain direction table")
+    with _table_for(scene.ctx, dirs, fire) as tab:
+        if tab is dirs and fire is not None and \
+                (tab.fire is None or not np.array_equal(tab.fire, np.asarray(fire, np.float64).reshape(-1))):
+            tab.set_fire(fire)
+        if tab.fire is None:
+            raise ValueError("the direction table has no firing fractions")
+        handle, rec = None, None
+        if movers is not None:
+            handle = movers.handle(scene.ctx)
+            rec = np.ascontiguousarray(mover_records, dtype=np.float32)
+            if rec.shape != (P, len(movers), 24):
+                raise ValueError(f"mover_records must be (P, M, 24) = ({P}, {len(movers)}, 24), got {rec.shape}")
+        return scene._scan_frames("lrc_scan_mover_sweeps_compact", P, tab.n, want, capacity, lambda fr, cap, total, rows:
+                                  lib.lrc_scan_mover_sweeps_compact(h, handle, _ptr(motion), P, tab._h, _ptr(rec), reach, fr, rows,
+                                                                    cap, total),
+                                  side=[("mover", np.uint8, ())])
+
+
+def scan_mover_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh, movers, mover_records, want=("point3", "sem", "ins"),
+                            inputs=None):
+    """``RaycastEngineHIP.scan_sweep_frames`` with moving objects that move while the sweep is scanned: sweep k moves from
+    start_poses[k] to end_poses[k], and every ray meets mover m at the pose ``mover_records[k, m]`` gives for the moment the ray
+    fires.  The dict of ``scan_sweep_frames`` (``point_times`` included) plus ``mover``, one uint8 per kept row: 0 for the static
+    mesh, m + 1 for mover m.  ``inputs``: a ``sweep_inputs`` triple to scan exactly those sensor records again."""
+    motion, fire, T = inputs if inputs is not None else engine.sweep_inputs(intrinsics, start_poses, end_poses)
+    engine._need_table(intrinsics, "movers under moving-sensor sweeps need a sensor with a pose-independent direction table",
+                       NotImplementedError)
+    ask = tuple(want) + (() if "index" in want else ("index",))
+    fr = scan_mover_sweeps_compact(engine.scene_for(mesh), motion, engine._resident_table(intrinsics), fire,
+                                   intrinsics.max_range, movers, mover_records, want=ask)
+    fr["point_times"] = fire[fr["index"]] * T
+    if "index" not in want:
+        del fr["index"]
+    return fr

@@ -367,31 +367,44 @@ class S3DISSimulator:
         kw = {k: cfg[k] for k in ("max_bounces", "min_intensity") if k in cfg}
         return MaterialTable.from_classes(cfg.get("classes", {}), **kw)
 
-    def _mover_plan(self):
+    def _mover_plan(self, nested=False):
         """The moving objects of the config key ``movers`` (None without the key): ``period`` (seconds between frames; frame k
         is at k * period) and ``objects``, each ``{mesh: pedestrian | <path to a mesh>, semantic: id or S3DIS class name,
         instance: id, path: [[t, x, y, z, yaw_deg], ...]}``, and optionally ``flow: true`` (scene flow: frames then carry the flow
         to the next frame and its status).  Returns {period, meshes, tracks, objects (JSON-ready), flow}.
-        The key stands alone: motion, noise, beam and materials are refused beside it."""
-        cfg = self.config.get("movers")
+        The key stands alone: motion, noise, beam and materials are refused beside it.
+        ``nested``: the same entries under ``motion: {movers: ...}``, movers that go on moving while a sweep is scanned (DESIGN.md
+        section 5n): sweep k starts at k * period.  There ``flow: true`` is refused (no scene flow under sweeps), and so are
+        ``motion.noise``, beam and materials beside it."""
+        cfg = (self.config.get("motion") or {}).get("movers") if nested else self.config.get("movers")
+        key = "motion.movers" if nested else "movers"
         if cfg is None:
             return None
-        for other in ("motion", "noise", "beam", "materials"):
-            if self.config.get(other) is not None:
-                raise ValueError(f"the movers key cannot be combined with the {other} key")
+        if nested:
+            if (self.config.get("motion") or {}).get("noise") is not None:
+                raise ValueError("motion.movers cannot be combined with motion.noise: noise under mover sweeps is not built")
+            for other in ("beam", "materials"):
+                if self.config.get(other) is not None:
+                    raise ValueError(f"motion.movers cannot be combined with the {other} key")
+        else:
+            for other in ("motion", "noise", "beam", "materials"):
+                if self.config.get(other) is not None:
+                    raise ValueError(f"the movers key cannot be combined with the {other} key")
         unknown = set(cfg) - {"period", "objects", "flow"}
         if unknown:
-            raise ValueError(f"unknown entries under the movers key: {sorted(unknown)}")
+            raise ValueError(f"unknown entries under the {key} key: {sorted(unknown)}")
         if not isinstance(cfg.get("flow", False), bool):
-            raise ValueError("movers.flow must be true or false")
+            raise ValueError(f"{key}.flow must be true or false")
+        if nested and cfg.get("flow", False):
+            raise ValueError("motion.movers.flow is not available: scene flow under moving-sensor sweeps is not built")
         period = float(cfg.get("period", 0.1))
         if not (np.isfinite(period) and period > 0.0):
-            raise ValueError("movers.period must be a positive number of seconds")
+            raise ValueError(f"{key}.period must be a positive number of seconds")
         objects = cfg.get("objects")
         if not objects:
-            raise ValueError("the movers key needs at least one object")
+            raise ValueError(f"the {key} key needs at least one object")
         if len(objects) > 255:
-            raise ValueError("the movers key takes at most 255 objects")
+            raise ValueError(f"the {key} key takes at most 255 objects")
         from lidarcast import synth
         from lidarcast.movers import MoverTrack
         meshes, tracks, listed = [], [], []
@@ -479,7 +492,7 @@ class S3DISSimulator:
         # opt-in moving-sensor sweeps (config key ``motion: {speed: m/s}``): every ray is cast from the pose of the sensor at
         # the moment it fires; frames then carry per-point times.  Without the key nothing changes.
         motion = self.config.get("motion")
-        sweep = sweep_noise = None
+        sweep = sweep_noise = sweep_movers = None
         if motion is not None and len(waypoints) > 0:
             if dist is not None:
                 raise NotImplementedError("moving-sensor sweeps are not available on a multi-rank process group")
@@ -491,6 +504,10 @@ class S3DISSimulator:
             # ... with seeded sensor noise under them (nested key ``motion: {speed, noise: {seed, range_std?, angle_std_deg?,
             # dropout?}}``, the entries of the noise key below): the row is jittered and the range drawn in the sweep's own
             # kernel; frame p has frame id p.  Without the nested entry nothing changes.
+            # ... or with moving objects under them (nested key ``motion: {speed, movers: {period, objects: [...]}}``, the entries
+            # of the movers key above): every ray meets each mover at the pose the mover has at the moment the ray fires (DESIGN.md
+            # section 5n); sweep k starts at k * period and lasts 1 / scan_frequency; frames carry point_times AND mover_ids.
+            sweep_movers = self._mover_plan(nested=True)
             sweep_noise = self._noise_model(nested=True)
         # opt-in seeded sensor noise (config key ``noise: {seed, range_std?, angle_std_deg?, dropout?}``): range noise, angle
         # jitter and dropout drawn in the kernel; frame p of the run has frame id p, so scanning any
@@ -546,6 +563,23 @@ class S3DISSimulator:
             fr = engine.scan_echo_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, beam, want=want)
         elif noise is not None:
             fr = engine.scan_noisy_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, noise, want=want)
+        elif sweep is not None and sweep_movers is not None:
+            from lidarcast.movers import MoverSet, scan_mover_sweep_frames, sweep_records
+            duration = 1.0 / float(self.lidar_config.scan_frequency)
+            times = np.arange(len(waypoints), dtype=np.float64) * sweep_movers["period"]
+            states = np.stack([t.state(times) for t in sweep_movers["tracks"]], axis=1)                  # (P, M, 4) at the sweep's start
+            end_states = np.stack([t.state(times + duration) for t in sweep_movers["tracks"]], axis=1)   # ... and at its end
+            records = sweep_records(sweep_movers["tracks"], times, times + duration)                      # (P, M, 24) float32
+            if "sem" not in want:           # the labels are the winner's: they come with the points
+                want = want[:1] + ("sem", "ins") + want[1:]
+            mset = MoverSet(engine.ctx, sweep_movers["meshes"])
+            try:
+                fr = scan_mover_sweep_frames(engine, self.lidar_config, None, None, mesh, mset, records, want=want, inputs=sweep)
+            finally:
+                mset.close()
+            sim_scene.mover_tracks = {"period": sweep_movers["period"], "objects": sweep_movers["objects"], "times": times,
+                                      "states": states, "poses12": records[:, :, :12], "sensor_poses": poses_from_waypoints(waypoints),
+                                      "end_states": end_states, "records24": records, "sweep_duration": duration}
         elif sweep is not None and sweep_noise is not None:
             from lidarcast.noise import scan_noisy_sweep_frames
             fr = scan_noisy_sweep_frames(engine, self.lidar_config, None, None, mesh, sweep_noise, want=want, inputs=sweep)

@@ -22,6 +22,11 @@ int movers_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const doub
                     uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
 int movers_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, const lrc_frames*,
                         uint8_t*, uint64_t, uint64_t*) { return LRC_ERR_INTERNAL; }
+int mover_sweeps_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const double*, const double*, uint64_t, const float*, double,
+                          const lrc_hits*, uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
+int mover_sweeps_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, const lrc_frames*,
+                              uint8_t*, uint64_t, uint64_t*) { return LRC_ERR_INTERNAL; }
+int check_motion(const char*, const double*, uint64_t) { return LRC_OK; }
 int flow_scan_dev(lrc_scene*, lrc_movers*, const lrc_hits*, const uint8_t*, uint64_t, uint64_t, const float*, const FlowNext&, double,
                   float*, uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
 int flow_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, const FlowNext&, double,

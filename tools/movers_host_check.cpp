@@ -1,6 +1,6 @@
 // movers_host_check.cpp -- stand-alone driver of the host side of the moving objects (csrc/lrc_movers.hip, csrc/lrc_movers.h)
-// for a sanitizer build: lrc_mover_rays and lrc_mover_merge on random and crafted columns in exactly sized heap arrays, checked
-// against a plain restatement of the header's text; the refusals that need no device; and the cull test of the ray kernel
+// for a sanitizer build: lrc_mover_rays, lrc_mover_merge, lrc_mover_sweep_rays and lrc_mover_sweep_normals on random and crafted
+// columns in exactly sized heap arrays, checked against a plain restatement of the header's text; the refusals that need no device; and the cull test of the ray kernel
 // (lrcmov::culled) against a float64 slab test: a ray that meets the mover's box must never be left out.  Uses no GPU.  The
 // units lrc_movers.hip calls into are stubbed below.  Build and run from csrc/:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -I. -Xarch_host -fsanitize=address,undefined \
@@ -23,6 +23,11 @@ int movers_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const doub
                     uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
 int movers_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, const lrc_frames*,
                         uint8_t*, uint64_t, uint64_t*) { return LRC_ERR_INTERNAL; }
+int mover_sweeps_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const double*, const double*, uint64_t, const float*, double,
+                          const lrc_hits*, uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
+int mover_sweeps_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, const lrc_frames*,
+                              uint8_t*, uint64_t, uint64_t*) { return LRC_ERR_INTERNAL; }
+int check_motion(const char*, const double*, uint64_t) { return LRC_OK; }
 
 static int g_bad = 0;
 #define EXPECT(c) do { if (!(c)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); ++g_bad; } } while (0)
@@ -114,6 +119,72 @@ int main() {
         EXPECT(lrc_mover_merge(1, 1, &t, n3, &t, n3, nullptr, &ot, on, &ow) == LRC_ERR_INVALID_ARG);
         EXPECT(lrc_mover_merge(1, 0, &t, n3, nullptr, nullptr, nullptr, &ot, on, &ow) == LRC_OK && ow == 0 && ot == 1.f);
         EXPECT(lrc_mover_merge(0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == LRC_OK);
+    }
+
+    // ---- lrc_mover_sweep_rays / lrc_mover_sweep_normals against the header's text: general, still and one-sided records ----
+    for (int round = 0; round < 60; ++round) {
+        const size_t n = 1 + (g() % 2000);
+        std::vector<float> rays(n * 6), out(n * 6), want(n * 6), n3(n * 3), on(n * 3), wn(n * 3);
+        std::vector<double> fire(n);
+        std::uniform_real_distribution<float> u(-20.f, 20.f), un(-1.f, 1.f);
+        std::uniform_real_distribution<double> uf(0.0, 1.0), ang(-0.78, 0.78), ax(-1.0, 1.0);
+        for (float& v : rays) v = u(g);
+        for (float& v : n3) v = un(g);
+        for (size_t i = 0; i < n; ++i) fire[i] = i % 13 == 0 ? 0.0 : uf(g);
+        float r[24] = {0};
+        random_pose(g, r);
+        r[12] = 1.f;
+        if (round % 4 != 1) {                      // a rotation about a random axis (round % 4 == 1: translation only or still)
+            const double a = ang(g), x = ax(g), y = ax(g), z = ax(g), l = std::sqrt(x * x + y * y + z * z) + 1e-9;
+            r[12] = (float)std::cos(a); r[13] = (float)(std::sin(a) * x / l); r[14] = (float)(std::sin(a) * y / l); r[15] = (float)(std::sin(a) * z / l);
+        }
+        if (round % 4 != 2 && round % 8 != 1)      // round % 4 == 2: rotation only; round % 8 == 1: the still record
+            for (int j = 16; j < 19; ++j) r[j] = u(g) * 0.05f;
+        const bool still = r[12] == 1.f && !std::memcmp(&r[13], std::vector<float>(6, 0.f).data(), 24);
+        EXPECT(still == (round % 8 == 1));
+        EXPECT(lrc_mover_sweep_rays(rays.data(), fire.data(), n, r, out.data()) == LRC_OK);
+        EXPECT(lrc_mover_sweep_normals(n3.data(), fire.data(), n, r, on.data()) == LRC_OK);
+        for (size_t i = 0; i < n; ++i) {
+            const float s = (float)fire[i];
+            const float c[3] = {r[3] + s * r[16], r[7] + s * r[17], r[11] + s * r[18]};
+            const float qw = (1.0f - s) + s * r[12], ux = s * r[13], uy = s * r[14], uz = s * r[15];
+            const float k = 2.0f / (((qw * qw + ux * ux) + uy * uy) + uz * uz);
+            auto rot = [&](const float* v, bool inverse, float* o) {
+                const float tx = uy * v[2] - uz * v[1], ty = uz * v[0] - ux * v[2], tz = ux * v[1] - uy * v[0];
+                const float wx = uy * tz - uz * ty, wy = uz * tx - ux * tz, wz = ux * ty - uy * tx;
+                if (inverse) { o[0] = v[0] + k * (wx - qw * tx); o[1] = v[1] + k * (wy - qw * ty); o[2] = v[2] + k * (wz - qw * tz); }
+                else { o[0] = v[0] + k * (qw * tx + wx); o[1] = v[1] + k * (qw * ty + wy); o[2] = v[2] + k * (qw * tz + wz); }
+            };
+            const float* ry = &rays[i * 6];
+            float e[3] = {ry[0] - (still ? r[3] : c[0]), ry[1] - (still ? r[7] : c[1]), ry[2] - (still ? r[11] : c[2])}, d[3] = {ry[3], ry[4], ry[5]};
+            if (!still) { float t3[3]; rot(e, true, t3); std::memcpy(e, t3, 12); rot(d, true, t3); std::memcpy(d, t3, 12); }
+            for (int j = 0; j < 3; ++j) {
+                want[i * 6 + j] = (r[j] * e[0] + r[4 + j] * e[1]) + r[8 + j] * e[2];
+                want[i * 6 + 3 + j] = (r[j] * d[0] + r[4 + j] * d[1]) + r[8 + j] * d[2];
+            }
+            const float* q = &n3[i * 3];
+            float w[3];
+            for (int j = 0; j < 3; ++j) w[j] = (r[4 * j] * q[0] + r[4 * j + 1] * q[1]) + r[4 * j + 2] * q[2];
+            if (!still) { float t3[3]; rot(w, false, t3); std::memcpy(w, t3, 12); }
+            std::memcpy(&wn[i * 3], w, 12);
+        }
+        EXPECT(same_bits(out.data(), want.data(), n * 6));
+        EXPECT(same_bits(on.data(), wn.data(), n * 3));
+    }
+    {
+        float r[24] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1}, ray[6] = {1, 2, 3, 4, 5, 6}, o[6];
+        double f = 0.5;
+        EXPECT(lrc_mover_sweep_rays(ray, &f, 1, nullptr, o) == LRC_ERR_INVALID_ARG);
+        EXPECT(lrc_mover_sweep_rays(ray, nullptr, 1, r, o) == LRC_ERR_INVALID_ARG);
+        EXPECT(lrc_mover_sweep_rays(nullptr, &f, 1, r, o) == LRC_ERR_INVALID_ARG);
+        EXPECT(lrc_mover_sweep_rays(nullptr, nullptr, 0, r, nullptr) == LRC_OK);
+        EXPECT(lrc_mover_sweep_rays(ray, &f, 1, r, o) == LRC_OK && same_bits(ray, o, 6));
+        EXPECT(lrc_mover_sweep_normals(ray, &f, 1, r, nullptr) == LRC_ERR_INVALID_ARG);
+        EXPECT(lrc_mover_sweep_normals(ray, &f, 1, r, o) == LRC_OK && same_bits(ray, o, 3));
+        lrc_hits hits{};
+        lrc_frames fr{};
+        EXPECT(lrc_scan_mover_sweeps_dev(nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 1.0, &hits, nullptr, nullptr) == LRC_ERR_INVALID_ARG);
+        EXPECT(lrc_scan_mover_sweeps_compact(nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1.0, &fr, nullptr, 0, nullptr) == LRC_ERR_INVALID_ARG);
     }
 
     // ---- refusals that need no device ----
