@@ -859,6 +859,56 @@ int lrc_flow_rays(const float* t, const float* point3, const uint8_t* mover, uin
 int lrc_flow_status(uint64_t num_rows, uint32_t num_movers, const float* t_static, const float* t_movers, const float* thr,
                     const uint8_t* status, uint8_t* out_status);
 
+/* ---- deforming movers: keyframed meshes blended and refitted on the device (opt-in) -----------------
+ * A DEFORMABLE is one topology (tris3) with K keyframes of its V vertices.  lrc_deform_create builds an ordinary lrc_scene from
+ * keyframe 0 by the builders of lrc_scene_create (device or host as that call chooses), always with float32 nodes whatever
+ * LRC_QNODES says (the quantisation grid is tied to bounds that a deformation moves): its arrays for keyframe 0 are the bytes
+ * of lrc_scene_create under LRC_QNODES=0.  Creation is synchronous.  The deformable keeps the keyframes, tris3, the current
+ * vertices and a height table of the tree resident, and owns the scene: lrc_deform_scene hands it out, lrc_scene_destroy on
+ * it is refused, lrc_deform_destroy frees it.
+ *
+ * lrc_deform_set_dev ENQUEUES on `stream`, without a host synchronisation, the next shape and the refit of the scene to it:
+ *   blend    per coordinate v = a + w * (b - a) of keyframes k0 (a) and k1 (b), then clamped into [min(a, b), max(a, b)]
+ *            (float32, one rounding per operation, nothing fused): a blended vertex lies in the box of its two keyframes
+ *            exactly.  w == 0 or k0 == k1 copies the bits of keyframe k0, w == 1 those of k1.
+ *   refit    per leaf slot the 48-byte record (v0, e1, e2, Ng) and the slot box of its triangle from the current vertices, by
+ *            the builders' own expressions; then per inner node, height by height from the leaves up, both child boxes: a
+ *            leaf child's box is the min / max over its <= 4 slot boxes, an inner child's the min / max of that node's two
+ *            boxes, in the builders' total order (-0 below +0).  An empty leaf keeps its all-zero box.  References, slot_prim,
+ *            slot_label and the three padding records are not touched; the tree keeps the splits of keyframe 0.
+ * Any tree whose child boxes are the exact vertex min / max below them gives the same hits bit for bit, so every cast and
+ * scan call takes the scene as the ordinary scene it is, as the static scene or as a mover of a set, and returns what a fresh
+ * lrc_scene_create of the current vertices returns.  A scan enqueued on the SAME stream after lrc_deform_set_dev sees the new
+ * shape and needs no wait; calls on other streams, and the host-pointer calls (they run on streams of the library), are the
+ * caller's to order (synchronise the stream of the set first).
+ * info.bounds_lo / bounds_hi of the scene are the union of ALL keyframes' boxes and never change; the movers' cull sphere is
+ * made from them.  Entry points that cache per-triangle geometry of a scene refuse a deformable scene (LRC_ERR_INVALID_ARG):
+ * the plane table behind lrc_cloud_from_prims_dev / _own_dev, the gathered rebuild of a pipe and LRC_ARRAY_PRIM_PLANE.  lrc_coverage_create
+ * and lrc_frameobj_create take a mesh, not a scene: their tables describe the vertices they were given and nothing else.
+ *
+ * LRC_ERR_INVALID_ARG before any launch: K = 0, T = 0, a keyframe entry that is not finite or above 1e6 in magnitude, a
+ * triangle index >= V (lrc_deform_create); k0 or k1 >= K, w outside [0, 1] or not finite (lrc_deform_set_dev).
+ *
+ *   lrc_deform_create    keyframes3: host (K, V, 3) float32; tris3, tri_sem, tri_ins as lrc_scene_create takes them
+ *   lrc_deform_vertices  synchronous read-back of the current (V, 3) vertices (waits for the device)
+ *   lrc_deform_launches  kernel launches one lrc_deform_set_dev enqueues: with a blend, and with a keyframe copy instead
+ * Host functions, no GPU, by the inline functions the kernels call:
+ *   lrc_deform_blend     out3 = blend of a3 and b3 ((num_vertices, 3) float32 each); a3 == b3, w == 0 and w == 1 copy
+ *   lrc_deform_refit     nodes16 in: the topology (references), out: the boxes; out_tri_rec12 (num_slots, 12) and
+ *                        out_slot_box6 (num_slots, 6) are written.  LRC_ERR_INVALID_ARG for nodes that are no tree over the
+ *                        slots, a slot_prim entry >= T or a triangle index >= V. */
+typedef struct lrc_deform lrc_deform;
+int lrc_deform_create(lrc_ctx* ctx, const float* keyframes3, uint32_t K, uint64_t V, const uint32_t* tris3, uint64_t T,
+                      const uint16_t* tri_sem, const uint16_t* tri_ins, lrc_deform** out);
+int lrc_deform_destroy(lrc_deform* deform);
+lrc_scene* lrc_deform_scene(lrc_deform* deform);
+int lrc_deform_set_dev(lrc_deform* deform, uint32_t k0, uint32_t k1, float w, void* stream);
+int lrc_deform_vertices(lrc_deform* deform, float* out_verts3);
+int lrc_deform_launches(const lrc_deform* deform, uint32_t* blended, uint32_t* copied);
+int lrc_deform_blend(const float* a3, const float* b3, uint64_t num_vertices, float w, float* out3);
+int lrc_deform_refit(float* nodes16, uint64_t num_nodes, const uint32_t* slot_prim, uint64_t num_slots, const uint32_t* tris3,
+                     uint64_t T, const float* verts3, uint64_t V, float* out_tri_rec12, float* out_slot_box6);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

@@ -389,7 +389,9 @@ class S3DISSimScene:
         """Ground truth of the moving objects of a run under the movers key, written to ``output_dir``/<scene>_mover_tracks.json:
         the period, the object table (mesh, semantic, instance, the mesh's own box) and, per frame and mover, the time, the
         pose (x, y, z, yaw_deg and the row-major 3 x 4 object-to-world matrix), the oriented box (``box7``: world centre,
-        extents of the mesh's own AABB, heading = yaw) and ``num_points``, the frame's returns from that mover.  Under the
+        extents of the mesh's own AABB, heading = yaw) and ``num_points``, the frame's returns from that mover.  An animated
+        mover (``animation`` entry) also carries ``shape``: [k0, k1, w] of the frame, and its box is that of the frame's own
+        blended vertices.  Under the
         nested key ``motion: {movers: ...}`` (movers that move while a sweep is scanned) ``pose`` is the pose at the START of the
         frame's sweep, every mover additionally carries ``end_pose`` (x, y, z, yaw_deg at the END of the sweep) and ``record24``
         (the mover sweep record the scan used), and every frame ``sweep_duration`` in seconds.  Returns the dict."""
@@ -407,6 +409,13 @@ class S3DISSimScene:
             for m, obj in enumerate(objs):
                 x, y, z, yaw = (float(v) for v in tr["states"][f][m])
                 lo, hi = np.asarray(obj["box_min"], np.float64), np.asarray(obj["box_max"], np.float64)
+                shape = None
+                if m in tr.get("shapes", {}):       # an animated mover: the box of the frame's own blended vertices (host blend)
+                    from lidarcast.deform import blend
+                    shape = [float(v) for v in tr["shapes"][m][f]]
+                    keys = tr["keyframes"][m]
+                    verts = blend(keys[int(shape[0])], keys[int(shape[1])], shape[2]).astype(np.float64)
+                    lo, hi = verts.min(0), verts.max(0)
                 c, s = np.cos(yaw), np.sin(yaw)
                 mid = 0.5 * (lo + hi)
                 centre = np.array([c * mid[0] - s * mid[1] + x, s * mid[0] + c * mid[1] + y, mid[2] + z])
@@ -415,6 +424,8 @@ class S3DISSimScene:
                                         "matrix12": [float(v) for v in tr["poses12"][f][m]]},
                                "box7": [float(v) for v in centre] + [float(v) for v in (hi - lo)] + [yaw],
                                "num_points": int(counts[m + 1])})
+                if shape is not None:
+                    movers[-1]["shape"] = [int(shape[0]), int(shape[1]), shape[2]]
                 if "end_states" in tr:
                     ex, ey, ez, eyaw = (float(v) for v in tr["end_states"][f][m])
                     movers[-1]["end_pose"] = {"x": ex, "y": ey, "z": ez, "yaw_deg": float(np.degrees(eyaw))}

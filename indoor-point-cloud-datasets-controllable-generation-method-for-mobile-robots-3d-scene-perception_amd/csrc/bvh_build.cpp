@@ -13,6 +13,7 @@
 //     the rest in depth-first order (a subtree is contiguous in HBM);
 //   * deterministic for a given input.
 #include "lrc_bvh.h"
+#include "lrc_trirec.h"
 
 #include <algorithm>
 #include <atomic>
@@ -34,9 +35,9 @@ struct Prim {
 // min / max under the total order of the float32 bit patterns (-0.0 < +0.0): a box plane does not depend on the
 // order its members were visited in, so the device builder (lrc_bvh_device.hip, integer min / max on the same
 // encoding) produces the same bytes.  The sign of a zero plane never changes a traversal result.
-inline int32_t ford(float f) { int32_t i; std::memcpy(&i, &f, 4); return i ^ ((i >> 31) & 0x7FFFFFFF); }
-inline float fmin_t(float a, float b) { return ford(b) < ford(a) ? b : a; }
-inline float fmax_t(float a, float b) { return ford(b) > ford(a) ? b : a; }
+// (lrc_trirec.h: the one encoding both builders and the refit of a deformable scene use)
+inline float fmin_t(float a, float b) { return lrctri::tmin(a, b); }
+inline float fmax_t(float a, float b) { return lrctri::tmax(a, b); }
 
 struct Box {
     float lo[3], hi[3];
@@ -209,8 +210,6 @@ struct Builder {
     }
 };
 
-inline float fmaf_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-
 }  // namespace
 
 void build_bvh(const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T,
@@ -317,19 +316,9 @@ void build_bvh(const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t 
         const float* v0 = verts3 + 3 * (uint64_t)tris3[3 * (uint64_t)id + 0];
         const float* v1 = verts3 + 3 * (uint64_t)tris3[3 * (uint64_t)id + 1];
         const float* v2 = verts3 + 3 * (uint64_t)tris3[3 * (uint64_t)id + 2];
-        float e1[3], e2[3];
-        for (int k = 0; k < 3; ++k) { e1[k] = v0[k] - v1[k]; e2[k] = v2[k] - v0[k]; }
-        float* r = &o.tri_rec[s * kTriFloats];
-        for (int k = 0; k < 3; ++k) { r[k] = v0[k]; r[3 + k] = e1[k]; r[6 + k] = e2[k]; }
         if (o.slot_box.empty()) o.slot_box.assign(T * 6, 0.0f);
-        for (int k = 0; k < 3; ++k) {
-            o.slot_box[s * 6 + k] = fmin_t(fmin_t(v0[k], v1[k]), v2[k]);
-            o.slot_box[s * 6 + 3 + k] = fmax_t(fmax_t(v0[k], v1[k]), v2[k]);
-        }
-        // Ng = cross(e2, e1), component = fma(a_j, b_k, -(a_k * b_j))
-        r[9]  = fmaf_(e2[1], e1[2], -(e2[2] * e1[1]));
-        r[10] = fmaf_(e2[2], e1[0], -(e2[0] * e1[2]));
-        r[11] = fmaf_(e2[0], e1[1], -(e2[1] * e1[0]));
+        // v0, e1, e2, Ng = cross(e2, e1) and the slot box: lrc_trirec.h
+        lrctri::tri_record(v0, v1, v2, &o.tri_rec[s * kTriFloats], &o.slot_box[s * 6]);
         o.slot_prim[s] = id;
         uint32_t sem = tri_sem ? tri_sem[id] : 0u, ins = tri_ins ? tri_ins[id] : 0u;
         o.slot_label[s] = sem | (ins << 16);

@@ -2060,6 +2060,8 @@ int lrc_ctx_synchronize(lrc_ctx* ctx) {
 
 int lrc_scene_destroy(lrc_scene* s) {
     if (!s) return LRC_OK;
+    if (s->deform)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scene_destroy: the scene belongs to a deformable (lrc_deform_destroy frees it)");
     if (s->ctx) (void)hipSetDevice(s->ctx->device);
     if (s->slab) {
         (void)hipFree(s->slab);
@@ -2108,7 +2110,7 @@ void qnodes_report(const lrc_scene* s, double infl) {
 // The scene build on the device (lrc_bvh_device.hip): the same tree, the same bytes as the host builder below, in
 // milliseconds.  Returns lrc::kDevBuildUnsupported (1) for a mesh the device path does not take (<= max_leaf triangles).
 int scene_create_device(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T,
-                        const uint16_t* tri_sem, const uint16_t* tri_ins, bool on_device, lrc_scene** out_scene) {
+                        const uint16_t* tri_sem, const uint16_t* tri_ins, bool on_device, int qmode, lrc_scene** out_scene) {
     lrc_scene* s = new (std::nothrow) lrc_scene();
     if (!s) return fail(LRC_ERR_OOM, "lrc_scene_create: out of host memory");
     s->ctx = ctx;
@@ -2116,7 +2118,7 @@ int scene_create_device(lrc_ctx* ctx, const float* verts3, uint64_t V, const uin
     lrc::BuildOptions opt;
     build_options_from_env(opt);
     const int rc = lrc::build_bvh_device(&ctx->build_arena, verts3, V, tris3, T, tri_sem, tri_ins, on_device, opt,
-                                         qnodes_mode(), &d);
+                                         qmode, &d);
     if (rc != lrc::kDevBuildOk) {
         delete s;
         return rc;
@@ -2151,7 +2153,7 @@ int scene_create_device(lrc_ctx* ctx, const float* verts3, uint64_t V, const uin
 }
 
 int scene_create_host(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T,
-                      const uint16_t* tri_sem, const uint16_t* tri_ins, lrc_scene** out_scene) {
+                      const uint16_t* tri_sem, const uint16_t* tri_ins, int qmode, lrc_scene** out_scene) {
     for (uint64_t i = 0; i < 3 * T; ++i)
         if (tris3[i] >= V)
             return fail(LRC_ERR_INVALID_ARG, "lrc_scene_create: triangle index out of range");
@@ -2214,7 +2216,7 @@ int scene_create_host(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint3
         std::vector<uint32_t> q8, q16;
         std::vector<float> n16, n32;
         double infl = 1.0;
-        const int mode = qnodes_mode();
+        const int mode = qmode;
         lrc::QGrid g;
         if (mode != 0 && lrc::make_qgrid(h, s->qbase, s->qW, s->qinvW, g) && lrc::build_qnodes(h, g, q8, n16, &infl) &&
             (mode >= 2 || infl <= lrc::kQnodeMaxInflation)) {
@@ -2260,6 +2262,14 @@ extern "C" {
 
 int lrc_scene_create(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T,
                      const uint16_t* tri_sem, const uint16_t* tri_ins, lrc_scene** out_scene) {
+    return scene_create_mode(ctx, verts3, V, tris3, T, tri_sem, tri_ins, qnodes_mode(), out_scene);
+}
+
+}  // extern "C"
+
+// lrc_scene_create with the node images chosen by the caller (qmode as LRC_QNODES): lrc_deform_create asks for 0
+int scene_create_mode(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T,
+                      const uint16_t* tri_sem, const uint16_t* tri_ins, int qmode, lrc_scene** out_scene) {
     if (!out_scene) return fail(LRC_ERR_INVALID_ARG, "lrc_scene_create: out_scene is NULL");
     *out_scene = nullptr;
     if (!ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_scene_create: ctx is NULL");
@@ -2269,11 +2279,13 @@ int lrc_scene_create(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint32
         return fail(LRC_ERR_INVALID_ARG, "lrc_scene_create: mesh too large (T < 2^28, V < 2^32)");
     LRC_HIP(hipSetDevice(ctx->device));
     if (want_device_build()) {
-        const int rc = scene_create_device(ctx, verts3, V, tris3, T, tri_sem, tri_ins, false, out_scene);
+        const int rc = scene_create_device(ctx, verts3, V, tris3, T, tri_sem, tri_ins, false, qmode, out_scene);
         if (rc != lrc::kDevBuildUnsupported) return rc;
     }
-    return scene_create_host(ctx, verts3, V, tris3, T, tri_sem, tri_ins, out_scene);
+    return scene_create_host(ctx, verts3, V, tris3, T, tri_sem, tri_ins, qmode, out_scene);
 }
+
+extern "C" {
 
 int lrc_scene_create_dev(lrc_ctx* ctx, const float* d_verts3, uint64_t V, const uint32_t* d_tris3, uint64_t T,
                          const uint16_t* d_tri_sem, const uint16_t* d_tri_ins, lrc_scene** out_scene) {
@@ -2286,7 +2298,7 @@ int lrc_scene_create_dev(lrc_ctx* ctx, const float* d_verts3, uint64_t V, const 
         return fail(LRC_ERR_INVALID_ARG, "lrc_scene_create_dev: mesh too large (T < 2^28, V < 2^32)");
     LRC_HIP(hipSetDevice(ctx->device));
     if (want_device_build()) {
-        const int rc = scene_create_device(ctx, d_verts3, V, d_tris3, T, d_tri_sem, d_tri_ins, true, out_scene);
+        const int rc = scene_create_device(ctx, d_verts3, V, d_tris3, T, d_tri_sem, d_tri_ins, true, qnodes_mode(), out_scene);
         if (rc != lrc::kDevBuildUnsupported) return rc;
     }
     // a mesh the device builder does not take (a handful of triangles), or LRC_DEVICE_BUILD=0: build on the host
@@ -2298,7 +2310,7 @@ int lrc_scene_create_dev(lrc_ctx* ctx, const float* d_verts3, uint64_t V, const 
     if (d_tri_sem && T) LRC_HIP(hipMemcpy(hs.data(), d_tri_sem, T * 2, hipMemcpyDeviceToHost));
     if (d_tri_ins && T) LRC_HIP(hipMemcpy(hi.data(), d_tri_ins, T * 2, hipMemcpyDeviceToHost));
     return scene_create_host(ctx, hv.data(), V, ht.data(), T, d_tri_sem ? hs.data() : nullptr,
-                             d_tri_ins ? hi.data() : nullptr, out_scene);
+                             d_tri_ins ? hi.data() : nullptr, qnodes_mode(), out_scene);
 }
 
 int lrc_scene_get_info(const lrc_scene* scene, lrc_scene_info* out_info) {
@@ -2337,6 +2349,8 @@ int lrc_scene_export_bvh(const lrc_scene* s, float* nodes16, uint32_t* slot_prim
 // synchronisation, once per scene): a second caller -- another host thread, or another non-blocking stream -- either sees
 // NULL and waits for the mutex, or sees a finished table; it can never read a zeroed or half-written one.
 static int ensure_prim_plane(lrc_scene* s, hipStream_t st) {
+    if (s->deform)
+        return fail(LRC_ERR_INVALID_ARG, "the plane table caches per-triangle geometry: not available on a deformable scene");
     if (s->info.num_triangles == 0) return LRC_OK;
     if (__atomic_load_n(&s->d_prim_plane, __ATOMIC_ACQUIRE)) return LRC_OK;
     std::lock_guard<std::mutex> lock(s->plane_mutex);

@@ -32,6 +32,7 @@
 
 #include "lrc_internal.h"
 #include "lrc_qnodes.h"
+#include "lrc_trirec.h"
 
 #undef LRC_HIP_WHERE
 #define LRC_HIP_WHERE "device BVH build: "      // what LRC_HIP puts in front of the call text in this unit
@@ -52,10 +53,11 @@ constexpr int kEncNegMax = (int)0x80800000u;     // enc(-FLT_MAX)
 
 // float <-> int with the same order (and -0.0 < +0.0): min / max become integer min / max, associative and
 // commutative, so a box does not depend on the order its members arrive in
-DI int enc(float f) { const int i = __float_as_int(f); return i ^ ((i >> 31) & 0x7FFFFFFF); }
-DI float dec(int i) { return __int_as_float(i ^ ((i >> 31) & 0x7FFFFFFF)); }
-DI int imin(int a, int b) { return a < b ? a : b; }
-DI int imax(int a, int b) { return a > b ? a : b; }
+// (lrc_trirec.h: shared with the host builder and the refit of a deformable scene)
+using lrctri::enc;
+using lrctri::dec;
+using lrctri::imin;
+using lrctri::imax;
 
 struct PrimRec { float4 a, b; };     // a = lo.xyz, hi.x   b = hi.y, hi.z, triangle row (bits), 0
 
@@ -1467,20 +1469,13 @@ __global__ __launch_bounds__(256) void k_tri_records(const float* verts3, const 
     const float* v0 = verts3 + 3 * (size_t)tris3[3 * (size_t)id];
     const float* v1 = verts3 + 3 * (size_t)tris3[3 * (size_t)id + 1];
     const float* v2 = verts3 + 3 * (size_t)tris3[3 * (size_t)id + 2];
-    float a[3], b[3], c[3], e1[3], e2[3];
+    float r[12], bx[6];
+    lrctri::tri_record(v0, v1, v2, r, bx);
+    o[0] = make_float4(r[0], r[1], r[2], r[3]);
+    o[1] = make_float4(r[4], r[5], r[6], r[7]);
+    o[2] = make_float4(r[8], r[9], r[10], r[11]);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { a[k] = v0[k]; b[k] = v1[k]; c[k] = v2[k]; e1[k] = a[k] - b[k]; e2[k] = c[k] - a[k]; }
-    const float nx = __builtin_fmaf(e2[1], e1[2], -(e2[2] * e1[1]));
-    const float ny = __builtin_fmaf(e2[2], e1[0], -(e2[0] * e1[2]));
-    const float nz = __builtin_fmaf(e2[0], e1[1], -(e2[1] * e1[0]));
-    o[0] = make_float4(a[0], a[1], a[2], e1[0]);
-    o[1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
-    o[2] = make_float4(e2[2], nx, ny, nz);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        slot_box[(size_t)s * 6 + k] = dec(imin(imin(enc(a[k]), enc(b[k])), enc(c[k])));
-        slot_box[(size_t)s * 6 + 3 + k] = dec(imax(imax(enc(a[k]), enc(b[k])), enc(c[k])));
-    }
+    for (int k = 0; k < 6; ++k) slot_box[(size_t)s * 6 + k] = bx[k];
     const uint32_t lab = (sem ? (uint32_t)sem[id] : 0u) | ((ins ? (uint32_t)ins[id] : 0u) << 16);
     slot_prim[s] = id;
     slot_label[s] = lab;

@@ -17,6 +17,7 @@
 #include "lrc_material.h"
 #include "lrc_movers.h"
 #include "lrc_flow.h"
+#include "lrc_deform.h"
 
 // sets lrc_last_error() (lidarcast.hip).  Exported: lrc_nprandom.cpp, built without HIP headers, reports through it.
 extern "C" int lrc_internal_fail(int code, const char* msg);
@@ -146,6 +147,7 @@ struct lrc_scene {
     lrc_scene_info info{};
     lrc_scan_options opts{};          // sticky opt-in options (lrc_scene_set_options)
     uint64_t launches = 0, rays = 0;
+    lrc_deform* deform = nullptr;     // the deformable that owns this scene (lrc_deform_create); NULL for an ordinary scene
     void* flow_scratch = nullptr;     // flow_scan_dev without a mover set: grown on demand (a set brings its own scratch)
     uint64_t flow_scratch_cap = 0;
 };
@@ -186,6 +188,11 @@ inline int env_int(const char* name, int dflt) { const char* e = std::getenv(nam
 
 // the mesh checks of lrc_coverage_create and lrc_frameobj_create (non-finite vertex, triangle index out of range); `who`
 // prefixes the message.  Defined in lidarcast.hip, beside fail(): host code with no unit of its own.
+// lrc_scene_create with the node images chosen by the caller (qmode as LRC_QNODES; lidarcast.hip): lrc_deform_create asks for
+// float32 nodes whatever the environment says
+int scene_create_mode(lrc_ctx* ctx, const float* verts3, uint64_t V, const uint32_t* tris3, uint64_t T, const uint16_t* tri_sem,
+                      const uint16_t* tri_ins, int qmode, lrc_scene** out_scene);
+
 int check_mesh(const char* who, const double* verts3, uint64_t V, const int32_t* tris3, uint64_t T);
 
 // lrc_noise.hip: checks an lrc_noise for a table of N rays (LRC_ERR_INVALID_ARG, `who` prefixes the message), makes the

@@ -44,6 +44,8 @@ SYMBOLS = (
     "lrc_mover_merge",
     "lrc_scan_mover_sweeps_dev", "lrc_scan_mover_sweeps_compact", "lrc_mover_sweep_rays", "lrc_mover_sweep_normals",
     "lrc_scan_flow_dev", "lrc_scan_flow_compact", "lrc_flow_rays", "lrc_flow_status",
+    "lrc_deform_create", "lrc_deform_destroy", "lrc_deform_scene", "lrc_deform_set_dev", "lrc_deform_vertices",
+    "lrc_deform_launches", "lrc_deform_blend", "lrc_deform_refit",
     "lrc_compact", "lrc_compact_dev", "lrc_cloud_from_ranges_dev", "lrc_cloud_from_prims_dev",
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
@@ -225,6 +227,8 @@ def load():
     lib.lrc_last_error.argtypes = []
     lib.lrc_device_count.restype = i32
     lib.lrc_device_count.argtypes = []
+    lib.lrc_deform_scene.restype = C.c_void_p
+    lib.lrc_deform_scene.argtypes = [C.c_void_p]
     sig = {
         "lrc_ctx_create": [i32, C.POINTER(vp)],
         "lrc_ctx_destroy": [vp],
@@ -303,6 +307,13 @@ def load():
         "lrc_scan_flow_compact": [vp, vp, vp, u64, vp, vp, vp, vp, vp, dbl, C.POINTER(LrcFrames), vp, vp, vp, u64, C.POINTER(u64)],
         "lrc_flow_rays": [vp, vp, vp, u64, u64, C.c_uint32, vp, vp, vp, vp, dbl, dbl, vp, vp, vp, vp, vp],
         "lrc_flow_status": [u64, C.c_uint32, vp, vp, vp, vp, vp],
+        "lrc_deform_create": [vp, vp, C.c_uint32, u64, vp, u64, vp, vp, C.POINTER(vp)],
+        "lrc_deform_destroy": [vp],
+        "lrc_deform_set_dev": [vp, C.c_uint32, C.c_uint32, C.c_float, vp],
+        "lrc_deform_vertices": [vp, vp],
+        "lrc_deform_launches": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+        "lrc_deform_blend": [vp, vp, u64, C.c_float, vp],
+        "lrc_deform_refit": [vp, u64, vp, u64, vp, u64, vp, u64, vp, vp],
         "lrc_occ_create": [vp, vp, u64, C.POINTER(vp)],
         "lrc_occ_destroy": [vp],
         "lrc_occ_query": [vp, vp, u64, dbl, vp],

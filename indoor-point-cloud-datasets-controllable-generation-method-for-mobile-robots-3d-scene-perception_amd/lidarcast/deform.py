@@ -1,0 +1,250 @@
+"""Deforming movers: keyframed meshes blended and refitted on the device (include/lidarcast.h "deforming movers", DESIGN.md
+section 5o).
+
+``Deformable`` holds one topology with K keyframes of its vertices and owns an ordinary ``Scene`` built from keyframe 0;
+``set(k0, k1, w)`` enqueues the blend of two keyframes and the refit of the scene's triangle records, slot boxes and node
+boxes -- the tree is not rebuilt, and the refitted tree gives the hits of a fresh build bit for bit.  ``blend`` and ``refit``
+are the two host steps of that, without a GPU (lrc_deform_blend, lrc_deform_refit).  ``Clip`` turns times into the
+(k0, k1, w) of a cyclic or one-shot animation.  A ``lidarcast.movers.MoverSet`` takes a ``Deformable`` among its meshes;
+``scan_deforming_frames`` / ``scan_deforming_dev`` scan frames whose movers change shape from frame to frame.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import LrcHits, check
+from .core import Scene
+
+
+class _OwnedScene(Scene):
+    """The ``Scene`` of a deformable: every method of ``lidarcast.Scene`` on a handle the deformable owns."""
+
+    def __init__(self, ctx, handle, num_vertices, num_triangles):
+        self._lib = _capi.load()
+        self.ctx = ctx
+        self._h = C.c_void_p(handle)
+        self.num_vertices, self.num_triangles = num_vertices, num_triangles
+
+    def close(self):            # lrc_deform_destroy frees the scene
+        self._h = None
+
+
+class Deformable:
+    """keyframes: (K, V, 3), narrowed to float32 once; triangles (T, 3); optional per-triangle labels.  ``scene`` is the
+    deformable's scene (float32 nodes, built from keyframe 0), valid until ``close``; ``keyframes`` the float32 array."""
+
+    def __init__(self, ctx, keyframes, triangles, triangle_sem=None, triangle_ins=None):
+        self._lib = _capi.load()
+        self.ctx = ctx
+        self._h = None
+        self.scene = None
+        k = np.ascontiguousarray(np.asarray(keyframes), dtype=np.float32)
+        if k.ndim != 3 or k.shape[2] != 3:
+            raise ValueError("keyframes must be (K, V, 3)")
+        f = np.asarray(triangles)
+        if f.size == 0:
+            f = np.zeros((0, 3), dtype=np.uint32)
+        if f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError("triangles must be (T, 3)")
+        if f.size and f.dtype.kind != "u" and f.min() < 0:
+            raise ValueError("negative triangle index")
+        f = np.ascontiguousarray(f, dtype=np.uint32)
+        sem = None if triangle_sem is None else np.ascontiguousarray(triangle_sem, dtype=np.uint16)
+        ins = None if triangle_ins is None else np.ascontiguousarray(triangle_ins, dtype=np.uint16)
+        for lab in (sem, ins):
+            if lab is not None and lab.shape != (f.shape[0],):
+                raise ValueError("per-triangle labels must have shape (T,)")
+        self.keyframes, self.triangles = k, f
+        h = C.c_void_p()
+        check(self._lib.lrc_deform_create(ctx._h, k.ctypes.data, k.shape[0], k.shape[1], f.ctypes.data, f.shape[0],
+                                          None if sem is None else sem.ctypes.data, None if ins is None else ins.ctypes.data,
+                                          C.byref(h)), "lrc_deform_create")
+        self._h = h
+        self.scene = _OwnedScene(ctx, self._lib.lrc_deform_scene(h), k.shape[1], f.shape[0])
+
+    def __len__(self):
+        return len(self.triangles)
+
+    @property
+    def num_keyframes(self):
+        return self.keyframes.shape[0]
+
+    def set(self, k0, k1, w, stream=0):
+        """Enqueue on ``stream`` the shape ``blend(keyframes[k0], keyframes[k1], w)`` and the refit of the scene to it
+        (lrc_deform_set_dev); no host synchronisation.  A scan enqueued on the same stream afterwards sees the new shape."""
+        if not self._h:
+            raise ValueError("deformable is closed")
+        if int(k0) < 0 or int(k1) < 0:
+            raise ValueError("keyframe index out of range")
+        check(self._lib.lrc_deform_set_dev(self._h, int(k0), int(k1), float(np.float32(w)), C.c_void_p(int(stream))),
+              "lrc_deform_set_dev")
+
+    def vertices(self):
+        """The current (V, 3) float32 vertices, read back synchronously."""
+        out = np.empty((self.keyframes.shape[1], 3), np.float32)
+        check(self._lib.lrc_deform_vertices(self._h, out.ctypes.data), "lrc_deform_vertices")
+        return out
+
+    def launches(self):
+        """(kernel launches of one ``set`` that blends, of one that copies a keyframe)."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        check(self._lib.lrc_deform_launches(self._h, C.byref(a), C.byref(b)), "lrc_deform_launches")
+        return int(a.value), int(b.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                self._lib.lrc_deform_destroy(self._h)
+            self._h = None
+        if getattr(self, "scene", None) is not None:
+            self.scene._h = None
+            self.scene = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def blend(a, b, w):
+    """lrc_deform_blend: the (V, 3) float32 blend of vertex arrays ``a`` and ``b``; no GPU.  Per coordinate
+    v = a + w * (b - a), clamped into [min(a, b), max(a, b)]; w == 0 copies ``a`` and w == 1 copies ``b`` bit for bit."""
+    lib = _capi.load()
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError("a and b must have the same shape")
+    out = np.empty_like(a)
+    check(lib.lrc_deform_blend(a.ctypes.data, b.ctypes.data, len(a), float(np.float32(w)), out.ctypes.data), "lrc_deform_blend")
+    return out
+
+
+def refit(nodes16, slot_prim, triangles, vertices):
+    """lrc_deform_refit: the tree ``nodes16`` (num_nodes, 16) float32 over the leaf slots ``slot_prim`` refitted to
+    ``vertices``; no GPU.  Returns (nodes with every child box recomputed and the references untouched, (num_slots, 12)
+    triangle records, (num_slots, 6) slot boxes)."""
+    lib = _capi.load()
+    nodes = np.array(nodes16, dtype=np.float32, order="C").reshape(-1, 16)       # a copy: the input keeps its boxes
+    sp = np.ascontiguousarray(slot_prim, dtype=np.uint32).reshape(-1)
+    f = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    rec = np.zeros((len(sp), 12), np.float32)
+    box = np.zeros((len(sp), 6), np.float32)
+    check(lib.lrc_deform_refit(nodes.ctypes.data, len(nodes), sp.ctypes.data, len(sp), f.ctypes.data, len(f), v.ctypes.data,
+                               len(v), rec.ctypes.data, box.ctypes.data), "lrc_deform_refit")
+    return nodes, rec, box
+
+
+class Clip:
+    """An animation of K keyframes that takes ``cycle`` seconds: at time t the shape lies at x = (t / cycle + phase) * K
+    keyframes.  ``loop``: k0 = floor(x) mod K, k1 = (k0 + 1) mod K (the last keyframe blends back into the first); without
+    ``loop`` x is clamped to [0, K - 1] and the clip holds its first and last keyframe.  w = x - floor(x), float64 arithmetic,
+    narrowed to float32 last."""
+
+    def __init__(self, K, cycle, phase=0.0, loop=True):
+        self.K, self.cycle, self.phase, self.loop = int(K), float(cycle), float(phase), bool(loop)
+        if self.K < 1:
+            raise ValueError("a clip has at least one keyframe")
+        if not (np.isfinite(self.cycle) and self.cycle > 0.0) or not np.isfinite(self.phase):
+            raise ValueError("a clip needs a positive finite cycle and a finite phase")
+
+    def shape(self, times):
+        """(k0, k1, w) at ``times``: two (n,) uint32 arrays and one (n,) float32 array."""
+        t = np.atleast_1d(np.asarray(times, dtype=np.float64))
+        if not np.isfinite(t).all():
+            raise ValueError("times must be finite")
+        x = (t / self.cycle + self.phase) * self.K
+        if not self.loop:
+            x = np.clip(x, 0.0, float(self.K - 1))
+        fl = np.floor(x)
+        w = (x - fl).astype(np.float32)
+        if self.loop:
+            k0 = np.mod(fl, self.K).astype(np.int64)
+            k1 = (k0 + 1) % self.K
+        else:
+            k0 = fl.astype(np.int64)
+            k1 = np.minimum(k0 + 1, self.K - 1)
+        return k0.astype(np.uint32), k1.astype(np.uint32), w
+
+    def shapes3(self, times):
+        """The same as an (n, 3) float64 array [k0, k1, w]: one mover's column of the ``shapes`` of ``scan_deforming_*``."""
+        k0, k1, w = self.shape(times)
+        return np.stack([k0.astype(np.float64), k1.astype(np.float64), w.astype(np.float64)], 1)
+
+
+def _shapes(shapes, P, movers):
+    ds = [m for m in movers.deformables]
+    s = np.asarray(shapes, dtype=np.float64)
+    if s.shape != (P, len(ds), 3):
+        raise ValueError(f"shapes must be (P, D, 3) = ({P}, {len(ds)}, 3), got {s.shape}")
+    return ds, s
+
+
+def _runs(s):
+    """[(first, past-the-end)] of the runs of consecutive frames with equal shapes."""
+    P = len(s)
+    cut = [0] + [p for p in range(1, P) if not np.array_equal(s[p], s[p - 1])] + [P]
+    return [(a, b) for a, b in zip(cut[:-1], cut[1:]) if b > a]
+
+
+def scan_deforming_frames(engine, intrinsics, poses, mesh, movers, mover_poses, shapes, want=("point3", "sem", "ins")):
+    """``RaycastEngineHIP.scan_mover_frames`` with movers that change shape from frame to frame: ``shapes`` (P, D, 3) float64
+    holds [k0, k1, w] per frame and per deformable of the set, in the set's order (``Clip.shapes3``).  Per run of consecutive
+    frames with equal shapes every deformable is set once and the run is scanned by lrc_scan_movers_compact; a scan does not
+    depend on how its poses are split into calls, so the runs stack to the dict ``scan_mover_frames``
+    returns for all frames."""
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    P = len(poses)
+    ds, s = _shapes(shapes, P, movers)
+    mp = np.ascontiguousarray(mover_poses, dtype=np.float32)
+    if mp.shape != (P, len(movers), 12):
+        raise ValueError(f"mover_poses must be (P, M, 12) = ({P}, {len(movers)}, 12), got {mp.shape}")
+    parts = []
+    for a, b in _runs(s):
+        for j, d in enumerate(ds):
+            d.set(int(s[a, j, 0]), int(s[a, j, 1]), s[a, j, 2])
+        engine.ctx.synchronize()          # the frame path scans on the library's own streams
+        parts.append(engine.scan_mover_frames(intrinsics, poses[a:b], mesh, movers, mp[a:b], want=want))
+    if not parts:
+        return engine.scan_mover_frames(intrinsics, poses, mesh, movers, mp, want=want)
+    out = {}
+    for key in parts[0]:
+        if key == "total":
+            out[key] = int(sum(p[key] for p in parts))
+        else:
+            out[key] = np.concatenate([p[key] for p in parts], 0)
+    return out
+
+
+def scan_deforming_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover_poses_t, shapes, mover_t=None, stream=0):
+    """``Scene.scan_movers_dev`` with movers that change shape from frame to frame, everything enqueued on ``stream`` with no
+    host synchronisation: per run of consecutive frames with equal ``shapes`` (P, D, 3) one ``set`` per deformable, then
+    lrc_scan_movers_dev on the run's slice of the poses, the records and ``mover_t``."""
+    P, N = poses_t.shape[0], dirs_t.shape[0]
+    if hits.n != P * N:
+        raise ValueError("hits must hold P * N records")
+    if "tile_count" in hits.want:
+        raise ValueError("tile_count is not written by this scan")
+    ds, s = _shapes(shapes, P, movers)
+    M = len(movers)
+    mp = mover_poses_t.reshape(P, M, 12)
+    for a, b in _runs(s):
+        for j, d in enumerate(ds):
+            d.set(int(s[a, j, 0]), int(s[a, j, 1]), s[a, j, 2], stream=stream)
+        part = _HitsSlice(hits, a * N, b * N)
+        scene.scan_movers_dev(poses_t[a:b], dirs_t, part, max_range, movers, mp[a:b],
+                              None if mover_t is None else mover_t[a * N:b * N], stream=stream)
+
+
+class _HitsSlice:
+    """Records [first, last) of a ``DeviceHits`` as the records of a call of their own."""
+
+    def __init__(self, hits, first, last):
+        self.n = last - first
+        self.want = hits.want
+        self.tensors = {a: hits.tensors[a][first:last] for a in hits.want}
+        self.struct = LrcHits()
+        for a, t in self.tensors.items():
+            setattr(self.struct, a, t.data_ptr())

@@ -23,10 +23,13 @@ MAX_MOVERS = 255
 class MoverSet:
     """meshes: 1 to 255 triangle meshes (``vertices``, ``triangles`` and optionally ``triangle_sem`` / ``triangle_ins``, as
     ``lidarcast.synth.TriangleMesh``), each around its own origin.  Builds and owns one ``Scene`` per mesh on ``ctx`` and the
-    set's handle; ``boxes`` holds every mesh's own (lo, hi) float64 box."""
+    set's handle; ``boxes`` holds every mesh's own (lo, hi) float64 box.  A ``lidarcast.deform.Deformable`` among the meshes
+    brings its own scene, which the set uses without owning it (close the set before the deformable); its box is that of
+    all its keyframes."""
 
     def __init__(self, ctx, meshes):
         from .core import Scene
+        from .deform import Deformable
         meshes = list(meshes)
         if not 1 <= len(meshes) <= MAX_MOVERS:
             raise ValueError("a mover set has 1 to 255 movers")
@@ -34,11 +37,22 @@ class MoverSet:
         self.ctx = ctx
         self.scenes = []
         self.boxes = []
+        self.deformables = []       # the ``lidarcast.deform.Deformable`` members, in the set's order
+        self._owned = []
         self._h = None
         try:
             for m in meshes:
+                if isinstance(m, Deformable):       # its own scene, not owned here; the box of all its keyframes
+                    if m.ctx is not ctx:
+                        raise ValueError("a deformable of a mover set must belong to the set's context")
+                    inf = m.scene.info
+                    self.scenes.append(m.scene)
+                    self.deformables.append(m)
+                    self.boxes.append((np.array(inf["bounds_lo"], np.float64), np.array(inf["bounds_hi"], np.float64)))
+                    continue
                 v = np.asarray(m.vertices, dtype=np.float64)
                 self.scenes.append(Scene(ctx, v, m.triangles, getattr(m, "triangle_sem", None), getattr(m, "triangle_ins", None)))
+                self._owned.append(self.scenes[-1])
                 self.boxes.append((v.min(0), v.max(0)) if len(v) else (np.zeros(3), np.zeros(3)))
             arr = (C.c_void_p * len(self.scenes))(*[s._h for s in self.scenes])
             h = C.c_void_p()
@@ -64,9 +78,9 @@ class MoverSet:
             if getattr(self.ctx, "_h", None):
                 self._lib.lrc_movers_destroy(self._h)
             self._h = None
-        for s in getattr(self, "scenes", []):
+        for s in getattr(self, "_owned", []):
             s.close()
-        self.scenes = []
+        self.scenes, self._owned, self.deformables = [], [], []
 
     def __del__(self):
         try:

@@ -231,6 +231,70 @@ def make_pedestrian(height=1.7, radius=0.25, segments=16, rings=8, semantic=13, 
                         triangle_ins=np.full(len(t), instance, np.uint16))
 
 
+def _prism(cx, cy, z0, z1, rx, ry, segments, rings):
+    """A closed elliptic prism about the vertical through (cx, cy) from z0 to z1, wound outward: the topology of
+    ``make_pedestrian`` (2 * segments * rings + 2 * segments triangles).  Returns (float64 vertices, int32 triangles)."""
+    ang = 2.0 * np.pi * np.arange(segments) / segments
+    ring = np.stack([cx + rx * np.cos(ang), cy + ry * np.sin(ang)], 1)
+    v = np.concatenate([np.concatenate([ring, np.full((segments, 1), zk)], 1) for zk in np.linspace(z0, z1, rings + 1)] +
+                       [np.array([[cx, cy, z0], [cx, cy, z1]])], 0)
+    bottom, top = segments * (rings + 1), segments * (rings + 1) + 1
+    t = []
+    for k in range(rings):
+        for j in range(segments):
+            a, b = k * segments + j, k * segments + (j + 1) % segments
+            t += [(a, b, b + segments), (a, b + segments, a + segments)]
+    for j in range(segments):
+        a, b = j, (j + 1) % segments
+        t += [(bottom, b, a), (top, rings * segments + a, rings * segments + b)]
+    return v, np.array(t, dtype=np.int32)
+
+
+def make_walker(height=1.7, keyframes=8, swing_deg=25, semantic=13, instance=1):
+    """A walking person for ``lidarcast.deform``: torso, head, two legs and two arms as closed eight-sided prisms (384
+    triangles), facing +x, feet at z = 0, standing on its own origin.  Keyframe k of ``keyframes`` turns the legs about the hip
+    axis and the arms about the shoulder axis (both along y) by swing_deg * sin(2 pi k / keyframes), the left leg and the right
+    arm one way, the right leg and the left arm the other; every keyframe is then lowered so that its lowest vertex stays at
+    z = 0.  Computed in float64 and narrowed to float32.  Returns the ``TriangleMesh`` of keyframe 0 (its vertices are keyframe
+    0's float32 values) with ``keyframes``, the (K, V, 3) float32 array, as an attribute; the topology is the same in every
+    keyframe."""
+    K, H = int(keyframes), float(height)
+    if K < 1 or not H > 0.0:
+        raise ValueError("a walker needs at least one keyframe and a positive height")
+    seg = 8
+    # (centre x, y, z0, z1, radius x, y, rings, pivot height or None, swing sign)
+    parts = [(0.0, 0.0, 0.50 * H, 0.85 * H, 0.07 * H, 0.12 * H, 4, None, 0.0),            # torso
+             (0.0, 0.0, 0.87 * H, 1.00 * H, 0.06 * H, 0.06 * H, 2, None, 0.0),            # head
+             (0.0, 0.06 * H, 0.0, 0.50 * H, 0.045 * H, 0.045 * H, 3, 0.50 * H, 1.0),      # left leg
+             (0.0, -0.06 * H, 0.0, 0.50 * H, 0.045 * H, 0.045 * H, 3, 0.50 * H, -1.0),    # right leg
+             (0.0, 0.155 * H, 0.47 * H, 0.83 * H, 0.03 * H, 0.03 * H, 3, 0.83 * H, -1.0),  # left arm
+             (0.0, -0.155 * H, 0.47 * H, 0.83 * H, 0.03 * H, 0.03 * H, 3, 0.83 * H, 1.0)]  # right arm
+    verts, tris, pivot, sign, base = [], [], [], [], 0
+    for cx, cy, z0, z1, rx, ry, rings, pz, sg in parts:
+        v, t = _prism(cx, cy, z0, z1, rx, ry, seg, rings)
+        verts.append(v)
+        tris.append(t + base)
+        pivot.append(np.full(len(v), z0 if pz is None else pz))
+        sign.append(np.full(len(v), sg))
+        base += len(v)
+    v0, t = np.concatenate(verts, 0), np.concatenate(tris, 0)
+    pivot, sign = np.concatenate(pivot), np.concatenate(sign)
+    keys = np.empty((K, len(v0), 3), np.float64)
+    for k in range(K):
+        a = sign * np.deg2rad(float(swing_deg)) * np.sin(2.0 * np.pi * k / K)
+        c, s = np.cos(a), np.sin(a)
+        dz = v0[:, 2] - pivot
+        keys[k, :, 0] = v0[:, 0] * c + dz * s
+        keys[k, :, 1] = v0[:, 1]
+        keys[k, :, 2] = pivot - v0[:, 0] * s + dz * c
+        keys[k, :, 2] -= keys[k, :, 2].min()
+    keys = keys.astype(np.float32)
+    mesh = TriangleMesh(vertices=keys[0].astype(np.float64), triangles=t, triangle_sem=np.full(len(t), semantic, np.uint16),
+                        triangle_ins=np.full(len(t), instance, np.uint16))
+    mesh.keyframes = keys
+    return mesh
+
+
 def quad(z=2.0, half=1.0):
     """Two triangles forming the square |x|,|y| <= half in the plane z."""
     v = np.array([[-half, -half, z], [half, -half, z], [half, half, z], [-half, half, z]], dtype=np.float64)

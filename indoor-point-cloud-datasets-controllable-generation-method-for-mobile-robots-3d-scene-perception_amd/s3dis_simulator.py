@@ -373,6 +373,11 @@ class S3DISSimulator:
         instance: id, path: [[t, x, y, z, yaw_deg], ...]}``, and optionally ``flow: true`` (scene flow: frames then carry the flow
         to the next frame and its status).  Returns {period, meshes, tracks, objects (JSON-ready), flow}.
         The key stands alone: motion, noise, beam and materials are refused beside it.
+        An object may carry ``animation: {cycle: <seconds>, phase: 0.0, loop: true}`` (a deforming mover):
+        with ``mesh: walker`` the keyframes come from ``synth.make_walker``, with ``keyframes: <file.npy>`` a (K, V, 3) array serves
+        the mesh file's own topology; frame k takes the shape of k * period.  The plan then also holds ``clips`` and ``keyframes``
+        (one entry per object, None for a rigid one).  ``flow: true`` is refused in a set with an animated mover (the rigid flow
+        step is wrong for it), and so is ``animation`` under ``motion.movers`` (no deformation within a sweep).
         ``nested``: the same entries under ``motion: {movers: ...}``, movers that go on moving while a sweep is scanned (DESIGN.md
         section 5n): sweep k starts at k * period.  There ``flow: true`` is refused (no scene flow under sweeps), and so are
         ``motion.noise``, beam and materials beside it."""
@@ -407,9 +412,9 @@ class S3DISSimulator:
             raise ValueError(f"the {key} key takes at most 255 objects")
         from lidarcast import synth
         from lidarcast.movers import MoverTrack
-        meshes, tracks, listed = [], [], []
+        meshes, tracks, listed, clips, keyframes = [], [], [], [], []
         for k, obj in enumerate(objects):
-            unknown = set(obj) - {"mesh", "semantic", "instance", "path"}
+            unknown = set(obj) - {"mesh", "semantic", "instance", "path", "animation", "keyframes"}
             if unknown:
                 raise ValueError(f"unknown entries of mover {k}: {sorted(unknown)}")
             if "path" not in obj:
@@ -425,18 +430,58 @@ class S3DISSimulator:
             name = obj.get("mesh", "pedestrian")
             if name == "pedestrian":
                 mesh = synth.make_pedestrian(semantic=sem, instance=ins)
+            elif name == "walker":
+                mesh = synth.make_walker(semantic=sem, instance=ins)
             else:
                 from lidarcast.ply import read_triangle_mesh
                 src = read_triangle_mesh(str(name))
                 f = np.asarray(src.triangles, np.int32)
                 mesh = synth.TriangleMesh(vertices=np.asarray(src.vertices, np.float64), triangles=f,
                                           triangle_sem=np.full(len(f), sem, np.uint16), triangle_ins=np.full(len(f), ins, np.uint16))
+            clip, keys = self._mover_animation(k, key, obj, mesh, nested)
             meshes.append(mesh)
             tracks.append(MoverTrack(obj["path"]))
+            clips.append(clip)
+            keyframes.append(keys)
+            box = np.asarray(mesh.vertices) if keys is None else keys.reshape(-1, 3)      # an animated mover: all its keyframes
             listed.append({"index": k, "mesh": str(name), "semantic": sem, "instance": ins, "num_triangles": len(mesh.triangles),
-                           "box_min": [float(x) for x in np.asarray(mesh.vertices).min(0)],
-                           "box_max": [float(x) for x in np.asarray(mesh.vertices).max(0)]})
-        return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed, "flow": bool(cfg.get("flow", False))}
+                           "box_min": [float(x) for x in box.min(0)], "box_max": [float(x) for x in box.max(0)]})
+            if clip is not None:
+                listed[-1]["animation"] = {"cycle": clip.cycle, "phase": clip.phase, "loop": clip.loop, "num_keyframes": clip.K}
+        if cfg.get("flow", False) and any(c is not None for c in clips):
+            raise ValueError(f"{key}.flow is not available in a set with an animated mover: the flow of a rigid step is wrong "
+                             "for a surface that changes shape (non-rigid flow is not built)")
+        return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed, "flow": bool(cfg.get("flow", False)),
+                "clips": clips, "keyframes": keyframes}
+
+    @staticmethod
+    def _mover_animation(k, key, obj, mesh, nested):
+        """(Clip, (K, V, 3) float32 keyframes) of mover ``k``'s ``animation`` entry, (None, None) without one."""
+        anim = obj.get("animation")
+        if anim is None:
+            if obj.get("keyframes") is not None:
+                raise ValueError(f"mover {k}: keyframes need an animation entry")
+            return None, None
+        if nested:
+            raise ValueError("animation is not available under motion.movers: deformation within a sweep is not built")
+        if not isinstance(anim, dict) or set(anim) - {"cycle", "phase", "loop"} or "cycle" not in anim:
+            raise ValueError(f"mover {k}: animation is {{cycle: <seconds>, phase: 0.0, loop: true}}")
+        if not isinstance(anim.get("loop", True), bool):
+            raise ValueError(f"mover {k}: animation.loop must be true or false")
+        if obj.get("keyframes") is not None:
+            keys = np.load(str(obj["keyframes"]), allow_pickle=False)
+            if keys.ndim != 3 or keys.shape[1:] != (len(mesh.vertices), 3) or keys.shape[0] < 1:
+                raise ValueError(f"mover {k}: keyframes must be (K, V, 3) with V = {len(mesh.vertices)} vertices of its mesh, "
+                                 f"got {keys.shape}")
+            keys = np.ascontiguousarray(keys, dtype=np.float32)
+        elif getattr(mesh, "keyframes", None) is not None:
+            keys = mesh.keyframes
+        else:
+            raise ValueError(f"mover {k}: an animation needs mesh: walker or a keyframes file")
+        if not np.isfinite(keys).all():
+            raise ValueError(f"mover {k}: keyframes must be finite")
+        from lidarcast.deform import Clip
+        return Clip(len(keys), anim["cycle"], phase=float(anim.get("phase", 0.0)), loop=anim.get("loop", True)), keys
 
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
@@ -544,15 +589,34 @@ class S3DISSimulator:
             times = np.arange(len(waypoints), dtype=np.float64) * movers["period"]
             states = np.stack([t.state(times) for t in movers["tracks"]], axis=1)            # (P, M, 4): x, y, z, yaw
             mover_poses = np.stack([t.poses12(times) for t in movers["tracks"]], axis=1)       # (P, M, 12) float32
-            mset = MoverSet(engine.ctx, movers["meshes"])
+            animated = [m for m, c in enumerate(movers["clips"]) if c is not None]
+            deformables, mset = {}, None
             try:
-                scan = engine.scan_flow_frames if movers["flow"] else engine.scan_mover_frames
-                fr = scan(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, want=want)
+                if animated:        # deforming movers: one Deformable each, set per run of frames with equal shapes
+                    from lidarcast import deform
+                    for m in animated:
+                        mm = movers["meshes"][m]
+                        deformables[m] = deform.Deformable(engine.ctx, movers["keyframes"][m], mm.triangles, mm.triangle_sem,
+                                                           mm.triangle_ins)
+                    mset = MoverSet(engine.ctx, [deformables.get(m, mm) for m, mm in enumerate(movers["meshes"])])
+                    shapes = np.stack([movers["clips"][m].shapes3(times) for m in animated], axis=1)      # (P, D, 3)
+                    fr = deform.scan_deforming_frames(engine, self.lidar_config, poses_from_waypoints(waypoints), mesh, mset,
+                                                      mover_poses, shapes, want=want)
+                else:
+                    mset = MoverSet(engine.ctx, movers["meshes"])
+                    scan = engine.scan_flow_frames if movers["flow"] else engine.scan_mover_frames
+                    fr = scan(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, want=want)
             finally:
-                mset.close()
+                if mset is not None:
+                    mset.close()
+                for d in deformables.values():
+                    d.close()
             sim_scene.mover_tracks = {"period": movers["period"], "objects": movers["objects"], "times": times,
                                       "states": states, "poses12": mover_poses,
                                       "sensor_poses": poses_from_waypoints(waypoints)}
+            if animated:
+                sim_scene.mover_tracks["shapes"] = {m: movers["clips"][m].shapes3(times) for m in animated}
+                sim_scene.mover_tracks["keyframes"] = {m: movers["keyframes"][m] for m in animated}
         elif materials is not None:
             if dist is not None:
                 raise ValueError("the materials key is not available on a multi-rank process group")
