@@ -909,6 +909,64 @@ int lrc_deform_blend(const float* a3, const float* b3, uint64_t num_vertices, fl
 int lrc_deform_refit(float* nodes16, uint64_t num_nodes, const uint32_t* slot_prim, uint64_t num_slots, const uint32_t* tris3,
                      uint64_t T, const float* verts3, uint64_t V, float* out_tri_rec12, float* out_slot_box6);
 
+/* ---- non-rigid scene flow: the flow of deforming movers (opt-in) -----------------------------------------
+ * The scene flow above for a set with deformables: a row on a deforming triangle flows to where ITS point of the triangle is in
+ * the next shape at the next pose, not to the rigid step.  A row has x = point3, w = mover, j = prim (a mover scan's prim is the
+ * row in the winner's own mesh).  A SURFACE PAIR for mover m = w - 1 is two vertex arrays of that mover's deformable: VA (the
+ * shape the row was scanned with) and VB (the next shape), (V, 3) float32 each, with the deformable's tris3 and T.  A row has no
+ * pair if its mover has none, if j >= T, or if w == 0 or w > M: it takes steps 1 and 2 of the scene flow unchanged.  A row with
+ * a pair, in float64, one rounding per operation, nothing fused:
+ *   1  q = R_A^T (x - c_A), by the expressions of step 1 there
+ *   2  (i0, i1, i2) = tris3[j]; a_k = float64(VA[i_k])
+ *   3  e1 = a1 - a0, e2 = a2 - a0, r = q - a0
+ *   4  dot products as (p_x q_x + p_y q_y) + p_z q_z: d11 = e1.e1, d12 = e1.e2, d22 = e2.e2, r1 = r.e1, r2 = r.e2
+ *   5  den = d11 * d22 - d12 * d12
+ *   6  u = (d22 * r1 - d12 * r2) / den, v = (d11 * r2 - d12 * r1) / den; unless den > 0, u = v = 0 (a triangle without area
+ *      yields no NaN)
+ *   7  s = (1 - u) - v; no clamp
+ *   8  D_k = float64(VB[i_k]) - a_k.  If all nine components compare equal to zero, z = q with no addition: a triangle that keeps
+ *      its shape gives the rigid step's bytes.  Otherwise z_c = q_c + ((s * D0_c + u * D1_c) + v * D2_c): the DISPLACEMENT is
+ *      interpolated, not the position, so what the float32 point lies off its plane by is carried along, not lost
+ *   9  y = R_B z + c_B, by the expressions of step 1 there
+ *  10  y = x, and +0 flow, if and only if the two poses have the same 48 bytes AND all D_k are zero
+ * From y on, steps 2 to 6 of the scene flow apply as they stand.  The status is cast against the movers' scenes AS THEY STAND on
+ * `stream`: the caller has set the next shape (lrc_deform_set_dev) before the call, on the same stream.
+ *   lrc_deform_snapshot_dev     enqueues on `stream` a copy of the deformable's current (V, 3) vertices into a caller's device
+ *                               buffer, with no wait: what a caller keeps as VA before it sets the next shape.  Refuses NULL.
+ *   lrc_scan_nonrigid_flow_dev  lrc_scan_flow_dev plus `pairs`: at most 16 per call, handed to the kernel in its arguments (no
+ *                               table upload, no host synchronisation); all P frames of a call share them, so a caller whose
+ *                               shapes change every frame calls it per frame.  A NULL d_verts_b3 means the deformable's current
+ *                               vertices.  The records need prim as well as t and point3.  num_pairs == 0 gives
+ *                               lrc_scan_flow_dev's bytes.  LRC_ERR_INVALID_ARG before any launch: what lrc_scan_flow_dev
+ *                               refuses; num_pairs > 16, or NULL pairs with num_pairs > 0; a pair whose mover >= M or whose
+ *                               mover is not a deformable's scene; a mover listed twice; a NULL d_verts_a3; records without prim.
+ *   lrc_nonrigid_flow_rays      host, no GPU: lrc_flow_rays plus prim and host pairs, by the inline functions the kernel calls.
+ *                               LRC_ERR_INVALID_ARG for more than 16 pairs, a mover >= M or listed twice, a NULL array of a pair
+ *                               or a triangle index >= V.  lrc_flow_status serves as it is. */
+typedef struct lrc_surface_pair {
+    uint32_t mover;                /* m: the rows with w == m + 1 */
+    const float* d_verts_a3;       /* (V, 3) device: the shape the rows were scanned with */
+    const float* d_verts_b3;       /* (V, 3) device: the next shape; NULL: the deformable's current vertices */
+} lrc_surface_pair;
+typedef struct lrc_surface_pair_host {
+    uint32_t mover;
+    const float* verts_a3;         /* (V, 3) host */
+    const float* verts_b3;         /* (V, 3) host */
+    const uint32_t* tris3;         /* (T, 3) host */
+    uint64_t T, V;
+} lrc_surface_pair_host;
+int lrc_deform_snapshot_dev(lrc_deform* deform, float* d_out_verts3, void* stream);
+int lrc_scan_nonrigid_flow_dev(lrc_scene* scene, lrc_movers* set /* nullable */, const lrc_hits* d_records, const uint8_t* d_mover,
+                               uint64_t num_poses, uint64_t rays_per_pose, const float* d_mover_poses12,
+                               const float* d_next_mover_poses12, const double* d_next_poses16,
+                               const uint8_t* d_has_next /* nullable */, double max_range, const lrc_surface_pair* pairs,
+                               uint32_t num_pairs, float* d_flow3, uint8_t* d_status /* nullable */, void* stream);
+int lrc_nonrigid_flow_rays(const float* t, const float* point3, const uint8_t* mover, const uint32_t* prim, uint64_t num_poses,
+                           uint64_t rays_per_pose, uint32_t num_movers, const float* mover_poses12,
+                           const float* next_mover_poses12, const double* next_poses16, const uint8_t* has_next /* nullable */,
+                           double max_range, double min_range, const lrc_surface_pair_host* pairs, uint32_t num_pairs,
+                           float* out_flow3, float* out_rays6, uint8_t* out_keep, float* out_thr, uint8_t* out_status);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

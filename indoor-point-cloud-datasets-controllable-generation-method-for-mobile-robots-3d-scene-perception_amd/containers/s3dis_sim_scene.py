@@ -446,7 +446,9 @@ class S3DISSimScene:
         ``points`` (K, 3) float32 of all frames stacked, ``flow`` (K, 3) float32 (world displacement of the surface under the
         point up to the next frame), ``status`` (K,) uint8 (0 no next frame, 1 visible from the next pose, 2 occluded, 3 out of
         range), ``mover_ids`` (K,) uint8, ``frame_offsets`` (F + 1,) int64 (frame f = rows [offsets[f], offsets[f + 1])),
-        ``sensor_poses`` (F, 4, 4) float64, ``mover_poses12`` (F, M, 12) float32 and ``times`` (F,).  Returns the arrays."""
+        ``sensor_poses`` (F, 4, 4) float64, ``mover_poses12`` (F, M, 12) float32 and ``times`` (F,).  A run under
+        ``nonrigid_flow: true`` with animated movers adds ``animated_movers`` (D,) int64, their places among the movers, and
+        ``mover_shapes`` (F, D, 3) float64, each one's [k0, k1, w] per frame.  Returns the arrays."""
         tr = self.mover_tracks
         if tr is None:
             raise ValueError("this scene was not simulated under the movers key")
@@ -469,6 +471,10 @@ class S3DISSimScene:
         out["sensor_poses"] = np.asarray(tr["sensor_poses"], np.float64).reshape(-1, 4, 4)
         out["mover_poses12"] = np.asarray(tr["poses12"], np.float32)
         out["times"] = np.asarray(tr["times"], np.float64)
+        if tr.get("shapes"):        # a run under nonrigid_flow: true with animated movers
+            animated = sorted(tr["shapes"])
+            out["animated_movers"] = np.asarray(animated, np.int64)
+            out["mover_shapes"] = np.stack([np.asarray(tr["shapes"][m], np.float64) for m in animated], axis=1)
         path = Path(output_dir)
         path.mkdir(parents=True, exist_ok=True)
         np.savez(path / f"{self.scene_name}_scene_flow.npz", **out)

@@ -696,6 +696,62 @@ __global__ __launch_bounds__(kBlock) void flow_rays_kernel(const FlowRays q) {
     o[2] = make_float2(r.h.y, r.h.z);
 }
 
+// The ray kernel of lrc_scan_nonrigid_flow_dev: flow_rays_kernel whose mover rows look their mover up among
+// the call's surface pairs (at most 16, in the kernel arguments: a wave-uniform walk of scalars) and, with a pair and prim < T,
+// fetch the triangle's three indices and its three vertices in both shapes per lane.  Every other row takes the rigid step.
+__global__ __launch_bounds__(kBlock) void nonrigid_target_kernel(const FlowRays q, const FlowPairs pp) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= q.total) return;
+    const uint32_t pose = (uint32_t)(gid / q.rays_per_pose);
+    const bool live = (q.t[gid] < __builtin_inff()) & (q.has_next == nullptr || q.has_next[pose] != 0);
+    const uint32_t w = (live && q.mover) ? q.mover[gid] : 0u;
+    float x[3] = {0.f, 0.f, 0.f}, A[12], B[12];
+    bool moved = false, paired = false;
+    if (live) {
+        x[0] = q.point3[gid * 3]; x[1] = q.point3[gid * 3 + 1]; x[2] = q.point3[gid * 3 + 2];
+    }
+    const float* va = nullptr;
+    const float* vb = nullptr;
+    const uint32_t* tris = nullptr;
+    uint32_t T = 0u;
+    if (w != 0u && w <= q.M) {
+        const size_t row = ((size_t)pose * q.M + (w - 1u)) * 12;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { A[k] = q.A[row + k]; B[k] = q.B[row + k]; }
+        moved = !lrcflow::same_pose(A, B);
+#pragma unroll
+        for (uint32_t k = 0; k < lrcflow::kMaxPairs; ++k)
+            if (k < pp.count && pp.mover[k] == w - 1u) { va = pp.va[k]; vb = pp.vb[k]; tris = pp.tris3[k]; T = pp.T[k]; }
+    }
+    lrcflow::Ray r;
+    if (T != 0u) {
+        const uint32_t j = pp.prim[gid];
+        if (j < T) {                                     // before any fetch: a miss's prim is 0xFFFFFFFF, a stale one anything
+            float a9[9], b9[9];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const size_t i = (size_t)tris[(size_t)j * 3 + c] * 3;
+#pragma unroll
+                for (int e = 0; e < 3; ++e) { a9[3 * c + e] = va[i + e]; b9[3 * c + e] = vb[i + e]; }
+            }
+            r = lrcflow::nonrigid_ray(x, A, B, a9, b9, q.next16 + (size_t)pose * 16, q.max_range, q.min_range);
+            paired = true;
+        }
+    }
+    if (!paired) r = lrcflow::ray(live, moved, x, A, B, q.next16 + (size_t)pose * 16, q.max_range, q.min_range);
+    q.flow3[gid * 3] = r.flow[0]; q.flow3[gid * 3 + 1] = r.flow[1]; q.flow3[gid * 3 + 2] = r.flow[2];
+    if (!q.status) return;
+    const bool cast = r.status == lrcflow::kVisible;
+    q.status[gid] = r.status;
+    q.keep[gid] = cast ? (uint8_t)1 : (uint8_t)0;
+    if (!cast) return;
+    q.thr[gid] = r.thr;
+    float2* o = (float2*)(q.rays6 + gid * 6);      // 24-byte records: 8-byte aligned
+    o[0] = make_float2(r.o.x, r.o.y);
+    o[1] = make_float2(r.o.z, r.h.x);
+    o[2] = make_float2(r.h.y, r.h.z);
+}
+
 // A mover's pass: the world ray of every row that is cast, taken into mover q.m's frame with its NEXT pose, and the keep byte of
 // the explicit-ray launch (0: not cast at all, or left out by lrcmov::culled).
 __global__ __launch_bounds__(kBlock) void flow_object_rays_kernel(const float* __restrict__ world6, const uint8_t* __restrict__ cast,
@@ -4430,13 +4486,14 @@ int mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion2
 
 // lrc_scan_flow_dev behind its checks (lrc_flow.hip).  All on `st`, nothing waited for:
 //   the ray kernel     flow_rays_kernel: the flow and, with d_status, the world line of sight, its cast byte, thr, the first status
+//                      (nonrigid_target_kernel instead when the call brings surface pairs)
 //   the static pass    the explicit-ray launch on the scene, straight into the running minimum
 //   per mover m        flow_object_rays_kernel (object-frame rays by the NEXT pose + keep bytes), the explicit-ray launch on the
 //                      mover's scene, flow_merge_kernel; the last merge writes the status
 // in the set's scratch (the scene's own without a set): two ray sets, two byte columns and three float columns whatever M is.
 int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const uint8_t* d_mover, uint64_t P, uint64_t N,
                   const float* d_mover_poses12, const FlowNext& next, double max_range, float* d_flow3, uint8_t* d_status,
-                  hipStream_t st) {
+                  hipStream_t st, const FlowPairs* pairs) {
     const uint64_t n = P * N;
     if (!n) return LRC_OK;
     if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
@@ -4450,8 +4507,14 @@ int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const ui
     fr.M = M; fr.rays_per_pose = N; fr.total = n;
     fr.max_range = max_range; fr.min_range = s->opts.min_range;
     fr.flow3 = d_flow3;
+    // with surface pairs (lrc_scan_nonrigid_flow_dev) the non-rigid ray kernel stands in for the rigid one; the passes behind it
+    // are the same
+    auto ray_kernel = [&]() {
+        if (pairs && pairs->count) hipLaunchKernelGGL(nonrigid_target_kernel, grid, dim3(kBlock), 0, st, fr, *pairs);
+        else hipLaunchKernelGGL(flow_rays_kernel, grid, dim3(kBlock), 0, st, fr);
+    };
     if (!d_status) {
-        hipLaunchKernelGGL(flow_rays_kernel, grid, dim3(kBlock), 0, st, fr);
+        ray_kernel();
         LRC_HIP(hipGetLastError());
         return LRC_OK;
     }
@@ -4478,7 +4541,7 @@ int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const ui
     w.t = (float*)(b + off[5]);
     mv.t = (float*)(b + off[6]);
     fr.rays6 = world6; fr.keep = cast; fr.thr = thr; fr.status = d_status;
-    hipLaunchKernelGGL(flow_rays_kernel, grid, dim3(kBlock), 0, st, fr);
+    ray_kernel();
     LRC_HIP(hipGetLastError());
     int rc;
     if ((rc = cast_plain(s, world6, cast, n, w, st))) return rc;

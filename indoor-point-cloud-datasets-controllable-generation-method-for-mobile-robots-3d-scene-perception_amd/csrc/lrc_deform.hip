@@ -130,6 +130,8 @@ bool coordinate_ok(float f) {        // the bit test of scene_create_host: finit
 
 }  // namespace
 
+DeformMesh deform_mesh(const lrc_deform* d) { return DeformMesh{d->d_verts, d->d_tris3, d->V, d->T}; }
+
 extern "C" {
 
 int lrc_deform_destroy(lrc_deform* d) {
@@ -277,6 +279,13 @@ int lrc_deform_vertices(lrc_deform* d, float* out_verts3) {
     LRC_HIP(hipSetDevice(d->ctx->device));
     LRC_HIP(hipDeviceSynchronize());
     if (d->V) LRC_HIP(hipMemcpy(out_verts3, d->d_verts, d->V * 12, hipMemcpyDeviceToHost));
+    return LRC_OK;
+}
+
+int lrc_deform_snapshot_dev(lrc_deform* d, float* d_out_verts3, void* stream) {
+    if (!d || !d_out_verts3) return fail(LRC_ERR_INVALID_ARG, "lrc_deform_snapshot_dev: NULL argument");
+    LRC_HIP(hipSetDevice(d->ctx->device));
+    if (d->V) LRC_HIP(hipMemcpyAsync(d_out_verts3, d->d_verts, d->V * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return LRC_OK;
 }
 

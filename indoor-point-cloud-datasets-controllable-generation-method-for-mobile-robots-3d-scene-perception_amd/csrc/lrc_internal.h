@@ -258,9 +258,24 @@ struct FlowNext {             // what pairs every frame of a call with its next 
     const double* next_poses16;
     const uint8_t* has_next;              // nullable: all ones
 };
+// non-rigid scene flow (lrc_scan_nonrigid_flow_dev): the surface pairs of one call as the kernel takes them, by value in its
+// arguments.  Entry k serves the rows of mover mover[k] (w - 1) whose prim is below T[k]; vb is never NULL here (lrc_flow.hip
+// has put the deformable's current vertices in).  count == 0, or a NULL pointer: the rigid ray kernel.
+struct FlowPairs {
+    uint32_t count;
+    uint32_t mover[16];
+    uint32_t T[16];
+    const float* va[16];
+    const float* vb[16];
+    const uint32_t* tris3[16];
+    const uint32_t* prim;                 // the records' prim column
+};
 int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const uint8_t* d_mover, uint64_t P, uint64_t N,
                   const float* d_mover_poses12, const FlowNext& next, double max_range, float* d_flow3, uint8_t* d_status,
-                  hipStream_t st);
+                  hipStream_t st, const FlowPairs* pairs = nullptr);
+// what a deformable keeps resident (lrc_deform.hip): its current vertices and its triangles
+struct DeformMesh { const float* d_verts3; const uint32_t* d_tris3; uint64_t V, T; };
+DeformMesh deform_mesh(const lrc_deform* d);
 int flow_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
                       const float* mover_poses12, const FlowNext& next, double max_range, const lrc_frames* out, uint8_t* mover_rows,
                       float* flow_rows, uint8_t* status_rows, uint64_t capacity, uint64_t* out_total);

@@ -46,6 +46,7 @@ SYMBOLS = (
     "lrc_scan_flow_dev", "lrc_scan_flow_compact", "lrc_flow_rays", "lrc_flow_status",
     "lrc_deform_create", "lrc_deform_destroy", "lrc_deform_scene", "lrc_deform_set_dev", "lrc_deform_vertices",
     "lrc_deform_launches", "lrc_deform_blend", "lrc_deform_refit",
+    "lrc_deform_snapshot_dev", "lrc_scan_nonrigid_flow_dev", "lrc_nonrigid_flow_rays",
     "lrc_compact", "lrc_compact_dev", "lrc_cloud_from_ranges_dev", "lrc_cloud_from_prims_dev",
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
@@ -103,6 +104,15 @@ class LrcMaterial(C.Structure):
 class LrcMaterialModel(C.Structure):
     _fields_ = [("num_classes", C.c_uint32), ("max_bounces", C.c_uint32), ("min_intensity", C.c_float),
                 ("reserved_", C.c_uint32)]
+
+
+class LrcSurfacePair(C.Structure):
+    _fields_ = [("mover", C.c_uint32), ("d_verts_a3", C.c_void_p), ("d_verts_b3", C.c_void_p)]
+
+
+class LrcSurfacePairHost(C.Structure):
+    _fields_ = [("mover", C.c_uint32), ("verts_a3", C.c_void_p), ("verts_b3", C.c_void_p), ("tris3", C.c_void_p),
+                ("T", C.c_uint64), ("V", C.c_uint64)]
 
 
 class LrcCoverageInfo(C.Structure):
@@ -314,6 +324,10 @@ def load():
         "lrc_deform_launches": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         "lrc_deform_blend": [vp, vp, u64, C.c_float, vp],
         "lrc_deform_refit": [vp, u64, vp, u64, vp, u64, vp, u64, vp, vp],
+        "lrc_deform_snapshot_dev": [vp, vp, vp],
+        "lrc_scan_nonrigid_flow_dev": [vp, vp, C.POINTER(LrcHits), vp, u64, u64, vp, vp, vp, vp, dbl, vp, C.c_uint32, vp, vp, vp],
+        "lrc_nonrigid_flow_rays": [vp, vp, vp, vp, u64, u64, C.c_uint32, vp, vp, vp, vp, dbl, dbl, vp, C.c_uint32, vp, vp, vp, vp,
+                                   vp],
         "lrc_occ_create": [vp, vp, u64, C.POINTER(vp)],
         "lrc_occ_destroy": [vp],
         "lrc_occ_query": [vp, vp, u64, dbl, vp],

@@ -6,7 +6,9 @@ section 5o).
 boxes -- the tree is not rebuilt, and the refitted tree gives the hits of a fresh build bit for bit.  ``blend`` and ``refit``
 are the two host steps of that, without a GPU (lrc_deform_blend, lrc_deform_refit).  ``Clip`` turns times into the
 (k0, k1, w) of a cyclic or one-shot animation.  A ``lidarcast.movers.MoverSet`` takes a ``Deformable`` among its meshes;
-``scan_deforming_frames`` / ``scan_deforming_dev`` scan frames whose movers change shape from frame to frame.
+``scan_deforming_frames`` / ``scan_deforming_dev`` scan frames whose movers change shape from frame to frame;
+``scan_deforming_flow_frames`` / ``scan_deforming_flow_dev`` add the non-rigid scene flow from each frame to the next (DESIGN.md
+section 5p), for which ``Deformable.snapshot`` keeps the shape a frame was scanned with while the next one is set.
 """
 import ctypes as C
 
@@ -85,6 +87,22 @@ class Deformable:
         out = np.empty((self.keyframes.shape[1], 3), np.float32)
         check(self._lib.lrc_deform_vertices(self._h, out.ctypes.data), "lrc_deform_vertices")
         return out
+
+    def snapshot(self, out_t=None, stream=0):
+        """Enqueue on ``stream`` a copy of the current vertices into ``out_t``, a (V, 3) float32 device tensor (None: a new one),
+        and return it (lrc_deform_snapshot_dev); no host synchronisation.  What the non-rigid flow keeps of a shape before the
+        next one is set."""
+        import torch
+        if not self._h:
+            raise ValueError("deformable is closed")
+        V = self.keyframes.shape[1]
+        if out_t is None:
+            out_t = torch.empty((V, 3), dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        if out_t.dtype != torch.float32 or not out_t.is_cuda or not out_t.is_contiguous() or out_t.numel() != 3 * V:
+            raise ValueError("out_t must be a contiguous (V, 3) float32 device tensor")
+        check(self._lib.lrc_deform_snapshot_dev(self._h, C.c_void_p(out_t.data_ptr()), C.c_void_p(int(stream))),
+              "lrc_deform_snapshot_dev")
+        return out_t
 
     def launches(self):
         """(kernel launches of one ``set`` that blends, of one that copies a keyframe)."""
@@ -236,6 +254,101 @@ def scan_deforming_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover_po
         part = _HitsSlice(hits, a * N, b * N)
         scene.scan_movers_dev(poses_t[a:b], dirs_t, part, max_range, movers, mp[a:b],
                               None if mover_t is None else mover_t[a * N:b * N], stream=stream)
+
+
+def _mover_index(movers, d):
+    """The place of deformable ``d`` among the movers of the set."""
+    return next(m for m, sc in enumerate(movers.scenes) if sc is d.scene)
+
+
+def scan_deforming_flow_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover_poses_t, shapes, flow_t, status_t=None,
+                            mover_t=None, stream=0):
+    """``scan_deforming_dev`` with non-rigid scene flow: frame k is paired with frame k + 1 -- the next
+    sensor pose ``poses_t[k + 1]``, the movers' poses ``mover_poses_t[k + 1]`` and the shapes ``shapes[k + 1]`` -- and everything
+    is enqueued on ``stream`` with no host wait.  Per frame: shape k is set unless it already stands, the frame is scanned, the
+    deformables whose shape changes are snapshot, shape k + 1 is set, and lrc_scan_nonrigid_flow_dev is called with one surface
+    pair per changed deformable (snapshot -> current vertices); so every shape is blended and refitted once.  ``hits`` must hold
+    t, point3 and prim; ``flow_t`` (P * N, 3) float32 and ``status_t`` (P * N) uint8 or None receive the two columns, the last
+    frame's +0 and 0 (it has no next).  ``mover_t`` (P * N) uint8 receives the mover column (None: a tensor of this call's)."""
+    import torch
+    P, N = poses_t.shape[0], dirs_t.shape[0]
+    if hits.n != P * N:
+        raise ValueError("hits must hold P * N records")
+    if "tile_count" in hits.want:
+        raise ValueError("tile_count is not written by this scan")
+    if not all(a in hits.want for a in ("t", "point3", "prim")):
+        raise ValueError("hits must hold t, point3 and prim")
+    if flow_t is None or flow_t.numel() != 3 * P * N:
+        raise ValueError("flow_t must be (P * N, 3)")
+    ds, s = _shapes(shapes, P, movers)
+    if len(ds) > 16:
+        raise ValueError("at most 16 deforming movers take part in a non-rigid flow")
+    M = len(movers)
+    mp = mover_poses_t.reshape(P, M, 12)
+    pt = poses_t.reshape(P, 16)
+    flow = flow_t.reshape(P * N, 3)
+    where = [_mover_index(movers, d) for d in ds]
+    # torch's own work (the mover column, the snapshots, the last frame's zeros) goes to the caller's stream as well
+    own = torch.cuda.ExternalStream(int(stream), device=poses_t.device) if int(stream) else torch.cuda.default_stream(poses_t.device)
+    with torch.cuda.stream(own):
+        if mover_t is None:
+            mover_t = torch.empty(P * N, dtype=torch.uint8, device=poses_t.device)
+        snaps = [None] * len(ds)
+        standing = [None] * len(ds)                # the shape each deformable's scene holds
+        for k in range(P):
+            for j, d in enumerate(ds):
+                if standing[j] is None or not np.array_equal(standing[j], s[k, j]):
+                    d.set(int(s[k, j, 0]), int(s[k, j, 1]), s[k, j, 2], stream=stream)
+                    standing[j] = s[k, j]
+            rows = slice(k * N, (k + 1) * N)
+            part = _HitsSlice(hits, k * N, (k + 1) * N)
+            scene.scan_movers_dev(pt[k:k + 1], dirs_t, part, max_range, movers, mp[k:k + 1], mover_t[rows], stream=stream)
+            if k + 1 == P:
+                flow[rows].zero_()
+                if status_t is not None:
+                    status_t[rows].zero_()
+                break
+            pairs = []
+            for j, d in enumerate(ds):
+                if not np.array_equal(s[k + 1, j], s[k, j]):
+                    snaps[j] = d.snapshot(snaps[j], stream=stream)
+                    d.set(int(s[k + 1, j, 0]), int(s[k + 1, j, 1]), s[k + 1, j, 2], stream=stream)
+                    standing[j] = s[k + 1, j]
+                    pairs.append((where[j], snaps[j], None))
+            scene.scan_nonrigid_flow_dev(part, mover_t[rows], 1, N, max_range, movers, mp[k:k + 1], mp[k + 1:k + 2], pt[k + 1:k + 2],
+                                         flow[rows], pairs=pairs, status_t=None if status_t is None else status_t[rows],
+                                         stream=stream)
+    return mover_t
+
+
+def scan_deforming_flow_frames(engine, intrinsics, poses, mesh, movers, mover_poses, shapes, want=("point3", "sem", "ins")):
+    """``scan_deforming_frames`` with non-rigid scene flow: the dict it returns plus ``flow`` (float32 x 3) and ``flow_status``
+    (uint8: 0 no next frame, 1 visible, 2 occluded, 3 out of range), one entry per kept row; frame k is paired with k + 1.  The
+    shared columns are ``scan_deforming_frames``' own; the two flow columns come from ``scan_deforming_flow_dev`` on the
+    engine's context, gathered for the kept rows by the frames' index column."""
+    import torch
+    engine._need_table(intrinsics, "scene flow needs a sensor with a pose-independent direction table")
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    P = len(poses)
+    ask = tuple(want) + (() if "index" in want else ("index",))
+    out = scan_deforming_frames(engine, intrinsics, poses, mesh, movers, mover_poses, shapes, want=ask)
+    from .core import DeviceHits
+    dirs = np.ascontiguousarray(engine._direction_table(intrinsics), dtype=np.float64)
+    N = len(dirs)
+    dev = f"cuda:{engine.ctx.device}"
+    hits = DeviceHits(P * N, dev, want=("t", "point3", "prim"))
+    flow_t = torch.empty((P * N, 3), dtype=torch.float32, device=dev)
+    status_t = torch.empty(P * N, dtype=torch.uint8, device=dev)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    scan_deforming_flow_dev(engine.scene_for(mesh), to(poses.reshape(P, 16)), to(dirs), hits, intrinsics.max_range, movers,
+                            to(np.ascontiguousarray(mover_poses, dtype=np.float32)), shapes, flow_t, status_t)
+    row = np.repeat(np.arange(P, dtype=np.int64) * N, out["counts"].astype(np.int64)) + out["index"].astype(np.int64)
+    row_t = torch.from_numpy(row).to(dev)
+    out["flow"] = flow_t[row_t].cpu().numpy()
+    out["flow_status"] = status_t[row_t].cpu().numpy()
+    if "index" not in want:
+        del out["index"]
+    return out
 
 
 class _HitsSlice:

@@ -5,6 +5,8 @@ For every return of a frame scanned with movers (``Scene.scan_movers_dev``): ``f
 lies on up to a next frame, ``status`` whether that place has a line of sight from the next sensor pose and lies in range.
 ``Scene.scan_flow_dev`` / ``Scene.scan_flow_compact`` compute both on the GPU; ``rays`` and ``status`` are the host steps of
 that, without a GPU (lrc_flow_rays, lrc_flow_status); ``sensor_flow`` turns the world flow into the moving sensor's coordinates.
+``Scene.scan_nonrigid_flow_dev`` and ``nonrigid_rays`` are the same for a set with deforming movers: rows on
+a deforming triangle flow with the triangle from one shape to the next; ``lidarcast.deform`` pairs the frames of an animation.
 """
 import numpy as np
 
@@ -60,6 +62,51 @@ def rays(t, point3, mover, mover_poses, next_mover_poses, next_poses, has_next, 
     check(lib.lrc_flow_rays(ptr(t), ptr(x), ptr(w), P, N, M, ptr(A), ptr(B), ptr(nxt), ptr(hn), float(max_range), float(min_range),
                             ptr(out["flow3"]), ptr(out["rays6"]), ptr(out["keep"]), ptr(out["thr"]), ptr(out["status"])),
           "lrc_flow_rays")
+    return out
+
+
+def nonrigid_rays(t, point3, mover, prim, mover_poses, next_mover_poses, next_poses, has_next, max_range, pairs, min_range=0.0):
+    """lrc_nonrigid_flow_rays: ``rays`` for a set with deforming movers (non-rigid scene flow); no GPU.
+    ``prim`` (P * N,) uint32 is the records' prim column; ``pairs`` a list of (mover m, verts_a (V, 3) float32, verts_b (V, 3)
+    float32, triangles (T, 3)): rows of mover m + 1 whose prim is below T flow with their triangle from shape a to shape b,
+    every other row takes the rigid step.  The dict of ``rays``."""
+    import ctypes as C
+    lib = _capi.load()
+    nxt = np.ascontiguousarray(next_poses, dtype=np.float64).reshape(-1, 16)
+    P = len(nxt)
+    t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
+    n = len(t)
+    if P == 0 or n % P:
+        raise ValueError("t must hold P * N entries")
+    N = n // P
+    x = np.ascontiguousarray(point3, dtype=np.float32).reshape(n, 3)
+    j = np.ascontiguousarray(prim, dtype=np.uint32).reshape(n)
+    M, w, A, B = 0, None, None, None
+    if mover_poses is not None:
+        A = np.ascontiguousarray(mover_poses, dtype=np.float32)
+        B = np.ascontiguousarray(next_mover_poses, dtype=np.float32)
+        if A.ndim != 3 or A.shape[0] != P or A.shape[2] != 12 or B.shape != A.shape:
+            raise ValueError("mover_poses and next_mover_poses must be (P, M, 12)")
+        M = A.shape[1]
+        w = np.ascontiguousarray(mover, dtype=np.uint8).reshape(n)
+    hn = None if has_next is None else np.ascontiguousarray(has_next, dtype=np.uint8).reshape(P)
+    pairs = list(pairs)
+    held = []               # the arrays behind the pointers, alive across the call
+    table = (_capi.LrcSurfacePairHost * max(len(pairs), 1))()
+    for k, (m, va, vb, tris) in enumerate(pairs):
+        va = np.ascontiguousarray(va, dtype=np.float32).reshape(-1, 3)
+        vb = np.ascontiguousarray(vb, dtype=np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(tris, dtype=np.uint32).reshape(-1, 3)
+        if va.shape != vb.shape:
+            raise ValueError(f"pair {k}: verts_a and verts_b must have the same shape")
+        held.append((va, vb, f))
+        table[k] = _capi.LrcSurfacePairHost(int(m), va.ctypes.data, vb.ctypes.data, f.ctypes.data, len(f), len(va))
+    out = {"flow3": np.empty((n, 3), np.float32), "rays6": np.empty((n, 6), np.float32), "keep": np.empty(n, np.uint8),
+           "thr": np.empty(n, np.float32), "status": np.empty(n, np.uint8)}
+    ptr = lambda a: None if a is None else a.ctypes.data
+    check(lib.lrc_nonrigid_flow_rays(ptr(t), ptr(x), ptr(w), ptr(j), P, N, M, ptr(A), ptr(B), ptr(nxt), ptr(hn), float(max_range),
+                                     float(min_range), C.cast(table, C.c_void_p), len(pairs), ptr(out["flow3"]), ptr(out["rays6"]),
+                                     ptr(out["keep"]), ptr(out["thr"]), ptr(out["status"])), "lrc_nonrigid_flow_rays")
     return out
 
 
@@ -127,6 +174,49 @@ def scan_flow_dev(scene, hits, mover_t, P, N, max_range, movers, mover_poses_t, 
                                        _dptr(flow_t), _dptr(status_t), _stream(stream)), "lrc_scan_flow_dev")
 
 
+def scan_nonrigid_flow_dev(scene, hits, mover_t, P, N, max_range, movers, mover_poses_t, next_mover_poses_t, next_poses_t, flow_t,
+                           pairs=(), status_t=None, has_next_t=None, stream=0):
+    """``scan_flow_dev`` for a set with deforming movers (lrc_scan_nonrigid_flow_dev): ``hits`` holds t,
+    point3 AND prim; ``pairs`` is a list of at most 16 (mover m, verts_a_t, verts_b_t) with (V, 3) float32 device tensors of
+    mover m's deformable -- the shape the records were scanned with (``Deformable.snapshot``) and the next shape, None for the
+    deformable's current vertices.  All P frames share the pairs.  The status is cast against the movers' scenes as they stand
+    on ``stream``: set the next shape before the call.  Without pairs this is ``scan_flow_dev``."""
+    import ctypes as C
+
+    import torch
+
+    from .core import _check_side_tensor, _dptr, _stream
+    if hits.n != P * N:
+        raise ValueError("hits must hold P * N records")
+    if flow_t is None:
+        raise ValueError("flow_t must be (P * N, 3)")
+    handle, entries = None, None
+    if movers is not None:
+        handle, entries = movers.handle(scene.ctx), P * len(movers) * 12
+        if mover_poses_t is None or next_mover_poses_t is None:
+            raise ValueError("mover_poses_t and next_mover_poses_t must be (P, M, 12)")
+    _check_side_tensor("mover_poses_t", mover_poses_t, torch.float32, entries, "be (P, M, 12)", flow_t)
+    _check_side_tensor("next_mover_poses_t", next_mover_poses_t, torch.float32, entries, "be (P, M, 12)", flow_t)
+    _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", flow_t)
+    _check_side_tensor("next_poses_t", next_poses_t, torch.float64, P * 16, "be (P, 16)", flow_t)
+    _check_side_tensor("has_next_t", has_next_t, torch.uint8, P, "hold P entries", flow_t)
+    _check_side_tensor("flow_t", flow_t, torch.float32, 3 * P * N, "be (P * N, 3)", flow_t)
+    _check_side_tensor("status_t", status_t, torch.uint8, P * N, "hold P * N entries", flow_t)
+    pairs = list(pairs)
+    table = (_capi.LrcSurfacePair * max(len(pairs), 1))()
+    for k, (m, va_t, vb_t) in enumerate(pairs):
+        V = None                # the size is checked where the mover is known to be a deformable's scene; the library refuses the rest
+        if movers is not None and 0 <= int(m) < len(movers) and any(d.scene is movers.scenes[int(m)] for d in movers.deformables):
+            V = 3 * movers.scenes[int(m)].num_vertices
+        _check_side_tensor(f"pairs[{k}] verts_a_t", va_t, torch.float32, V, "be (V, 3)", flow_t)
+        _check_side_tensor(f"pairs[{k}] verts_b_t", vb_t, torch.float32, V, "be (V, 3)", flow_t)
+        table[k] = _capi.LrcSurfacePair(int(m), _dptr(va_t), _dptr(vb_t))
+    check(scene._lib.lrc_scan_nonrigid_flow_dev(scene._h, handle, C.byref(hits.struct), _dptr(mover_t), P, N, _dptr(mover_poses_t),
+                                                _dptr(next_mover_poses_t), _dptr(next_poses_t), _dptr(has_next_t),
+                                                float(max_range), C.cast(table, C.c_void_p) if pairs else None, len(pairs),
+                                                _dptr(flow_t), _dptr(status_t), _stream(stream)), "lrc_scan_nonrigid_flow_dev")
+
+
 def scan_flow_compact(scene, poses, dirs, max_range, movers, mover_poses, next_poses, next_mover_poses, has_next=None,
                       want=("point3", "sem", "ins"), capacity=None, with_status=True):
     """``Scene.scan_movers_compact`` with scene flow (lrc_scan_flow_compact): per pose the sensor pose ``next_poses`` (P, 4, 4)
@@ -174,6 +264,7 @@ def scan_flow_frames(engine, intrinsics, poses, mesh, movers, mover_poses, want=
 def _bind():
     from .core import Scene
     Scene.scan_flow_dev = scan_flow_dev
+    Scene.scan_nonrigid_flow_dev = scan_nonrigid_flow_dev
     Scene.scan_flow_compact = scan_flow_compact
 
 

@@ -372,6 +372,9 @@ class S3DISSimulator:
         is at k * period) and ``objects``, each ``{mesh: pedestrian | <path to a mesh>, semantic: id or S3DIS class name,
         instance: id, path: [[t, x, y, z, yaw_deg], ...]}``, and optionally ``flow: true`` (scene flow: frames then carry the flow
         to the next frame and its status).  Returns {period, meshes, tracks, objects (JSON-ready), flow}.
+        ``nonrigid_flow: true`` is ``flow: true`` for a set with animated movers: their rows flow with
+        their triangle from the frame's shape to the next frame's, rigid movers take the rigid step; refused beside ``flow:
+        true``, under ``motion.movers`` and with more than 16 animated movers.
         The key stands alone: motion, noise, beam and materials are refused beside it.
         An object may carry ``animation: {cycle: <seconds>, phase: 0.0, loop: true}`` (a deforming mover):
         with ``mesh: walker`` the keyframes come from ``synth.make_walker``, with ``keyframes: <file.npy>`` a (K, V, 3) array serves
@@ -395,13 +398,21 @@ class S3DISSimulator:
             for other in ("motion", "noise", "beam", "materials"):
                 if self.config.get(other) is not None:
                     raise ValueError(f"the movers key cannot be combined with the {other} key")
-        unknown = set(cfg) - {"period", "objects", "flow"}
+        unknown = set(cfg) - {"period", "objects", "flow", "nonrigid_flow"}
         if unknown:
             raise ValueError(f"unknown entries under the {key} key: {sorted(unknown)}")
         if not isinstance(cfg.get("flow", False), bool):
             raise ValueError(f"{key}.flow must be true or false")
         if nested and cfg.get("flow", False):
             raise ValueError("motion.movers.flow is not available: scene flow under moving-sensor sweeps is not built")
+        nonrigid = cfg.get("nonrigid_flow", False)
+        if not isinstance(nonrigid, bool):
+            raise ValueError(f"{key}.nonrigid_flow must be true or false")
+        if nested and nonrigid:
+            raise ValueError("motion.movers.nonrigid_flow is not available: scene flow under moving-sensor sweeps is not built")
+        if nonrigid and cfg.get("flow", False):
+            raise ValueError(f"{key}.nonrigid_flow and {key}.flow exclude each other: nonrigid_flow gives the rigid movers of "
+                             "the set the rigid step")
         period = float(cfg.get("period", 0.1))
         if not (np.isfinite(period) and period > 0.0):
             raise ValueError(f"{key}.period must be a positive number of seconds")
@@ -451,8 +462,10 @@ class S3DISSimulator:
         if cfg.get("flow", False) and any(c is not None for c in clips):
             raise ValueError(f"{key}.flow is not available in a set with an animated mover: the flow of a rigid step is wrong "
                              "for a surface that changes shape (non-rigid flow is not built)")
+        if nonrigid and sum(c is not None for c in clips) > 16:
+            raise ValueError(f"{key}.nonrigid_flow takes at most 16 animated movers")
         return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed, "flow": bool(cfg.get("flow", False)),
-                "clips": clips, "keyframes": keyframes}
+                "nonrigid_flow": nonrigid, "clips": clips, "keyframes": keyframes}
 
     @staticmethod
     def _mover_animation(k, key, obj, mesh, nested):
@@ -600,11 +613,12 @@ class S3DISSimulator:
                                                            mm.triangle_ins)
                     mset = MoverSet(engine.ctx, [deformables.get(m, mm) for m, mm in enumerate(movers["meshes"])])
                     shapes = np.stack([movers["clips"][m].shapes3(times) for m in animated], axis=1)      # (P, D, 3)
-                    fr = deform.scan_deforming_frames(engine, self.lidar_config, poses_from_waypoints(waypoints), mesh, mset,
-                                                      mover_poses, shapes, want=want)
+                    scan = deform.scan_deforming_flow_frames if movers["nonrigid_flow"] else deform.scan_deforming_frames
+                    fr = scan(engine, self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, shapes,
+                              want=want)
                 else:
                     mset = MoverSet(engine.ctx, movers["meshes"])
-                    scan = engine.scan_flow_frames if movers["flow"] else engine.scan_mover_frames
+                    scan = engine.scan_flow_frames if movers["flow"] or movers["nonrigid_flow"] else engine.scan_mover_frames
                     fr = scan(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, want=want)
             finally:
                 if mset is not None:
