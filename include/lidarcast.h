@@ -909,6 +909,39 @@ int lrc_deform_blend(const float* a3, const float* b3, uint64_t num_vertices, fl
 int lrc_deform_refit(float* nodes16, uint64_t num_nodes, const uint32_t* slot_prim, uint64_t num_slots, const uint32_t* tris3,
                      uint64_t T, const float* verts3, uint64_t V, float* out_tri_rec12, float* out_slot_box6);
 
+/* ---- skinned deforming movers: bone poses skinned and refitted on the device (opt-in) ----------------
+ * A SKINNED deformable keeps no keyframes.  It keeps a REST shape (V, 3), up to four bone influences per vertex -- idx4 (V, 4)
+ * uint8 bone indices and wgt4 (V, 4) float32 weights; an unused influence carries weight +0 and any valid index -- and K KEY
+ * POSES of B bones, poses12 (K, B, 12) float32: a bone pose is the row-major 3 x 4 [A | c] of a mover pose, any affine map (no
+ * orthonormality is demanded).  Key pose k is "keyframe k": the vertices of key pose k are, per vertex at rest position
+ * (x, y, z), with all four influences always evaluated in index order and m = bones + 12 * idx[j],
+ *   p_j.i = ((m[4i] * x + m[4i+1] * y) + m[4i+2] * z) + m[4i+3]
+ *   v.i   = ((wgt0 * p_0.i + wgt1 * p_1.i) + wgt2 * p_2.i) + wgt3 * p_3.i
+ * (float32, one rounding per operation, nothing fused), and lrc_deform_set_dev(k0, k1, w) gives blend(skin(pose k0),
+ * skin(pose k1), w) by the blend above; for w == 0, w == 1 or k0 == k1 it is the skin of the one pose and nothing is blended.
+ * Those are the bytes a keyframe deformable made from the host-skinned keyframes (lrc_skin_apply per key pose) holds after the
+ * same call, so everything said above about the refit, the scans, the bounds and the refusing entry points holds as it stands.
+ * The handle IS an lrc_deform: lrc_deform_scene, lrc_deform_set_dev (one skinning launch in place of the blend or the copy),
+ * lrc_deform_vertices, lrc_deform_snapshot_dev, lrc_deform_launches (both counts are 1 + the refit's) and lrc_deform_destroy
+ * take it.  It keeps resident 12 + 4 + 16 = 32 bytes per vertex and 48 bytes per bone and key pose, counted in
+ * info.device_bytes, where the keyframe route keeps 12 bytes per vertex and keyframe.
+ *
+ * lrc_deform_create_skinned skins the K key poses on the host, one at a time, keeping none but key pose 0, from which the scene
+ * is built; the scene's fixed bounds are the union box of all key poses over the vertices triangles use.  Synchronous.
+ * LRC_ERR_INVALID_ARG before any launch, the message naming the offender: B outside 1 .. 255, K = 0, T = 0, a triangle index
+ * >= V, a bone index >= B, a weight that is not finite or is negative, a vertex whose weights (summed in float64) lie further
+ * than 2^-10 from 1, a pose entry that is not finite, a key pose that puts a vertex at a coordinate that is not finite or
+ * exceeds 1e6 (the key pose is named).  The arrays are checked before the context, so all of this is refused without a GPU.
+ *   lrc_skin_apply  host, no GPU, by the inline function the kernel calls: out3 (V, 3) = the vertices under ONE pose's
+ *                   bones12 (B, 12).  Refuses B outside 1 .. 255 and a bone index >= B; weights are taken as they are.
+ * Not built: a shape from a pose that is not in the clip (a set_pose_dev): the scene's bounds and the movers' cull sphere
+ * would need a bound on vertices the host has never seen. */
+int lrc_skin_apply(const float* rest3, uint64_t V, const uint8_t* idx4, const float* wgt4, const float* bones12, uint32_t B,
+                   float* out3);
+int lrc_deform_create_skinned(lrc_ctx* ctx, const float* rest3, uint64_t V, const uint8_t* idx4, const float* wgt4,
+                              const float* poses12, uint32_t K, uint32_t B, const uint32_t* tris3, uint64_t T,
+                              const uint16_t* tri_sem, const uint16_t* tri_ins, lrc_deform** out);
+
 /* ---- non-rigid scene flow: the flow of deforming movers (opt-in) -----------------------------------------
  * The scene flow above for a set with deformables: a row on a deforming triangle flows to where ITS point of the triangle is in
  * the next shape at the next pose, not to the rigid step.  A row has x = point3, w = mover, j = prim (a mover scan's prim is the

@@ -391,7 +391,9 @@ class S3DISSimScene:
         pose (x, y, z, yaw_deg and the row-major 3 x 4 object-to-world matrix), the oriented box (``box7``: world centre,
         extents of the mesh's own AABB, heading = yaw) and ``num_points``, the frame's returns from that mover.  An animated
         mover (``animation`` entry) also carries ``shape``: [k0, k1, w] of the frame, and its box is that of the frame's own
-        blended vertices.  Under the
+        blended vertices.  A skinned mover with a skeleton also carries ``joints``: its B joint positions at the frame's shape in
+        world coordinates -- the joints under key pose k0 and under k1 blended with w in float64 (j0 + w (j1 - j0)), then taken
+        out by the mover's pose.  Under the
         nested key ``motion: {movers: ...}`` (movers that move while a sweep is scanned) ``pose`` is the pose at the START of the
         frame's sweep, every mover additionally carries ``end_pose`` (x, y, z, yaw_deg at the END of the sweep) and ``record24``
         (the mover sweep record the scan used), and every frame ``sweep_duration`` in seconds.  Returns the dict."""
@@ -409,12 +411,23 @@ class S3DISSimScene:
             for m, obj in enumerate(objs):
                 x, y, z, yaw = (float(v) for v in tr["states"][f][m])
                 lo, hi = np.asarray(obj["box_min"], np.float64), np.asarray(obj["box_max"], np.float64)
-                shape = None
+                shape = joints = None
                 if m in tr.get("shapes", {}):       # an animated mover: the box of the frame's own blended vertices (host blend)
                     from lidarcast.deform import blend
                     shape = [float(v) for v in tr["shapes"][m][f]]
-                    keys = tr["keyframes"][m]
-                    verts = blend(keys[int(shape[0])], keys[int(shape[1])], shape[2]).astype(np.float64)
+                    rig = tr.get("skins", {}).get(m)
+                    if rig is not None:         # a skinned mover: its two key poses skinned on the host (lidarcast.skin.apply)
+                        from lidarcast import skin
+                        k0 = skin.apply(rig["rest"], rig["bone_index"], rig["bone_weight"], rig["poses12"][int(shape[0])])
+                        k1 = k0 if shape[1] == shape[0] else \
+                            skin.apply(rig["rest"], rig["bone_index"], rig["bone_weight"], rig["poses12"][int(shape[1])])
+                        if rig.get("skeleton") is not None:
+                            j0, j1 = (rig["skeleton"].joints(rig["poses12"][int(k)]) for k in shape[:2])
+                            m12 = np.asarray(tr["poses12"][f][m], np.float64).reshape(3, 4)
+                            joints = (j0 + shape[2] * (j1 - j0)) @ m12[:, :3].T + m12[:, 3]
+                    else:
+                        k0, k1 = tr["keyframes"][m][int(shape[0])], tr["keyframes"][m][int(shape[1])]
+                    verts = blend(k0, k1, shape[2]).astype(np.float64)
                     lo, hi = verts.min(0), verts.max(0)
                 c, s = np.cos(yaw), np.sin(yaw)
                 mid = 0.5 * (lo + hi)
@@ -426,6 +439,8 @@ class S3DISSimScene:
                                "num_points": int(counts[m + 1])})
                 if shape is not None:
                     movers[-1]["shape"] = [int(shape[0]), int(shape[1]), shape[2]]
+                if joints is not None:
+                    movers[-1]["joints"] = [[float(v) for v in j] for j in joints]
                 if "end_states" in tr:
                     ex, ey, ez, eyaw = (float(v) for v in tr["end_states"][f][m])
                     movers[-1]["end_pose"] = {"x": ex, "y": ey, "z": ez, "yaw_deg": float(np.degrees(eyaw))}

@@ -11,24 +11,15 @@
 //   k_tail    ONE workgroup finishes every height from `first` up, __syncthreads() between heights: the writer and the
 //             reader of a box sit on one CU, so no other workgroup's cache is involved.
 // The host functions lrc_deform_blend and lrc_deform_refit run the same inline functions on arrays, without a GPU.
+// A skinned deformable (lrc_skin.hip) is the same handle: its vertices come from k_skin instead of k_blend
+// or the keyframe copy, and creation (deform_build) and the refit launches (deform_refit_enqueue) are shared with it.
 #include <cmath>
 #include <cstring>
 
 #include "lrc_internal.h"
 #include "lrc_deform.h"
 
-struct lrc_deform {
-    lrc_ctx* ctx = nullptr;
-    lrc_scene* scene = nullptr;       // owned
-    uint32_t K = 0;
-    uint64_t V = 0, T = 0;
-    float* d_keys = nullptr;          // (K, V, 3)
-    float* d_verts = nullptr;         // (V, 3): the current shape
-    uint32_t* d_tris3 = nullptr;      // (T, 3)
-    uint32_t* d_order = nullptr;      // inner nodes grouped by height, height 0 first
-    std::vector<uint32_t> level_off;  // level_off[h] .. level_off[h + 1]: the nodes of height h in d_order
-    uint32_t tail_first = 0;          // heights >= tail_first are finished by k_tail (== number of heights: no tail)
-};
+// struct lrc_deform: lrc_internal.h (lrc_skin.hip makes skinned ones)
 
 namespace {
 
@@ -122,22 +113,80 @@ bool height_table(const float* nodes, uint64_t num_nodes, uint64_t num_slots, st
     return true;
 }
 
-bool coordinate_ok(float f) {        // the bit test of scene_create_host: finite and |f| <= 1e6
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    return (u & 0x7FFFFFFFu) <= 0x49742400u;
-}
-
 }  // namespace
 
 DeformMesh deform_mesh(const lrc_deform* d) { return DeformMesh{d->d_verts, d->d_tris3, d->V, d->T}; }
+
+int deform_build(lrc_deform* d, const char* who, const float* verts0_3, const uint32_t* tris3, const uint16_t* tri_sem,
+                 const uint16_t* tri_ins, const int lo[3], const int hi[3]) {
+    lrc_ctx* ctx = d->ctx;
+    const uint64_t V = d->V, T = d->T;
+    // float32 nodes whatever LRC_QNODES says: the quantisation grid is tied to bounds that a deformation moves
+    int rc = scene_create_mode(ctx, verts0_3, V, tris3, T, tri_sem, tri_ins, 0, &d->scene);
+    if (rc) return rc;
+    lrc_scene* s = d->scene;
+    s->deform = d;
+    for (int a = 0; a < 3; ++a) { s->info.bounds_lo[a] = lrctri::dec(lo[a]); s->info.bounds_hi[a] = lrctri::dec(hi[a]); }
+
+    // the height table, on the host from the exported nodes
+    std::vector<float> nodes(s->info.num_nodes * 16);
+    std::vector<uint32_t> order;
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return LRC_OK;
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP, std::string(who) + ": " + what + ": " + hipGetErrorString(e));
+    };
+    if ((rc = hip(hipMemcpy(nodes.data(), s->d_nodes, nodes.size() * 4, hipMemcpyDeviceToHost), "node read-back"))) return rc;
+    if (!height_table(nodes.data(), s->info.num_nodes, s->info.num_slots, order, d->level_off) || order.size() != s->info.num_nodes ||
+        d->level_off.size() > (size_t)lrc::kMaxDepth + 2)
+        return fail(LRC_ERR_INTERNAL, std::string(who) + ": the built tree has no height table");
+    const uint32_t heights = (uint32_t)d->level_off.size() - 1;
+    d->tail_first = heights;
+    if (env_int("LRC_DEFORM_TAIL", 1) != 0)        // 0: one launch per height to the top (the A/B of tools/deform_time.py)
+        for (uint32_t h = 0; h < heights; ++h)
+            if (d->level_off[h + 1] - d->level_off[h] <= kTailMax) { d->tail_first = h; break; }
+
+    const size_t vert_bytes = (size_t)V * 12, tri_bytes = (size_t)T * 12, ord_bytes = order.size() * 4;
+    if ((rc = hip(hipMalloc((void**)&d->d_verts, vert_bytes ? vert_bytes : 4), "vertices")) ||
+        (rc = hip(hipMalloc((void**)&d->d_tris3, tri_bytes), "triangles")) ||
+        (rc = hip(hipMalloc((void**)&d->d_order, ord_bytes ? ord_bytes : 4), "height table")) ||
+        (rc = hip(hipMemcpy(d->d_verts, verts0_3, vert_bytes, hipMemcpyHostToDevice), "vertex upload")) ||
+        (rc = hip(hipMemcpy(d->d_tris3, tris3, tri_bytes, hipMemcpyHostToDevice), "triangle upload")) ||
+        (rc = hip(hipMemcpy(d->d_order, order.data(), ord_bytes, hipMemcpyHostToDevice), "height table upload")))
+        return rc;
+    s->info.device_bytes += vert_bytes + tri_bytes + ord_bytes;
+    return LRC_OK;
+}
+
+int deform_refit_enqueue(lrc_deform* d, hipStream_t st) {
+    lrc_scene* s = d->scene;
+    const uint32_t S = (uint32_t)s->info.num_slots;
+    hipLaunchKernelGGL(k_slots, dim3((uint32_t)blocks_of(S, kDefBlock)), dim3(kDefBlock), 0, st, (const float*)d->d_verts,
+                       (const uint32_t*)d->d_tris3, (const uint32_t*)s->d_slot_prim, S, s->d_tris, s->d_slot_box);
+    const uint32_t heights = (uint32_t)d->level_off.size() - 1;
+    for (uint32_t h = 0; h < d->tail_first; ++h) {
+        const uint32_t n = d->level_off[h + 1] - d->level_off[h];
+        hipLaunchKernelGGL(k_level, dim3((uint32_t)blocks_of(n, kDefBlock)), dim3(kDefBlock), 0, st, (float*)s->d_nodes,
+                           (const float*)s->d_slot_box, (const uint32_t*)(d->d_order + d->level_off[h]), n);
+    }
+    if (d->tail_first < heights) {
+        TailArgs a{};
+        for (uint32_t h = 0; h <= heights; ++h) a.off[h] = d->level_off[h];
+        a.first = d->tail_first; a.heights = heights;
+        hipLaunchKernelGGL(k_tail, dim3(1), dim3(kDefBlock), 0, st, (float*)s->d_nodes, (const float*)s->d_slot_box,
+                           (const uint32_t*)d->d_order, a);
+    }
+    LRC_HIP(hipGetLastError());
+    return LRC_OK;
+}
 
 extern "C" {
 
 int lrc_deform_destroy(lrc_deform* d) {
     if (!d) return LRC_OK;
     if (d->ctx) (void)hipSetDevice(d->ctx->device);
-    for (void* p : {(void*)d->d_keys, (void*)d->d_verts, (void*)d->d_tris3, (void*)d->d_order})
+    for (void* p : {(void*)d->d_keys, (void*)d->d_verts, (void*)d->d_tris3, (void*)d->d_order, (void*)d->d_rest, (void*)d->d_idx4,
+                    (void*)d->d_wgt4, (void*)d->d_poses})
         if (p) (void)hipFree(p);
     if (d->scene) {
         d->scene->deform = nullptr;
@@ -159,69 +208,41 @@ int lrc_deform_create(lrc_ctx* ctx, const float* keyframes3, uint32_t K, uint64_
     for (uint64_t i = 0; i < 3 * T; ++i)
         if (tris3[i] >= V) return fail(LRC_ERR_INVALID_ARG, "lrc_deform_create: triangle index out of range");
     for (uint64_t i = 0; i < (uint64_t)K * V * 3; ++i)
-        if (!coordinate_ok(keyframes3[i]))
+        if (!deform_coordinate_ok(keyframes3[i]))
             return fail(LRC_ERR_INVALID_ARG, "lrc_deform_create: keyframe " + std::to_string(i / (V * 3)) +
                                                  " has a coordinate that is not finite or exceeds 1e6");
-    LRC_HIP(hipSetDevice(ctx->device));
-
-    lrc_deform* d = new (std::nothrow) lrc_deform();
-    if (!d) return fail(LRC_ERR_OOM, "lrc_deform_create: out of host memory");
-    d->ctx = ctx; d->K = K; d->V = V; d->T = T;
-    auto bail = [&](int rc) { const std::string keep = lrc_last_error(); lrc_deform_destroy(d); return fail(rc, keep); };
-
-    // float32 nodes whatever LRC_QNODES says: the quantisation grid is tied to bounds that a deformation moves
-    int rc = scene_create_mode(ctx, keyframes3, V, tris3, T, tri_sem, tri_ins, 0, &d->scene);
-    if (rc) return bail(rc);
-    lrc_scene* s = d->scene;
-    s->deform = d;
-
     // bounds: the union of every keyframe's box over the vertices triangles use, fixed for the deformable's life.  A blended
     // vertex lies in the box of its two keyframes (the clamp of blend1), so the movers' cull sphere made from these bounds at
     // every scan stays valid without a read-back.
+    int lo[3] = {0x7F7FFFFF, 0x7F7FFFFF, 0x7F7FFFFF}, hi[3] = {(int)0x80800000u, (int)0x80800000u, (int)0x80800000u};
     {
         std::vector<uint8_t> used(V, 0);
         for (uint64_t i = 0; i < 3 * T; ++i) used[tris3[i]] = 1;
-        int lo[3] = {0x7F7FFFFF, 0x7F7FFFFF, 0x7F7FFFFF}, hi[3] = {(int)0x80800000u, (int)0x80800000u, (int)0x80800000u};
         for (uint32_t k = 0; k < K; ++k)
             for (uint64_t v = 0; v < V; ++v) {
                 if (!used[v]) continue;
                 const float* p = keyframes3 + ((uint64_t)k * V + v) * 3;
                 for (int a = 0; a < 3; ++a) { lo[a] = lrctri::imin(lo[a], lrctri::enc(p[a])); hi[a] = lrctri::imax(hi[a], lrctri::enc(p[a])); }
             }
-        for (int a = 0; a < 3; ++a) { s->info.bounds_lo[a] = lrctri::dec(lo[a]); s->info.bounds_hi[a] = lrctri::dec(hi[a]); }
     }
+    LRC_HIP(hipSetDevice(ctx->device));
 
-    // the height table, on the host from the exported nodes
-    std::vector<float> nodes(s->info.num_nodes * 16);
-    std::vector<uint32_t> order;
+    lrc_deform* d = new (std::nothrow) lrc_deform();
+    if (!d) return fail(LRC_ERR_OOM, "lrc_deform_create: out of host memory");
+    d->ctx = ctx; d->K = K; d->V = V; d->T = T;
+    auto bail = [&](int rc) { const std::string keep = lrc_last_error(); lrc_deform_destroy(d); return fail(rc, keep); };
+    int rc = deform_build(d, "lrc_deform_create", keyframes3, tris3, tri_sem, tri_ins, lo, hi);
+    if (rc) return bail(rc);
     auto hip = [&](hipError_t e, const char* what) {
         if (e == hipSuccess) return LRC_OK;
         (void)hipGetLastError();
         return fail(e == hipErrorOutOfMemory ? LRC_ERR_OOM : LRC_ERR_HIP, std::string("lrc_deform_create: ") + what + ": " + hipGetErrorString(e));
     };
-    if ((rc = hip(hipMemcpy(nodes.data(), s->d_nodes, nodes.size() * 4, hipMemcpyDeviceToHost), "node read-back"))) return bail(rc);
-    if (!height_table(nodes.data(), s->info.num_nodes, s->info.num_slots, order, d->level_off) || order.size() != s->info.num_nodes ||
-        d->level_off.size() > (size_t)lrc::kMaxDepth + 2) {
-        fail(LRC_ERR_INTERNAL, "lrc_deform_create: the built tree has no height table");
-        return bail(LRC_ERR_INTERNAL);
-    }
-    const uint32_t heights = (uint32_t)d->level_off.size() - 1;
-    d->tail_first = heights;
-    if (env_int("LRC_DEFORM_TAIL", 1) != 0)        // 0: one launch per height to the top (the A/B of tools/deform_time.py)
-        for (uint32_t h = 0; h < heights; ++h)
-            if (d->level_off[h + 1] - d->level_off[h] <= kTailMax) { d->tail_first = h; break; }
-
-    const size_t key_bytes = (size_t)K * V * 12, vert_bytes = (size_t)V * 12, tri_bytes = (size_t)T * 12, ord_bytes = order.size() * 4;
+    const size_t key_bytes = (size_t)K * V * 12;
     if ((rc = hip(hipMalloc((void**)&d->d_keys, key_bytes ? key_bytes : 4), "keyframes")) ||
-        (rc = hip(hipMalloc((void**)&d->d_verts, vert_bytes ? vert_bytes : 4), "vertices")) ||
-        (rc = hip(hipMalloc((void**)&d->d_tris3, tri_bytes), "triangles")) ||
-        (rc = hip(hipMalloc((void**)&d->d_order, ord_bytes ? ord_bytes : 4), "height table")) ||
-        (rc = hip(hipMemcpy(d->d_keys, keyframes3, key_bytes, hipMemcpyHostToDevice), "keyframe upload")) ||
-        (rc = hip(hipMemcpy(d->d_verts, keyframes3, vert_bytes, hipMemcpyHostToDevice), "vertex upload")) ||
-        (rc = hip(hipMemcpy(d->d_tris3, tris3, tri_bytes, hipMemcpyHostToDevice), "triangle upload")) ||
-        (rc = hip(hipMemcpy(d->d_order, order.data(), ord_bytes, hipMemcpyHostToDevice), "height table upload")))
+        (rc = hip(hipMemcpy(d->d_keys, keyframes3, key_bytes, hipMemcpyHostToDevice), "keyframe upload")))
         return bail(rc);
-    s->info.device_bytes += key_bytes + vert_bytes + tri_bytes + ord_bytes;
+    d->scene->info.device_bytes += key_bytes;
     *out = d;
     return LRC_OK;
 }
@@ -233,7 +254,7 @@ int lrc_deform_launches(const lrc_deform* d, uint32_t* blended, uint32_t* copied
     const uint32_t heights = (uint32_t)d->level_off.size() - 1;
     const uint32_t refit = 1u + d->tail_first + (d->tail_first < heights ? 1u : 0u);
     if (blended) *blended = 1u + refit;
-    if (copied) *copied = refit;
+    if (copied) *copied = d->B ? 1u + refit : refit;     // a skinned deformable skins where a keyframe is copied
     return LRC_OK;
 }
 
@@ -243,9 +264,11 @@ int lrc_deform_set_dev(lrc_deform* d, uint32_t k0, uint32_t k1, float w, void* s
     if (!(w >= 0.0f && w <= 1.0f)) return fail(LRC_ERR_INVALID_ARG, "lrc_deform_set_dev: w must lie in [0, 1]");
     LRC_HIP(hipSetDevice(d->ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    lrc_scene* s = d->scene;
     const uint64_t n3 = d->V * 3;
-    if (n3) {
+    if (d->B) {                                            // a skinned deformable: k_skin writes the vertices (lrc_skin.hip)
+        const int rc = skin_enqueue(d, k0, k1, w, st);
+        if (rc) return rc;
+    } else if (n3) {
         if (w == 0.0f || w == 1.0f || k0 == k1) {          // the bits of one keyframe
             const uint32_t k = (w == 1.0f) ? k1 : k0;
             LRC_HIP(hipMemcpyAsync(d->d_verts, d->d_keys + (uint64_t)k * n3, n3 * 4, hipMemcpyDeviceToDevice, st));
@@ -254,24 +277,7 @@ int lrc_deform_set_dev(lrc_deform* d, uint32_t k0, uint32_t k1, float w, void* s
                                (const float*)(d->d_keys + (uint64_t)k0 * n3), (const float*)(d->d_keys + (uint64_t)k1 * n3), w, d->d_verts, n3);
         }
     }
-    const uint32_t S = (uint32_t)s->info.num_slots;
-    hipLaunchKernelGGL(k_slots, dim3((uint32_t)blocks_of(S, kDefBlock)), dim3(kDefBlock), 0, st, (const float*)d->d_verts,
-                       (const uint32_t*)d->d_tris3, (const uint32_t*)s->d_slot_prim, S, s->d_tris, s->d_slot_box);
-    const uint32_t heights = (uint32_t)d->level_off.size() - 1;
-    for (uint32_t h = 0; h < d->tail_first; ++h) {
-        const uint32_t n = d->level_off[h + 1] - d->level_off[h];
-        hipLaunchKernelGGL(k_level, dim3((uint32_t)blocks_of(n, kDefBlock)), dim3(kDefBlock), 0, st, (float*)s->d_nodes,
-                           (const float*)s->d_slot_box, (const uint32_t*)(d->d_order + d->level_off[h]), n);
-    }
-    if (d->tail_first < heights) {
-        TailArgs a{};
-        for (uint32_t h = 0; h <= heights; ++h) a.off[h] = d->level_off[h];
-        a.first = d->tail_first; a.heights = heights;
-        hipLaunchKernelGGL(k_tail, dim3(1), dim3(kDefBlock), 0, st, (float*)s->d_nodes, (const float*)s->d_slot_box,
-                           (const uint32_t*)d->d_order, a);
-    }
-    LRC_HIP(hipGetLastError());
-    return LRC_OK;
+    return deform_refit_enqueue(d, st);
 }
 
 int lrc_deform_vertices(lrc_deform* d, float* out_verts3) {

@@ -276,6 +276,41 @@ int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const ui
 // what a deformable keeps resident (lrc_deform.hip): its current vertices and its triangles
 struct DeformMesh { const float* d_verts3; const uint32_t* d_tris3; uint64_t V, T; };
 DeformMesh deform_mesh(const lrc_deform* d);
+
+// a deformable (lrc_deform_create: keyframes; lrc_deform_create_skinned: a rest shape, bone influences and K key poses).  Both
+// routes write d_verts and refit the scene from it; every other call on the handle does not know which route made it.
+struct lrc_deform {
+    lrc_ctx* ctx = nullptr;
+    lrc_scene* scene = nullptr;       // owned
+    uint32_t K = 0;
+    uint64_t V = 0, T = 0;
+    float* d_keys = nullptr;          // (K, V, 3); NULL for a skinned deformable
+    float* d_verts = nullptr;         // (V, 3): the current shape
+    uint32_t* d_tris3 = nullptr;      // (T, 3)
+    uint32_t* d_order = nullptr;      // inner nodes grouped by height, height 0 first
+    std::vector<uint32_t> level_off;  // level_off[h] .. level_off[h + 1]: the nodes of height h in d_order
+    uint32_t tail_first = 0;          // heights >= tail_first are finished by k_tail (== number of heights: no tail)
+    // skinned deformables (lrc_skin.hip); B == 0: the keyframe route
+    uint32_t B = 0;                   // bones per key pose
+    float* d_rest = nullptr;          // (V, 3) rest positions
+    uint32_t* d_idx4 = nullptr;       // (V) four uint8 bone indices, influence j in bits 8 j .. 8 j + 7
+    float4* d_wgt4 = nullptr;         // (V) four weights
+    float* d_poses = nullptr;         // (K, B, 12) bone poses
+};
+// lrc_deform.hip, for both routes.  deform_coordinate_ok: the bit test of scene_create_host, finite and |f| <= 1e6.
+// deform_build: what creation does after the route's own checks -- the scene from `verts0_3` (float32 nodes), the fixed bounds
+// (enc'ed lo / hi planes of the union box the caller has gathered), the height table, the vertex, triangle and height arrays;
+// on failure the caller destroys `d`.  deform_refit_enqueue: k_slots, k_level per height and k_tail on `st`, from d_verts.
+inline bool deform_coordinate_ok(float f) {
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    return (u & 0x7FFFFFFFu) <= 0x49742400u;
+}
+int deform_build(lrc_deform* d, const char* who, const float* verts0_3, const uint32_t* tris3, const uint16_t* tri_sem,
+                 const uint16_t* tri_ins, const int lo[3], const int hi[3]);
+int deform_refit_enqueue(lrc_deform* d, hipStream_t st);
+// lrc_skin.hip: the k_skin launch of lrc_deform_set_dev on a skinned deformable (arguments checked by the caller)
+int skin_enqueue(lrc_deform* d, uint32_t k0, uint32_t k1, float w, hipStream_t st);
 int flow_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
                       const float* mover_poses12, const FlowNext& next, double max_range, const lrc_frames* out, uint8_t* mover_rows,
                       float* flow_rows, uint8_t* status_rows, uint64_t capacity, uint64_t* out_total);

@@ -5,7 +5,8 @@ section 5o).
 ``set(k0, k1, w)`` enqueues the blend of two keyframes and the refit of the scene's triangle records, slot boxes and node
 boxes -- the tree is not rebuilt, and the refitted tree gives the hits of a fresh build bit for bit.  ``blend`` and ``refit``
 are the two host steps of that, without a GPU (lrc_deform_blend, lrc_deform_refit).  ``Clip`` turns times into the
-(k0, k1, w) of a cyclic or one-shot animation.  A ``lidarcast.movers.MoverSet`` takes a ``Deformable`` among its meshes;
+(k0, k1, w) of a cyclic or one-shot animation.  ``SkinnedDeformable`` is a ``Deformable`` whose shapes are bone poses skinned on
+the device instead of whole vertex arrays (DESIGN.md section 5q).  A ``lidarcast.movers.MoverSet`` takes a ``Deformable`` among its meshes;
 ``scan_deforming_frames`` / ``scan_deforming_dev`` scan frames whose movers change shape from frame to frame;
 ``scan_deforming_flow_frames`` / ``scan_deforming_flow_dev`` add the non-rigid scene flow from each frame to the next (DESIGN.md
 section 5p), for which ``Deformable.snapshot`` keeps the shape a frame was scanned with while the next one is set.
@@ -44,6 +45,19 @@ class Deformable:
         k = np.ascontiguousarray(np.asarray(keyframes), dtype=np.float32)
         if k.ndim != 3 or k.shape[2] != 3:
             raise ValueError("keyframes must be (K, V, 3)")
+        f, sem, ins = self._topology(triangles, triangle_sem, triangle_ins)
+        self.keyframes, self.triangles = k, f
+        self._V = k.shape[1]
+        h = C.c_void_p()
+        check(self._lib.lrc_deform_create(ctx._h, k.ctypes.data, k.shape[0], k.shape[1], f.ctypes.data, f.shape[0],
+                                          None if sem is None else sem.ctypes.data, None if ins is None else ins.ctypes.data,
+                                          C.byref(h)), "lrc_deform_create")
+        self._h = h
+        self.scene = _OwnedScene(ctx, self._lib.lrc_deform_scene(h), k.shape[1], f.shape[0])
+
+    @staticmethod
+    def _topology(triangles, triangle_sem, triangle_ins):
+        """(triangles (T, 3) uint32, labels (T,) uint16 or None) as the library takes them."""
         f = np.asarray(triangles)
         if f.size == 0:
             f = np.zeros((0, 3), dtype=np.uint32)
@@ -57,13 +71,7 @@ class Deformable:
         for lab in (sem, ins):
             if lab is not None and lab.shape != (f.shape[0],):
                 raise ValueError("per-triangle labels must have shape (T,)")
-        self.keyframes, self.triangles = k, f
-        h = C.c_void_p()
-        check(self._lib.lrc_deform_create(ctx._h, k.ctypes.data, k.shape[0], k.shape[1], f.ctypes.data, f.shape[0],
-                                          None if sem is None else sem.ctypes.data, None if ins is None else ins.ctypes.data,
-                                          C.byref(h)), "lrc_deform_create")
-        self._h = h
-        self.scene = _OwnedScene(ctx, self._lib.lrc_deform_scene(h), k.shape[1], f.shape[0])
+        return f, sem, ins
 
     def __len__(self):
         return len(self.triangles)
@@ -84,7 +92,7 @@ class Deformable:
 
     def vertices(self):
         """The current (V, 3) float32 vertices, read back synchronously."""
-        out = np.empty((self.keyframes.shape[1], 3), np.float32)
+        out = np.empty((self._V, 3), np.float32)
         check(self._lib.lrc_deform_vertices(self._h, out.ctypes.data), "lrc_deform_vertices")
         return out
 
@@ -95,7 +103,7 @@ class Deformable:
         import torch
         if not self._h:
             raise ValueError("deformable is closed")
-        V = self.keyframes.shape[1]
+        V = self._V
         if out_t is None:
             out_t = torch.empty((V, 3), dtype=torch.float32, device=f"cuda:{self.ctx.device}")
         if out_t.dtype != torch.float32 or not out_t.is_cuda or not out_t.is_contiguous() or out_t.numel() != 3 * V:
@@ -124,6 +132,44 @@ class Deformable:
             self.close()
         except Exception:
             pass
+
+
+class SkinnedDeformable(Deformable):
+    """A ``Deformable`` that keeps no keyframes: a rest shape ``rest`` (V, 3), up to four bone influences per vertex
+    (``bone_index`` (V, 4) uint8, ``bone_weight`` (V, 4) float32) and K key poses ``poses12`` (K, B, 12) float32, skinned on the
+    device at every ``set`` (lrc_deform_create_skinned).  Key pose k is keyframe k: ``set(k0, k1, w)``
+    gives the bytes a ``Deformable`` made from ``lidarcast.skin.keyframes(...)`` holds after the same call, so ``scene``,
+    ``set``, ``vertices``, ``snapshot``, ``launches`` and ``close`` are the base class's, and a ``MoverSet``, the
+    ``scan_deforming_*`` functions and the non-rigid flow take it as they take a ``Deformable``.  It has no ``keyframes``
+    array; ``keyframe(k)`` skins one on the host on demand."""
+
+    def __init__(self, ctx, rest, triangles, bone_index, bone_weight, poses12, triangle_sem=None, triangle_ins=None):
+        from . import skin
+        self._lib = _capi.load()
+        self.ctx = ctx
+        self._h = None
+        self.scene = None
+        r, i, w = skin.influences(rest, bone_index, bone_weight)
+        p = skin.clip_poses(poses12)
+        f, sem, ins = self._topology(triangles, triangle_sem, triangle_ins)
+        self.rest, self.bone_index, self.bone_weight, self.poses12, self.triangles = r, i, w, p, f
+        self._V = len(r)
+        h = C.c_void_p()
+        check(self._lib.lrc_deform_create_skinned(ctx._h, r.ctypes.data, len(r), i.ctypes.data, w.ctypes.data, p.ctypes.data,
+                                                  p.shape[0], p.shape[1], f.ctypes.data, f.shape[0],
+                                                  None if sem is None else sem.ctypes.data, None if ins is None else ins.ctypes.data,
+                                                  C.byref(h)), "lrc_deform_create_skinned")
+        self._h = h
+        self.scene = _OwnedScene(ctx, self._lib.lrc_deform_scene(h), len(r), f.shape[0])
+
+    @property
+    def num_keyframes(self):
+        return self.poses12.shape[0]
+
+    def keyframe(self, k):
+        """The (V, 3) float32 vertices of key pose ``k``, skinned on the host (``lidarcast.skin.apply``)."""
+        from . import skin
+        return skin.apply(self.rest, self.bone_index, self.bone_weight, self.poses12[int(k)])
 
 
 def blend(a, b, w):

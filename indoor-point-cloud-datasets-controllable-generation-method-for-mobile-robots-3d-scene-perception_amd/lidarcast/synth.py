@@ -250,6 +250,29 @@ def _prism(cx, cy, z0, z1, rx, ry, segments, rings):
     return v, np.array(t, dtype=np.int32)
 
 
+def _walker_rest(H):
+    """The walker at rest: (float64 vertices, int32 triangles, per vertex the pivot height, the swing sign and the part: 0 torso,
+    1 head, 2 left leg, 3 right leg, 4 left arm, 5 right arm), and nothing else; ``make_walker`` and ``make_walker_rig`` share it."""
+    seg = 8
+    # (centre x, y, z0, z1, radius x, y, rings, pivot height or None, swing sign)
+    parts = [(0.0, 0.0, 0.50 * H, 0.85 * H, 0.07 * H, 0.12 * H, 4, None, 0.0),            # torso
+             (0.0, 0.0, 0.87 * H, 1.00 * H, 0.06 * H, 0.06 * H, 2, None, 0.0),            # head
+             (0.0, 0.06 * H, 0.0, 0.50 * H, 0.045 * H, 0.045 * H, 3, 0.50 * H, 1.0),      # left leg
+             (0.0, -0.06 * H, 0.0, 0.50 * H, 0.045 * H, 0.045 * H, 3, 0.50 * H, -1.0),    # right leg
+             (0.0, 0.155 * H, 0.47 * H, 0.83 * H, 0.03 * H, 0.03 * H, 3, 0.83 * H, -1.0),  # left arm
+             (0.0, -0.155 * H, 0.47 * H, 0.83 * H, 0.03 * H, 0.03 * H, 3, 0.83 * H, 1.0)]  # right arm
+    verts, tris, pivot, sign, part, base = [], [], [], [], [], 0
+    for n, (cx, cy, z0, z1, rx, ry, rings, pz, sg) in enumerate(parts):
+        v, t = _prism(cx, cy, z0, z1, rx, ry, seg, rings)
+        verts.append(v)
+        tris.append(t + base)
+        pivot.append(np.full(len(v), z0 if pz is None else pz))
+        sign.append(np.full(len(v), sg))
+        part.append(np.full(len(v), n))
+        base += len(v)
+    return np.concatenate(verts, 0), np.concatenate(tris, 0), np.concatenate(pivot), np.concatenate(sign), np.concatenate(part)
+
+
 def make_walker(height=1.7, keyframes=8, swing_deg=25, semantic=13, instance=1):
     """A walking person for ``lidarcast.deform``: torso, head, two legs and two arms as closed eight-sided prisms (384
     triangles), facing +x, feet at z = 0, standing on its own origin.  Keyframe k of ``keyframes`` turns the legs about the hip
@@ -261,24 +284,7 @@ def make_walker(height=1.7, keyframes=8, swing_deg=25, semantic=13, instance=1):
     K, H = int(keyframes), float(height)
     if K < 1 or not H > 0.0:
         raise ValueError("a walker needs at least one keyframe and a positive height")
-    seg = 8
-    # (centre x, y, z0, z1, radius x, y, rings, pivot height or None, swing sign)
-    parts = [(0.0, 0.0, 0.50 * H, 0.85 * H, 0.07 * H, 0.12 * H, 4, None, 0.0),            # torso
-             (0.0, 0.0, 0.87 * H, 1.00 * H, 0.06 * H, 0.06 * H, 2, None, 0.0),            # head
-             (0.0, 0.06 * H, 0.0, 0.50 * H, 0.045 * H, 0.045 * H, 3, 0.50 * H, 1.0),      # left leg
-             (0.0, -0.06 * H, 0.0, 0.50 * H, 0.045 * H, 0.045 * H, 3, 0.50 * H, -1.0),    # right leg
-             (0.0, 0.155 * H, 0.47 * H, 0.83 * H, 0.03 * H, 0.03 * H, 3, 0.83 * H, -1.0),  # left arm
-             (0.0, -0.155 * H, 0.47 * H, 0.83 * H, 0.03 * H, 0.03 * H, 3, 0.83 * H, 1.0)]  # right arm
-    verts, tris, pivot, sign, base = [], [], [], [], 0
-    for cx, cy, z0, z1, rx, ry, rings, pz, sg in parts:
-        v, t = _prism(cx, cy, z0, z1, rx, ry, seg, rings)
-        verts.append(v)
-        tris.append(t + base)
-        pivot.append(np.full(len(v), z0 if pz is None else pz))
-        sign.append(np.full(len(v), sg))
-        base += len(v)
-    v0, t = np.concatenate(verts, 0), np.concatenate(tris, 0)
-    pivot, sign = np.concatenate(pivot), np.concatenate(sign)
+    v0, t, pivot, sign, _ = _walker_rest(H)
     keys = np.empty((K, len(v0), 3), np.float64)
     for k in range(K):
         a = sign * np.deg2rad(float(swing_deg)) * np.sin(2.0 * np.pi * k / K)
@@ -292,6 +298,52 @@ def make_walker(height=1.7, keyframes=8, swing_deg=25, semantic=13, instance=1):
     mesh = TriangleMesh(vertices=keys[0].astype(np.float64), triangles=t, triangle_sem=np.full(len(t), semantic, np.uint16),
                         triangle_ins=np.full(len(t), instance, np.uint16))
     mesh.keyframes = keys
+    return mesh
+
+
+def make_walker_rig(height=1.7, keyframes=8, swing_deg=25, smooth=0.0, semantic=13, instance=1):
+    """``make_walker`` as a skinned rig for ``lidarcast.deform.SkinnedDeformable``: the ``TriangleMesh`` of the walker at rest
+    (``make_walker``'s keyframe 0: no swing) carrying ``skeleton`` (a ``lidarcast.skin.Skeleton`` of six bones: torso, head, left
+    leg, right leg, left arm, right arm; the torso is the root, the limbs turn about the hip and shoulder pivots),
+    ``bone_index`` (V, 4) uint8, ``bone_weight`` (V, 4) float32 and ``poses12`` (K, 6, 12) float32.  Key pose k turns the limbs as
+    ``make_walker``'s keyframe k does and lowers the whole body by a root translation, as ``make_walker`` lowers its keyframe, so
+    that the lowest vertex stays on the floor.  With ``smooth`` = 0 every vertex has one influence of weight 1 and the skinned
+    key poses are ``make_walker``'s keyframes up to float32 rounding; with ``smooth`` > 0 a limb vertex closer than ``smooth``
+    metres to its limb's pivot shares its weight linearly with the torso (distance / smooth to the limb, the rest to the torso)."""
+    from .skin import Skeleton
+    K, H, smooth = int(keyframes), float(height), float(smooth)
+    if K < 1 or not H > 0.0:
+        raise ValueError("a walker needs at least one keyframe and a positive height")
+    if not smooth >= 0.0:
+        raise ValueError("smooth is a distance in metres, >= 0")
+    v0, t, pivot, sign, part = _walker_rest(H)
+    rest = v0.astype(np.float32)
+    joints = np.array([[0.0, 0.0, 0.50 * H], [0.0, 0.0, 0.87 * H], [0.0, 0.06 * H, 0.50 * H], [0.0, -0.06 * H, 0.50 * H],
+                       [0.0, 0.155 * H, 0.83 * H], [0.0, -0.155 * H, 0.83 * H]])
+    swing = np.array([0.0, 0.0, 1.0, -1.0, -1.0, 1.0])
+    skeleton = Skeleton([-1, 0, 0, 0, 0, 0], joints)
+    rot = np.zeros((K, 6, 3, 3))
+    drop = np.zeros((K, 3))
+    for k in range(K):
+        a = swing * np.deg2rad(float(swing_deg)) * np.sin(2.0 * np.pi * k / K)
+        c, s = np.cos(a), np.sin(a)
+        rot[k, :, 0, 0], rot[k, :, 0, 2], rot[k, :, 1, 1], rot[k, :, 2, 0], rot[k, :, 2, 2] = c, s, 1.0, -s, c
+        av = sign * np.deg2rad(float(swing_deg)) * np.sin(2.0 * np.pi * k / K)          # make_walker's own lowest vertex
+        drop[k, 2] = -(pivot - v0[:, 0] * np.sin(av) + (v0[:, 2] - pivot) * np.cos(av)).min()
+    index = np.zeros((len(rest), 4), np.uint8)
+    weight = np.zeros((len(rest), 4), np.float32)
+    index[:, 0] = part
+    weight[:, 0] = 1.0
+    if smooth > 0.0:
+        dist = np.linalg.norm(v0 - joints[part], axis=1)
+        near = (part >= 2) & (dist < smooth)
+        share = (dist[near] / smooth).astype(np.float32)
+        weight[near, 0] = share
+        weight[near, 1] = np.float32(1.0) - share          # index 0 in column 1: the torso
+    mesh = TriangleMesh(vertices=rest.astype(np.float64), triangles=t, triangle_sem=np.full(len(t), semantic, np.uint16),
+                        triangle_ins=np.full(len(t), instance, np.uint16))
+    mesh.skeleton, mesh.bone_index, mesh.bone_weight = skeleton, index, weight
+    mesh.poses12 = skeleton.matrices(rot, root_translation=drop)
     return mesh
 
 

@@ -381,6 +381,12 @@ class S3DISSimulator:
         the mesh file's own topology; frame k takes the shape of k * period.  The plan then also holds ``clips`` and ``keyframes``
         (one entry per object, None for a rigid one).  ``flow: true`` is refused in a set with an animated mover (the rigid flow
         step is wrong for it), and so is ``animation`` under ``motion.movers`` (no deformation within a sweep).
+        An animated object may be SKINNED instead: ``mesh: walker_rig`` takes ``synth.make_walker_rig``, and
+        ``skin: <file.npz>`` beside ``mesh: <file>`` takes the mesh file's vertices as the rest shape and, from the file,
+        ``bone_index`` (V, 4) uint8, ``bone_weight`` (V, 4) float32, ``poses`` (K, B, 12) float32 and optionally ``parents`` (B,) and
+        ``joints`` (B, 3), a skeleton whose joints then go to the tracks file.  The plan's ``skins`` holds one dict per such object
+        (None otherwise) and its ``keyframes`` entry is None: the key poses are skinned on the device.  ``skin`` beside
+        ``keyframes`` is refused, and so is ``skin`` without ``animation``.
         ``nested``: the same entries under ``motion: {movers: ...}``, movers that go on moving while a sweep is scanned (DESIGN.md
         section 5n): sweep k starts at k * period.  There ``flow: true`` is refused (no scene flow under sweeps), and so are
         ``motion.noise``, beam and materials beside it."""
@@ -423,9 +429,9 @@ class S3DISSimulator:
             raise ValueError(f"the {key} key takes at most 255 objects")
         from lidarcast import synth
         from lidarcast.movers import MoverTrack
-        meshes, tracks, listed, clips, keyframes = [], [], [], [], []
+        meshes, tracks, listed, clips, keyframes, skins = [], [], [], [], [], []
         for k, obj in enumerate(objects):
-            unknown = set(obj) - {"mesh", "semantic", "instance", "path", "animation", "keyframes"}
+            unknown = set(obj) - {"mesh", "semantic", "instance", "path", "animation", "keyframes", "skin"}
             if unknown:
                 raise ValueError(f"unknown entries of mover {k}: {sorted(unknown)}")
             if "path" not in obj:
@@ -443,18 +449,25 @@ class S3DISSimulator:
                 mesh = synth.make_pedestrian(semantic=sem, instance=ins)
             elif name == "walker":
                 mesh = synth.make_walker(semantic=sem, instance=ins)
+            elif name == "walker_rig":
+                mesh = synth.make_walker_rig(semantic=sem, instance=ins)
             else:
                 from lidarcast.ply import read_triangle_mesh
                 src = read_triangle_mesh(str(name))
                 f = np.asarray(src.triangles, np.int32)
                 mesh = synth.TriangleMesh(vertices=np.asarray(src.vertices, np.float64), triangles=f,
                                           triangle_sem=np.full(len(f), sem, np.uint16), triangle_ins=np.full(len(f), ins, np.uint16))
-            clip, keys = self._mover_animation(k, key, obj, mesh, nested)
+            clip, keys, rig = self._mover_animation(k, key, obj, mesh, nested)
             meshes.append(mesh)
             tracks.append(MoverTrack(obj["path"]))
             clips.append(clip)
             keyframes.append(keys)
+            skins.append(rig)
             box = np.asarray(mesh.vertices) if keys is None else keys.reshape(-1, 3)      # an animated mover: all its keyframes
+            if rig is not None:             # a skinned mover: all its key poses, skinned on the host one at a time
+                from lidarcast import skin
+                each = [skin.apply(rig["rest"], rig["bone_index"], rig["bone_weight"], p) for p in rig["poses12"]]
+                box = np.stack([np.min([v.min(0) for v in each], 0), np.max([v.max(0) for v in each], 0)])
             listed.append({"index": k, "mesh": str(name), "semantic": sem, "instance": ins, "num_triangles": len(mesh.triangles),
                            "box_min": [float(x) for x in box.min(0)], "box_max": [float(x) for x in box.max(0)]})
             if clip is not None:
@@ -465,22 +478,37 @@ class S3DISSimulator:
         if nonrigid and sum(c is not None for c in clips) > 16:
             raise ValueError(f"{key}.nonrigid_flow takes at most 16 animated movers")
         return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed, "flow": bool(cfg.get("flow", False)),
-                "nonrigid_flow": nonrigid, "clips": clips, "keyframes": keyframes}
+                "nonrigid_flow": nonrigid, "clips": clips, "keyframes": keyframes, "skins": skins}
 
     @staticmethod
     def _mover_animation(k, key, obj, mesh, nested):
-        """(Clip, (K, V, 3) float32 keyframes) of mover ``k``'s ``animation`` entry, (None, None) without one."""
+        """(Clip, (K, V, 3) float32 keyframes or None, skin dict or None) of mover ``k``'s ``animation`` entry, three times None
+        without one.  A skinned mover has no keyframes; its dict holds rest, bone_index, bone_weight, poses12 and skeleton
+        (a ``lidarcast.skin.Skeleton`` or None)."""
         anim = obj.get("animation")
         if anim is None:
             if obj.get("keyframes") is not None:
                 raise ValueError(f"mover {k}: keyframes need an animation entry")
-            return None, None
+            if obj.get("skin") is not None:
+                raise ValueError(f"mover {k}: skin needs an animation entry")
+            return None, None, None
         if nested:
             raise ValueError("animation is not available under motion.movers: deformation within a sweep is not built")
         if not isinstance(anim, dict) or set(anim) - {"cycle", "phase", "loop"} or "cycle" not in anim:
             raise ValueError(f"mover {k}: animation is {{cycle: <seconds>, phase: 0.0, loop: true}}")
         if not isinstance(anim.get("loop", True), bool):
             raise ValueError(f"mover {k}: animation.loop must be true or false")
+        if obj.get("skin") is not None and obj.get("keyframes") is not None:
+            raise ValueError(f"mover {k}: skin and keyframes exclude each other")
+        from lidarcast.deform import Clip
+        rig = None
+        if obj.get("skin") is not None:
+            rig = S3DISSimulator._skin_file(k, str(obj["skin"]), mesh)
+        elif getattr(mesh, "poses12", None) is not None:        # mesh: walker_rig
+            rig = {"rest": np.asarray(mesh.vertices, np.float32), "bone_index": mesh.bone_index, "bone_weight": mesh.bone_weight,
+                   "poses12": mesh.poses12, "skeleton": mesh.skeleton}
+        if rig is not None:
+            return Clip(len(rig["poses12"]), anim["cycle"], phase=float(anim.get("phase", 0.0)), loop=anim.get("loop", True)), None, rig
         if obj.get("keyframes") is not None:
             keys = np.load(str(obj["keyframes"]), allow_pickle=False)
             if keys.ndim != 3 or keys.shape[1:] != (len(mesh.vertices), 3) or keys.shape[0] < 1:
@@ -490,11 +518,38 @@ class S3DISSimulator:
         elif getattr(mesh, "keyframes", None) is not None:
             keys = mesh.keyframes
         else:
-            raise ValueError(f"mover {k}: an animation needs mesh: walker or a keyframes file")
+            raise ValueError(f"mover {k}: an animation needs mesh: walker or a keyframes file (or mesh: walker_rig or a skin file)")
         if not np.isfinite(keys).all():
             raise ValueError(f"mover {k}: keyframes must be finite")
-        from lidarcast.deform import Clip
-        return Clip(len(keys), anim["cycle"], phase=float(anim.get("phase", 0.0)), loop=anim.get("loop", True)), keys
+        return Clip(len(keys), anim["cycle"], phase=float(anim.get("phase", 0.0)), loop=anim.get("loop", True)), keys, None
+
+    @staticmethod
+    def _skin_file(k, path, mesh):
+        """The skin dict of mover ``k`` from ``skin: <file.npz>``; the rest shape is the mesh file's vertices."""
+        from lidarcast import skin
+        V = len(mesh.vertices)
+        with np.load(path, allow_pickle=False) as z:
+            missing = {"bone_index", "bone_weight", "poses"} - set(z.files)
+            if missing:
+                raise ValueError(f"mover {k}: the skin file lacks {sorted(missing)}")
+            index, weight, poses = z["bone_index"], z["bone_weight"], z["poses"]
+            parents = z["parents"] if "parents" in z.files else None
+            joints = z["joints"] if "joints" in z.files else None
+        if index.shape != (V, 4) or index.dtype != np.uint8 or weight.shape != (V, 4):
+            raise ValueError(f"mover {k}: skin needs bone_index (V, 4) uint8 and bone_weight (V, 4) with V = {V} vertices of its "
+                             f"mesh, got {index.shape} {index.dtype} and {weight.shape}")
+        if poses.ndim != 3 or poses.shape[0] < 1 or not 1 <= poses.shape[1] <= 255 or poses.shape[2] != 12:
+            raise ValueError(f"mover {k}: skin poses must be (K, B, 12) with 1 <= B <= 255, got {poses.shape}")
+        if (parents is None) != (joints is None):
+            raise ValueError(f"mover {k}: a skin file holds parents and joints together or neither")
+        skeleton = None
+        if parents is not None:
+            skeleton = skin.Skeleton(parents, joints)
+            if len(skeleton) != poses.shape[1]:
+                raise ValueError(f"mover {k}: the skin file's skeleton has {len(skeleton)} bones, its poses {poses.shape[1]}")
+        return {"rest": np.ascontiguousarray(mesh.vertices, dtype=np.float32), "bone_index": np.ascontiguousarray(index),
+                "bone_weight": np.ascontiguousarray(weight, dtype=np.float32),
+                "poses12": np.ascontiguousarray(poses, dtype=np.float32), "skeleton": skeleton}
 
     def run_simulation(self, waypoints: List[Waypoint], process_group=None) -> S3DISSimScene:
         """The scan stage (reference :220-296).  Inside an initialised ``torch.distributed`` job with more than one
@@ -609,6 +664,12 @@ class S3DISSimulator:
                     from lidarcast import deform
                     for m in animated:
                         mm = movers["meshes"][m]
+                        rig = movers["skins"][m]
+                        if rig is not None:         # bone poses skinned on the device
+                            deformables[m] = deform.SkinnedDeformable(engine.ctx, rig["rest"], mm.triangles, rig["bone_index"],
+                                                                      rig["bone_weight"], rig["poses12"], mm.triangle_sem,
+                                                                      mm.triangle_ins)
+                            continue
                         deformables[m] = deform.Deformable(engine.ctx, movers["keyframes"][m], mm.triangles, mm.triangle_sem,
                                                            mm.triangle_ins)
                     mset = MoverSet(engine.ctx, [deformables.get(m, mm) for m, mm in enumerate(movers["meshes"])])
@@ -630,7 +691,8 @@ class S3DISSimulator:
                                       "sensor_poses": poses_from_waypoints(waypoints)}
             if animated:
                 sim_scene.mover_tracks["shapes"] = {m: movers["clips"][m].shapes3(times) for m in animated}
-                sim_scene.mover_tracks["keyframes"] = {m: movers["keyframes"][m] for m in animated}
+                sim_scene.mover_tracks["keyframes"] = {m: movers["keyframes"][m] for m in animated if movers["skins"][m] is None}
+                sim_scene.mover_tracks["skins"] = {m: movers["skins"][m] for m in animated if movers["skins"][m] is not None}
         elif materials is not None:
             if dist is not None:
                 raise ValueError("the materials key is not available on a multi-rank process group")
