@@ -797,6 +797,45 @@ int lrc_mover_sweep_rays(const float* rays6, const double* fire, uint64_t num_ra
 int lrc_mover_sweep_normals(const float* normal3, const double* fire, uint64_t num_rays, const float* motion24,
                             float* out_normal3);
 
+/* ---- seeded sensor noise under movers (opt-in) ---------------------------------------------------------
+ * The moving objects and the seeded sensor noise, composed: a frame with people in it that has range noise, angle jitter and
+ * dropped returns, drawn in the kernels and reproducible bit for bit.  The noise cannot be added afterwards: the jitter decides
+ * which surface a ray meets, the room or a mover; a dropped ray is never cast; the range filter and min_range act on the noisy
+ * range.  float32 with one rounding per operation and nothing fused, except where the seeded sensor noise fuses (the quantile's
+ * one fmaf).  The noise of ray i of pose p is the Philox block of (seed, first_frame + p, i): the words w0..w3 of the seeded
+ * sensor noise.
+ *   1 dropout   dropout != 0 and w3 < thr: the ray is dropped.  It is cast against neither the room nor any mover; its record is a
+ *               miss and its mover byte is 0.
+ *   2 jitter    angle_std != 0: the table row is jittered in the sensor frame before the rotation into the world, as there.  (o, d)
+ *               is the ray of lrc_scan_noisy_dev, bit for bit.  That ray is taken into every mover's frame and culled: steps 1-3
+ *               of the moving objects, unchanged, on the jittered ray.
+ *   3 winner    decided on the CLEAN ranges: the smallest float32 t of t_s, t_0, ..., t_(M-1) wins; on an exact tie the static
+ *               scene, then the smaller m.  The range draw is one measurement error per ray: it does not reorder surfaces.
+ *   4 range     range_std != 0: t' = t_winner + float32(range_std) * z(w0), a float32 multiply, then an add; t' <= 0 is no
+ *               return.  The record is step 4 of the moving objects at t': the point, the range filter, min_range, incident_deg
+ *               (both modes) and intensity use t', the jittered d and the winner's written normal; prim, sem and ins are the
+ *               winner's; the mover byte is the winner's where the record is kept and 0 elsewhere.
+ *   5 zeros     a zero parameter skips its step (wave-uniform branches on kernel arguments).  The all-zero model gives the bytes
+ *               of lrc_scan_movers_dev; a NULL set gives the bytes of lrc_scan_noisy_dev and a zero mover column.
+ * The result does not depend on how the poses are split into calls when each call brings its own first_frame.
+ * LRC_ERR_INVALID_ARG before any launch, the offender named: what lrc_scan_noisy_dev refuses (a NULL model, a negative or
+ * non-finite standard deviation, dropout outside [0, 1), rays_per_pose >= 2^32, a range_noise option) and what lrc_scan_movers_*
+ * refuse (the static scene among the movers, a set or table of another context, d_out->tile_count != NULL and, in the compact
+ * call, a bad mover pose).  min_range and incident_mode of the STATIC scene apply, as there.
+ * Scratch: the set's, grown under the same rule: what lrc_scan_movers_dev holds there plus the world ray set and the live
+ * column, 123 bytes per ray whatever M is.
+ *   lrc_scan_noisy_movers_dev      device pointers, as lrc_scan_movers_dev takes them, and the model; enqueued on `stream`,
+ *                                  nothing is waited for
+ *   lrc_scan_noisy_movers_compact  lrc_scan_movers_compact with the model: pose p of the call is frame first_frame + p; frames
+ *                                  and mover_rows as there */
+int lrc_scan_noisy_movers_dev(lrc_scene* scene, lrc_movers* set /* nullable */, const double* d_poses16, uint64_t num_poses,
+                              const double* d_dirs3, uint64_t rays_per_pose, const float* d_mover_poses12, double max_range,
+                              const lrc_noise* noise, const lrc_hits* d_out, uint8_t* d_mover /* nullable */, void* stream);
+int lrc_scan_noisy_movers_compact(lrc_scene* scene, lrc_movers* set /* nullable */, const double* poses16, uint64_t num_poses,
+                                  const lrc_table* table, const float* mover_poses12, double max_range, const lrc_noise* noise,
+                                  const lrc_frames* out, uint8_t* mover_rows /* nullable */, uint64_t capacity,
+                                  uint64_t* out_total);
+
 /* ---- scene flow under movers: per-point flow and visibility at the next frame (opt-in) ----------------
  * For every return of a frame scanned with movers: where the surface the point lies on will be at a NEXT frame, and whether
  * that place can be seen from the next sensor pose (the occlusion mask of scene-flow benchmarks).  "Next" is given per frame,

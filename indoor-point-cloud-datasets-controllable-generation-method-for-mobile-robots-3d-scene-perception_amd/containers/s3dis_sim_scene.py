@@ -396,7 +396,10 @@ class S3DISSimScene:
         out by the mover's pose.  Under the
         nested key ``motion: {movers: ...}`` (movers that move while a sweep is scanned) ``pose`` is the pose at the START of the
         frame's sweep, every mover additionally carries ``end_pose`` (x, y, z, yaw_deg at the END of the sweep) and ``record24``
-        (the mover sweep record the scan used), and every frame ``sweep_duration`` in seconds.  Returns the dict."""
+        (the mover sweep record the scan used), and every frame ``sweep_duration`` in seconds.  Under ``movers: {noise: ...}``
+        (seeded sensor noise drawn in the mover kernels) the file additionally holds the noise model -- ``noise``: seed,
+        range_std, angle_std_deg, dropout and first_frame (frame f has frame id first_frame + f) -- and every frame ``returns``,
+        its kept noisy returns (static_points plus every mover's num_points).  Returns the dict."""
         tr = self.mover_tracks
         if tr is None:
             raise ValueError("this scene was not simulated under the movers key")
@@ -448,8 +451,15 @@ class S3DISSimScene:
             frames.append({"frame": f, "time": float(tr["times"][f]), "static_points": int(counts[0]), "movers": movers})
             if "end_states" in tr:
                 frames[-1]["sweep_duration"] = float(tr["sweep_duration"])
+            if tr.get("noise") is not None:
+                frames[-1]["returns"] = int(len(ids))
         summary = {"scene_name": self.scene_name, "period": float(tr["period"]), "num_frames": len(frames), "objects": objs,
                    "frames": frames}
+        if tr.get("noise") is not None:
+            nz = tr["noise"]
+            summary["noise"] = {"seed": int(nz.seed), "range_std": float(nz.range_std),
+                                "angle_std_deg": float(np.degrees(nz.angle_std)), "dropout": float(nz.dropout),
+                                "first_frame": int(nz.first_frame)}
         out = Path(output_dir)
         out.mkdir(parents=True, exist_ok=True)
         with open(out / f"{self.scene_name}_mover_tracks.json", "w") as fh:

@@ -231,6 +231,16 @@ int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, ui
                         const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
                         uint64_t* out_total);
 
+// seeded sensor noise under movers: the same split.  lrc_movers.hip checks the arguments of lrc_scan_noisy_movers_* and fills the
+// lrcnoise::Params (noise_params); lidarcast.hip holds the two noisy kernels and enqueues the passes (noisy_movers_scan_dev; set ==
+// NULL: the scan of lrc_scan_noisy_dev and a zero mover column) and scans to frames (noisy_movers_scan_compact).
+int noisy_movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
+                          const float* d_mover_poses12, double max_range, const lrcnoise::Params& np, const lrc_hits* d_out,
+                          uint8_t* d_mover, hipStream_t st);
+int noisy_movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                              const float* mover_poses12, double max_range, const lrcnoise::Params& noise, const lrc_frames* out,
+                              uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total);
+
 // the checks lrc_scan_movers_* and lrc_scan_flow_* share (lrc_movers.hip).  check_call: NULL scene or output, a set of another
 // context or one that holds the static scene, a range_noise option; `set` may be NULL.  check_poses12: `count` host mover poses,
 // every entry finite and max |R^T R - I| <= 2^-16 in float64.

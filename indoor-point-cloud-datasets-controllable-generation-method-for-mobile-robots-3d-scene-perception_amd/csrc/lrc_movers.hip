@@ -3,7 +3,8 @@
 // movers_scan_compact) and the two host functions lrc_mover_rays and lrc_mover_merge, which run the inline functions the
 // kernels call on arrays.  The same for the movers under moving-sensor sweeps: the checks of lrc_scan_mover_sweeps_dev /
 // lrc_scan_mover_sweeps_compact (mover_sweeps_scan_dev, mover_sweeps_scan_compact) and the host functions lrc_mover_sweep_rays and
-// lrc_mover_sweep_normals.
+// lrc_mover_sweep_normals.  And for the seeded sensor noise under movers: the checks of lrc_scan_noisy_movers_dev /
+// lrc_scan_noisy_movers_compact (noisy_movers_scan_dev, noisy_movers_scan_compact).
 #include <cmath>
 
 #include "lrc_internal.h"
@@ -226,6 +227,50 @@ int lrc_mover_sweep_normals(const float* normal3, const double* fire, uint64_t n
         out_normal3[i * 3] = w.x; out_normal3[i * 3 + 1] = w.y; out_normal3[i * 3 + 2] = w.z;
     }
     return LRC_OK;
+}
+
+// ---- seeded sensor noise under movers ----------------------------------------------------------------------------------------
+// Every refusal comes before the first device call: the mover calls' own (check_call, tile_count, NULL inputs, bad host poses),
+// then the model's (noise_params_host: the checks of lrc_scan_noisy_dev with no context).  noise_params then makes the
+// quantile table resident.
+
+int lrc_scan_noisy_movers_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
+                              const float* d_mover_poses12, double max_range, const lrc_noise* noise, const lrc_hits* d_out,
+                              uint8_t* d_mover, void* stream) {
+    const char* const who = "lrc_scan_noisy_movers_dev";
+    int rc = check_call(who, s, set, d_out);
+    if (rc) return rc;
+    if (d_out->tile_count)
+        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": tile_count is not written by this scan (lrc_compact_dev counts itself)");
+    if (P && N && (!d_poses16 || !d_dirs3)) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": poses16 or dirs3 is NULL");
+    if (P && N && set && !d_mover_poses12) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_poses12 is NULL");
+    lrcnoise::Params np{};
+    if ((rc = noise_params_host(who, noise, N, &np))) return rc;
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    if ((rc = noise_params(s->ctx, who, noise, N, &np))) return rc;
+    return noisy_movers_scan_dev(s, set, d_poses16, P, d_dirs3, N, d_mover_poses12, max_range, np, d_out, d_mover, (hipStream_t)stream);
+}
+
+int lrc_scan_noisy_movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
+                                  const float* mover_poses12, double max_range, const lrc_noise* noise, const lrc_frames* out,
+                                  uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total) {
+    const char* const who = "lrc_scan_noisy_movers_compact";
+    if (out_total) *out_total = 0;
+    int rc = check_call(who, s, set, out);
+    if (rc) return rc;
+    if (!table) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table is NULL");
+    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table and scene belong to different contexts");
+    lrcnoise::Params np{};
+    if ((rc = noise_params_host(who, noise, table->n, &np))) return rc;      // checked for an empty call too
+    if (!(P * table->n)) return LRC_OK;
+    if (!poses16 || !out->counts) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": poses16 or counts is NULL");
+    if (set) {
+        if (!mover_poses12) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_poses12 is NULL");
+        if ((rc = check_poses12(who, mover_poses12, P * set->scenes.size()))) return rc;
+    }
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    if ((rc = noise_params(s->ctx, who, noise, table->n, &np))) return rc;
+    return noisy_movers_scan_compact(s, set, poses16, P, table, mover_poses12, max_range, np, out, mover_rows, capacity, out_total);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ from .voxgrid import OccupancyGrid, OccupancyResult, scan_occupancy
 from .frameobj import FrameObjects, FrameObjectsResult, scan_frame_objects
 from .noise import NoiseModel
 from . import flow  # noqa: F401  (binds Scene.scan_flow_dev / Scene.scan_flow_compact)
+from . import movers  # noqa: F401  (binds Scene.scan_noisy_movers_dev / Scene.scan_noisy_movers_compact)
 
 __all__ = ["LIB_PATH", "LRC_INVALID_PRIM", "LidarcastError", "load", "ATTRS", "Context",
            "DeviceHits", "DirectionTable", "Scene", "motion_records", "ScanPipe", "PinnedPool", "FRAME_ATTRS", "NearestIndex", "OccupancyIndex", "bake_triangle_labels", "BOX_DTYPE", "instance_boxes", "instance_boxes_dev",

@@ -253,15 +253,24 @@ def _runs(s):
     return [(a, b) for a, b in zip(cut[:-1], cut[1:]) if b > a]
 
 
-def scan_deforming_frames(engine, intrinsics, poses, mesh, movers, mover_poses, shapes, want=("point3", "sem", "ins")):
+def scan_deforming_frames(engine, intrinsics, poses, mesh, movers, mover_poses, shapes, want=("point3", "sem", "ins"), noise=None):
     """``RaycastEngineHIP.scan_mover_frames`` with movers that change shape from frame to frame: ``shapes`` (P, D, 3) float64
     holds [k0, k1, w] per frame and per deformable of the set, in the set's order (``Clip.shapes3``).  Per run of consecutive
     frames with equal shapes every deformable is set once and the run is scanned by lrc_scan_movers_compact; a scan does not
     depend on how its poses are split into calls, so the runs stack to the dict ``scan_mover_frames``
-    returns for all frames."""
+    returns for all frames.  ``noise``: an optional ``lidarcast.noise.NoiseModel``: frame f is scanned
+    with the noise of frame ``noise.first_frame + f`` (a run that starts at frame a scans with ``noise.at_frame(noise.first_frame
+    + a)``), by ``scan_noisy_mover_frames``."""
     poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
     P = len(poses)
     ds, s = _shapes(shapes, P, movers)
+
+    def scan(a, b):
+        if noise is None:
+            return engine.scan_mover_frames(intrinsics, poses[a:b], mesh, movers, mp[a:b], want=want)
+        return engine.scan_noisy_mover_frames(intrinsics, poses[a:b], mesh, movers, mp[a:b],
+                                              noise.at_frame(noise.first_frame + a), want=want)
+
     mp = np.ascontiguousarray(mover_poses, dtype=np.float32)
     if mp.shape != (P, len(movers), 12):
         raise ValueError(f"mover_poses must be (P, M, 12) = ({P}, {len(movers)}, 12), got {mp.shape}")
@@ -270,9 +279,9 @@ def scan_deforming_frames(engine, intrinsics, poses, mesh, movers, mover_poses, 
         for j, d in enumerate(ds):
             d.set(int(s[a, j, 0]), int(s[a, j, 1]), s[a, j, 2])
         engine.ctx.synchronize()          # the frame path scans on the library's own streams
-        parts.append(engine.scan_mover_frames(intrinsics, poses[a:b], mesh, movers, mp[a:b], want=want))
+        parts.append(scan(a, b))
     if not parts:
-        return engine.scan_mover_frames(intrinsics, poses, mesh, movers, mp, want=want)
+        return scan(0, P)
     out = {}
     for key in parts[0]:
         if key == "total":
@@ -282,10 +291,12 @@ def scan_deforming_frames(engine, intrinsics, poses, mesh, movers, mover_poses, 
     return out
 
 
-def scan_deforming_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover_poses_t, shapes, mover_t=None, stream=0):
+def scan_deforming_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover_poses_t, shapes, mover_t=None, stream=0, noise=None):
     """``Scene.scan_movers_dev`` with movers that change shape from frame to frame, everything enqueued on ``stream`` with no
     host synchronisation: per run of consecutive frames with equal ``shapes`` (P, D, 3) one ``set`` per deformable, then
-    lrc_scan_movers_dev on the run's slice of the poses, the records and ``mover_t``."""
+    lrc_scan_movers_dev on the run's slice of the poses, the records and ``mover_t``.  ``noise``: an optional
+    ``lidarcast.noise.NoiseModel``: a run that starts at frame a is scanned by lrc_scan_noisy_movers_dev
+    with ``noise.at_frame(noise.first_frame + a)``, so frame f has the noise of frame ``noise.first_frame + f``."""
     P, N = poses_t.shape[0], dirs_t.shape[0]
     if hits.n != P * N:
         raise ValueError("hits must hold P * N records")
@@ -298,8 +309,12 @@ def scan_deforming_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover_po
         for j, d in enumerate(ds):
             d.set(int(s[a, j, 0]), int(s[a, j, 1]), s[a, j, 2], stream=stream)
         part = _HitsSlice(hits, a * N, b * N)
-        scene.scan_movers_dev(poses_t[a:b], dirs_t, part, max_range, movers, mp[a:b],
-                              None if mover_t is None else mover_t[a * N:b * N], stream=stream)
+        rows = None if mover_t is None else mover_t[a * N:b * N]
+        if noise is None:
+            scene.scan_movers_dev(poses_t[a:b], dirs_t, part, max_range, movers, mp[a:b], rows, stream=stream)
+        else:
+            scene.scan_noisy_movers_dev(poses_t[a:b], dirs_t, part, max_range, movers, mp[a:b],
+                                        noise.at_frame(noise.first_frame + a), rows, stream=stream)
 
 
 def _mover_index(movers, d):

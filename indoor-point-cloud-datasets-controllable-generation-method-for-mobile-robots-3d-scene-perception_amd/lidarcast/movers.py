@@ -9,6 +9,9 @@ Movers under moving-sensor sweeps are this module's own, 
 ``sweep_records`` makes the (P, M, 24) mover sweep records from tracks, ``sweep_rays`` / ``sweep_normals`` are the host steps,
 ``scan_mover_sweeps_dev``, ``scan_mover_sweeps_compact`` and ``scan_mover_sweep_frames`` the scans -- module functions that take
 the scene or the engine as their first argument.
+
+Seeded sensor noise under movers is at the end: ``scan_noisy_movers_dev``, ``scan_noisy_movers_compact``
+and ``scan_noisy_mover_frames``, module functions as well, bound as ``Scene`` and engine methods of the same names.
 """
 import ctypes as C
 
@@ -299,3 +302,71 @@ def scan_mover_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh, mo
     if "index" not in want:
         del fr["index"]
     return fr
+
+
+# ---- seeded sensor noise under movers (include/lidarcast.h "seeded sensor noise under movers") --------------
+# Module functions with the scene and the engine as arguments, as the scans above are; they are also bound below as
+# ``Scene.scan_noisy_movers_dev`` and ``Scene.scan_noisy_movers_compact``, and by ``raycast_engine`` as
+# ``RaycastEngineHIP.scan_noisy_mover_frames``.
+
+def scan_noisy_movers_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover_poses_t, noise, mover_t=None, stream=0):
+    """``Scene.scan_movers_dev`` with seeded sensor noise drawn in the mover kernels (lrc_scan_noisy_movers_dev): ``noise`` a
+    ``lidarcast.noise.NoiseModel`` (pose p of the call is frame ``noise.first_frame + p``); everything else as there.  The
+    all-zero model gives ``scan_movers_dev``'s bytes, ``movers=None`` those of ``Scene.scan_noisy_dev`` and a zero column."""
+    import torch
+    from .core import _check_side_tensor, _dptr, _stream
+    P, N = poses_t.shape[0], dirs_t.shape[0]
+    if hits.n != P * N:
+        raise ValueError("hits must hold P * N records")
+    handle, entries = None, None
+    if movers is not None:
+        handle, entries = movers.handle(scene.ctx), P * len(movers) * 12
+        if mover_poses_t is None:
+            raise ValueError("mover_poses_t must be (P, M, 12)")
+    _check_side_tensor("mover_poses_t", mover_poses_t, torch.float32, entries, "be (P, M, 12)", poses_t)
+    _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", poses_t)
+    nz = noise.struct()
+    check(scene._lib.lrc_scan_noisy_movers_dev(scene._h, handle, _dptr(poses_t), P, _dptr(dirs_t), N, _dptr(mover_poses_t),
+                                               float(max_range), C.byref(nz), C.byref(hits.struct), _dptr(mover_t),
+                                               _stream(stream)), "lrc_scan_noisy_movers_dev")
+
+
+def scan_noisy_movers_compact(scene, poses, dirs, max_range, movers, mover_poses, noise, want=("point3", "sem", "ins"),
+                              capacity=None):
+    """``Scene.scan_movers_compact`` with seeded sensor noise drawn in the mover kernels (lrc_scan_noisy_movers_compact):
+    ``noise`` a ``lidarcast.noise.NoiseModel`` (pose p of the call is frame ``noise.first_frame + p``).  The return value of
+    ``scan_movers_compact``: the frames plus ``mover``, one uint8 per kept row."""
+    from .core import _ptr, _table_for
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
+    lib, h, P, reach = scene._lib, scene._h, poses.shape[0], float(max_range)
+    with _table_for(scene.ctx, dirs) as table:
+        handle, mp = None, None
+        if movers is not None:
+            handle = movers.handle(scene.ctx)
+            mp = np.ascontiguousarray(mover_poses, dtype=np.float32)
+            if mp.shape != (P, len(movers), 12):
+                raise ValueError(f"mover_poses must be (P, M, 12) = ({P}, {len(movers)}, 12), got {mp.shape}")
+        nz = noise.struct()
+        return scene._scan_frames("lrc_scan_noisy_movers_compact", P, table.n, want, capacity, lambda fr, cap, total, rows:
+                                  lib.lrc_scan_noisy_movers_compact(h, handle, _ptr(poses), P, table._h, _ptr(mp), reach, C.byref(nz),
+                                                                    fr, rows, cap, total),
+                                  side=[("mover", np.uint8, ())])
+
+
+def scan_noisy_mover_frames(engine, intrinsics, poses, mesh, movers, mover_poses, noise, want=("point3", "sem", "ins")):
+    """``RaycastEngineHIP.scan_mover_frames`` with seeded sensor noise drawn in the mover kernels: ``noise`` a
+    ``lidarcast.noise.NoiseModel``; pose p is frame ``noise.first_frame + p``, so any subset of a run can be scanned again with
+    its exact noise (``noise.at_frame``).  The dict of ``scan_mover_frames``."""
+    engine._need_table(intrinsics, "seeded sensor noise under movers needs a sensor with a pose-independent direction table")
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    return scan_noisy_movers_compact(engine.scene_for(mesh), poses, engine._resident_table(intrinsics), intrinsics.max_range, movers,
+                                     mover_poses, noise, want=want)
+
+
+def _bind():
+    from .core import Scene
+    Scene.scan_noisy_movers_dev = scan_noisy_movers_dev
+    Scene.scan_noisy_movers_compact = scan_noisy_movers_compact
+
+
+_bind()

@@ -9,5 +9,8 @@ mesh_arrays = _hip.mesh_arrays
 # scene flow under movers lives in lidarcast.flow, the engine as its first argument; bound here as the engines' method
 from lidarcast.flow import scan_flow_frames as _scan_flow_frames  # noqa: E402
 RaycastEngineHIP.scan_flow_frames = _scan_flow_frames
+# ... and so does the seeded sensor noise under movers, in lidarcast.movers
+from lidarcast.movers import scan_noisy_mover_frames as _scan_noisy_mover_frames  # noqa: E402
+RaycastEngineHIP.scan_noisy_mover_frames = _scan_noisy_mover_frames
 
 __all__ = ["RaycastEngineBase", "RaycastEngineCPU", "RaycastEngineGPU", "RaycastEngineHIP", "mesh_arrays"]

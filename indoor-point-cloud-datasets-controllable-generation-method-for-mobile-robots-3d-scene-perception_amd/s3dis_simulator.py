@@ -312,15 +312,21 @@ class S3DISSimulator:
             json.dump(summary, fh, indent=2)
         return summary
 
-    def _noise_model(self, nested=False):
+    def _noise_model(self, nested=False, under_movers=False):
         """The NoiseModel of the config key ``noise`` (None without the key): ``seed`` is required; ``range_std`` (m),
         ``angle_std_deg`` and ``dropout`` default to the sensor record's range_noise_std, angle_noise_std (degrees) and
         dropout_probability.  first_frame = 0: frame p of a run has frame id p.  ``nested``: the same entries under
-        ``motion: {noise: ...}``, the seeded noise of moving-sensor sweeps."""
-        cfg = (self.config.get("motion") or {}).get("noise") if nested else self.config.get("noise")
-        key = "motion.noise" if nested else "noise"
+        ``motion: {noise: ...}``, the seeded noise of moving-sensor sweeps.  ``under_movers``: the same entries under
+        ``movers: {noise: ...}``, the seeded noise drawn in the mover kernels."""
+        if under_movers:
+            cfg, key = (self.config.get("movers") or {}).get("noise"), "movers.noise"
+        else:
+            cfg = (self.config.get("motion") or {}).get("noise") if nested else self.config.get("noise")
+            key = "motion.noise" if nested else "noise"
         if cfg is None:
             return None
+        if not isinstance(cfg, dict):
+            raise ValueError(f"the {key} key must be a mapping with a seed: {{seed, range_std?, angle_std_deg?, dropout?}}")
         if "seed" not in cfg:
             raise ValueError(f"the {key} key needs a seed")
         unknown = set(cfg) - {"seed", "range_std", "angle_std_deg", "dropout"}
@@ -389,7 +395,11 @@ class S3DISSimulator:
         ``keyframes`` is refused, and so is ``skin`` without ``animation``.
         ``nested``: the same entries under ``motion: {movers: ...}``, movers that go on moving while a sweep is scanned (DESIGN.md
         section 5n): sweep k starts at k * period.  There ``flow: true`` is refused (no scene flow under sweeps), and so are
-        ``motion.noise``, beam and materials beside it."""
+        ``motion.noise``, beam and materials beside it.
+        ``noise: {seed, range_std?, angle_std_deg?, dropout?}`` under the (top-level) movers key draws seeded sensor noise in the
+        mover kernels: the entries and defaults of the noise key, frame p has frame id p; the plan's
+        ``noise`` holds the NoiseModel (None without the entry).  ``flow: true`` and ``nonrigid_flow: true`` are refused beside it;
+        a top-level noise key beside movers stays refused, and so does ``motion.noise`` beside ``motion.movers``."""
         cfg = (self.config.get("motion") or {}).get("movers") if nested else self.config.get("movers")
         key = "motion.movers" if nested else "movers"
         if cfg is None:
@@ -404,9 +414,10 @@ class S3DISSimulator:
             for other in ("motion", "noise", "beam", "materials"):
                 if self.config.get(other) is not None:
                     raise ValueError(f"the movers key cannot be combined with the {other} key")
-        unknown = set(cfg) - {"period", "objects", "flow", "nonrigid_flow"}
+        unknown = set(cfg) - {"period", "objects", "flow", "nonrigid_flow"} - (set() if nested else {"noise"})
         if unknown:
             raise ValueError(f"unknown entries under the {key} key: {sorted(unknown)}")
+        noise = None if nested else self._noise_model(under_movers=True)
         if not isinstance(cfg.get("flow", False), bool):
             raise ValueError(f"{key}.flow must be true or false")
         if nested and cfg.get("flow", False):
@@ -419,6 +430,10 @@ class S3DISSimulator:
         if nonrigid and cfg.get("flow", False):
             raise ValueError(f"{key}.nonrigid_flow and {key}.flow exclude each other: nonrigid_flow gives the rigid movers of "
                              "the set the rigid step")
+        if noise is not None and (cfg.get("flow", False) or nonrigid):
+            raise ValueError(f"movers.{'nonrigid_flow' if nonrigid else 'flow'} is not available beside movers.noise: a noisy point "
+                             "sits off its surface by more than the status margin of 2^-12 max(L, 1), so its own surface would "
+                             "occlude it (scene flow under noise is not built)")
         period = float(cfg.get("period", 0.1))
         if not (np.isfinite(period) and period > 0.0):
             raise ValueError(f"{key}.period must be a positive number of seconds")
@@ -478,7 +493,7 @@ class S3DISSimulator:
         if nonrigid and sum(c is not None for c in clips) > 16:
             raise ValueError(f"{key}.nonrigid_flow takes at most 16 animated movers")
         return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed, "flow": bool(cfg.get("flow", False)),
-                "nonrigid_flow": nonrigid, "clips": clips, "keyframes": keyframes, "skins": skins}
+                "nonrigid_flow": nonrigid, "clips": clips, "keyframes": keyframes, "skins": skins, "noise": noise}
 
     @staticmethod
     def _mover_animation(k, key, obj, mesh, nested):
@@ -675,12 +690,17 @@ class S3DISSimulator:
                     mset = MoverSet(engine.ctx, [deformables.get(m, mm) for m, mm in enumerate(movers["meshes"])])
                     shapes = np.stack([movers["clips"][m].shapes3(times) for m in animated], axis=1)      # (P, D, 3)
                     scan = deform.scan_deforming_flow_frames if movers["nonrigid_flow"] else deform.scan_deforming_frames
+                    extra = {} if movers["noise"] is None else {"noise": movers["noise"]}      # (never beside nonrigid_flow)
                     fr = scan(engine, self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, shapes,
-                              want=want)
+                              want=want, **extra)
                 else:
                     mset = MoverSet(engine.ctx, movers["meshes"])
-                    scan = engine.scan_flow_frames if movers["flow"] or movers["nonrigid_flow"] else engine.scan_mover_frames
-                    fr = scan(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, want=want)
+                    if movers["noise"] is not None:      # seeded noise drawn in the mover kernels
+                        fr = engine.scan_noisy_mover_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset,
+                                                            mover_poses, movers["noise"], want=want)
+                    else:
+                        scan = engine.scan_flow_frames if movers["flow"] or movers["nonrigid_flow"] else engine.scan_mover_frames
+                        fr = scan(self.lidar_config, poses_from_waypoints(waypoints), mesh, mset, mover_poses, want=want)
             finally:
                 if mset is not None:
                     mset.close()
@@ -689,6 +709,8 @@ class S3DISSimulator:
             sim_scene.mover_tracks = {"period": movers["period"], "objects": movers["objects"], "times": times,
                                       "states": states, "poses12": mover_poses,
                                       "sensor_poses": poses_from_waypoints(waypoints)}
+            if movers["noise"] is not None:
+                sim_scene.mover_tracks["noise"] = movers["noise"]
             if animated:
                 sim_scene.mover_tracks["shapes"] = {m: movers["clips"][m].shapes3(times) for m in animated}
                 sim_scene.mover_tracks["keyframes"] = {m: movers["keyframes"][m] for m in animated if movers["skins"][m] is None}
