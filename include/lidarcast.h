@@ -1039,6 +1039,46 @@ int lrc_nonrigid_flow_rays(const float* t, const float* point3, const uint8_t* m
                            double max_range, double min_range, const lrc_surface_pair_host* pairs, uint32_t num_pairs,
                            float* out_flow3, float* out_rays6, uint8_t* out_keep, float* out_thr, uint8_t* out_status);
 
+/* ---- animated movers under sweeps: a per-ray shape traced on the device (opt-in) ------------------------
+ * Under lrc_scan_mover_sweeps_* a mover has a per-ray POSE; a deformable that was merely set keeps ONE shape for the whole
+ * sweep.  A SPANNED deformable has a per-ray SHAPE as well.  lrc_deform_span_dev gives it two end shapes, A = (k0a, k1a, wa)
+ * and B = (k0b, k1b, wb), each the vertices lrc_deform_set_dev of that triple gives (VA, VB; keyframe and skinned route alike),
+ * and ray i of a sweep, with s = (float)fire[i] -- the fraction the mover's pose is taken at -- meets the mover at the vertices
+ *   span_vertex(a, b, s) = a                    if s == 0 or a and b have the same bits
+ *                          b                    if s == 1
+ *                          blend(a, b, s)       otherwise: v = a + s * (b - a), clamped into [min(a, b), max(a, b)]
+ * per coordinate (float32, one rounding per operation, nothing fused; the blend of the deforming movers above, whose copy rule
+ * the three cases are).  The hit is the library's own, unchanged: with the 48-byte record and the vertex box the builders form
+ * from the ray's own three blended vertices, the Moeller-Trumbore conditions and the box clause against that box, the smallest
+ * t, and on an exact tie the smaller triangle row.  So a ray's t, prim, normal3, sem and ins are, bit for bit, what lrc_cast_dev
+ * returns for that ray on a fresh lrc_scene_create of span_vertex(VA, VB, s); the mover's pose per ray, the merge with the room
+ * and the other movers, the filter and the record are those of the movers under moving-sensor sweeps, untouched.  A shape that
+ * does not change (A == B), or a fire table of zeros, gives the bytes of the scan with the deformable set to A.
+ *
+ * lrc_deform_span_dev ENQUEUES on `stream`, with no host wait: shape A into the deformable's vertices and the slot refit of
+ * lrc_deform_set_dev for it (records and exact slot boxes are A's: every OTHER entry point that takes the scene returns shape
+ * A's bytes, only its node boxes are larger than need be); shape B into a second vertex array; per leaf slot the SPAN BOX, the
+ * min / max of the triangle's vertex boxes at A and at B, and the slot's six vertices gathered side by side; the node refit
+ * of lrc_deform_set_dev from the span boxes.  The tree is never rebuilt.  Every blended coordinate lies between its two ends
+ * exactly, so every blended triangle's box lies inside its slot's span box and no box test prunes a hit.  The call marks the
+ * deformable SPANNED; lrc_deform_set_dev clears the mark and restores the one-shape scan.  lrc_scan_mover_sweeps_dev / _compact
+ * trace a spanned deformable of the set per ray and everything else as before.  The extra arrays (12 bytes per vertex, 104
+ * bytes per leaf slot) are allocated by the first call, counted in info.device_bytes and freed by lrc_deform_destroy.
+ * LRC_ERR_INVALID_ARG before any launch: what lrc_deform_set_dev refuses, for either shape (the message names it).
+ *   lrc_deform_span_launches  kernel launches one lrc_deform_span_dev enqueues: with both shapes blended, and with both copied
+ * Host functions, no GPU, by the inline functions the kernels call:
+ *   lrc_span_vertices      out3 = span_vertex(a3, b3, s) per coordinate ((num_vertices, 3) float32 each); s in [0, 1]
+ *   lrc_deform_span_refit  nodes16: the topology (references; not written); out_nodes16 receives the nodes with every child box
+ *                          refitted to the span, out_span_box6 (num_slots, 6) the span boxes, out_span_rec18 (num_slots, 18;
+ *                          nullable) the slots' vertices, A's three then B's.  Refuses what lrc_deform_refit refuses. */
+int lrc_deform_span_dev(lrc_deform* deform, uint32_t k0a, uint32_t k1a, float wa, uint32_t k0b, uint32_t k1b, float wb,
+                        void* stream);
+int lrc_deform_span_launches(const lrc_deform* deform, uint32_t* blended, uint32_t* copied);
+int lrc_span_vertices(const float* a3, const float* b3, uint64_t num_vertices, float s, float* out3);
+int lrc_deform_span_refit(const float* nodes16, uint64_t num_nodes, const uint32_t* slot_prim, uint64_t num_slots,
+                          const uint32_t* tris3, uint64_t T, const float* verts_a3, const float* verts_b3, uint64_t V,
+                          float* out_nodes16, float* out_span_box6, float* out_span_rec18 /* nullable */);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

@@ -396,7 +396,9 @@ class S3DISSimScene:
         out by the mover's pose.  Under the
         nested key ``motion: {movers: ...}`` (movers that move while a sweep is scanned) ``pose`` is the pose at the START of the
         frame's sweep, every mover additionally carries ``end_pose`` (x, y, z, yaw_deg at the END of the sweep) and ``record24``
-        (the mover sweep record the scan used), and every frame ``sweep_duration`` in seconds.  Under ``movers: {noise: ...}``
+        (the mover sweep record the scan used), and every frame ``sweep_duration`` in seconds.  With ``per_ray_shape: true``
+        there an animated mover's ``shape`` is the shape at the START of the sweep and it additionally carries ``end_shape``,
+        [k0, k1, w] at its END, and a rig with a skeleton ``end_joints``, the joints at the end shape taken out by the end pose.  Under ``movers: {noise: ...}``
         (seeded sensor noise drawn in the mover kernels) the file additionally holds the noise model -- ``noise``: seed,
         range_std, angle_std_deg, dropout and first_frame (frame f has frame id first_frame + f) -- and every frame ``returns``,
         its kept noisy returns (static_points plus every mover's num_points).  Returns the dict."""
@@ -448,6 +450,16 @@ class S3DISSimScene:
                     ex, ey, ez, eyaw = (float(v) for v in tr["end_states"][f][m])
                     movers[-1]["end_pose"] = {"x": ex, "y": ey, "z": ez, "yaw_deg": float(np.degrees(eyaw))}
                     movers[-1]["record24"] = [float(v) for v in tr["records24"][f][m]]
+                if m in tr.get("end_shapes", {}):       # per-ray shape: the shape at the end of the sweep
+                    end = [float(v) for v in tr["end_shapes"][m][f]]
+                    movers[-1]["end_shape"] = [int(end[0]), int(end[1]), end[2]]
+                    rig = tr.get("skins", {}).get(m)
+                    if rig is not None and rig.get("skeleton") is not None:
+                        from lidarcast.movers import pose12
+                        j0, j1 = (rig["skeleton"].joints(rig["poses12"][int(k)]) for k in end[:2])
+                        e12 = pose12(tr["end_states"][f][m]).astype(np.float64).reshape(3, 4)
+                        ej = (j0 + end[2] * (j1 - j0)) @ e12[:, :3].T + e12[:, 3]
+                        movers[-1]["end_joints"] = [[float(v) for v in j] for j in ej]
             frames.append({"frame": f, "time": float(tr["times"][f]), "static_points": int(counts[0]), "movers": movers})
             if "end_states" in tr:
                 frames[-1]["sweep_duration"] = float(tr["sweep_duration"])

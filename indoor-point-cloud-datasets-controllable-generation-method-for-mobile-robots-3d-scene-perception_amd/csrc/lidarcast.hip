@@ -4595,7 +4595,9 @@ int noisy_movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16
 // movers_scan_dev under moving-sensor sweeps.  A NULL set: the launch of lrc_scan_sweeps_dev and a zero mover column.  Otherwise
 //   the static pass    mover_sweep_rays_kernel (gen_ray_sweep's world rays, stored) and the explicit-ray launch on the scene
 //   per mover m        mover_sweep_rays_kernel (the stored world ray in the frame the mover has at the ray's s + keep bytes), the
-//                      explicit-ray launch on the mover's scene, and mover_sweep_merge_kernel, whose last pass writes the records
+//                      explicit-ray launch on the mover's scene -- or, for the scene of a spanned deformable, the per-ray-shape
+//                      cast of lrc_span.hip (span_cast: the same five columns) --, and
+//                      mover_sweep_merge_kernel, whose last pass writes the records
 // in the set's scratch: what movers_scan_dev holds there plus the world ray set (24 bytes per ray), grown under the same rule.
 int mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
                           const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range, const lrc_hits* d_out,
@@ -4662,7 +4664,10 @@ int mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion2
         hipLaunchKernelGGL(mover_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, N, n, rp, uniform, world6,
                            rays6, keep);
         LRC_HIP(hipGetLastError());
-        if ((rc = cast_plain(ms, rays6, keep, n, mv, st))) return rc;
+        // a spanned deformable (lrc_deform_span_dev) is met per ray at the shape of the ray's own s (lrc_span.hip)
+        if ((rc = (ms->deform && ms->deform->spanned) ? span_cast(ms->deform, rays6, keep, d_fire, N, n, mv, st)
+                                                       : cast_plain(ms, rays6, keep, n, mv, st)))
+            return rc;
         MoverSweepMerge q{};
         q.motion24 = d_mover_motion24; q.world6 = world6; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
         q.w_t = w.t; q.w_prim = w.prim; q.w_n3 = w.normal3; q.w_sem = w.sem; q.w_ins = w.ins; q.w_who = who;

@@ -13,6 +13,9 @@
 // The host functions lrc_deform_blend and lrc_deform_refit run the same inline functions on arrays, without a GPU.
 // A skinned deformable (lrc_skin.hip) is the same handle: its vertices come from k_skin instead of k_blend
 // or the keyframe copy, and creation (deform_build) and the refit launches (deform_refit_enqueue) are shared with it.
+// A span between two shapes (lrc_span.hip) takes the same pieces apart: the shape of a triple into any
+// vertex array (deform_shape_enqueue), k_slots alone (deform_slots_enqueue), and k_level / k_tail from slot boxes of the
+// caller's choice (deform_nodes_enqueue).
 #include <cmath>
 #include <cstring>
 
@@ -158,26 +161,56 @@ int deform_build(lrc_deform* d, const char* who, const float* verts0_3, const ui
     return LRC_OK;
 }
 
-int deform_refit_enqueue(lrc_deform* d, hipStream_t st) {
+int deform_slots_enqueue(lrc_deform* d, hipStream_t st) {
     lrc_scene* s = d->scene;
     const uint32_t S = (uint32_t)s->info.num_slots;
     hipLaunchKernelGGL(k_slots, dim3((uint32_t)blocks_of(S, kDefBlock)), dim3(kDefBlock), 0, st, (const float*)d->d_verts,
                        (const uint32_t*)d->d_tris3, (const uint32_t*)s->d_slot_prim, S, s->d_tris, s->d_slot_box);
+    LRC_HIP(hipGetLastError());
+    return LRC_OK;
+}
+
+int deform_nodes_enqueue(lrc_deform* d, const float* d_slot_box, hipStream_t st) {
+    lrc_scene* s = d->scene;
     const uint32_t heights = (uint32_t)d->level_off.size() - 1;
     for (uint32_t h = 0; h < d->tail_first; ++h) {
         const uint32_t n = d->level_off[h + 1] - d->level_off[h];
         hipLaunchKernelGGL(k_level, dim3((uint32_t)blocks_of(n, kDefBlock)), dim3(kDefBlock), 0, st, (float*)s->d_nodes,
-                           (const float*)s->d_slot_box, (const uint32_t*)(d->d_order + d->level_off[h]), n);
+                           d_slot_box, (const uint32_t*)(d->d_order + d->level_off[h]), n);
     }
     if (d->tail_first < heights) {
         TailArgs a{};
         for (uint32_t h = 0; h <= heights; ++h) a.off[h] = d->level_off[h];
         a.first = d->tail_first; a.heights = heights;
-        hipLaunchKernelGGL(k_tail, dim3(1), dim3(kDefBlock), 0, st, (float*)s->d_nodes, (const float*)s->d_slot_box,
-                           (const uint32_t*)d->d_order, a);
+        hipLaunchKernelGGL(k_tail, dim3(1), dim3(kDefBlock), 0, st, (float*)s->d_nodes, d_slot_box, (const uint32_t*)d->d_order, a);
     }
     LRC_HIP(hipGetLastError());
     return LRC_OK;
+}
+
+int deform_refit_enqueue(lrc_deform* d, hipStream_t st) {
+    const int rc = deform_slots_enqueue(d, st);
+    return rc ? rc : deform_nodes_enqueue(d, d->scene->d_slot_box, st);
+}
+
+int deform_shape_enqueue(lrc_deform* d, uint32_t k0, uint32_t k1, float w, float* d_out, hipStream_t st) {
+    const uint64_t n3 = d->V * 3;
+    if (d->B) return skin_enqueue(d, k0, k1, w, d_out, st);     // a skinned deformable: k_skin writes the vertices (lrc_skin.hip)
+    if (!n3) return LRC_OK;
+    if (w == 0.0f || w == 1.0f || k0 == k1) {              // the bits of one keyframe
+        const uint32_t k = (w == 1.0f) ? k1 : k0;
+        LRC_HIP(hipMemcpyAsync(d_out, d->d_keys + (uint64_t)k * n3, n3 * 4, hipMemcpyDeviceToDevice, st));
+    } else {
+        hipLaunchKernelGGL(k_blend, dim3((uint32_t)blocks_of(n3, kDefBlock)), dim3(kDefBlock), 0, st,
+                           (const float*)(d->d_keys + (uint64_t)k0 * n3), (const float*)(d->d_keys + (uint64_t)k1 * n3), w, d_out, n3);
+        LRC_HIP(hipGetLastError());
+    }
+    return LRC_OK;
+}
+
+bool deform_height_table(const float* nodes, uint64_t num_nodes, uint64_t num_slots, std::vector<uint32_t>& order) {
+    std::vector<uint32_t> level_off;
+    return height_table(nodes, num_nodes, num_slots, order, level_off);
 }
 
 extern "C" {
@@ -186,7 +219,7 @@ int lrc_deform_destroy(lrc_deform* d) {
     if (!d) return LRC_OK;
     if (d->ctx) (void)hipSetDevice(d->ctx->device);
     for (void* p : {(void*)d->d_keys, (void*)d->d_verts, (void*)d->d_tris3, (void*)d->d_order, (void*)d->d_rest, (void*)d->d_idx4,
-                    (void*)d->d_wgt4, (void*)d->d_poses})
+                    (void*)d->d_wgt4, (void*)d->d_poses, (void*)d->d_verts_b, (void*)d->d_span_box, (void*)d->d_span_rec})
         if (p) (void)hipFree(p);
     if (d->scene) {
         d->scene->deform = nullptr;
@@ -264,19 +297,9 @@ int lrc_deform_set_dev(lrc_deform* d, uint32_t k0, uint32_t k1, float w, void* s
     if (!(w >= 0.0f && w <= 1.0f)) return fail(LRC_ERR_INVALID_ARG, "lrc_deform_set_dev: w must lie in [0, 1]");
     LRC_HIP(hipSetDevice(d->ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t n3 = d->V * 3;
-    if (d->B) {                                            // a skinned deformable: k_skin writes the vertices (lrc_skin.hip)
-        const int rc = skin_enqueue(d, k0, k1, w, st);
-        if (rc) return rc;
-    } else if (n3) {
-        if (w == 0.0f || w == 1.0f || k0 == k1) {          // the bits of one keyframe
-            const uint32_t k = (w == 1.0f) ? k1 : k0;
-            LRC_HIP(hipMemcpyAsync(d->d_verts, d->d_keys + (uint64_t)k * n3, n3 * 4, hipMemcpyDeviceToDevice, st));
-        } else {
-            hipLaunchKernelGGL(k_blend, dim3((uint32_t)blocks_of(n3, kDefBlock)), dim3(kDefBlock), 0, st,
-                               (const float*)(d->d_keys + (uint64_t)k0 * n3), (const float*)(d->d_keys + (uint64_t)k1 * n3), w, d->d_verts, n3);
-        }
-    }
+    const int rc = deform_shape_enqueue(d, k0, k1, w, d->d_verts, st);
+    if (rc) return rc;
+    d->spanned = false;
     return deform_refit_enqueue(d, st);
 }
 

@@ -306,11 +306,20 @@ struct lrc_deform {
     uint32_t* d_idx4 = nullptr;       // (V) four uint8 bone indices, influence j in bits 8 j .. 8 j + 7
     float4* d_wgt4 = nullptr;         // (V) four weights
     float* d_poses = nullptr;         // (K, B, 12) bone poses
+    // animated movers under sweeps (lrc_span.hip); allocated by the first lrc_deform_span_dev
+    bool spanned = false;             // the node boxes hold both shapes of a span: set by lrc_deform_span_dev, cleared by lrc_deform_set_dev
+    float* d_verts_b = nullptr;       // (V, 3): shape B of the span (d_verts holds shape A)
+    float* d_span_box = nullptr;      // per leaf slot the span box (lo xyz, hi xyz)
+    float* d_span_rec = nullptr;      // per leaf slot lrcspan::kRecFloats floats: v0, v1, v2 of A, then of B, two of padding
 };
 // lrc_deform.hip, for both routes.  deform_coordinate_ok: the bit test of scene_create_host, finite and |f| <= 1e6.
 // deform_build: what creation does after the route's own checks -- the scene from `verts0_3` (float32 nodes), the fixed bounds
 // (enc'ed lo / hi planes of the union box the caller has gathered), the height table, the vertex, triangle and height arrays;
-// on failure the caller destroys `d`.  deform_refit_enqueue: k_slots, k_level per height and k_tail on `st`, from d_verts.
+// on failure the caller destroys `d`.  deform_refit_enqueue: k_slots, k_level per height and k_tail on `st`, from d_verts; its two
+// halves are deform_slots_enqueue (k_slots) and deform_nodes_enqueue (k_level / k_tail from `slot_box`: the scene's exact slot
+// boxes, or the span boxes of lrc_span.hip).  deform_shape_enqueue: the vertices of shape (k0, k1, w) into `out` (V, 3) by the
+// handle's route -- keyframe copy, k_blend or k_skin -- arguments checked by the caller.  deform_height_table: the inner nodes of
+// `nodes` grouped by height, height 0 first (false: no tree over the slots), for the host refits.
 inline bool deform_coordinate_ok(float f) {
     uint32_t u;
     __builtin_memcpy(&u, &f, 4);
@@ -319,8 +328,16 @@ inline bool deform_coordinate_ok(float f) {
 int deform_build(lrc_deform* d, const char* who, const float* verts0_3, const uint32_t* tris3, const uint16_t* tri_sem,
                  const uint16_t* tri_ins, const int lo[3], const int hi[3]);
 int deform_refit_enqueue(lrc_deform* d, hipStream_t st);
-// lrc_skin.hip: the k_skin launch of lrc_deform_set_dev on a skinned deformable (arguments checked by the caller)
-int skin_enqueue(lrc_deform* d, uint32_t k0, uint32_t k1, float w, hipStream_t st);
+int deform_slots_enqueue(lrc_deform* d, hipStream_t st);
+int deform_nodes_enqueue(lrc_deform* d, const float* d_slot_box, hipStream_t st);
+int deform_shape_enqueue(lrc_deform* d, uint32_t k0, uint32_t k1, float w, float* d_out, hipStream_t st);
+bool deform_height_table(const float* nodes, uint64_t num_nodes, uint64_t num_slots, std::vector<uint32_t>& order);
+// lrc_span.hip: the per-ray-shape cast of a spanned deformable's scene in the place of cast_plain (lidarcast.hip,
+// mover_sweeps_scan_dev): ray g of `n` has the firing fraction d_fire[g % rays_per_pose]; the five columns of `out` the merge reads
+int span_cast(lrc_deform* d, const float* d_rays6, const uint8_t* d_keep, const double* d_fire, uint64_t rays_per_pose, uint64_t n,
+              const lrc_hits& out, hipStream_t st);
+// lrc_skin.hip: the k_skin launch of deform_shape_enqueue on a skinned deformable, into `d_out` (V, 3)
+int skin_enqueue(lrc_deform* d, uint32_t k0, uint32_t k1, float w, float* d_out, hipStream_t st);
 int flow_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
                       const float* mover_poses12, const FlowNext& next, double max_range, const lrc_frames* out, uint8_t* mover_rows,
                       float* flow_rows, uint8_t* status_rows, uint64_t capacity, uint64_t* out_total);

@@ -51,18 +51,18 @@ __global__ __launch_bounds__(kSkinBlock) void k_skin(const float* rest3, const u
 
 }  // namespace
 
-int skin_enqueue(lrc_deform* d, uint32_t k0, uint32_t k1, float w, hipStream_t st) {
+int skin_enqueue(lrc_deform* d, uint32_t k0, uint32_t k1, float w, float* d_out, hipStream_t st) {
     if (!d->V) return LRC_OK;
     const uint32_t n12 = 12u * d->B;
     const dim3 grid((uint32_t)blocks_of(d->V, kSkinBlock)), block(kSkinBlock);
     if (w == 0.0f || w == 1.0f || k0 == k1) {              // one key pose: skinned, nothing blended
         const float* bones = d->d_poses + (uint64_t)((w == 1.0f) ? k1 : k0) * n12;
         hipLaunchKernelGGL(k_skin<false>, grid, block, n12 * sizeof(float), st, (const float*)d->d_rest, (const uint32_t*)d->d_idx4,
-                           (const float4*)d->d_wgt4, bones, bones, n12, w, d->d_verts, d->V);
+                           (const float4*)d->d_wgt4, bones, bones, n12, w, d_out, d->V);
     } else {
         hipLaunchKernelGGL(k_skin<true>, grid, block, 2 * n12 * sizeof(float), st, (const float*)d->d_rest, (const uint32_t*)d->d_idx4,
                            (const float4*)d->d_wgt4, (const float*)(d->d_poses + (uint64_t)k0 * n12),
-                           (const float*)(d->d_poses + (uint64_t)k1 * n12), n12, w, d->d_verts, d->V);
+                           (const float*)(d->d_poses + (uint64_t)k1 * n12), n12, w, d_out, d->V);
     }
     LRC_HIP(hipGetLastError());
     return LRC_OK;

@@ -49,6 +49,7 @@ SYMBOLS = (
     "lrc_deform_launches", "lrc_deform_blend", "lrc_deform_refit",
     "lrc_deform_snapshot_dev", "lrc_scan_nonrigid_flow_dev", "lrc_nonrigid_flow_rays",
     "lrc_skin_apply", "lrc_deform_create_skinned",
+    "lrc_deform_span_dev", "lrc_deform_span_launches", "lrc_span_vertices", "lrc_deform_span_refit",
     "lrc_compact", "lrc_compact_dev", "lrc_cloud_from_ranges_dev", "lrc_cloud_from_prims_dev",
     "lrc_cloud_from_prims_own_dev", "lrc_cloud_range_stats_dev",
     "lrc_nn_create", "lrc_nn_destroy", "lrc_nn_query", "lrc_nn_query_dev",
@@ -330,6 +331,10 @@ def load():
         "lrc_deform_blend": [vp, vp, u64, C.c_float, vp],
         "lrc_deform_refit": [vp, u64, vp, u64, vp, u64, vp, u64, vp, vp],
         "lrc_deform_snapshot_dev": [vp, vp, vp],
+        "lrc_deform_span_dev": [vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_float, vp],
+        "lrc_deform_span_launches": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+        "lrc_span_vertices": [vp, vp, u64, C.c_float, vp],
+        "lrc_deform_span_refit": [vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp],
         "lrc_skin_apply": [vp, u64, vp, vp, vp, C.c_uint32, vp],
         "lrc_deform_create_skinned": [vp, vp, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, u64, vp, vp, C.POINTER(vp)],
         "lrc_scan_nonrigid_flow_dev": [vp, vp, C.POINTER(LrcHits), vp, u64, u64, vp, vp, vp, vp, dbl, vp, C.c_uint32, vp, vp, vp],

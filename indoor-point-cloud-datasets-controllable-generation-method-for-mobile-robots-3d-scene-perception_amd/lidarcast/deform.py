@@ -10,6 +10,11 @@ the device instead of whole vertex arrays.  A ``lidarcast
 ``scan_deforming_frames`` / ``scan_deforming_dev`` scan frames whose movers change shape from frame to frame;
 ``scan_deforming_flow_frames`` / ``scan_deforming_flow_dev`` add the non-rigid scene flow from each frame to the next (DESIGN.md
 section 5p), for which ``Deformable.snapshot`` keeps the shape a frame was scanned with while the next one is set.
+
+Animated movers under sweeps: ``Deformable.span(shape_a, shape_b)`` puts the deformable between two shapes,
+and the mover-sweep scans then meet it, ray by ray, at the shape it has at the ray's own firing fraction; ``span_vertices`` and
+``span_refit`` are the host steps (lrc_span_vertices, lrc_deform_span_refit), ``scan_deforming_sweeps_dev`` /
+``scan_deforming_sweep_frames`` the scans of sweeps whose movers change shape while the sweep is scanned.
 """
 import ctypes as C
 
@@ -89,6 +94,26 @@ class Deformable:
             raise ValueError("keyframe index out of range")
         check(self._lib.lrc_deform_set_dev(self._h, int(k0), int(k1), float(np.float32(w)), C.c_void_p(int(stream))),
               "lrc_deform_set_dev")
+
+    def span(self, shape_a, shape_b, stream=0):
+        """Enqueue on ``stream`` the span between two shapes, each a (k0, k1, w) triple as ``set`` takes it
+        (lrc_deform_span_dev); no host synchronisation.  A mover-sweep scan enqueued on the same stream afterwards meets the
+        deformable per ray at ``span_vertices(VA, VB, float32(fire))``; every other scan or cast sees shape A.  ``set`` ends it."""
+        if not self._h:
+            raise ValueError("deformable is closed")
+        a, b = tuple(shape_a), tuple(shape_b)
+        if len(a) != 3 or len(b) != 3:
+            raise ValueError("a shape is (k0, k1, w)")
+        if min(int(a[0]), int(a[1]), int(b[0]), int(b[1])) < 0:
+            raise ValueError("keyframe index out of range")
+        check(self._lib.lrc_deform_span_dev(self._h, int(a[0]), int(a[1]), float(np.float32(a[2])), int(b[0]), int(b[1]),
+                                            float(np.float32(b[2])), C.c_void_p(int(stream))), "lrc_deform_span_dev")
+
+    def span_launches(self):
+        """(kernel launches of one ``span`` whose two shapes are blended, of one whose two shapes are keyframe copies)."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        check(self._lib.lrc_deform_span_launches(self._h, C.byref(a), C.byref(b)), "lrc_deform_span_launches")
+        return int(a.value), int(b.value)
 
     def vertices(self):
         """The current (V, 3) float32 vertices, read back synchronously."""
@@ -199,6 +224,41 @@ def refit(nodes16, slot_prim, triangles, vertices):
     check(lib.lrc_deform_refit(nodes.ctypes.data, len(nodes), sp.ctypes.data, len(sp), f.ctypes.data, len(f), v.ctypes.data,
                                len(v), rec.ctypes.data, box.ctypes.data), "lrc_deform_refit")
     return nodes, rec, box
+
+
+def span_vertices(a, b, s):
+    """lrc_span_vertices: the (V, 3) float32 shape a span between vertex arrays ``a`` and ``b`` has at the firing fraction ``s``
+    (narrowed to float32 as the kernel narrows it); no GPU.  Per coordinate ``a`` where s == 0 or the two have the same bits,
+    ``b`` where s == 1, else ``blend``'s value."""
+    lib = _capi.load()
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError("a and b must have the same shape")
+    out = np.empty_like(a)
+    check(lib.lrc_span_vertices(a.ctypes.data, b.ctypes.data, len(a), float(np.float32(s)), out.ctypes.data), "lrc_span_vertices")
+    return out
+
+
+def span_refit(nodes16, slot_prim, triangles, vertices_a, vertices_b):
+    """lrc_deform_span_refit: the tree ``nodes16`` (num_nodes, 16) float32 over the leaf slots ``slot_prim`` refitted to hold
+    both ``vertices_a`` and ``vertices_b``; no GPU.  Returns (nodes with every child box recomputed and the references untouched,
+    (num_slots, 6) span boxes, (num_slots, 18) slot vertices: A's three, then B's)."""
+    lib = _capi.load()
+    nodes = np.ascontiguousarray(nodes16, dtype=np.float32).reshape(-1, 16)
+    sp = np.ascontiguousarray(slot_prim, dtype=np.uint32).reshape(-1)
+    f = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+    va = np.ascontiguousarray(vertices_a, dtype=np.float32).reshape(-1, 3)
+    vb = np.ascontiguousarray(vertices_b, dtype=np.float32).reshape(-1, 3)
+    if va.shape != vb.shape:
+        raise ValueError("vertices_a and vertices_b must have the same shape")
+    out = np.zeros_like(nodes)
+    box = np.zeros((len(sp), 6), np.float32)
+    rec = np.zeros((len(sp), 18), np.float32)
+    check(lib.lrc_deform_span_refit(nodes.ctypes.data, len(nodes), sp.ctypes.data, len(sp), f.ctypes.data, len(f), va.ctypes.data,
+                                    vb.ctypes.data, len(va), out.ctypes.data, box.ctypes.data, rec.ctypes.data),
+          "lrc_deform_span_refit")
+    return out, box, rec
 
 
 class Clip:
@@ -315,6 +375,69 @@ def scan_deforming_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover_po
         else:
             scene.scan_noisy_movers_dev(poses_t[a:b], dirs_t, part, max_range, movers, mp[a:b],
                                         noise.at_frame(noise.first_frame + a), rows, stream=stream)
+
+
+def _span_shapes(shapes_a, shapes_b, P, movers):
+    ds, a = _shapes(shapes_a, P, movers)
+    _, b = _shapes(shapes_b, P, movers)
+    return ds, a, b, _runs(np.concatenate([a, b], axis=2))
+
+
+def scan_deforming_sweeps_dev(scene, motion_t, dirs_t, fire_t, hits, max_range, movers, records_t, shapes_a, shapes_b,
+                              mover_t=None, stream=0):
+    """``lidarcast.movers.scan_mover_sweeps_dev`` with movers that change shape while a sweep is scanned,
+    everything enqueued on ``stream`` with no host synchronisation: ``shapes_a`` / ``shapes_b`` (P, D, 3) float64 hold [k0, k1,
+    w] at the start and at the end of every sweep per deformable of the set, in the set's order (``Clip.shapes3`` of the two
+    times).  Per run of consecutive sweeps with equal (A, B) one ``span`` per deformable, then lrc_scan_mover_sweeps_dev on the
+    run's slice of the sensor records, the mover records, the hit records and ``mover_t``."""
+    from .movers import scan_mover_sweeps_dev
+    P, N = motion_t.shape[0], dirs_t.shape[0]
+    if hits.n != P * N:
+        raise ValueError("hits must hold P * N records")
+    if "tile_count" in hits.want:
+        raise ValueError("tile_count is not written by this scan")
+    ds, sa, sb, runs = _span_shapes(shapes_a, shapes_b, P, movers)
+    mt = motion_t.reshape(P, 24)
+    rt = records_t.reshape(P, len(movers), 24)
+    for a, b in runs:
+        for j, d in enumerate(ds):
+            d.span(sa[a, j], sb[a, j], stream=stream)
+        rows = None if mover_t is None else mover_t[a * N:b * N]
+        scan_mover_sweeps_dev(scene, mt[a:b], dirs_t, fire_t, _HitsSlice(hits, a * N, b * N), max_range, movers, rt[a:b], rows,
+                              stream=stream)
+
+
+def scan_deforming_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh, movers, mover_records, shapes_a, shapes_b,
+                                want=("point3", "sem", "ins"), inputs=None):
+    """``lidarcast.movers.scan_mover_sweep_frames`` with movers that change shape while a sweep is scanned: the host-pointer twin
+    of ``scan_deforming_sweeps_dev``.  Per run of consecutive sweeps with equal (A, B) every deformable is spanned once, the
+    context is synchronised (the frame path scans on the library's own streams) and the run is scanned by
+    lrc_scan_mover_sweeps_compact; the runs stack to the dict ``scan_mover_sweep_frames`` returns for all sweeps
+    (``point_times`` and ``mover`` included)."""
+    from .movers import scan_mover_sweep_frames
+    motion, fire, T = inputs if inputs is not None else engine.sweep_inputs(intrinsics, start_poses, end_poses)
+    motion = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 24)
+    P = len(motion)
+    rec = np.ascontiguousarray(mover_records, dtype=np.float32)
+    if rec.shape != (P, len(movers), 24):
+        raise ValueError(f"mover_records must be (P, M, 24) = ({P}, {len(movers)}, 24), got {rec.shape}")
+    ds, sa, sb, runs = _span_shapes(shapes_a, shapes_b, P, movers)
+    parts = []
+    for a, b in runs:
+        for j, d in enumerate(ds):
+            d.span(sa[a, j], sb[a, j])
+        engine.ctx.synchronize()
+        parts.append(scan_mover_sweep_frames(engine, intrinsics, None, None, mesh, movers, rec[a:b], want=want,
+                                             inputs=(motion[a:b], fire, T)))
+    if not parts:
+        return scan_mover_sweep_frames(engine, intrinsics, None, None, mesh, movers, rec, want=want, inputs=(motion, fire, T))
+    out = {}
+    for key in parts[0]:
+        if key == "total":
+            out[key] = int(sum(p[key] for p in parts))
+        else:
+            out[key] = np.concatenate([p[key] for p in parts], 0)
+    return out
 
 
 def _mover_index(movers, d):

@@ -386,7 +386,10 @@ class S3DISSimulator:
         with ``mesh: walker`` the keyframes come from ``synth.make_walker``, with ``keyframes: <file.npy>`` a (K, V, 3) array serves
         the mesh file's own topology; frame k takes the shape of k * period.  The plan then also holds ``clips`` and ``keyframes``
         (one entry per object, None for a rigid one).  ``flow: true`` is refused in a set with an animated mover (the rigid flow
-        step is wrong for it), and so is ``animation`` under ``motion.movers`` (no deformation within a sweep).
+        step is wrong for it), and so is ``animation`` under ``motion.movers`` unless that key carries ``per_ray_shape: true``.
+        ``per_ray_shape: true`` (under ``motion.movers`` only) accepts animated objects there: each one's
+        clip is evaluated at the start and at the end of every sweep, and every ray meets the mover at the shape it has at the
+        moment the ray fires.  The plan's ``per_ray_shape`` holds the flag.
         An animated object may be SKINNED instead: ``mesh: walker_rig`` takes ``synth.make_walker_rig``, and
         ``skin: <file.npz>`` beside ``mesh: <file>`` takes the mesh file's vertices as the rest shape and, from the file,
         ``bone_index`` (V, 4) uint8, ``bone_weight`` (V, 4) float32, ``poses`` (K, B, 12) float32 and optionally ``parents`` (B,) and
@@ -414,9 +417,12 @@ class S3DISSimulator:
             for other in ("motion", "noise", "beam", "materials"):
                 if self.config.get(other) is not None:
                     raise ValueError(f"the movers key cannot be combined with the {other} key")
-        unknown = set(cfg) - {"period", "objects", "flow", "nonrigid_flow"} - (set() if nested else {"noise"})
+        unknown = set(cfg) - {"period", "objects", "flow", "nonrigid_flow"} - ({"per_ray_shape"} if nested else {"noise"})
         if unknown:
             raise ValueError(f"unknown entries under the {key} key: {sorted(unknown)}")
+        per_ray_shape = cfg.get("per_ray_shape", False)
+        if not isinstance(per_ray_shape, bool):
+            raise ValueError(f"{key}.per_ray_shape must be true or false")
         noise = None if nested else self._noise_model(under_movers=True)
         if not isinstance(cfg.get("flow", False), bool):
             raise ValueError(f"{key}.flow must be true or false")
@@ -472,7 +478,7 @@ class S3DISSimulator:
                 f = np.asarray(src.triangles, np.int32)
                 mesh = synth.TriangleMesh(vertices=np.asarray(src.vertices, np.float64), triangles=f,
                                           triangle_sem=np.full(len(f), sem, np.uint16), triangle_ins=np.full(len(f), ins, np.uint16))
-            clip, keys, rig = self._mover_animation(k, key, obj, mesh, nested)
+            clip, keys, rig = self._mover_animation(k, key, obj, mesh, nested and not per_ray_shape)
             meshes.append(mesh)
             tracks.append(MoverTrack(obj["path"]))
             clips.append(clip)
@@ -493,13 +499,15 @@ class S3DISSimulator:
         if nonrigid and sum(c is not None for c in clips) > 16:
             raise ValueError(f"{key}.nonrigid_flow takes at most 16 animated movers")
         return {"period": period, "meshes": meshes, "tracks": tracks, "objects": listed, "flow": bool(cfg.get("flow", False)),
-                "nonrigid_flow": nonrigid, "clips": clips, "keyframes": keyframes, "skins": skins, "noise": noise}
+                "nonrigid_flow": nonrigid, "clips": clips, "keyframes": keyframes, "skins": skins, "noise": noise,
+                "per_ray_shape": per_ray_shape}
 
     @staticmethod
-    def _mover_animation(k, key, obj, mesh, nested):
+    def _mover_animation(k, key, obj, mesh, refuse):
         """(Clip, (K, V, 3) float32 keyframes or None, skin dict or None) of mover ``k``'s ``animation`` entry, three times None
         without one.  A skinned mover has no keyframes; its dict holds rest, bone_index, bone_weight, poses12 and skeleton
-        (a ``lidarcast.skin.Skeleton`` or None)."""
+        (a ``lidarcast.skin.Skeleton`` or None).  ``refuse``: the key is ``motion.movers`` without ``per_ray_shape: true``,
+        where an animation is refused."""
         anim = obj.get("animation")
         if anim is None:
             if obj.get("keyframes") is not None:
@@ -507,7 +515,7 @@ class S3DISSimulator:
             if obj.get("skin") is not None:
                 raise ValueError(f"mover {k}: skin needs an animation entry")
             return None, None, None
-        if nested:
+        if refuse:
             raise ValueError("animation is not available under motion.movers: deformation within a sweep is not built")
         if not isinstance(anim, dict) or set(anim) - {"cycle", "phase", "loop"} or "cycle" not in anim:
             raise ValueError(f"mover {k}: animation is {{cycle: <seconds>, phase: 0.0, loop: true}}")
@@ -734,14 +742,41 @@ class S3DISSimulator:
             records = sweep_records(sweep_movers["tracks"], times, times + duration)                      # (P, M, 24) float32
             if "sem" not in want:           # the labels are the winner's: they come with the points
                 want = want[:1] + ("sem", "ins") + want[1:]
-            mset = MoverSet(engine.ctx, sweep_movers["meshes"])
+            animated = [m for m, c in enumerate(sweep_movers["clips"]) if c is not None]
+            deformables, mset = {}, None
             try:
-                fr = scan_mover_sweep_frames(engine, self.lidar_config, None, None, mesh, mset, records, want=want, inputs=sweep)
+                if animated:        # animated movers under sweeps: a per-ray shape between the sweep's two end shapes
+                    from lidarcast import deform
+                    for m in animated:
+                        mm, rig = sweep_movers["meshes"][m], sweep_movers["skins"][m]
+                        if rig is not None:
+                            deformables[m] = deform.SkinnedDeformable(engine.ctx, rig["rest"], mm.triangles, rig["bone_index"],
+                                                                      rig["bone_weight"], rig["poses12"], mm.triangle_sem,
+                                                                      mm.triangle_ins)
+                        else:
+                            deformables[m] = deform.Deformable(engine.ctx, sweep_movers["keyframes"][m], mm.triangles,
+                                                               mm.triangle_sem, mm.triangle_ins)
+                    mset = MoverSet(engine.ctx, [deformables.get(m, mm) for m, mm in enumerate(sweep_movers["meshes"])])
+                    shapes_a = np.stack([sweep_movers["clips"][m].shapes3(times) for m in animated], axis=1)             # (P, D, 3)
+                    shapes_b = np.stack([sweep_movers["clips"][m].shapes3(times + duration) for m in animated], axis=1)
+                    fr = deform.scan_deforming_sweep_frames(engine, self.lidar_config, None, None, mesh, mset, records, shapes_a,
+                                                            shapes_b, want=want, inputs=sweep)
+                else:
+                    mset = MoverSet(engine.ctx, sweep_movers["meshes"])
+                    fr = scan_mover_sweep_frames(engine, self.lidar_config, None, None, mesh, mset, records, want=want, inputs=sweep)
             finally:
-                mset.close()
+                if mset is not None:
+                    mset.close()
+                for d in deformables.values():
+                    d.close()
             sim_scene.mover_tracks = {"period": sweep_movers["period"], "objects": sweep_movers["objects"], "times": times,
                                       "states": states, "poses12": records[:, :, :12], "sensor_poses": poses_from_waypoints(waypoints),
                                       "end_states": end_states, "records24": records, "sweep_duration": duration}
+            if animated:
+                sim_scene.mover_tracks["shapes"] = {m: shapes_a[:, j] for j, m in enumerate(animated)}
+                sim_scene.mover_tracks["end_shapes"] = {m: shapes_b[:, j] for j, m in enumerate(animated)}
+                sim_scene.mover_tracks["keyframes"] = {m: sweep_movers["keyframes"][m] for m in animated if sweep_movers["skins"][m] is None}
+                sim_scene.mover_tracks["skins"] = {m: sweep_movers["skins"][m] for m in animated if sweep_movers["skins"][m] is not None}
         elif sweep is not None and sweep_noise is not None:
             from lidarcast.noise import scan_noisy_sweep_frames
             fr = scan_noisy_sweep_frames(engine, self.lidar_config, None, None, mesh, sweep_noise, want=want, inputs=sweep)
