@@ -1079,6 +1079,49 @@ int lrc_deform_span_refit(const float* nodes16, uint64_t num_nodes, const uint32
                           const uint32_t* tris3, uint64_t T, const float* verts_a3, const float* verts_b3, uint64_t V,
                           float* out_nodes16, float* out_span_box6, float* out_span_rec18 /* nullable */);
 
+/* ---- seeded sensor noise under movers in sweeps (opt-in) ----------------------------------------------
+ * The movers under moving-sensor sweeps and the seeded sensor noise, composed: a walking person seen from a moving robot, with
+ * range noise, angle jitter and dropped returns, drawn in the kernels and reproducible bit for bit.  The noise cannot be added
+ * afterwards: the jitter decides whether a ray meets the room or a mover; a dropped ray is never cast, not against a spanned
+ * deformable either; the range filter and min_range act on the noisy range.  float32 with one rounding per operation and
+ * nothing fused, beyond what the reused functions already fuse (the quantile's one fmaf).  For ray i of sweep k:
+ * frame = first_frame + k in 64 bits, s = (float)fire[i], and the noise is the Philox block of (seed, frame, i), words w0..w3.
+ *   1 ray       (o, d, live) is the ray of lrc_scan_noisy_sweeps_dev, bit for bit: dropout != 0 and w3 < thr drops the ray; the
+ *               jitter is applied to the table row in front of the rotation, the sweep behind it.  A ray that is not live is cast
+ *               against neither the room nor any mover: its record is the miss lrc_scan_noisy_sweeps_dev writes for a dropped
+ *               ray and its mover byte is 0.
+ *   2 movers    THAT ray is taken into every mover's frame at s (step 2 of the movers under moving-sensor sweeps; a still record
+ *               takes the shortcut there) and culled, unchanged.  The scene of a spanned deformable is cast per ray at the shape
+ *               of the same s: the jitter does not touch s.
+ *   3 winner    decided on the CLEAN ranges: the smallest float32 t of t_s, t_0, ..., t_(M-1) wins; on an exact tie the static
+ *               scene, then the smaller m.  The winner's normal is turned into the world by the mover's pose at s.
+ *   4 range     range_std != 0 and something was hit: t' = t_winner + float32(range_std) * z(w0), a float32 multiply, then an
+ *               add; t' <= 0 is no return.  The point, the range filter, min_range, incident_deg (both modes) and the record use
+ *               t', the jittered swept d and the sensor's centre c(s) of the moving-sensor sweeps in float64; prim, sem and ins
+ *               are the winner's; the mover byte is the winner's where the record is kept and 0 elsewhere.
+ *   5 zeros     a zero parameter skips its step (wave-uniform branches on kernel arguments).  The all-zero model gives the bytes
+ *               of lrc_scan_mover_sweeps_dev; a NULL set gives the bytes of lrc_scan_noisy_sweeps_dev and a zero mover column;
+ *               a sensor and movers that all stand still give the bytes of lrc_scan_noisy_movers_dev.
+ * The result does not depend on how the sweeps are split into calls when each call brings its own first_frame.
+ * LRC_ERR_INVALID_ARG before any launch, the call and the offender named: what lrc_scan_noisy_sweeps_dev refuses (a NULL model, a
+ * negative or non-finite standard deviation, dropout outside [0, 1), rays_per_pose >= 2^32, a range_noise option; in the compact
+ * call no fire table and a bad sensor record) and what lrc_scan_mover_sweeps_* refuse (the static scene among the movers, a set
+ * or table of another context, d_out->tile_count != NULL and, in the compact call, a bad mover sweep record).  min_range and
+ * incident_mode of the STATIC scene apply.  Scratch: the set's, laid out as under the seeded sensor noise under movers, 123 bytes
+ * per ray whatever M is.
+ *   lrc_scan_noisy_mover_sweeps_dev      device pointers, as lrc_scan_mover_sweeps_dev takes them, and the model; enqueued on
+ *                                        `stream`, nothing is waited for
+ *   lrc_scan_noisy_mover_sweeps_compact  lrc_scan_mover_sweeps_compact with the model: all sweeps are traced in one call, so sweep
+ *                                        p of the call is frame first_frame + p; frames and mover_rows as there */
+int lrc_scan_noisy_mover_sweeps_dev(lrc_scene* scene, lrc_movers* set /* nullable */, const double* d_motion24, uint64_t num_poses,
+                                    const double* d_dirs3, const double* d_fire, uint64_t rays_per_pose,
+                                    const float* d_mover_motion24, double max_range, const lrc_noise* noise, const lrc_hits* d_out,
+                                    uint8_t* d_mover /* nullable */, void* stream);
+int lrc_scan_noisy_mover_sweeps_compact(lrc_scene* scene, lrc_movers* set /* nullable */, const double* motion24,
+                                        uint64_t num_poses, const lrc_table* table, const float* mover_motion24, double max_range,
+                                        const lrc_noise* noise, const lrc_frames* out, uint8_t* mover_rows /* nullable */,
+                                        uint64_t capacity, uint64_t* out_total);
+
 /* Page-locked host memory for the frame buffers above (hipHostMalloc / hipHostFree).  The caller owns it. */
 int lrc_host_alloc(lrc_ctx* ctx, uint64_t bytes, void** out_ptr);
 int lrc_host_free(lrc_ctx* ctx, void* ptr);

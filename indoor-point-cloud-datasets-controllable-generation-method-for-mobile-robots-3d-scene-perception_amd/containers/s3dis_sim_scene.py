@@ -399,7 +399,7 @@ class S3DISSimScene:
         (the mover sweep record the scan used), and every frame ``sweep_duration`` in seconds.  With ``per_ray_shape: true``
         there an animated mover's ``shape`` is the shape at the START of the sweep and it additionally carries ``end_shape``,
         [k0, k1, w] at its END, and a rig with a skeleton ``end_joints``, the joints at the end shape taken out by the end pose.  Under ``movers: {noise: ...}``
-        (seeded sensor noise drawn in the mover kernels) the file additionally holds the noise model -- ``noise``: seed,
+        and under ``motion: {movers: {sensor_noise: ...}}`` (seeded sensor noise drawn in the mover kernels) the file additionally holds the noise model -- ``noise``: seed,
         range_std, angle_std_deg, dropout and first_frame (frame f has frame id first_frame + f) -- and every frame ``returns``,
         its kept noisy returns (static_points plus every mover's num_points).  Returns the dict."""
         tr = self.mover_tracks

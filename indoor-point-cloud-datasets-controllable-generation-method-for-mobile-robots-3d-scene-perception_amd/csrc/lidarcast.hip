@@ -754,6 +754,105 @@ __global__ __launch_bounds__(kBlock) void mover_sweep_merge_kernel(const TracePa
     if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
 }
 
+// ---- seeded sensor noise under movers in sweeps (lrc_scan_noisy_mover_sweeps_*; the arithmetic is lrc_movers.h's,
+// gen_ray_noisy_sweep's, sweep_centre's and noisy_range's, the orchestration noisy_mover_sweeps_scan_dev's) --
+// The noisy sweep ray kernel: one thread per (sweep, i).  The static pass (q.motion24 == NULL) forms gen_ray_noisy_sweep's bits
+// once -- the one Philox block for the jitter and the dropout, the one float64 chain -- and stores them as the world ray with the
+// ray's live byte (0: dropped, never cast; its stored ray is zeros, not what the generator left).  A mover's pass reads both
+// back, takes the world ray into the frame the mover has at s = (float)fire[i] (the jitter does not touch s) and stores it with
+// the keep byte of the explicit-ray launch: live && !culled (0: no ray stored).  The zero tests are on kernel arguments.
+__global__ __launch_bounds__(kBlock) void mover_noisy_sweep_rays_kernel(const double* __restrict__ motion24,
+                                                                        const double* __restrict__ dirs3,
+                                                                        const double* __restrict__ fire, const lrcnoise::Params np,
+                                                                        uint64_t rays_per_pose, uint64_t total,
+                                                                        const lrcmov::SweepRayPass q, int uniform,
+                                                                        float* __restrict__ world6, uint8_t* __restrict__ live,
+                                                                        float* __restrict__ rays6, uint8_t* __restrict__ keep) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= total) return;
+    const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
+    const uint64_t i = gid - (uint64_t)pose * rays_per_pose;
+    if (q.motion24 == nullptr) {
+        V3 o, d;
+        bool alive = true;
+        gen_ray_noisy_sweep(motion24, dirs3, fire, np, pose, i, o, d, alive);
+        if (!alive) o = d = V3{0.f, 0.f, 0.f};
+        float2* w = (float2*)(world6 + gid * 6);      // 24-byte records: 8-byte aligned
+        w[0] = make_float2(o.x, o.y);
+        w[1] = make_float2(o.z, d.x);
+        w[2] = make_float2(d.y, d.z);
+        live[gid] = alive ? (uint8_t)1 : (uint8_t)0;
+        return;
+    }
+    if (live[gid] == 0) {      // dropped: cast against no mover either
+        keep[gid] = 0;
+        return;
+    }
+    float r19[19];
+    mover_record_load(q.motion24, pose, q.M, q.m, uniform, r19);
+    const float2* w = (const float2*)(world6 + gid * 6);
+    const float2 a = w[0], b = w[1], c = w[2];
+    lrcmov::Vec ro, rd;
+    lrcmov::to_object_at(r19, (float)fire[i], lrcmov::Vec{a.x, a.y, b.x}, lrcmov::Vec{b.y, c.x, c.y}, ro, rd);
+    const bool out = lrcmov::culled(q.sphere, ro, rd);
+    keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
+    if (out) return;
+    float2* r = (float2*)(rays6 + gid * 6);
+    r[0] = make_float2(ro.x, ro.y);
+    r[1] = make_float2(ro.z, rd.x);
+    r[2] = make_float2(rd.y, rd.z);
+}
+
+// One thread per (sweep, i): mover_sweep_merge_kernel's winner on the CLEAN ranges (a dropped ray was cast nowhere: +inf
+// throughout), over MoverSweepMerge's view.  The last pass reads the stored world ray back, takes the filter centre from the
+// sensor's record (sweep_centre), draws the winner's range (noisy_range of frame first_frame + sweep: the ray's second Philox
+// block, only where range_std != 0 and something was hit; a non-positive range is no return) and writes the record
+// lrc_scan_noisy_sweeps_dev would write had the ray hit the winner (write_back, GIVEN), filter included, and the mover column.
+__global__ __launch_bounds__(kBlock) void mover_noisy_sweep_merge_kernel(const TraceParams p, const MoverSweepMerge q) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= p.total) return;
+    float t = q.w_t[gid];
+    uint32_t prim = q.w_prim[gid];
+    uint32_t label = (uint32_t)q.w_sem[gid] | ((uint32_t)q.w_ins[gid] << 16);
+    V3 n{q.w_n3[gid * 3], q.w_n3[gid * 3 + 1], q.w_n3[gid * 3 + 2]};
+    uint32_t who = q.w_who[gid];
+    const uint32_t pose = mover_pose_of(gid, p.rays_per_pose, q.uniform);
+    const uint64_t i = gid - (uint64_t)pose * p.rays_per_pose;
+    const float tm = q.m_t[gid];
+    if (lrcmov::takes(tm, t)) {
+        float r19[19];
+        mover_record_load(q.motion24, pose, q.M, q.m, q.uniform, r19);
+        const lrcmov::Vec w = lrcmov::to_world_at(r19, (float)p.fire[i], lrcmov::Vec{q.m_n3[gid * 3], q.m_n3[gid * 3 + 1], q.m_n3[gid * 3 + 2]});
+        t = tm;
+        prim = q.m_prim[gid];
+        label = (uint32_t)q.m_sem[gid] | ((uint32_t)q.m_ins[gid] << 16);
+        n = V3{w.x, w.y, w.z};
+        who = q.m + 1u;
+    }
+    if (!q.last) {
+        q.w_t[gid] = t;
+        q.w_prim[gid] = prim;
+        q.w_n3[gid * 3] = n.x; q.w_n3[gid * 3 + 1] = n.y; q.w_n3[gid * 3 + 2] = n.z;
+        q.w_sem[gid] = (uint16_t)(label & 0xFFFFu);
+        q.w_ins[gid] = (uint16_t)(label >> 16);
+        q.w_who[gid] = (uint8_t)who;
+        return;
+    }
+    const float2* wr = (const float2*)(q.world6 + gid * 6);
+    const float2 a = wr[0], b = wr[1], c = wr[2];
+    const V3 o{a.x, a.y, b.x}, d{b.y, c.x, c.y};
+    double cx, cy, cz;
+    sweep_centre(p.motion24 + (size_t)pose * 24, p.fire[i], cx, cy, cz);
+    bool hit = t < __builtin_inff();
+    if (p.noise.range_std != 0.0f && hit) {
+        t = noisy_range(p.noise, p.noise.first_frame + pose, (uint32_t)i, t);
+        hit = t > 0.0f;
+    }
+    const bool kept = write_back<true, false, true, false, true>(p, gid, threadIdx.x, o, d, cx, cy, cz, t, hit ? prim : 0xFFFFFFFFu,
+                                                                 label, false, V3{0.f, 0.f, 0.f}, 0.f, n);
+    if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
+}
+
 // ---- scene flow under movers (lrc_scan_flow_*; the arithmetic is lrc_flow.h's, the orchestration flow_scan_dev's) -------------
 // What the flow's ray kernel reads and writes.  The four line-of-sight columns are NULL together (flow only).
 struct FlowRays {
@@ -4679,6 +4778,97 @@ int mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion2
     return LRC_OK;
 }
 
+// mover_sweeps_scan_dev under seeded sensor noise.  A NULL set: the launch of lrc_scan_noisy_sweeps_dev and a zero mover column.
+// Otherwise
+//   the static pass    mover_noisy_sweep_rays_kernel (gen_ray_noisy_sweep's world rays and live bytes, stored) and the
+//                      explicit-ray launch on the scene under the live bytes: a dropped ray is never cast
+//   per mover m        mover_noisy_sweep_rays_kernel (the stored world ray in the frame the mover has at the ray's s + keep
+//                      bytes: live && !culled), the explicit-ray launch on the mover's scene -- or span_cast for the scene of a
+//                      spanned deformable, with the same firing fractions: the jitter does not touch s --, and
+//                      mover_noisy_sweep_merge_kernel, whose last pass draws the range and writes the records
+// in the set's scratch, laid out as noisy_movers_scan_dev lays it out (123 bytes per ray), grown under the same rule.
+int noisy_mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
+                                const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range,
+                                const lrcnoise::Params& np, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st) {
+    const uint64_t n = P * N;
+    if (!n) return LRC_OK;
+    if (!set) {
+        TraceParams p{};
+        p.noise = np;
+        p.motion24 = d_motion24;
+        p.dirs3 = d_dirs3;
+        p.fire = d_fire;
+        scan_fields(p, N, n, max_range, d_out);
+        const int rc = launch_trace(s, p, kGenNoisySweeps, st);
+        if (rc) return rc;
+        if (d_mover) LRC_HIP(hipMemsetAsync(d_mover, 0, n, st));
+        return LRC_OK;
+    }
+    if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_mover_sweeps: too many sweeps or rays for one call");
+    // scratch, 256-byte aligned columns: world6 | live | rays6 | keep | winner (t, prim, normal3, sem, ins, who) | mover (t, prim, normal3, sem, ins)
+    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
+    const uint64_t sizes[15] = {n * 24, n, n * 24, n, n * 4, n * 4, n * 12, n * 2, n * 2, n, n * 4, n * 4, n * 12, n * 2, n * 2};
+    uint64_t off[16] = {0};
+    for (int k = 0; k < 15; ++k) off[k + 1] = off[k] + al(sizes[k]);
+    if (set->scratch_cap < off[15]) {
+        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
+        if (set->scratch) { (void)hipFree(set->scratch); set->scratch = nullptr; set->scratch_cap = 0; }
+        LRC_HIP(hipMalloc(&set->scratch, off[15] + off[15] / 8));
+        set->scratch_cap = off[15] + off[15] / 8;
+    }
+    uint8_t* const b = (uint8_t*)set->scratch;
+    float* const world6 = (float*)(b + off[0]);
+    uint8_t* const live = b + off[1];
+    float* const rays6 = (float*)(b + off[2]);
+    uint8_t* const keep = b + off[3];
+    lrc_hits w{}, mv{};
+    w.t = (float*)(b + off[4]); w.prim = (uint32_t*)(b + off[5]); w.normal3 = (float*)(b + off[6]);
+    w.sem = (uint16_t*)(b + off[7]); w.ins = (uint16_t*)(b + off[8]);
+    uint8_t* const who = b + off[9];
+    mv.t = (float*)(b + off[10]); mv.prim = (uint32_t*)(b + off[11]); mv.normal3 = (float*)(b + off[12]);
+    mv.sem = (uint16_t*)(b + off[13]); mv.ins = (uint16_t*)(b + off[14]);
+    const dim3 grid((uint32_t)blocks_of(n, kBlock));
+    const int uniform = N % 64 == 0;
+    const uint32_t M = (uint32_t)set->scenes.size();
+    int rc;
+    lrcmov::SweepRayPass rp{};
+    hipLaunchKernelGGL(mover_noisy_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, np, N, n, rp, uniform,
+                       world6, live, rays6, keep);
+    LRC_HIP(hipGetLastError());
+    if ((rc = cast_plain(s, world6, live, n, w, st))) return rc;
+    LRC_HIP(hipMemsetAsync(who, 0, n, st));
+    TraceParams p{};       // what write_back and the range draw read: the sweep's inputs, the model, the filter, the scene's options, the caller's records
+    p.noise = np;
+    p.motion24 = d_motion24;
+    p.dirs3 = d_dirs3;
+    p.fire = d_fire;
+    scan_fields(p, N, n, max_range, d_out);
+    p.min_range = s->opts.min_range;
+    p.incident_mode = s->opts.incident_mode;
+    for (uint32_t m = 0; m < M; ++m) {
+        lrc_scene* const ms = set->scenes[m];
+        rp.motion24 = d_mover_motion24;
+        rp.M = M;
+        rp.m = m;
+        rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
+        hipLaunchKernelGGL(mover_noisy_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, np, N, n, rp,
+                           uniform, world6, live, rays6, keep);
+        LRC_HIP(hipGetLastError());
+        if ((rc = (ms->deform && ms->deform->spanned) ? span_cast(ms->deform, rays6, keep, d_fire, N, n, mv, st)
+                                                       : cast_plain(ms, rays6, keep, n, mv, st)))
+            return rc;
+        MoverSweepMerge q{};
+        q.motion24 = d_mover_motion24; q.world6 = world6; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
+        q.w_t = w.t; q.w_prim = w.prim; q.w_n3 = w.normal3; q.w_sem = w.sem; q.w_ins = w.ins; q.w_who = who;
+        q.m_t = mv.t; q.m_prim = mv.prim; q.m_n3 = mv.normal3; q.m_sem = mv.sem; q.m_ins = mv.ins;
+        q.d_mover = d_mover;
+        hipLaunchKernelGGL(mover_noisy_sweep_merge_kernel, grid, dim3(kBlock), 0, st, p, q);
+        LRC_HIP(hipGetLastError());
+    }
+    return LRC_OK;
+}
+
 // lrc_scan_flow_dev behind its checks (lrc_flow.hip).  All on `st`, nothing waited for:
 //   the ray kernel     flow_rays_kernel: the flow and, with d_status, the world line of sight, its cast byte, thr, the first status
 //                      (nonrigid_target_kernel instead when the call brings surface pairs)
@@ -4769,6 +4959,7 @@ int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const ui
 // With `motion24` (mover_sweeps_scan_compact): poses16 is unread, the P sensor records are staged in its place, `mover_poses12`
 // holds the (P, M, 24) mover sweep records, the table brings its fire table and mover_sweeps_scan_dev scans.
 // With `noise` (noisy_movers_scan_compact): noisy_movers_scan_dev scans in the place of movers_scan_dev.
+// With both (noisy_mover_sweeps_scan_compact): noisy_mover_sweeps_scan_dev scans; sweep p of the call is frame first_frame + p.
 namespace {
 struct FlowCompact {
     FlowNext next;             // host pointers
@@ -4779,7 +4970,8 @@ int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_
                    const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
                    uint64_t* out_total, const FlowCompact* flow, const double* motion24 = nullptr,
                    const lrcnoise::Params* noise = nullptr) {
-    const char* const who = motion24 ? "lrc_scan_mover_sweeps_compact" : flow ? "lrc_scan_flow_compact"
+    const char* const who = motion24 ? (noise ? "lrc_scan_noisy_mover_sweeps_compact" : "lrc_scan_mover_sweeps_compact")
+                            : flow   ? "lrc_scan_flow_compact"
                             : noise  ? "lrc_scan_noisy_movers_compact" : "lrc_scan_movers_compact";
     SyncUnlessOk guard;
     lrc_ctx* const ctx = s->ctx;
@@ -4828,8 +5020,10 @@ int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_
         LRC_HIP(hipHostMalloc((void**)&ctx->h_counts, (P + P / 4 + 64) * 8 * 5, hipHostMallocDefault));
         ctx->h_counts_cap = P + P / 4 + 64;
     }
-    if ((rc = motion24 ? mover_sweeps_scan_dev(s, set, d_poses, P, table->d_dirs3, table->d_fire, N, d_mp, max_range, &st.rec,
-                                               (uint8_t*)mbuf.p, cs)
+    if ((rc = motion24 && noise ? noisy_mover_sweeps_scan_dev(s, set, d_poses, P, table->d_dirs3, table->d_fire, N, d_mp, max_range,
+                                                              *noise, &st.rec, (uint8_t*)mbuf.p, cs)
+             : motion24 ? mover_sweeps_scan_dev(s, set, d_poses, P, table->d_dirs3, table->d_fire, N, d_mp, max_range, &st.rec,
+                                                (uint8_t*)mbuf.p, cs)
              : noise ? noisy_movers_scan_dev(s, set, d_poses, P, table->d_dirs3, N, d_mp, max_range, *noise, &st.rec,
                                              (uint8_t*)mbuf.p, cs)
                      : movers_scan_dev(s, set, d_poses, P, table->d_dirs3, N, d_mp, max_range, &st.rec, (uint8_t*)mbuf.p, cs)))
@@ -4898,6 +5092,13 @@ int mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motio
                               const float* mover_motion24, double max_range, const lrc_frames* out, uint8_t* mover_rows,
                               uint64_t capacity, uint64_t* out_total) {
     return movers_compact(s, set, nullptr, P, table, mover_motion24, max_range, out, mover_rows, capacity, out_total, nullptr, motion24);
+}
+
+int noisy_mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
+                                    const float* mover_motion24, double max_range, const lrcnoise::Params& noise,
+                                    const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total) {
+    return movers_compact(s, set, nullptr, P, table, mover_motion24, max_range, out, mover_rows, capacity, out_total, nullptr, motion24,
+                          &noise);
 }
 
 int flow_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,

@@ -259,6 +259,18 @@ int mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motio
                               uint64_t capacity, uint64_t* out_total);
 int check_motion(const char* who, const double* m, uint64_t P);
 
+// seeded sensor noise under movers in sweeps: the same split.  lrc_movers.hip checks the arguments of lrc_scan_noisy_mover_sweeps_*
+// and fills the lrcnoise::Params (noise_params); lidarcast.hip holds the two kernels and enqueues the passes
+// (noisy_mover_sweeps_scan_dev: everything on `st`, no host synchronisation; set == NULL: the scan of lrc_scan_noisy_sweeps_dev and
+// a zero mover column) and scans to frames (noisy_mover_sweeps_scan_compact: all sweeps in one call, sweep p is frame
+// first_frame + p).
+int noisy_mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
+                                const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range,
+                                const lrcnoise::Params& np, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st);
+int noisy_mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
+                                    const float* mover_motion24, double max_range, const lrcnoise::Params& noise,
+                                    const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total);
+
 // scene flow under movers.  lrc_flow.hip checks the arguments of lrc_scan_flow_* and owns the host functions; lidarcast.hip holds
 // the kernels and enqueues the passes (flow_scan_dev: everything on `st`, no host synchronisation; d_status == NULL: the flow
 // alone, nothing cast) and scans to frames (flow_scan_compact: the mover scan and the flow at the fixed stride, then the frame

@@ -4,7 +4,9 @@
 // kernels call on arrays.  The same for the movers under moving-sensor sweeps: the checks of lrc_scan_mover_sweeps_dev /
 // lrc_scan_mover_sweeps_compact (mover_sweeps_scan_dev, mover_sweeps_scan_compact) and the host functions lrc_mover_sweep_rays and
 // lrc_mover_sweep_normals.  And for the seeded sensor noise under movers: the checks of lrc_scan_noisy_movers_dev /
-// lrc_scan_noisy_movers_compact (noisy_movers_scan_dev, noisy_movers_scan_compact).
+// lrc_scan_noisy_movers_compact (noisy_movers_scan_dev, noisy_movers_scan_compact).  And for that noise under movers in sweeps:
+// the checks of lrc_scan_noisy_mover_sweeps_dev / lrc_scan_noisy_mover_sweeps_compact (noisy_mover_sweeps_scan_dev,
+// noisy_mover_sweeps_scan_compact).
 #include <cmath>
 
 #include "lrc_internal.h"
@@ -271,6 +273,55 @@ int lrc_scan_noisy_movers_compact(lrc_scene* s, lrc_movers* set, const double* p
     LRC_HIP(hipSetDevice(s->ctx->device));
     if ((rc = noise_params(s->ctx, who, noise, table->n, &np))) return rc;
     return noisy_movers_scan_compact(s, set, poses16, P, table, mover_poses12, max_range, np, out, mover_rows, capacity, out_total);
+}
+
+// ---- seeded sensor noise under movers in sweeps ------------------------------------------------------------------------------
+// Every refusal comes before the first device call, as above: the mover sweep calls' own (check_call, tile_count, NULL inputs,
+// the fire table, bad host records), then the model's (noise_params_host: the checks of lrc_scan_noisy_sweeps_dev with no
+// context, N >= 2^32 among them).
+
+int lrc_scan_noisy_mover_sweeps_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
+                                    const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range,
+                                    const lrc_noise* noise, const lrc_hits* d_out, uint8_t* d_mover, void* stream) {
+    const char* const who = "lrc_scan_noisy_mover_sweeps_dev";
+    int rc = check_call(who, s, set, d_out);
+    if (rc) return rc;
+    if (d_out->tile_count)
+        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": tile_count is not written by this scan (lrc_compact_dev counts itself)");
+    if (P && N && (!d_motion24 || !d_dirs3 || !d_fire))
+        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": motion24, dirs3 or fire is NULL");
+    if (P && N && set && !d_mover_motion24) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_motion24 is NULL");
+    lrcnoise::Params np{};
+    if ((rc = noise_params_host(who, noise, N, &np))) return rc;
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    if ((rc = noise_params(s->ctx, who, noise, N, &np))) return rc;
+    return noisy_mover_sweeps_scan_dev(s, set, d_motion24, P, d_dirs3, d_fire, N, d_mover_motion24, max_range, np, d_out, d_mover,
+                                       (hipStream_t)stream);
+}
+
+int lrc_scan_noisy_mover_sweeps_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
+                                        const float* mover_motion24, double max_range, const lrc_noise* noise, const lrc_frames* out,
+                                        uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total) {
+    const char* const who = "lrc_scan_noisy_mover_sweeps_compact";
+    if (out_total) *out_total = 0;
+    int rc = check_call(who, s, set, out);
+    if (rc) return rc;
+    if (!table) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table is NULL");
+    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table and scene belong to different contexts");
+    if (!table->d_fire) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": the table has no fire table (lrc_table_set_fire)");
+    lrcnoise::Params np{};
+    if ((rc = noise_params_host(who, noise, table->n, &np))) return rc;      // checked for an empty call too
+    if (!(P * table->n)) return LRC_OK;      // before motion24 is looked at
+    if (!motion24 || !out->counts) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": motion24 or counts is NULL");
+    if ((rc = check_motion(who, motion24, P))) return rc;
+    if (set) {
+        if (!mover_motion24) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_motion24 is NULL");
+        if ((rc = check_motion24(who, mover_motion24, P * set->scenes.size()))) return rc;
+    }
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    if ((rc = noise_params(s->ctx, who, noise, table->n, &np))) return rc;
+    return noisy_mover_sweeps_scan_compact(s, set, motion24, P, table, mover_motion24, max_range, np, out, mover_rows, capacity,
+                                           out_total);
 }
 
 }  // extern "C"

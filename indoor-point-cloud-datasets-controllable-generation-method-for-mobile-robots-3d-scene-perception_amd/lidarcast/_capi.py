@@ -44,6 +44,7 @@ SYMBOLS = (
     "lrc_mover_merge",
     "lrc_scan_mover_sweeps_dev", "lrc_scan_mover_sweeps_compact", "lrc_mover_sweep_rays", "lrc_mover_sweep_normals",
     "lrc_scan_noisy_movers_dev", "lrc_scan_noisy_movers_compact",
+    "lrc_scan_noisy_mover_sweeps_dev", "lrc_scan_noisy_mover_sweeps_compact",
     "lrc_scan_flow_dev", "lrc_scan_flow_compact", "lrc_flow_rays", "lrc_flow_status",
     "lrc_deform_create", "lrc_deform_destroy", "lrc_deform_scene", "lrc_deform_set_dev", "lrc_deform_vertices",
     "lrc_deform_launches", "lrc_deform_blend", "lrc_deform_refit",
@@ -319,6 +320,9 @@ def load():
         "lrc_scan_noisy_movers_dev": [vp, vp, vp, u64, vp, u64, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcHits), vp, vp],
         "lrc_scan_noisy_movers_compact": [vp, vp, vp, u64, vp, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcFrames), vp, u64,
                                           C.POINTER(u64)],
+        "lrc_scan_noisy_mover_sweeps_dev": [vp, vp, vp, u64, vp, vp, u64, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcHits), vp, vp],
+        "lrc_scan_noisy_mover_sweeps_compact": [vp, vp, vp, u64, vp, vp, dbl, C.POINTER(LrcNoise), C.POINTER(LrcFrames), vp, u64,
+                                                C.POINTER(u64)],
         "lrc_scan_flow_dev": [vp, vp, C.POINTER(LrcHits), vp, u64, u64, vp, vp, vp, vp, dbl, vp, vp, vp],
         "lrc_scan_flow_compact": [vp, vp, vp, u64, vp, vp, vp, vp, vp, dbl, C.POINTER(LrcFrames), vp, vp, vp, u64, C.POINTER(u64)],
         "lrc_flow_rays": [vp, vp, vp, u64, u64, C.c_uint32, vp, vp, vp, vp, dbl, dbl, vp, vp, vp, vp, vp],

@@ -384,13 +384,16 @@ def _span_shapes(shapes_a, shapes_b, P, movers):
 
 
 def scan_deforming_sweeps_dev(scene, motion_t, dirs_t, fire_t, hits, max_range, movers, records_t, shapes_a, shapes_b,
-                              mover_t=None, stream=0):
+                              mover_t=None, stream=0, noise=None):
     """``lidarcast.movers.scan_mover_sweeps_dev`` with movers that change shape while a sweep is scanned,
     everything enqueued on ``stream`` with no host synchronisation: ``shapes_a`` / ``shapes_b`` (P, D, 3) float64 hold [k0, k1,
     w] at the start and at the end of every sweep per deformable of the set, in the set's order (``Clip.shapes3`` of the two
     times).  Per run of consecutive sweeps with equal (A, B) one ``span`` per deformable, then lrc_scan_mover_sweeps_dev on the
-    run's slice of the sensor records, the mover records, the hit records and ``mover_t``."""
-    from .movers import scan_mover_sweeps_dev
+    run's slice of the sensor records, the mover records, the hit records and ``mover_t``.  ``noise``: an optional
+    ``lidarcast.noise.NoiseModel``: a run that starts at sweep a is scanned by
+    lrc_scan_noisy_mover_sweeps_dev with ``noise.at_frame(noise.first_frame + a)``, so sweep p has the noise of frame
+    ``noise.first_frame + p``; a dropped ray meets no shape, and the jitter does not touch the fraction the shape is taken at."""
+    from .movers import scan_mover_sweeps_dev, scan_noisy_mover_sweeps_dev
     P, N = motion_t.shape[0], dirs_t.shape[0]
     if hits.n != P * N:
         raise ValueError("hits must hold P * N records")
@@ -403,18 +406,30 @@ def scan_deforming_sweeps_dev(scene, motion_t, dirs_t, fire_t, hits, max_range, 
         for j, d in enumerate(ds):
             d.span(sa[a, j], sb[a, j], stream=stream)
         rows = None if mover_t is None else mover_t[a * N:b * N]
-        scan_mover_sweeps_dev(scene, mt[a:b], dirs_t, fire_t, _HitsSlice(hits, a * N, b * N), max_range, movers, rt[a:b], rows,
-                              stream=stream)
+        if noise is None:
+            scan_mover_sweeps_dev(scene, mt[a:b], dirs_t, fire_t, _HitsSlice(hits, a * N, b * N), max_range, movers, rt[a:b], rows,
+                                  stream=stream)
+        else:
+            scan_noisy_mover_sweeps_dev(scene, mt[a:b], dirs_t, fire_t, _HitsSlice(hits, a * N, b * N), max_range, movers, rt[a:b],
+                                        noise.at_frame(noise.first_frame + a), rows, stream=stream)
 
 
 def scan_deforming_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh, movers, mover_records, shapes_a, shapes_b,
-                                want=("point3", "sem", "ins"), inputs=None):
+                                want=("point3", "sem", "ins"), inputs=None, noise=None):
     """``lidarcast.movers.scan_mover_sweep_frames`` with movers that change shape while a sweep is scanned: the host-pointer twin
     of ``scan_deforming_sweeps_dev``.  Per run of consecutive sweeps with equal (A, B) every deformable is spanned once, the
     context is synchronised (the frame path scans on the library's own streams) and the run is scanned by
     lrc_scan_mover_sweeps_compact; the runs stack to the dict ``scan_mover_sweep_frames`` returns for all sweeps
-    (``point_times`` and ``mover`` included)."""
-    from .movers import scan_mover_sweep_frames
+    (``point_times`` and ``mover`` included).  ``noise``: an optional ``lidarcast.noise.NoiseModel``: a
+    run that starts at sweep a is scanned by lrc_scan_noisy_mover_sweeps_compact with ``noise.at_frame(noise.first_frame + a)``."""
+    from .movers import scan_mover_sweep_frames, scan_noisy_mover_sweep_frames
+
+    def scan(a, b):
+        if noise is None:
+            return scan_mover_sweep_frames(engine, intrinsics, None, None, mesh, movers, rec[a:b], want=want,
+                                           inputs=(motion[a:b], fire, T))
+        return scan_noisy_mover_sweep_frames(engine, intrinsics, None, None, mesh, movers, rec[a:b],
+                                             noise.at_frame(noise.first_frame + a), want=want, inputs=(motion[a:b], fire, T))
     motion, fire, T = inputs if inputs is not None else engine.sweep_inputs(intrinsics, start_poses, end_poses)
     motion = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 24)
     P = len(motion)
@@ -427,10 +442,9 @@ def scan_deforming_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh
         for j, d in enumerate(ds):
             d.span(sa[a, j], sb[a, j])
         engine.ctx.synchronize()
-        parts.append(scan_mover_sweep_frames(engine, intrinsics, None, None, mesh, movers, rec[a:b], want=want,
-                                             inputs=(motion[a:b], fire, T)))
+        parts.append(scan(a, b))
     if not parts:
-        return scan_mover_sweep_frames(engine, intrinsics, None, None, mesh, movers, rec, want=want, inputs=(motion, fire, T))
+        return scan(0, P)
     out = {}
     for key in parts[0]:
         if key == "total":

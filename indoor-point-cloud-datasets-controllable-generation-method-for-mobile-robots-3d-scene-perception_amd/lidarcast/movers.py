@@ -11,7 +11,9 @@ Movers under moving-sensor sweeps are this module's own, 
 the scene or the engine as their first argument.
 
 Seeded sensor noise under movers is at the end: ``scan_noisy_movers_dev``, ``scan_noisy_movers_compact``
-and ``scan_noisy_mover_frames``, module functions as well, bound as ``Scene`` and engine methods of the same names.
+and ``scan_noisy_mover_frames``, module functions as well, bound as ``Scene`` and engine methods of the same names.  The same
+noise under movers in sweeps follows: ``scan_noisy_mover_sweeps_dev``, ``scan_noisy_mover_sweeps_compact``
+and ``scan_noisy_mover_sweep_frames``.
 """
 import ctypes as C
 
@@ -361,6 +363,82 @@ def scan_noisy_mover_frames(engine, intrinsics, poses, mesh, movers, mover_poses
     poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4, 4)
     return scan_noisy_movers_compact(engine.scene_for(mesh), poses, engine._resident_table(intrinsics), intrinsics.max_range, movers,
                                      mover_poses, noise, want=want)
+
+
+# ---- seeded sensor noise under movers in sweeps (include/lidarcast.h "seeded sensor noise under movers in sweeps", DESIGN.md
+# section 5t) --------------------------------------------------------------------------------------------------------------------
+# Module functions with the scene and the engine as arguments, as the scans of the movers under moving-sensor sweeps are.
+
+def scan_noisy_mover_sweeps_dev(scene, motion_t, dirs_t, fire_t, hits, max_range, movers, mover_records_t, noise, mover_t=None,
+                                stream=0):
+    """``scan_mover_sweeps_dev`` with seeded sensor noise drawn in the mover kernels (lrc_scan_noisy_mover_sweeps_dev): ``noise`` a
+    ``lidarcast.noise.NoiseModel`` (sweep p of the call is frame ``noise.first_frame + p``); everything else as there.  The
+    all-zero model gives ``scan_mover_sweeps_dev``'s bytes, ``movers=None`` those of ``lidarcast.noise.scan_noisy_sweeps_dev`` and a
+    zero column."""
+    import torch
+    from .core import _check_side_tensor, _dptr, _stream
+    P, N = motion_t.shape[0], dirs_t.shape[0]
+    if motion_t.numel() != P * 24 or fire_t.numel() != N:
+        raise ValueError("motion_t must be (P, 24) and fire_t (N,)")
+    if hits.n != P * N:
+        raise ValueError("hits must hold P * N records")
+    handle, entries = None, None
+    if movers is not None:
+        handle, entries = movers.handle(scene.ctx), P * len(movers) * 24
+        if mover_records_t is None:
+            raise ValueError("mover_records_t must be (P, M, 24)")
+    _check_side_tensor("mover_records_t", mover_records_t, torch.float32, entries, "be (P, M, 24)", motion_t)
+    _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", motion_t)
+    nz = noise.struct()
+    check(scene._lib.lrc_scan_noisy_mover_sweeps_dev(scene._h, handle, _dptr(motion_t), P, _dptr(dirs_t), _dptr(fire_t), N,
+                                                     _dptr(mover_records_t), float(max_range), C.byref(nz), C.byref(hits.struct),
+                                                     _dptr(mover_t), _stream(stream)), "lrc_scan_noisy_mover_sweeps_dev")
+
+
+def scan_noisy_mover_sweeps_compact(scene, motion, dirs, fire, max_range, movers, mover_records, noise,
+                                    want=("point3", "sem", "ins"), capacity=None):
+    """``scan_mover_sweeps_compact`` with seeded sensor noise drawn in the mover kernels (lrc_scan_noisy_mover_sweeps_compact):
+    ``noise`` a ``lidarcast.noise.NoiseModel``; all sweeps are traced in one call, so sweep p is frame ``noise.first_frame + p``.
+    The return value of ``scan_mover_sweeps_compact``."""
+    from .core import DirectionTable, _ptr, _table_for
+    motion = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 24)
+    lib, h, P, reach = scene._lib, scene._h, motion.shape[0], float(max_range)
+    if fire is None and not isinstance(dirs, DirectionTable):
+        raise ValueError("fire is required with a plain direction table")
+    with _table_for(scene.ctx, dirs, fire) as tab:
+        if tab is dirs and fire is not None and \
+                (tab.fire is None or not np.array_equal(tab.fire, np.asarray(fire, np.float64).reshape(-1))):
+            tab.set_fire(fire)
+        if tab.fire is None:
+            raise ValueError("the direction table has no firing fractions")
+        handle, rec = None, None
+        if movers is not None:
+            handle = movers.handle(scene.ctx)
+            rec = np.ascontiguousarray(mover_records, dtype=np.float32)
+            if rec.shape != (P, len(movers), 24):
+                raise ValueError(f"mover_records must be (P, M, 24) = ({P}, {len(movers)}, 24), got {rec.shape}")
+        nz = noise.struct()
+        return scene._scan_frames("lrc_scan_noisy_mover_sweeps_compact", P, tab.n, want, capacity, lambda fr, cap, total, rows:
+                                  lib.lrc_scan_noisy_mover_sweeps_compact(h, handle, _ptr(motion), P, tab._h, _ptr(rec), reach,
+                                                                          C.byref(nz), fr, rows, cap, total),
+                                  side=[("mover", np.uint8, ())])
+
+
+def scan_noisy_mover_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh, movers, mover_records, noise,
+                                  want=("point3", "sem", "ins"), inputs=None):
+    """``scan_mover_sweep_frames`` with seeded sensor noise drawn in the mover kernels: ``noise`` a
+    ``lidarcast.noise.NoiseModel``; sweep k is frame ``noise.first_frame + k``, so any run of sweeps can be scanned again with its
+    exact noise (``noise.at_frame``).  The dict of ``scan_mover_sweep_frames``: ``point_times`` and ``mover`` included."""
+    motion, fire, T = inputs if inputs is not None else engine.sweep_inputs(intrinsics, start_poses, end_poses)
+    engine._need_table(intrinsics, "seeded sensor noise under movers in sweeps needs a sensor with a pose-independent direction table",
+                       NotImplementedError)
+    ask = tuple(want) + (() if "index" in want else ("index",))
+    fr = scan_noisy_mover_sweeps_compact(engine.scene_for(mesh), motion, engine._resident_table(intrinsics), fire,
+                                         intrinsics.max_range, movers, mover_records, noise, want=ask)
+    fr["point_times"] = fire[fr["index"]] * T
+    if "index" not in want:
+        del fr["index"]
+    return fr
 
 
 def _bind():

@@ -312,13 +312,16 @@ class S3DISSimulator:
             json.dump(summary, fh, indent=2)
         return summary
 
-    def _noise_model(self, nested=False, under_movers=False):
+    def _noise_model(self, nested=False, under_movers=False, under_sweep_movers=False):
         """The NoiseModel of the config key ``noise`` (None without the key): ``seed`` is required; ``range_std`` (m),
         ``angle_std_deg`` and ``dropout`` default to the sensor record's range_noise_std, angle_noise_std (degrees) and
         dropout_probability.  first_frame = 0: frame p of a run has frame id p.  ``nested``: the same entries under
         ``motion: {noise: ...}``, the seeded noise of moving-sensor sweeps.  ``under_movers``: the same entries under
-        ``movers: {noise: ...}``, the seeded noise drawn in the mover kernels."""
-        if under_movers:
+        ``movers: {noise: ...}``, the seeded noise drawn in the mover kernels.  ``under_sweep_movers``: the
+        same entries under ``motion: {movers: {sensor_noise: ...}}``, that noise under movers in sweeps."""
+        if under_sweep_movers:
+            cfg, key = ((self.config.get("motion") or {}).get("movers") or {}).get("sensor_noise"), "motion.movers.sensor_noise"
+        elif under_movers:
             cfg, key = (self.config.get("movers") or {}).get("noise"), "movers.noise"
         else:
             cfg = (self.config.get("motion") or {}).get("noise") if nested else self.config.get("noise")
@@ -402,14 +405,22 @@ class S3DISSimulator:
         ``noise: {seed, range_std?, angle_std_deg?, dropout?}`` under the (top-level) movers key draws seeded sensor noise in the
         mover kernels: the entries and defaults of the noise key, frame p has frame id p; the plan's
         ``noise`` holds the NoiseModel (None without the entry).  ``flow: true`` and ``nonrigid_flow: true`` are refused beside it;
-        a top-level noise key beside movers stays refused, and so does ``motion.noise`` beside ``motion.movers``."""
+        a top-level noise key beside movers stays refused, and so does ``motion.noise`` beside ``motion.movers``.
+        ``sensor_noise: {seed, range_std?, angle_std_deg?, dropout?}`` under ``motion.movers`` (there only)
+        draws that noise under movers in sweeps: the entries, defaults and unknown-entry refusal of the noise key, sweep p has
+        frame id p, and the plan's ``noise`` holds the NoiseModel.  Rigid, ``animation`` and ``skin`` objects all work (animated
+        ones with ``per_ray_shape: true``, as without noise).  The entry is not called ``noise``: ``noise`` under ``motion.movers``
+        and ``motion.noise`` beside ``motion.movers`` have been refused since sections 5n and 5r, configurations that spell them
+        rely on that refusal, and a name of its own keeps both refusals as they are.  ``flow`` and ``nonrigid_flow`` are refused
+        beside it as beside ``movers.noise``."""
         cfg = (self.config.get("motion") or {}).get("movers") if nested else self.config.get("movers")
         key = "motion.movers" if nested else "movers"
         if cfg is None:
             return None
         if nested:
             if (self.config.get("motion") or {}).get("noise") is not None:
-                raise ValueError("motion.movers cannot be combined with motion.noise: noise under mover sweeps is not built")
+                raise ValueError("motion.movers cannot be combined with motion.noise: noise under mover sweeps is not built by "
+                                 "this pair of keys; it is asked for with motion: {speed, movers: {sensor_noise: {seed, ...}, ...}}")
             for other in ("beam", "materials"):
                 if self.config.get(other) is not None:
                     raise ValueError(f"motion.movers cannot be combined with the {other} key")
@@ -417,13 +428,18 @@ class S3DISSimulator:
             for other in ("motion", "noise", "beam", "materials"):
                 if self.config.get(other) is not None:
                     raise ValueError(f"the movers key cannot be combined with the {other} key")
-        unknown = set(cfg) - {"period", "objects", "flow", "nonrigid_flow"} - ({"per_ray_shape"} if nested else {"noise"})
+        unknown = set(cfg) - {"period", "objects", "flow", "nonrigid_flow"} - ({"per_ray_shape", "sensor_noise"} if nested else {"noise"})
         if unknown:
             raise ValueError(f"unknown entries under the {key} key: {sorted(unknown)}")
         per_ray_shape = cfg.get("per_ray_shape", False)
         if not isinstance(per_ray_shape, bool):
             raise ValueError(f"{key}.per_ray_shape must be true or false")
-        noise = None if nested else self._noise_model(under_movers=True)
+        noise = self._noise_model(under_sweep_movers=True) if nested else self._noise_model(under_movers=True)
+        if nested and noise is not None and (cfg.get("flow", False) is True or cfg.get("nonrigid_flow", False) is True):
+            which = "nonrigid_flow" if cfg.get("nonrigid_flow", False) is True else "flow"
+            raise ValueError(f"motion.movers.{which} is not available beside motion.movers.sensor_noise: a noisy point sits off its "
+                             "surface by more than the status margin of 2^-12 max(L, 1), so its own surface would occlude it "
+                             "(scene flow under noise is not built)")
         if not isinstance(cfg.get("flow", False), bool):
             raise ValueError(f"{key}.flow must be true or false")
         if nested and cfg.get("flow", False):
@@ -643,6 +659,7 @@ class S3DISSimulator:
             # ... or with moving objects under them (nested key ``motion: {speed, movers: {period, objects: [...]}}``, the entries
             # of the movers key above): every ray meets each mover at the pose the mover has at the moment the ray fires (DESIGN.md
             # section 5n); sweep k starts at k * period and lasts 1 / scan_frequency; frames carry point_times AND mover_ids.
+            # ... and seeded sensor noise under those (``sensor_noise: {seed, ...}`` under motion.movers).
             sweep_movers = self._mover_plan(nested=True)
             sweep_noise = self._noise_model(nested=True)
         # opt-in seeded sensor noise (config key ``noise: {seed, range_std?, angle_std_deg?, dropout?}``): range noise, angle
@@ -734,7 +751,7 @@ class S3DISSimulator:
         elif noise is not None:
             fr = engine.scan_noisy_frames(self.lidar_config, poses_from_waypoints(waypoints), mesh, noise, want=want)
         elif sweep is not None and sweep_movers is not None:
-            from lidarcast.movers import MoverSet, scan_mover_sweep_frames, sweep_records
+            from lidarcast.movers import MoverSet, scan_mover_sweep_frames, scan_noisy_mover_sweep_frames, sweep_records
             duration = 1.0 / float(self.lidar_config.scan_frequency)
             times = np.arange(len(waypoints), dtype=np.float64) * sweep_movers["period"]
             states = np.stack([t.state(times) for t in sweep_movers["tracks"]], axis=1)                  # (P, M, 4) at the sweep's start
@@ -759,11 +776,17 @@ class S3DISSimulator:
                     mset = MoverSet(engine.ctx, [deformables.get(m, mm) for m, mm in enumerate(sweep_movers["meshes"])])
                     shapes_a = np.stack([sweep_movers["clips"][m].shapes3(times) for m in animated], axis=1)             # (P, D, 3)
                     shapes_b = np.stack([sweep_movers["clips"][m].shapes3(times + duration) for m in animated], axis=1)
+                    extra = {} if sweep_movers["noise"] is None else {"noise": sweep_movers["noise"]}
                     fr = deform.scan_deforming_sweep_frames(engine, self.lidar_config, None, None, mesh, mset, records, shapes_a,
-                                                            shapes_b, want=want, inputs=sweep)
+                                                            shapes_b, want=want, inputs=sweep, **extra)
                 else:
                     mset = MoverSet(engine.ctx, sweep_movers["meshes"])
-                    fr = scan_mover_sweep_frames(engine, self.lidar_config, None, None, mesh, mset, records, want=want, inputs=sweep)
+                    if sweep_movers["noise"] is not None:      # seeded noise drawn in the sweep's mover kernels
+                        fr = scan_noisy_mover_sweep_frames(engine, self.lidar_config, None, None, mesh, mset, records,
+                                                           sweep_movers["noise"], want=want, inputs=sweep)
+                    else:
+                        fr = scan_mover_sweep_frames(engine, self.lidar_config, None, None, mesh, mset, records, want=want,
+                                                     inputs=sweep)
             finally:
                 if mset is not None:
                     mset.close()
@@ -772,6 +795,8 @@ class S3DISSimulator:
             sim_scene.mover_tracks = {"period": sweep_movers["period"], "objects": sweep_movers["objects"], "times": times,
                                       "states": states, "poses12": records[:, :, :12], "sensor_poses": poses_from_waypoints(waypoints),
                                       "end_states": end_states, "records24": records, "sweep_duration": duration}
+            if sweep_movers["noise"] is not None:
+                sim_scene.mover_tracks["noise"] = sweep_movers["noise"]
             if animated:
                 sim_scene.mover_tracks["shapes"] = {m: shapes_a[:, j] for j, m in enumerate(animated)}
                 sim_scene.mover_tracks["end_shapes"] = {m: shapes_b[:, j] for j, m in enumerate(animated)}

@@ -1,0 +1,24 @@
+"""CPU: the two kernels of the seeded sensor noise under movers in sweeps (mover_noisy_sweep_rays_kernel: gen_ray_noisy_sweep
+stored once with its live byte, the stored world ray in the frame a mover has at the ray's own firing fraction, the cull;
+mover_noisy_sweep_merge_kernel: the running winner on the clean ranges and, in the last pass, sweep_centre, the range draw and
+write_back with a given normal and triangle row on the stored world ray) are found exactly once each and use no scratch and no
+LDS -- read from the compiler's kernel-resource-usage remarks as tests/test_mover_noise_kernel_resources.py reads them.  VGPRs,
+SGPRs and occupancy are printed, not fixed (DESIGN.md section 5t records them)."""
+import pytest
+
+from kernel_resources import usage_of
+
+
+@pytest.fixture(scope="module")
+def usage():
+    return usage_of("lidarcast.hip")
+
+
+@pytest.mark.parametrize("kernel", ["mover_noisy_sweep_rays_kernel", "mover_noisy_sweep_merge_kernel"])
+def test_mover_sweep_noise_kernel_has_no_scratch_and_no_lds(usage, kernel):
+    names = [k for k in usage if kernel in k]
+    assert len(names) == 1, sorted(k for k in usage if "mover" in k)
+    u = usage[names[0]]
+    print(f"\n[mover sweep noise] {kernel}: {u}")
+    assert u["ScratchSize"] == 0, u
+    assert u["LDS"] == 0, u
