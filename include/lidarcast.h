@@ -1581,6 +1581,101 @@ int lrc_voxgrid_finalize(lrc_voxgrid* vg, uint32_t min_returns, uint32_t* out_id
 /* Copy out the free bitset (words uint32; bit v of word v/32, least significant bit first). */
 int lrc_voxgrid_export_bits(lrc_voxgrid* vg, uint32_t* out_bits);
 
+/* ---- dynamic occupancy: per-frame grids under movers ------------------------------------------
+ * An occupancy SEQUENCE is F frame slots of one grid geometry.  lrc_voxgrid ORs the free space of all poses into one grid,
+ * which is wrong as soon as something moves: a pedestrian smears into a corridor of occupied voxels that the free space
+ * carved while they stood elsewhere contradicts.  A sequence keeps one grid per frame (4D occupancy, single-sweep scene
+ * completion) and, with LRC_VOXSEQ_STATIC_ONLY and every pose mapped to one slot, the static map with the movers' returns
+ * left out.  Definitions:
+ *   grid       origin, voxel size, dims, the voxel of a point and the linear index exactly as lrc_voxgrid defines them
+ *              above.  F >= 1 slots; each slot's free bits start on a word boundary (words_per_frame = ceil(V / 32) words
+ *              per slot, V = nx*ny*nz).  Create refuses F * 32 * words_per_frame > 2^31 - 1 and everything
+ *              lrc_voxgrid_create refuses.
+ *   segments   ray (p, i), entry r = p*N + i of the records, contributes iff t[r] is finite.  Its segment runs from o to e:
+ *              o = d_origins3[p] when origin_per_ray == 0 (a float32 triple; for every pose-batched scan the float32 of the
+ *              pose's translation, as the scan forms its ray origin), o = d_origins3[r] when origin_per_ray == 1 (taken as
+ *              given); e = point3[r].  Its labels are sem[r], ins[r]; its mover id d_mover[r] (NULL: all zero; 0 is the
+ *              room, m + 1 mover m, the column the mover scans write).  Its slot is f = d_frame_of_pose[p] (uint32), or
+ *              first_frame + p when that array is NULL.  With a NULL array first_frame + num_poses > F is refused before
+ *              any launch; with an array a pose whose f >= F contributes nothing, its returned rays are counted in
+ *              `skipped`, and no access is made with that f.
+ *   walk       the walk, the limits and the rejection of lrc_voxgrid, verbatim: float64 without contraction, ties x, then
+ *              y, then z, a == b carves nothing, rejected rays are counted (per slot).  Free bits and returns go to slot f
+ *              only.
+ *   flags      LRC_VOXSEQ_STATIC_ONLY: a returned ray with mover id != 0 carves its free voxels as usual but records no
+ *              return; its end voxel gets neither a free bit nor a return from it.
+ *   accumulate additive over calls until reset; the result depends neither on pose order, nor on chunking, nor on the order
+ *              of atomics: free bits are an OR, returns and the counters are integer counts.
+ *   finalize   (min_returns >= 1) per slot, returns, the state, sem and ins exactly as lrc_voxgrid_finalize defines them.
+ *              Two more columns come from a SECOND, INDEPENDENT vote over the same returns: mover[v] (uint8) = the most
+ *              frequent mover id among all of v's returns, ties to the smallest id; mover_returns[v] (uint32) = the number
+ *              of v's returns with id != 0.  sem / ins and mover are voted separately: in a voxel shared by a mover and the
+ *              room they can name different surfaces (sem / ins of the mover's majority class beside mover == 0, or the
+ *              reverse).  Outputs (lrc_voxseq_out): ONE sparse list of every (slot, voxel) with >= 1 return, ascending by
+ *              (slot, idx), idx within the slot; frame_offsets (F + 1 uint64): slot f owns entries
+ *              [frame_offsets[f], frame_offsets[f + 1]), frame_offsets[F] is the list's length; an optional dense state of
+ *              F * V bytes, slot-major (0 unknown, 1 free, 2 occupied); counts, F x 6 uint64 in the order of
+ *              lrc_voxgrid_counts; one `skipped` word.
+ * Every ray of an accumulate call reserves two 8-byte key slots until the next reset (the key buffers grow, no return is
+ * dropped; at most 2^31 - 1 rays between resets).  The object is not thread-safe and its calls must be ordered on one
+ * stream; "_dev" entry points enqueue on `stream`, the others return after the work finished. */
+#define LRC_VOXSEQ_STATIC_ONLY 1u
+
+typedef struct lrc_voxseq lrc_voxseq;
+
+typedef struct lrc_voxseq_info {
+    double   origin[3];
+    double   voxel_size;
+    int64_t  dims[3];
+    uint64_t num_voxels;       /* V = nx*ny*nz, per slot                                           */
+    uint64_t words_per_frame;  /* ceil(V / 32): the free bitset holds num_frames * this many words */
+    uint64_t num_frames;       /* F                                                                */
+    uint64_t reserved_keys;    /* rays accumulated since the last reset (key slots)                */
+    uint64_t sparse_bound;     /* min(F * V, reserved_keys): capacity the sparse outputs need      */
+} lrc_voxseq_info;             /* 96 bytes */
+
+/* The outputs of finalize: device pointers for the _dev form, host pointers for the host form. */
+typedef struct lrc_voxseq_out {
+    uint32_t* idx;             /* (capacity)  linear index within the slot                         */
+    uint16_t* sem;             /* (capacity)                                                       */
+    uint16_t* ins;             /* (capacity)                                                       */
+    uint32_t* returns;         /* (capacity)                                                       */
+    uint8_t*  mover;           /* (capacity)  the mover vote                                       */
+    uint32_t* mover_returns;   /* (capacity)  returns with mover id != 0                           */
+    uint64_t* frame_offsets;   /* (F + 1)     required                                             */
+    uint8_t*  state;           /* (F * V)     nullable                                             */
+    uint64_t* counts;          /* (F, 6)      required; rows in the order of lrc_voxgrid_counts    */
+    uint64_t* skipped;         /* (1)         required                                             */
+} lrc_voxseq_out;              /* 80 bytes */
+
+int lrc_voxseq_create(lrc_ctx* ctx, const double* origin3, double voxel_size, const int64_t* dims3, uint64_t num_frames,
+                      lrc_voxseq** out_seq);
+int lrc_voxseq_destroy(lrc_voxseq* seq);
+int lrc_voxseq_get_info(const lrc_voxseq* seq, lrc_voxseq_info* out);
+/* Clear the free bits, the returns and the counters (skipped and rejected included). */
+int lrc_voxseq_reset(lrc_voxseq* seq, void* stream);
+/* Walk the segments of num_poses * rays_per_pose records (pose-major, as every pose-batched scan writes them).  d_records is
+ * a host struct of DEVICE pointers; its t, point3, sem and ins are required (LRC_ERR_INVALID_ARG otherwise), the other
+ * columns are not read.  d_origins3: num_poses (origin_per_ray == 0) or num_poses * rays_per_pose (== 1) float32 triples. */
+int lrc_voxseq_accumulate_dev(lrc_voxseq* seq, const float* d_origins3, int origin_per_ray, uint64_t num_poses,
+                              uint64_t rays_per_pose, const uint32_t* d_frame_of_pose /* nullable */, uint64_t first_frame,
+                              const lrc_hits* d_records, const uint8_t* d_mover /* nullable */, uint32_t flags,
+                              void* stream);
+/* The sparse columns need capacity >= sparse_bound entries each (unused tail entries are left as they were).  The _dev form
+ * needs no host synchronisation; the host form synchronises and copies frame_offsets[F] entries. */
+int lrc_voxseq_finalize_dev(lrc_voxseq* seq, uint32_t min_returns, const lrc_voxseq_out* d_out, uint64_t capacity,
+                            void* stream);
+int lrc_voxseq_finalize(lrc_voxseq* seq, uint32_t min_returns, const lrc_voxseq_out* out, uint64_t capacity);
+/* Copy out the free bitset (num_frames * words_per_frame uint32; bit v of slot f is bit v % 32 of word
+ * f * words_per_frame + v / 32). */
+int lrc_voxseq_export_bits(lrc_voxseq* seq, uint32_t* out_bits);
+/* Host step, no GPU: the walk of n segments o3[r] -> e3[r] (float32 triples) on a grid, compiled from the very functions the
+ * kernel calls.  ORs the free bits into io_free_bits (ceil(V / 32) words), writes b = the voxel of e3[r] to out_end3 (n x 3
+ * int64; inside the grid or not; zeros where o, e or a voxel coordinate was refused) and out_rejected[r] = 1 for a segment
+ * the limits refuse.  A segment is walked whatever its range: the caller selects the returned rays. */
+int lrc_voxseq_walk(const double* origin3, double voxel_size, const int64_t* dims3, const float* o3, const float* e3,
+                    uint64_t n, uint32_t* io_free_bits, int64_t* out_end3, uint8_t* out_rejected);
+
 /* ---- per-frame object annotations of scans ----------------------------------------------------
  * What a detector that trains on one sweep at a time needs, per (frame, object), in the SENSOR's frame: how many returns
  * the object got, how much of it is visible and where the visible part lies.  Definitions:

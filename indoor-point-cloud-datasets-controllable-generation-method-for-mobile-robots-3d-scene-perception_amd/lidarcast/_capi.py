@@ -63,6 +63,8 @@ SYMBOLS = (
     "lrc_coverage_select_dev", "lrc_coverage_export",
     "lrc_voxgrid_create", "lrc_voxgrid_destroy", "lrc_voxgrid_get_info", "lrc_voxgrid_reset", "lrc_voxgrid_accumulate_dev",
     "lrc_voxgrid_finalize", "lrc_voxgrid_finalize_dev", "lrc_voxgrid_export_bits",
+    "lrc_voxseq_create", "lrc_voxseq_destroy", "lrc_voxseq_get_info", "lrc_voxseq_reset", "lrc_voxseq_accumulate_dev",
+    "lrc_voxseq_finalize", "lrc_voxseq_finalize_dev", "lrc_voxseq_export_bits", "lrc_voxseq_walk",
     "lrc_frameobj_create", "lrc_frameobj_destroy", "lrc_frameobj_get_info", "lrc_frameobj_objects", "lrc_frameobj_reset",
     "lrc_frameobj_accumulate_dev", "lrc_frameobj_export", "lrc_frameobj_export_dev",
     "lrc_occ_create", "lrc_occ_destroy", "lrc_occ_query",
@@ -138,6 +140,18 @@ class LrcVoxgridInfo(C.Structure):
 class LrcVoxgridCounts(C.Structure):
     _fields_ = [("num_sparse", C.c_uint64), ("num_free", C.c_uint64), ("num_occupied", C.c_uint64),
                 ("num_unknown", C.c_uint64), ("rejected_rays", C.c_uint64), ("returns", C.c_uint64)]
+
+
+class LrcVoxseqInfo(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("voxel_size", C.c_double), ("dims", C.c_int64 * 3),
+                ("num_voxels", C.c_uint64), ("words_per_frame", C.c_uint64), ("num_frames", C.c_uint64),
+                ("reserved_keys", C.c_uint64), ("sparse_bound", C.c_uint64)]
+
+
+class LrcVoxseqOut(C.Structure):
+    _fields_ = [("idx", C.c_void_p), ("sem", C.c_void_p), ("ins", C.c_void_p), ("returns", C.c_void_p),
+                ("mover", C.c_void_p), ("mover_returns", C.c_void_p), ("frame_offsets", C.c_void_p),
+                ("state", C.c_void_p), ("counts", C.c_void_p), ("skipped", C.c_void_p)]
 
 
 class LrcFrameobjInfo(C.Structure):
@@ -376,6 +390,15 @@ def load():
         "lrc_voxgrid_finalize": [vp, C.c_uint32, vp, vp, vp, vp, u64, vp, C.POINTER(LrcVoxgridCounts)],
         "lrc_voxgrid_finalize_dev": [vp, C.c_uint32, vp, vp, vp, vp, u64, vp, vp, vp],
         "lrc_voxgrid_export_bits": [vp, vp],
+        "lrc_voxseq_create": [vp, vp, dbl, vp, u64, C.POINTER(vp)],
+        "lrc_voxseq_destroy": [vp],
+        "lrc_voxseq_get_info": [vp, C.POINTER(LrcVoxseqInfo)],
+        "lrc_voxseq_reset": [vp, vp],
+        "lrc_voxseq_accumulate_dev": [vp, vp, i32, u64, u64, vp, u64, C.POINTER(LrcHits), vp, C.c_uint32, vp],
+        "lrc_voxseq_finalize": [vp, C.c_uint32, C.POINTER(LrcVoxseqOut), u64],
+        "lrc_voxseq_finalize_dev": [vp, C.c_uint32, C.POINTER(LrcVoxseqOut), u64, vp],
+        "lrc_voxseq_export_bits": [vp, vp],
+        "lrc_voxseq_walk": [vp, dbl, vp, vp, vp, u64, vp, vp, vp],
         "lrc_frameobj_create": [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(vp)],
         "lrc_frameobj_destroy": [vp],
         "lrc_frameobj_get_info": [vp, C.POINTER(LrcFrameobjInfo)],

@@ -12,5 +12,8 @@ RaycastEngineHIP.scan_flow_frames = _scan_flow_frames
 # ... and so does the seeded sensor noise under movers, in lidarcast.movers
 from lidarcast.movers import scan_noisy_mover_frames as _scan_noisy_mover_frames  # noqa: E402
 RaycastEngineHIP.scan_noisy_mover_frames = _scan_noisy_mover_frames
+# ... and dynamic occupancy (per-frame grids under movers), in lidarcast.voxseq
+from lidarcast.voxseq import dynamic_occupancy as _dynamic_occupancy  # noqa: E402
+RaycastEngineHIP.dynamic_occupancy = _dynamic_occupancy
 
 __all__ = ["RaycastEngineBase", "RaycastEngineCPU", "RaycastEngineGPU", "RaycastEngineHIP", "mesh_arrays"]

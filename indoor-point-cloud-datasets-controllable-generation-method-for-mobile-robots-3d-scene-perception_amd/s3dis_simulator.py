@@ -251,6 +251,84 @@ class S3DISSimulator:
             json.dump(summary, f, indent=2)
         return summary
 
+    def export_dynamic_occupancy(self, waypoints: List[Waypoint], output_dir, voxel_size: float = 0.05,
+                                 min_returns: int = 1, process_group=None) -> Dict[str, Any]:
+        """Per-frame occupancy of the scan of ``waypoints`` over the loaded room and its movers, written to
+        ``output_dir``: <scene>_dynamic_occupancy.npz (one grid per frame: the dense state (F, nx, ny, nz) and the sparse list with
+        sem, ins, returns, mover and mover_returns), <scene>_static_map.npz (one slot: every frame's free space, the movers'
+        returns left out) and <scene>_dynamic_occupancy.json (per frame the counts, occupied voxels per class keyed by the S3DIS
+        class name where known, and dynamic voxels per mover).  Works with the top-level ``movers`` key (rigid, ``animation``,
+        ``skin`` and ``movers.noise``; frame k is at k * period) and with no feature key at all (the room alone, one grid per
+        waypoint).  The extent is the room mesh's bounds with a one-voxel margin.  Scans again on the GPU; run_simulation is not
+        involved.  Returns the JSON summary."""
+        if self.scene is None:
+            raise ValueError("Scene not loaded. Call load_scene() first.")
+        motion = self.config.get("motion")
+        if motion is not None:
+            key = "motion.movers" if isinstance(motion, dict) and motion.get("movers") is not None else "motion"
+            raise NotImplementedError(f"dynamic occupancy under the {key} key is outside its scope: no sweep scan exports its "
+                                      "per-ray origins yet")
+        for key in ("noise", "beam", "materials"):
+            if self.config.get(key) is not None:
+                raise NotImplementedError(f"dynamic occupancy under the {key} key is outside its scope")
+        batched = isinstance(self.lidar_config, Indoor8LineLidarIntrinsics) and self.lidar_config.vertical_degrees is not None
+        if not batched:
+            raise NotImplementedError("dynamic occupancy needs a multi-line sensor with a direction table (the dual-axis sensor "
+                                      "is outside its scope)")
+        from lidarcast.distributed import active_group
+        dist, _ = (None, None) if process_group is _NO_GROUP else active_group(process_group)
+        if dist is not None:
+            raise NotImplementedError("dynamic occupancy on a multi-rank process group is outside its scope")
+        from lidarcast.synth import S3DIS_CLASSES
+        engine, mesh = self.raycast_engine, self.scene.room_mesh
+        poses = poses_from_waypoints(waypoints)
+        plan = self._mover_plan() if len(waypoints) > 0 else None
+        deformables, mset, mover_poses, shapes, noise = {}, None, None, None, None
+        try:
+            if plan is not None:
+                from lidarcast.movers import MoverSet
+                times = np.arange(len(waypoints), dtype=np.float64) * plan["period"]
+                mover_poses = np.stack([t.poses12(times) for t in plan["tracks"]], axis=1)       # (P, M, 12) float32
+                noise = plan["noise"]
+                animated = [m for m, c in enumerate(plan["clips"]) if c is not None]
+                if animated:
+                    from lidarcast import deform
+                    for m in animated:
+                        mm, rig = plan["meshes"][m], plan["skins"][m]
+                        if rig is not None:
+                            deformables[m] = deform.SkinnedDeformable(engine.ctx, rig["rest"], mm.triangles, rig["bone_index"],
+                                                                      rig["bone_weight"], rig["poses12"], mm.triangle_sem,
+                                                                      mm.triangle_ins)
+                        else:
+                            deformables[m] = deform.Deformable(engine.ctx, plan["keyframes"][m], mm.triangles, mm.triangle_sem,
+                                                               mm.triangle_ins)
+                    shapes = np.stack([plan["clips"][m].shapes3(times) for m in animated], axis=1)      # (P, D, 3)
+                mset = MoverSet(engine.ctx, [deformables.get(m, mm) for m, mm in enumerate(plan["meshes"])])
+            r, static = engine.dynamic_occupancy(self.lidar_config, poses, mesh, movers=mset, mover_poses=mover_poses,
+                                                 shapes=shapes, noise=noise, voxel_size=voxel_size, min_returns=min_returns,
+                                                 static_map=True)
+        finally:
+            if mset is not None:
+                mset.close()
+            for d in deformables.values():
+                d.close()
+        out = Path(output_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        name = self.scene.scene_name
+        r.to_npz(out / f"{name}_dynamic_occupancy.npz")
+        static.to_npz(out / f"{name}_static_map.npz")
+        names = dict(enumerate(S3DIS_CLASSES))
+        summary = r.to_dict(class_names=names)
+        if len(waypoints) == 0:             # the one slot the object needs to exist is not a scanned frame
+            summary["num_frames"], summary["frames"] = 0, []
+        summary["scene_name"] = name
+        summary["num_poses"] = len(waypoints)
+        summary["movers"] = [] if plan is None else plan["objects"]
+        summary["static_map"] = static.to_dict(class_names=names)["frames"][0]
+        with open(out / f"{name}_dynamic_occupancy.json", "w") as f:
+            json.dump(summary, f, indent=2)
+        return summary
+
     def export_frame_annotations(self, waypoints: List[Waypoint], output_dir, min_points: int = 10,
                                  semantic_mapping: Optional[Dict[str, int]] = None) -> Dict[str, Any]:
         """Per-frame detection annotations of the scan of ``waypoints`` over the loaded room,
