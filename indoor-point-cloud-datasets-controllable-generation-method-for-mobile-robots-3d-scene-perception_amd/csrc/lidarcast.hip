@@ -443,7 +443,13 @@ __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, u
     return keep;
 }
 
-// ---- moving objects (lrc_scan_movers_*; the arithmetic is lrc_movers.h's, the orchestration movers_scan_dev's) ---------------
+// ---- moving objects: the mover scan family (lrc_scan_movers_*, lrc_scan_noisy_movers_*, lrc_scan_mover_sweeps_*,
+// lrc_scan_noisy_mover_sweeps_*; the arithmetic is lrc_movers.h's and the generators', the orchestration movers_scan_dev's;
+// DESIGN.md sections 5k, 5n, 5r, 5t) -------------------------------------------------------------------------------------------
+// One algorithm under two switches.  SWEEP: the sensor's records are (P,24) motion records and a mover is met at the pose its
+// (P,M,24) record has at the ray's firing fraction s = (float)fire[i] (to_object_at / to_world_at), not at its (P,M,12) pose.
+// NOISY: the ray is the noisy generator's, with a live byte (0: dropped, never cast), and the last merge draws the winner's range.
+//
 // Pose of ray gid and, with `uniform` (rays_per_pose % 64 == 0: a wave lies in one pose), the same value as a scalar, so that what
 // is read per pose comes through the scalar cache.
 __device__ __forceinline__ uint32_t mover_pose_of(uint64_t gid, uint64_t rays_per_pose, int uniform) {
@@ -451,406 +457,183 @@ __device__ __forceinline__ uint32_t mover_pose_of(uint64_t gid, uint64_t rays_pe
     if (uniform) pose = (uint32_t)__builtin_amdgcn_readfirstlane((int)pose);
     return pose;
 }
-__device__ __forceinline__ void mover_pose_load(const float* poses12, uint32_t pose, uint32_t M, uint32_t m, int uniform, float* out12) {
-    const float* mp = poses12 + ((size_t)pose * M + m) * 12;
+// The WORDS words that are read of record (pose, m) of a (P, M, STRIDE) float32 table -- a pose12 (12 of 12) or a mover sweep
+// record (19 of 24) --: through the scalar cache where a wave lies in one pose.
+template <int WORDS, int STRIDE>
+__device__ __forceinline__ void mover_record_load(const float* records, uint32_t pose, uint32_t M, uint32_t m, int uniform, float* out) {
+    const float* mp = records + ((size_t)pose * M + m) * STRIDE;
     if (uniform) {
         cfloat* c = (cfloat*)mp;
 #pragma unroll
-        for (int k = 0; k < 12; ++k) out12[k] = c[k];
+        for (int k = 0; k < WORDS; ++k) out[k] = c[k];
     } else {
 #pragma unroll
-        for (int k = 0; k < 12; ++k) out12[k] = mp[k];
+        for (int k = 0; k < WORDS; ++k) out[k] = mp[k];
     }
 }
+template <bool SWEEP> constexpr int kMoverWords = SWEEP ? 19 : 12;
+template <bool SWEEP> constexpr int kMoverStride = SWEEP ? 24 : 12;
 
-// The ray kernel: one thread per (pose, i) forms gen_ray's bits; the static pass (q.poses12 == NULL) stores them, a mover's pass
-// stores the ray in the mover's frame and the keep byte of the explicit-ray launch (0: left out by lrcmov::culled, no ray stored).
-__global__ __launch_bounds__(kBlock) void mover_rays_kernel(const double* __restrict__ poses16, const double* __restrict__ dirs3,
+// Ray gid of a ray set as three float2 (24-byte records: 8-byte aligned).  T: V3 or lrcmov::Vec.
+template <class T>
+__device__ __forceinline__ void store_ray6(float* rays6, uint64_t gid, T o, T d) {
+    float2* r = (float2*)(rays6 + gid * 6);
+    r[0] = make_float2(o.x, o.y);
+    r[1] = make_float2(o.z, d.x);
+    r[2] = make_float2(d.y, d.z);
+}
+template <class T>
+__device__ __forceinline__ void load_ray6(const float* rays6, uint64_t gid, T& o, T& d) {
+    const float2* r = (const float2*)(rays6 + gid * 6);
+    const float2 a = r[0], b = r[1], c = r[2];
+    o = T{a.x, a.y, b.x};
+    d = T{b.y, c.x, c.y};
+}
+
+// The ray kernel: one thread per (pose, i).  The static pass (q.records == NULL) forms the variant's generator's bits and stores
+// them: the clean non-sweep variant straight as the rays to cast, the other three as the world ray set (world6), the noisy ones
+// with the ray's live byte -- the one Philox block for the jitter and the dropout, the one float64 chain.  A mover's pass takes
+// the world ray into the mover's frame and stores it with the keep byte of the explicit-ray launch (0: dropped, or left out by
+// lrcmov::culled; no ray stored).  The three variants that stored the world ray read it back (no float64 chain, no division per
+// mover); the clean non-sweep variant has no world6 and forms gen_ray's bits again.  The zero tests are on kernel arguments.
+// Side by side, and kept: only the noisy sweep static pass zeroes a dropped ray's stored ray; the noisy non-sweep one stores
+// what the generator left.
+template <bool SWEEP, bool NOISY>
+__global__ __launch_bounds__(kBlock) void mover_rays_kernel(const double* __restrict__ sensor, const double* __restrict__ dirs3,
+                                                            const double* __restrict__ fire, const lrcnoise::Params np,
                                                             uint64_t rays_per_pose, uint64_t total, const lrcmov::RayPass q,
-                                                            int uniform, float* __restrict__ rays6, uint8_t* __restrict__ keep) {
+                                                            int uniform, float* __restrict__ world6, uint8_t* __restrict__ live,
+                                                            float* __restrict__ rays6, uint8_t* __restrict__ keep) {
+    constexpr bool STORED = SWEEP || NOISY;
     const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (gid >= total) return;
     const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
+    const uint64_t i = gid - (uint64_t)pose * rays_per_pose;
+    const bool first = q.records == nullptr;
     V3 o, d;
-    double cx, cy, cz;
-    gen_ray(poses16, dirs3, pose, gid - (uint64_t)pose * rays_per_pose, o, d, cx, cy, cz);
-    lrcmov::Vec ro{o.x, o.y, o.z}, rd{d.x, d.y, d.z};
-    if (q.poses12 != nullptr) {
-        float m12[12];
-        mover_pose_load(q.poses12, pose, q.M, q.m, uniform, m12);
-        lrcmov::to_object(m12, lrcmov::Vec{o.x, o.y, o.z}, lrcmov::Vec{d.x, d.y, d.z}, ro, rd);
-        const bool out = lrcmov::culled(q.sphere, ro, rd);
-        keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
-        if (out) return;
+    if (first || !STORED) {
+        double cx, cy, cz;
+        bool alive = true;
+        if constexpr (SWEEP && NOISY) gen_ray_noisy_sweep(sensor, dirs3, fire, np, pose, i, o, d, alive);
+        else if constexpr (SWEEP) gen_ray_sweep(sensor, dirs3, fire, pose, i, o, d);
+        else if constexpr (NOISY) gen_ray_noisy(sensor, dirs3, np, pose, i, o, d, cx, cy, cz, alive);
+        else gen_ray(sensor, dirs3, pose, i, o, d, cx, cy, cz);
+        if (first) {
+            if constexpr (SWEEP && NOISY) { if (!alive) o = d = V3{0.f, 0.f, 0.f}; }
+            store_ray6(STORED ? world6 : rays6, gid, o, d);
+            if constexpr (NOISY) live[gid] = alive ? (uint8_t)1 : (uint8_t)0;
+            return;
+        }
     }
-    float2* r = (float2*)(rays6 + gid * 6);      // 24-byte records: 8-byte aligned
-    r[0] = make_float2(ro.x, ro.y);
-    r[1] = make_float2(ro.z, rd.x);
-    r[2] = make_float2(rd.y, rd.z);
+    if constexpr (NOISY) {
+        if (live[gid] == 0) {      // dropped: cast against no mover either
+            keep[gid] = 0;
+            return;
+        }
+    }
+    float rec[kMoverWords<SWEEP>];
+    mover_record_load<kMoverWords<SWEEP>, kMoverStride<SWEEP>>(q.records, pose, q.M, q.m, uniform, rec);
+    lrcmov::Vec wo, wd, ro, rd;
+    if constexpr (STORED) {
+        load_ray6(world6, gid, wo, wd);
+    } else {
+        wo = lrcmov::Vec{o.x, o.y, o.z};
+        wd = lrcmov::Vec{d.x, d.y, d.z};
+    }
+    if constexpr (SWEEP) lrcmov::to_object_at(rec, (float)fire[i], wo, wd, ro, rd);
+    else lrcmov::to_object(rec, wo, wd, ro, rd);
+    const bool out = lrcmov::culled(q.sphere, ro, rd);
+    keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
+    if (out) return;
+    store_ray6(rays6, gid, ro, rd);
 }
 
 // The merge kernel's view of one mover's pass: the running winner (the static cast's record set to begin with), this mover's
-// cast, and -- in the last pass -- the caller's record set (p.out) and mover column.
+// cast, and -- in the last pass -- the caller's record set (p.out) and mover column.  p brings the sensor's records, the firing
+// fractions and the model (p.noise).
 struct MoverMerge {
-    const float* poses12;      // (P, M, 12)
+    const float* records;      // (P, M, 12) poses, or (P, M, 24) mover sweep records
+    const float* world6;       // the static pass's world rays; unused by the clean non-sweep variant, which stores none
     uint32_t M, m;
     int uniform, last;
     float* w_t; uint32_t* w_prim; float* w_n3; uint16_t* w_sem; uint16_t* w_ins; uint8_t* w_who;
     const float* m_t; const uint32_t* m_prim; const float* m_n3; const uint16_t* m_sem; const uint16_t* m_ins;
     uint8_t* d_mover;          // nullable
 };
+struct MoverWinner { float t; uint32_t prim, label; V3 n; uint32_t who; };
 
-// One thread per (pose, i): the running winner against mover q.m (lrcmov::takes), the mover's normal turned into the world.  Every
-// pass but the last stores the winner; the last forms gen_ray's bits again and writes the record lrc_scan_poses_dev would write
-// had the ray hit the winner (write_back, GIVEN), filter included, and the mover column.
+// The running winner of ray gid against mover q.m (lrcmov::takes: on the CLEAN ranges; a dropped ray was cast nowhere, +inf
+// throughout), the mover's normal turned into the world by its pose, or by the pose it has at s (`fire`: the firing fractions).
+template <bool SWEEP>
+__device__ __forceinline__ MoverWinner mover_take(const MoverMerge& q, const double* fire, uint64_t gid, uint32_t pose, uint64_t i) {
+    MoverWinner w{q.w_t[gid], q.w_prim[gid], (uint32_t)q.w_sem[gid] | ((uint32_t)q.w_ins[gid] << 16),
+                  V3{q.w_n3[gid * 3], q.w_n3[gid * 3 + 1], q.w_n3[gid * 3 + 2]}, q.w_who[gid]};
+    const float tm = q.m_t[gid];
+    if (lrcmov::takes(tm, w.t)) {
+        float rec[kMoverWords<SWEEP>];
+        mover_record_load<kMoverWords<SWEEP>, kMoverStride<SWEEP>>(q.records, pose, q.M, q.m, q.uniform, rec);
+        const lrcmov::Vec mn{q.m_n3[gid * 3], q.m_n3[gid * 3 + 1], q.m_n3[gid * 3 + 2]};
+        lrcmov::Vec n;
+        if constexpr (SWEEP) n = lrcmov::to_world_at(rec, (float)fire[i], mn);
+        else n = lrcmov::to_world(rec, mn);
+        w.t = tm;
+        w.prim = q.m_prim[gid];
+        w.label = (uint32_t)q.m_sem[gid] | ((uint32_t)q.m_ins[gid] << 16);
+        w.n = V3{n.x, n.y, n.z};
+        w.who = q.m + 1u;
+    }
+    return w;
+}
+__device__ __forceinline__ void winner_store(const MoverMerge& q, uint64_t gid, const MoverWinner& w) {
+    q.w_t[gid] = w.t;
+    q.w_prim[gid] = w.prim;
+    q.w_n3[gid * 3] = w.n.x; q.w_n3[gid * 3 + 1] = w.n.y; q.w_n3[gid * 3 + 2] = w.n.z;
+    q.w_sem[gid] = (uint16_t)(w.label & 0xFFFFu);
+    q.w_ins[gid] = (uint16_t)(w.label >> 16);
+    q.w_who[gid] = (uint8_t)w.who;
+}
+
+// One thread per (pose, i): mover_take; every pass but the last stores the winner.  The last pass writes the record the
+// variant's plain scan (lrc_scan_poses_dev, lrc_scan_noisy_dev, lrc_scan_sweeps_dev, lrc_scan_noisy_sweeps_dev) would write had
+// the ray hit the winner (write_back, GIVEN), filter included, and the mover column.  Its ray and filter centre, side by side and
+// kept as they are: the clean non-sweep variant forms gen_ray's bits again; the others read the stored world ray back, the
+// noisy non-sweep one with the centre from the pose (poses16[3], [7], [11]), the sweep ones with sweep_centre of the sensor's
+// record.  NOISY draws the winner's range (noisy_range of frame first_frame + pose: the ray's second Philox block, only where
+// range_std != 0 and something was hit; a non-positive range is no return).
+template <bool SWEEP, bool NOISY>
 __global__ __launch_bounds__(kBlock) void mover_merge_kernel(const TraceParams p, const MoverMerge q) {
     const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (gid >= p.total) return;
-    float t = q.w_t[gid];
-    uint32_t prim = q.w_prim[gid];
-    uint32_t label = (uint32_t)q.w_sem[gid] | ((uint32_t)q.w_ins[gid] << 16);
-    V3 n{q.w_n3[gid * 3], q.w_n3[gid * 3 + 1], q.w_n3[gid * 3 + 2]};
-    uint32_t who = q.w_who[gid];
     const uint32_t pose = mover_pose_of(gid, p.rays_per_pose, q.uniform);
-    const float tm = q.m_t[gid];
-    if (lrcmov::takes(tm, t)) {
-        float m12[12];
-        mover_pose_load(q.poses12, pose, q.M, q.m, q.uniform, m12);
-        const lrcmov::Vec w = lrcmov::to_world(m12, lrcmov::Vec{q.m_n3[gid * 3], q.m_n3[gid * 3 + 1], q.m_n3[gid * 3 + 2]});
-        t = tm;
-        prim = q.m_prim[gid];
-        label = (uint32_t)q.m_sem[gid] | ((uint32_t)q.m_ins[gid] << 16);
-        n = V3{w.x, w.y, w.z};
-        who = q.m + 1u;
-    }
+    const uint64_t i = gid - (uint64_t)pose * p.rays_per_pose;
+    MoverWinner w = mover_take<SWEEP>(q, p.fire, gid, pose, i);
     if (!q.last) {
-        q.w_t[gid] = t;
-        q.w_prim[gid] = prim;
-        q.w_n3[gid * 3] = n.x; q.w_n3[gid * 3 + 1] = n.y; q.w_n3[gid * 3 + 2] = n.z;
-        q.w_sem[gid] = (uint16_t)(label & 0xFFFFu);
-        q.w_ins[gid] = (uint16_t)(label >> 16);
-        q.w_who[gid] = (uint8_t)who;
+        winner_store(q, gid, w);
         return;
     }
     V3 o, d;
     double cx, cy, cz;
-    gen_ray(p.poses16, p.dirs3, pose, gid - (uint64_t)pose * p.rays_per_pose, o, d, cx, cy, cz);
-    const bool hit = t < __builtin_inff();
-    const bool kept = write_back<true, false, true, false, true>(p, gid, threadIdx.x, o, d, cx, cy, cz, t, hit ? prim : 0xFFFFFFFFu,
-                                                                 label, false, V3{0.f, 0.f, 0.f}, 0.f, n);
-    if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
-}
-
-// ---- seeded sensor noise under movers (lrc_scan_noisy_movers_*; the arithmetic is lrc_movers.h's, gen_ray_noisy's and
-// noisy_range's, the orchestration noisy_movers_scan_dev's) ------------------------------------------------
-// The noisy ray kernel: one thread per (pose, i).  The static pass (q.poses12 == NULL) forms gen_ray_noisy's bits once -- the one
-// Philox block for the jitter and the dropout, the one float64 chain -- and stores them as the world ray with the ray's live
-// byte (0: dropped, never cast).  A mover's pass reads both back, takes the world ray into the mover's frame and stores it with the
-// keep byte of the explicit-ray launch: live && !culled (0: no ray stored).  The zero tests are on kernel arguments.
-__global__ __launch_bounds__(kBlock) void mover_noisy_rays_kernel(const double* __restrict__ poses16, const double* __restrict__ dirs3,
-                                                                  const lrcnoise::Params np, uint64_t rays_per_pose, uint64_t total,
-                                                                  const lrcmov::RayPass q, int uniform, float* __restrict__ world6,
-                                                                  uint8_t* __restrict__ live, float* __restrict__ rays6,
-                                                                  uint8_t* __restrict__ keep) {
-    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= total) return;
-    const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
-    if (q.poses12 == nullptr) {
-        V3 o, d;
-        double cx, cy, cz;
-        bool alive = true;
-        gen_ray_noisy(poses16, dirs3, np, pose, gid - (uint64_t)pose * rays_per_pose, o, d, cx, cy, cz, alive);
-        float2* w = (float2*)(world6 + gid * 6);      // 24-byte records: 8-byte aligned
-        w[0] = make_float2(o.x, o.y);
-        w[1] = make_float2(o.z, d.x);
-        w[2] = make_float2(d.y, d.z);
-        live[gid] = alive ? (uint8_t)1 : (uint8_t)0;
-        return;
-    }
-    if (live[gid] == 0) {      // dropped: cast against no mover either
-        keep[gid] = 0;
-        return;
-    }
-    float m12[12];
-    mover_pose_load(q.poses12, pose, q.M, q.m, uniform, m12);
-    const float2* w = (const float2*)(world6 + gid * 6);
-    const float2 a = w[0], b = w[1], c = w[2];
-    lrcmov::Vec ro, rd;
-    lrcmov::to_object(m12, lrcmov::Vec{a.x, a.y, b.x}, lrcmov::Vec{b.y, c.x, c.y}, ro, rd);
-    const bool out = lrcmov::culled(q.sphere, ro, rd);
-    keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
-    if (out) return;
-    float2* r = (float2*)(rays6 + gid * 6);
-    r[0] = make_float2(ro.x, ro.y);
-    r[1] = make_float2(ro.z, rd.x);
-    r[2] = make_float2(rd.y, rd.z);
-}
-
-// The noisy merge kernel's view of one mover's pass: MoverMerge and the stored world rays.  p.noise is the call's model.
-struct MoverNoisyMerge {
-    const float* poses12;      // (P, M, 12)
-    const float* world6;       // the static pass's world rays
-    uint32_t M, m;
-    int uniform, last;
-    float* w_t; uint32_t* w_prim; float* w_n3; uint16_t* w_sem; uint16_t* w_ins; uint8_t* w_who;
-    const float* m_t; const uint32_t* m_prim; const float* m_n3; const uint16_t* m_sem; const uint16_t* m_ins;
-    uint8_t* d_mover;          // nullable
-};
-
-// One thread per (pose, i): mover_merge_kernel's winner on the CLEAN ranges (a dropped ray was cast nowhere: +inf throughout).
-// The last pass reads the stored world ray back, takes the filter centre from the pose, draws the winner's range (noisy_range:
-// the ray's second Philox block, only where range_std != 0 and something was hit; a non-positive range is no return) and writes the
-// record lrc_scan_noisy_dev would write had the ray hit the winner (write_back, GIVEN), filter included, and the mover column.
-__global__ __launch_bounds__(kBlock) void mover_noisy_merge_kernel(const TraceParams p, const MoverNoisyMerge q) {
-    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= p.total) return;
-    float t = q.w_t[gid];
-    uint32_t prim = q.w_prim[gid];
-    uint32_t label = (uint32_t)q.w_sem[gid] | ((uint32_t)q.w_ins[gid] << 16);
-    V3 n{q.w_n3[gid * 3], q.w_n3[gid * 3 + 1], q.w_n3[gid * 3 + 2]};
-    uint32_t who = q.w_who[gid];
-    const uint32_t pose = mover_pose_of(gid, p.rays_per_pose, q.uniform);
-    const float tm = q.m_t[gid];
-    if (lrcmov::takes(tm, t)) {
-        float m12[12];
-        mover_pose_load(q.poses12, pose, q.M, q.m, q.uniform, m12);
-        const lrcmov::Vec w = lrcmov::to_world(m12, lrcmov::Vec{q.m_n3[gid * 3], q.m_n3[gid * 3 + 1], q.m_n3[gid * 3 + 2]});
-        t = tm;
-        prim = q.m_prim[gid];
-        label = (uint32_t)q.m_sem[gid] | ((uint32_t)q.m_ins[gid] << 16);
-        n = V3{w.x, w.y, w.z};
-        who = q.m + 1u;
-    }
-    if (!q.last) {
-        q.w_t[gid] = t;
-        q.w_prim[gid] = prim;
-        q.w_n3[gid * 3] = n.x; q.w_n3[gid * 3 + 1] = n.y; q.w_n3[gid * 3 + 2] = n.z;
-        q.w_sem[gid] = (uint16_t)(label & 0xFFFFu);
-        q.w_ins[gid] = (uint16_t)(label >> 16);
-        q.w_who[gid] = (uint8_t)who;
-        return;
-    }
-    const float2* wr = (const float2*)(q.world6 + gid * 6);
-    const float2 a = wr[0], b = wr[1], c = wr[2];
-    const V3 o{a.x, a.y, b.x}, d{b.y, c.x, c.y};
-    const double* Mp = p.poses16 + (size_t)pose * 16;
-    const double cx = Mp[3], cy = Mp[7], cz = Mp[11];
-    bool hit = t < __builtin_inff();
-    if (p.noise.range_std != 0.0f && hit) {
-        t = noisy_range(p.noise, p.noise.first_frame + pose, (uint32_t)(gid - (uint64_t)pose * p.rays_per_pose), t);
-        hit = t > 0.0f;
-    }
-    const bool kept = write_back<true, false, true, false, true>(p, gid, threadIdx.x, o, d, cx, cy, cz, t, hit ? prim : 0xFFFFFFFFu,
-                                                                 label, false, V3{0.f, 0.f, 0.f}, 0.f, n);
-    if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
-}
-
-// ---- movers under moving-sensor sweeps (lrc_scan_mover_sweeps_*; the arithmetic is lrc_movers.h's and gen_ray_sweep's, the
-// orchestration mover_sweeps_scan_dev's) ----------------------------------------------------------------------------------
-// The 19 words of mover sweep record (pose, m) that are read: through the scalar cache where a wave lies in one sweep.
-__device__ __forceinline__ void mover_record_load(const float* motion24, uint32_t pose, uint32_t M, uint32_t m, int uniform, float* out19) {
-    const float* mp = motion24 + ((size_t)pose * M + m) * 24;
-    if (uniform) {
-        cfloat* c = (cfloat*)mp;
-#pragma unroll
-        for (int k = 0; k < 19; ++k) out19[k] = c[k];
+    if constexpr (!SWEEP && !NOISY) {
+        gen_ray(p.poses16, p.dirs3, pose, i, o, d, cx, cy, cz);
     } else {
-#pragma unroll
-        for (int k = 0; k < 19; ++k) out19[k] = mp[k];
+        load_ray6(q.world6, gid, o, d);
+        if constexpr (SWEEP) {
+            sweep_centre(p.motion24 + (size_t)pose * 24, p.fire[i], cx, cy, cz);
+        } else {
+            const double* Mp = p.poses16 + (size_t)pose * 16;
+            cx = Mp[3]; cy = Mp[7]; cz = Mp[11];
+        }
     }
-}
-
-// The sweep ray kernel: one thread per (sweep, i).  The static pass (q.motion24 == NULL) forms gen_ray_sweep's bits once and
-// stores them as the world ray; a mover's pass reads that world ray back (no float64 chain, no division per mover), takes it into
-// the frame the mover has at s = (float)fire[i] (lrcmov::to_object_at) and stores it with the keep byte of the explicit-ray launch
-// (0: left out by lrcmov::culled, no ray stored).  The still test of a record is wave-uniform with `uniform`.
-__global__ __launch_bounds__(kBlock) void mover_sweep_rays_kernel(const double* __restrict__ motion24, const double* __restrict__ dirs3,
-                                                                  const double* __restrict__ fire, uint64_t rays_per_pose,
-                                                                  uint64_t total, const lrcmov::SweepRayPass q, int uniform,
-                                                                  float* __restrict__ world6, float* __restrict__ rays6,
-                                                                  uint8_t* __restrict__ keep) {
-    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= total) return;
-    const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
-    const uint64_t i = gid - (uint64_t)pose * rays_per_pose;
-    if (q.motion24 == nullptr) {
-        V3 o, d;
-        gen_ray_sweep(motion24, dirs3, fire, pose, i, o, d);
-        float2* w = (float2*)(world6 + gid * 6);      // 24-byte records: 8-byte aligned
-        w[0] = make_float2(o.x, o.y);
-        w[1] = make_float2(o.z, d.x);
-        w[2] = make_float2(d.y, d.z);
-        return;
+    bool hit = w.t < __builtin_inff();
+    if constexpr (NOISY) {
+        if (p.noise.range_std != 0.0f && hit) {
+            w.t = noisy_range(p.noise, p.noise.first_frame + pose, (uint32_t)i, w.t);
+            hit = w.t > 0.0f;
+        }
     }
-    float r19[19];
-    mover_record_load(q.motion24, pose, q.M, q.m, uniform, r19);
-    const float2* w = (const float2*)(world6 + gid * 6);
-    const float2 a = w[0], b = w[1], c = w[2];
-    lrcmov::Vec ro, rd;
-    lrcmov::to_object_at(r19, (float)fire[i], lrcmov::Vec{a.x, a.y, b.x}, lrcmov::Vec{b.y, c.x, c.y}, ro, rd);
-    const bool out = lrcmov::culled(q.sphere, ro, rd);
-    keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
-    if (out) return;
-    float2* r = (float2*)(rays6 + gid * 6);
-    r[0] = make_float2(ro.x, ro.y);
-    r[1] = make_float2(ro.z, rd.x);
-    r[2] = make_float2(rd.y, rd.z);
-}
-
-// The sweep merge kernel's view of one mover's pass: MoverMerge with the mover sweep records in the place of the poses, and the
-// stored world rays.  p.motion24 / p.fire are the SENSOR's records and the firing fractions.
-struct MoverSweepMerge {
-    const float* motion24;     // (P, M, 24)
-    const float* world6;       // the static pass's world rays
-    uint32_t M, m;
-    int uniform, last;
-    float* w_t; uint32_t* w_prim; float* w_n3; uint16_t* w_sem; uint16_t* w_ins; uint8_t* w_who;
-    const float* m_t; const uint32_t* m_prim; const float* m_n3; const uint16_t* m_sem; const uint16_t* m_ins;
-    uint8_t* d_mover;          // nullable
-};
-
-// One thread per (sweep, i): the running winner against mover q.m (lrcmov::takes), the mover's normal turned into the world by the
-// pose the mover has at s (lrcmov::to_world_at).  Every pass but the last stores the winner; the last writes the record
-// lrc_scan_sweeps_dev would write had the ray hit the winner (write_back, GIVEN: the stored world ray, the filter centre
-// sweep_centre forms from the sensor's record), filter included, and the mover column.
-__global__ __launch_bounds__(kBlock) void mover_sweep_merge_kernel(const TraceParams p, const MoverSweepMerge q) {
-    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= p.total) return;
-    float t = q.w_t[gid];
-    uint32_t prim = q.w_prim[gid];
-    uint32_t label = (uint32_t)q.w_sem[gid] | ((uint32_t)q.w_ins[gid] << 16);
-    V3 n{q.w_n3[gid * 3], q.w_n3[gid * 3 + 1], q.w_n3[gid * 3 + 2]};
-    uint32_t who = q.w_who[gid];
-    const uint32_t pose = mover_pose_of(gid, p.rays_per_pose, q.uniform);
-    const uint64_t i = gid - (uint64_t)pose * p.rays_per_pose;
-    const float tm = q.m_t[gid];
-    if (lrcmov::takes(tm, t)) {
-        float r19[19];
-        mover_record_load(q.motion24, pose, q.M, q.m, q.uniform, r19);
-        const lrcmov::Vec w = lrcmov::to_world_at(r19, (float)p.fire[i], lrcmov::Vec{q.m_n3[gid * 3], q.m_n3[gid * 3 + 1], q.m_n3[gid * 3 + 2]});
-        t = tm;
-        prim = q.m_prim[gid];
-        label = (uint32_t)q.m_sem[gid] | ((uint32_t)q.m_ins[gid] << 16);
-        n = V3{w.x, w.y, w.z};
-        who = q.m + 1u;
-    }
-    if (!q.last) {
-        q.w_t[gid] = t;
-        q.w_prim[gid] = prim;
-        q.w_n3[gid * 3] = n.x; q.w_n3[gid * 3 + 1] = n.y; q.w_n3[gid * 3 + 2] = n.z;
-        q.w_sem[gid] = (uint16_t)(label & 0xFFFFu);
-        q.w_ins[gid] = (uint16_t)(label >> 16);
-        q.w_who[gid] = (uint8_t)who;
-        return;
-    }
-    const float2* wr = (const float2*)(q.world6 + gid * 6);
-    const float2 a = wr[0], b = wr[1], c = wr[2];
-    const V3 o{a.x, a.y, b.x}, d{b.y, c.x, c.y};
-    double cx, cy, cz;
-    sweep_centre(p.motion24 + (size_t)pose * 24, p.fire[i], cx, cy, cz);
-    const bool hit = t < __builtin_inff();
-    const bool kept = write_back<true, false, true, false, true>(p, gid, threadIdx.x, o, d, cx, cy, cz, t, hit ? prim : 0xFFFFFFFFu,
-                                                                 label, false, V3{0.f, 0.f, 0.f}, 0.f, n);
-    if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
-}
-
-// ---- seeded sensor noise under movers in sweeps (lrc_scan_noisy_mover_sweeps_*; the arithmetic is lrc_movers.h's,
-// gen_ray_noisy_sweep's, sweep_centre's and noisy_range's, the orchestration noisy_mover_sweeps_scan_dev's) --
-// The noisy sweep ray kernel: one thread per (sweep, i).  The static pass (q.motion24 == NULL) forms gen_ray_noisy_sweep's bits
-// once -- the one Philox block for the jitter and the dropout, the one float64 chain -- and stores them as the world ray with the
-// ray's live byte (0: dropped, never cast; its stored ray is zeros, not what the generator left).  A mover's pass reads both
-// back, takes the world ray into the frame the mover has at s = (float)fire[i] (the jitter does not touch s) and stores it with
-// the keep byte of the explicit-ray launch: live && !culled (0: no ray stored).  The zero tests are on kernel arguments.
-__global__ __launch_bounds__(kBlock) void mover_noisy_sweep_rays_kernel(const double* __restrict__ motion24,
-                                                                        const double* __restrict__ dirs3,
-                                                                        const double* __restrict__ fire, const lrcnoise::Params np,
-                                                                        uint64_t rays_per_pose, uint64_t total,
-                                                                        const lrcmov::SweepRayPass q, int uniform,
-                                                                        float* __restrict__ world6, uint8_t* __restrict__ live,
-                                                                        float* __restrict__ rays6, uint8_t* __restrict__ keep) {
-    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= total) return;
-    const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
-    const uint64_t i = gid - (uint64_t)pose * rays_per_pose;
-    if (q.motion24 == nullptr) {
-        V3 o, d;
-        bool alive = true;
-        gen_ray_noisy_sweep(motion24, dirs3, fire, np, pose, i, o, d, alive);
-        if (!alive) o = d = V3{0.f, 0.f, 0.f};
-        float2* w = (float2*)(world6 + gid * 6);      // 24-byte records: 8-byte aligned
-        w[0] = make_float2(o.x, o.y);
-        w[1] = make_float2(o.z, d.x);
-        w[2] = make_float2(d.y, d.z);
-        live[gid] = alive ? (uint8_t)1 : (uint8_t)0;
-        return;
-    }
-    if (live[gid] == 0) {      // dropped: cast against no mover either
-        keep[gid] = 0;
-        return;
-    }
-    float r19[19];
-    mover_record_load(q.motion24, pose, q.M, q.m, uniform, r19);
-    const float2* w = (const float2*)(world6 + gid * 6);
-    const float2 a = w[0], b = w[1], c = w[2];
-    lrcmov::Vec ro, rd;
-    lrcmov::to_object_at(r19, (float)fire[i], lrcmov::Vec{a.x, a.y, b.x}, lrcmov::Vec{b.y, c.x, c.y}, ro, rd);
-    const bool out = lrcmov::culled(q.sphere, ro, rd);
-    keep[gid] = out ? (uint8_t)0 : (uint8_t)1;
-    if (out) return;
-    float2* r = (float2*)(rays6 + gid * 6);
-    r[0] = make_float2(ro.x, ro.y);
-    r[1] = make_float2(ro.z, rd.x);
-    r[2] = make_float2(rd.y, rd.z);
-}
-
-// One thread per (sweep, i): mover_sweep_merge_kernel's winner on the CLEAN ranges (a dropped ray was cast nowhere: +inf
-// throughout), over MoverSweepMerge's view.  The last pass reads the stored world ray back, takes the filter centre from the
-// sensor's record (sweep_centre), draws the winner's range (noisy_range of frame first_frame + sweep: the ray's second Philox
-// block, only where range_std != 0 and something was hit; a non-positive range is no return) and writes the record
-// lrc_scan_noisy_sweeps_dev would write had the ray hit the winner (write_back, GIVEN), filter included, and the mover column.
-__global__ __launch_bounds__(kBlock) void mover_noisy_sweep_merge_kernel(const TraceParams p, const MoverSweepMerge q) {
-    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= p.total) return;
-    float t = q.w_t[gid];
-    uint32_t prim = q.w_prim[gid];
-    uint32_t label = (uint32_t)q.w_sem[gid] | ((uint32_t)q.w_ins[gid] << 16);
-    V3 n{q.w_n3[gid * 3], q.w_n3[gid * 3 + 1], q.w_n3[gid * 3 + 2]};
-    uint32_t who = q.w_who[gid];
-    const uint32_t pose = mover_pose_of(gid, p.rays_per_pose, q.uniform);
-    const uint64_t i = gid - (uint64_t)pose * p.rays_per_pose;
-    const float tm = q.m_t[gid];
-    if (lrcmov::takes(tm, t)) {
-        float r19[19];
-        mover_record_load(q.motion24, pose, q.M, q.m, q.uniform, r19);
-        const lrcmov::Vec w = lrcmov::to_world_at(r19, (float)p.fire[i], lrcmov::Vec{q.m_n3[gid * 3], q.m_n3[gid * 3 + 1], q.m_n3[gid * 3 + 2]});
-        t = tm;
-        prim = q.m_prim[gid];
-        label = (uint32_t)q.m_sem[gid] | ((uint32_t)q.m_ins[gid] << 16);
-        n = V3{w.x, w.y, w.z};
-        who = q.m + 1u;
-    }
-    if (!q.last) {
-        q.w_t[gid] = t;
-        q.w_prim[gid] = prim;
-        q.w_n3[gid * 3] = n.x; q.w_n3[gid * 3 + 1] = n.y; q.w_n3[gid * 3 + 2] = n.z;
-        q.w_sem[gid] = (uint16_t)(label & 0xFFFFu);
-        q.w_ins[gid] = (uint16_t)(label >> 16);
-        q.w_who[gid] = (uint8_t)who;
-        return;
-    }
-    const float2* wr = (const float2*)(q.world6 + gid * 6);
-    const float2 a = wr[0], b = wr[1], c = wr[2];
-    const V3 o{a.x, a.y, b.x}, d{b.y, c.x, c.y};
-    double cx, cy, cz;
-    sweep_centre(p.motion24 + (size_t)pose * 24, p.fire[i], cx, cy, cz);
-    bool hit = t < __builtin_inff();
-    if (p.noise.range_std != 0.0f && hit) {
-        t = noisy_range(p.noise, p.noise.first_frame + pose, (uint32_t)i, t);
-        hit = t > 0.0f;
-    }
-    const bool kept = write_back<true, false, true, false, true>(p, gid, threadIdx.x, o, d, cx, cy, cz, t, hit ? prim : 0xFFFFFFFFu,
-                                                                 label, false, V3{0.f, 0.f, 0.f}, 0.f, n);
-    if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)who : (uint8_t)0;
+    const bool kept = write_back<true, false, true, false, true>(p, gid, threadIdx.x, o, d, cx, cy, cz, w.t, hit ? w.prim : 0xFFFFFFFFu,
+                                                                 w.label, false, V3{0.f, 0.f, 0.f}, 0.f, w.n);
+    if (q.d_mover) q.d_mover[gid] = kept ? (uint8_t)w.who : (uint8_t)0;
 }
 
 // ---- scene flow under movers (lrc_scan_flow_*; the arithmetic is lrc_flow.h's, the orchestration flow_scan_dev's) -------------
@@ -964,7 +747,7 @@ __global__ __launch_bounds__(kBlock) void flow_object_rays_kernel(const float* _
     if (gid >= total) return;
     const uint32_t pose = mover_pose_of(gid, rays_per_pose, uniform);
     float m12[12];
-    mover_pose_load(q.poses12, pose, q.M, q.m, uniform, m12);
+    mover_record_load<12, 12>(q.records, pose, q.M, q.m, uniform, m12);
     bool out = cast[gid] == 0;
     lrcmov::Vec ro{0.f, 0.f, 0.f}, rd{0.f, 0.f, 0.f};
     if (!out) {
@@ -4512,7 +4295,7 @@ int material_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const
     return guard.done(rc);
 }
 
-// ---- moving objects: lrc_scan_movers_* behind their checks (lrc_movers.hip; declared in lrc_internal.h) -----------------------
+// ---- moving objects: the four lrc_scan_*movers*_dev calls behind their checks (lrc_movers.hip; declared in lrc_internal.h) ----
 namespace {
 // The explicit-ray launch as lrc_cast_dev makes it with no centre and no filter, whatever options the scene carries: the
 // ranges the merge compares are taken before any filter.  d_keep: nullable, 0 = the ray is not cast (a miss).
@@ -4527,343 +4310,109 @@ int cast_plain(lrc_scene* sc, const float* d_rays6, const uint8_t* d_keep, uint6
     sc->opts = saved;
     return rc;
 }
+
+// The scratch of the mover and flow scans: `count` columns of width[k] bytes per ray for n rays, each 256-byte aligned, column k
+// at off[k].  A block that is too small is replaced by one an eighth larger than is needed.
+int scratch_columns(void*& block, uint64_t& cap, uint64_t n, const uint32_t* width, int count, uint64_t* off) {
+    uint64_t end = 0;
+    for (int k = 0; k < count; ++k) {
+        off[k] = end;
+        end += (n * width[k] + 255u) & ~(uint64_t)255u;
+    }
+    if (cap < end) {
+        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
+        if (block) { (void)hipFree(block); block = nullptr; cap = 0; }
+        LRC_HIP(hipMalloc(&block, end + end / 8));
+        cap = end + end / 8;
+    }
+    return LRC_OK;
+}
 }  // namespace
 
-// All on `st`, nothing waited for.  A NULL set: the launch of lrc_scan_poses_dev and a zero mover column.  Otherwise
-//   the static pass    mover_rays_kernel (the world rays) and the explicit-ray launch on the scene, into the winner's columns
-//   per mover m        mover_rays_kernel (object-frame rays + keep bytes), the explicit-ray launch on the mover's scene, and
-//                      mover_merge_kernel, whose last pass writes the caller's records
-// in the set's scratch, which holds one ray set, one keep column and two record sets (winner, mover) whatever M is.
-int movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
-                    const float* d_mover_poses12, double max_range, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st) {
-    const uint64_t n = P * N;
+// All on `st`, nothing waited for.  c.fire selects SWEEP and c.noise NOISY (the kernels' two switches).  A NULL set: the launch of
+// the variant's plain scan (lrc_scan_poses_dev, lrc_scan_noisy_dev, lrc_scan_sweeps_dev, lrc_scan_noisy_sweeps_dev) and a zero
+// mover column.  Otherwise
+//   the static pass    mover_rays_kernel (the world rays; NOISY: and the live bytes) and the explicit-ray launch on the scene
+//                      (NOISY: under the live bytes, a dropped ray is never cast), into the winner's columns
+//   per mover m        mover_rays_kernel (object-frame rays + keep bytes), the explicit-ray launch on the mover's scene -- or,
+//                      under SWEEP for the scene of a spanned deformable, the per-ray-shape cast of lrc_span.hip (span_cast: the
+//                      same five columns, the same firing fractions) --, and mover_merge_kernel, whose
+//                      last pass writes the caller's records
+// in the set's scratch, which holds one ray set, one keep column and two record sets (winner, mover) whatever M is: 74 bytes per
+// ray, and in front of them the stored world ray set unless the scan is neither SWEEP nor NOISY (+24) and NOISY's live column (+1).
+int movers_scan_dev(lrc_scene* s, lrc_movers* set, const MoverScan& c, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st) {
+    const bool sweep = c.fire != nullptr, noisy = c.noise != nullptr, stored = sweep || noisy;
+    const uint64_t N = c.N, n = c.P * N;
     if (!n) return LRC_OK;
+    const lrcnoise::Params np = noisy ? *c.noise : lrcnoise::Params{};
+    TraceParams p{};       // what the plain scan, write_back and the range draw read: the scan's inputs, the model, the filter, the caller's records
+    p.noise = np;
+    (sweep ? p.motion24 : p.poses16) = c.sensor;
+    p.dirs3 = c.dirs3;
+    p.fire = c.fire;
+    scan_fields(p, N, n, c.max_range, d_out);
+    int rc;
     if (!set) {
-        TraceParams p{};
-        p.poses16 = d_poses16;
-        p.dirs3 = d_dirs3;
-        scan_fields(p, N, n, max_range, d_out);
-        const int rc = launch_trace(s, p, kGenPoses, st);
-        if (rc) return rc;
+        if ((rc = launch_trace(s, p, sweep ? (noisy ? kGenNoisySweeps : kGenSweeps) : (noisy ? kGenNoisy : kGenPoses), st))) return rc;
         if (d_mover) LRC_HIP(hipMemsetAsync(d_mover, 0, n, st));
         return LRC_OK;
     }
-    if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers: too many poses or rays for one call");
-    // scratch, 256-byte aligned columns: rays6 | keep | winner (t, prim, normal3, sem, ins, who) | mover (t, prim, normal3, sem, ins)
-    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
-    const uint64_t sizes[13] = {n * 24, n, n * 4, n * 4, n * 12, n * 2, n * 2, n, n * 4, n * 4, n * 12, n * 2, n * 2};
-    uint64_t off[14] = {0};
-    for (int k = 0; k < 13; ++k) off[k + 1] = off[k] + al(sizes[k]);
-    if (set->scratch_cap < off[13]) {
-        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
-        if (set->scratch) { (void)hipFree(set->scratch); set->scratch = nullptr; set->scratch_cap = 0; }
-        LRC_HIP(hipMalloc(&set->scratch, off[13] + off[13] / 8));
-        set->scratch_cap = off[13] + off[13] / 8;
-    }
+    if (c.P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, std::string("lrc_scan_") + (noisy ? "noisy_" : "") +
+                                             (sweep ? "mover_sweeps: too many sweeps" : "movers: too many poses") + " or rays for one call");
+    // scratch columns: [world6] | [live] | rays6 | keep | winner (t, prim, normal3, sem, ins, who) | mover (t, prim, normal3, sem, ins)
+    uint32_t width[15];
+    int cols = 0;
+    if (stored) width[cols++] = 24;
+    if (noisy) width[cols++] = 1;
+    const int first = cols;
+    for (uint32_t bytes : {24u, 1u, 4u, 4u, 12u, 2u, 2u, 1u, 4u, 4u, 12u, 2u, 2u}) width[cols++] = bytes;
+    uint64_t off[15];
+    if ((rc = scratch_columns(set->scratch, set->scratch_cap, n, width, cols, off))) return rc;
     uint8_t* const b = (uint8_t*)set->scratch;
-    float* const rays6 = (float*)(b + off[0]);
-    uint8_t* const keep = b + off[1];
+    float* const world6 = stored ? (float*)(b + off[0]) : nullptr;
+    uint8_t* const live = noisy ? b + off[1] : nullptr;
+    const uint64_t* const o = off + first;
+    float* const rays6 = (float*)(b + o[0]);
+    uint8_t* const keep = b + o[1];
     lrc_hits w{}, mv{};
-    w.t = (float*)(b + off[2]); w.prim = (uint32_t*)(b + off[3]); w.normal3 = (float*)(b + off[4]);
-    w.sem = (uint16_t*)(b + off[5]); w.ins = (uint16_t*)(b + off[6]);
-    uint8_t* const who = b + off[7];
-    mv.t = (float*)(b + off[8]); mv.prim = (uint32_t*)(b + off[9]); mv.normal3 = (float*)(b + off[10]);
-    mv.sem = (uint16_t*)(b + off[11]); mv.ins = (uint16_t*)(b + off[12]);
+    w.t = (float*)(b + o[2]); w.prim = (uint32_t*)(b + o[3]); w.normal3 = (float*)(b + o[4]);
+    w.sem = (uint16_t*)(b + o[5]); w.ins = (uint16_t*)(b + o[6]);
+    uint8_t* const who = b + o[7];
+    mv.t = (float*)(b + o[8]); mv.prim = (uint32_t*)(b + o[9]); mv.normal3 = (float*)(b + o[10]);
+    mv.sem = (uint16_t*)(b + o[11]); mv.ins = (uint16_t*)(b + o[12]);
+    auto* const rays_kernel = sweep ? (noisy ? mover_rays_kernel<true, true> : mover_rays_kernel<true, false>)
+                                    : (noisy ? mover_rays_kernel<false, true> : mover_rays_kernel<false, false>);
+    auto* const merge_kernel = sweep ? (noisy ? mover_merge_kernel<true, true> : mover_merge_kernel<true, false>)
+                                     : (noisy ? mover_merge_kernel<false, true> : mover_merge_kernel<false, false>);
     const dim3 grid((uint32_t)blocks_of(n, kBlock));
     const int uniform = N % 64 == 0;
     const uint32_t M = (uint32_t)set->scenes.size();
-    int rc;
     lrcmov::RayPass rp{};
-    hipLaunchKernelGGL(mover_rays_kernel, grid, dim3(kBlock), 0, st, d_poses16, d_dirs3, N, n, rp, uniform, rays6, keep);
+    hipLaunchKernelGGL(rays_kernel, grid, dim3(kBlock), 0, st, c.sensor, c.dirs3, c.fire, np, N, n, rp, uniform, world6, live, rays6, keep);
     LRC_HIP(hipGetLastError());
-    if ((rc = cast_plain(s, rays6, nullptr, n, w, st))) return rc;
+    if ((rc = cast_plain(s, stored ? world6 : rays6, live, n, w, st))) return rc;
     LRC_HIP(hipMemsetAsync(who, 0, n, st));
-    TraceParams p{};       // what write_back reads: the scan's inputs, the filter, the scene's options, the caller's records
-    p.poses16 = d_poses16;
-    p.dirs3 = d_dirs3;
-    scan_fields(p, N, n, max_range, d_out);
-    p.min_range = s->opts.min_range;
+    p.min_range = s->opts.min_range;       // the scene's options, as launch_trace would set them
     p.incident_mode = s->opts.incident_mode;
     for (uint32_t m = 0; m < M; ++m) {
         lrc_scene* const ms = set->scenes[m];
-        rp.poses12 = d_mover_poses12;
+        rp.records = c.movers;
         rp.M = M;
         rp.m = m;
         rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
-        hipLaunchKernelGGL(mover_rays_kernel, grid, dim3(kBlock), 0, st, d_poses16, d_dirs3, N, n, rp, uniform, rays6, keep);
+        hipLaunchKernelGGL(rays_kernel, grid, dim3(kBlock), 0, st, c.sensor, c.dirs3, c.fire, np, N, n, rp, uniform, world6, live, rays6, keep);
         LRC_HIP(hipGetLastError());
-        if ((rc = cast_plain(ms, rays6, keep, n, mv, st))) return rc;
+        // under SWEEP a spanned deformable (lrc_deform_span_dev) is met per ray at the shape of the ray's own s (lrc_span.hip)
+        if ((rc = (sweep && ms->deform && ms->deform->spanned) ? span_cast(ms->deform, rays6, keep, c.fire, N, n, mv, st)
+                                                                : cast_plain(ms, rays6, keep, n, mv, st)))
+            return rc;
         MoverMerge q{};
-        q.poses12 = d_mover_poses12; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
+        q.records = c.movers; q.world6 = world6; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
         q.w_t = w.t; q.w_prim = w.prim; q.w_n3 = w.normal3; q.w_sem = w.sem; q.w_ins = w.ins; q.w_who = who;
         q.m_t = mv.t; q.m_prim = mv.prim; q.m_n3 = mv.normal3; q.m_sem = mv.sem; q.m_ins = mv.ins;
         q.d_mover = d_mover;
-        hipLaunchKernelGGL(mover_merge_kernel, grid, dim3(kBlock), 0, st, p, q);
-        LRC_HIP(hipGetLastError());
-    }
-    return LRC_OK;
-}
-
-// movers_scan_dev under seeded sensor noise.  A NULL set: the launch of lrc_scan_noisy_dev and a zero mover column.  Otherwise
-//   the static pass    mover_noisy_rays_kernel (gen_ray_noisy's world rays and live bytes, stored) and the explicit-ray launch on
-//                      the scene under the live bytes: a dropped ray is never cast
-//   per mover m        mover_noisy_rays_kernel (the stored world ray in the mover's frame + keep bytes: live && !culled), the
-//                      explicit-ray launch on the mover's scene, and mover_noisy_merge_kernel, whose last pass draws the range
-//                      and writes the records
-// in the set's scratch: what movers_scan_dev holds there plus the world ray set and the live column (25 bytes per ray), grown
-// under the same rule.
-int noisy_movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
-                          const float* d_mover_poses12, double max_range, const lrcnoise::Params& np, const lrc_hits* d_out,
-                          uint8_t* d_mover, hipStream_t st) {
-    const uint64_t n = P * N;
-    if (!n) return LRC_OK;
-    if (!set) {
-        TraceParams p{};
-        p.noise = np;
-        p.poses16 = d_poses16;
-        p.dirs3 = d_dirs3;
-        scan_fields(p, N, n, max_range, d_out);
-        const int rc = launch_trace(s, p, kGenNoisy, st);
-        if (rc) return rc;
-        if (d_mover) LRC_HIP(hipMemsetAsync(d_mover, 0, n, st));
-        return LRC_OK;
-    }
-    if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_movers: too many poses or rays for one call");
-    // scratch, 256-byte aligned columns: world6 | live | rays6 | keep | winner (t, prim, normal3, sem, ins, who) | mover (t, prim, normal3, sem, ins)
-    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
-    const uint64_t sizes[15] = {n * 24, n, n * 24, n, n * 4, n * 4, n * 12, n * 2, n * 2, n, n * 4, n * 4, n * 12, n * 2, n * 2};
-    uint64_t off[16] = {0};
-    for (int k = 0; k < 15; ++k) off[k + 1] = off[k] + al(sizes[k]);
-    if (set->scratch_cap < off[15]) {
-        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
-        if (set->scratch) { (void)hipFree(set->scratch); set->scratch = nullptr; set->scratch_cap = 0; }
-        LRC_HIP(hipMalloc(&set->scratch, off[15] + off[15] / 8));
-        set->scratch_cap = off[15] + off[15] / 8;
-    }
-    uint8_t* const b = (uint8_t*)set->scratch;
-    float* const world6 = (float*)(b + off[0]);
-    uint8_t* const live = b + off[1];
-    float* const rays6 = (float*)(b + off[2]);
-    uint8_t* const keep = b + off[3];
-    lrc_hits w{}, mv{};
-    w.t = (float*)(b + off[4]); w.prim = (uint32_t*)(b + off[5]); w.normal3 = (float*)(b + off[6]);
-    w.sem = (uint16_t*)(b + off[7]); w.ins = (uint16_t*)(b + off[8]);
-    uint8_t* const who = b + off[9];
-    mv.t = (float*)(b + off[10]); mv.prim = (uint32_t*)(b + off[11]); mv.normal3 = (float*)(b + off[12]);
-    mv.sem = (uint16_t*)(b + off[13]); mv.ins = (uint16_t*)(b + off[14]);
-    const dim3 grid((uint32_t)blocks_of(n, kBlock));
-    const int uniform = N % 64 == 0;
-    const uint32_t M = (uint32_t)set->scenes.size();
-    int rc;
-    lrcmov::RayPass rp{};
-    hipLaunchKernelGGL(mover_noisy_rays_kernel, grid, dim3(kBlock), 0, st, d_poses16, d_dirs3, np, N, n, rp, uniform, world6, live,
-                       rays6, keep);
-    LRC_HIP(hipGetLastError());
-    if ((rc = cast_plain(s, world6, live, n, w, st))) return rc;
-    LRC_HIP(hipMemsetAsync(who, 0, n, st));
-    TraceParams p{};       // what write_back and the range draw read: the scan's inputs, the model, the filter, the scene's options, the caller's records
-    p.noise = np;
-    p.poses16 = d_poses16;
-    p.dirs3 = d_dirs3;
-    scan_fields(p, N, n, max_range, d_out);
-    p.min_range = s->opts.min_range;
-    p.incident_mode = s->opts.incident_mode;
-    for (uint32_t m = 0; m < M; ++m) {
-        lrc_scene* const ms = set->scenes[m];
-        rp.poses12 = d_mover_poses12;
-        rp.M = M;
-        rp.m = m;
-        rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
-        hipLaunchKernelGGL(mover_noisy_rays_kernel, grid, dim3(kBlock), 0, st, d_poses16, d_dirs3, np, N, n, rp, uniform, world6,
-                           live, rays6, keep);
-        LRC_HIP(hipGetLastError());
-        if ((rc = cast_plain(ms, rays6, keep, n, mv, st))) return rc;
-        MoverNoisyMerge q{};
-        q.poses12 = d_mover_poses12; q.world6 = world6; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
-        q.w_t = w.t; q.w_prim = w.prim; q.w_n3 = w.normal3; q.w_sem = w.sem; q.w_ins = w.ins; q.w_who = who;
-        q.m_t = mv.t; q.m_prim = mv.prim; q.m_n3 = mv.normal3; q.m_sem = mv.sem; q.m_ins = mv.ins;
-        q.d_mover = d_mover;
-        hipLaunchKernelGGL(mover_noisy_merge_kernel, grid, dim3(kBlock), 0, st, p, q);
-        LRC_HIP(hipGetLastError());
-    }
-    return LRC_OK;
-}
-
-// movers_scan_dev under moving-sensor sweeps.  A NULL set: the launch of lrc_scan_sweeps_dev and a zero mover column.  Otherwise
-//   the static pass    mover_sweep_rays_kernel (gen_ray_sweep's world rays, stored) and the explicit-ray launch on the scene
-//   per mover m        mover_sweep_rays_kernel (the stored world ray in the frame the mover has at the ray's s + keep bytes), the
-//                      explicit-ray launch on the mover's scene -- or, for the scene of a spanned deformable, the per-ray-shape
-//                      cast of lrc_span.hip (span_cast: the same five columns) --, and
-//                      mover_sweep_merge_kernel, whose last pass writes the records
-// in the set's scratch: what movers_scan_dev holds there plus the world ray set (24 bytes per ray), grown under the same rule.
-int mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
-                          const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range, const lrc_hits* d_out,
-                          uint8_t* d_mover, hipStream_t st) {
-    const uint64_t n = P * N;
-    if (!n) return LRC_OK;
-    if (!set) {
-        TraceParams p{};
-        p.motion24 = d_motion24;
-        p.dirs3 = d_dirs3;
-        p.fire = d_fire;
-        scan_fields(p, N, n, max_range, d_out);
-        const int rc = launch_trace(s, p, kGenSweeps, st);
-        if (rc) return rc;
-        if (d_mover) LRC_HIP(hipMemsetAsync(d_mover, 0, n, st));
-        return LRC_OK;
-    }
-    if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_mover_sweeps: too many sweeps or rays for one call");
-    // scratch, 256-byte aligned columns: world6 | rays6 | keep | winner (t, prim, normal3, sem, ins, who) | mover (t, prim, normal3, sem, ins)
-    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
-    const uint64_t sizes[14] = {n * 24, n * 24, n, n * 4, n * 4, n * 12, n * 2, n * 2, n, n * 4, n * 4, n * 12, n * 2, n * 2};
-    uint64_t off[15] = {0};
-    for (int k = 0; k < 14; ++k) off[k + 1] = off[k] + al(sizes[k]);
-    if (set->scratch_cap < off[14]) {
-        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
-        if (set->scratch) { (void)hipFree(set->scratch); set->scratch = nullptr; set->scratch_cap = 0; }
-        LRC_HIP(hipMalloc(&set->scratch, off[14] + off[14] / 8));
-        set->scratch_cap = off[14] + off[14] / 8;
-    }
-    uint8_t* const b = (uint8_t*)set->scratch;
-    float* const world6 = (float*)(b + off[0]);
-    float* const rays6 = (float*)(b + off[1]);
-    uint8_t* const keep = b + off[2];
-    lrc_hits w{}, mv{};
-    w.t = (float*)(b + off[3]); w.prim = (uint32_t*)(b + off[4]); w.normal3 = (float*)(b + off[5]);
-    w.sem = (uint16_t*)(b + off[6]); w.ins = (uint16_t*)(b + off[7]);
-    uint8_t* const who = b + off[8];
-    mv.t = (float*)(b + off[9]); mv.prim = (uint32_t*)(b + off[10]); mv.normal3 = (float*)(b + off[11]);
-    mv.sem = (uint16_t*)(b + off[12]); mv.ins = (uint16_t*)(b + off[13]);
-    const dim3 grid((uint32_t)blocks_of(n, kBlock));
-    const int uniform = N % 64 == 0;
-    const uint32_t M = (uint32_t)set->scenes.size();
-    int rc;
-    lrcmov::SweepRayPass rp{};
-    hipLaunchKernelGGL(mover_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, N, n, rp, uniform, world6,
-                       rays6, keep);
-    LRC_HIP(hipGetLastError());
-    if ((rc = cast_plain(s, world6, nullptr, n, w, st))) return rc;
-    LRC_HIP(hipMemsetAsync(who, 0, n, st));
-    TraceParams p{};       // what write_back reads: the sweep's inputs, the filter, the scene's options, the caller's records
-    p.motion24 = d_motion24;
-    p.dirs3 = d_dirs3;
-    p.fire = d_fire;
-    scan_fields(p, N, n, max_range, d_out);
-    p.min_range = s->opts.min_range;
-    p.incident_mode = s->opts.incident_mode;
-    for (uint32_t m = 0; m < M; ++m) {
-        lrc_scene* const ms = set->scenes[m];
-        rp.motion24 = d_mover_motion24;
-        rp.M = M;
-        rp.m = m;
-        rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
-        hipLaunchKernelGGL(mover_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, N, n, rp, uniform, world6,
-                           rays6, keep);
-        LRC_HIP(hipGetLastError());
-        // a spanned deformable (lrc_deform_span_dev) is met per ray at the shape of the ray's own s (lrc_span.hip)
-        if ((rc = (ms->deform && ms->deform->spanned) ? span_cast(ms->deform, rays6, keep, d_fire, N, n, mv, st)
-                                                       : cast_plain(ms, rays6, keep, n, mv, st)))
-            return rc;
-        MoverSweepMerge q{};
-        q.motion24 = d_mover_motion24; q.world6 = world6; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
-        q.w_t = w.t; q.w_prim = w.prim; q.w_n3 = w.normal3; q.w_sem = w.sem; q.w_ins = w.ins; q.w_who = who;
-        q.m_t = mv.t; q.m_prim = mv.prim; q.m_n3 = mv.normal3; q.m_sem = mv.sem; q.m_ins = mv.ins;
-        q.d_mover = d_mover;
-        hipLaunchKernelGGL(mover_sweep_merge_kernel, grid, dim3(kBlock), 0, st, p, q);
-        LRC_HIP(hipGetLastError());
-    }
-    return LRC_OK;
-}
-
-// mover_sweeps_scan_dev under seeded sensor noise.  A NULL set: the launch of lrc_scan_noisy_sweeps_dev and a zero mover column.
-// Otherwise
-//   the static pass    mover_noisy_sweep_rays_kernel (gen_ray_noisy_sweep's world rays and live bytes, stored) and the
-//                      explicit-ray launch on the scene under the live bytes: a dropped ray is never cast
-//   per mover m        mover_noisy_sweep_rays_kernel (the stored world ray in the frame the mover has at the ray's s + keep
-//                      bytes: live && !culled), the explicit-ray launch on the mover's scene -- or span_cast for the scene of a
-//                      spanned deformable, with the same firing fractions: the jitter does not touch s --, and
-//                      mover_noisy_sweep_merge_kernel, whose last pass draws the range and writes the records
-// in the set's scratch, laid out as noisy_movers_scan_dev lays it out (123 bytes per ray), grown under the same rule.
-int noisy_mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
-                                const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range,
-                                const lrcnoise::Params& np, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st) {
-    const uint64_t n = P * N;
-    if (!n) return LRC_OK;
-    if (!set) {
-        TraceParams p{};
-        p.noise = np;
-        p.motion24 = d_motion24;
-        p.dirs3 = d_dirs3;
-        p.fire = d_fire;
-        scan_fields(p, N, n, max_range, d_out);
-        const int rc = launch_trace(s, p, kGenNoisySweeps, st);
-        if (rc) return rc;
-        if (d_mover) LRC_HIP(hipMemsetAsync(d_mover, 0, n, st));
-        return LRC_OK;
-    }
-    if (P > 0xFFFFFFFFull || blocks_of(n, kBlock) > 0x7FFFFFFFull)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_noisy_mover_sweeps: too many sweeps or rays for one call");
-    // scratch, 256-byte aligned columns: world6 | live | rays6 | keep | winner (t, prim, normal3, sem, ins, who) | mover (t, prim, normal3, sem, ins)
-    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
-    const uint64_t sizes[15] = {n * 24, n, n * 24, n, n * 4, n * 4, n * 12, n * 2, n * 2, n, n * 4, n * 4, n * 12, n * 2, n * 2};
-    uint64_t off[16] = {0};
-    for (int k = 0; k < 15; ++k) off[k + 1] = off[k] + al(sizes[k]);
-    if (set->scratch_cap < off[15]) {
-        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
-        if (set->scratch) { (void)hipFree(set->scratch); set->scratch = nullptr; set->scratch_cap = 0; }
-        LRC_HIP(hipMalloc(&set->scratch, off[15] + off[15] / 8));
-        set->scratch_cap = off[15] + off[15] / 8;
-    }
-    uint8_t* const b = (uint8_t*)set->scratch;
-    float* const world6 = (float*)(b + off[0]);
-    uint8_t* const live = b + off[1];
-    float* const rays6 = (float*)(b + off[2]);
-    uint8_t* const keep = b + off[3];
-    lrc_hits w{}, mv{};
-    w.t = (float*)(b + off[4]); w.prim = (uint32_t*)(b + off[5]); w.normal3 = (float*)(b + off[6]);
-    w.sem = (uint16_t*)(b + off[7]); w.ins = (uint16_t*)(b + off[8]);
-    uint8_t* const who = b + off[9];
-    mv.t = (float*)(b + off[10]); mv.prim = (uint32_t*)(b + off[11]); mv.normal3 = (float*)(b + off[12]);
-    mv.sem = (uint16_t*)(b + off[13]); mv.ins = (uint16_t*)(b + off[14]);
-    const dim3 grid((uint32_t)blocks_of(n, kBlock));
-    const int uniform = N % 64 == 0;
-    const uint32_t M = (uint32_t)set->scenes.size();
-    int rc;
-    lrcmov::SweepRayPass rp{};
-    hipLaunchKernelGGL(mover_noisy_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, np, N, n, rp, uniform,
-                       world6, live, rays6, keep);
-    LRC_HIP(hipGetLastError());
-    if ((rc = cast_plain(s, world6, live, n, w, st))) return rc;
-    LRC_HIP(hipMemsetAsync(who, 0, n, st));
-    TraceParams p{};       // what write_back and the range draw read: the sweep's inputs, the model, the filter, the scene's options, the caller's records
-    p.noise = np;
-    p.motion24 = d_motion24;
-    p.dirs3 = d_dirs3;
-    p.fire = d_fire;
-    scan_fields(p, N, n, max_range, d_out);
-    p.min_range = s->opts.min_range;
-    p.incident_mode = s->opts.incident_mode;
-    for (uint32_t m = 0; m < M; ++m) {
-        lrc_scene* const ms = set->scenes[m];
-        rp.motion24 = d_mover_motion24;
-        rp.M = M;
-        rp.m = m;
-        rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
-        hipLaunchKernelGGL(mover_noisy_sweep_rays_kernel, grid, dim3(kBlock), 0, st, d_motion24, d_dirs3, d_fire, np, N, n, rp,
-                           uniform, world6, live, rays6, keep);
-        LRC_HIP(hipGetLastError());
-        if ((rc = (ms->deform && ms->deform->spanned) ? span_cast(ms->deform, rays6, keep, d_fire, N, n, mv, st)
-                                                       : cast_plain(ms, rays6, keep, n, mv, st)))
-            return rc;
-        MoverSweepMerge q{};
-        q.motion24 = d_mover_motion24; q.world6 = world6; q.M = M; q.m = m; q.uniform = uniform; q.last = m + 1 == M;
-        q.w_t = w.t; q.w_prim = w.prim; q.w_n3 = w.normal3; q.w_sem = w.sem; q.w_ins = w.ins; q.w_who = who;
-        q.m_t = mv.t; q.m_prim = mv.prim; q.m_n3 = mv.normal3; q.m_sem = mv.sem; q.m_ins = mv.ins;
-        q.d_mover = d_mover;
-        hipLaunchKernelGGL(mover_noisy_sweep_merge_kernel, grid, dim3(kBlock), 0, st, p, q);
+        hipLaunchKernelGGL(merge_kernel, grid, dim3(kBlock), 0, st, p, q);
         LRC_HIP(hipGetLastError());
     }
     return LRC_OK;
@@ -4903,19 +4452,12 @@ int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const ui
         LRC_HIP(hipGetLastError());
         return LRC_OK;
     }
-    // scratch, 256-byte aligned columns: world rays6 | object rays6 | cast | keep | thr | t_min | t_mover
-    auto al = [](uint64_t b) { return (b + 255u) & ~(uint64_t)255u; };
-    const uint64_t sizes[7] = {n * 24, n * 24, n, n, n * 4, n * 4, n * 4};
-    uint64_t off[8] = {0};
-    for (int k = 0; k < 7; ++k) off[k + 1] = off[k] + al(sizes[k]);
+    // scratch columns: world rays6 | object rays6 | cast | keep | thr | t_min | t_mover
+    const uint32_t width[7] = {24, 24, 1, 1, 4, 4, 4};
+    uint64_t off[7];
     void*& block = set ? set->scratch : s->flow_scratch;
-    uint64_t& cap = set ? set->scratch_cap : s->flow_scratch_cap;
-    if (cap < off[7]) {
-        // (hipFree waits for the device: nothing enqueued earlier still reads the old block)
-        if (block) { (void)hipFree(block); block = nullptr; cap = 0; }
-        LRC_HIP(hipMalloc(&block, off[7] + off[7] / 8));
-        cap = off[7] + off[7] / 8;
-    }
+    int rc;
+    if ((rc = scratch_columns(block, set ? set->scratch_cap : s->flow_scratch_cap, n, width, 7, off))) return rc;
     uint8_t* const b = (uint8_t*)block;
     float* const world6 = (float*)(b + off[0]);
     float* const obj6 = (float*)(b + off[1]);
@@ -4928,13 +4470,12 @@ int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const ui
     fr.rays6 = world6; fr.keep = cast; fr.thr = thr; fr.status = d_status;
     ray_kernel();
     LRC_HIP(hipGetLastError());
-    int rc;
     if ((rc = cast_plain(s, world6, cast, n, w, st))) return rc;
     const int uniform = N % 64 == 0;
     for (uint32_t m = 0; m < M; ++m) {
         lrc_scene* const ms = set->scenes[m];
         lrcmov::RayPass rp{};
-        rp.poses12 = next.next_mover_poses12;
+        rp.records = next.next_mover_poses12;
         rp.M = M;
         rp.m = m;
         rp.sphere = lrcmov::bounding_sphere(ms->info.bounds_lo, ms->info.bounds_hi);
@@ -4951,28 +4492,19 @@ int flow_scan_dev(lrc_scene* s, lrc_movers* set, const lrc_hits* d_rec, const ui
     return LRC_OK;
 }
 
-// Host poses, a resident direction table: the records at the fixed stride by movers_scan_dev on the context's compute stream,
-// compacted by lrc_compact_dev (which counts itself: the merge kernel writes no per-tile keep counts); the counts come home
-// first, then exactly the kept rows.  The mover column stays at the fixed stride and is gathered for the kept rows by the
+// Host sensor records, a resident direction table: the records at the fixed stride by movers_scan_dev on the context's compute
+// stream, compacted by lrc_compact_dev (which counts itself: the merge kernel writes no per-tile keep counts); the counts come
+// home first, then exactly the kept rows.  The mover column stays at the fixed stride and is gathered for the kept rows by the
 // compacted index column (gather_rows_by_index above).
+// With `sweep`: `sensor` holds P (P,24) motion records (else (P,16) poses), `movers` the (P, M, 24) mover sweep records (else
+// (P, M, 12) poses), and the table brings its fire table.  With `noise` the scan is noisy: the one call traces every pose at once
+// (no pose chunks), pose or sweep p of the call is frame first_frame + p throughout.
 // With `flow` (flow_scan_compact): the flow and its status at the fixed stride behind the mover scan, gathered like the mover column.
-// With `motion24` (mover_sweeps_scan_compact): poses16 is unread, the P sensor records are staged in its place, `mover_poses12`
-// holds the (P, M, 24) mover sweep records, the table brings its fire table and mover_sweeps_scan_dev scans.
-// With `noise` (noisy_movers_scan_compact): noisy_movers_scan_dev scans in the place of movers_scan_dev.
-// With both (noisy_mover_sweeps_scan_compact): noisy_mover_sweeps_scan_dev scans; sweep p of the call is frame first_frame + p.
-namespace {
-struct FlowCompact {
-    FlowNext next;             // host pointers
-    float* flow_rows;          // nullable
-    uint8_t* status_rows;      // nullable: flow only, nothing cast
-};
-int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
-                   const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
-                   uint64_t* out_total, const FlowCompact* flow, const double* motion24 = nullptr,
-                   const lrcnoise::Params* noise = nullptr) {
-    const char* const who = motion24 ? (noise ? "lrc_scan_noisy_mover_sweeps_compact" : "lrc_scan_mover_sweeps_compact")
-                            : flow   ? "lrc_scan_flow_compact"
-                            : noise  ? "lrc_scan_noisy_movers_compact" : "lrc_scan_movers_compact";
+int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* sensor, uint64_t P, const lrc_table* table, const float* movers,
+                        double max_range, bool sweep, const lrcnoise::Params* noise, const lrc_frames* out, uint8_t* mover_rows,
+                        uint64_t capacity, uint64_t* out_total, const FlowCompact* flow) {
+    const std::string who = flow ? "lrc_scan_flow_compact"
+                                 : std::string("lrc_scan_") + (noise ? "noisy_" : "") + (sweep ? "mover_sweeps_compact" : "movers_compact");
     SyncUnlessOk guard;
     lrc_ctx* const ctx = s->ctx;
     const uint64_t N = table->n, n = P * N;
@@ -4985,10 +4517,8 @@ int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_
     } drain{cs};
     const double* d_poses = nullptr;
     const float* d_mp = nullptr;
-    if ((rc = motion24 ? stage_input(ctx, kPoolPoses, motion24, P * 24, &d_poses, &cs)
-                       : stage_input(ctx, kPoolPoses, poses16, P * 16, &d_poses, &cs)))
-        return rc;
-    if (set && (rc = stage_input(ctx, kPoolNoise, mover_poses12, P * set->scenes.size() * (motion24 ? 24 : 12), &d_mp, &cs))) return rc;
+    if ((rc = stage_input(ctx, kPoolPoses, sensor, P * (sweep ? 24 : 16), &d_poses, &cs))) return rc;
+    if (set && (rc = stage_input(ctx, kPoolNoise, movers, P * set->scenes.size() * (sweep ? 24 : 12), &d_mp, &cs))) return rc;
     FrameStage st;
     if ((rc = st.alloc(ctx, *out, P, n))) return rc;
     st.rec.tile_count = nullptr;
@@ -5020,14 +4550,8 @@ int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_
         LRC_HIP(hipHostMalloc((void**)&ctx->h_counts, (P + P / 4 + 64) * 8 * 5, hipHostMallocDefault));
         ctx->h_counts_cap = P + P / 4 + 64;
     }
-    if ((rc = motion24 && noise ? noisy_mover_sweeps_scan_dev(s, set, d_poses, P, table->d_dirs3, table->d_fire, N, d_mp, max_range,
-                                                              *noise, &st.rec, (uint8_t*)mbuf.p, cs)
-             : motion24 ? mover_sweeps_scan_dev(s, set, d_poses, P, table->d_dirs3, table->d_fire, N, d_mp, max_range, &st.rec,
-                                                (uint8_t*)mbuf.p, cs)
-             : noise ? noisy_movers_scan_dev(s, set, d_poses, P, table->d_dirs3, N, d_mp, max_range, *noise, &st.rec,
-                                             (uint8_t*)mbuf.p, cs)
-                     : movers_scan_dev(s, set, d_poses, P, table->d_dirs3, N, d_mp, max_range, &st.rec, (uint8_t*)mbuf.p, cs)))
-        return rc;
+    const MoverScan scan{d_poses, table->d_dirs3, sweep ? table->d_fire : nullptr, d_mp, noise, P, N, max_range};
+    if ((rc = movers_scan_dev(s, set, scan, &st.rec, (uint8_t*)mbuf.p, cs))) return rc;
     if (want_flow && (rc = flow_scan_dev(s, set, &st.rec, (const uint8_t*)mbuf.p, P, N, d_mp, d_next, max_range, (float*)fbuf.p,
                                          (uint8_t*)sbuf.p, cs)))
         return rc;
@@ -5048,16 +4572,9 @@ int movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_
         const GatherColumn cols[3] = {{mbuf.p, mover_rows, 1, 1},
                                       {fbuf.p, flow ? flow->flow_rows : nullptr, 4, 3},
                                       {sbuf.p, flow ? flow->status_rows : nullptr, 1, 1}};
-        rc = gather_rows_by_index(who, out->counts, P, st.io.out_index, N, K, cols, 3);
+        rc = gather_rows_by_index(who.c_str(), out->counts, P, st.io.out_index, N, K, cols, 3);
     }
     return guard.done(rc);
-}
-}  // namespace
-
-int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
-                        const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
-                        uint64_t* out_total) {
-    return movers_compact(s, set, poses16, P, table, mover_poses12, max_range, out, mover_rows, capacity, out_total, nullptr);
 }
 
 // Host check of (P,24) motion records (lrc_scan_sweeps_compact): finite, dq.w >= cos(pi/4) (a rotation of at most pi/2 per
@@ -5080,32 +4597,11 @@ int check_motion(const char* who, const double* m, uint64_t P) {
     return LRC_OK;
 }
 
-// The one call traces every pose at once (no pose chunks): pose p is frame noise.first_frame + p throughout.
-int noisy_movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
-                              const float* mover_poses12, double max_range, const lrcnoise::Params& noise, const lrc_frames* out,
-                              uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total) {
-    return movers_compact(s, set, poses16, P, table, mover_poses12, max_range, out, mover_rows, capacity, out_total, nullptr, nullptr,
-                          &noise);
-}
-
-int mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
-                              const float* mover_motion24, double max_range, const lrc_frames* out, uint8_t* mover_rows,
-                              uint64_t capacity, uint64_t* out_total) {
-    return movers_compact(s, set, nullptr, P, table, mover_motion24, max_range, out, mover_rows, capacity, out_total, nullptr, motion24);
-}
-
-int noisy_mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
-                                    const float* mover_motion24, double max_range, const lrcnoise::Params& noise,
-                                    const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total) {
-    return movers_compact(s, set, nullptr, P, table, mover_motion24, max_range, out, mover_rows, capacity, out_total, nullptr, motion24,
-                          &noise);
-}
-
 int flow_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
                       const float* mover_poses12, const FlowNext& next, double max_range, const lrc_frames* out, uint8_t* mover_rows,
                       float* flow_rows, uint8_t* status_rows, uint64_t capacity, uint64_t* out_total) {
     const FlowCompact flow{next, flow_rows, status_rows};
-    return movers_compact(s, set, poses16, P, table, mover_poses12, max_range, out, mover_rows, capacity, out_total, &flow);
+    return movers_scan_compact(s, set, poses16, P, table, mover_poses12, max_range, false, nullptr, out, mover_rows, capacity, out_total, &flow);
 }
 
 extern "C" {

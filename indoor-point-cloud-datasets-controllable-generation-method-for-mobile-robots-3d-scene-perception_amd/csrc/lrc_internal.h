@@ -221,55 +221,37 @@ int material_scan_compact(lrc_scene* s, const double* poses16, uint64_t P, const
                           double max_range, const lrc_frames* out, float* intensity_rows, uint8_t* bounces_rows, float* surface_rows,
                           uint64_t capacity, uint64_t* out_total);
 
-// moving objects.  lrc_movers.hip checks the arguments of lrc_scan_movers_* and owns the handle and the host functions;
-// lidarcast.hip, which owns the trace launch, write_back and the frame path, holds the kernels and enqueues the passes
-// (movers_scan_dev: everything on `st`, no host synchronisation; movers_scan_compact: host poses, the mover column gathered for
-// the kept rows by the compacted index column).  set == NULL: the scan of lrc_scan_poses_dev and a zero mover column.
-int movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
-                    const float* d_mover_poses12, double max_range, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st);
-int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
-                        const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity,
-                        uint64_t* out_total);
-
-// seeded sensor noise under movers: the same split.  lrc_movers.hip checks the arguments of lrc_scan_noisy_movers_* and fills the
-// lrcnoise::Params (noise_params); lidarcast.hip holds the two noisy kernels and enqueues the passes (noisy_movers_scan_dev; set ==
-// NULL: the scan of lrc_scan_noisy_dev and a zero mover column) and scans to frames (noisy_movers_scan_compact).
-int noisy_movers_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
-                          const float* d_mover_poses12, double max_range, const lrcnoise::Params& np, const lrc_hits* d_out,
-                          uint8_t* d_mover, hipStream_t st);
-int noisy_movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
-                              const float* mover_poses12, double max_range, const lrcnoise::Params& noise, const lrc_frames* out,
-                              uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total);
+// moving objects: the four scans lrc_scan_movers_*, lrc_scan_noisy_movers_*, lrc_scan_mover_sweeps_* and
+// lrc_scan_noisy_mover_sweeps_* are one scan under two switches.  lrc_movers.hip checks their arguments, fills the
+// lrcnoise::Params (noise_params) and owns the handle and the host functions; lidarcast.hip, which owns the trace launch,
+// write_back and the frame path, holds the two kernel templates and enqueues the passes.
+struct MoverScan {                   // one call of the family: device pointers
+    const double* sensor;            // (P,16) poses, or with `fire` the sensor's (P,24) motion records
+    const double* dirs3;             // (N,3)
+    const double* fire;              // (N) firing fractions; non-NULL: the scan is under moving-sensor sweeps
+    const float* movers;             // (P,M,12) mover poses, or with `fire` the (P,M,24) mover sweep records; unread without a set
+    const lrcnoise::Params* noise;   // non-NULL: the scan is under seeded sensor noise
+    uint64_t P, N;
+    double max_range;
+};
+// movers_scan_dev: everything on `st`, no host synchronisation; set == NULL: the variant's plain scan (lrc_scan_poses_dev,
+// lrc_scan_noisy_dev, lrc_scan_sweeps_dev, lrc_scan_noisy_sweeps_dev) and a zero mover column.  movers_scan_compact: host
+// records (`sensor`, `movers` as in MoverScan, by `sweep`), the table with its directions and under `sweep` its fire table, all
+// poses in one call (pose p is frame first_frame + p of `noise`), the mover column gathered for the kept rows by the compacted
+// index column; `flow`: flow_scan_compact's columns beside it.
+struct FlowCompact;
+int movers_scan_dev(lrc_scene* s, lrc_movers* set, const MoverScan& scan, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st);
+int movers_scan_compact(lrc_scene* s, lrc_movers* set, const double* sensor, uint64_t P, const lrc_table* table, const float* movers,
+                        double max_range, bool sweep, const lrcnoise::Params* noise, const lrc_frames* out, uint8_t* mover_rows,
+                        uint64_t capacity, uint64_t* out_total, const FlowCompact* flow = nullptr);
 
 // the checks lrc_scan_movers_* and lrc_scan_flow_* share (lrc_movers.hip).  check_call: NULL scene or output, a set of another
 // context or one that holds the static scene, a range_noise option; `set` may be NULL.  check_poses12: `count` host mover poses,
-// every entry finite and max |R^T R - I| <= 2^-16 in float64.
+// every entry finite and max |R^T R - I| <= 2^-16 in float64.  check_motion (lidarcast.hip): the host check of (P,24) sensor
+// records every *_sweeps_compact call makes.
 int check_call(const char* who, const lrc_scene* s, const lrc_movers* set, const void* out);
 int check_poses12(const char* who, const float* m, uint64_t count);
-
-// movers under moving-sensor sweeps: the same split.  lidarcast.hip: mover_sweeps_scan_dev (movers_scan_dev with the sensor's
-// (P,24) float64 records, the firing fractions and the (P, M, 24) float32 mover sweep records; set == NULL: the scan of
-// lrc_scan_sweeps_dev and a zero mover column), mover_sweeps_scan_compact (host records, the table with its fire table) and
-// check_motion, the host check of (P,24) sensor records every *_sweeps_compact call makes.
-int mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
-                          const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range, const lrc_hits* d_out,
-                          uint8_t* d_mover, hipStream_t st);
-int mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
-                              const float* mover_motion24, double max_range, const lrc_frames* out, uint8_t* mover_rows,
-                              uint64_t capacity, uint64_t* out_total);
 int check_motion(const char* who, const double* m, uint64_t P);
-
-// seeded sensor noise under movers in sweeps: the same split.  lrc_movers.hip checks the arguments of lrc_scan_noisy_mover_sweeps_*
-// and fills the lrcnoise::Params (noise_params); lidarcast.hip holds the two kernels and enqueues the passes
-// (noisy_mover_sweeps_scan_dev: everything on `st`, no host synchronisation; set == NULL: the scan of lrc_scan_noisy_sweeps_dev and
-// a zero mover column) and scans to frames (noisy_mover_sweeps_scan_compact: all sweeps in one call, sweep p is frame
-// first_frame + p).
-int noisy_mover_sweeps_scan_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
-                                const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range,
-                                const lrcnoise::Params& np, const lrc_hits* d_out, uint8_t* d_mover, hipStream_t st);
-int noisy_mover_sweeps_scan_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
-                                    const float* mover_motion24, double max_range, const lrcnoise::Params& noise,
-                                    const lrc_frames* out, uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total);
 
 // scene flow under movers.  lrc_flow.hip checks the arguments of lrc_scan_flow_* and owns the host functions; lidarcast.hip holds
 // the kernels and enqueues the passes (flow_scan_dev: everything on `st`, no host synchronisation; d_status == NULL: the flow
@@ -279,6 +261,11 @@ struct FlowNext {             // what pairs every frame of a call with its next 
     const float* next_mover_poses12;      // pointers for flow_scan_compact
     const double* next_poses16;
     const uint8_t* has_next;              // nullable: all ones
+};
+struct FlowCompact {          // what flow_scan_compact adds to movers_scan_compact
+    FlowNext next;                        // host pointers
+    float* flow_rows;                     // nullable
+    uint8_t* status_rows;                 // nullable: flow only, nothing cast
 };
 // non-rigid scene flow (lrc_scan_nonrigid_flow_dev): the surface pairs of one call as the kernel takes them, by value in its
 // arguments.  Entry k serves the rows of mover mover[k] (w - 1) whose prim is below T[k]; vb is never NULL here (lrc_flow.hip
@@ -345,7 +332,7 @@ int deform_nodes_enqueue(lrc_deform* d, const float* d_slot_box, hipStream_t st)
 int deform_shape_enqueue(lrc_deform* d, uint32_t k0, uint32_t k1, float w, float* d_out, hipStream_t st);
 bool deform_height_table(const float* nodes, uint64_t num_nodes, uint64_t num_slots, std::vector<uint32_t>& order);
 // lrc_span.hip: the per-ray-shape cast of a spanned deformable's scene in the place of cast_plain (lidarcast.hip,
-// mover_sweeps_scan_dev): ray g of `n` has the firing fraction d_fire[g % rays_per_pose]; the five columns of `out` the merge reads
+// movers_scan_dev under sweeps): ray g of `n` has the firing fraction d_fire[g % rays_per_pose]; the five columns of `out` the merge reads
 int span_cast(lrc_deform* d, const float* d_rays6, const uint8_t* d_keep, const double* d_fire, uint64_t rays_per_pose, uint64_t n,
               const lrc_hits& out, hipStream_t st);
 // lrc_skin.hip: the k_skin launch of deform_shape_enqueue on a skinned deformable, into `d_out` (V, 3)

@@ -87,9 +87,10 @@ LRC_VHD bool culled(const Sphere s, Vec o, Vec d) {
     return (beside | behind) & finite_bits(k2) & finite_bits(d2) & finite_bits(e2);
 }
 
-// What the ray kernel needs of one mover of a call (lidarcast.hip, mover_rays_kernel).
+// What the ray kernel needs of one mover of a call (lidarcast.hip, mover_rays_kernel<SWEEP, NOISY>; flow_object_rays_kernel).
 struct RayPass {
-    const float* poses12;      // device: (P, M, 12); NULL: the static pass, the world ray itself, nothing culled
+    const float* records;      // device: the mover poses (P, M, 12), under SWEEP the mover sweep records (P, M, 24) below;
+                               // NULL: the static pass, the world ray itself is formed and stored, nothing culled
     uint32_t M, m;
     Sphere sphere;
 };
@@ -154,12 +155,5 @@ LRC_VHD Vec to_world_at(const float* r, float s, Vec n) {
     if (still(r)) return to_world(r, n);
     return rot_at(pose_at(r, s), to_world(r, n), false);
 }
-
-// What the sweep ray kernel needs of one mover of a call (lidarcast.hip, mover_sweep_rays_kernel).
-struct SweepRayPass {
-    const float* motion24;     // device: the mover sweep records (P, M, 24); NULL: the static pass, the world ray is formed and stored
-    uint32_t M, m;
-    Sphere sphere;
-};
 
 }  // namespace lrcmov

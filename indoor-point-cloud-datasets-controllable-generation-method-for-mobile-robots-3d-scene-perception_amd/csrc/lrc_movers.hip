@@ -1,12 +1,7 @@
-// lrc_movers.hip -- host side of the moving objects (lrc_movers.h): the mover set, the checks of lrc_scan_movers_dev /
-// lrc_scan_movers_compact (the kernels, the launches and the frame path are lidarcast.hip's: movers_scan_dev,
-// movers_scan_compact) and the two host functions lrc_mover_rays and lrc_mover_merge, which run the inline functions the
-// kernels call on arrays.  The same for the movers under moving-sensor sweeps: the checks of lrc_scan_mover_sweeps_dev /
-// lrc_scan_mover_sweeps_compact (mover_sweeps_scan_dev, mover_sweeps_scan_compact) and the host functions lrc_mover_sweep_rays and
-// lrc_mover_sweep_normals.  And for the seeded sensor noise under movers: the checks of lrc_scan_noisy_movers_dev /
-// lrc_scan_noisy_movers_compact (noisy_movers_scan_dev, noisy_movers_scan_compact).  And for that noise under movers in sweeps:
-// the checks of lrc_scan_noisy_mover_sweeps_dev / lrc_scan_noisy_mover_sweeps_compact (noisy_mover_sweeps_scan_dev,
-// noisy_mover_sweeps_scan_compact).
+// lrc_movers.hip -- host side of the moving objects (lrc_movers.h): the mover set, the checks of the eight scan entry points
+// lrc_scan_movers_*, lrc_scan_noisy_movers_*, lrc_scan_mover_sweeps_* and lrc_scan_noisy_mover_sweeps_* (the kernels, the launches
+// and the frame path are lidarcast.hip's: movers_scan_dev, movers_scan_compact) and the host functions lrc_mover_rays,
+// lrc_mover_merge, lrc_mover_sweep_rays and lrc_mover_sweep_normals, which run the inline functions the kernels call on arrays.
 #include <cmath>
 
 #include "lrc_internal.h"
@@ -70,6 +65,62 @@ static int check_motion24(const char* who, const float* m, uint64_t count) {
     return LRC_OK;
 }
 
+// ---- the eight scan entry points behind two checkers ---------------------------------------------------------------------------
+// `sweep`: the sensor's records are motion24 with a fire table, the movers' are mover sweep records.  `noisy`: the call brings an
+// lrc_noise.  Every refusal comes before the first device call, in this order: the mover calls' own (check_call, tile_count or the
+// table, NULL inputs, bad host records), among them the model's (noise_params_host: the checks of lrc_scan_noisy_dev /
+// lrc_scan_noisy_sweeps_dev with no context, N >= 2^32 among them) where each call has always made them.  noise_params then
+// makes the quantile table resident.
+static int scan_dev(const char* name, bool sweep, bool noisy, lrc_scene* s, lrc_movers* set, const double* d_sensor, uint64_t P,
+                    const double* d_dirs3, const double* d_fire, uint64_t N, const float* d_movers, double max_range,
+                    const lrc_noise* noise, const lrc_hits* d_out, uint8_t* d_mover, void* stream) {
+    const std::string who = name;
+    int rc = check_call(name, s, set, d_out);
+    if (rc) return rc;
+    if (d_out->tile_count)
+        return fail(LRC_ERR_INVALID_ARG, who + ": tile_count is not written by this scan (lrc_compact_dev counts itself)");
+    if (P && N && (!d_sensor || !d_dirs3 || (sweep && !d_fire)))
+        return fail(LRC_ERR_INVALID_ARG, who + (sweep ? ": motion24, dirs3 or fire is NULL" : ": poses16 or dirs3 is NULL"));
+    if (P && N && set && !d_movers) return fail(LRC_ERR_INVALID_ARG, who + (sweep ? ": mover_motion24 is NULL" : ": mover_poses12 is NULL"));
+    lrcnoise::Params np{};
+    if (noisy && (rc = noise_params_host(name, noise, N, &np))) return rc;
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    if (noisy && (rc = noise_params(s->ctx, name, noise, N, &np))) return rc;
+    const MoverScan scan{d_sensor, d_dirs3, sweep ? d_fire : nullptr, d_movers, noisy ? &np : nullptr, P, N, max_range};
+    return movers_scan_dev(s, set, scan, d_out, d_mover, (hipStream_t)stream);
+}
+
+// An empty call (P * table->n == 0) returns after the table's checks -- under `sweep` the fire table among them -- and the
+// model's, before the sensor's records are looked at.  Only the calls without a model have a rays_per_pose message of their own:
+// the model's checks refuse N >= 2^32 before it.
+static int scan_compact(const char* name, bool sweep, bool noisy, lrc_scene* s, lrc_movers* set, const double* sensor, uint64_t P,
+                        const lrc_table* table, const float* movers, double max_range, const lrc_noise* noise, const lrc_frames* out,
+                        uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total) {
+    const std::string who = name;
+    if (out_total) *out_total = 0;
+    int rc = check_call(name, s, set, out);
+    if (rc) return rc;
+    if (!table) return fail(LRC_ERR_INVALID_ARG, who + ": table is NULL");
+    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, who + ": table and scene belong to different contexts");
+    if (sweep && !table->d_fire) return fail(LRC_ERR_INVALID_ARG, who + ": the table has no fire table (lrc_table_set_fire)");
+    lrcnoise::Params np{};
+    if (noisy && (rc = noise_params_host(name, noise, table->n, &np))) return rc;
+    if (!(P * table->n)) return LRC_OK;
+    if (!sensor || !out->counts) return fail(LRC_ERR_INVALID_ARG, who + (sweep ? ": motion24 or counts is NULL" : ": poses16 or counts is NULL"));
+    if (!noisy && table->n > 0xFFFFFFFFull)
+        return fail(LRC_ERR_INVALID_ARG, who + ": rays_per_pose must stay below 2^32 (the index column)");
+    if (sweep && (rc = check_motion(name, sensor, P))) return rc;
+    if (set) {
+        if (!movers) return fail(LRC_ERR_INVALID_ARG, who + (sweep ? ": mover_motion24 is NULL" : ": mover_poses12 is NULL"));
+        const uint64_t count = P * set->scenes.size();
+        if ((rc = sweep ? check_motion24(name, movers, count) : check_poses12(name, movers, count))) return rc;
+    }
+    LRC_HIP(hipSetDevice(s->ctx->device));
+    if (noisy && (rc = noise_params(s->ctx, name, noise, table->n, &np))) return rc;
+    return movers_scan_compact(s, set, sensor, P, table, movers, max_range, sweep, noisy ? &np : nullptr, out, mover_rows, capacity,
+                               out_total);
+}
+
 extern "C" {
 
 int lrc_movers_create(lrc_ctx* ctx, lrc_scene* const* scenes, uint32_t num_movers, lrc_movers** out_set) {
@@ -103,34 +154,15 @@ int lrc_movers_destroy(lrc_movers* set) {
 
 int lrc_scan_movers_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
                         const float* d_mover_poses12, double max_range, const lrc_hits* d_out, uint8_t* d_mover, void* stream) {
-    int rc = check_call("lrc_scan_movers_dev", s, set, d_out);
-    if (rc) return rc;
-    if (d_out->tile_count)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_dev: tile_count is not written by this scan (lrc_compact_dev counts itself)");
-    if (P && N && (!d_poses16 || !d_dirs3)) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_dev: poses16 or dirs3 is NULL");
-    if (P && N && set && !d_mover_poses12) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_dev: mover_poses12 is NULL");
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    return movers_scan_dev(s, set, d_poses16, P, d_dirs3, N, d_mover_poses12, max_range, d_out, d_mover, (hipStream_t)stream);
+    return scan_dev("lrc_scan_movers_dev", false, false, s, set, d_poses16, P, d_dirs3, nullptr, N, d_mover_poses12, max_range, nullptr,
+                    d_out, d_mover, stream);
 }
 
 int lrc_scan_movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
                             const float* mover_poses12, double max_range, const lrc_frames* out, uint8_t* mover_rows,
                             uint64_t capacity, uint64_t* out_total) {
-    if (out_total) *out_total = 0;
-    int rc = check_call("lrc_scan_movers_compact", s, set, out);
-    if (rc) return rc;
-    if (!table) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: table is NULL");
-    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: table and scene belong to different contexts");
-    if (!(P * table->n)) return LRC_OK;
-    if (!poses16 || !out->counts) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: poses16 or counts is NULL");
-    if (table->n > 0xFFFFFFFFull)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: rays_per_pose must stay below 2^32 (the index column)");
-    if (set) {
-        if (!mover_poses12) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_movers_compact: mover_poses12 is NULL");
-        if ((rc = check_poses12("lrc_scan_movers_compact", mover_poses12, P * set->scenes.size()))) return rc;
-    }
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    return movers_scan_compact(s, set, poses16, P, table, mover_poses12, max_range, out, mover_rows, capacity, out_total);
+    return scan_compact("lrc_scan_movers_compact", false, false, s, set, poses16, P, table, mover_poses12, max_range, nullptr, out,
+                        mover_rows, capacity, out_total);
 }
 
 int lrc_mover_rays(const float* rays6, uint64_t n, const float* pose12, float* out_rays6) {
@@ -174,39 +206,15 @@ int lrc_mover_merge(uint64_t n, uint32_t M, const float* t_static, const float* 
 int lrc_scan_mover_sweeps_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
                               const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range,
                               const lrc_hits* d_out, uint8_t* d_mover, void* stream) {
-    int rc = check_call("lrc_scan_mover_sweeps_dev", s, set, d_out);
-    if (rc) return rc;
-    if (d_out->tile_count)
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_mover_sweeps_dev: tile_count is not written by this scan (lrc_compact_dev counts itself)");
-    if (P && N && (!d_motion24 || !d_dirs3 || !d_fire))
-        return fail(LRC_ERR_INVALID_ARG, "lrc_scan_mover_sweeps_dev: motion24, dirs3 or fire is NULL");
-    if (P && N && set && !d_mover_motion24) return fail(LRC_ERR_INVALID_ARG, "lrc_scan_mover_sweeps_dev: mover_motion24 is NULL");
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    return mover_sweeps_scan_dev(s, set, d_motion24, P, d_dirs3, d_fire, N, d_mover_motion24, max_range, d_out, d_mover,
-                                 (hipStream_t)stream);
+    return scan_dev("lrc_scan_mover_sweeps_dev", true, false, s, set, d_motion24, P, d_dirs3, d_fire, N, d_mover_motion24, max_range,
+                    nullptr, d_out, d_mover, stream);
 }
 
 int lrc_scan_mover_sweeps_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
                                   const float* mover_motion24, double max_range, const lrc_frames* out, uint8_t* mover_rows,
                                   uint64_t capacity, uint64_t* out_total) {
-    const char* const who = "lrc_scan_mover_sweeps_compact";
-    if (out_total) *out_total = 0;
-    int rc = check_call(who, s, set, out);
-    if (rc) return rc;
-    if (!table) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table is NULL");
-    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table and scene belong to different contexts");
-    if (!table->d_fire) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": the table has no fire table (lrc_table_set_fire)");
-    if (!(P * table->n)) return LRC_OK;
-    if (!motion24 || !out->counts) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": motion24 or counts is NULL");
-    if (table->n > 0xFFFFFFFFull)
-        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": rays_per_pose must stay below 2^32 (the index column)");
-    if ((rc = check_motion(who, motion24, P))) return rc;
-    if (set) {
-        if (!mover_motion24) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_motion24 is NULL");
-        if ((rc = check_motion24(who, mover_motion24, P * set->scenes.size()))) return rc;
-    }
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    return mover_sweeps_scan_compact(s, set, motion24, P, table, mover_motion24, max_range, out, mover_rows, capacity, out_total);
+    return scan_compact("lrc_scan_mover_sweeps_compact", true, false, s, set, motion24, P, table, mover_motion24, max_range, nullptr,
+                        out, mover_rows, capacity, out_total);
 }
 
 int lrc_mover_sweep_rays(const float* rays6, const double* fire, uint64_t n, const float* motion24, float* out_rays6) {
@@ -231,97 +239,34 @@ int lrc_mover_sweep_normals(const float* normal3, const double* fire, uint64_t n
     return LRC_OK;
 }
 
-// ---- seeded sensor noise under movers ----------------------------------------------------------------------------------------
-// Every refusal comes before the first device call: the mover calls' own (check_call, tile_count, NULL inputs, bad host poses),
-// then the model's (noise_params_host: the checks of lrc_scan_noisy_dev with no context).  noise_params then makes the
-// quantile table resident.
+// ---- seeded sensor noise under movers, and under movers in sweeps --------------------------------------------------------------
 
 int lrc_scan_noisy_movers_dev(lrc_scene* s, lrc_movers* set, const double* d_poses16, uint64_t P, const double* d_dirs3, uint64_t N,
                               const float* d_mover_poses12, double max_range, const lrc_noise* noise, const lrc_hits* d_out,
                               uint8_t* d_mover, void* stream) {
-    const char* const who = "lrc_scan_noisy_movers_dev";
-    int rc = check_call(who, s, set, d_out);
-    if (rc) return rc;
-    if (d_out->tile_count)
-        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": tile_count is not written by this scan (lrc_compact_dev counts itself)");
-    if (P && N && (!d_poses16 || !d_dirs3)) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": poses16 or dirs3 is NULL");
-    if (P && N && set && !d_mover_poses12) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_poses12 is NULL");
-    lrcnoise::Params np{};
-    if ((rc = noise_params_host(who, noise, N, &np))) return rc;
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    if ((rc = noise_params(s->ctx, who, noise, N, &np))) return rc;
-    return noisy_movers_scan_dev(s, set, d_poses16, P, d_dirs3, N, d_mover_poses12, max_range, np, d_out, d_mover, (hipStream_t)stream);
+    return scan_dev("lrc_scan_noisy_movers_dev", false, true, s, set, d_poses16, P, d_dirs3, nullptr, N, d_mover_poses12, max_range,
+                    noise, d_out, d_mover, stream);
 }
 
 int lrc_scan_noisy_movers_compact(lrc_scene* s, lrc_movers* set, const double* poses16, uint64_t P, const lrc_table* table,
                                   const float* mover_poses12, double max_range, const lrc_noise* noise, const lrc_frames* out,
                                   uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total) {
-    const char* const who = "lrc_scan_noisy_movers_compact";
-    if (out_total) *out_total = 0;
-    int rc = check_call(who, s, set, out);
-    if (rc) return rc;
-    if (!table) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table is NULL");
-    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table and scene belong to different contexts");
-    lrcnoise::Params np{};
-    if ((rc = noise_params_host(who, noise, table->n, &np))) return rc;      // checked for an empty call too
-    if (!(P * table->n)) return LRC_OK;
-    if (!poses16 || !out->counts) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": poses16 or counts is NULL");
-    if (set) {
-        if (!mover_poses12) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_poses12 is NULL");
-        if ((rc = check_poses12(who, mover_poses12, P * set->scenes.size()))) return rc;
-    }
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    if ((rc = noise_params(s->ctx, who, noise, table->n, &np))) return rc;
-    return noisy_movers_scan_compact(s, set, poses16, P, table, mover_poses12, max_range, np, out, mover_rows, capacity, out_total);
+    return scan_compact("lrc_scan_noisy_movers_compact", false, true, s, set, poses16, P, table, mover_poses12, max_range, noise, out,
+                        mover_rows, capacity, out_total);
 }
-
-// ---- seeded sensor noise under movers in sweeps ------------------------------------------------------------------------------
-// Every refusal comes before the first device call, as above: the mover sweep calls' own (check_call, tile_count, NULL inputs,
-// the fire table, bad host records), then the model's (noise_params_host: the checks of lrc_scan_noisy_sweeps_dev with no
-// context, N >= 2^32 among them).
 
 int lrc_scan_noisy_mover_sweeps_dev(lrc_scene* s, lrc_movers* set, const double* d_motion24, uint64_t P, const double* d_dirs3,
                                     const double* d_fire, uint64_t N, const float* d_mover_motion24, double max_range,
                                     const lrc_noise* noise, const lrc_hits* d_out, uint8_t* d_mover, void* stream) {
-    const char* const who = "lrc_scan_noisy_mover_sweeps_dev";
-    int rc = check_call(who, s, set, d_out);
-    if (rc) return rc;
-    if (d_out->tile_count)
-        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": tile_count is not written by this scan (lrc_compact_dev counts itself)");
-    if (P && N && (!d_motion24 || !d_dirs3 || !d_fire))
-        return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": motion24, dirs3 or fire is NULL");
-    if (P && N && set && !d_mover_motion24) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_motion24 is NULL");
-    lrcnoise::Params np{};
-    if ((rc = noise_params_host(who, noise, N, &np))) return rc;
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    if ((rc = noise_params(s->ctx, who, noise, N, &np))) return rc;
-    return noisy_mover_sweeps_scan_dev(s, set, d_motion24, P, d_dirs3, d_fire, N, d_mover_motion24, max_range, np, d_out, d_mover,
-                                       (hipStream_t)stream);
+    return scan_dev("lrc_scan_noisy_mover_sweeps_dev", true, true, s, set, d_motion24, P, d_dirs3, d_fire, N, d_mover_motion24,
+                    max_range, noise, d_out, d_mover, stream);
 }
 
 int lrc_scan_noisy_mover_sweeps_compact(lrc_scene* s, lrc_movers* set, const double* motion24, uint64_t P, const lrc_table* table,
                                         const float* mover_motion24, double max_range, const lrc_noise* noise, const lrc_frames* out,
                                         uint8_t* mover_rows, uint64_t capacity, uint64_t* out_total) {
-    const char* const who = "lrc_scan_noisy_mover_sweeps_compact";
-    if (out_total) *out_total = 0;
-    int rc = check_call(who, s, set, out);
-    if (rc) return rc;
-    if (!table) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table is NULL");
-    if (table->ctx != s->ctx) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": table and scene belong to different contexts");
-    if (!table->d_fire) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": the table has no fire table (lrc_table_set_fire)");
-    lrcnoise::Params np{};
-    if ((rc = noise_params_host(who, noise, table->n, &np))) return rc;      // checked for an empty call too
-    if (!(P * table->n)) return LRC_OK;      // before motion24 is looked at
-    if (!motion24 || !out->counts) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": motion24 or counts is NULL");
-    if ((rc = check_motion(who, motion24, P))) return rc;
-    if (set) {
-        if (!mover_motion24) return fail(LRC_ERR_INVALID_ARG, std::string(who) + ": mover_motion24 is NULL");
-        if ((rc = check_motion24(who, mover_motion24, P * set->scenes.size()))) return rc;
-    }
-    LRC_HIP(hipSetDevice(s->ctx->device));
-    if ((rc = noise_params(s->ctx, who, noise, table->n, &np))) return rc;
-    return noisy_mover_sweeps_scan_compact(s, set, motion24, P, table, mover_motion24, max_range, np, out, mover_rows, capacity,
-                                           out_total);
+    return scan_compact("lrc_scan_noisy_mover_sweeps_compact", true, true, s, set, motion24, P, table, mover_motion24, max_range, noise,
+                        out, mover_rows, capacity, out_total);
 }
 
 }  // extern "C"

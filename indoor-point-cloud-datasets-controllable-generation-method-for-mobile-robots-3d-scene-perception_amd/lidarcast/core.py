@@ -760,19 +760,8 @@ class Scene:
         ``lidarcast.movers.MoverSet`` or None, ``mover_poses`` (P, M, 12) float32 object-to-world poses (``MoverTrack.poses12``),
         ``dirs`` a DirectionTable or an (N, 3) table.  The return value of ``scan_poses_compact`` plus ``mover``, one uint8 per
         kept row: 0 for the static scene, m + 1 for mover m."""
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
-        lib, h, P, reach = self._lib, self._h, poses.shape[0], float(max_range)
-        with _table_for(self.ctx, dirs) as table:
-            handle, mp = None, None
-            if movers is not None:
-                handle = movers.handle(self.ctx)
-                mp = np.ascontiguousarray(mover_poses, dtype=np.float32)
-                if mp.shape != (P, len(movers), 12):
-                    raise ValueError(f"mover_poses must be (P, M, 12) = ({P}, {len(movers)}, 12), got {mp.shape}")
-            return self._scan_frames("lrc_scan_movers_compact", P, table.n, want, capacity, lambda fr, cap, total, rows:
-                                     lib.lrc_scan_movers_compact(h, handle, _ptr(poses), P, table._h, _ptr(mp), reach, fr, rows,
-                                                                 cap, total),
-                                     side=[("mover", np.uint8, ())])
+        from .movers import _scan_movers_compact
+        return _scan_movers_compact(self, False, False, poses, dirs, None, max_range, movers, mover_poses, None, want, capacity)
 
     def scan_angles_compact(self, poses, angles, keep, max_range, want=("point3", "sem", "ins"), capacity=None):
         """Dual-axis sensor, rays generated in the kernel from host-drawn (phi, theta) (lrc_scan_angles_compact).
@@ -881,20 +870,8 @@ class Scene:
         (N, 3) float64, ``movers`` a ``lidarcast.movers.MoverSet`` or None, ``mover_poses_t`` (P, M, 12) float32 (the caller
         vouches for them), ``mover_t`` an optional (P * N) uint8 tensor: 0 for the static scene, m + 1 for mover m.  ``hits``
         holds P * N records and no tile_count."""
-        import torch
-        P, N = poses_t.shape[0], dirs_t.shape[0]
-        if hits.n != P * N:
-            raise ValueError("hits must hold P * N records")
-        handle, entries = None, None
-        if movers is not None:
-            handle, entries = movers.handle(self.ctx), P * len(movers) * 12
-            if mover_poses_t is None:
-                raise ValueError("mover_poses_t must be (P, M, 12)")
-        _check_side_tensor("mover_poses_t", mover_poses_t, torch.float32, entries, "be (P, M, 12)", poses_t)
-        _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", poses_t)
-        check(self._lib.lrc_scan_movers_dev(self._h, handle, _dptr(poses_t), P, _dptr(dirs_t), N, _dptr(mover_poses_t),
-                                            float(max_range), C.byref(hits.struct), _dptr(mover_t), _stream(stream)),
-              "lrc_scan_movers_dev")
+        from .movers import _scan_movers_dev
+        _scan_movers_dev(self, False, False, poses_t, dirs_t, None, hits, max_range, movers, mover_poses_t, None, mover_t, stream)
 
     def scan_sweeps_dev(self, motion_t, dirs_t, fire_t, hits, max_range, stream=0):
         """Moving-sensor sweeps on device tensors (lrc_scan_sweeps_dev): motion_t (P, 24) float64, dirs_t (N, 3) float64,

@@ -236,28 +236,85 @@ def sweep_normals(normal3, fire_of_ray, record24):
     return out
 
 
-def scan_mover_sweeps_dev(scene, motion_t, dirs_t, fire_t, hits, max_range, movers, mover_records_t, mover_t=None, stream=0):
-    """Moving-sensor sweeps with moving objects on device tensors (lrc_scan_mover_sweeps_dev): motion_t (P, 24) float64, dirs_t
-    (N, 3) float64, fire_t (N,) float64 as ``Scene.scan_sweeps_dev`` takes them; ``movers`` a MoverSet or None,
-    ``mover_records_t`` (P, M, 24) float32 (``sweep_records``; the caller vouches for them), ``mover_t`` an optional (P * N)
-    uint8 tensor: 0 for the static scene, m + 1 for mover m.  Records as ``Scene.scan_poses_dev``."""
+def _scan_name(sweep, noisy, tail):
+    return "lrc_scan_" + ("noisy_" if noisy else "") + ("mover_sweeps_" if sweep else "movers_") + tail
+
+
+def _scan_movers_dev(scene, sweep, noisy, sensor_t, dirs_t, fire_t, hits, max_range, movers, side_t, noise, mover_t, stream):
+    """The four ``*_dev`` scans of the mover family.  ``sweep``: sensor_t holds (P, 24) motion records, fire_t the firing
+    fractions and side_t the (P, M, 24) mover sweep records, else (P, 16) poses and (P, M, 12) mover poses.  ``noisy``: the call
+    brings ``noise``."""
     import torch
     from .core import _check_side_tensor, _dptr, _stream
-    P, N = motion_t.shape[0], dirs_t.shape[0]
-    if motion_t.numel() != P * 24 or fire_t.numel() != N:
+    name, width = ("mover_records_t", 24) if sweep else ("mover_poses_t", 12)
+    P, N = sensor_t.shape[0], dirs_t.shape[0]
+    if sweep and (sensor_t.numel() != P * 24 or fire_t.numel() != N):
         raise ValueError("motion_t must be (P, 24) and fire_t (N,)")
     if hits.n != P * N:
         raise ValueError("hits must hold P * N records")
     handle, entries = None, None
     if movers is not None:
-        handle, entries = movers.handle(scene.ctx), P * len(movers) * 24
-        if mover_records_t is None:
-            raise ValueError("mover_records_t must be (P, M, 24)")
-    _check_side_tensor("mover_records_t", mover_records_t, torch.float32, entries, "be (P, M, 24)", motion_t)
-    _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", motion_t)
-    check(scene._lib.lrc_scan_mover_sweeps_dev(scene._h, handle, _dptr(motion_t), P, _dptr(dirs_t), _dptr(fire_t), N,
-                                               _dptr(mover_records_t), float(max_range), C.byref(hits.struct), _dptr(mover_t),
-                                               _stream(stream)), "lrc_scan_mover_sweeps_dev")
+        handle, entries = movers.handle(scene.ctx), P * len(movers) * width
+        if side_t is None:
+            raise ValueError(f"{name} must be (P, M, {width})")
+    _check_side_tensor(name, side_t, torch.float32, entries, f"be (P, M, {width})", sensor_t)
+    _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", sensor_t)
+    nz = [noise.struct()] if noisy else []
+    fn = _scan_name(sweep, noisy, "dev")
+    check(getattr(scene._lib, fn)(scene._h, handle, _dptr(sensor_t), P, _dptr(dirs_t), *([_dptr(fire_t)] if sweep else []), N,
+                                  _dptr(side_t), float(max_range), *[C.byref(z) for z in nz], C.byref(hits.struct), _dptr(mover_t),
+                                  _stream(stream)), fn)
+
+
+def _scan_movers_compact(scene, sweep, noisy, sensor, dirs, fire, max_range, movers, side, noise, want, capacity):
+    """The four ``*_compact`` scans of the mover family, by the same two switches; ``side`` is mover_records under ``sweep``,
+    else mover_poses.  Under ``sweep`` the table brings the firing fractions, or takes ``fire``."""
+    from .core import DirectionTable, _ptr, _table_for
+    name, width = ("mover_records", 24) if sweep else ("mover_poses", 12)
+    sensor = np.ascontiguousarray(sensor, dtype=np.float64).reshape(-1, 24 if sweep else 16)
+    h, P, reach = scene._h, sensor.shape[0], float(max_range)
+    if sweep and fire is None and not isinstance(dirs, DirectionTable):
+        raise ValueError("fire is required with a plain direction table")
+    with _table_for(scene.ctx, dirs, fire) as tab:
+        if sweep:
+            if tab is dirs and fire is not None and \
+                    (tab.fire is None or not np.array_equal(tab.fire, np.asarray(fire, np.float64).reshape(-1))):
+                tab.set_fire(fire)
+            if tab.fire is None:
+                raise ValueError("the direction table has no firing fractions")
+        handle, rec = None, None
+        if movers is not None:
+            handle = movers.handle(scene.ctx)
+            rec = np.ascontiguousarray(side, dtype=np.float32)
+            if rec.shape != (P, len(movers), width):
+                raise ValueError(f"{name} must be (P, M, {width}) = ({P}, {len(movers)}, {width}), got {rec.shape}")
+        nz = [noise.struct()] if noisy else []
+        fn = _scan_name(sweep, noisy, "compact")
+        return scene._scan_frames(fn, P, tab.n, want, capacity, lambda fr, cap, total, rows:
+                                  getattr(scene._lib, fn)(h, handle, _ptr(sensor), P, tab._h, _ptr(rec), reach,
+                                                          *[C.byref(z) for z in nz], fr, rows, cap, total),
+                                  side=[("mover", np.uint8, ())])
+
+
+def _sweep_frames(engine, noisy, intrinsics, start_poses, end_poses, mesh, movers, mover_records, noise, want, inputs, need):
+    """The two ``*_sweep_frames`` scans: the sweep's inputs, the compact scan with the index column, and ``point_times``."""
+    motion, fire, T = inputs if inputs is not None else engine.sweep_inputs(intrinsics, start_poses, end_poses)
+    engine._need_table(intrinsics, need, NotImplementedError)
+    ask = tuple(want) + (() if "index" in want else ("index",))
+    fr = _scan_movers_compact(engine.scene_for(mesh), True, noisy, motion, engine._resident_table(intrinsics), fire,
+                              intrinsics.max_range, movers, mover_records, noise, ask, None)
+    fr["point_times"] = fire[fr["index"]] * T
+    if "index" not in want:
+        del fr["index"]
+    return fr
+
+
+def scan_mover_sweeps_dev(scene, motion_t, dirs_t, fire_t, hits, max_range, movers, mover_records_t, mover_t=None, stream=0):
+    """Moving-sensor sweeps with moving objects on device tensors (lrc_scan_mover_sweeps_dev): motion_t (P, 24) float64, dirs_t
+    (N, 3) float64, fire_t (N,) float64 as ``Scene.scan_sweeps_dev`` takes them; ``movers`` a MoverSet or None,
+    ``mover_records_t`` (P, M, 24) float32 (``sweep_records``; the caller vouches for them), ``mover_t`` an optional (P * N)
+    uint8 tensor: 0 for the static scene, m + 1 for mover m.  Records as ``Scene.scan_poses_dev``."""
+    _scan_movers_dev(scene, True, False, motion_t, dirs_t, fire_t, hits, max_range, movers, mover_records_t, None, mover_t, stream)
 
 
 def scan_mover_sweeps_compact(scene, motion, dirs, fire, max_range, movers, mover_records, want=("point3", "sem", "ins"),
@@ -265,27 +322,7 @@ def scan_mover_sweeps_compact(scene, motion, dirs, fire, max_range, movers, move
     """Moving-sensor sweeps with moving objects straight to frames (lrc_scan_mover_sweeps_compact): ``motion``, ``dirs`` and
     ``fire`` as ``Scene.scan_sweeps_compact`` takes them, ``movers`` a MoverSet or None, ``mover_records`` (P, M, 24) float32.
     The return value of ``Scene.scan_movers_compact``: the frames plus ``mover``, one uint8 per kept row."""
-    from .core import DirectionTable, _ptr, _table_for
-    motion = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 24)
-    lib, h, P, reach = scene._lib, scene._h, motion.shape[0], float(max_range)
-    if fire is None and not isinstance(dirs, DirectionTable):
-        raise ValueError("fire is required with a plain direction table")
-    with _table_for(scene.ctx, dirs, fire) as tab:
-        if tab is dirs and fire is not None and \
-                (tab.fire is None or not np.array_equal(tab.fire, np.asarray(fire, np.float64).reshape(-1))):
-            tab.set_fire(fire)
-        if tab.fire is None:
-            raise ValueError("the direction table has no firing fractions")
-        handle, rec = None, None
-        if movers is not None:
-            handle = movers.handle(scene.ctx)
-            rec = np.ascontiguousarray(mover_records, dtype=np.float32)
-            if rec.shape != (P, len(movers), 24):
-                raise ValueError(f"mover_records must be (P, M, 24) = ({P}, {len(movers)}, 24), got {rec.shape}")
-        return scene._scan_frames("lrc_scan_mover_sweeps_compact", P, tab.n, want, capacity, lambda fr, cap, total, rows:
-                                  lib.lrc_scan_mover_sweeps_compact(h, handle, _ptr(motion), P, tab._h, _ptr(rec), reach, fr, rows,
-                                                                    cap, total),
-                                  side=[("mover", np.uint8, ())])
+    return _scan_movers_compact(scene, True, False, motion, dirs, fire, max_range, movers, mover_records, None, want, capacity)
 
 
 def scan_mover_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh, movers, mover_records, want=("point3", "sem", "ins"),
@@ -294,16 +331,8 @@ def scan_mover_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh, mo
     start_poses[k] to end_poses[k], and every ray meets mover m at the pose ``mover_records[k, m]`` gives for the moment the ray
     fires.  The dict of ``scan_sweep_frames`` (``point_times`` included) plus ``mover``, one uint8 per kept row: 0 for the static
     mesh, m + 1 for mover m.  ``inputs``: a ``sweep_inputs`` triple to scan exactly those sensor records again."""
-    motion, fire, T = inputs if inputs is not None else engine.sweep_inputs(intrinsics, start_poses, end_poses)
-    engine._need_table(intrinsics, "movers under moving-sensor sweeps need a sensor with a pose-independent direction table",
-                       NotImplementedError)
-    ask = tuple(want) + (() if "index" in want else ("index",))
-    fr = scan_mover_sweeps_compact(engine.scene_for(mesh), motion, engine._resident_table(intrinsics), fire,
-                                   intrinsics.max_range, movers, mover_records, want=ask)
-    fr["point_times"] = fire[fr["index"]] * T
-    if "index" not in want:
-        del fr["index"]
-    return fr
+    return _sweep_frames(engine, False, intrinsics, start_poses, end_poses, mesh, movers, mover_records, None, want, inputs,
+                         "movers under moving-sensor sweeps need a sensor with a pose-independent direction table")
 
 
 # ---- seeded sensor noise under movers (include/lidarcast.h "seeded sensor noise under movers", DESIGN.md section 5r) --------------
@@ -315,22 +344,7 @@ def scan_noisy_movers_dev(scene, poses_t, dirs_t, hits, max_range, movers, mover
     """``Scene.scan_movers_dev`` with seeded sensor noise drawn in the mover kernels (lrc_scan_noisy_movers_dev): ``noise`` a
     ``lidarcast.noise.NoiseModel`` (pose p of the call is frame ``noise.first_frame + p``); everything else as there.  The
     all-zero model gives ``scan_movers_dev``'s bytes, ``movers=None`` those of ``Scene.scan_noisy_dev`` and a zero column."""
-    import torch
-    from .core import _check_side_tensor, _dptr, _stream
-    P, N = poses_t.shape[0], dirs_t.shape[0]
-    if hits.n != P * N:
-        raise ValueError("hits must hold P * N records")
-    handle, entries = None, None
-    if movers is not None:
-        handle, entries = movers.handle(scene.ctx), P * len(movers) * 12
-        if mover_poses_t is None:
-            raise ValueError("mover_poses_t must be (P, M, 12)")
-    _check_side_tensor("mover_poses_t", mover_poses_t, torch.float32, entries, "be (P, M, 12)", poses_t)
-    _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", poses_t)
-    nz = noise.struct()
-    check(scene._lib.lrc_scan_noisy_movers_dev(scene._h, handle, _dptr(poses_t), P, _dptr(dirs_t), N, _dptr(mover_poses_t),
-                                               float(max_range), C.byref(nz), C.byref(hits.struct), _dptr(mover_t),
-                                               _stream(stream)), "lrc_scan_noisy_movers_dev")
+    _scan_movers_dev(scene, False, True, poses_t, dirs_t, None, hits, max_range, movers, mover_poses_t, noise, mover_t, stream)
 
 
 def scan_noisy_movers_compact(scene, poses, dirs, max_range, movers, mover_poses, noise, want=("point3", "sem", "ins"),
@@ -338,21 +352,7 @@ def scan_noisy_movers_compact(scene, poses, dirs, max_range, movers, mover_poses
     """``Scene.scan_movers_compact`` with seeded sensor noise drawn in the mover kernels (lrc_scan_noisy_movers_compact):
     ``noise`` a ``lidarcast.noise.NoiseModel`` (pose p of the call is frame ``noise.first_frame + p``).  The return value of
     ``scan_movers_compact``: the frames plus ``mover``, one uint8 per kept row."""
-    from .core import _ptr, _table_for
-    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
-    lib, h, P, reach = scene._lib, scene._h, poses.shape[0], float(max_range)
-    with _table_for(scene.ctx, dirs) as table:
-        handle, mp = None, None
-        if movers is not None:
-            handle = movers.handle(scene.ctx)
-            mp = np.ascontiguousarray(mover_poses, dtype=np.float32)
-            if mp.shape != (P, len(movers), 12):
-                raise ValueError(f"mover_poses must be (P, M, 12) = ({P}, {len(movers)}, 12), got {mp.shape}")
-        nz = noise.struct()
-        return scene._scan_frames("lrc_scan_noisy_movers_compact", P, table.n, want, capacity, lambda fr, cap, total, rows:
-                                  lib.lrc_scan_noisy_movers_compact(h, handle, _ptr(poses), P, table._h, _ptr(mp), reach, C.byref(nz),
-                                                                    fr, rows, cap, total),
-                                  side=[("mover", np.uint8, ())])
+    return _scan_movers_compact(scene, False, True, poses, dirs, None, max_range, movers, mover_poses, noise, want, capacity)
 
 
 def scan_noisy_mover_frames(engine, intrinsics, poses, mesh, movers, mover_poses, noise, want=("point3", "sem", "ins")):
@@ -375,24 +375,7 @@ def scan_noisy_mover_sweeps_dev(scene, motion_t, dirs_t, fire_t, hits, max_range
     ``lidarcast.noise.NoiseModel`` (sweep p of the call is frame ``noise.first_frame + p``); everything else as there.  The
     all-zero model gives ``scan_mover_sweeps_dev``'s bytes, ``movers=None`` those of ``lidarcast.noise.scan_noisy_sweeps_dev`` and a
     zero column."""
-    import torch
-    from .core import _check_side_tensor, _dptr, _stream
-    P, N = motion_t.shape[0], dirs_t.shape[0]
-    if motion_t.numel() != P * 24 or fire_t.numel() != N:
-        raise ValueError("motion_t must be (P, 24) and fire_t (N,)")
-    if hits.n != P * N:
-        raise ValueError("hits must hold P * N records")
-    handle, entries = None, None
-    if movers is not None:
-        handle, entries = movers.handle(scene.ctx), P * len(movers) * 24
-        if mover_records_t is None:
-            raise ValueError("mover_records_t must be (P, M, 24)")
-    _check_side_tensor("mover_records_t", mover_records_t, torch.float32, entries, "be (P, M, 24)", motion_t)
-    _check_side_tensor("mover_t", mover_t, torch.uint8, P * N, "hold P * N entries", motion_t)
-    nz = noise.struct()
-    check(scene._lib.lrc_scan_noisy_mover_sweeps_dev(scene._h, handle, _dptr(motion_t), P, _dptr(dirs_t), _dptr(fire_t), N,
-                                                     _dptr(mover_records_t), float(max_range), C.byref(nz), C.byref(hits.struct),
-                                                     _dptr(mover_t), _stream(stream)), "lrc_scan_noisy_mover_sweeps_dev")
+    _scan_movers_dev(scene, True, True, motion_t, dirs_t, fire_t, hits, max_range, movers, mover_records_t, noise, mover_t, stream)
 
 
 def scan_noisy_mover_sweeps_compact(scene, motion, dirs, fire, max_range, movers, mover_records, noise,
@@ -400,28 +383,7 @@ def scan_noisy_mover_sweeps_compact(scene, motion, dirs, fire, max_range, movers
     """``scan_mover_sweeps_compact`` with seeded sensor noise drawn in the mover kernels (lrc_scan_noisy_mover_sweeps_compact):
     ``noise`` a ``lidarcast.noise.NoiseModel``; all sweeps are traced in one call, so sweep p is frame ``noise.first_frame + p``.
     The return value of ``scan_mover_sweeps_compact``."""
-    from .core import DirectionTable, _ptr, _table_for
-    motion = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 24)
-    lib, h, P, reach = scene._lib, scene._h, motion.shape[0], float(max_range)
-    if fire is None and not isinstance(dirs, DirectionTable):
-        raise ValueError("fire is required with a plain direction table")
-    with _table_for(scene.ctx, dirs, fire) as tab:
-        if tab is dirs and fire is not None and \
-                (tab.fire is None or not np.array_equal(tab.fire, np.asarray(fire, np.float64).reshape(-1))):
-            tab.set_fire(fire)
-        if tab.fire is None:
-            raise ValueError("the direction table has no firing fractions")
-        handle, rec = None, None
-        if movers is not None:
-            handle = movers.handle(scene.ctx)
-            rec = np.ascontiguousarray(mover_records, dtype=np.float32)
-            if rec.shape != (P, len(movers), 24):
-                raise ValueError(f"mover_records must be (P, M, 24) = ({P}, {len(movers)}, 24), got {rec.shape}")
-        nz = noise.struct()
-        return scene._scan_frames("lrc_scan_noisy_mover_sweeps_compact", P, tab.n, want, capacity, lambda fr, cap, total, rows:
-                                  lib.lrc_scan_noisy_mover_sweeps_compact(h, handle, _ptr(motion), P, tab._h, _ptr(rec), reach,
-                                                                          C.byref(nz), fr, rows, cap, total),
-                                  side=[("mover", np.uint8, ())])
+    return _scan_movers_compact(scene, True, True, motion, dirs, fire, max_range, movers, mover_records, noise, want, capacity)
 
 
 def scan_noisy_mover_sweep_frames(engine, intrinsics, start_poses, end_poses, mesh, movers, mover_records, noise,
@@ -429,16 +391,8 @@ def scan_noisy_mover_sweep_frames(engine, intrinsics, start_poses, end_poses, me
     """``scan_mover_sweep_frames`` with seeded sensor noise drawn in the mover kernels: ``noise`` a
     ``lidarcast.noise.NoiseModel``; sweep k is frame ``noise.first_frame + k``, so any run of sweeps can be scanned again with its
     exact noise (``noise.at_frame``).  The dict of ``scan_mover_sweep_frames``: ``point_times`` and ``mover`` included."""
-    motion, fire, T = inputs if inputs is not None else engine.sweep_inputs(intrinsics, start_poses, end_poses)
-    engine._need_table(intrinsics, "seeded sensor noise under movers in sweeps needs a sensor with a pose-independent direction table",
-                       NotImplementedError)
-    ask = tuple(want) + (() if "index" in want else ("index",))
-    fr = scan_noisy_mover_sweeps_compact(engine.scene_for(mesh), motion, engine._resident_table(intrinsics), fire,
-                                         intrinsics.max_range, movers, mover_records, noise, want=ask)
-    fr["point_times"] = fire[fr["index"]] * T
-    if "index" not in want:
-        del fr["index"]
-    return fr
+    return _sweep_frames(engine, True, intrinsics, start_poses, end_poses, mesh, movers, mover_records, noise, want, inputs,
+                         "seeded sensor noise under movers in sweeps needs a sensor with a pose-independent direction table")
 
 
 def _bind():

@@ -350,6 +350,40 @@ def test_non_default_stream(world):
         assert_bit_equal(got[col], ref[col], f"own stream: {col}")
 
 
+def test_one_set_serves_the_four_variants_in_turn(world):
+    """The four dev scans share one scratch per set, laid out per variant (74 bytes per ray, + 24 with stored world rays, + 1 with
+    live bytes).  On ONE set and stream, in the order clean (74), noisy sweep (99: the block grows), sweep (98) and noisy (99: both
+    in a block an eighth larger than the noisy sweep needed), every record column and the mover column is byte-equal to the same scan on a set
+    created for it alone.  (N, P, M) = (200, 2, 3), then (64, 5, 1): a set has its M for life, so each shape has its own used set."""
+    from lidarcast.movers import MoverSet
+    from test_mover_noise_gpu import movers_dev, noisy_movers_dev
+    scene, model = world.scenes["quantised"], msn.model_of(dropout=0.25)
+    assert model.range_std > 0 and model.dropout == 0.25
+    for N, P, M in ((200, 2, 3), (64, 5, 1)):
+        dirs, fire, start, motion, _, _ = inputs(N, min(P, 3))
+        start, motion = np.concatenate([start, start[::-1]])[:P], np.concatenate([motion, motion[::-1]])[:P]
+        rec = mover_records(P, M)
+        mp = np.ascontiguousarray(rec[:, :, :12])
+        scans = [("clean", lambda s: movers_dev(scene, s, start, dirs, mp, 2.2)),
+                 ("noisy sweep", lambda s: noisy_sweeps_dev(scene, s, motion, dirs, fire, rec, model, 2.2)),
+                 ("sweep", lambda s: sweeps_dev(scene, s, motion, dirs, fire, rec, 2.2)),
+                 ("noisy", lambda s: noisy_movers_dev(scene, s, start, dirs, mp, model, 2.2))]
+        used = MoverSet(world.ctx, world.meshes[:M])
+        try:
+            got = [scan(used) for _, scan in scans]
+        finally:
+            used.close()
+        for (name, scan), g in zip(scans, got):
+            fresh = MoverSet(world.ctx, world.meshes[:M])
+            try:
+                want = scan(fresh)
+            finally:
+                fresh.close()
+            assert (want["mover"] != 0).any() and np.isinf(want["t"]).any()
+            for col in ALL:
+                assert_bit_equal(g[col], want[col], f"{name} on a used set, (N, P, M) = ({N}, {P}, {M}): {col}")
+
+
 # ---- 5: the compact call and the frames ---------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("route", ROUTES)

@@ -1,6 +1,6 @@
-"""CPU: the two kernels of the seeded sensor noise under movers in sweeps (mover_noisy_sweep_rays_kernel: gen_ray_noisy_sweep
+"""CPU: the two kernels of the seeded sensor noise under movers in sweeps (mover_rays_kernel<true, true>: gen_ray_noisy_sweep
 stored once with its live byte, the stored world ray in the frame a mover has at the ray's own firing fraction, the cull;
-mover_noisy_sweep_merge_kernel: the running winner on the clean ranges and, in the last pass, sweep_centre, the range draw and
+mover_merge_kernel<true, true>: the running winner on the clean ranges and, in the last pass, sweep_centre, the range draw and
 write_back with a given normal and triangle row on the stored world ray) are found exactly once each and use no scratch and no
 LDS -- read from the compiler's kernel-resource-usage remarks as tests/test_mover_noise_kernel_resources.py reads them.  VGPRs,
 SGPRs and occupancy are printed, not fixed (DESIGN.md section 5t records them)."""
@@ -14,7 +14,12 @@ def usage():
     return usage_of("lidarcast.hip")
 
 
-@pytest.mark.parametrize("kernel", ["mover_noisy_sweep_rays_kernel", "mover_noisy_sweep_merge_kernel"])
+# the instantiation by its mangled template arguments <SWEEP, NOISY>; the ids are the names the two kernels had before the family
+KERNELS = [pytest.param("mover_rays_kernelILb1ELb1E", id="mover_noisy_sweep_rays_kernel"),
+           pytest.param("mover_merge_kernelILb1ELb1E", id="mover_noisy_sweep_merge_kernel")]
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
 def test_mover_sweep_noise_kernel_has_no_scratch_and_no_lds(usage, kernel):
     names = [k for k in usage if kernel in k]
     assert len(names) == 1, sorted(k for k in usage if "mover" in k)

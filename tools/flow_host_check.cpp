@@ -18,17 +18,15 @@
 // ---- what lrc_flow.hip and lrc_movers.hip expect of the other units ----
 static std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
-int movers_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const double*, uint64_t, const float*, double, const lrc_hits*,
-                    uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
-int movers_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, const lrc_frames*,
-                        uint8_t*, uint64_t, uint64_t*) { return LRC_ERR_INTERNAL; }
-int mover_sweeps_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const double*, const double*, uint64_t, const float*, double,
-                          const lrc_hits*, uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
-int mover_sweeps_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, const lrc_frames*,
-                              uint8_t*, uint64_t, uint64_t*) { return LRC_ERR_INTERNAL; }
+int movers_scan_dev(lrc_scene*, lrc_movers*, const MoverScan&, const lrc_hits*, uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
+int movers_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, bool, const lrcnoise::Params*,
+                        const lrc_frames*, uint8_t*, uint64_t, uint64_t*, const FlowCompact*) { return LRC_ERR_INTERNAL; }
+int noise_params(lrc_ctx*, const char*, const lrc_noise*, uint64_t, lrcnoise::Params*) { return LRC_ERR_INTERNAL; }
+int noise_params_host(const char*, const lrc_noise*, uint64_t, lrcnoise::Params*) { return LRC_ERR_INTERNAL; }
 int check_motion(const char*, const double*, uint64_t) { return LRC_OK; }
 int flow_scan_dev(lrc_scene*, lrc_movers*, const lrc_hits*, const uint8_t*, uint64_t, uint64_t, const float*, const FlowNext&, double,
-                  float*, uint8_t*, hipStream_t) { return LRC_ERR_INTERNAL; }
+                  float*, uint8_t*, hipStream_t, const FlowPairs*) { return LRC_ERR_INTERNAL; }
+DeformMesh deform_mesh(const lrc_deform*) { return DeformMesh{}; }
 int flow_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, const FlowNext&, double,
                       const lrc_frames*, uint8_t*, float*, uint8_t*, uint64_t, uint64_t*) { return LRC_ERR_INTERNAL; }
 

@@ -20,22 +20,9 @@
 static std::string g_err;
 static int g_entered = 0;      // calls that reached a unit that launches
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
-int movers_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const double*, uint64_t, const float*, double, const lrc_hits*,
-                    uint8_t*, hipStream_t) { ++g_entered; return LRC_ERR_INTERNAL; }
-int movers_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, const lrc_frames*,
-                        uint8_t*, uint64_t, uint64_t*) { ++g_entered; return LRC_ERR_INTERNAL; }
-int mover_sweeps_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const double*, const double*, uint64_t, const float*, double,
-                          const lrc_hits*, uint8_t*, hipStream_t) { ++g_entered; return LRC_ERR_INTERNAL; }
-int mover_sweeps_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, const lrc_frames*,
-                              uint8_t*, uint64_t, uint64_t*) { ++g_entered; return LRC_ERR_INTERNAL; }
-int noisy_movers_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const double*, uint64_t, const float*, double,
-                          const lrcnoise::Params&, const lrc_hits*, uint8_t*, hipStream_t) { ++g_entered; return LRC_ERR_INTERNAL; }
-int noisy_movers_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double,
-                              const lrcnoise::Params&, const lrc_frames*, uint8_t*, uint64_t, uint64_t*) { ++g_entered; return LRC_ERR_INTERNAL; }
-int noisy_mover_sweeps_scan_dev(lrc_scene*, lrc_movers*, const double*, uint64_t, const double*, const double*, uint64_t, const float*,
-                                double, const lrcnoise::Params&, const lrc_hits*, uint8_t*, hipStream_t) { ++g_entered; return LRC_ERR_INTERNAL; }
-int noisy_mover_sweeps_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double,
-                                    const lrcnoise::Params&, const lrc_frames*, uint8_t*, uint64_t, uint64_t*) { ++g_entered; return LRC_ERR_INTERNAL; }
+int movers_scan_dev(lrc_scene*, lrc_movers*, const MoverScan&, const lrc_hits*, uint8_t*, hipStream_t) { ++g_entered; return LRC_ERR_INTERNAL; }
+int movers_scan_compact(lrc_scene*, lrc_movers*, const double*, uint64_t, const lrc_table*, const float*, double, bool, const lrcnoise::Params*,
+                        const lrc_frames*, uint8_t*, uint64_t, uint64_t*, const FlowCompact*) { ++g_entered; return LRC_ERR_INTERNAL; }
 // the sensor's records: the two checks of the real check_motion (lidarcast.hip) that the cases below meet
 int check_motion(const char* who, const double* m, uint64_t P) {
     for (uint64_t k = 0; k < P; ++k) {
