@@ -1487,8 +1487,9 @@ int lrc_coverage_summary_dev(lrc_coverage* cov, int64_t set_index, uint64_t* d_o
 /* Greedy view selection over the object's sets.  covered starts as initial_bits (words_per_set words; NULL = empty);
  * each round picks the set k with the largest gain_k = sum of q over the bits of (bits_k & ~covered), ties to the
  * smallest k, and ORs it into covered.  Selection stops after `budget` picks, at a gain of 0, or as soon as
- * covered_q / total_q >= target_ratio (target_ratio <= 0: no target; an initial cover that already reaches it picks
- * nothing).  Writes the picks (uint32) and their gains (uint64 q units) in pick order and their number.  The rounds
+ * float64(covered_q) / float64(total_q) >= target_ratio: both uint64 sums are converted to float64 (round to nearest
+ * even), then divided once in float64, the arithmetic of `ratio` above (target_ratio <= 0: no target; an initial
+ * cover that already reaches it picks nothing).  Writes the picks (uint32) and their gains (uint64 q units) in pick order and their number.  The rounds
  * run on the device, the pick of round r read by the launches of round r + 1; the host form synchronises once. */
 int lrc_coverage_select(lrc_coverage* cov, uint32_t budget, double target_ratio, const uint32_t* initial_bits,
                         uint32_t* out_picks, uint64_t* out_gains, uint32_t* out_num_picks);
