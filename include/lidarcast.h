@@ -250,9 +250,13 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t num_segments, uint64_t seg_len,
  * mesh (the reference's batch driver, s3dis_simulator.py:594-726, runs them one after the other).  A caller that stays on
  * the device -- dataset generation, the multi-GPU step, bench.py -- submits batch after batch; each submit is one pose-batched
  * scan (lrc_scan_poses_dev, into one of four record sets the pipeline owns) plus the stable compaction (lrc_compact_dev) into
- * the CALLER's rows / counts.  With rays_per_pose % 64 == 0 a set holds only what the compaction reads -- per ray the packed
- * (x, y, z, label) row and (t, triangle slot), per 64 rays the keep mask -- and the complete 36-byte record is formed from it
- * only when lrc_pipe_records asks for it.  The pipeline arranges the launches so that the trace
+ * the CALLER's rows / counts.  With rays_per_pose % 64 == 0 a set holds per ray 12 bytes -- (t, label, triangle slot) -- and per
+ * 64 rays the keep mask.  The compaction forms the (x, y, z, label) row of a ray from that record, the unit vector of its row
+ * in the submit's ray table (lrc_pipe_set_ray_table; the pipeline keeps one table per set) and the pose's float32 origin, with
+ * the arithmetic the scan itself forms the point with; rays of a pose that does not take the table (its rotation is not pose
+ * 0's, or the table is off) have their packed row stored beside the record instead.  The complete 36-byte record is formed from
+ * the same only when lrc_pipe_records asks for it, out of nothing but what the pipeline and the scene own.  The pipeline
+ * arranges the launches so that the trace
  * of submit k+1 fills the wave slots the trace of submit k leaves empty while its last, long-running waves finish, and the
  * rows of submit k are scattered by the first workgroups of the trace launch of submit k+2 (DESIGN.md "the launch tail":
  * a 64-pose launch alone loses a sixth of its time to that tail).  Same arithmetic, same bytes as lrc_scan_poses_dev +
@@ -269,9 +273,10 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t num_segments, uint64_t seg_len,
  *                     The same holds for the inputs of lrc_pipe_submit_sharded.
  *   lrc_pipe_records  the fixed-stride records (lrc_hits, device pointers, tile_count included) of submit `ticket`;
  *                     valid while at most three further submits have been made (four sets rotate; the fourth rewrites
- *                     them).  For a submit that kept only rows (rays_per_pose % 64 == 0) the complete records are rebuilt
- *                     first, behind that submit's trace, and the host waits for them: the same bytes lrc_scan_poses_dev
- *                     writes.  A verification surface.
+ *                     them).  For a submit that kept only the 12-byte records (rays_per_pose % 64 == 0) the complete records
+ *                     are rebuilt first, behind that submit's trace, and the host waits for them: the same bytes
+ *                     lrc_scan_poses_dev writes.  The rebuild reads the set, its ray table and the scene, never d_poses16 or
+ *                     d_dirs3: it is valid after lrc_pipe_wait, when the caller may have changed them.  A verification surface.
  *   lrc_pipe_trace_ms the time the trace launch of submit `ticket` spent between its stream reaching it and its last wave
  *                     (HIP events on the launch stream; inside the pipeline launches overlap, so this is longer than the
  *                     launch's share of the step).  Synchronises the host with that launch.

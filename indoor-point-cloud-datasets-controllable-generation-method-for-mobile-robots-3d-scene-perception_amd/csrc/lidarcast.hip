@@ -86,12 +86,17 @@ struct RebuildParams {
     uint32_t skip_slab;                      // tiles of this slab are not rebuilt (the caller scatters its own records); ~0u: none
 };
 
-// The lean record set of a pipeline submit (lrc_pipe_submit), as the scatter reads it: per ray the packed row
-// (x, y, z, label bits) exactly as it goes to lrc_compact_io::out_xyzl (zeros for a ray that is not kept), per 64-ray tile
-// the keep mask (bit l: lane l kept).  Only for segments of a multiple of 64 rays: tile t holds rays 64 t ... 64 t + 63.
+// The lean record set of a pipeline submit (lrc_pipe_submit), as its consumers read it: per ray the 12-byte record
+// (t bits, label, slot), per 64-ray tile the keep mask (bit l: lane l kept).  Only for segments of a multiple of 64 rays: tile t
+// holds rays 64 t ... 64 t + 63 of ONE pose.  The tile's form is the trace wave's own decision, read where the trace read it:
+// tab != NULL (the submit's launch carried this ray table) and the flag `same` of the tile's pose record in it -> RECORD form,
+// the output row is pair_row(pose record's origin, table row's h, t, label) and `row` was not written; otherwise ROW form, `row`
+// holds the packed row (x, y, z, label bits) exactly as it goes to lrc_compact_io::out_xyzl (zeros for a ray that is not kept).
 struct LeanIn {
+    const uint32_t* rec;       // three words per ray
     const float4* row;
     const uint64_t* keep_mask;
+    const float4* tab;         // the set's own ray table (RayPose below: rows of seg_len, then the pose records), or NULL
 };
 
 struct TraceParams {
@@ -140,11 +145,12 @@ struct TraceParams {
         lrc_compact_io io;
         LeanIn lean;               // plain form: the earlier scan's lean record set (io's t / point3 / sem / ins are not read)
     } pre;
-    // lean record set (scan pipeline): row != NULL -> write_back stores per ray the packed row and (t bits, slot), per wave
-    // the keep mask, and no column of `out`.  Wave-uniform: a run-time branch.
+    // lean record set (scan pipeline): row != NULL -> write_back stores per ray the 12-byte record, per wave the keep mask, and
+    // no column of `out`.  Wave-uniform: a run-time branch.  A wave that did not take the prepared path
+    // (no ray table, or its pose turns relative to pose 0) stores the packed row into `row` as well: see LeanIn.
     struct Lean {
         float4* row;
-        uint2* aux;                // (t bits, slot): t after range noise, slot = 0xFFFFFFFF for a ray that is not kept
+        uint32_t* rec;             // (t bits, label, slot): t after range noise; (inf, 0, 0xFFFFFFFF) for a ray that is not kept
         uint64_t* keep_mask;
     } lean;
     float qbase[3], qW[3], qinvW[3];   // normalised coordinate n = (x - qbase) * qinvW in [2, 4); qW = 1 / qinvW = 2^k
@@ -213,6 +219,12 @@ __device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t nwg) {
 }
 
 struct alignas(16) F4 { float x, y, z, w; };                       // plain 16-byte record (loads as dwordx4)
+// the 12-byte record of a lean record set (LeanIn) and its first two words, as the compiler's vector types at the alignment the
+// packed array gives them: one dwordx3 store, one dwordx2 load
+typedef uint32_t u32x3_ __attribute__((ext_vector_type(3)));
+typedef uint32_t u32x2_ __attribute__((ext_vector_type(2)));
+typedef u32x3_ rec3 __attribute__((aligned(4)));
+typedef u32x2_ rec2 __attribute__((aligned(4)));
 typedef __attribute__((address_space(4))) const float cfloat;      // constant address space: uniform loads become s_load
 __device__ __forceinline__ F4 ld_uniform(const float4* gp) {
     cfloat* c = (cfloat*)gp;
@@ -366,7 +378,8 @@ __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, u
         V3 hh, pp;
         if (have_h) {
             hh = h_in;
-            pp.x = o.x + hh.x * tbest; pp.y = o.y + hh.y * tbest; pp.z = o.z + hh.z * tbest;
+            const PairRow r = pair_row(o, hh, tbest, 0u);      // what the consumers of the record form again (LeanIn)
+            pp.x = r.x; pp.y = r.y; pp.z = r.z;
         } else {
             hit_point(o, d, tbest, hh, pp);
         }
@@ -417,14 +430,17 @@ __device__ __forceinline__ bool write_back(const TraceParams& p, uint64_t gid, u
         }
     }
     if (lean) {
-        // two stores per ray: the row as the scatter copies it, and what the expansion for lrc_pipe_records needs besides
-        // the keep mask as four 16-bit words: each quarter of the wave is a quarter of a 1-D tile (of four different ones in a
+        // one 12-byte store per ray: all a consumer needs to form the row of a prepared wave again (pair_row) and the expansion
+        // for lrc_pipe_records to find triangle id and normal.  A wave that did not take the prepared path (have_h is
+        // wave-uniform: one pose per tile) has no table row to form its point from later and stores the packed row beside it.
+        // The keep mask goes as four 16-bit words: each quarter of the wave is a quarter of a 1-D tile (of four different ones in a
         // four-line tile, lrc_device.h tile_ray), so up to four waves fill one mask, no atomics, nothing to zero.  The per-tile
         // counts of a lean set are the scan pass's to form (popcount of the masks, compact_scan_masks_kernel).
         const unsigned long long m = __ballot(keep);
         if ((tid & 15u) == 0) ((uint16_t*)p.lean.keep_mask)[gid >> 4] = (uint16_t)(m >> (tid & 48u));
-        p.lean.row[gid] = make_float4(px, py, pz, __uint_as_float(label));
-        p.lean.aux[gid] = make_uint2(__float_as_uint(t_out), keep ? best_slot : 0xFFFFFFFFu);
+        const rec3 r = {__float_as_uint(t_out), label, keep ? best_slot : 0xFFFFFFFFu};
+        *(rec3*)(p.lean.rec + gid * 3) = r;
+        if (!have_h) p.lean.row[gid] = make_float4(px, py, pz, __uint_as_float(label));
         return keep;
     }
     if (p.out.tile_count) {   // kept rays of this wave's 64 consecutive outputs (feeds lrc_compact_dev)
@@ -897,9 +913,76 @@ __device__ __forceinline__ void scatter_tiles_xyzl(const lrc_compact_io& io, uin
         }
     }
 }
-// scatter_tile from a lean record set (LeanIn): the tile's keep mask is one scalar load, a kept lane loads its row (one
-// 16-byte load) and every output is a function of that row and the lane -- the same values scatter_tile forms from the
-// 36-byte record.  seg_len % 64 == 0 (a lean set exists only then).
+// ---- the ray table of a prepared pipeline submit (lrc_pipe_submit; lrc_device.h ray_row; DESIGN.md section 5.2) -------------
+// One buffer behind TraceParams::ray_tab, for a table of N rows and P poses, in units of 16 bytes:
+//   [0, 2N)        per row i two records: (d.x, d.y, d.z, 0) and (inv.x, inv.y, inv.z, 0)      -- the prologue's two loads
+//   [2N, 3N)       per row i (h.x, h.y, h.z, 0)                      -- the epilogue's one load, and every record consumer's
+//   [3N, 3N + 4P)  per pose p a RayPose: whether its rotation block is pose 0's bit for bit (then the rows are its rays'),
+//                  its float32 origin and its float64 range-filter centre; read through the scalar cache
+// All of it is rebuilt for every submit from that submit's poses and table (ray_table_kernel): nothing is keyed on an
+// address, so a table edited in place or a new one at a recycled address cannot leave stale rows behind.  A pipeline holds
+// one table per record set: the consumers of a set's records (LeanIn) read the table its trace read.
+struct alignas(64) RayPose {
+    double cx, cy, cz;
+    uint32_t same;             // 1: the nine rotation doubles equal pose 0's as bit patterns (-0.0 != +0.0; a NaN equals only a NaN of the same bits)
+    float ox, oy, oz;          // (the flag between the two: centre + flag are one 32-byte load, flag + origin one of 16)
+    uint32_t pad[6];
+};
+static_assert(sizeof(RayPose) == 64, "RayPose: four 16-byte units");
+// (the trace kernel derives the offsets 2N and 3N from tiles_per_pose as N = 64 * tiles_per_pose: a pipeline allocates its
+// tables, and hence carries one, only in a build with kTBlock == 64 -- lrc_pipe_create)
+constexpr uint64_t kRayTabMaxRows = 1ull << 24;     // rows a pipeline prepares a table for (the offsets stay in 32 bits)
+__host__ __device__ inline uint64_t ray_tab_bytes(uint64_t N, uint64_t P) { return N * 48u + P * sizeof(RayPose); }
+
+// Streaming accesses of the scan pipeline's scatter: a record of a lean record set is read once, two launches after it was
+// written, and the caller's output row is written once and not read again by the library.  With non-temporal loads and stores
+// the pipelined step is 3-4 % faster on every scene (profiles/pipe_fused_scatter.txt, items 4-6) -- presumably because the
+// bytes no longer pass through L2 and the Infinity Cache in front of the tracing waves, which want the scene's nodes
+// there.  The trace's own stores of the set stay ordinary: streaming them measured slower.  The table's h rows are NOT
+// streamed: 1 MB that all poses of a submit share, and the trace of the same launch reads its own table's likewise.
+typedef float nt_float4 __attribute__((ext_vector_type(4)));       // the builtins take the compiler's vector types
+__device__ __forceinline__ void store_streaming(float4* q, float4 v) {
+    const nt_float4 w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, (nt_float4*)q);
+}
+__device__ __forceinline__ float4 load_streaming(const float4* q) {
+    const nt_float4 w = __builtin_nontemporal_load((const nt_float4*)q);
+    return make_float4(w.x, w.y, w.z, w.w);
+}
+
+// The form of the tiles of pose `seg` (wave-uniform) of a lean record set, decided where the trace wave decided it: the launch
+// carried a table and the pose record's flag `same` is set (trace_kernel: have_h).  One 16-byte scalar load, flag + origin.
+struct LeanPose { bool rec; V3 o; };
+__device__ __forceinline__ LeanPose lean_pose(const LeanIn& in, uint32_t seg_len, uint32_t seg) {
+    typedef __attribute__((address_space(4))) const RayPose cpose;
+    LeanPose q{false, V3{0.f, 0.f, 0.f}};
+    if (in.tab != nullptr) {
+        cpose* rp = (cpose*)(in.tab + (size_t)seg_len * 3u) + seg;
+        q.rec = rp->same != 0u;
+        q.o = V3{rp->ox, rp->oy, rp->oz};
+    }
+    return q;
+}
+// (t bits, label) of ray `ray` of the set and the unit vector of table row i, as the loads of a record-form tile
+template <bool STREAMING>      // (a template argument: two loads merged behind a run-time flag lose the hint)
+__device__ __forceinline__ rec2 lean_pair(const LeanIn& in, uint64_t ray) {
+    const rec2* q = (const rec2*)(in.rec + ray * 3);
+    if (STREAMING) return __builtin_nontemporal_load(q);
+    return *q;
+}
+__device__ __forceinline__ V3 lean_h(const LeanIn& in, uint32_t seg_len, uint32_t i) {
+    typedef float f32x3_ __attribute__((ext_vector_type(3)));
+    const f32x3_ h = *(const f32x3_*)(in.tab + (size_t)seg_len * 2u + i);
+    return V3{h.x, h.y, h.z};
+}
+__device__ __forceinline__ float4 lean_row(const LeanPose& ps, V3 h, rec2 a) {
+    const PairRow r = pair_row(ps.o, h, __uint_as_float(a.x), a.y);
+    return make_float4(r.x, r.y, r.z, __uint_as_float(r.label));
+}
+
+// scatter_tile from a lean record set (LeanIn): the tile's keep mask is one scalar load, a kept lane loads its record and
+// the table's unit vector (or, row form, its row: one 16-byte load) and every output is a function of that row and the lane --
+// the same values scatter_tile forms from the 36-byte record.  seg_len % 64 == 0 (a lean set exists only then).
 __device__ __forceinline__ void scatter_tile_lean(const lrc_compact_io& io, const LeanIn& in, uint64_t seg_len, uint64_t tps,
                                                   uint64_t tile, uint32_t lane, const uint32_t* tile_off,
                                                   const uint32_t* super_total) {
@@ -907,9 +990,11 @@ __device__ __forceinline__ void scatter_tile_lean(const lrc_compact_io& io, cons
     const unsigned long long m = ((cu64*)in.keep_mask)[tile];
     if (m == 0ull) return;
     const uint64_t sbase = super_prefix_wave(super_total, tile >> 10, lane);
-    if (!((m >> lane) & 1ull)) return;
     const uint64_t seg = tile / tps, i = (tile - seg * tps) * 64 + lane;
-    const float4 r = in.row[seg * seg_len + i];
+    const LeanPose ps = lean_pose(in, (uint32_t)seg_len, (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)seg));
+    if (!((m >> lane) & 1ull)) return;
+    const float4 r = ps.rec ? lean_row(ps, lean_h(in, (uint32_t)seg_len, (uint32_t)i), lean_pair<false>(in, seg * seg_len + i))
+                            : in.row[seg * seg_len + i];
     const uint64_t dst = sbase + tile_off[tile] + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
     const uint32_t lab = __float_as_uint(r.w);
     if (io.out_xyzl) ((float4*)io.out_xyzl)[dst] = r;
@@ -923,54 +1008,78 @@ __device__ __forceinline__ void scatter_tile_lean(const lrc_compact_io& io, cons
     if (io.out_range_origin) io.out_range_origin[dst] = __builtin_sqrtf((r.x * r.x + r.y * r.y) + r.z * r.z);   // as scatter_tile
 }
 
-// Streaming accesses of the scan pipeline's scatter: a row of a lean record set is read once, two launches after it was
-// written, and the caller's output row is written once and not read again by the library.  With non-temporal loads and stores
-// the pipelined step is 3-4 % faster on every scene (profiles/pipe_fused_scatter.txt, items 4-6) -- presumably because 134 MB
-// per launch no longer pass through L2 and the Infinity Cache in front of the tracing waves, which want the scene's nodes
-// there.  The trace's own stores of the set stay ordinary: streaming them measured slower.
-typedef float nt_float4 __attribute__((ext_vector_type(4)));       // the builtins take the compiler's vector types
-__device__ __forceinline__ void store_streaming(float4* q, float4 v) {
-    const nt_float4 w = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(w, (nt_float4*)q);
-}
-__device__ __forceinline__ float4 load_streaming(const float4* q) {
-    const nt_float4 w = __builtin_nontemporal_load((const nt_float4*)q);
-    return make_float4(w.x, w.y, w.z, w.w);
-}
-
-// scatter_tiles_xyzl from a lean record set: scalar loads of the keep masks instead of per-lane t loads, then one 16-byte row
-// load per lane instead of five loads per kept lane -- the row IS the output row.  Four tiles at a time: eight rows in flight
-// per lane (32 registers) pushed the trace kernel, whose registers this wave holds, into scratch.
+// scatter_tiles_xyzl from a lean record set: scalar loads of the keep masks instead of per-lane t loads, then per lane 8 bytes
+// of its record and the 12 of the table's unit vector -- or, row form, the 16-byte row, which IS the output row -- instead of
+// five loads per kept lane.  Four tiles at a time: eight rows in flight per lane (32 registers) pushed the trace kernel, whose
+// registers this wave holds, into scratch.  Four tiles of ONE pose share the form and the origin (one pose record load, one
+// branch around all their loads); a group that straddles two poses (tables of fewer than four tiles, or not a multiple of
+// four) goes tile by tile.  tile0 < 2^31 (the launch's grid).
 template <int R>
 __device__ __forceinline__ void scatter_tiles_xyzl_lean(const lrc_compact_io& io, const LeanIn& in, uint64_t ntiles, uint64_t tile0,
-                                                        uint32_t lane, const uint32_t* tile_off, const uint32_t* super_total) {
+                                                        uint32_t lane, const uint32_t* tile_off, const uint32_t* super_total,
+                                                        uint32_t seg_len, uint32_t tps) {
     typedef __attribute__((address_space(4))) const uint64_t cu64;
     typedef __attribute__((address_space(4))) const uint32_t cu32;
     constexpr int H = R < 4 ? R : 4;
     static_assert(R % H == 0, "R: a multiple of four, or below four");
     const uint64_t sbase = super_prefix_wave(super_total, tile0 >> 10, lane);
     const unsigned long long below = (1ull << lane) - 1ull;
+    float4* const out = (float4*)io.out_xyzl;
+    // pose and in-pose tile of the run's first tile by one division, of the others by counting (all wave-uniform)
+    uint32_t seg = (uint32_t)tile0 / tps, u = (uint32_t)tile0 - seg * tps;
 #pragma unroll
     for (int h = 0; h < R; h += H) {
+        const uint64_t t0 = tile0 + h;
+        if (u + (uint32_t)H > tps) {
+            for (int r = 0; r < H; ++r) {
+                const uint64_t tile = t0 + r;
+                if (tile < ntiles) {
+                    const unsigned long long m = ((cu64*)in.keep_mask)[tile];
+                    const uint32_t off = ((cu32*)tile_off)[tile];
+                    const LeanPose ps = lean_pose(in, seg_len, seg);
+                    if ((m >> lane) & 1ull)
+                        store_streaming(&out[sbase + off + (uint64_t)__popcll(m & below)],
+                                        ps.rec ? lean_row(ps, lean_h(in, seg_len, u * 64u + lane), lean_pair<true>(in, tile * 64 + lane))
+                                               : load_streaming(&in.row[tile * 64 + lane]));
+                }
+                if (++u == tps) { u = 0u; ++seg; }
+            }
+            continue;
+        }
         unsigned long long m[H];
         uint32_t off[H];
 #pragma unroll
         for (int r = 0; r < H; ++r) {
-            const uint64_t tile = tile0 + h + r;
-            const bool valid = tile < ntiles;          // wave-uniform
-            m[r] = valid ? ((cu64*)in.keep_mask)[tile] : 0ull;
-            off[r] = valid ? ((cu32*)tile_off)[tile] : 0u;
+            const bool valid = t0 + r < ntiles;          // wave-uniform
+            m[r] = valid ? ((cu64*)in.keep_mask)[t0 + r] : 0ull;
+            off[r] = valid ? ((cu32*)tile_off)[t0 + r] : 0u;
         }
-        // every lane of a tile with a kept ray loads its row: one coalesced 1 KiB read per tile and no divergent branch
-        // between the loads, so all of them are in flight at once (rays that are not kept have zero rows, never stored)
-        float4 row[H];
+        // (a group wholly past the last tile may be past the last pose record too: it loads nothing)
+        const LeanPose ps = t0 < ntiles ? lean_pose(in, seg_len, seg) : LeanPose{false, V3{0.f, 0.f, 0.f}};
+        // every lane of a tile with a kept ray loads: coalesced reads and no divergent branch between the loads, so all of
+        // them are in flight at once (what a ray that is not kept loads is never stored)
+        if (ps.rec) {
+            rec2 a[H];
+            V3 hv[H];
 #pragma unroll
-        for (int r = 0; r < H; ++r)
-            row[r] = m[r] != 0ull ? load_streaming(&in.row[(tile0 + h + r) * 64 + lane]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int r = 0; r < H; ++r) {
+                a[r] = m[r] != 0ull ? lean_pair<true>(in, (t0 + r) * 64 + lane) : rec2{0u, 0u};
+                hv[r] = m[r] != 0ull ? lean_h(in, seg_len, (u + r) * 64u + lane) : V3{0.f, 0.f, 0.f};
+            }
 #pragma unroll
-        for (int r = 0; r < H; ++r)
-            if ((m[r] >> lane) & 1ull)
-                store_streaming(&((float4*)io.out_xyzl)[sbase + off[r] + (uint64_t)__popcll(m[r] & below)], row[r]);
+            for (int r = 0; r < H; ++r)
+                if ((m[r] >> lane) & 1ull) store_streaming(&out[sbase + off[r] + (uint64_t)__popcll(m[r] & below)], lean_row(ps, hv[r], a[r]));
+        } else {
+            float4 row[H];
+#pragma unroll
+            for (int r = 0; r < H; ++r)
+                row[r] = m[r] != 0ull ? load_streaming(&in.row[(t0 + r) * 64 + lane]) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int r = 0; r < H; ++r)
+                if ((m[r] >> lane) & 1ull) store_streaming(&out[sbase + off[r] + (uint64_t)__popcll(m[r] & below)], row[r]);
+        }
+        u += (uint32_t)H;
+        if (u == tps) { u = 0u; ++seg; }
     }
 }
 #ifndef LRC_PRE_TILES
@@ -980,28 +1089,9 @@ constexpr int kPreTiles = LRC_PRE_TILES;      // tiles per leading workgroup of 
 
 template <int I> struct IntTag { static constexpr int value = I; };
 
-// ---- the ray table of a prepared pipeline submit (lrc_pipe_submit; lrc_device.h ray_row; DESIGN.md section 5.2) -------------
-// One buffer behind TraceParams::ray_tab, for a table of N rows and P poses, in units of 16 bytes:
-//   [0, 2N)        per row i two records: (d.x, d.y, d.z, 0) and (inv.x, inv.y, inv.z, 0)      -- the prologue's two loads
-//   [2N, 3N)       per row i (h.x, h.y, h.z, 0)                                                -- the epilogue's one load
-//   [3N, 3N + 4P)  per pose p a RayPose: whether its rotation block is pose 0's bit for bit (then the rows are its rays'),
-//                  its float32 origin and its float64 range-filter centre; read through the scalar cache
-// All of it is rebuilt for every submit from that submit's poses and table (ray_table_kernel): nothing is keyed on an
-// address, so a table edited in place or a new one at a recycled address cannot leave stale rows behind.
-struct alignas(64) RayPose {
-    double cx, cy, cz;
-    uint32_t same;             // 1: the nine rotation doubles equal pose 0's as bit patterns (-0.0 != +0.0; a NaN equals only a NaN of the same bits)
-    float ox, oy, oz;          // (the flag between the two: centre + flag are one 32-byte load, flag + origin one of 16)
-    uint32_t pad[6];
-};
-static_assert(sizeof(RayPose) == 64, "RayPose: four 16-byte units");
-// (the kernel derives the offsets 2N and 3N from tiles_per_pose as N = 64 * tiles_per_pose: a pipeline allocates its tables,
-// and hence carries one, only in a build with kTBlock == 64 -- lrc_pipe_create)
-constexpr uint64_t kRayTabMaxRows = 1ull << 24;     // rows a pipeline prepares a table for (the offsets stay in 32 bits)
-__host__ __device__ inline uint64_t ray_tab_bytes(uint64_t N, uint64_t P) { return N * 48u + P * sizeof(RayPose); }
-
-// One-wave workgroups, like the scan pass: beside the other stream's running trace launch they are handed wave slots one by
-// one.  Lane-strided over the rows, then over the poses.
+// The kernel that fills a ray table (its layout: RayPose, in front of the lean scatters, which read it too).  One-wave
+// workgroups, like the scan pass: beside the other stream's running trace launch they are handed wave slots one by one.
+// Lane-strided over the rows, then over the poses.
 __global__ __launch_bounds__(64) void ray_table_kernel(const double* __restrict__ poses16, uint32_t P,
                                                        const double* __restrict__ dirs3, uint32_t N, float4* __restrict__ tab) {
     const uint32_t first = blockIdx.x * 64u + threadIdx.x, step = gridDim.x * 64u;
@@ -1063,7 +1153,7 @@ __global__ __launch_bounds__(kTBlock, gen_min_waves(GEN, QN, STATS)) void trace_
             if (tile0 < p.pre.ntiles) {      // the earlier scan's records are a lean set (only fused submits ride here)
                 if (p.pre.rows_only) {
                     scatter_tiles_xyzl_lean<kPreTiles>(p.pre.io, p.pre.lean, p.pre.ntiles, tile0, tid, p.pre.tile_off,
-                                                       p.pre.super_total);
+                                                       p.pre.super_total, (uint32_t)p.pre.seg_len, (uint32_t)p.pre.tps);
                 } else {
                     for (int r = 0; r < kPreTiles; ++r)
                         if (tile0 + r < p.pre.ntiles)
@@ -1826,28 +1916,32 @@ __global__ __launch_bounds__(kBlock) void compact_scatter_lean_kernel(const lrc_
     scatter_tile_lean(io, in, seg_len, tps, tile, threadIdx.x & 63u, tile_off, super_total);
 }
 
-// lrc_pipe_records of a lean set: the 36-byte record of every ray rebuilt from (row, t, slot) -- the triangle id through the
-// scene's slot table, the normal by the helper write_back forms it with; a ray that is not kept gets the miss record
-__global__ __launch_bounds__(kBlock) void expand_lean_kernel(const float4* __restrict__ row, const uint2* __restrict__ aux,
+// lrc_pipe_records of a lean set: the 36-byte record of every ray rebuilt from its 12-byte record (t, label, slot) -- the
+// triangle id through the scene's slot table, the normal by the helper write_back forms it with, the point by pair_row from the
+// set's own table (or, a tile in the row form, from its row: LeanIn); a ray that is not kept gets the miss record.  Reads nothing
+// of the caller's: its poses and table may have changed since the submit.  seg_len % 64 == 0: a wave lies in one pose.
+__global__ __launch_bounds__(kBlock) void expand_lean_kernel(const LeanIn in, uint64_t seg_len,
                                                              const uint32_t* __restrict__ slot_prim, const float4* __restrict__ tris,
                                                              lrc_hits out, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const float4 r = row[i];
-    const uint2 a = aux[i];
-    const uint32_t lab = __float_as_uint(r.w);
+    const uint64_t seg = i / seg_len;
+    const LeanPose ps = lean_pose(in, (uint32_t)seg_len, (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)seg));
+    const rec3 a = *(const rec3*)(in.rec + i * 3);
     uint32_t prim = LRC_INVALID_PRIM;
-    float nx = 0.f, ny = 0.f, nz = 0.f;
-    if (a.y != 0xFFFFFFFFu) {
-        prim = slot_prim[a.y];
-        slot_normal(tris[(size_t)a.y * 3 + 2], nx, ny, nz);
+    float nx = 0.f, ny = 0.f, nz = 0.f, px = 0.f, py = 0.f, pz = 0.f;
+    if (a.z != 0xFFFFFFFFu) {
+        prim = slot_prim[a.z];
+        slot_normal(tris[(size_t)a.z * 3 + 2], nx, ny, nz);
+        const float4 r = ps.rec ? lean_row(ps, lean_h(in, (uint32_t)seg_len, (uint32_t)(i - seg * seg_len)), rec2{a.x, a.y}) : in.row[i];
+        px = r.x; py = r.y; pz = r.z;
     }
     out.t[i] = __uint_as_float(a.x);
     out.prim[i] = prim;
     out.normal3[i * 3] = nx; out.normal3[i * 3 + 1] = ny; out.normal3[i * 3 + 2] = nz;
-    out.point3[i * 3] = r.x; out.point3[i * 3 + 1] = r.y; out.point3[i * 3 + 2] = r.z;
-    out.sem[i] = (uint16_t)(lab & 0xFFFFu);
-    out.ins[i] = (uint16_t)(lab >> 16);
+    out.point3[i * 3] = px; out.point3[i * 3 + 1] = py; out.point3[i * 3 + 2] = pz;
+    out.sem[i] = (uint16_t)(a.y & 0xFFFFu);
+    out.ins[i] = (uint16_t)(a.y >> 16);
 }
 
 // |p| of assembled (x, y, z, label) rows from the WORLD origin, float32, as np.linalg.norm(points, axis=1) forms it
@@ -2017,6 +2111,16 @@ void lrc_internal_ray_table_rows(const double* rot9, const double* dirs3, uint64
         const RayRow r = ray_row(rot9, dirs3[3 * i], dirs3[3 * i + 1], dirs3[3 * i + 2]);
         float* q = out9 + 9 * i;
         q[0] = r.d.x; q[1] = r.d.y; q[2] = r.d.z; q[3] = r.inv.x; q[4] = r.inv.y; q[5] = r.inv.z; q[6] = r.h.x; q[7] = r.h.y; q[8] = r.h.z;
+    }
+}
+
+// test hook (tests/test_pipe_pair_rows_host.py): the output rows of n rays from origin, unit vector, t and label, made by the host
+// compilation of the very function the trace's write-back and the consumers of a lean record set call (lrc_device.h, pair_row):
+// per ray 4 words x, y, z, label
+void lrc_internal_pair_rows(const float* o3, const float* h3, const float* t, const uint32_t* label, uint64_t n, uint32_t* out4) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const PairRow r = pair_row(V3{o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]}, V3{h3[3 * i], h3[3 * i + 1], h3[3 * i + 2]}, t[i], label[i]);
+        std::memcpy(out4 + 4 * i, &r, 16);
     }
 }
 
@@ -3058,10 +3162,11 @@ int lrc_compact_dev(lrc_ctx* ctx, uint64_t nseg, uint64_t seg_len, const lrc_com
 // a launch at all: it rides at the FRONT of the trace launch of submit k+2 (same stream, TraceParams::pre: one tile per
 // one-wave workgroup), so it is handed out exactly when the previous launch's tail begins and is gone in microseconds.  Four
 // record sets: set k is read by launch k+2 and written again by launch k+4, both on its own stream.
-// A fused submit writes a set's LEAN form: per ray the packed row and (t, slot), 24 B, per tile the keep mask -- all the
-// scatter reads, two stores per ray instead of ten, no triangle id and no normal in the trace.  The
-// complete 36-byte record, in arrays of its own beside the lean ones, is what the plain fallback and the sharded submits
-// write, and what lrc_pipe_records expands a lean set into on demand.
+// A fused submit writes a set's LEAN form: per ray the record (t, label, slot), 12 B, per tile the keep mask -- one store
+// per ray instead of ten, no triangle id and no normal in the trace, and no point: the consumers form the output row from the
+// record and the set's ray table (LeanIn; a wave that did not take the table stores its 16-byte row as well; DESIGN.md section
+// 5.2).  The complete 36-byte record, in arrays of its own beside the lean ones, is what the plain fallback and the sharded
+// submits write, and what lrc_pipe_records expands a lean set into on demand.
 #ifndef LRC_PIPE_TILE_LINES
 #define LRC_PIPE_TILE_LINES 4      // lines per tile of an automatic submit (profiles/trace_line_group_tiles.txt)
 #endif
@@ -3075,8 +3180,8 @@ struct lrc_pipe {
     static constexpr int kSets = 4;
     void* slab[kSets] = {};                                  // one allocation per record set
     lrc_hits rec[kSets] = {};
-    float4* row[kSets] = {};                                 // the lean form (row, aux, keep_mask; tile_count is rec's)
-    uint2* aux[kSets] = {};
+    uint32_t* rec3[kSets] = {};                              // the lean form (rec3, row, keep_mask; tile_count is rec's)
+    float4* row[kSets] = {};                                 // ... its rows: written by the waves that took no table row only
     uint64_t* keep_mask[kSets] = {};
     bool lean[kSets] = {};                                   // the set holds its last submit in the lean form ...
     bool expanded[kSets] = {};                               // ... and lrc_pipe_records has rebuilt rec from it
@@ -3104,10 +3209,13 @@ struct lrc_pipe {
     // line-group tiles (lrc_pipe_set_tile_lines): lines per tile asked for (0: automatic = 4 where the table has a group of
     // four), the split line detected with line_auto, and what the last launch ran with
     uint32_t lines_hint = 0, split_auto = 0, lines_last = 1, group_last = 0;
-    // prepared submits (lrc_pipe_set_ray_table; ray_table_kernel): one ray table per trace stream -- the kernel that fills it
-    // for submit k sits on that stream between the scan pass of submit k - 2 and the trace of submit k, so stream order alone
-    // keeps it from being rewritten while a trace reads it.  NULL: not a fused pipeline, or more rows than kRayTabMaxRows.
-    float4* ray_tab[2] = {};
+    // prepared submits (lrc_pipe_set_ray_table; ray_table_kernel): one ray table per record set, because the set's records are
+    // read against it.  Table k % 4 is written by the ray_table_kernel of submit k, read by trace k, by the leading workgroups
+    // of launch k + 2, by lrc_pipe_wait's plain scatter and by lrc_pipe_records' expansion, and written again by submit k + 4.
+    // Every one of these is enqueued on trace stream k % 2 (k, k + 2 and k + 4 share it), in this order, so stream order alone
+    // keeps the table from being rewritten while anything reads it.  NULL: not a fused pipeline, or more rows than kRayTabMaxRows.
+    float4* ray_tab[kSets] = {};
+    bool tabbed[kSets] = {};                                 // the set's last submit carried its table (LeanIn::tab)
     bool use_ray_tab = true;
     bool ray_tab_last = false;                               // the last submit's launch carried a table
 };
@@ -3123,8 +3231,9 @@ int lrc_pipe_destroy(lrc_pipe* pp) {
     }
     if (pp->ev_expand) (void)hipEventDestroy(pp->ev_expand);
     if (pp->d_line) (void)hipFree(pp->d_line);
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < lrc_pipe::kSets; ++k)
         if (pp->ray_tab[k]) (void)hipFree(pp->ray_tab[k]);
+    for (int k = 0; k < 2; ++k) {
         if (pp->ev_flush[k]) (void)hipEventDestroy(pp->ev_flush[k]);
         pp->scratch[k].release();        // (the pipeline's device is current: above)
         pp->gscratch[k].release();
@@ -3153,11 +3262,11 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
     auto bail = [&](int rc) { (void)lrc_pipe_destroy(pp); return rc; };
     auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
     // a record set: t | prim | normal3 | point3 | sem | ins | tile_count, 36 B per ray + 4 B per 64 rays, and for a fused
-    // pipeline beside it the lean form row | aux | keep_mask, 24 B per ray + 8 B per 64 rays
+    // pipeline beside it the lean form row | rec3 | keep_mask, 16 + 12 B per ray + 8 B per 64 rays
     const uint64_t off_t = 0, off_prim = off_t + up(4 * n), off_nrm = off_prim + up(4 * n), off_pt = off_nrm + up(12 * n),
                    off_sem = off_pt + up(12 * n), off_ins = off_sem + up(2 * n), off_tc = off_ins + up(2 * n),
-                   off_row = off_tc + up(4 * ((n + 63) / 64)), off_aux = off_row + (pp->fused ? up(16 * n) : 0),
-                   off_km = off_aux + (pp->fused ? up(8 * n) : 0), bytes = off_km + (pp->fused ? up(8 * ((n + 63) / 64)) : 0);
+                   off_row = off_tc + up(4 * ((n + 63) / 64)), off_rec3 = off_row + (pp->fused ? up(16 * n) : 0),
+                   off_km = off_rec3 + (pp->fused ? up(12 * n) : 0), bytes = off_km + (pp->fused ? up(8 * ((n + 63) / 64)) : 0);
     for (int k = 0; k < lrc_pipe::kSets; ++k) {
         hipError_t e = hipMalloc(&pp->slab[k], bytes);
         if (e != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory for the record sets")); }
@@ -3167,7 +3276,7 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
         h.point3 = (float*)(b + off_pt); h.sem = (uint16_t*)(b + off_sem); h.ins = (uint16_t*)(b + off_ins);
         h.tile_count = (uint32_t*)(b + off_tc);
         if (pp->fused) {
-            pp->row[k] = (float4*)(b + off_row); pp->aux[k] = (uint2*)(b + off_aux); pp->keep_mask[k] = (uint64_t*)(b + off_km);
+            pp->row[k] = (float4*)(b + off_row); pp->rec3[k] = (uint32_t*)(b + off_rec3); pp->keep_mask[k] = (uint64_t*)(b + off_km);
         }
     }
     // The two trace streams must reach the hardware on queues of their own, or their launches cannot overlap.  The runtime
@@ -3191,7 +3300,7 @@ int lrc_pipe_create(lrc_scene* s, uint64_t max_poses, uint64_t rays_per_pose, lr
     if (hipEventCreateWithFlags(&pp->ev_expand, hipEventDisableTiming) != hipSuccess) return bail(fail(LRC_ERR_HIP, "lrc_pipe_create: event"));
     if (pp->fused && hipMalloc((void**)&pp->d_line, 2 * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory")); }
     if (pp->fused && kTBlock == 64 && rays_per_pose <= kRayTabMaxRows)
-        for (int k = 0; k < 2; ++k)
+        for (int k = 0; k < lrc_pipe::kSets; ++k)
             if (hipMalloc((void**)&pp->ray_tab[k], ray_tab_bytes(rays_per_pose, max_poses)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(LRC_ERR_OOM, "lrc_pipe_create: out of device memory for the ray tables")); }
     *out_pipe = pp;
     return LRC_OK;
@@ -3209,8 +3318,8 @@ lrc_compact_io pipe_io(const lrc_pipe* pp, int set) {
 }
 // ... and its lean form (row == NULL: the set holds complete records)
 LeanIn pipe_lean(const lrc_pipe* pp, int set) {
-    if (!pp->lean[set]) return LeanIn{nullptr, nullptr};
-    return LeanIn{pp->row[set], pp->keep_mask[set]};
+    if (!pp->lean[set]) return LeanIn{nullptr, nullptr, nullptr, nullptr};
+    return LeanIn{pp->rec3[set], pp->row[set], pp->keep_mask[set], pp->tabbed[set] ? pp->ray_tab[set] : nullptr};
 }
 // before the launch of a submit overwrites `set` on stream T: an assembly that read the set's own records in a launch on the
 // OTHER trace stream (lag 1 or 3) is ordered before this launch only by dispatch, so T waits for that launch's event.  Lag 2
@@ -3251,7 +3360,7 @@ int lrc_pipe_set_ray_table(lrc_pipe* pp, int enable) {
 // pointer: 48 bytes per table row, then 64 per pose, see RayPose), or NULL -- the table changes no byte of the outputs, so only
 // its own content can tell whether it was there and which poses took it
 const void* lrc_internal_pipe_ray_table(const lrc_pipe* pp) {
-    return pp && pp->ray_tab_last ? (const void*)pp->ray_tab[(pp->ticket - 1) % 2] : nullptr;
+    return pp && pp->ray_tab_last ? (const void*)pp->ray_tab[(pp->ticket - 1) % lrc_pipe::kSets] : nullptr;
 }
 
 int lrc_pipe_set_line_width(lrc_pipe* pp, uint64_t line_width) {
@@ -3284,7 +3393,7 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     p.dirs3 = d_dirs3;
     scan_fields(p, N, P * N, max_range, &pp->rec[set]);
     if (pp->fused) {           // the lean form: only what the scatter reads (the plain fallback below reads the full record)
-        p.lean.row = pp->row[set]; p.lean.aux = pp->aux[set]; p.lean.keep_mask = pp->keep_mask[set];
+        p.lean.row = pp->row[set]; p.lean.rec = pp->rec3[set]; p.lean.keep_mask = pp->keep_mask[set];
         // line-group tiles: the hinted line width, or the table's own, detected once per table address -- on the caller's
         // stream, whose position the table is valid at, with a 4-byte read-back; nothing afterwards.  A stale width (a new
         // table at a recycled address, a table edited in place) maps the rays as well as the right one: same bytes.
@@ -3306,16 +3415,16 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
             p.line_group = line_group_for(pp->line_hint == 0 ? pp->split_auto : 0u,
                                           pp->lines_hint == 0u ? (uint32_t)LRC_PIPE_TILE_LINES : pp->lines_hint);
     }
-    // prepared submit: this stream's ray table is rebuilt from THIS submit's poses and table, behind the scan pass of submit
+    // prepared submit: this set's ray table is rebuilt from THIS submit's poses and table, behind the scan pass of submit
     // k - 2 and in front of the trace (at most 64 one-wave workgroups: a few microseconds on an idle GPU, and beside the other
     // stream's launch they trickle in during a step that has nothing else for this stream to do)
     pp->ray_tab_last = false;
-    if (pp->fused && pp->use_ray_tab && pp->ray_tab[lane]) {
+    if (pp->fused && pp->use_ray_tab && pp->ray_tab[set]) {
         const uint64_t rows = N > P ? N : P, waves = blocks_of(rows, 64);
         hipLaunchKernelGGL(ray_table_kernel, dim3((uint32_t)(waves < 64 ? waves : 64)), dim3(64), 0, T, d_poses16, (uint32_t)P, d_dirs3,
-                           (uint32_t)N, pp->ray_tab[lane]);
+                           (uint32_t)N, pp->ray_tab[set]);
         LRC_HIP(hipGetLastError());
-        p.ray_tab = pp->ray_tab[lane];
+        p.ray_tab = pp->ray_tab[set];
         pp->ray_tab_last = true;
     }
     // the rows of submit k - 2 (this stream's previous scan; its scan pass was enqueued behind its trace) ride in front
@@ -3345,6 +3454,11 @@ int lrc_pipe_submit(lrc_pipe* pp, const double* d_poses16, uint64_t P, const dou
     pp->out[set] = *d_out;
     pp->poses[set] = P;
     pp->lean[set] = p.lean.row != nullptr;
+    // what the trace kernel calls `tabbed`: with it, the pose records of the set's table say which tiles are in the record form
+    // (read back from the launch's own argument block: launch_trace fills tiles_per_pose, and a laboratory kernel that takes
+    // no table drops the pointer)
+    pp->tabbed[set] = p.lean.row != nullptr && p.ray_tab != nullptr && p.tiles_per_pose != 0u;
+    pp->ray_tab_last = p.ray_tab != nullptr;
     pp->expanded[set] = false;
     if (pp->fused) {
         // the scan pass over this scan's per-wave keep counts: 32-64 one-wave workgroups behind the trace; the rows follow
@@ -3594,7 +3708,7 @@ int lrc_pipe_records(lrc_pipe* pp, uint64_t ticket, lrc_hits* out_records) {
         hipStream_t T = pp->s_trace[(ticket - 1) % 2];
         const uint64_t n = pp->poses[set] * pp->rays_per_pose;
         hipLaunchKernelGGL(expand_lean_kernel, dim3((uint32_t)blocks_of(n, kBlock)), dim3(kBlock), 0, T,
-                           (const float4*)pp->row[set], (const uint2*)pp->aux[set], (const uint32_t*)s->d_slot_prim,
+                           pipe_lean(pp, set), pp->rays_per_pose, (const uint32_t*)s->d_slot_prim,
                            (const float4*)s->d_tris, pp->rec[set], n);
         LRC_HIP(hipGetLastError());
         LRC_HIP(hipEventRecord(pp->ev_expand, T));

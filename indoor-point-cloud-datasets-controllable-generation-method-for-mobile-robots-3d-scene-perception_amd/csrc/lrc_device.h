@@ -386,6 +386,14 @@ LRC_HDI RayRow ray_row(const double* R, double a, double b, double c) {
     r.h = unit_dir(r.d);
     return r;
 }
+// The packed output row (x, y, z, label bits) of a ray of a prepared submit from what its 12-byte record and the submit's table
+// hold: p = o + h * t, numpy float32, one rounding per operation (multiply, then add: the file is built with -ffp-contract=off),
+// o the pose record's float32 origin and h the table row's unit vector.  The write-back of the trace (for its range filter) and
+// every consumer of a record set (the scatters, the expansion for lrc_pipe_records) form the point here, so they cannot drift.
+struct PairRow { float x, y, z; uint32_t label; };
+LRC_HDI PairRow pair_row(V3 o, V3 h, float t, uint32_t label) {
+    return PairRow{o.x + h.x * t, o.y + h.y * t, o.z + h.z * t, label};
+}
 
 // ---- two-line tiles of the scan pipeline ----------------------------------------------------------
 // A pose of tpp tiles of 64 rays, its rays in scan lines of W = 64 * wt consecutive table rows.  Tile u of the pose does not

@@ -252,6 +252,9 @@ static int launch_trace_lab(lrc_scene* s, TraceParams& p, int gen, hipStream_t s
         const uint64_t nb = (p.total + 64ull * K - 1) / (64ull * K);
         const size_t ldsK = ((size_t)depth * 64 + (size_t)K * 64 * 2) * sizeof(int);
         static const int rw = env_int("LRC_REFILL_W", 0);
+        // this kernel takes no ray table: the launch carries none, so that the consumers of a pipeline's lean record set
+        // (LeanIn), who decide a tile's form by the table the launch carried, find the rows its write_back stores
+        p.ray_tab = nullptr;
 #define LRC_RF(KK, WW) hipLaunchKernelGGL((trace_refill_kernel<KK, WW>), dim3((uint32_t)nb), dim3(kTBlock), ldsK, st, p, depth)
         if (K == 4) { if (rw >= 7) LRC_RF(4, 7); else LRC_RF(4, 5); }
         else { if (rw >= 7) LRC_RF(2, 7); else LRC_RF(2, 6); }
