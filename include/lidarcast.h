@@ -1306,7 +1306,12 @@ int lrc_rbf_kernel_sum(lrc_ctx* ctx, const float* a3, uint64_t n, const float* b
  *              distances (dx*dx + dy*dy) + dz*dz to rows of the same instance, itself included, ascending, one after
  *              the other) / k.
  *   filter   : mean = sum_{avg>0} avg / n, std = sqrt(sum_{avg>0} (avg - mean)^2 / (n - 1)), threshold = mean +
- *              std_ratio * std; a row is kept iff avg > 0 && avg < threshold (k or more coincident rows go).
+ *              std_ratio * std; a row is kept iff avg > 0 && avg < threshold (k or more coincident rows go).  An
+ *              instance of one row with k == 1 (and min_points <= 1) is filtered: mean = 0, 0 / 0 under the root makes
+ *              the threshold a NaN (sign and payload unspecified), and the row is removed.
+ *   box      : min3 / max3 are the float32 minimum / maximum of the kept rows as numpy's points.min(axis=0) /
+ *              .max(axis=0) return them: an extreme that equals zero has the sign of the last kept row (ascending row
+ *              order) whose coordinate on that axis is +0 or -0; every other extreme is the plain minimum / maximum.
  * One lrc_box per instance of min_points rows or more, ordered by (position of the class in class_ids, ins); the
  * call writes min(total, capacity) of them and the total to *out_num_boxes.  The optional per-row outputs (num_rows
  * entries, input order): avg (-1 where the filter did not run) and keep (1 = the row is in its instance's box).
@@ -1320,7 +1325,7 @@ typedef struct lrc_box {
     uint32_t num_points;     /* rows of the instance                                               */
     uint32_t num_kept;       /* rows inside the box (0: the filter removed all; min3 = +inf, max3 = -inf) */
     uint32_t filtered;       /* 1: num_points >= k and the filter ran; 0: every row kept             */
-    float    min3[3];        /* float32 minimum of the kept rows                                   */
+    float    min3[3];        /* float32 minimum of the kept rows (a zero: the last kept zero row's) */
     float    max3[3];
     double   mean;           /* filter statistics; 0 and +inf when filtered == 0                    */
     double   threshold;
@@ -1392,7 +1397,12 @@ int lrc_cloud_preprocess_dev(lrc_ctx* ctx, const double* d_points3, uint64_t n, 
  *   m >= k   : exactly the outlier stage of lrc_cloud_preprocess(nb_neighbors = k, std_ratio) run on the object's rows
  *              alone, bit for bit: neighbours come only from the same object, avg = (sum of the square roots of the k
  *              smallest float64 squared distances (dx*dx + dy*dy) + dz*dz, itself included, ascending) / k, mean and
- *              std reduced in the order lrc_cloud_preprocess fixes for m rows, keep = avg > 0 && avg < threshold.
+ *              std reduced in the order lrc_cloud_preprocess fixes for m rows, keep = avg > 0 && avg < threshold.  An
+ *              object of one row with k == 1 is filtered: mean = 0, 0 / 0 under the root makes the threshold a NaN
+ *              (sign and payload unspecified), and the row is removed.
+ *   box      : min3 / max3 are the float64 minimum / maximum of the kept rows as numpy's points.min(axis=0) /
+ *              .max(axis=0) return them: an extreme that equals zero has the sign of the last kept row whose coordinate
+ *              on that axis is +0 or -0; every other extreme is the plain minimum / maximum.
  * One lrc_objbox per object, in object order (HOST memory in both entry points).  The optional per-row outputs: out_kept
  * (n entries; the kept rows' indices, ascending, so object s's kept rows start at the sum of num_kept over the objects
  * before it), avg and keep (n entries, input order).  1 <= k <= 32, finite std_ratio > 0, n < 2^31 and num_objects <
@@ -1404,7 +1414,7 @@ typedef struct lrc_objbox {
     uint64_t num_kept;       /* rows inside the box (0: the filter removed all; min3 = +inf, max3 = -inf) */
     uint32_t filtered;       /* 1: num_points >= k and the filter ran; 0: every row kept             */
     uint32_t reserved_;
-    double   min3[3];        /* float64 minimum of the kept rows                                   */
+    double   min3[3];        /* float64 minimum of the kept rows (a zero: the last kept zero row's) */
     double   max3[3];
     double   mean;           /* filter statistics; 0 and +inf when filtered == 0                    */
     double   threshold;

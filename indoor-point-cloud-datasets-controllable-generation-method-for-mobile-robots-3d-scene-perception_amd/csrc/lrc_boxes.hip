@@ -13,7 +13,8 @@
 //      instance, itself included, over expanding cube shells of cells until the k-th cannot be beaten (lrc_nn.hip's
 //      exactness argument); avg = (sum of the k square roots, ascending, one after the other) / k;
 //   4. one workgroup per segment: mean = sum_{avg>0} avg / n and std = sqrt(sum_{avg>0} (avg-mean)^2 / (n-1)) in a
-//      fixed reduction order, thr = mean + std_ratio * std, keep = avg > 0 && avg < thr, min / max of the kept rows.
+//      fixed reduction order, thr = mean + std_ratio * std, keep = avg > 0 && avg < thr, min / max of the kept rows
+//      (as numpy's min / max over the rows: a zero extreme has the sign of the last kept zero row).
 // The k-best list lives in registers: one instantiation per list length, compile-time indices only (no scratch).
 // Only distances are used, so ties and the cell size cannot change a result.
 #include <hip/hip_runtime.h>
@@ -264,6 +265,9 @@ __device__ double block_sum(double v, double* red) {
 // one workgroup per segment: statistics, keep flags, box of the kept rows.  Every sum has one fixed order, whatever the
 // grid: each lane accumulates rows t, t+256, ... of the instance (ascending row order) in turn, then a fixed tree over
 // the lanes.
+// zr: per axis, 1 + the position in the instance of the last kept row whose coordinate is +0 or -0.  numpy's min / max
+// over the rows (a running np.minimum / np.maximum, row after row) keeps the later of two equal values, so a zero
+// extreme takes the sign of the last kept zero row; fminf / fmaxf and the tree over the lanes cannot know which that is.
 __global__ __launch_bounds__(kBlock) void box_stats_kernel(const float4* __restrict__ xyzl, const uint32_t* __restrict__ rows,
                                                            const double* __restrict__ avg,
                                                            const uint32_t* __restrict__ seg_start,
@@ -274,6 +278,7 @@ __global__ __launch_bounds__(kBlock) void box_stats_kernel(const float4* __restr
     __shared__ double red[kBlock];
     __shared__ float fred[6][kBlock];
     __shared__ uint32_t cred[kBlock];
+    __shared__ uint32_t zred[3][kBlock];
     const uint32_t s = blockIdx.x, t = threadIdx.x;
     const uint32_t a = seg_start[s], n = seg_count[s];
     if (n < min_points) {
@@ -299,7 +304,7 @@ __global__ __launch_bounds__(kBlock) void box_stats_kernel(const float4* __restr
         thr = mean + std_ratio * sd;
     }
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    uint32_t kept = 0;
+    uint32_t kept = 0, zr[3] = {0, 0, 0};
     for (uint32_t j = t; j < n; j += kBlock) {
         const double v = filtered ? avg[a + j] : -1.0;
         const bool keep = !filtered || (v > 0.0 && v < thr);
@@ -309,12 +314,16 @@ __global__ __launch_bounds__(kBlock) void box_stats_kernel(const float4* __restr
             ++kept;
             lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
             hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
+            // positions ascend in a lane: the last one wins
+            if ((bits_of(p.x) << 1) == 0) zr[0] = j + 1;
+            if ((bits_of(p.y) << 1) == 0) zr[1] = j + 1;
+            if ((bits_of(p.z) << 1) == 0) zr[2] = j + 1;
         }
         if (out_avg) out_avg[r] = v;
         if (out_keep) out_keep[r] = keep ? 1 : 0;
     }
     __syncthreads();
-    for (int c = 0; c < 3; ++c) { fred[c][t] = lo[c]; fred[3 + c][t] = hi[c]; }
+    for (int c = 0; c < 3; ++c) { fred[c][t] = lo[c]; fred[3 + c][t] = hi[c]; zred[c][t] = zr[c]; }
     cred[t] = kept;
     __syncthreads();
     for (int w = kBlock / 2; w > 0; w >>= 1) {
@@ -322,6 +331,7 @@ __global__ __launch_bounds__(kBlock) void box_stats_kernel(const float4* __restr
             for (int c = 0; c < 3; ++c) {
                 fred[c][t] = fminf(fred[c][t], fred[c][t + w]);
                 fred[3 + c][t] = fmaxf(fred[3 + c][t], fred[3 + c][t + w]);
+                zred[c][t] = max(zred[c][t], zred[c][t + w]);
             }
             cred[t] += cred[t + w];
         }
@@ -332,7 +342,16 @@ __global__ __launch_bounds__(kBlock) void box_stats_kernel(const float4* __restr
         b.num_points = n;
         b.num_kept = cred[0];
         b.filtered = filtered ? 1 : 0;
-        for (int c = 0; c < 3; ++c) { b.min3[c] = fred[c][0]; b.max3[c] = fred[3 + c][0]; }
+        for (int c = 0; c < 3; ++c) {
+            b.min3[c] = fred[c][0];
+            b.max3[c] = fred[3 + c][0];
+            const uint32_t z = zred[c][0];
+            if (z) {
+                const float zero = reinterpret_cast<const float*>(xyzl)[4 * (uint64_t)rows[a + z - 1] + c];
+                if (b.min3[c] == 0.0f) b.min3[c] = zero;
+                if (b.max3[c] == 0.0f) b.max3[c] = zero;
+            }
+        }
         b.mean = mean;
         b.threshold = thr;
     }
