@@ -1,6 +1,7 @@
 // lrc_echo.hip -- host side of the beam footprint and multi-echo returns (lrc_echo.h): the argument checks, the entry points
 // lrc_scan_echoes_dev / lrc_scan_echoes_compact (the trace launch and the frame path are lidarcast.hip's: echo_scan_dev,
-// echo_scan_compact, which also gathers the kept rows' weights) and the host reduction lrc_echo_reduce.
+// echo_scan_compact, which also gathers the kept rows' weights), the host reduction lrc_echo_reduce and the device test hook
+// lrc_internal_echo_lanes_dev (reduce_lanes on the caller's rows, without a traversal in front of it).
 #include <cmath>
 
 #include "lrc_internal.h"
@@ -25,6 +26,30 @@ int check_beam(const char* who, const lrc_beam* b, lrcecho::Params* out) {
         out->min_count = (uint8_t)b->min_count;
     }
     return LRC_OK;
+}
+
+constexpr int kLanesBlock = 256;      // whole waves
+
+// lrc_internal_echo_lanes_dev: lrcecho::reduce_lanes on rows of the caller's, in the trace kernel's lane layout -- lane
+// gid = beam * G + k, the `gid >= lanes` exit takes whole groups (lanes = num_beams * G), every other lane of the wave reaches
+// the reduction.  Lane k < K with t < +inf holds a hit of slot k and label beam * K + k; every other lane is a sub-ray without
+// a hit, whose range (0 for the lanes k >= K) must not count.
+__global__ __launch_bounds__(kLanesBlock) void echo_lanes_kernel(const float* __restrict__ t, uint64_t lanes, lrcecho::Params q,
+                                                                 int32_t* __restrict__ rep, float* __restrict__ range,
+                                                                 uint32_t* __restrict__ label) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kLanesBlock + threadIdx.x;
+    if (gid >= lanes) return;
+    const uint32_t tid = threadIdx.x & 63u, K = q.subrays;
+    const uint32_t k = tid & ((1u << q.group_log2) - 1u);
+    const uint64_t beam = gid >> q.group_log2;
+    const float tk = k < K ? t[beam * K + k] : 0.0f;
+    const bool hit = (k < K) & (tk < __builtin_inff());
+    lrcecho::reduce_lanes(q, tid, gid, tk, hit ? k : 0xFFFFFFFFu, (uint32_t)(beam * K + k),
+                          [&](uint64_t, uint64_t rec, float t_e, uint32_t slot_e, uint32_t label_e) {
+        rep[rec] = slot_e == 0xFFFFFFFFu ? -1 : (int32_t)slot_e;
+        range[rec] = t_e;
+        label[rec] = label_e;
+    });
 }
 
 }  // namespace
@@ -81,6 +106,29 @@ int lrc_echo_reduce(const float* t, uint64_t num_beams, const lrc_beam* beam, in
     const uint32_t K = beam->subrays, E = beam->max_echoes;
     for (uint64_t b = 0; b < num_beams; ++b)
         lrcecho::reduce_beam(t + b * K, K, E, beam->min_count, beam->separation, out_rep + b * E, out_weight + b * E);
+    return LRC_OK;
+}
+
+// test hook: the device reduction alone.  d_t (num_beams, K) float32; d_rep / d_range / d_label (num_beams, E): the representative
+// sub-ray of echo e (-1: empty slot), its range (+inf) and its label beam * K + rep (an empty slot's label is not specified);
+// d_weight (num_beams, E), nullable as lrcecho::Params::weight is.  Enqueued on `stream`, no host synchronisation.
+int lrc_internal_echo_lanes_dev(lrc_ctx* ctx, const float* d_t, uint64_t num_beams, const lrc_beam* beam, int32_t* d_rep,
+                                float* d_range, uint32_t* d_label, uint8_t* d_weight, void* stream) {
+    lrcecho::Params ep;
+    int rc = check_beam("lrc_internal_echo_lanes_dev", beam, &ep);
+    if (rc) return rc;
+    if (!ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_internal_echo_lanes_dev: ctx is NULL");
+    if (num_beams && (!d_t || !d_rep || !d_range || !d_label))
+        return fail(LRC_ERR_INVALID_ARG, "lrc_internal_echo_lanes_dev: NULL argument");
+    if (num_beams > 0xFFFFFFFFull / beam->subrays)
+        return fail(LRC_ERR_INVALID_ARG, "lrc_internal_echo_lanes_dev: num_beams * subrays must stay below 2^32 (the label)");
+    if (!num_beams) return LRC_OK;
+    LRC_HIP(hipSetDevice(ctx->device));
+    ep.weight = d_weight;
+    const uint64_t lanes = num_beams << ep.group_log2;
+    echo_lanes_kernel<<<dim3((unsigned)blocks_of(lanes, kLanesBlock)), dim3(kLanesBlock), 0, (hipStream_t)stream>>>(
+        d_t, lanes, ep, d_rep, d_range, d_label);
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 

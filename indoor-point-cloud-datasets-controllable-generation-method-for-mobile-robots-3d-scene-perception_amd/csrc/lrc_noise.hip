@@ -1,5 +1,7 @@
 // lrc_noise.hip -- host side of the seeded sensor noise (lrc_noise.h): the quantile table, the argument checks, the
-// resident copy of the table, and the host evaluation of the draws (lrc_noise_draws: what the kernel draws, without a GPU).
+// resident copy of the table, the host evaluation of the draws (lrc_noise_draws: what the kernel draws, without a GPU) and
+// the two test hooks that put a chosen counter, key or word in front of the generator: lrc_internal_noise_words on the host,
+// lrc_internal_noise_words_dev on the device.
 #include <cmath>
 
 #include "lrc_internal.h"
@@ -51,12 +53,8 @@ int check_noise(const char* who, const lrc_noise* nz, uint64_t N) {
     return LRC_OK;
 }
 
-}  // namespace
-
-#pragma GCC visibility push(hidden)
-int noise_params(lrc_ctx* ctx, const char* who, const lrc_noise* nz, uint64_t N, lrcnoise::Params* out) {
-    int rc = check_noise(who, nz, N);
-    if (rc) return rc;
+// the context's resident copy of the table, uploaded on first use
+int resident_table(lrc_ctx* ctx) {
     if (!ctx->d_noise_tab) {
         float* d = nullptr;
         LRC_HIP(hipMalloc((void**)&d, sizeof(float) * 2 * lrcnoise::kTable));
@@ -64,6 +62,42 @@ int noise_params(lrc_ctx* ctx, const char* who, const lrc_noise* nz, uint64_t N,
         if (e != hipSuccess) { (void)hipFree(d); LRC_HIP(e); }
         ctx->d_noise_tab = d;
     }
+    return LRC_OK;
+}
+
+// lrc_internal_noise_words_dev: block j of n -- philox4x32_10 of the caller's counter and key (ctr4 != NULL: words4 is written)
+// or the caller's words (ctr4 == NULL: words4 is read), and the variate of each of its four words from the resident table
+__global__ __launch_bounds__(kBlock) void noise_words_kernel(const uint32_t* __restrict__ ctr4, const uint32_t* __restrict__ key2,
+                                                             uint64_t n, uint32_t* words4, float* __restrict__ z4,
+                                                             const float* __restrict__ tab) {
+    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    uint32_t* w4 = words4 + j * 4;
+    lrcnoise::Words w;
+    if (ctr4) {
+        const uint32_t* c = ctr4 + j * 4;
+        w = lrcnoise::philox4x32_10(c[0], c[1], c[2], c[3], key2[j * 2], key2[j * 2 + 1]);
+        w4[0] = w.w0; w4[1] = w.w1; w4[2] = w.w2; w4[3] = w.w3;
+    } else {
+        w = lrcnoise::Words{w4[0], w4[1], w4[2], w4[3]};
+    }
+    if (z4) {
+        float* z = z4 + j * 4;
+        z[0] = lrcnoise::normal_of(w.w0, tab);
+        z[1] = lrcnoise::normal_of(w.w1, tab);
+        z[2] = lrcnoise::normal_of(w.w2, tab);
+        z[3] = lrcnoise::normal_of(w.w3, tab);
+    }
+}
+
+}  // namespace
+
+#pragma GCC visibility push(hidden)
+int noise_params(lrc_ctx* ctx, const char* who, const lrc_noise* nz, uint64_t N, lrcnoise::Params* out) {
+    int rc = check_noise(who, nz, N);
+    if (rc) return rc;
+    rc = resident_table(ctx);
+    if (rc) return rc;
     out->seed = nz->seed;
     out->first_frame = nz->first_frame;
     out->angle_std = nz->angle_std;
@@ -120,6 +154,24 @@ int lrc_internal_noise_words(const uint32_t* ctr4, const uint32_t* key2, uint32_
     const lrcnoise::Words w = lrcnoise::philox4x32_10(ctr4[0], ctr4[1], ctr4[2], ctr4[3], key2[0], key2[1]);
     out4[0] = w.w0; out4[1] = w.w1; out4[2] = w.w2; out4[3] = w.w3;
     if (z4) for (int k = 0; k < 4; ++k) z4[k] = lrcnoise::normal_of(out4[k], host_table());
+    return LRC_OK;
+}
+
+// test hook: the device twin of lrc_internal_noise_words for n blocks.  d_ctr4 (n, 4) and d_key2 (n, 2): d_words4 (n, 4)
+// receives the Philox blocks; d_ctr4 NULL: d_words4 is the input (any word can be put in front of normal_of).  d_z4 (n, 4),
+// nullable: the variates of the words from the context's resident table.  Enqueued on `stream`, no host synchronisation.
+int lrc_internal_noise_words_dev(lrc_ctx* ctx, const uint32_t* d_ctr4, const uint32_t* d_key2, uint64_t n, uint32_t* d_words4,
+                                 float* d_z4, void* stream) {
+    if (!ctx) return fail(LRC_ERR_INVALID_ARG, "lrc_internal_noise_words_dev: ctx is NULL");
+    if (!n) return LRC_OK;
+    if (!d_words4 || (d_ctr4 && !d_key2)) return fail(LRC_ERR_INVALID_ARG, "lrc_internal_noise_words_dev: NULL argument");
+    if (n > 0x7FFFFFFFull * kBlock) return fail(LRC_ERR_INVALID_ARG, "lrc_internal_noise_words_dev: too many blocks for one launch");
+    LRC_HIP(hipSetDevice(ctx->device));
+    int rc = resident_table(ctx);
+    if (rc) return rc;
+    noise_words_kernel<<<dim3((unsigned)blocks_of(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream>>>(
+        d_ctr4, d_key2, n, d_words4, d_z4, ctx->d_noise_tab);
+    LRC_HIP(hipGetLastError());
     return LRC_OK;
 }
 

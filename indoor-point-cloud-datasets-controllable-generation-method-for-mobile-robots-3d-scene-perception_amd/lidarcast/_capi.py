@@ -71,6 +71,10 @@ SYMBOLS = (
     "lrc_rng_scan_draws", "lrc_rays_from_trig",
 )
 
+# test hooks this package wraps: exported beside the API, declared in no header (lidarcast.echo.reduce_lanes_dev,
+# lidarcast.noise.words_dev; the host hook takes one block per call and is called by the tests themselves)
+INTERNAL_SYMBOLS = ("lrc_internal_echo_lanes_dev", "lrc_internal_noise_words", "lrc_internal_noise_words_dev")
+
 
 class LrcHits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("prim", C.c_void_p), ("normal3", C.c_void_p),
@@ -419,6 +423,9 @@ def load():
         "lrc_compact_dev": [vp, u64, u64, C.POINTER(LrcCompactIO), vp],
         "lrc_rng_scan_draws": [C.POINTER(LrcMt19937State), u64, u64, u64, dbl, dbl, vp, vp, i32],
         "lrc_rays_from_trig": [vp, vp, vp, vp, u64, vp, vp],
+        "lrc_internal_echo_lanes_dev": [vp, vp, u64, C.POINTER(LrcBeam), vp, vp, vp, vp, vp],
+        "lrc_internal_noise_words": [vp, vp, vp, vp],
+        "lrc_internal_noise_words_dev": [vp, vp, vp, u64, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)

@@ -100,3 +100,27 @@ def reduce(t, beam):
     weight = np.zeros((B, max(E, 1)), np.uint8)
     check(lib.lrc_echo_reduce(t.ctypes.data, B, C.byref(beam), rep.ctypes.data, weight.ctypes.data), "lrc_echo_reduce")
     return rep, weight
+
+
+def reduce_lanes_dev(ctx, t, beam, stream=0):
+    """The DEVICE reduction alone (test hook lrc_internal_echo_lanes_dev): the lanes of the trace kernel's tail on (B, K) float32
+    distances with an ``LrcBeam``, sub-ray k of beam b entering with slot k and label b * K + k.  Dict of (B, E) arrays:
+    ``rep`` int32 (-1: empty slot), ``range`` float32 (+inf), ``label`` uint32 (b * K + rep; not specified for an empty slot),
+    ``weight`` uint8.  ``ctx`` a ``lidarcast.Context``."""
+    import torch
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    K, E = int(beam.subrays), int(beam.max_echoes)
+    if t.ndim != 2 or (1 <= K <= 16 and t.shape[1] != K):
+        raise ValueError("t must be (B, K)")
+    B = t.shape[0]
+    dev = torch.device("cuda", ctx.device)
+    t_t = torch.from_numpy(t).to(dev)
+    rep, label = (torch.full((B, max(E, 1)), fill, dtype=torch.int32, device=dev) for fill in (-2, -2))
+    rng = torch.full((B, max(E, 1)), float("nan"), dtype=torch.float32, device=dev)
+    weight = torch.full((B, max(E, 1)), 255, dtype=torch.uint8, device=dev)
+    check(ctx._lib.lrc_internal_echo_lanes_dev(ctx._h, t_t.data_ptr(), B, C.byref(beam), rep.data_ptr(), rng.data_ptr(),
+                                               label.data_ptr(), weight.data_ptr(), C.c_void_p(int(stream))),
+          "lrc_internal_echo_lanes_dev")
+    torch.cuda.synchronize(dev)
+    return {"rep": rep.cpu().numpy(), "range": rng.cpu().numpy(), "label": label.cpu().numpy().view(np.uint32),
+            "weight": weight.cpu().numpy()}

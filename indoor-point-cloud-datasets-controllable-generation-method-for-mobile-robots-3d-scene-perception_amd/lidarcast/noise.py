@@ -68,6 +68,36 @@ def table():
     return base, slope
 
 
+def words_dev(ctx, ctr=None, key=None, words=None, stream=0):
+    """The generator and the variate on the DEVICE, on chosen inputs (test hook lrc_internal_noise_words_dev; ``ctx`` a
+    ``lidarcast.Context``).  With ``ctr`` (n, 4) and ``key`` (n, 2) of 32-bit words: the n Philox4x32-10 blocks.  With
+    ``words`` (n, 4) instead: those words as they are.  Returns (words (n, 4) uint32, z (n, 4) float32: the standard normal
+    variate of every word from the context's resident table)."""
+    import torch
+    if (ctr is None) == (words is None) or (ctr is not None and key is None):
+        raise ValueError("either ctr and key, or words")
+    dev = torch.device("cuda", ctx.device)
+
+    def up(a, width):
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, width)
+        return torch.from_numpy(a.view(np.int32)).to(dev)
+    if ctr is not None:
+        c_t, k_t = up(ctr, 4), up(key, 2)
+        if c_t.shape[0] != k_t.shape[0]:
+            raise ValueError("ctr must be (n, 4) and key (n, 2)")
+        w_t = torch.zeros_like(c_t)
+    else:
+        c_t = k_t = None
+        w_t = up(words, 4)
+    n = w_t.shape[0]
+    z_t = torch.full((n, 4), float("nan"), dtype=torch.float32, device=dev)
+    ptr = lambda x: None if x is None else x.data_ptr()
+    check(ctx._lib.lrc_internal_noise_words_dev(ctx._h, ptr(c_t), ptr(k_t), n, ptr(w_t), ptr(z_t), C.c_void_p(int(stream))),
+          "lrc_internal_noise_words_dev")
+    torch.cuda.synchronize(dev)
+    return w_t.cpu().numpy().view(np.uint32), z_t.cpu().numpy()
+
+
 # ---- noisy moving-sensor sweeps (include/lidarcast.h "noisy moving-sensor sweeps", DESIGN.md section 5l) ----------------
 # The seeded noise under moving-sensor sweeps: the table row is jittered in front of the rotation into the world, the world
 # direction swept behind it, dropout and the range draw as in the static noisy scan.  Module functions, as

@@ -25,6 +25,26 @@ def philox4x32_10(ctr, key):
     return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
 
 
+def philox4x32_10_inverse(words, key):
+    """The counter (..., 4) whose block under key (..., 2) is ``words`` (..., 4): the ten rounds backwards.  A round is a
+    bijection of the counter -- its low product words are multiples by odd numbers, undone by the inverses mod 2^32, and the
+    high product words then follow from the recovered inputs -- so any four words can be put behind an entry point that takes
+    a counter and a key."""
+    w = np.asarray(words, dtype=np.uint64)
+    key = np.asarray(key, dtype=np.uint64)
+    n0, n1, n2, n3 = (w[..., j] for j in range(4))
+    i0, i1 = np.uint64(pow(M0, -1, 1 << 32)), np.uint64(pow(M1, -1, 1 << 32))
+    for r in range(9, -1, -1):
+        k0 = (key[..., 0] + np.uint64((W0 * r) & 0xFFFFFFFF)) & LOW
+        k1 = (key[..., 1] + np.uint64((W1 * r) & 0xFFFFFFFF)) & LOW
+        c0 = (n3 * i0) & LOW                 # n3 = low(M0 * c0); 32 x 32 bits: exact in 64
+        c2 = (n1 * i1) & LOW
+        c1 = n0 ^ ((np.uint64(M1) * c2) >> S32) ^ k0
+        c3 = n2 ^ ((np.uint64(M0) * c0) >> S32) ^ k1
+        n0, n1, n2, n3 = c0, c1, c2, c3
+    return np.stack([n0, n1, n2, n3], axis=-1).astype(np.uint32)
+
+
 def ray_words(seed, first_frame, P, N):
     """(P, N, 4) uint32: the block of ray i of pose p -- key (seed lo, seed hi), counter (i, frame lo, frame hi, 0) with
     frame = first_frame + p in 64 bits."""

@@ -18,6 +18,8 @@ def test_header_and_library_agree():
     lib = lidarcast.load()
     for name in declared:
         assert hasattr(lib, name), f"liblidarcast.so does not export {name}"
+    for name in _capi.INTERNAL_SYMBOLS:                                  # test hooks: exported, in no header, not part of the API
+        assert name.startswith("lrc_internal_") and name not in declared and hasattr(lib, name), name
     assert lidarcast.version().startswith("lidarcast ")
     assert os.path.dirname(lidarcast.LIB_PATH).endswith("_amd")          # in-tree build
 
@@ -35,7 +37,8 @@ def test_libraries_export_only_the_api():
         assert names, lib
         stray = sorted(n for n in names if not re.match(r"lrc_|_Z|__hip_cuid_", n))
         assert not stray, (os.path.basename(lib), stray)
-        lost = sorted(set(_capi.SYMBOLS) - set(names))                     # ... and hiding must not take an API name along
+        lost = sorted((set(_capi.SYMBOLS) | set(_capi.INTERNAL_SYMBOLS)) - set(names))     # ... and hiding must not take an API name
+                                                                                            # or a wrapped test hook along
         assert not lost, (os.path.basename(lib), lost)
 
 

@@ -310,6 +310,73 @@ def test_three_subrays_every_echo_count(engine, soup, E, min_count):
     assert (rep[:, 0] < 0).sum() >= 50
 
 
+@pytest.mark.parametrize("K,E", [(1, 1), (2, 1), (1, 4), (2, 4), (3, 4), (7, 2), (16, 2)])
+def test_launch_shapes_with_partial_waves(engine, soup, K, E):
+    """Every group size G = 1, 2, 4, 8, 16 on two poses of 397 beams: a pose is no whole number of waves, so one wave holds
+    groups of both poses and the launch ends in a partial wave.  E > K: the echo-writing lanes e >= K cast nothing; G = 2 and
+    G = 1 run through the kernel at all."""
+    dirs, poses = table(4, 100)[:397], soup_poses(2)
+    N, P = len(dirs), len(poses)
+    beam = beam_model(K, 0.02, E=E)
+    G = 1 << er_group_log2(K, E)
+    assert (beam.subrays, beam.max_echoes) == (K, E) and G == {(1, 1): 1, (2, 1): 2, (7, 2): 8, (16, 2): 16}.get((K, E), 4)
+    assert P >= 2 and (N * G) % 64 != 0 and (P * N * G) % 64 != 0
+    got, want = run_case(engine.scene_for(soup), poses, dirs, beam, 20.0, what=f"soup K={K} E={E} N={N}")
+    rep = want["rep"]
+    print(f"\n[echo] K={K} E={E} G={G}: echoes per slot {(rep >= 0).sum(axis=0).tolist()}, all-miss beams {int((rep[:, 0] < 0).sum())}")
+    assert (rep[:, 0] >= 0).sum() >= 50 and (rep[:, 0] < 0).sum() >= 20
+    if min(K, E) >= 2:
+        assert (rep[:, 1] >= 0).sum() >= 1
+    if E > K:                                                # more slots than sub-rays: the slots behind K are always empty
+        assert (rep[:, K:] == -1).all()
+        empty = (rep < 0).reshape(-1)
+        assert np.isinf(got["t"][empty]).all() and (got["weight"][empty] == 0).all() and (got["prim"][empty] == INVALID).all()
+
+
+def er_group_log2(K, E):
+    g = 0
+    while (1 << g) < max(K, E):
+        g += 1
+    return g
+
+
+def test_separation_at_a_measured_gap(engine, soup):
+    """Three float32 gaps between consecutive sub-rays (in the order by range) that the soup's own beams show, each as the
+    separation and one float below it: at the gap itself the two sub-rays share a cluster (the gap does not EXCEED the
+    separation), one float below they do not.  In a scan such an equality happens by luck or not at all."""
+    dirs, poses = table(4, 100), soup_poses(3)
+    scene = engine.scene_for(soup)
+    K, E = 7, 4
+    sub, _, _, _ = explicit_subrays(scene, poses, dirs, ring(K, 0.02))
+    P, _, N = sub["t"].shape
+    t_k = np.ascontiguousarray(sub["t"].transpose(0, 2, 1)).reshape(P * N, K)
+    found = []                                               # (beam, gap)
+    for b in range(len(t_k)):
+        s = np.sort(t_k[b][np.isfinite(t_k[b])])
+        gaps = (s[1:] - s[:-1]).astype(np.float32)
+        ok = gaps[(gaps > np.float32(0.01)) & (gaps < np.float32(0.2))]
+        for g in ok:
+            below = np.nextafter(g, np.float32(0.0))
+            n_at, n_below = (int(er.count_clusters(t_k[b:b + 1], 1, s_)[0]) for s_ in (g, below))
+            if n_below == n_at + 1 and n_below <= E:
+                found.append((b, g))
+                break
+    assert len(found) >= 3, len(found)
+    for b, g in (found[0], found[len(found) // 2], found[-1]):
+        below = np.nextafter(g, np.float32(0.0))
+        assert g.dtype == np.float32 and 0.01 < g < 0.2 and below < g
+        res = {}
+        for name, sep in (("at", g), ("below", below)):
+            beam = beam_model(K, 0.02, E=E, separation=float(sep))
+            assert np.float32(beam.struct().separation) == sep
+            got, want = run_case(scene, poses, dirs, beam, 20.0, what=f"soup K=7 separation {name} the gap {g!r} of beam {b}")
+            res[name] = want
+        n_at, n_below = (int((res[k]["rep"][b] >= 0).sum()) for k in ("at", "below"))
+        print(f"\n[echo] beam {b}: gap {g!r}: {n_at} clusters at the gap, {n_below} one float below; "
+              f"beams that differ between the two scans {int((res['at']['rep'] != res['below']['rep']).any(axis=1).sum())}")
+        assert n_below == n_at + 1                          # the restatement shows that beam with one cluster fewer at g
+
+
 def test_range_filter_min_range_and_normal_incidence(engine, room):
     dirs, poses = table(4, 100), room_poses(3)
     scene = engine.scene_for(room)

@@ -1,7 +1,8 @@
 """CPU: the host side of the beam footprint and multi-echo returns (lrc_echo_reduce, the argument checks of lrc_scan_echoes_*,
 lidarcast.echo.BeamModel).  The reduction is compared with the numpy restatement of the header's text (tests/echo_restate.py)
 on crafted rows -- ties, gaps of exactly the separation and one ulp above it, chains, misses, more clusters than echoes, small
-clusters dropped -- and on random rows."""
+clusters dropped: the rows of tests/echo_rows.py, which the device reduction gets too (tests/test_echo_lanes_gpu.py) -- and on
+random rows."""
 import ctypes as C
 import math
 import os
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 import echo_restate as er
+import echo_rows as rows
 from conftest import REPO
 
 INF = np.float32(np.inf)
@@ -33,57 +35,64 @@ def _both(t, E=2, min_count=1, separation=0.05):
     return got
 
 
+def _crafted(group):
+    """Every row of the group through both reductions, each against the result tests/echo_rows.py records for it."""
+    cases = rows.crafted(group)
+    for c in cases:
+        rep, w = _both(c.t, E=c.E, min_count=c.min_count, separation=c.separation)
+        assert rep.tolist() == c.rep and w.tolist() == c.weight, c
+    return cases
+
+
 def test_exact_ties_are_broken_by_k():
-    rep, w = _both([[2.0, 1.0, 1.0, 2.0, 1.0]], E=2)
-    assert rep.tolist() == [[1, 0]] and w.tolist() == [[3, 2]]
-    rep, w = _both([[1.0, 1.0, 1.0]], E=3)
-    assert rep.tolist() == [[0, -1, -1]] and w.tolist() == [[3, 0, 0]]
+    a, b = _crafted("ties")
+    assert (a.rep, a.weight) == ([[1, 0]], [[3, 2]])
+    assert (b.rep, b.weight) == ([[0, -1, -1]], [[3, 0, 0]])
 
 
 def test_gap_of_exactly_the_separation_and_one_ulp_above():
-    sep = np.float32(0.25)
-    a = np.float32(1.0)
-    b = a + sep                                   # exact in float32
+    sep, a, b, b1 = rows.SEP, rows.A, rows.B, rows.B1
+    assert sep == np.float32(0.25) and a == np.float32(1.0) and b == a + sep          # exact in float32
     assert np.float32(b - a) == sep
-    rep, w = _both([[a, b, INF]], E=2, separation=sep)
-    assert rep.tolist() == [[0, -1]] and w.tolist() == [[2, 0]]          # a gap equal to the separation does not split
-    b1 = np.nextafter(b, INF)
-    assert np.float32(b1 - a) > sep
-    rep, w = _both([[a, b1, INF]], E=2, separation=sep)
-    assert rep.tolist() == [[0, 1]] and w.tolist() == [[1, 1]]
-    rep, w = _both([[b1, a, INF]], E=2, separation=sep)                  # the same two the other way round
-    assert rep.tolist() == [[1, 0]] and w.tolist() == [[1, 1]]
+    assert b1 == np.nextafter(b, INF) and np.float32(b1 - a) > sep
+    eq, above, back = _crafted("separation")
+    assert eq.t.tolist() == [[a, b, INF]] and above.t.tolist() == [[a, b1, INF]] and back.t.tolist() == [[b1, a, INF]]
+    assert eq.separation == above.separation == back.separation == sep
+    assert (eq.rep, eq.weight) == ([[0, -1]], [[2, 0]])              # a gap equal to the separation does not split
+    assert (above.rep, above.weight) == ([[0, 1]], [[1, 1]])
+    assert (back.rep, back.weight) == ([[1, 0]], [[1, 1]])           # the same two the other way round
 
 
 def test_a_chain_of_small_gaps_is_one_cluster():
     t = np.float32(1.0) + np.arange(7, dtype=np.float32) * np.float32(0.04)     # 0.24 m end to end, separation 0.05
-    rep, w = _both([t[::-1].copy()], E=2)
-    assert rep.tolist() == [[0, -1]] and w.tolist() == [[7, 0]]
-    rep, w = _both([t[[3, 0, 6, 1, 5, 2, 4]]], E=2)
-    assert rep.tolist() == [[0, -1]] and w.tolist() == [[7, 0]]
+    down, mixed = _crafted("chain")
+    assert down.t.tolist() == [t[::-1].tolist()] and mixed.t.tolist() == [t[[3, 0, 6, 1, 5, 2, 4]].tolist()]
+    for c in (down, mixed):
+        assert (c.rep, c.weight, c.E, float(c.separation)) == ([[0, -1]], [[7, 0]], 2, float(np.float32(0.05)))
 
 
 def test_all_misses_and_axis_miss_with_off_axis_hits():
-    rep, w = _both([[INF] * 5], E=2)
-    assert rep.tolist() == [[-1, -1]] and w.tolist() == [[0, 0]]
-    rep, w = _both([[INF, 3.0, INF, 1.0, 3.01]], E=2)
-    assert rep.tolist() == [[3, 1]] and w.tolist() == [[1, 2]]
+    miss, axis = _crafted("misses")
+    assert miss.t.tolist() == [[INF] * 5] and (miss.rep, miss.weight) == ([[-1, -1]], [[0, 0]])
+    assert axis.t.tolist() == np.array([[INF, 3.0, INF, 1.0, 3.01]], np.float32).tolist()
+    assert (axis.rep, axis.weight) == ([[3, 1]], [[1, 2]])
 
 
 def test_more_clusters_than_echoes_keeps_the_nearest():
-    rep, w = _both([[4.0, 1.0, 3.0, 2.0, 1.01, INF, 3.0]], E=2)
-    assert rep.tolist() == [[1, 3]] and w.tolist() == [[2, 1]]
-    rep, w = _both([[4.0, 1.0, 3.0, 2.0, 1.01, INF, 3.0]], E=4)
-    assert rep.tolist() == [[1, 3, 2, 0]] and w.tolist() == [[2, 1, 2, 1]]
-    rep, w = _both([[4.0, 1.0, 3.0, 2.0, 1.01, INF, 3.0]], E=1)
-    assert rep.tolist() == [[1]] and w.tolist() == [[2]]
+    two, four, one = _crafted("more_clusters")
+    t = np.array([[4.0, 1.0, 3.0, 2.0, 1.01, INF, 3.0]], np.float32).tolist()
+    assert two.t.tolist() == four.t.tolist() == one.t.tolist() == t and (two.E, four.E, one.E) == (2, 4, 1)
+    assert (two.rep, two.weight) == ([[1, 3]], [[2, 1]])
+    assert (four.rep, four.weight) == ([[1, 3, 2, 0]], [[2, 1, 2, 1]])
+    assert (one.rep, one.weight) == ([[1]], [[2]])
 
 
 def test_min_count_drops_the_nearest_cluster():
-    rep, w = _both([[1.0, 2.0, 2.01, 3.0, 3.0, 3.0, 5.0]], E=2, min_count=2)
-    assert rep.tolist() == [[1, 3]] and w.tolist() == [[2, 3]]
-    rep, w = _both([[1.0, 2.0, 2.01, 3.0, 3.0, 3.0, 5.0]], E=2, min_count=3)
-    assert rep.tolist() == [[3, -1]] and w.tolist() == [[3, 0]]
+    mc2, mc3 = _crafted("min_count")
+    t = np.array([[1.0, 2.0, 2.01, 3.0, 3.0, 3.0, 5.0]], np.float32).tolist()
+    assert mc2.t.tolist() == mc3.t.tolist() == t and (mc2.min_count, mc3.min_count, mc2.E, mc3.E) == (2, 3, 2, 2)
+    assert (mc2.rep, mc2.weight) == ([[1, 3]], [[2, 3]])
+    assert (mc3.rep, mc3.weight) == ([[3, -1]], [[3, 0]])
 
 
 @pytest.mark.parametrize("K", [1, 3, 5, 7, 16])
@@ -126,6 +135,19 @@ def test_refusals_of_the_beam():
     assert lib.lrc_echo_reduce(t.ctypes.data, 1, None, rep.ctypes.data, w.ctypes.data) == _capi.LRC_ERR_INVALID_ARG
     assert lib.lrc_echo_reduce(None, 1, C.byref(_beam(3)), rep.ctypes.data, w.ctypes.data) == _capi.LRC_ERR_INVALID_ARG
     assert lib.lrc_echo_reduce(None, 0, C.byref(_beam(3)), None, None) == 0
+
+
+def test_symbols_load():
+    from lidarcast import _capi
+    lib = _capi.load()
+    for name in ("lrc_scan_echoes_dev", "lrc_scan_echoes_compact", "lrc_echo_reduce"):
+        assert name in _capi.SYMBOLS and hasattr(lib, name), name
+    assert "lrc_internal_echo_lanes_dev" in _capi.INTERNAL_SYMBOLS and hasattr(lib, "lrc_internal_echo_lanes_dev")
+    b = _beam(0)                                   # the device hook checks the beam first, as lrc_echo_reduce does: no GPU needed
+    assert lib.lrc_internal_echo_lanes_dev(None, None, 0, C.byref(b), None, None, None, None, None) == _capi.LRC_ERR_INVALID_ARG
+    assert b"lrc_internal_echo_lanes_dev: subrays" in lib.lrc_last_error()
+    assert lib.lrc_internal_echo_lanes_dev(None, None, 0, C.byref(_beam(3)), None, None, None, None, None) == _capi.LRC_ERR_INVALID_ARG
+    assert b"ctx is NULL" in lib.lrc_last_error()
 
 
 def test_refusals_that_need_no_scene():

@@ -9,14 +9,9 @@ import numpy as np
 import pytest
 
 import noise_restate as nr
+import noise_words as nw
 from helpers import assert_bit_equal
-
-KNOWN = [
-    ((0, 0, 0, 0), (0, 0), (0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8)),
-    ((0xFFFFFFFF,) * 4, (0xFFFFFFFF,) * 2, (0x408F276D, 0x41C83B0E, 0xA20BC7C6, 0x6D5451FD)),
-    ((0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344), (0xA4093822, 0x299F31D0),
-     (0xD16CFE09, 0x94FDCCEB, 0x5001E420, 0x24126EA1)),
-]
+from noise_words import KNOWN          # shared with the device tests (tests/test_noise_words_gpu.py)
 
 
 @pytest.fixture(scope="module")
@@ -51,6 +46,36 @@ def test_draws_use_the_known_block(tab):
     assert bool(d["keep"][0, 0]) == bool(w[3] >= nr.drop_threshold(0.5))
     words, zl = _lib_words(KNOWN[0][0], KNOWN[0][1], want_z=True)
     assert_bit_equal(zl, nr.normal_of(np.array(words, dtype=np.uint32), base, slope))
+
+
+def test_philox_inverse_round_trip():
+    ctr, key = nw.random_pairs(20000, seed=5)
+    words = nr.philox4x32_10(ctr, key)
+    assert [tuple(int(x) for x in w) for w in words[:3]] == [k[2] for k in KNOWN]
+    assert np.array_equal(nr.philox4x32_10_inverse(words, key), ctr)
+    assert np.array_equal(nr.philox4x32_10(nr.philox4x32_10_inverse(ctr, key), key), ctr)       # any four words are a block
+
+
+def test_crafted_words_through_the_host_hook(tab):
+    """The edge words of normal_of (tests/noise_words.py) behind lrc_internal_noise_words, which takes a counter and a key:
+    the counter is the generator's inverse of the words.  The hook returns the words, and their variates are the restatement's
+    bit for bit; at a cell's first word the variate is the table's entry itself, below r = 128 the clamp."""
+    base, slope = tab
+    words = nw.crafted_words()
+    rng = np.random.default_rng(17)
+    key = rng.integers(0, 1 << 32, size=(len(words), 2), dtype=np.uint64).astype(np.uint32)
+    got_w, got_z = nw.host_blocks(nr.philox4x32_10_inverse(words, key), key)
+    assert np.array_equal(got_w, words)
+    assert_bit_equal(got_z, nr.normal_of(words, base, slope), "variates of the crafted words")
+    cells = nw.cell_words()
+    z = {int(w): v for w, v in zip(words.reshape(-1), got_z.reshape(-1))}
+    first = np.array([[z[int(w)] for w in row] for row in cells[:, :, 0]], np.float32)
+    assert_bit_equal(first, base[::-1], "first word of a cell: octave e = 30 - L")
+    neg = np.array([[z[int(w) | 0x80000000] for w in row] for row in cells[:, :, 0]], np.float32)
+    assert_bit_equal(neg, -base[::-1], "first word of a cell, sign bit set")
+    for r in (0, 1, 127):
+        assert z[r] == base[23, 0] and z[r | 0x80000000] == -base[23, 0]
+    assert z[128] == base[23, 0] and z[0x7FFFFFFF] < base[0, 63] and z[0x7FFFFFFF] > 0.0
 
 
 def test_table_is_the_exact_quantile_at_every_cell_start(tab):
@@ -160,6 +185,19 @@ def test_rejected_models(bad):
     assert lib.lrc_noise_draws(C.byref(nz), 1, 1, None, None, None, None) == _capi.LRC_ERR_INVALID_ARG
     with pytest.raises(ValueError, match="lrc_noise_draws"):
         noise.draws(noise.NoiseModel(seed=1, **bad), 1, 4)
+
+
+def test_symbols_load():
+    from lidarcast import _capi
+    lib = _capi.load()
+    for name in ("lrc_scan_noisy_dev", "lrc_scan_noisy_compact", "lrc_noise_draws", "lrc_noise_table"):
+        assert name in _capi.SYMBOLS and hasattr(lib, name), name
+    for name in ("lrc_internal_noise_words", "lrc_internal_noise_words_dev"):
+        assert name in _capi.INTERNAL_SYMBOLS and hasattr(lib, name), name
+    out = (C.c_uint32 * 4)()
+    assert lib.lrc_internal_noise_words(None, (C.c_uint32 * 2)(), out, None) == _capi.LRC_ERR_INVALID_ARG
+    assert lib.lrc_internal_noise_words_dev(None, None, None, 0, None, None, None) == _capi.LRC_ERR_INVALID_ARG       # no context
+    assert b"lrc_internal_noise_words_dev: ctx is NULL" in lib.lrc_last_error()
 
 
 def test_rejected_ray_count():
