@@ -14,7 +14,6 @@
 
 namespace lrcseq {
 
-constexpr uint64_t kMaxKeys = 0x7FFFFFFFull;        // reserved key slots between resets
 constexpr uint64_t kMaxBits = 0x7FFFFFFFull;        // F * 32 * W
 
 // accumulator words (uint64): keys appended, key slots overflowed (never expected), rays of poses without a slot

@@ -1,30 +1,27 @@
 // lrc_voxseq.hip -- dynamic occupancy: per-frame grids under movers, carved from explicit segments (gfx950).
 //
-// Definition: include/lidarcast.h "dynamic occupancy", DESIGN.md section 5u, tests/voxseq_restate.py.  The grid, the walk,
-// the limits and the sem / ins vote are lrc_voxgrid's; new are the frame slots (lrc_voxseq.h), the explicit segments
-// (origin, end point and labels come from the scan's records instead of regenerated rays), STATIC_ONLY and the mover vote.
+// Definition: include/lidarcast.h "dynamic occupancy", DESIGN.md section 5u, tests/voxseq_restate.py.  The grid, the walk and
+// its limits are lrc_voxwalk.h's, the keys, their runs and the sem / ins vote lrc_voxruns.h's, as for the static grid
+// (lrc_voxgrid.hip); new are the frame slots (lrc_voxseq.h), the explicit segments (origin, end point and labels come from the
+// scan's records instead of regenerated rays), STATIC_ONLY and the mover vote.
 //
 // Kernels
-//   seq_walk   one thread per ray.  The walk (lrc_voxwalk.h) goes to the ray's slot only.  Free bits: the voxels of one
-//              bitset word are gathered per ray, then a plain load first and an atomicOr only when a bit is still clear --
-//              all rays of a frame start in the sensor's voxel and a slot sees only its own frame's rays, so those words
-//              are contended by one frame's waves at once and set after the first of them.  Returns: the label key and the
-//              mover key of a returned ray go to the same position of two key columns, one atomic per wave for the slots.
-//   finalize   per key column: rocprim radix sort (unused reserved slots hold all-ones keys that sort last), run-length
-//              encoding, a head flag per (slot, voxel) and an exclusive scan for its place in the sparse list -- both columns
-//              hold the same (slot, voxel) set, so both give the same places.  One thread per head votes: sem then ins on
-//              the label runs, the mover id on the mover runs.  Frame offsets from the heads, per-slot counts by one
-//              block per slot (no atomics).  Integer work only after the walk.
+//   seq_walk   one thread per ray: walk_segment into a FreeSink on the ray's slot only -- a slot sees only its own frame's
+//              rays, so the words around the sensor's voxel are contended by one frame's waves at once and set after the
+//              first of them.  Returns: the label key and the mover key of a returned ray go to the same position of two key
+//              columns, one atomic per wave for the slots.
+//   finalize   the runs of each key column (KeyRuns) -- both columns hold the same (slot, voxel) set, so both give the same
+//              places in the sparse list.  One thread per head votes: sem then ins on the label runs, the mover id on the
+//              mover runs.  Frame offsets from the heads, per-slot counts by one block per slot (no atomics).  Integer work
+//              only after the walk.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <new>
 #include <vector>
 
 #include "lrc_internal.h"
 #include "lrc_voxwalk.h"
+#include "lrc_voxruns.h"
 #include "lrc_voxseq.h"
 
 namespace {
@@ -50,28 +47,10 @@ struct WalkArgs {
     unsigned long long* rejected;         // F
 };
 
-// Free bits of one ray in its slot: consecutive voxels in one bitset word (steps along z, the fastest axis) are gathered into
-// one mask; a word is written when the walk leaves it, with a plain load first and an atomicOr only when a bit is still clear.
-struct DevSink {
-    uint32_t* __restrict__ bits;          // the slot's first word
-    uint32_t w = 0xFFFFFFFFu, m = 0;
-    __device__ void flush() {
-        if (m && (bits[w] & m) != m) atomicOr(&bits[w], m);
-    }
-    __device__ void add(uint32_t idx) {
-        const uint32_t nw = idx >> 5;
-        if (nw != w) {
-            flush();
-            w = nw;
-            m = 0;
-        }
-        m |= 1u << (idx & 31u);
-    }
-};
-
 struct HostSink {
     uint32_t* bits;
     void add(uint32_t idx) { bits[idx >> 5] |= 1u << (idx & 31u); }
+    void flush() {}
 };
 
 __global__ __launch_bounds__(kBlock) void seq_walk_kernel(WalkArgs a) {
@@ -90,12 +69,11 @@ __global__ __launch_bounds__(kBlock) void seq_walk_kernel(WalkArgs a) {
                 const float* __restrict__ o = a.origins3 + 3 * (a.per_ray ? gid : p);
                 const float* __restrict__ e = a.point3 + 3 * gid;
                 mv = a.mover ? (uint32_t)a.mover[gid] : 0u;
-                DevSink sink{a.bits + (uint64_t)f * a.W};
+                FreeSink sink{a.bits + (uint64_t)f * a.W};
                 uint32_t end = 0;
                 int32_t b3[3];
                 const int rc = walk_segment(a.g, o[0], o[1], o[2], e[0], e[1], e[2], sink, end, b3);
-                sink.flush();
-                rejected = rc == kWalkRejected;
+                    rejected = rc == kWalkRejected;
                 if (rc == kWalkEnd && !((a.flags & LRC_VOXSEQ_STATIC_ONLY) && mv != 0u)) {
                     ret = true;
                     gidx = f * 32u * a.W + end;
@@ -115,39 +93,14 @@ __global__ __launch_bounds__(kBlock) void seq_walk_kernel(WalkArgs a) {
         if (lane == leader) atomicAdd(&a.rejected[fl], (unsigned long long)__popcll(same));
         else if (rejected && f != fl) atomicAdd(&a.rejected[f], 1ull);
     }
-    const unsigned long long m = __ballot(ret);
-    if (m) {                                                   // wave-uniform: one atomic per wave for the slots
-        const uint32_t leader = (uint32_t)__ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(&a.acc[kAccKeys], (unsigned long long)__popcll(m));
-        base = __shfl(base, (int)leader);
-        if (ret) {
-            const unsigned long long pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-            if (pos < a.key_cap) {
-                a.lkeys[pos] = label_key(gidx, label & 0xFFFFu, label >> 16);
-                a.mkeys[pos] = mover_key(gidx, mv);
-            } else {
-                atomicOr(&a.acc[kAccOverflow], 1ull);
-            }
-        }
+    const unsigned long long pos = wave_append(ret, &a.acc[kAccKeys], &a.acc[kAccOverflow], a.key_cap);
+    if (pos != kNoSlot) {
+        a.lkeys[pos] = label_key(gidx, label & 0xFFFFu, label >> 16);
+        a.mkeys[pos] = mover_key(gidx, mv);
     }
 }
 
 // ---- finalize ---------------------------------------------------------------------------------------------------
-// head of a (slot, voxel)'s runs among the unique keys; the global index is key >> shift
-__global__ __launch_bounds__(kBlock) void seq_head_kernel(const unsigned long long* __restrict__ ukeys,
-                                                          const uint32_t* __restrict__ nruns, uint64_t R, uint32_t shift,
-                                                          uint64_t G, uint32_t* __restrict__ flag) {
-    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j > R) return;
-    uint32_t f = 0;
-    if (j < *nruns) {
-        const unsigned long long g = ukeys[j] >> shift;
-        f = g < G && (j == 0 || (ukeys[j - 1] >> shift) != g);
-    }
-    flag[j] = f;
-}
-
 __global__ __launch_bounds__(kBlock) void seq_dense_kernel(const uint32_t* __restrict__ bits, uint32_t V, uint32_t W,
                                                            uint64_t FV, uint8_t* __restrict__ state) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -166,28 +119,14 @@ __global__ __launch_bounds__(kBlock) void seq_label_vote_kernel(
     uint32_t* __restrict__ o_ret, uint64_t* __restrict__ offsets, uint8_t* __restrict__ state) {
     const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= R || !flag[j]) return;
-    const uint64_t nr = *nruns;
+    const LabelVote v = label_vote(ukeys, counts, *nruns, j);
     const uint32_t gidx = (uint32_t)(ukeys[j] >> 32), bps = 32u * W;
-    uint32_t total = 0, best_cnt = 0, best_sem = 0, best_ins = 0;
-    uint64_t k = j;
-    while (k < nr && (uint32_t)(ukeys[k] >> 32) == gidx) {
-        const unsigned long long top = ukeys[k] >> 16;           // (gidx, sem)
-        uint32_t sem_cnt = 0, ins_cnt = 0, ins = 0;
-        while (k < nr && (ukeys[k] >> 16) == top) {
-            const uint32_t c = counts[k];
-            sem_cnt += c;
-            if (c > ins_cnt) { ins_cnt = c; ins = (uint32_t)(ukeys[k] & 0xFFFFull); }   // ascending ins: ties keep the smallest
-            ++k;
-        }
-        total += sem_cnt;
-        if (sem_cnt > best_cnt) { best_cnt = sem_cnt; best_sem = (uint32_t)(top & 0xFFFFull); best_ins = ins; }
-    }
     const uint32_t f = gidx / bps, idx = gidx - f * bps, o = pos[j];
     o_idx[o] = idx;
-    o_sem[o] = (uint16_t)best_sem;
-    o_ins[o] = (uint16_t)best_ins;
-    o_ret[o] = total;
-    if (state && total >= min_returns) state[(uint64_t)f * V + idx] = 2;
+    o_sem[o] = (uint16_t)v.sem;
+    o_ins[o] = (uint16_t)v.ins;
+    o_ret[o] = v.total;
+    if (state && v.total >= min_returns) state[(uint64_t)f * V + idx] = 2;
     const uint32_t first = j == 0 ? 0u : (uint32_t)(ukeys[j - 1] >> 32) / bps + 1u;       // j - 1: the voxel before
     for (uint32_t s = first; s <= f; ++s) offsets[s] = o;
 }
@@ -283,95 +222,25 @@ __global__ __launch_bounds__(kBlock) void seq_counts_kernel(const uint64_t* __re
 struct lrc_voxseq {
     int device = 0;
     Grid g{};
-    uint64_t V = 0, W = 0, F = 0, G = 0;        // G = F * 32 * W global indices
+    uint64_t V = 0, W = 0, F = 0;
     uint32_t* d_bits = nullptr;                 // F * W words
     unsigned long long* d_lkeys = nullptr;      // key_cap slots each; [0, reserved) valid or all-ones
     unsigned long long* d_mkeys = nullptr;
     uint64_t key_cap = 0, reserved = 0;
     unsigned long long* d_acc = nullptr;        // kAccWords + F rejected counters
-    // finalize scratch, sized for fin_cap keys
-    uint64_t fin_cap = 0;
-    unsigned long long* d_sorted = nullptr;
-    unsigned long long* d_ukeys = nullptr;
-    uint32_t* d_counts = nullptr;
-    uint32_t* d_flag = nullptr;                 // fin_cap + 1
-    uint32_t* d_pos = nullptr;                  // fin_cap + 1
-    uint32_t* d_nruns = nullptr;
-    void* d_tmp = nullptr;
-    size_t tmp_bytes = 0;
+    KeyRuns runs;                               // finalize scratch; runs.G = F * 32 * W global indices
 };
 
 namespace {
 
-void release_fin(lrc_voxseq* v) {
-    void* ps[] = {v->d_sorted, v->d_ukeys, v->d_counts, v->d_flag, v->d_pos, v->d_nruns, v->d_tmp};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    v->d_sorted = v->d_ukeys = nullptr;
-    v->d_counts = v->d_flag = v->d_pos = v->d_nruns = nullptr;
-    v->d_tmp = nullptr;
-    v->fin_cap = 0;
-    v->tmp_bytes = 0;
-}
-
 void release(lrc_voxseq* v) {
-    release_fin(v);
+    v->runs.release();
     void* ps[] = {v->d_bits, v->d_lkeys, v->d_mkeys, v->d_acc};
     for (void* p : ps)
         if (p) (void)hipFree(p);
     v->d_bits = nullptr;
     v->d_lkeys = v->d_mkeys = nullptr;
     v->d_acc = nullptr;
-}
-
-uint32_t index_bits(uint64_t G) {                     // G < 2^b: every valid key's index field is below all ones
-    uint32_t b = 0;
-    while (b < 32 && (1ull << b) <= G) ++b;
-    return b;
-}
-
-int ensure_fin(lrc_voxseq* v, uint64_t R, hipStream_t st) {
-    if (R <= v->fin_cap) return LRC_OK;
-    LRC_HIP(hipStreamSynchronize(st));                  // the old scratch may still be read by enqueued work
-    release_fin(v);
-    const uint64_t cap = R;
-    LRC_HIP(hipMalloc((void**)&v->d_sorted, cap * 8));
-    LRC_HIP(hipMalloc((void**)&v->d_ukeys, cap * 8));
-    LRC_HIP(hipMalloc((void**)&v->d_counts, cap * 4));
-    LRC_HIP(hipMalloc((void**)&v->d_flag, (cap + 1) * 4));
-    LRC_HIP(hipMalloc((void**)&v->d_pos, (cap + 1) * 4));
-    LRC_HIP(hipMalloc((void**)&v->d_nruns, 4));
-    size_t a = 0, a2 = 0, b = 0, c = 0;
-    LRC_HIP(rocprim::radix_sort_keys(nullptr, a, (const unsigned long long*)v->d_lkeys, v->d_sorted, (size_t)cap, 0,
-                                   32 + index_bits(v->G), st));
-    LRC_HIP(rocprim::radix_sort_keys(nullptr, a2, (const unsigned long long*)v->d_mkeys, v->d_sorted, (size_t)cap, 0,
-                                   8 + index_bits(v->G), st));
-    LRC_HIP(rocprim::run_length_encode(nullptr, b, (const unsigned long long*)v->d_sorted, (unsigned int)cap, v->d_ukeys,
-                                     v->d_counts, v->d_nruns, st));
-    LRC_HIP(rocprim::exclusive_scan(nullptr, c, (const uint32_t*)v->d_flag, v->d_pos, 0u, (size_t)(cap + 1),
-                                  rocprim::plus<uint32_t>(), st));
-    v->tmp_bytes = a > a2 ? a : a2;
-    if (b > v->tmp_bytes) v->tmp_bytes = b;
-    if (c > v->tmp_bytes) v->tmp_bytes = c;
-    LRC_HIP(hipMalloc(&v->d_tmp, v->tmp_bytes ? v->tmp_bytes : 1));
-    v->fin_cap = cap;
-    return LRC_OK;
-}
-
-// sort one key column, encode its runs, flag the heads and scan them into d_pos
-int runs_of(lrc_voxseq* v, const unsigned long long* keys, uint64_t R, uint32_t shift, hipStream_t st) {
-    size_t tb = v->tmp_bytes;
-    LRC_HIP(rocprim::radix_sort_keys(v->d_tmp, tb, keys, v->d_sorted, (size_t)R, 0, shift + index_bits(v->G), st));
-    tb = v->tmp_bytes;
-    LRC_HIP(rocprim::run_length_encode(v->d_tmp, tb, (const unsigned long long*)v->d_sorted, (unsigned int)R, v->d_ukeys,
-                                     v->d_counts, v->d_nruns, st));
-    hipLaunchKernelGGL(seq_head_kernel, dim3((uint32_t)blocks_of(R + 1, kBlock)), dim3(kBlock), 0, st,
-                       (const unsigned long long*)v->d_ukeys, (const uint32_t*)v->d_nruns, R, shift, v->G, v->d_flag);
-    LRC_HIP(hipGetLastError());
-    tb = v->tmp_bytes;
-    LRC_HIP(rocprim::exclusive_scan(v->d_tmp, tb, (const uint32_t*)v->d_flag, v->d_pos, 0u, (size_t)(R + 1),
-                                  rocprim::plus<uint32_t>(), st));
-    return LRC_OK;
 }
 
 uint64_t sparse_bound(const lrc_voxseq* v) {
@@ -428,7 +297,7 @@ int lrc_voxseq_create(lrc_ctx* ctx, const double* origin3, double voxel_size, co
     v->V = V;
     v->W = W;
     v->F = num_frames;
-    v->G = num_frames * 32 * W;
+    v->runs.G = num_frames * 32 * W;                    // global indices
     auto run = [&]() -> int {
         LRC_HIP(hipSetDevice(v->device));
         LRC_HIP(hipMalloc((void**)&v->d_bits, v->F * v->W * 4));
@@ -494,28 +363,9 @@ int lrc_voxseq_accumulate_dev(lrc_voxseq* seq, const float* d_origins3, int orig
     const hipStream_t st = (hipStream_t)stream;
     LRC_HIP(hipSetDevice(seq->device));
     const uint64_t need = seq->reserved + total;
-    if (need > seq->key_cap) {                            // grow both columns: no return is ever dropped
-        uint64_t cap = seq->key_cap * 2;
-        if (cap < need) cap = need;
-        if (cap > kMaxKeys) cap = kMaxKeys;
-        unsigned long long* nk[2] = {nullptr, nullptr};
-        unsigned long long* old[2] = {seq->d_lkeys, seq->d_mkeys};
-        hipError_t e = hipMalloc((void**)&nk[0], cap * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&nk[1], cap * 8);
-        for (int c = 0; c < 2 && e == hipSuccess && seq->reserved; ++c)
-            e = hipMemcpyAsync(nk[c], old[c], seq->reserved * 8, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            for (int c = 0; c < 2; ++c)
-                if (nk[c]) (void)hipFree(nk[c]);
-            LRC_HIP(e);
-        }
-        for (int c = 0; c < 2; ++c)
-            if (old[c]) (void)hipFree(old[c]);
-        seq->d_lkeys = nk[0];
-        seq->d_mkeys = nk[1];
-        seq->key_cap = cap;
-    }
+    // both columns grow together: no return is ever dropped
+    const int rc = grow_key_columns(&seq->d_lkeys, &seq->d_mkeys, &seq->key_cap, seq->reserved, need, st);
+    if (rc != LRC_OK) return rc;
     LRC_HIP(hipMemsetAsync(seq->d_lkeys + seq->reserved, 0xFF, total * 8, st));   // unfilled slots sort last
     LRC_HIP(hipMemsetAsync(seq->d_mkeys + seq->reserved, 0xFF, total * 8, st));
     seq->reserved = need;
@@ -563,24 +413,25 @@ int lrc_voxseq_finalize_dev(lrc_voxseq* seq, uint32_t min_returns, const lrc_vox
         hipLaunchKernelGGL(seq_dense_kernel, dim3((uint32_t)blocks_of(seq->F * seq->V, kBlock)), dim3(kBlock), 0, st,
                            (const uint32_t*)seq->d_bits, V, W, seq->F * seq->V, d_out->state);
     if (R) {
-        int rc = ensure_fin(seq, R, st);
-        if (rc != LRC_OK) return rc;
-        rc = runs_of(seq, seq->d_lkeys, R, 32, st);
+        KeyRuns& r = seq->runs;
+        const KeyColumn lcol{seq->d_lkeys, 32}, mcol{seq->d_mkeys, 8};
+        int rc = r.ensure(R, {lcol, mcol}, st);
+        if (rc == LRC_OK) rc = r.runs_of(lcol, R, st);
         if (rc != LRC_OK) return rc;
         hipLaunchKernelGGL(seq_label_vote_kernel, dim3((uint32_t)blocks_of(R, kBlock)), dim3(kBlock), 0, st,
-                           (const unsigned long long*)seq->d_ukeys, (const uint32_t*)seq->d_counts,
-                           (const uint32_t*)seq->d_nruns, (const uint32_t*)seq->d_flag, (const uint32_t*)seq->d_pos, R,
+                           (const unsigned long long*)r.d_ukeys, (const uint32_t*)r.d_counts,
+                           (const uint32_t*)r.d_nruns, (const uint32_t*)r.d_flag, (const uint32_t*)r.d_pos, R,
                            min_returns, V, W, d_out->idx, d_out->sem, d_out->ins, d_out->returns, d_out->frame_offsets,
                            d_out->state);
         hipLaunchKernelGGL(seq_tail_kernel, dim3((uint32_t)blocks_of(seq->F + 1, kBlock)), dim3(kBlock), 0, st,
-                           (const unsigned long long*)seq->d_ukeys, (const uint32_t*)seq->d_nruns, (const uint32_t*)seq->d_pos,
-                           R, seq->G, W, F, d_out->frame_offsets);
+                           (const unsigned long long*)r.d_ukeys, (const uint32_t*)r.d_nruns, (const uint32_t*)r.d_pos,
+                           R, r.G, W, F, d_out->frame_offsets);
         LRC_HIP(hipGetLastError());
-        rc = runs_of(seq, seq->d_mkeys, R, 8, st);
+        rc = r.runs_of(mcol, R, st);
         if (rc != LRC_OK) return rc;
         hipLaunchKernelGGL(seq_mover_vote_kernel, dim3((uint32_t)blocks_of(R, kBlock)), dim3(kBlock), 0, st,
-                           (const unsigned long long*)seq->d_ukeys, (const uint32_t*)seq->d_counts,
-                           (const uint32_t*)seq->d_nruns, (const uint32_t*)seq->d_flag, (const uint32_t*)seq->d_pos, R,
+                           (const unsigned long long*)r.d_ukeys, (const uint32_t*)r.d_counts,
+                           (const uint32_t*)r.d_nruns, (const uint32_t*)r.d_flag, (const uint32_t*)r.d_pos, R,
                            d_out->mover, d_out->mover_returns);
     } else {
         LRC_HIP(hipMemsetAsync(d_out->frame_offsets, 0, (seq->F + 1) * 8, st));

@@ -1,11 +1,18 @@
-// lrc_voxwalk.h -- the voxel walk of one segment, host and device (include/lidarcast.h "dynamic occupancy", DESIGN.md
-// section 5u).  lrc_voxseq.hip's walk kernel and its host step lrc_voxseq_walk are compiled from these very functions.
+// lrc_voxwalk.h -- the voxel walk of one segment, host and device: the one definition of the grid, the walk and its limits for
+// the static grid (lrc_voxgrid.hip) and the frame slots (lrc_voxseq.hip, section 5u).  Both walk kernels
+// and the host step lrc_voxseq_walk are compiled from these very functions; tests/voxgrid_restate.py restates them in numpy.
 //
-// The walk is the one lrc_voxgrid defines: float64, no contraction, o and e widened exactly; a = voxel(o), b = voxel(e),
-// D = e - o; per axis with b_a != a_a: n_a = |b_a - a_a|, step_a = sign(b_a - a_a), tMax_a = ((g_a + (a_a + 1)*s) - o_a) / D_a
-// stepping up, ((g_a + a_a*s) - o_a) / D_a stepping down, tDelta_a = s / |D_a|; visit a, then while any n_a > 0 step the axis
-// with the smallest tMax among those with n_a > 0 (ties x, y, z).  Every visited in-grid voxel but b goes to the sink.
-// lrc_voxgrid.hip still carries its own copy of this arithmetic (DESIGN.md section 5u lists moving it here as a follow-up).
+//   Grid    origin g (3 float64), voxel size s (float64 > 0), dims (nx, ny, nz), nx*ny*nz <= 2^31 - 1.  The voxel of a
+//           float64 point x is i_a = floor((x_a - g_a) / s) (an f64 subtract, then an f64 divide, then floor); it is
+//           inside iff 0 <= i < n on every axis; linear index (i*ny + j)*nz + k (C order, z fastest).
+//   Walk    float64, no contraction, the float32 o and e widened exactly: a = voxel(o), b = voxel(e), D = e - o.  Per axis with
+//           b_a != a_a: n_a = |b_a - a_a|, step_a = sign(b_a - a_a), tMax_a = ((g_a + (a_a + 1)*s) - o_a) / D_a stepping
+//           up, ((g_a + a_a*s) - o_a) / D_a stepping down, tDelta_a = s / |D_a|; axes with n_a = 0 take no part.  Visit a;
+//           while any n_a > 0: take the axis with the smallest tMax among those with n_a > 0 (ties x, then y, then z),
+//           step it, tMax_a += tDelta_a, n_a -= 1, visit the new voxel.  The walk ends in b (Manhattan + 1 voxels).
+//           Every visited in-grid voxel except b goes to the sink (its FREE bit); a == b carves nothing.
+//   Limits  a segment whose o or e is not finite, whose voxel coordinates leave [-2^31, 2^31), or whose walk is 2^24 or
+//           more steps long is REJECTED: nothing goes to the sink and it has no end voxel.
 #ifndef LRC_VOXWALK_H
 #define LRC_VOXWALK_H
 
@@ -51,7 +58,8 @@ LRC_WALK_HD uint32_t linear(const Grid& g, int32_t c0, int32_t c1, int32_t c2) {
     return ((uint32_t)c0 * (uint32_t)g.ny + (uint32_t)c1) * (uint32_t)g.nz + (uint32_t)c2;
 }
 
-// Walk o -> e.  sink.add(idx) receives every visited in-grid voxel except b, in walk order.  The walk stops early once it
+// Walk o -> e.  sink.add(idx) receives every visited in-grid voxel except b, in walk order, then sink.flush() once (a walk
+// that is rejected or never enters the grid calls neither).  The walk stops early once it
 // has left the grid on an axis in that axis' direction of travel: no later voxel, b included, can be inside again.
 // Returns kWalkRejected (limits: nothing was added; b3 is b when only the length was refused, else untouched), kWalkEnd (b
 // is in the grid, end_idx its linear index) or kWalkNoEnd.  b3 receives b whenever the coordinates are in range.
@@ -89,6 +97,7 @@ LRC_WALK_HD int walk_segment(const Grid& g, float ox_, float oy_, float oz_, flo
         t2 = ((g.gz + ((double)a2 + (s2 > 0 ? 1.0 : 0.0)) * g.s) - oz) / D2;
         q2 = g.s / __builtin_fabs(D2);
     }
+    bool inside = true;
     while (n0 + n1 + n2 > 0) {
         if (in_grid(g, c0, c1, c2)) sink.add(linear(g, c0, c1, c2));
         bool out;
@@ -102,13 +111,39 @@ LRC_WALK_HD int walk_segment(const Grid& g, float ox_, float oy_, float oz_, flo
             c2 += s2; t2 = t2 + q2; --n2;
             out = gone(c2, s2, g.nz);
         }
-        if (out) return kWalkNoEnd;
+        if (out) {
+            inside = false;
+            break;
+        }
     }
-    // the walk ended in b
-    if (!in_grid(g, c0, c1, c2)) return kWalkNoEnd;
+    sink.flush();           // here, not in the caller: after the return the sink's state would be carried through every exit
+    // the walk ended in b (or left the grid for good: b is outside then)
+    if (!(inside && in_grid(g, c0, c1, c2))) return kWalkNoEnd;
     end_idx = linear(g, c0, c1, c2);
     return kWalkEnd;
 }
+
+// Free bits of one ray on the device: consecutive voxels in one bitset word (steps along z, the fastest axis) are gathered
+// into one mask; a word is written when the walk leaves it (and by flush() after the walk), with a plain load
+// first and an atomicOr only when a bit is still clear -- all rays of a pose start in the sensor's voxel, and after the first
+// wave those words are set.  (An L1-bypassing check load measured 2x slower: the plain load's stale answer costs at most an
+// idempotent atomic.)
+struct FreeSink {
+    uint32_t* __restrict__ bits;                     // first word of the grid's (the frame slot's) bitset
+    uint32_t w = 0xFFFFFFFFu, m = 0;
+    __device__ void flush() {
+        if (m && (bits[w] & m) != m) atomicOr(&bits[w], m);
+    }
+    __device__ void add(uint32_t idx) {
+        const uint32_t nw = idx >> 5;
+        if (nw != w) {
+            flush();
+            w = nw;
+            m = 0;
+        }
+        m |= 1u << (idx & 31u);
+    }
+};
 
 }  // namespace lrcwalk
 
